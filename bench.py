@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""bench.py -- MK-CKKS MulRelin/sec on MI355X (BASELINE.json metric) + NTT roofline + CPU baseline.
+"""bench.py -- MK-CKKS MulRelin/sec on MI355X (BASELINE.json metric); with --full also the secondary figures, NTT roofline and CPU baseline.
 
 A "step" is one mkckks.Evaluator.MulRelinNew on synthetic k-party ciphertexts:
 hoisting of both operands (Decompose), KeySwitcher.MulAndRelinHoisted and Rescale -- the timed
 region of the reference benchmark (mkckks/mkckks_benchmark_test.go:78-82), all inputs and keys
 resident in HBM when the clock starts.
 
-  python bench.py --gpus 1 --steps K --warmup W          (default workload = configs[1])
+  python bench.py --gpus 1 --steps K --warmup W          (default workload = configs[1]; the headline steps only)
+  python bench.py --gpus 1 --steps K --warmup W --full   (the same line plus every secondary leg)
+  python bench.py ... --dump-outputs DIR                 (the last timed step's ciphertext(s) as DIR/*.npy)
   python bench.py --gpus N ...                           (spawns N ranks itself: torch.distributed.run on 127.0.0.1)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the same, launched from outside)
 
@@ -26,6 +28,31 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 60 << 20    # --dump-outputs: the residue arrays stay under this; level / scale / sample index add a few bytes (64 MB in all)
+
+
+def dump_outputs(dirname, cts):
+    """--dump-outputs DIR: the ciphertexts the last timed step returned, as float64 .npy files.  A residue (up to 61 bits) does not fit a
+    float64 mantissa, so each ciphertext <name> is written as two exact halves, <name>_lo32.npy and <name>_hi32.npy (value = hi32 * 2^32 + lo32,
+    shape [components][limbs][coefficients]), with <name>_level.npy and <name>_scale.npy beside them.  Above DUMP_LIMIT_BYTES in all, every array
+    keeps the same fixed, seeded sample of coefficient positions, written as coeff_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    host = [(name, ct.download(), ct) for name, ct in cts]
+    total = sum(16 * a.size for _, a, _ in host)
+    idx = None
+    if total > DUMP_LIMIT_BYTES:
+        n = host[0][1].shape[-1]
+        idx = np.sort(np.random.default_rng(0).choice(n, max(1, n * DUMP_LIMIT_BYTES // total), replace=False))
+        np.save(os.path.join(dirname, "coeff_index.npy"), idx.astype(np.float64))
+    for name, a, ct in host:
+        if idx is not None:
+            a = a[..., idx]
+        np.save(os.path.join(dirname, name + "_lo32.npy"), (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        np.save(os.path.join(dirname, name + "_hi32.npy"), (a >> np.uint64(32)).astype(np.float64))
+        if hasattr(ct, "Level"):
+            np.save(os.path.join(dirname, name + "_level.npy"), np.array([ct.Level()], dtype=np.float64))
+        if hasattr(ct, "Scale"):
+            np.save(os.path.join(dirname, name + "_scale.npy"), np.array([ct.Scale], dtype=np.float64))
 
 
 
@@ -82,17 +109,22 @@ def run_bfv(args):
         check(lib().mkhe_set_overlap(params.ctx, 0))
     step = lambda: ev.MulRelinNew(ct0, ct1, rlk)
     # same order of legs as run_single: a cold-start figure first, then a long window, then the contract's W + K steps on settled clocks
+    # (a plain run, no --full: set-up, the 180 settling steps, W + K)
     extras = {}
-    for _ in range(args.warmup):
-        res = step()
-    params.sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        res = step()
-    params.sync()
-    extras["mulrelin_per_sec_cold_start"] = args.steps / (time.perf_counter() - t0)
-    extras["timing_protocol"] = ("legs in this order: cold start (W warm-up + K timed steps right after the host-side set-up: mulrelin_per_sec_cold_start, the figure "
-                                 "rounds 1-2 reported as value) -> secondary legs -> 60 untimed + 120 timed steps (steady state) -> W + K = the timed region of `value` -> K steps under HIP events (roofline)")
+    if args.full:
+        for _ in range(args.warmup):
+            res = step()
+        params.sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            res = step()
+        params.sync()
+        extras["mulrelin_per_sec_cold_start"] = args.steps / (time.perf_counter() - t0)
+        extras["timing_protocol"] = ("legs in this order: cold start (W warm-up + K timed steps right after the host-side set-up: mulrelin_per_sec_cold_start, the figure "
+                                     "rounds 1-2 reported as value) -> secondary legs -> 60 untimed + 120 timed steps (steady state) -> W + K = the timed region of `value` -> K steps under HIP events (roofline)")
+    else:
+        extras["timing_protocol"] = ("plain run: host-side set-up -> 180 untimed steps (clocks and the engine's per-shape kernel choice settle) -> W + K = the timed "
+                                     "region of `value`; the secondary legs, the roofline and the CPU baseline run with --full")
     if not getattr(args, "no_extras", False):
         un = lambda: ev.mulRelin(ct0, ct1, rlk)         # the non-hoisted twin (mkbfv/keyswitch.go:115-251) on its own device path
         for _ in range(2):
@@ -110,7 +142,8 @@ def run_bfv(args):
     for _ in range(120):
         step()
     params.sync()
-    extras["mulrelin_per_sec_steady_state"] = 120 / (time.perf_counter() - t0)
+    if args.full:
+        extras["mulrelin_per_sec_steady_state"] = 120 / (time.perf_counter() - t0)
     for _ in range(args.warmup):
         res = step()
     params.sync()
@@ -119,7 +152,9 @@ def run_bfv(args):
         res = step()
     params.sync()
     dt = time.perf_counter() - t0
-    roofline = roofline_leg(args, params, step, pset["logN"], "%s-bfv k=%d" % (args.params, k))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("ct", res)])
+    roofline = roofline_leg(args, params, step, pset["logN"], "%s-bfv k=%d" % (args.params, k)) if args.full else None
     cpu = None
     if not args.no_cpu:
         bfv = HB.make_bfv(pset)
@@ -249,10 +284,14 @@ def run_cnn(args):
         issue += time.perf_counter() - ti
     params.sync()
     dt = time.perf_counter() - t0
-    for _ in range(args.steps):                      # per-layer figures: a second, untimed-for-`value` pass with a sync per layer
-        inference(True)
-    roofline = roofline_leg(args, params, lambda: inference(False), p["logN"], "cnn PN14QP433 k=%d" % len(set(owners.values())))
-    if B > 1:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("ct%d" % i, c) for i, c in enumerate(out.cts)] if B > 1 else [("ct", out)])
+    roofline = None
+    if args.full:                                    # (a plain run: set-up, W warm-up inferences, K timed)
+        for _ in range(args.steps):                  # per-layer figures: a second, untimed-for-`value` pass with a sync per layer
+            inference(True)
+        roofline = roofline_leg(args, params, lambda: inference(False), p["logN"], "cnn PN14QP433 k=%d" % len(set(owners.values())))
+    if B > 1 and args.full:
         # every image of the batch against its own single-image inference (bit for bit); `out` becomes image 0's ciphertext for the oracle leg below
         bout = out
         same_b = []
@@ -260,7 +299,8 @@ def run_cnn(args):
             ref_k = single_inference(False, ev, images[k], (ev.HoistedForm(images[k]), hoisted[1], hoisted[2]), forks)
             same_b.append(bool(ref_k.Scale == bout.cts[k].Scale and (ref_k.download() == bout.cts[k].download()).all()))
         batch_check = dict(images=B, identical_to_single_image_inference=all(same_b))
-        out = bout.cts[0]
+    if B > 1:
+        out = out.cts[0]
     # ---- CPU baseline (cnn/cnn_bench_test.go:12-75 on the host): the SAME inference -- same circuit (mkhe_kklss_amd/cnn.py is duck-typed over its
     # evaluator), same keys (downloaded once), same input limbs -- on the oracle through tests/oracle_evaluator.py, one host thread, then with the
     # oracle's limb loops spread over the cores; its output ciphertext is compared with the device's bit for bit
@@ -509,22 +549,27 @@ def run_single(args):
 
     # ---- order of the legs (round 3).  After an idle phase (the host-side set-up above is one) this GPU takes about 150 ms of load to settle its
     # clocks (tools/ramp_probe.py: a 5-step window runs at 1.10 ms per step right after 0.2 s of idleness and at 0.92 ms 120 steps later), and
-    # W + K = 23 steps last 22 ms.  Rounds 1 and 2 timed `value` first, i.e. on the ramp; that figure is still measured first and reported as
+    # W + K = 23 steps last 22 ms.  Rounds 1 and 2 timed `value` first, i.e. on the ramp; that figure is still measured first (--full) and reported as
     # config.mulrelin_per_sec_cold_start.  The secondary legs then run BEFORE the timed region instead of after it, so that the contract's
     # W warm-up + K timed steps run on settled clocks like any step of a running service; nothing is skipped or shortened in the timed region.
+    # A plain run (no --full) keeps only what `value` needs: set-up, the 300 settling steps, W + K.
     extras = {}
-    for _ in range(args.warmup):
-        res = step()
-    params.sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        res = step()
-    params.sync()
-    extras["mulrelin_per_sec_cold_start"] = args.steps / (time.perf_counter() - t0)
-    extras["timing_protocol"] = ("legs in this order: cold start (W warm-up + K timed steps right after the host-side set-up: mulrelin_per_sec_cold_start, the figure "
-                                 "rounds 1-2 reported as value) -> secondary legs (Rotate / Conjugate / key generation) -> 100 untimed + 200 timed steps "
-                                 "(steady state) -> W + K = the timed region of `value` -> K steps under HIP events (roofline) -> mkhe_mul_relin_batch with B = 2, 4 (40 untimed + 100 timed calls each) -> two / three "
-                                 "evaluations in flight on forked contexts (100 untimed + 100 timed rounds each)")
+    if args.full:
+        for _ in range(args.warmup):
+            res = step()
+        params.sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            res = step()
+        params.sync()
+        extras["mulrelin_per_sec_cold_start"] = args.steps / (time.perf_counter() - t0)
+        extras["timing_protocol"] = ("legs in this order: cold start (W warm-up + K timed steps right after the host-side set-up: mulrelin_per_sec_cold_start, the figure "
+                                     "rounds 1-2 reported as value) -> secondary legs (Rotate / Conjugate / key generation) -> 100 untimed + 200 timed steps "
+                                     "(steady state) -> W + K = the timed region of `value` -> K steps under HIP events (roofline) -> mkhe_mul_relin_batch with B = 2, 4 (40 untimed + 100 timed calls each) -> two / three "
+                                     "evaluations in flight on forked contexts (100 untimed + 100 timed rounds each)")
+    else:
+        extras["timing_protocol"] = ("plain run: host-side set-up -> 300 untimed steps (clocks and the engine's per-shape kernel choice settle) -> W + K = the timed "
+                                     "region of `value`; the secondary legs, the roofline and the CPU baseline run with --full")
 
     # ---- secondary figure: hoisted rotation of the same k-party ciphertext, hoisting included / excluded
     if not args.no_extras:
@@ -579,7 +624,8 @@ def run_single(args):
             params.sync()
             extras[name] = args.steps / (time.perf_counter() - t0)
 
-    # ---- the same single-stream MulRelin over a long window (200 steps after 100 untimed ones), then the contract's timed region
+    # ---- the same single-stream MulRelin over a long window (200 steps after 100 untimed ones), then the contract's timed region.  In a plain run
+    # these 300 steps are the warm-up that settles the clocks and the kernel choice; only --full reports their rate.
     for _ in range(100):
         step()
     params.sync()
@@ -587,7 +633,8 @@ def run_single(args):
     for _ in range(200):
         res_s = step()
     params.sync()
-    extras["mulrelin_per_sec_steady_state"] = 200 / (time.perf_counter() - t0)
+    if args.full:
+        extras["mulrelin_per_sec_steady_state"] = 200 / (time.perf_counter() - t0)
     del res_s
 
     for _ in range(args.warmup):
@@ -600,9 +647,10 @@ def run_single(args):
     dt = time.perf_counter() - t0
     ms_per_step = dt * 1e3 / args.steps
     value = B * args.steps / dt
-    if B > 1:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("ct%d" % i, c) for i, c in enumerate(res.cts)] if B > 1 else [("ct", res)])
+    if B > 1 and args.full:
         same_b = [bool((res.cts[i].download() == ev.MulRelinNew(b0.cts[i], b1.cts[i], rlk).download()).all()) for i in range(B)]
-        extras["batch"] = B
         extras["batch_check"] = dict(inputs=B, identical_to_single_mulrelin=all(same_b))
         extras["mulrelin_per_sec_single_input_same_run"] = None
         for _ in range(20):
@@ -613,6 +661,8 @@ def run_single(args):
             single_step()
         params.sync()
         extras["mulrelin_per_sec_single_input_same_run"] = 100 / (time.perf_counter() - t1)
+    if B > 1:
+        extras["batch"] = B
         res = res.cts[0]
 
     beta = params.Beta(level)
@@ -628,7 +678,7 @@ def run_single(args):
                 _lib().mkhe_ntt_choice(params.ctx, n * per_comp, 1)] for n in (2 * k, k)})
     roofline = roofline_leg(args, params, step, pset["logN"], "%s k=%d" % (args.params, k),
                             extra=dict(decompose=dict(limbs_per_component=beta * (level + 1 + len(pset["P"])), source_limbs_per_component=level + 1))
-                            if params.Alpha() == 1 else None)
+                            if params.Alpha() == 1 else None) if args.full else None
     if args.params == "PN15QP880" and not args.no_extras and roofline is not None:
         params.sync()
         vb = valu_bound_leg()
@@ -813,11 +863,25 @@ def main():
     ap.add_argument("--scheme", default="ckks", choices=["ckks", "bfv", "cnn"],
                     help="ckks = BASELINE.json headline metric (default); bfv = the mkbfv MulRelin line; cnn = one encrypted "
                          "CNN inference per step (cnn/cnn.go on PN14QP433; --parties 2 or 4) -- both single GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="single GPU: also run every secondary leg -- cold-start and steady-state figures, Rotate / Conjugate / key generation, the "
+                         "per-kernel HIP-event roofline and vector-ALU bound, batch and in-flight throughput, the CPU-oracle baseline with its bit-exact "
+                         "check (--no-cpu / --no-extras still drop theirs).  Without it a run sets up, warms up, times K steps and prints the line.  "
+                         "N > 1 runs always run their legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single GPU: after the timed steps, write the ciphertext(s) the last timed step returned to DIR/*.npy (float64; see dump_outputs)")
     args = ap.parse_args()
     # multi-process GPU work on this pool needs dmabuf IPC (RCCL fails with hipIpcGetMemHandle otherwise); the image exports it, a
     # stripped environment may not -- set before anything initialises the HIP runtime, inherited by the ranks we launch
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    multi = args.gpus > 1 or world > 1 or args.force_dist
+    if multi and args.dump_outputs:
+        ap.error("--dump-outputs is for single-GPU runs")
+    if multi:
+        args.full = True            # the N > 1 lines (bench_dist.py) validate themselves with their legs in every run
+    elif not args.full:
+        args.no_cpu = args.no_extras = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- N rank processes, one per GPU, started BEFORE anything in this
         # process has touched the GPU; rank 0 of the children prints the JSON line on the inherited stdout
@@ -849,7 +913,7 @@ def main():
         sys.stdout.flush()
         json_fd = os.dup(1)
         os.dup2(2, 1)
-    if args.gpus > 1 or world > 1 or args.force_dist:
+    if multi:
         import bench_dist
         out = (bench_dist.run_distributed_bfv if args.scheme == "bfv" else bench_dist.run_replicas_cnn if args.scheme == "cnn"
                else bench_dist.run_distributed)(args)

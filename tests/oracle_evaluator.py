@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE: the mkckks.Evaluator surface that cnn/cnn.go uses, on HOST ciphertexts with the CPU oracle doing all polynomial work.
 
 `mkhe_kklss_amd.cnn.Convolution / FC1Layer / FC2Layer / Inference` are duck-typed over their evaluator, so the same circuit runs on this class:
-that is the CPU baseline of the cnn bench line (bench.py --scheme cnn: one inference on one host thread, then limb-parallel) and the
+that is the CPU baseline of the cnn bench line (bench.py --scheme cnn --full: one inference on one host thread, then limb-parallel) and the
 bit-for-bit check of the device inference against the oracle.  Only tests/ and bench.py's cpu_baseline leg import this file.
 
 Restates the host-side logic of mkckks/evaluator.go (scale matching :270-292, nbRescales :376-384, power-of-two rotations :516-523) like

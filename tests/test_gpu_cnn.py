@@ -112,7 +112,7 @@ def test_capture_refused_on_old_runtime_or_works():
 
 def test_encrypted_cnn_matches_the_oracle_evaluator():
     """the whole inference, device against the CPU oracle running the same circuit on the same ciphertexts and keys (tests/oracle_evaluator.py:
-    the cpu_baseline leg of bench.py --scheme cnn): every output limb bit for bit, same level, same scale"""
+    the cpu_baseline leg of bench.py --scheme cnn --full): every output limb bit for bit, same level, same scale"""
     import oracle_evaluator as OE
     from oracle import oracle as O
     from mkhe_kklss_amd import cnn

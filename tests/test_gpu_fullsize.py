@@ -1,6 +1,6 @@
 """Full-size parity (-m gpu): BASELINE.json configs[3] shape on one GPU -- PN16QP1761 (N = 2^16, 34 + 4 primes,
 alpha = 2, beta = 17; mkrlwe_test.go:22-35), 2-party MulAndRelin and hoisted Rotate, device vs oracle bit for bit.
-(configs[1] / configs[2] at full size are checked by bench.py's cpu_baseline leg on every run.)
+(configs[1] / configs[2] at full size are checked by the cpu_baseline leg of every bench.py --full run.)
 """
 import numpy as np
 import pytest

@@ -12,7 +12,7 @@ for v in "$@"; do
   lib=$R/mkhe-kklss_amd/build/var_$name/lib.so
   [ "$name" = shipped ] && lib=$R/mkhe-kklss_amd/lib/libmkhe_hip.so
   [ "$name" = switches ] && lib=$R/mkhe-kklss_amd/lib/libmkhe_hip_switches.so
-  ( for e in ${envs//,/ }; do export "$e"; done; MKHE_LIB=$lib timeout -k 10 300 python3 bench.py --no-cpu --no-extras ${BENCH_ARGS} > $O/r$i.json 2> $O/r$i.err )
+  ( for e in ${envs//,/ }; do export "$e"; done; MKHE_LIB=$lib timeout -k 10 300 python3 bench.py --full --no-cpu --no-extras ${BENCH_ARGS} > $O/r$i.json 2> $O/r$i.err )
   python3 - $O/r$i.json "$v" <<'PY'
 import json, sys
 try:

@@ -9,7 +9,7 @@ export MKHE_LIB=$R/mkhe-kklss_amd/lib/libmkhe_hip_switches.so
 i=0
 for v in "$@"; do
   i=$((i+1))
-  env $NAME=$v python3 bench.py --no-cpu --no-extras ${BENCH_ARGS} > $O/r$i.json 2> $O/r$i.err
+  env $NAME=$v python3 bench.py --full --no-cpu --no-extras ${BENCH_ARGS} > $O/r$i.json 2> $O/r$i.err
   python3 - $O/r$i.json "$NAME=$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); k = d["roofline"]["kernels"]

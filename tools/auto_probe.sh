@@ -1,16 +1,17 @@
 #!/bin/bash
 # the measured kernel choice (MKHE_NTT32=2, default) beside both forced settings: one gpurun call
-mkdir -p gpurun_out/auto
+O=${1:-runs/auto}       # bash tools/auto_probe.sh [output directory, default runs/auto]
+mkdir -p "$O"
 for v in auto:MKHE_UNUSED=1 h32:MKHE_NTT32=1 h16:MKHE_NTT32=0 auto2:MKHE_UNUSED=1; do
   name=${v%%:*}; e=${v#*:}
-  env $e python3 bench.py --no-cpu > gpurun_out/auto/$name.json 2> gpurun_out/auto/$name.err
+  env $e python3 bench.py --full --no-cpu > $O/$name.json 2> $O/$name.err
 done
-env python3 bench.py --scheme bfv --no-cpu > gpurun_out/auto/bfv_auto.json 2> gpurun_out/auto/bfv_auto.err
-MKHE_NTT32=0 python3 bench.py --scheme bfv --no-cpu > gpurun_out/auto/bfv_h16.json 2> gpurun_out/auto/bfv_h16.err
-MKHE_NTT32=1 python3 bench.py --scheme bfv --no-cpu > gpurun_out/auto/bfv_h32.json 2> gpurun_out/auto/bfv_h32.err
-python3 - <<'PY'
-import json, glob
-for f in sorted(glob.glob("gpurun_out/auto/*.json")):
+env python3 bench.py --full --scheme bfv --no-cpu > $O/bfv_auto.json 2> $O/bfv_auto.err
+MKHE_NTT32=0 python3 bench.py --full --scheme bfv --no-cpu > $O/bfv_h16.json 2> $O/bfv_h16.err
+MKHE_NTT32=1 python3 bench.py --full --scheme bfv --no-cpu > $O/bfv_h32.json 2> $O/bfv_h32.err
+python3 - "$O" <<'PY'
+import json, glob, sys
+for f in sorted(glob.glob(sys.argv[1] + "/*.json")):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

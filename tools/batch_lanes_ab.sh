@@ -12,9 +12,9 @@ print('   %-34s %8.1f MulRelin/s   (one input at a time, same run: %s)' % ('$2',
 for k in ${PARTIES:-4 2 1}; do
   for B in ${BATCHES:-2 3 4 6}; do
     echo "== parties $k  B = $B"
-    python3 $R/bench.py --parties $k --batch $B --no-cpu --no-extras --steps 40 --warmup 5 > /tmp/bl_a.json 2>/tmp/bl.err || { tail -3 /tmp/bl.err; exit 1; }
+    python3 $R/bench.py --full --parties $k --batch $B --no-cpu --no-extras --steps 40 --warmup 5 > /tmp/bl_a.json 2>/tmp/bl.err || { tail -3 /tmp/bl.err; exit 1; }
     one /tmp/bl_a.json "in flight (product library)"
-    MKHE_LIB=$V python3 $R/bench.py --parties $k --batch $B --no-cpu --no-extras --steps 40 --warmup 5 > /tmp/bl_b.json 2>/tmp/bl.err || { tail -3 /tmp/bl.err; exit 1; }
+    MKHE_LIB=$V python3 $R/bench.py --full --parties $k --batch $B --no-cpu --no-extras --steps 40 --warmup 5 > /tmp/bl_b.json 2>/tmp/bl.err || { tail -3 /tmp/bl.err; exit 1; }
     one /tmp/bl_b.json "lock step (-DMKHE_BATCH_LANES=0)"
   done
 done

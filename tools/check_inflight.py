@@ -4,10 +4,11 @@ program order with the in-order completion model of vmcnt and reports any instru
 load that may still be in flight (a register spill placed by the allocator between an asm load and its wait reads garbage -- the compiler
 does not know that the asm statement is a load).  Straight-line model: branches are ignored, every label resets nothing.
   python tools/check_inflight.py [extra hipcc flags]     -> exit code 1 if anything is flagged"""
-import os, re, subprocess, sys
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "mkhe-kklss_amd", "csrc", os.environ.get("CHECK_SRC", "ntt16_kernels.hip"))
-asm = "/tmp/check_inflight.s"
+_tmp = tempfile.TemporaryDirectory(prefix="mkhe_asm_")       # private per run: no clash between users or parallel runs
+asm = os.path.join(_tmp.name, "check_inflight.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-S",
                        "--cuda-device-only", src, "-o", asm] + sys.argv[1:], stderr=subprocess.DEVNULL)
 def regs(tok):

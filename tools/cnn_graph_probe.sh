@@ -1,17 +1,18 @@
 #!/bin/bash
 # batched cnn inference replayed from a HIP graph beside eager issue, and the per-class breakdown of the PN14QP439 batched MulRelin (one gpurun call)
-mkdir -p gpurun_out/probe
+O=${1:-runs/probe}       # bash tools/cnn_graph_probe.sh [output directory, default runs/probe]
+mkdir -p "$O"
 for b in 8 16; do
   for g in 0 1; do
-    timeout -k 10 300 python bench.py --scheme cnn --parties 4 --batch $b --graph $g --steps 20 --warmup 3 --no-cpu > gpurun_out/probe/cnn4_b${b}_g${g}.json 2> gpurun_out/probe/cnn4_b${b}_g${g}.err || echo "cnn b=$b g=$g failed"
+    timeout -k 10 300 python bench.py --full --scheme cnn --parties 4 --batch $b --graph $g --steps 20 --warmup 3 --no-cpu > $O/cnn4_b${b}_g${g}.json 2> $O/cnn4_b${b}_g${g}.err || echo "cnn b=$b g=$g failed"
   done
 done
 for b in 1 4 8; do
-  timeout -k 10 300 python bench.py --params PN14QP439 --parties 4 --batch $b --steps 50 --warmup 5 --no-cpu --no-extras > gpurun_out/probe/pn14_b${b}.json 2> gpurun_out/probe/pn14_b${b}.err || echo "pn14 b=$b failed"
+  timeout -k 10 300 python bench.py --full --params PN14QP439 --parties 4 --batch $b --steps 50 --warmup 5 --no-cpu --no-extras > $O/pn14_b${b}.json 2> $O/pn14_b${b}.err || echo "pn14 b=$b failed"
 done
-python - <<'PY'
-import json, glob
-for f in sorted(glob.glob("gpurun_out/probe/*.json")):
+python - "$O" <<'PY'
+import json, glob, sys
+for f in sorted(glob.glob(sys.argv[1] + "/*.json")):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

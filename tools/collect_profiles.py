@@ -50,7 +50,7 @@ for d in ("sq_a", "sq_b", "sq_d"):
         if m:
             agg[m.group(1) + (m.group(2) or "").replace(" ", "")][r["Counter_Name"]].append(float(r["Counter_Value"]))
 with open(os.path.join(P, "%s_sq_counters.txt" % tag), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --pmc (3 passes) over `MKHE_NO_OVERLAP=1 python3 bench.py --steps 4 --warmup 2 --no-cpu --no-extras`\n")
+    f.write("# rocprofv3 --kernel-trace --pmc (3 passes) over `MKHE_NO_OVERLAP=1 python3 bench.py --full --steps 4 --warmup 2 --no-cpu --no-extras`\n")
     f.write("# mean per dispatch over all dispatches of the kernel; SQ_*CYCLES / SQ_WAIT_* / SQ_ACTIVE_* are quad-cycles summed over waves\n")
     for k in sorted(agg):
         c = {n: sum(v) / len(v) for n, v in agg[k].items()}

@@ -20,20 +20,20 @@ for k in ${PARTIES:-1 2 3 4}; do
     for rep in 1 2; do
         for plan in 1 0; do
             echo "== parties $k  MKHE_F2_FUSED=$((2 - plan))"
-            MKHE_F2_FUSED=$((2 - plan)) python3 $R/bench.py --parties $k --no-cpu --steps 40 --warmup 5 > /tmp/ab_${k}_${plan}.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
+            MKHE_F2_FUSED=$((2 - plan)) python3 $R/bench.py --full --parties $k --no-cpu --steps 40 --warmup 5 > /tmp/ab_${k}_${plan}.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
             line /tmp/ab_${k}_${plan}.json
         done
     done
 done
 echo "== mkbfv 2 parties"
 for plan in 1 0 1 0; do
-    MKHE_F2_FUSED=$((2 - plan)) python3 $R/bench.py --scheme bfv --parties 2 --no-cpu --no-extras --steps 30 --warmup 5 > /tmp/ab_bfv.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
+    MKHE_F2_FUSED=$((2 - plan)) python3 $R/bench.py --full --scheme bfv --parties 2 --no-cpu --no-extras --steps 30 --warmup 5 > /tmp/ab_bfv.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
     echo "   MKHE_F2_FUSED=$((2 - plan))"; line /tmp/ab_bfv.json
 done
 echo "== cnn 4 parties / 2 parties"
 for plan in 1 0 1 0; do
     for k in 4 2; do
-        MKHE_F2_FUSED=$((2 - plan)) python3 $R/bench.py --scheme cnn --parties $k --no-cpu --no-extras --steps 20 --warmup 3 > /tmp/ab_cnn.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
+        MKHE_F2_FUSED=$((2 - plan)) python3 $R/bench.py --full --scheme cnn --parties $k --no-cpu --no-extras --steps 20 --warmup 3 > /tmp/ab_cnn.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }
         python3 -c "
 import json,sys
 d=json.loads([l for l in open('/tmp/ab_cnn.json') if l.startswith('{')][-1]); print('   MKHE_F2_FUSED=$((2 - plan)) parties $k: %.1f %s (%.3f ms)' % (d['value'], d['unit'], d['ms_per_step']))"

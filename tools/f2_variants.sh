@@ -12,7 +12,7 @@ run() {
     cp $B/*.o $B/var_$name/
     /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -DMKHE_ABLATION -I$C $* -c $C/ntt16_f2_kernels.hip -o $B/var_$name/ntt16_f2_kernels.o 2>/dev/null || { echo "$name: build failed"; return; }
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/var_$name/lib.so $B/var_$name/*.o || { echo "$name: link failed"; return; }
-    MKHE_LIB=$B/var_$name/lib.so timeout -k 10 300 python3 $R/bench.py --no-cpu --no-extras > $B/var_$name/b.json 2>/dev/null
+    MKHE_LIB=$B/var_$name/lib.so timeout -k 10 300 python3 $R/bench.py --full --no-cpu --no-extras > $B/var_$name/b.json 2>/dev/null
     python3 - $B/var_$name/b.json "$name" "$*" <<'PY'
 import json, sys
 try:

@@ -1,5 +1,5 @@
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import oracle as O
 from mkhe_kklss_amd import mkrlwe
 Q = [0xfffffffff6a0001, 0x3fffffffd60001, 0x3fffffffca0001]

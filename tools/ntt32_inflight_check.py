@@ -3,10 +3,11 @@
 the current one and are in flight across the loop's back edge, invisible to the compiler -- so between a request and the counted wait that
 covers it (s_waitcnt vmcnt(61 - 4 g) in stage 0) NO instruction may read or write the destination registers (a register-allocator copy or spill
 there would move a value that has not landed).  Walks the gfx950 ISA of both kernels (hipcc -S, no GPU needed); exit code 1 on a violation."""
-import os, re, subprocess, sys
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "mkhe-kklss_amd", "csrc", "ntt32_kernels.hip")
-asm = "/tmp/ntt32_inflight.s"
+_tmp = tempfile.TemporaryDirectory(prefix="mkhe_asm_")       # private per run: no clash between users or parallel runs
+asm = os.path.join(_tmp.name, "ntt32_inflight.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-S", "--cuda-device-only"] +
                       sys.argv[1:] + [src, "-o", asm], stderr=subprocess.DEVNULL)
 txt = open(asm).read()

@@ -7,5 +7,5 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
 U=time; [ "$M" = stochastic ] && U=cycles
-timeout -k 10 240 rocprofv3 --output-format csv --kernel-trace --pc-sampling-beta-enabled 1 --pc-sampling-unit $U --pc-sampling-method $M --pc-sampling-interval $I -d $O -o p -- python3 bench.py --steps 40 --warmup 5 --no-cpu --no-extras > $O/bench.json 2> $O/err.txt
+timeout -k 10 240 rocprofv3 --output-format csv --kernel-trace --pc-sampling-beta-enabled 1 --pc-sampling-unit $U --pc-sampling-method $M --pc-sampling-interval $I -d $O -o p -- python3 bench.py --full --steps 40 --warmup 5 --no-cpu --no-extras > $O/bench.json 2> $O/err.txt
 echo "rc=$?"; tail -3 $O/err.txt; ls -la $O $O/* | head -30

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $R
 export MKHE_NO_OVERLAP=1
 P="rocprofv3 --output-format csv --kernel-trace"
-B="python3 bench.py --params PN16QP1761 --parties 8 --steps 2 --warmup 1 --no-cpu --no-extras"
+B="python3 bench.py --full --params PN16QP1761 --parties 8 --steps 2 --warmup 1 --no-cpu --no-extras"
 for mode in 1 0; do
     export MKHE_SPREAD_RADIX4=$mode
     $P --pmc FETCH_SIZE -d $O/fetch_$mode -o p -- $B > $O/bench_fetch_$mode.json 2> $O/bench_fetch_$mode.err

@@ -5,7 +5,7 @@ O=$R/gpurun_out/$1; shift
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
-rocprofv3 --output-format csv --kernel-trace -d $O/tr -o p -- python3 bench.py "$@" --no-cpu > $O/bench.json 2> $O/bench.err
+rocprofv3 --output-format csv --kernel-trace -d $O/tr -o p -- python3 bench.py --full "$@" --no-cpu > $O/bench.json 2> $O/bench.err
 python3 - $O <<'PY' > $O/by_grid.txt
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/tr/**/p_kernel_trace.csv", recursive=True)[0]

@@ -8,7 +8,7 @@ cd $R
 for v in "$@"; do
   name=${v%%:*}; envs=${v#*:}; [ "$envs" = "$v" ] && envs=""
   ( for e in ${envs//,/ }; do export "$e"; done
-    MKHE_NO_OVERLAP=1 rocprofv3 --output-format csv --kernel-trace -d $O/$name -o p -- python3 bench.py --steps 20 --warmup 3 --no-cpu --no-extras > $O/$name.json 2> $O/$name.err )
+    MKHE_NO_OVERLAP=1 rocprofv3 --output-format csv --kernel-trace -d $O/$name -o p -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu --no-extras > $O/$name.json 2> $O/$name.err )
   python3 - $O/$name/p_kernel_trace.csv $name <<'PY'
 import csv, sys, statistics as st
 allrows = list(csv.DictReader(open(sys.argv[1])))

@@ -77,7 +77,7 @@ def main():
     for fn in sorted(glob.glob(os.path.join(d, "*.hip")) + glob.glob(os.path.join(d, "*.h"))):      # same digest as bench.py csrc_digest()
         h.update(os.path.basename(fn).encode()); h.update(open(fn, "rb").read())
     json.dump(dict(workload=workload, csrc_sha256=h.hexdigest(), formula="(2*FETCH_SIZE + WRITE_SIZE) * 1024 bytes per launch",
-                   command="MKHE_NO_OVERLAP=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py --steps %s --warmup %s --no-cpu --no-extras" % (steps, warmup),
+                   command="MKHE_NO_OVERLAP=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py --full --steps %s --warmup %s --no-cpu --no-extras" % (steps, warmup),
                    steps=steps, warmup=warmup, kernels=kernels), sys.stdout, indent=1)
 
 

@@ -145,7 +145,7 @@ generated (`tools/write_profiles_readme.py {tag}`: a figure that is missing from
 Earlier rounds: `README_r5.md` (its narrative of rounds 1–5 stands, except where this file says otherwise) and the `r1a_ … r5_` files.  Boxes differ by ± 3 %
 (parts that throttle at 1255 W by more): compare only inside one file or one call.
 
-## The bench line (`{tag}_bench_plain.json` = one plain `python bench.py`)
+## The bench line (`{tag}_bench_plain.json` = one `python bench.py --full`)
 
 **{pl["value"]:.1f} MulRelin/s** ({pl["ms_per_step"]:.4f} ms per step; right after the host-side set-up: {C["mulrelin_per_sec_cold_start"]:.1f}), workload `{C["workload"]}`, bit-exact against the oracle in the same run
 (`cpu_baseline.bit_exact_vs_gpu = {cb["bit_exact_vs_gpu"]}`; CPU oracle {cb["value"]:.3f} MulRelin/s on one thread, {cb["value_limb_parallel"]:.2f} on {cb["cores_limb_parallel"]}).
@@ -156,13 +156,13 @@ through `mkhe_mul_relin_batch` (in flight on internal contexts at this launch si
 
 `roofline`: dominant kernel `{R["kernel"].split("  ")[0]}` — {R["alg_bytes_per_launch"] / 1e6:.1f} MB algorithmic (16·N bytes × {R["alg_bytes_per_launch"] / (16 * 32768):.0f} limbs) in {R["avg_launch_us"]:.1f} µs = {R["achieved"]:.0f} GB/s,
 **frac {R["frac"]:.3f}** inside the step; **back to back** (`frac_back_to_back`, the `valu_bound` leg's shipped timings of the same launch shape): {", ".join("`%s` %.3f" % (k.split("<")[0], v) for k, v in b2b.items())};
-`traffic` {R["traffic"] / 1e6:.0f} MB per launch by the PMC counters (`traffic.json`: (2·FETCH_SIZE + WRITE_SIZE)·1024, separate `--pmc` passes of `bench.py --steps 6 --warmup 2 --no-cpu --no-extras`) = {R["traffic"] / (R["avg_launch_us"] * 1e-6) / 1e9 / 8000:.3f} of the peak;
+`traffic` {R["traffic"] / 1e6:.0f} MB per launch by the PMC counters (`traffic.json`: (2·FETCH_SIZE + WRITE_SIZE)·1024, separate `--pmc` passes of `bench.py --full --steps 6 --warmup 2 --no-cpu --no-extras`) = {R["traffic"] / (R["avg_launch_us"] * 1e-6) / 1e9 / 8000:.3f} of the peak;
 compulsory bytes (every source limb once, every digit limb once) {R["compulsory_bytes_per_launch"] / 1e6:.0f} MB = {R["frac_compulsory"]:.3f}.
 `valu_bound` (the kernel with loads, stores and LDS exchanges compiled out, 300 launches back to back): """ + "; ".join(
     "`%s` shipped %.0f µs, butterflies only %.0f µs (%.2f of it; %.2f of the roofline if the memory side were free)" % (k.split("<")[0], v["shipped_us"]["1792_limbs"], v["butterflies_only_us"]["1792_limbs"],
                                                                                                             v["butterflies_share"]["1792_limbs"], v["frac_if_alu_only"]["1792_limbs"])
     for k, v in vb.items() if isinstance(v, dict) and "shipped_us" in v) + f""".
-rocprofv3 cross-check (`{tag}_kernel_stats_noovl.csv`, `--kernel-trace --stats` of `MKHE_NO_OVERLAP=1 bench.py --steps 20 --warmup 3 --no-cpu --no-extras`): `{DOM.split("<")[0]}` {dcalls} calls, average {davg:.1f} µs
+rocprofv3 cross-check (`{tag}_kernel_stats_noovl.csv`, `--kernel-trace --stats` of `MKHE_NO_OVERLAP=1 bench.py --full --steps 20 --warmup 3 --no-cpu --no-extras`): `{DOM.split("<")[0]}` {dcalls} calls, average {davg:.1f} µs
 (min {dmn:.1f}, max {dmx:.1f}); `ntt16_f2_kernel` {f2calls} calls, average {f2avg:.1f} µs; `ext_inner_xy_kernel<4,4,true>` {xycalls} calls, average {xyavg:.1f} µs.
 The two forms of the dominant kernel forced: `MKHE_NTT32=1` {plh["value"]:.1f} MulRelin/s (frac {plh["roofline"]["frac"]:.3f}), `MKHE_NTT32=0` {pl16["value"]:.1f} (frac {pl16["roofline"]["frac"]:.3f}); this run's own choice: `{C.get("ntt_kernel_choice")}`.
 
@@ -179,7 +179,7 @@ The latency-bound tail (inverse NTTs, ModDowns, tensor, small forward NTTs): {ta
 
 ## Step F2 inside the Decompose NTT of the t_i (`ntt16_f2_kernel`, DESIGN.md §4.6)
 
-Same call, same box, alternating (`{tag}_f2_fused_ab.txt`; diagnostic library, `MKHE_F2_FUSED` = 1 / 0; `bench.py --no-cpu --no-extras`):
+Same call, same box, alternating (`{tag}_f2_fused_ab.txt`; diagnostic library, `MKHE_F2_FUSED` = 1 / 0; `bench.py --full --no-cpu --no-extras`):
 
 | | MulRelin/s (three runs) | cold start | Decompose NTT µs / step | streaming inner products µs / step | `ntt16_f2_kernel` | inverse NTT µs / step |
 |---|---|---|---|---|---|---|
