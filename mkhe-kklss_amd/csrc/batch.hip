@@ -12,7 +12,7 @@
 // biases) is passed B times.  Results are the integers of the single-operation entry points, bit for bit (tests/test_gpu_batch.py): the
 // batch path takes no shortcut that changes a representative.  The fusions of the single-operation path carry over per input: the tensor term
 // rides on the first product of every output slot, the Rescale on the merged ModDown's store (Context::rs_maps_), the diagonal of engine-hoisted
-// digits is the tensor input, and x_b comes out of input b's step F1 (up to four parties per operand: Context::ext_xmap_).
+// digits is the tensor input, and x_b comes out of input b's step F1 (up to four parties per operand: ExtFuse::xmap).
 //
 // Replaces, B at a time: KeySwitcher.MulAndRelin[Hoisted] (mkrlwe/keyswitch_hoisted.go:44-179) + Rescale (mkckks/evaluator.go:558-581),
 // RotateHoisted / Rotate (:183-247, keyswitch.go:234-298), Evaluator.HoistedForm (mkckks/evaluator.go:543-553), AddNew / SubNew (:316-356).
@@ -107,9 +107,9 @@ void Context::rotate_batch(u64 galEl, const std::vector<const Ct*>& ins, const s
                 if (a == 0) items.back().addend = ins[b]->d;
                 items.push_back(ExtItem{h[b * n + a], crs.d, outs[b]->d + (size_t)(1 + a) * PO, false});
             }
-        if (stage) ext_staged_.assign(h.begin() + b0 * n, h.begin() + std::min(B, b0 + per) * n);
-        try { ext_batch(level, items, -1, 0, galEl); } catch (...) { ext_staged_.clear(); staged_open_.clear(); throw; }
-        ext_staged_.clear();
+        ExtFuse fuse;
+        if (stage) fuse.staged.assign(h.begin() + b0 * n, h.begin() + std::min(B, b0 + per) * n);
+        ext_batch(level, items, -1, 0, galEl, fuse);
     }
     MKHE_HIP(hipGetLastError());
 }
@@ -186,9 +186,9 @@ void Context::rotate_multi(const std::vector<u64>& galEl, const std::vector<cons
                 if (PP) items.back().post = post_add[b]->d + (size_t)(1 + a) * PP;
             }
         }
-        if (stage) ext_staged_.assign(h.begin() + b0 * n, h.begin() + std::min(B, b0 + per) * n);
-        try { ext_batch(level, items, -1, 0, 0); } catch (...) { ext_staged_.clear(); staged_open_.clear(); throw; }
-        ext_staged_.clear();
+        ExtFuse fuse;
+        if (stage) fuse.staged.assign(h.begin() + b0 * n, h.begin() + std::min(B, b0 + per) * n);
+        ext_batch(level, items, -1, 0, 0, fuse);
     }
     MKHE_HIP(hipGetLastError());
 }
@@ -392,19 +392,18 @@ void Context::mul_relin_batch(const std::vector<const Ct*>& op0, const std::vect
         const size_t per = std::max<size_t>(1, EXT_MAX_ITEMS / (size_t)n0);
         for (size_t b0 = 0; b0 < B; b0 += per) {
             std::vector<ExtItem> items;
-            ext_xmap_.clear(); ext_ykeys_.clear(); ext_yh_.clear(); ext_eouts_.clear();
+            ExtFuse fuse;
             for (size_t b = b0; b < std::min(B, b0 + per); ++b) {
-                if (fuse_e) ext_eouts_.push_back(epre[b]);
+                if (fuse_e) fuse.eouts.push_back(epre[b]);
                 for (int a = 0; a < n0; ++a) {
                     items.push_back(ExtItem{h0[b * n0 + a], y[b], tbuf[b] + (size_t)a * PO, false});
                     if (fuse_x) items.back().xkey = rlk_d0[a]->d;
                 }
-                if (fuse_y) for (int a = 0; a < n1; ++a) ext_yh_.push_back(h1[b * n1 + a]);
-                if (fuse_x) ext_xmap_.push_back({y[b], x[b]});
+                if (fuse_y) for (int a = 0; a < n1; ++a) fuse.yh.push_back(h1[b * n1 + a]);
+                if (fuse_x) fuse.xmap.push_back({y[b], x[b]});
             }
-            if (fuse_y) for (int a = 0; a < n1; ++a) ext_ykeys_.push_back(rlk_b1[a]->d);
-            try { ext_batch(level, items); } catch (...) { ext_xmap_.clear(); ext_ykeys_.clear(); ext_yh_.clear(); ext_eouts_.clear(); throw; }
-            ext_xmap_.clear(); ext_ykeys_.clear(); ext_yh_.clear(); ext_eouts_.clear();
+            if (fuse_y) for (int a = 0; a < n1; ++a) fuse.ykeys.push_back(rlk_b1[a]->d);
+            ext_batch(level, items, -1, 0, 0, fuse);
         }
         std::vector<const u64*> dsrc; std::vector<u64*> ddst;
         for (size_t b = 0; b < B; ++b)

@@ -46,8 +46,22 @@ struct ExtItem { const u64* ah; const u64* bg; u64* dst; bool accumulate; const 
                  unsigned gal = 0;            /* rotate_multi: this destination's own Galois element (0: the ext_batch call's); same for every product of a destination */
                  const u64* post = nullptr;   /* rotate_multi: polynomial [L][N] added to the finished destination at the STORED (permuted) position --
                                                  ring.Add(post, Rotate(..)) of AddNew(ct, RotateNew(ct, r)), cnn/cnn.go:33-37 -- by the last product of the destination */
-                 int f2_party = -1;           /* >= 0: step F2 computed by ntt16_f2_kernel (ntt_kernels.h F2FusedArgs) from the party's t (Context::ext_f2_src_): `ah` is not read */
+                 int f2_party = -1;           /* >= 0: step F2 computed by ntt16_f2_kernel (ntt_kernels.h F2FusedArgs) from the party's t (ExtFuse::f2_src): `ah` is not read */
                  int f2_key = 0;              /* ... 0: the product with v_i, 1: with the CRS u */ };
+// what one ext_batch call fuses into its product kernel (Context::ext_front); the default is the plain inner-product launch
+struct ExtFuse {
+    u64* xout = nullptr;                           // the x by-product of step F1
+    u64* xout2 = nullptr;                          // ... and the second gadget's x (mkbfv)
+    std::vector<const u64*> ykeys, yh;             // y computed inside the F1 kernel (ExtXyArgs::ykey / yh); with xmap (a batch): yh holds every
+                                                   // input's digits in turn, ykeys.size() per input
+    std::vector<const u64*> ykeys2, yh2;           // second gadget of ykeys / yh
+    int e_slot = -1;                               // >= 0: the F1 kernel computes step E too: first c1 slot of the E products
+    std::vector<std::pair<const u64*, u64*>> xmap; // batch.hip: (shared key y_b, x_b) per input of a batch's F1 call: one x per group
+    std::vector<u64*> eouts;                       // a batch's F1 call that computes step E too: where input b's E products go ([n1][mtot][N])
+    std::vector<const u64*> staged;                // the digit vectors, read by the items, that decompose_batch left staged (stage_only)
+    std::vector<const u64*> f2_src;                // N = 2^15: the t_i by party of a batch whose F2 products come out of their Decompose NTT itself
+                                                   // (ntt16_f2_kernel); the items carry ExtItem::f2_party
+};
 
 typedef unsigned long long seq_t;
 // per handle: (uid of a context, that context's call counter at its latest use of the buffer); `exposed` once the raw device
@@ -103,7 +117,6 @@ class Context {
     void bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u64* x2, const u64* y1, const u64* y2,
                        const Swk* const* rlk_v, const Swk& crs_u, Ct& out);
     void bfv_slots(const Ct& op0, const Ct& op1, const Ct& out, std::vector<int>& slot0, std::vector<int>& slot1) const;
-    bool bfv_plan_valid_ = false;
     void mul_relin_rescale(const Ct& op0, const Ct& op1, const Swk* const* hoist0, const Swk* const* hoist1, const Swk* const* rlk_b1,
                            const Swk* const* rlk_d0, const Swk* const* rlk_v0, const Swk& crs_u, Ct& out);
     void bfv_mul_relin_unhoisted(const Ct& op0, const Ct& op1, const Swk* const* rlk_b1, const Swk* const* rlk_b2,
@@ -158,32 +171,18 @@ class Context {
     // internal = true: the digits stay inside the engine (hoist pools): their forward NTT skips the final
     // normalisation (values < 34q with the same residues; every consumer is a Montgomery product)
     // stage_only (alpha = 1, N = 2^14, engine-internal): digit spread + the three cross stages only -- the digits are then consumed by ext_batch through
-    // ext_fused_lds_kernel (ext_staged_ names them), which finishes the transform in LDS and multiplies in the same kernel (ntt_kernels.h, ExtFusedArgs)
+    // ext_fused_lds_kernel (ExtFuse::staged names them), which finishes the transform in LDS and multiplies in the same kernel (ntt_kernels.h, ExtFusedArgs)
     void decompose_batch(int level, const std::vector<const u64*>& src, const std::vector<u64*>& dst, bool internal = false, bool stage_only = false);
     bool ext_fused_ok(int level, int nvec) const;
     // stage 0: whole external products; 1: front half only (inner products + inverse NTT into the c1 pool);
     // 2: back half only (ModDown of the c1 pool filled by the preceding stage-1 call with the same items)
-    void ext_batch(int level, const std::vector<ExtItem>& items, int join_before_moddown = -1, int stage = 0, u64 galEl = 0);
-    u64* ext_xout_ = nullptr;             // set around the one ext_batch call that carries the x by-product
+    void ext_batch(int level, const std::vector<ExtItem>& items, int join_before_moddown = -1, int stage = 0, u64 galEl = 0, const ExtFuse& fuse = {});
     std::vector<const u64*> staged_open_; // digit vectors left after the cross stages that no product kernel has finished yet: an ext_batch that reads one of them as a
                                           // full transform is an engine bug and throws (round 5: mkhe_rotate_batch did, for one afternoon, on launches only a fuzz run reached)
-    std::vector<const u64*> ext_staged_;  // set around the one ext_batch call whose items read digit vectors that decompose_batch left staged (stage_only)
-    // N = 2^15 (round 6): the tail batch of a MulAndRelin whose F2 products come out of the Decompose NTT of the t_i itself (ntt16_f2_kernel): the t_i by
-    // party, set around that ext_batch call; the items carry ExtItem::f2_party
-    std::vector<const u64*> ext_f2_src_;
     struct F2Sched { F2Seg* d_segs = nullptr; int nwg = 0, parts = 1; };
     std::map<long, F2Sched> f2_sched_;                   // by (parties, level): the runs of every workgroup, in device memory
     const F2Sched& f2_schedule(int nparties, int level);
-    bool f2_fused_ok(int level, int n0, int n1) const;
-    u64* ext_xout2_ = nullptr;            // ... and the second gadget's x (mkbfv)
-    std::vector<u64*> ext_eouts_;                           // a batch's F1 call that computes step E too: where input b's E products go ([n1][mtot][N])
-    int ext_e_slot_ = -1;                                  // >= 0 around the F1 call that computes step E too: first c1 slot of the E products
-    std::vector<const u64*> ext_ykeys_, ext_yh_;          // set around the F1 call whose kernel computes y itself (ExtXyArgs::ykey / yh); with ext_xmap_ (a
-                                                         // batch): ext_yh_ holds every input's digits in turn, ext_ykeys_.size() per input
-    std::vector<std::pair<const u64*, u64*>> ext_xmap_;   // batch.hip: (shared key y_b, x_b) per input around the F1 call of a batch: one x per group
-    std::vector<const u64*> bfv_xk1_, bfv_xk2_;   // mkbfv single-device MulRelinNew: d1_i, d2_i for the fused x1, x2
-    std::vector<const u64*> bfv_yk1_, bfv_yk2_;   // ... and b1_j, b2_j when y1, y2 (and step E) are computed inside the F1 kernel too
-    std::vector<const u64*> ext_ykeys2_, ext_yh2_;  // second gadget of ext_ykeys_ / ext_yh_
+    bool f2_fused_ok(int level, int n0, int n1);         // (fills the f2_sched_ entry of the shape)
     // External products that ModDown adds into ONE destination are merged (ModDown is linear in the Q part, see NttBatch::vi and
     // ModDownMergedArgs): virtual item v = up to VI_MAX items of the batch with the same destination; their Q limbs are summed in the
     // NTT domain at the load of ONE inverse NTT, their P limbs are transformed and lifted one by one.  MKHE_EXT_MERGE=0 switches it off.
@@ -198,8 +197,12 @@ class Context {
     };
     int ext_merge_members(int level) const;      // members a virtual item may have at this level (< 2: no merging)
     bool ext_plan_merge(int level, const ExtItem* items, int n, ExtMerge& mp) const;
-    void ext_front(int level, const ExtItem* items, int n, u64* c1, const ExtMerge* mp = nullptr);   // inner products + lazy inverse NTT into c1 [n][mtot][N]
-    bool ext_front_f2(int level, const ExtItem* items, int n, u64* c1, ExtInnerArgs& ia, unsigned short* f2_parts);
+    void ext_front(int level, const ExtItem* items, int n, u64* c1, const ExtMerge* mp, const ExtFuse& fuse);   // inner products + lazy inverse NTT into c1 [n][mtot][N]
+    // the product kernels of ext_front's fused forms
+    bool ext_front_f2(int level, const ExtItem* items, int n, u64* c1, ExtInnerArgs& ia, const ExtFuse& fuse, unsigned short* f2_parts);
+    bool ext_front_staged(int level, const ExtItem* items, int n, u64* c1, const ExtFuse& fuse);
+    void ext_front_xy(int level, const ExtItem* items, int n, u64* c1, const ExtFuse& fuse);
+    void ext_front_xy_batch(int level, const ExtItem* items, int n, u64* c1, const ExtFuse& fuse);
     void ext_back(int level, const ExtItem* items, int n, const u64* c1, u64 galEl = 0, const ExtMerge* mp = nullptr);   // ModDown of c1 into / onto the destinations [signed-permuted]
 
     // ---- limb-sharded multi-GPU evaluation (mkhe_kklss_amd/dist.py LimbShardedMulRelin): this context owns a subset of
@@ -349,6 +352,13 @@ class Context {
         const u64* f2_tbuf = nullptr;
         bool e_done = false;                 // ... and so was step E: its products sit in the c1 slots 2 n0 .. 2 n0 + n1 - 1 of the scratch, for the tail batch
     } plan_;
+    // bfv_mr_partial -> bfv_mr_finish
+    struct BfvPlan {
+        bool valid = false;
+        std::vector<const u64*> xk1, xk2;        // single-device MulRelinNew: d1_i, d2_i for the fused x1, x2
+        std::vector<const u64*> yk1, yk2;        // ... and b1_j, b2_j when y1, y2 (and step E) are computed inside the F1 kernel too
+        u64 *xout1 = nullptr, *xout2 = nullptr;  // fused: where the F1 kernel of bfv_mr_finish stores x1, x2
+    } bfv_plan_;
 
     // Stream-ordered buffer pool.  A buffer freed through this context may still be in use by kernels that ANOTHER context of the
     // same device enqueued (handles are shared freely between forked contexts).  Ordering between contexts is tracked with one

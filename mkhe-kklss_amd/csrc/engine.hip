@@ -700,9 +700,8 @@ void Context::side_done(int k) { if (!overlap) return; MKHE_HIP(hipEventRecord(e
 void Context::join_side(int k) { if (!overlap) return; MKHE_HIP(hipStreamWaitEvent(s_, ev_[2 * k + 1], 0)); }
 void Context::recover() {
     s_ = stream;
-    plan_.valid = false; plan_.x_pending = false; plan_.head_done = false; plan_.xkeys.clear(); ext_xout_ = ext_xout2_ = nullptr;
-    rs_maps_.clear();
-    bfv_plan_valid_ = false; bfv_xk1_.clear(); bfv_xk2_.clear();
+    plan_ = MrPlan{}; bfv_plan_ = BfvPlan{};
+    rs_maps_.clear(); staged_open_.clear();
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &cs);
     if (cs == hipStreamCaptureStatusNone) { (void)hipStreamSynchronize(stream2); (void)hipStreamSynchronize(stream); }
@@ -1089,7 +1088,7 @@ bool Context::ext_plan_merge(int level, const ExtItem* it, int n, ExtMerge& mp) 
 
 // The product kernel of a batch whose F2 items come out of the Decompose NTT of the t_i itself (N = 2^15, ntt16_f2_kernel; ExtItem::f2_party).  Returns whether
 // the products arrive in parts (f2_parts[i]: NttBatch::vi_parts of item i -- the inverse NTT adds them at its load).
-bool Context::ext_front_f2(int level, const ExtItem* it, int n, u64* c1, ExtInnerArgs& ia, unsigned short* f2_parts) {
+bool Context::ext_front_f2(int level, const ExtItem* it, int n, u64* c1, ExtInnerArgs& ia, const ExtFuse& fuse, unsigned short* f2_parts) {
     const size_t item_words = (size_t)mtot * N;
     // N = 2^15: the F2 products come out of the Decompose NTT of the t_i itself (ntt16_f2_kernel).  The other items of the batch exist already
     // (step E computed by the F1 kernel: `pre`) or are plain products of stored digits -- the sharded finish, more parties than the F1 kernel's
@@ -1100,11 +1099,11 @@ bool Context::ext_front_f2(int level, const ExtItem* it, int n, u64* c1, ExtInne
         else others = others || !(it[i].pre && !it[i].pre_src);
     }
     if (others) launch_ext_inner(ia, s_);
-    const int np0 = (int)ext_f2_src_.size();
+    const int np0 = (int)fuse.f2_src.size();
     const F2Sched& sc = f2_schedule(np0, level);
     F2FusedArgs fa{};
     fa.segs = sc.d_segs; fa.nwg = sc.nwg; fa.c1 = c1; fa.item_words = (long)item_words; fa.digit_stride = (long)item_words;
-    for (int a = 0; a < np0; ++a) { fa.src[a] = ext_f2_src_[a]; fa.item_v[a] = fa.item_u[a] = -1; }
+    for (int a = 0; a < np0; ++a) { fa.src[a] = fuse.f2_src[a]; fa.item_v[a] = fa.item_u[a] = -1; }
     int nf2 = 0;
     for (int i = 0; i < n; ++i) {
         const int a = it[i].f2_party;
@@ -1125,15 +1124,90 @@ bool Context::ext_front_f2(int level, const ExtItem* it, int n, u64* c1, ExtInne
     return sc.parts > 1;
 }
 
-void Context::ext_front(int level, const ExtItem* it, int n, u64* c1, const ExtMerge* mp) {
+// The items' digit vectors were left after the cross stages (decompose_batch, stage_only): sub-transforms and products in one kernel (true: the inverse too)
+bool Context::ext_front_staged(int level, const ExtItem* it, int n, u64* c1, const ExtFuse& fuse) {
+    const size_t item_words = (size_t)mtot * N;
+    if ((int)fuse.staged.size() > EXTF_MAX_V) throw Error("mkhe: internal: staged digits in a launch that cannot take them");
+    ExtFusedArgs fa{};
+    fa.nv = (int)fuse.staged.size();
+    for (int v = 0; v < fa.nv; ++v) fa.stage[v] = fuse.staged[v];
+    for (int v = 0; v < fa.nv; ++v) staged_open_.erase(std::remove(staged_open_.begin(), staged_open_.end(), fuse.staged[v]), staged_open_.end());
+    for (int i = 0; i < n; ++i) {
+        if (it[i].pre && !it[i].pre_src) continue;                 // (computed before, in its slot)
+        int v = -1;
+        for (int k = 0; k < fa.nv; ++k) if (fuse.staged[k] == it[i].ah) v = k;
+        if (v < 0 || it[i].pre || fa.nk[v] >= 2) throw Error("mkhe: internal: staged digits in a launch that cannot take them");
+        fa.bg[v][fa.nk[v]] = it[i].bg; fa.out[v][fa.nk[v]] = c1 + (size_t)i * item_words; ++fa.nk[v];
+    }
+    for (int v = 0; v < fa.nv; ++v) if (!fa.nk[v]) throw Error("mkhe: internal: a staged digit vector without a product");
+    fa.mods = d_mods; fa.map = map_qp(level); fa.psi = d_psi; fa.digit_stride = (long)item_words;
+    for (int m2 = 0; m2 < mall && m2 < 64; ++m2) if (small_q_[m2]) fa.small_mask |= 1ull << m2;
+    fa.nb = beta(level); fa.nslots = nslots_qp(level); fa.N = N; fa.logN = logN;
+    // every product of the launch made here, no NTT-domain summand (rotations, conjugations): the inverse sub-transforms as well
+    static const int inv_env = MKHE_AB_INT("MKHE_EXT_FUSED_INV", 1);
+    bool fused_inv = inv_env != 0;
+    for (int i = 0; i < n; ++i) fused_inv = fused_inv && !it[i].pre && !it[i].qadd;
+    if (fused_inv) { fa.inv = 1; fa.psiinv = d_psiinv; fa.aux = d_inv_aux; }
+    launch_ext_fused_lds(fa, s_);
+    return fused_inv;
+}
+// Step F1 with y computed in the thread beside the x by-product (and step E too when fuse.e_slot >= 0): up to four items, or five to eight of one gadget.
+void Context::ext_front_xy(int level, const ExtItem* it, int n, u64* c1, const ExtFuse& fuse) {
+    const int nb = beta(level), nslots = nslots_qp(level), ny = (int)fuse.ykeys.size();
+    const size_t item_words = (size_t)mtot * N;
+    u64 *const xout = fuse.e_slot >= 0 ? nullptr : fuse.xout, *const e_out = fuse.e_slot >= 0 ? c1 + (size_t)fuse.e_slot * item_words : nullptr;
+    if (n > 4) {
+        ExtXyWideArgs xa{};
+        for (int j = 0; j < n; ++j) { xa.ah[j] = it[j].ah; xa.xkey[j] = it[j].xkey; xa.ykey[j] = fuse.ykeys[j]; xa.yh[j] = fuse.yh[j]; }
+        xa.xout = xout; xa.e_out = e_out; xa.c1 = c1; xa.mods = d_mods; xa.map = map_qp(level); xa.digit_stride = (long)item_words; xa.c1_item = (long)item_words;
+        xa.g = n; xa.nb = nb; xa.nslots = nslots; xa.N = N;
+        launch_ext_inner_xy_wide(xa, s_);
+        return;
+    }
+    ExtXyArgs xa{};
+    for (int j = 0; j < n; ++j) { xa.ah[j] = it[j].ah; xa.xkey[j] = it[j].xkey; }
+    for (int j = 0; j < ny; ++j) { xa.ykey[j] = fuse.ykeys[j]; xa.yh[j] = fuse.yh[j]; }
+    if (fuse.xout2) { for (int j = 0; j < n; ++j) { xa.ah2[j] = it[j].ah2; xa.xkey2[j] = it[j].xkey2; } for (int j = 0; j < ny; ++j) { xa.ykey2[j] = fuse.ykeys2[j]; xa.yh2[j] = fuse.yh2[j]; } }
+    xa.xout2 = fuse.e_slot < 0 ? fuse.xout2 : nullptr;
+    xa.xout = xout; xa.e_out = e_out; xa.c1 = c1; xa.mods = d_mods; xa.map = map_qp(level); xa.digit_stride = (long)item_words; xa.c1_item = (long)item_words;
+    xa.g = n; xa.g1 = ny; xa.nb = nb; xa.nslots = nslots; xa.N = N;
+    launch_ext_inner_xy(xa, s_);
+}
+// B inputs' step F1 with x_b and y_b in the thread: the items come input by input (g per input, mul_relin_batch), up to XYB_MAX inputs per launch
+void Context::ext_front_xy_batch(int level, const ExtItem* it, int n, u64* c1, const ExtFuse& fuse) {
+    const int nb = beta(level), nslots = nslots_qp(level);
+    const size_t item_words = (size_t)mtot * N;
+    const int nin = (int)fuse.xmap.size(), g = nin ? n / nin : 0, g1 = (int)fuse.ykeys.size();
+    if (g < 1 || g > 4 || g1 < 1 || g1 > 4 || nin * g != n || (int)fuse.yh.size() != nin * g1 || (!fuse.eouts.empty() && (int)fuse.eouts.size() != nin)) throw Error("mkhe: internal: per-input y on a batch that cannot carry it");
+    for (int b0 = 0; b0 < nin; b0 += XYB_MAX) {
+        ExtXyBatchArgs xa{};
+        const int cnt = std::min(XYB_MAX, nin - b0);
+        for (int b = 0; b < cnt; ++b) {
+            for (int j = 0; j < g; ++j) {
+                const ExtItem& e = it[(b0 + b) * g + j];
+                if (e.bg != fuse.xmap[b0 + b].first || !e.xkey) throw Error("mkhe: internal: per-input y on a batch that cannot carry it");
+                xa.ah[b][j] = e.ah;
+                if (b == 0) xa.xkey[j] = e.xkey; else if (e.xkey != xa.xkey[j]) throw Error("mkhe: internal: per-input y on a batch that cannot carry it");
+            }
+            for (int j = 0; j < g1; ++j) xa.yh[b][j] = fuse.yh[(b0 + b) * g1 + j];
+            xa.xout[b] = fuse.xmap[b0 + b].second;
+            if (!fuse.eouts.empty()) xa.eout[b] = fuse.eouts[b0 + b];
+        }
+        for (int j = 0; j < g1; ++j) xa.ykey[j] = fuse.ykeys[j];
+        xa.c1 = c1 + (size_t)b0 * g * item_words; xa.mods = d_mods; xa.map = map_qp(level); xa.digit_stride = (long)item_words; xa.c1_item = (long)item_words;
+        xa.g = g; xa.g1 = g1; xa.nbatch = cnt; xa.nb = nb; xa.nslots = nslots; xa.N = N;
+        launch_ext_inner_xy_batch(xa, s_);
+    }
+}
+void Context::ext_front(int level, const ExtItem* it, int n, u64* c1, const ExtMerge* mp, const ExtFuse& fuse) {
     const int nb = beta(level), nslots = nslots_qp(level);
     const size_t item_words = (size_t)mtot * N;
     if (n < 1 || nslots < 1) return;
     ExtInnerArgs ia{};
     bool two = false, fused_inv = false, any_parts = false;
     unsigned short f2_parts[EXT_MAX_ITEMS] = {};
-    bool xby = ext_xout_ != nullptr && n <= (ext_xout2_ ? 4 : 16);     // (five to sixteen single-gadget items: ext_inner_xwide_kernel)
-    const bool xby2 = ext_xout2_ != nullptr;               // mkbfv: both gadgets carry their x
+    bool xby = fuse.xout != nullptr && n <= (fuse.xout2 ? 4 : 16);     // (five to sixteen single-gadget items: ext_inner_xwide_kernel)
+    const bool xby2 = fuse.xout2 != nullptr;               // mkbfv: both gadgets carry their x
     for (int i = 0; i < n; ++i) {
         ia.ah[i] = it[i].ah; ia.bg[i] = it[i].bg;
         ia.ah2[i] = it[i].ah2; ia.bg2[i] = it[i].bg2;
@@ -1142,19 +1216,19 @@ void Context::ext_front(int level, const ExtItem* it, int n, u64* c1, const ExtM
         xby = xby && it[i].xkey && it[i].bg == it[0].bg;
         if (xby2) xby = xby && it[i].ah2 && it[i].xkey2 && it[i].bg2 == it[0].bg2; else xby = xby && !it[i].ah2;
     }
-    if ((ext_xout_ || ext_xout2_) && !xby) throw Error("mkhe: internal: x by-product requested for a batch that cannot carry it");
-    ia.xout = xby ? ext_xout_ : nullptr; ia.xout2 = xby && xby2 ? ext_xout2_ : nullptr; ia.xmform = 1;
-    const bool xy = !ext_ykeys_.empty() && ext_xmap_.empty(), xyb = !ext_ykeys_.empty() && !ext_xmap_.empty();
-    const int ny = (int)ext_ykeys_.size();
-    if (xy && (!xby || mp || n > (xby2 ? 4 : 8) || (n > 4 && ny != n) || ny < 1 || ny > 8 || (n <= 4 && ny > 4) || (int)ext_yh_.size() != ny ||
-               (xby2 && ((int)ext_ykeys2_.size() != ny || (int)ext_yh2_.size() != ny)))) throw Error("mkhe: internal: y inside a launch that cannot compute it");
+    if ((fuse.xout || fuse.xout2) && !xby) throw Error("mkhe: internal: x by-product requested for a batch that cannot carry it");
+    ia.xout = xby ? fuse.xout : nullptr; ia.xout2 = xby && xby2 ? fuse.xout2 : nullptr; ia.xmform = 1;
+    const bool xy = !fuse.ykeys.empty() && fuse.xmap.empty(), xyb = !fuse.ykeys.empty() && !fuse.xmap.empty();
+    const int ny = (int)fuse.ykeys.size();
+    if (xy && (!xby || mp || n > (xby2 ? 4 : 8) || (n > 4 && ny != n) || ny < 1 || ny > 8 || (n <= 4 && ny > 4) || (int)fuse.yh.size() != ny ||
+               (xby2 && ((int)fuse.ykeys2.size() != ny || (int)fuse.yh2.size() != ny)))) throw Error("mkhe: internal: y inside a launch that cannot compute it");
     int xgroups = 0;
-    if (!ext_xmap_.empty()) {
+    if (!fuse.xmap.empty()) {
         // B inputs' step F1 in one launch (mul_relin_batch): the items that share y_b are input b's, at most four, and carry x_b
         if (xby || two || mp) throw Error("mkhe: internal: per-input x by-products on a batch that cannot carry them");
         for (int i = 0; i < n; ++i) {
             u64* xo = nullptr; int cnt = 0;
-            for (const auto& e : ext_xmap_) if (e.first == it[i].bg) xo = e.second;
+            for (const auto& e : fuse.xmap) if (e.first == it[i].bg) xo = e.second;
             for (int k = 0; k < n; ++k) cnt += it[k].bg == it[i].bg;
             if (!xo || !it[i].xkey || cnt > 4) throw Error("mkhe: internal: per-input x by-products on a batch that cannot carry them");
             ia.xkey2[i] = xo;
@@ -1162,7 +1236,7 @@ void Context::ext_front(int level, const ExtItem* it, int n, u64* c1, const ExtM
             for (int k = 0; k < i; ++k) first = first && it[k].bg != it[i].bg;
             xgroups += first;
         }
-        ia.xout = ext_xmap_[0].second; ia.xmulti = 1;
+        ia.xout = fuse.xmap[0].second; ia.xmulti = 1;
         xby = true;
     }
     // keys that a single item reads (v_i, rotation keys) are streamed; x, y, u are shared by several items and stay cached
@@ -1182,7 +1256,6 @@ void Context::ext_front(int level, const ExtItem* it, int n, u64* c1, const ExtM
     ia.nitems = n; ia.nb = nb; ia.nslots = nslots; ia.N = N;
     // algorithmic bytes: every DISTINCT digit / key array once (items that share x, y or the CRS u are computed by one thread that loads the
     // shared operand once per coefficient, ext_inner_group_kernel), one output limb per item, and the x by-product's keys and result
-    (void)two;
     int distinct = 0;
     {
         const u64* seen[4 * EXT_MAX_ITEMS]; int ns = 0;
@@ -1191,81 +1264,23 @@ void Context::ext_front(int level, const ExtItem* it, int n, u64* c1, const ExtM
         distinct = ns;
     }
     // (the fused F2 launch: every t_i limb once, every key once, the parts of the products out)
-    const bool f2 = !ext_f2_src_.empty();
-    const double f2_bytes = f2 ? 8.0 * N * ((double)ext_f2_src_.size() * nb + (double)nb * nslots * (ext_f2_src_.size() + 1.0) + 2.0 * ext_f2_src_.size() * nslots * f2_schedule((int)ext_f2_src_.size(), level).parts) : 0.0;
-    { ProfScope ps(this, f2 ? PROF_NTT_F2 : PROF_EXT_INNER, f2 ? f2_bytes : 8.0 * N * nslots * ((double)nb * distinct + n + (xby ? nb * (n + (xgroups ? xgroups : 1.0)) * (xby2 ? 2 : 1) : 0.0) + (xy ? nb * (2.0 * ny - 1.0) : 0.0) + (xyb ? nb * (1.0 * n + ext_ykeys_.size() - xgroups) : 0.0)));
-      if (ext_staged_.empty()) {
+    const bool f2 = !fuse.f2_src.empty();
+    const double f2_bytes = f2 ? 8.0 * N * ((double)fuse.f2_src.size() * nb + (double)nb * nslots * (fuse.f2_src.size() + 1.0) + 2.0 * fuse.f2_src.size() * nslots * f2_schedule((int)fuse.f2_src.size(), level).parts) : 0.0;
+    { ProfScope ps(this, f2 ? PROF_NTT_F2 : PROF_EXT_INNER, f2 ? f2_bytes : 8.0 * N * nslots * ((double)nb * distinct + n + (xby ? nb * (n + (xgroups ? xgroups : 1.0)) * (xby2 ? 2 : 1) : 0.0) + (xy ? nb * (2.0 * ny - 1.0) : 0.0) + (xyb ? nb * (1.0 * n + fuse.ykeys.size() - xgroups) : 0.0)));
+      if (fuse.staged.empty()) {
           for (int i = 0; i < n; ++i)
               if (!it[i].pre && std::find(staged_open_.begin(), staged_open_.end(), it[i].ah) != staged_open_.end())
                   throw Error("mkhe: internal: digits left after the cross stages read as a full transform");
       }
-      if (!ext_f2_src_.empty()) {
-          if (xby || xy || xyb || !mp || !ext_staged_.empty()) throw Error("mkhe: internal: fused F2 products in a launch that cannot take them");
-          any_parts = ext_front_f2(level, it, n, c1, ia, f2_parts);
-      } else if (!ext_staged_.empty()) {
-          // the items' digit vectors were left after the cross stages (decompose_batch, stage_only): sub-transforms and products in one kernel
-          if (xby || xy || xyb || two || (int)ext_staged_.size() > EXTF_MAX_V) throw Error("mkhe: internal: staged digits in a launch that cannot take them");
-          ExtFusedArgs fa{};
-          fa.nv = (int)ext_staged_.size();
-          for (int v = 0; v < fa.nv; ++v) fa.stage[v] = ext_staged_[v];
-          for (int v = 0; v < fa.nv; ++v) staged_open_.erase(std::remove(staged_open_.begin(), staged_open_.end(), ext_staged_[v]), staged_open_.end());
-          for (int i = 0; i < n; ++i) {
-              if (it[i].pre && !it[i].pre_src) continue;                 // (computed before, in its slot)
-              int v = -1;
-              for (int k = 0; k < fa.nv; ++k) if (ext_staged_[k] == it[i].ah) v = k;
-              if (v < 0 || it[i].pre || fa.nk[v] >= 2) throw Error("mkhe: internal: staged digits in a launch that cannot take them");
-              fa.bg[v][fa.nk[v]] = it[i].bg; fa.out[v][fa.nk[v]] = c1 + (size_t)i * item_words; ++fa.nk[v];
-          }
-          for (int v = 0; v < fa.nv; ++v) if (!fa.nk[v]) throw Error("mkhe: internal: a staged digit vector without a product");
-          fa.mods = d_mods; fa.map = map_qp(level); fa.psi = d_psi; fa.digit_stride = (long)item_words;
-          for (int m2 = 0; m2 < mall && m2 < 64; ++m2) if (small_q_[m2]) fa.small_mask |= 1ull << m2;
-          fa.nb = nb; fa.nslots = nslots; fa.N = N; fa.logN = logN;
-          // every product of the launch made here, no NTT-domain summand (rotations, conjugations): the inverse sub-transforms as well
-          static const int inv_env = MKHE_AB_INT("MKHE_EXT_FUSED_INV", 1);
-          fused_inv = inv_env != 0;
-          for (int i = 0; i < n; ++i) fused_inv = fused_inv && !it[i].pre && !it[i].qadd;
-          if (fused_inv) { fa.inv = 1; fa.psiinv = d_psiinv; fa.aux = d_inv_aux; }
-          launch_ext_fused_lds(fa, s_);
-      } else if (xy && n > 4) {
-          ExtXyWideArgs xa{};
-          for (int j = 0; j < n; ++j) { xa.ah[j] = it[j].ah; xa.xkey[j] = it[j].xkey; xa.ykey[j] = ext_ykeys_[j]; xa.yh[j] = ext_yh_[j]; }
-          xa.xout = ext_e_slot_ >= 0 ? nullptr : ext_xout_; xa.e_out = ext_e_slot_ >= 0 ? c1 + (size_t)ext_e_slot_ * item_words : nullptr; xa.c1 = c1;
-          xa.mods = d_mods; xa.map = map_qp(level); xa.digit_stride = (long)item_words; xa.c1_item = (long)item_words;
-          xa.g = n; xa.nb = nb; xa.nslots = nslots; xa.N = N;
-          launch_ext_inner_xy_wide(xa, s_);
-      } else if (xy) {
-          ExtXyArgs xa{};
-          for (int j = 0; j < n; ++j) { xa.ah[j] = it[j].ah; xa.xkey[j] = it[j].xkey; }
-          for (int j = 0; j < ny; ++j) { xa.ykey[j] = ext_ykeys_[j]; xa.yh[j] = ext_yh_[j]; }
-          if (xby2) { for (int j = 0; j < n; ++j) { xa.ah2[j] = it[j].ah2; xa.xkey2[j] = it[j].xkey2; } for (int j = 0; j < ny; ++j) { xa.ykey2[j] = ext_ykeys2_[j]; xa.yh2[j] = ext_yh2_[j]; } }
-          xa.xout2 = (xby2 && ext_e_slot_ < 0) ? ext_xout2_ : nullptr;
-          xa.xout = ext_e_slot_ >= 0 ? nullptr : ext_xout_; xa.e_out = ext_e_slot_ >= 0 ? c1 + (size_t)ext_e_slot_ * item_words : nullptr; xa.c1 = c1; xa.mods = d_mods; xa.map = map_qp(level); xa.digit_stride = (long)item_words; xa.c1_item = (long)item_words;
-          xa.g = n; xa.g1 = ny; xa.nb = nb; xa.nslots = nslots; xa.N = N;
-          launch_ext_inner_xy(xa, s_);
-      } else if (xyb) {
-          // B inputs' step F1 with x_b and y_b in the thread: the items come input by input (g per input, mul_relin_batch), up to XYB_MAX inputs per launch
-          const int nin = (int)ext_xmap_.size(), g = nin ? n / nin : 0, g1 = (int)ext_ykeys_.size();
-          if (two || mp || g < 1 || g > 4 || g1 < 1 || g1 > 4 || nin * g != n || (int)ext_yh_.size() != nin * g1 || (!ext_eouts_.empty() && (int)ext_eouts_.size() != nin)) throw Error("mkhe: internal: per-input y on a batch that cannot carry it");
-          for (int b0 = 0; b0 < nin; b0 += XYB_MAX) {
-              ExtXyBatchArgs xa{};
-              const int cnt = std::min(XYB_MAX, nin - b0);
-              for (int b = 0; b < cnt; ++b) {
-                  for (int j = 0; j < g; ++j) {
-                      const ExtItem& e = it[(b0 + b) * g + j];
-                      if (e.bg != ext_xmap_[b0 + b].first || !e.xkey) throw Error("mkhe: internal: per-input y on a batch that cannot carry it");
-                      xa.ah[b][j] = e.ah;
-                      if (b == 0) xa.xkey[j] = e.xkey; else if (e.xkey != xa.xkey[j]) throw Error("mkhe: internal: per-input y on a batch that cannot carry it");
-                  }
-                  for (int j = 0; j < g1; ++j) xa.yh[b][j] = ext_yh_[(b0 + b) * g1 + j];
-                  xa.xout[b] = ext_xmap_[b0 + b].second;
-                  if (!ext_eouts_.empty()) xa.eout[b] = ext_eouts_[b0 + b];
-              }
-              for (int j = 0; j < g1; ++j) xa.ykey[j] = ext_ykeys_[j];
-              xa.c1 = c1 + (size_t)b0 * g * item_words; xa.mods = d_mods; xa.map = map_qp(level); xa.digit_stride = (long)item_words; xa.c1_item = (long)item_words;
-              xa.g = g; xa.g1 = g1; xa.nbatch = cnt; xa.nb = nb; xa.nslots = nslots; xa.N = N;
-              launch_ext_inner_xy_batch(xa, s_);
-          }
-      } else launch_ext_inner(ia, s_); }
+      if (f2) {
+          if (xby || xy || xyb || !mp || !fuse.staged.empty()) throw Error("mkhe: internal: fused F2 products in a launch that cannot take them");
+          any_parts = ext_front_f2(level, it, n, c1, ia, fuse, f2_parts);
+      } else if (!fuse.staged.empty()) {
+          if (xby || xy || xyb || two) throw Error("mkhe: internal: staged digits in a launch that cannot take them");
+          fused_inv = ext_front_staged(level, it, n, c1, fuse);
+      } else if (xy) ext_front_xy(level, it, n, c1, fuse);
+      else if (xyb) ext_front_xy_batch(level, it, n, c1, fuse);      // (xby, two and mp were ruled out with fuse.xmap above)
+      else launch_ext_inner(ia, s_); }
     NttBatch b{};
     b.src = c1; b.dst = c1; b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux;
     b.src_inner = b.dst_inner = N; b.src_mapped = b.dst_mapped = 1;
@@ -1357,23 +1372,20 @@ void Context::ext_back(int level, const ExtItem* it, int n, const u64* c1, u64 g
     md.galEl = galEl; md.logN = logN;
     { ProfScope ps(this, PROF_MODDOWN, bytes); launch_moddown_batch(md, s_); }
 }
-void Context::ext_batch(int level, const std::vector<ExtItem>& items, int join_before_moddown, int stage, u64 galEl) {
+void Context::ext_batch(int level, const std::vector<ExtItem>& items, int join_before_moddown, int stage, u64 galEl, const ExtFuse& fuse) {
     if (galEl && items.size() > (size_t)EXT_MAX_ITEMS) throw Error("mkhe: too many external products for a fused rotation");
     if (stage != 0 && items.size() > (size_t)EXT_MAX_ITEMS) throw Error("mkhe: too many external products for a staged batch");
     check_level(level);
     const size_t item_words = (size_t)mtot * N;
     for (size_t base = 0; base < items.size(); base += EXT_MAX_ITEMS) {
         const int n = (int)std::min<size_t>(EXT_MAX_ITEMS, items.size() - base);
-        int extra = 0;
-        if (!ext_f2_src_.empty()) {
-            int nf2 = 0;
-            for (int i = 0; i < n; ++i) nf2 += items[base + i].f2_party >= 0;
-            extra = nf2 * (f2_schedule((int)ext_f2_src_.size(), level).parts - 1);
-        }
+        int nf2 = 0;
+        for (int i = 0; i < n; ++i) nf2 += items[base + i].f2_party >= 0;
+        const int extra = fuse.f2_src.empty() ? 0 : nf2 * (f2_schedule((int)fuse.f2_src.size(), level).parts - 1);
         u64* c1 = scratch(c1b_, c1b_words_, (size_t)(n + extra) * item_words);
         ExtMerge mp;
         const bool merged = stage == 0 && ext_plan_merge(level, items.data() + base, n, mp);
-        if (stage != 2) ext_front(level, items.data() + base, n, c1, merged ? &mp : nullptr);
+        if (stage != 2) ext_front(level, items.data() + base, n, c1, merged ? &mp : nullptr, fuse);
         if (stage == 1) continue;
         if (join_before_moddown >= 0) { join_side(join_before_moddown); join_before_moddown = -1; }
         ext_back(level, items.data() + base, n, c1, galEl, merged ? &mp : nullptr);

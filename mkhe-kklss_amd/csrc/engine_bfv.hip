@@ -155,7 +155,7 @@ void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk
                              u64* x1, u64* x2, u64* y1, u64* y2, bool fuse_x, bool fuse_y) {
     if (!is_bfv()) throw Error("mkhe: not a BFV context");
     const int level = nq - 1, L = nq, n0 = op0.n, n1 = op1.n;
-    bfv_xk1_.clear(); bfv_xk2_.clear(); bfv_yk1_.clear(); bfv_yk2_.clear();
+    BfvPlan& bp = bfv_plan_ = BfvPlan{};
     std::vector<int> slot0, slot1;
     bfv_slots(op0, op1, out, slot0, slot1);
     for (int a = 0; a < n0; ++a) if (!rlk_d1[a] || !rlk_d2[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
@@ -209,12 +209,13 @@ void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk
     // (Context::mul_and_relin does the same for mkckks) -- two inner-product launches and one pass over h1(c0_i), h2(c0_i) less
     if (fuse_x) {
         if (!mform) throw Error("mkhe: internal: the fused x is produced in Montgomery form");
-        for (int a = 0; a < n0; ++a) { bfv_xk1_.push_back(rlk_d1[a]->d); bfv_xk2_.push_back(rlk_d2[a]->d); }
+        for (int a = 0; a < n0; ++a) { bp.xk1.push_back(rlk_d1[a]->d); bp.xk2.push_back(rlk_d2[a]->d); }
+        bp.xout1 = x1; bp.xout2 = x2;
     }
     // ... and y1, y2 (and step E) inside it as well, when op1 has as many parties (Context::mul_and_relin, round 4)
     if (fuse_y) {
         if (!fuse_x || n1 < 1 || n1 > 4 || n0 > 4) throw Error("mkhe: internal: y inside the F1 kernel needs the x by-product and one to four parties per operand");
-        for (int a = 0; a < n1; ++a) { bfv_yk1_.push_back(rlk_b1[a]->d); bfv_yk2_.push_back(rlk_b2[a]->d); }
+        for (int a = 0; a < n1; ++a) { bp.yk1.push_back(rlk_b1[a]->d); bp.yk2.push_back(rlk_b2[a]->d); }
     }
     for (int which = fuse_y ? 1 : 3; which >= (fuse_x ? 2 : 0); --which) {
         const int side = which >> 1, half = which & 1;
@@ -237,14 +238,15 @@ void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk
     }
     // split-phase callers read x1, x2 between the phases (cross-device reduction): the side chain joins the main stream here
     if (!mform) join_side(2);
-    bfv_plan_valid_ = true;
+    bp.valid = true;
     MKHE_HIP(hipGetLastError());
 }
 
 void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u64* x2, const u64* y1, const u64* y2,
                             const Swk* const* rlk_v, const Swk& crs_u, Ct& out) {
     if (!is_bfv()) throw Error("mkhe: not a BFV context");
-    if (!bfv_plan_valid_) throw Error("mkhe: bfv_mr_finish without bfv_mr_partial");
+    const BfvPlan& bp = bfv_plan_;
+    if (!bp.valid) throw Error("mkhe: bfv_mr_finish without bfv_mr_partial");
     const int level = nq - 1, n0 = op0.n, n1 = op1.n;
     std::vector<int> slot0, slot1;
     bfv_slots(op0, op1, out, slot0, slot1);
@@ -253,17 +255,18 @@ void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u
     // F1: t_i = <h(c0_i), (y1,y2)>
     u64* tbuf = scratch(tbuf_, tbuf_words_, (size_t)n0 * PQ);
     std::vector<ExtItem> items;
-    const bool fused = !bfv_xk1_.empty();
+    const bool fused = !bp.xk1.empty();
     for (int a = 0; a < n0; ++a) {
         ExtItem it{hoist_slot(0, a).d, y1, tbuf + (size_t)a * PQ, false}; it.ah2 = hoist_slot(3, a).d; it.bg2 = y2;
-        if (fused) { it.xkey = bfv_xk1_[a]; it.xkey2 = bfv_xk2_[a]; }
+        if (fused) { it.xkey = bp.xk1[a]; it.xkey2 = bp.xk2[a]; }
         items.push_back(it);
     }
-    if (fused) { ext_xout_ = const_cast<u64*>(x1); ext_xout2_ = const_cast<u64*>(x2); }
-    bool e_done = false, f2 = false;
-    if (fused && !bfv_yk1_.empty()) {
-        ext_ykeys_ = bfv_yk1_; ext_ykeys2_ = bfv_yk2_;
-        for (int a = 0; a < n1; ++a) { ext_yh_.push_back(hoist_slot(1, a).d); ext_yh2_.push_back(hoist_slot(4, a).d); }
+    ExtFuse fuse;
+    if (fused) { fuse.xout = bp.xout1; fuse.xout2 = bp.xout2; }
+    bool f2 = false;
+    if (fused && !bp.yk1.empty()) {
+        fuse.ykeys = bp.yk1; fuse.ykeys2 = bp.yk2;
+        for (int a = 0; a < n1; ++a) { fuse.yh.push_back(hoist_slot(1, a).d); fuse.yh2.push_back(hoist_slot(4, a).d); }
         const int fuse_e_env = ab_fuse_e();
         if (fuse_e_env && 2 * n0 + n1 <= EXT_MAX_ITEMS) {
             // (step F2 is the plain Q gadget here too, keyswitch_hoisted.go:199-204: with step E done by the F1 kernel the digits of the t_i stay in the
@@ -271,20 +274,18 @@ void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u
             f2 = n0 >= 2 && f2_fused_ok(level, n0, n1);
             const int f2_extra = f2 ? 2 * n0 * (f2_schedule(n0, level).parts - 1) : 0;
             scratch(c1b_, c1b_words_, (size_t)(2 * n0 + n1 + f2_extra) * mtot * N);
-            ext_e_slot_ = 2 * n0;
+            fuse.e_slot = 2 * n0;
         }
     }
-    auto clear_xy = [&] { ext_xout_ = ext_xout2_ = nullptr; ext_ykeys_.clear(); ext_ykeys2_.clear(); ext_yh_.clear(); ext_yh2_.clear(); ext_e_slot_ = -1; };
-    try { ext_batch(level, items); } catch (...) { clear_xy(); throw; }
-    e_done = ext_e_slot_ >= 0;
-    clear_xy();
-    bfv_xk1_.clear(); bfv_xk2_.clear(); bfv_yk1_.clear(); bfv_yk2_.clear();
+    ext_batch(level, items, -1, 0, 0, fuse);
+    const bool e_done = fuse.e_slot >= 0;
     // F2: ks.Decompose(t_i) ; out_0 += <h(t_i), v_i> ; out_i += <h(t_i), u>
+    ExtFuse tail;
     {
         std::vector<const u64*> dsrc; std::vector<u64*> ddst;
         f2 = f2 && e_done;
         for (int a = 0; a < n0; ++a) { dsrc.push_back(tbuf + (size_t)a * PQ); if (!f2) ddst.push_back(hoist_slot(2, a).d); }
-        if (f2) ext_f2_src_.assign(dsrc.begin(), dsrc.end());
+        if (f2) tail.f2_src = dsrc;
         else if (n0) decompose_batch(level, dsrc, ddst, true);
     }
     // E: out_j += <h(c1_j), (x1,x2)> together with F2
@@ -301,9 +302,8 @@ void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u
         ExtItem it{hoist_slot(1, a).d, x1, out.d + (size_t)(1 + slot1[a]) * PQ, true}; it.ah2 = hoist_slot(4, a).d; it.bg2 = x2; it.pre = e_done; items.push_back(it);
     }
     join_side(2);
-    try { ext_batch(level, items, 1); } catch (...) { ext_f2_src_.clear(); throw; }        // joins the tensor / Quantize chain before the ModDown accumulates into out
-    ext_f2_src_.clear();
-    bfv_plan_valid_ = false;
+    ext_batch(level, items, 1, 0, 0, tail);        // joins the tensor / Quantize chain before the ModDown accumulates into out
+    bfv_plan_ = BfvPlan{};
     MKHE_HIP(hipGetLastError());
 }
 

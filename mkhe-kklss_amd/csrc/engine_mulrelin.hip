@@ -1,6 +1,5 @@
 // engine_mulrelin.hip -- Context: MulAndRelin[Hoisted] (steps A-F), its split-phase and limb-sharded forms (engine.hip has the tables, pools and the external-product batch)
 #include "engine.h"
-#include <exception>
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -209,7 +208,8 @@ void Context::mr_finish_head(const Ct& op0, const Ct& op1, const u64* y, Ct& out
         if (!p.xkeys.empty()) it.xkey = p.xkeys[a];
         items.push_back(it);
     }
-    if (!p.xkeys.empty()) ext_xout_ = p.xfused;          // x = sum_i d_i (.) h(c0_i) comes out of the same pass over h(c0_i)
+    ExtFuse fuse;
+    if (!p.xkeys.empty()) fuse.xout = p.xfused;          // x = sum_i d_i (.) h(c0_i) comes out of the same pass over h(c0_i)
     // N = 2^15 (round 6): the digits of the t_i never reach HBM -- no Decompose launch below, the tail batch's product kernel transforms them itself
     // (ntt16_f2_kernel) -- when that batch is a merged one (the parts of its products meet at the load of the inverse NTT); step E is either done by
     // then (inside the F1 kernel) or computed by the inner-product kernel in front of it (the sharded finish: x arrives from the other ranks)
@@ -219,18 +219,17 @@ void Context::mr_finish_head(const Ct& op0, const Ct& op1, const u64* y, Ct& out
     const int f2_extra = p.f2_fused ? 2 * n0 * (f2_schedule(n0, level).parts - 1) : 0;
     if (p.f2_fused && p.ykeys.empty()) scratch(c1b_, c1b_words_, (size_t)(2 * n0 + p.n1 + f2_extra) * mtot * N);
     if (!p.ykeys.empty()) {
-        ext_ykeys_ = p.ykeys; ext_yh_ = p.h1;            // ... and y is computed in it
+        fuse.ykeys = p.ykeys; fuse.yh = p.h1;            // ... and y is computed in it
         // ... and step E: the thread holds x[d] and h(c1_j)[d], so <h(c1_j), x> costs it G more accumulators, and x is never stored nor the h(c1_j) read
         // again by the tail batch -- whose c1 slots 2 n0 .. 2 n0 + n1 - 1 (the E items) are filled here: the scratch is sized for the tail now, so
         // that it is the same allocation then (nothing else of a MulAndRelin touches it in between)
         if (will_e) {
             scratch(c1b_, c1b_words_, (size_t)(2 * n0 + p.n1 + f2_extra) * mtot * N);
-            ext_e_slot_ = 2 * n0;
+            fuse.e_slot = 2 * n0;
         }
     }
-    try { ext_batch(level, items); } catch (...) { ext_xout_ = nullptr; ext_ykeys_.clear(); ext_yh_.clear(); ext_e_slot_ = -1; throw; }
-    p.e_done = ext_e_slot_ >= 0;
-    ext_xout_ = nullptr; ext_ykeys_.clear(); ext_yh_.clear(); ext_e_slot_ = -1;
+    ext_batch(level, items, -1, 0, 0, fuse);
+    p.e_done = fuse.e_slot >= 0;
     // F2: h(t_i) ; out_0 += <h(t_i), v_i>_P ; out_i += <h(t_i), u>_P
     p.f2_tbuf = tbuf;
     if (!p.f2_fused) {
@@ -263,10 +262,10 @@ void Context::mr_finish_tail(const Ct& op0, const Ct& op1, const u64* x, const S
         if (p.f2_fused) { items.back().f2_party = a; items.back().f2_key = 1; }
     }
     for (int a = 0; a < n1; ++a) { items.push_back(ExtItem{p.h1[a], x, out.d + (size_t)(1 + p.slot1[a]) * PO, true}); items.back().pre = p.e_done; }
-    if (p.f2_fused) { ext_f2_src_.clear(); for (int a = 0; a < n0; ++a) ext_f2_src_.push_back(p.f2_tbuf + (size_t)a * PO); }
+    ExtFuse fuse;
+    if (p.f2_fused) for (int a = 0; a < n0; ++a) fuse.f2_src.push_back(p.f2_tbuf + (size_t)a * PO);
     if (p.x_pending) { join_side(2); p.x_pending = false; }
-    if (p.f2_staged) { ext_staged_.clear(); for (int a = 0; a < n0; ++a) ext_staged_.push_back(hoist_slot(2, a).d); }
-    struct Unstage { Context* c; ~Unstage() { c->ext_staged_.clear(); c->ext_f2_src_.clear(); if (std::uncaught_exceptions()) c->staged_open_.clear(); } } unstage{this};
+    if (p.f2_staged) for (int a = 0; a < n0; ++a) fuse.staged.push_back(hoist_slot(2, a).d);
     if (p.tens) {
         // the tensor term of every output slot rides on the first product that goes there (see mr_prepare)
         std::vector<const u64*> seen;
@@ -277,9 +276,9 @@ void Context::mr_finish_tail(const Ct& op0, const Ct& op1, const u64* x, const S
         }
         if ((int)seen.size() != 1 + out.n) throw Error("mkhe: internal: an output slot without an external product");
         join_side(1);                  // the tensor chain, before the inverse NTT that sums it in
-        ext_batch(level, items);
+        ext_batch(level, items, -1, 0, 0, fuse);
     } else
-    ext_batch(level, items, 1);        // joins the tensor chain before the ModDown accumulates into out
+    ext_batch(level, items, 1, 0, 0, fuse);        // joins the tensor chain before the ModDown accumulates into out
     p.valid = false; p.head_done = false;
     MKHE_HIP(hipGetLastError());
 }
@@ -295,12 +294,12 @@ void Context::mr_finish(const Ct& op0, const Ct& op1, const u64* x, const u64* y
 // reduction point of the modulus's schedule; 0, the default: every pass the same, the cuts then fall on whole and half groups).  A workgroup's
 // passes of one (party, slot, half) are a run = one part of that group's two products; parts = the most any group is cut into (the inverse NTT adds
 // them at its load: VI_SUMS), a group cut into fewer has its last run zero the others.  parts = 0: no schedule within the kernel's limits.
-bool Context::f2_fused_ok(int level, int n0, int n1) const {
+bool Context::f2_fused_ok(int level, int n0, int n1) {
     (void)n1;
     if (logN != 15 || alpha != 1 || masked_ || !d_psi31 || !d_psi31n || mall > NTT_MAX_SLOTS || h16_gap_) return false;
     if (!ntt16_f2_ok(logN, n0, beta(level), nslots_qp(level))) return false;
     if (ext_merge_members(level) < 2) return false;
-    return const_cast<Context*>(this)->f2_schedule(n0, level).parts >= 1;
+    return f2_schedule(n0, level).parts >= 1;
 }
 // the cut itself, a pure function of the shape (also behind mkhe_f2_schedule_probe: tests/test_f2_schedule.py checks on the CPU that every pass of
 // every shape is dealt exactly once).  weights: per limb slot; segs: G * F2_SEGS entries.  Returns the number of workgroups, parts in *parts_out;

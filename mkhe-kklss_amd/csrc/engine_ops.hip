@@ -42,6 +42,7 @@ void Context::rotate_core(const Ct& in, const Swk* const* hoist, const Swk* cons
     }
     std::vector<const u64*> h(n);
     bool f2 = false;
+    ExtFuse fuse;
     {
         std::vector<const u64*> dsrc; std::vector<u64*> ddst;
         for (int a = 0; a < n; ++a) {
@@ -53,9 +54,9 @@ void Context::rotate_core(const Ct& in, const Swk* const* hoist, const Swk* cons
         // transform inside the product kernel; N = 2^15 launches that fill the chip never store them at all: ntt16_f2_kernel, as step F2 of MulAndRelin)
         f2 = !hoist && n >= 2 && f2_fused_ok(level, n, 0);
         const bool stage = !f2 && !hoist && ext_fused_ok(level, (int)dsrc.size());
-        if (f2) { ext_f2_src_.assign(dsrc.begin(), dsrc.end()); for (int a = 0; a < n; ++a) h[a] = dsrc[a]; }
+        if (f2) { fuse.f2_src = dsrc; h = dsrc; }
         else if (!dsrc.empty()) decompose_batch(level, dsrc, ddst, true, stage);
-        if (stage) ext_staged_.assign(ddst.begin(), ddst.end());
+        if (stage) fuse.staged.assign(ddst.begin(), ddst.end());
     }
     std::vector<ExtItem> items;
     for (int a = 0; a < n; ++a) {
@@ -65,8 +66,7 @@ void Context::rotate_core(const Ct& in, const Swk* const* hoist, const Swk* cons
         items.push_back(ExtItem{h[a], crs.d, tmp + (size_t)(1 + a) * PO, false});
         if (f2) { items.back().f2_party = a; items.back().f2_key = 1; }
     }
-    try { ext_batch(level, items, -1, 0, galEl); } catch (...) { ext_staged_.clear(); ext_f2_src_.clear(); staged_open_.clear(); throw; }
-    ext_staged_.clear(); ext_f2_src_.clear();
+    ext_batch(level, items, -1, 0, galEl, fuse);
     MKHE_HIP(hipGetLastError());
 }
 
@@ -100,9 +100,10 @@ void Context::conjugate(u64 galEl, const Ct& in, const Swk* const* ck, const Swk
     }
     const bool f2 = n >= 2 && f2_fused_ok(level, n, 0);           // (as Rotate: the digits of the permuted polynomials stay in registers)
     const bool stage = !f2 && ext_fused_ok(level, n);
-    if (f2) ext_f2_src_.assign(dsrc.begin(), dsrc.end());
+    ExtFuse fuse;
+    if (f2) fuse.f2_src = dsrc;
     else decompose_batch(level, dsrc, ddst, true, stage);
-    if (stage) ext_staged_.assign(ddst.begin(), ddst.end());
+    if (stage) fuse.staged.assign(ddst.begin(), ddst.end());
     std::vector<ExtItem> items;
     for (int a = 0; a < n; ++a) {
         items.push_back(ExtItem{f2 ? dsrc[a] : ddst[a], ck[a]->d, out.d, true});
@@ -111,8 +112,7 @@ void Context::conjugate(u64 galEl, const Ct& in, const Swk* const* ck, const Swk
         items.push_back(ExtItem{f2 ? dsrc[a] : ddst[a], crs.d, out.d + (size_t)(1 + a) * PO, false});
         if (f2) { items.back().f2_party = a; items.back().f2_key = 1; }
     }
-    try { ext_batch(level, items); } catch (...) { ext_staged_.clear(); ext_f2_src_.clear(); staged_open_.clear(); throw; }
-    ext_staged_.clear(); ext_f2_src_.clear();
+    ext_batch(level, items, -1, 0, 0, fuse);
     MKHE_HIP(hipGetLastError());
 }
 
