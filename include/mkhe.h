@@ -370,6 +370,24 @@ int  mkhe_bfv_keygen_relin_key(mkhe_ctx* ctx, const void* dev_sk, const void* de
  * the seed derive the same CRS. */
 int  mkhe_crs_expand(mkhe_ctx* ctx, uint64_t seed, int32_t idx, mkhe_swk* out);
 
+/* ==== public-key encryption and decryption ==========================================================
+ * mkrlwe/encryptor.go:55-118 (ciphertexts are coefficient domain: the branch :95-112) and mkrlwe/decryptor.go:26-66, which
+ * mkckks/{encryptor,decryptor}.go and mkbfv/{encryptor,decryptor}.go wrap; ring Q, on mkhe_ctx_create_bfv contexts too.
+ * As in key generation the small-norm samples come from the caller (host int32) and are wiped from the device
+ * scratch behind their last use.  Public keys are the device buffers of mkhe_keygen_public_key, secret keys those of
+ * mkhe_keygen_secret; raw device buffers must be 16-byte aligned (mkhe_buf_alloc's are). */
+/* Encrypt encryptor.go:55-118 for `count` plaintexts under one public key as one launch set: dev_pt = uint64[count][level+1][N],
+ * coefficient domain or (pt_is_ntt, :107-109) NTT domain; samples = int32[count][3][N], per plaintext u (ternary), e0, e1
+ * (Gaussian) in this order; out[b] = a ciphertext over exactly one party with level+1 limbs: c0 = u*pk0 + e0 + pt, c1 = u*pk1 + e1 */
+int  mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt,
+                  const int32_t* samples, mkhe_ct* const* out);
+/* PartialDecrypt decryptor.go:26-43: slot = 1 .. n names the party (the ciphertext slot of its polynomial); out is over the ids of
+ * `in` without that one, at the same level: out[0] = in[0] + c_slot*sk (one ring.Add), the other polynomials are copied */
+int  mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out);
+/* Decrypt decryptor.go:48-66: dev_sk[i] = the secret of the party at slot 1+i; dev_pt_out = uint64[limbs][N], canonical residues,
+ * coefficient domain */
+int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, void* dev_pt_out);
+
 /* ---- measurement support (no reference counterpart): HIP-event timing per kernel class on the
  *      context stream, one record per kernel launch.  Classes (mkhe_prof_name gives the kernel symbol
  *      each class corresponds to in a rocprofv3 kernel trace). */

@@ -315,6 +315,64 @@ class KeyGenerator {
         return it->second;
     }
 };
+
+// mkrlwe.SecretKeySet keys.go:70-94 (the keys stay with their owner: the set only names them)
+struct SecretKeySet {
+    std::map<std::string, const SecretKey*> Value;
+    void AddSecretKey(const SecretKey& sk) { Value[sk.ID] = &sk; }
+    void DelSecretKey(const std::string& id) { Value.erase(id); }
+    const SecretKey& GetSecretKey(const std::string& id) const {
+        auto it = Value.find(id);
+        if (it == Value.end()) throw Error("cannot GetPublicKey: there is no public key with given id");                 // keys.go:91
+        return *it->second;
+    }
+};
+
+// mkrlwe.Encryptor (encryptor.go:8-52) on the device.  Like the samples of KeyGenerator, u (ternary) and e0, e1 (Gaussian) are
+// arguments: samples = int32[count][3][N] from the caller's CSPRNG.  Plaintexts are device buffers uint64[count][level+1][N].
+class Encryptor {
+  public:
+    explicit Encryptor(Parameters& p) : params(p) {}
+    void Encrypt(const void* dev_pt, const PublicKey& pk, Ciphertext& ctOut, const int32_t* samples, bool ptIsNTT = false) {   // encryptor.go:55-118
+        if (ctOut.ids.size() != 1 || ctOut.ids[0] != pk.ID) throw Error("Cannot Encrypt: ctOut must be a ciphertext over the id of pk alone");
+        mkhe_ct* out[1] = {ctOut.h};
+        check(mkhe_encrypt(params.ctx, ctOut.Level(), 1, pk.Value.d, dev_pt, ptIsNTT ? 1 : 0, samples, out));
+    }
+    // count plaintexts under one public key as one engine call
+    std::vector<std::shared_ptr<Ciphertext>> EncryptBatch(int level, int count, const void* dev_pt, const PublicKey& pk, const int32_t* samples, bool ptIsNTT = false) {
+        std::vector<std::shared_ptr<Ciphertext>> cts;
+        std::vector<mkhe_ct*> out;
+        for (int b = 0; b < count; ++b) { cts.push_back(std::make_shared<Ciphertext>(params, IDSet{pk.ID}, level, false)); out.push_back(cts.back()->h); }
+        check(mkhe_encrypt(params.ctx, level, count, pk.Value.d, dev_pt, ptIsNTT ? 1 : 0, samples, out.data()));
+        return cts;
+    }
+    Parameters& params;
+};
+
+// mkrlwe.Decryptor (decryptor.go:8-23) on the device
+class Decryptor {
+  public:
+    explicit Decryptor(Parameters& p) : params(p) {}
+    // decryptor.go:26-43; the Go version works in place and deletes ct.Value[sk.ID]: here the result is a new ciphertext over the remaining ids
+    std::shared_ptr<Ciphertext> PartialDecrypt(const Ciphertext& ct, const SecretKey& sk) {
+        IDSet rest = ct.IDSet_();
+        rest.erase(sk.ID);
+        auto out = std::make_shared<Ciphertext>(params, rest, ct.Level(), false);
+        check(mkhe_partial_decrypt(params.ctx, ct.h, ct.slot(sk.ID), sk.Value.d, out->h));
+        return out;
+    }
+    // decryptor.go:48-66: dev_pt_out = uint64[level+1][N], canonical residues, coefficient domain
+    void Decrypt(const Ciphertext& ct, const SecretKeySet& skSet, void* dev_pt_out) {
+        std::vector<const void*> sks;
+        for (auto& id : ct.ids) {
+            auto it = skSet.Value.find(id);
+            if (it == skSet.Value.end()) throw Error("Cannot Decrypt: there is a missing secretkey");                     // decryptor.go:61-63
+            sks.push_back(it->second->Value.d);
+        }
+        check(mkhe_decrypt(params.ctx, ct.h, sks.data(), dev_pt_out));
+    }
+    Parameters& params;
+};
 }  // namespace mkrlwe
 
 namespace mkckks {

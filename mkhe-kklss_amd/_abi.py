@@ -108,6 +108,9 @@ SIGNATURES = {
     "mkhe_bfv_keygen_switching_key": (C.c_int, [vp, vp, u64p, s32p, vp]),
     "mkhe_bfv_keygen_relin_key": (C.c_int, [vp, vp, vp, u64p, u64p, s32p, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mkhe_crs_expand": (C.c_int, [vp, C.c_uint64, C.c_int32, vp]),
+    "mkhe_encrypt": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, s32p, vpp]),
+    "mkhe_partial_decrypt": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "mkhe_decrypt": (C.c_int, [vp, vp, vpp, vp]),
     "mkhe_prof_enable": (C.c_int, [vp, C.c_int]),
     "mkhe_ntt_trace": (C.c_int, [vp, vp]),
     "mkhe_set_overlap": (C.c_int, [vp, C.c_int]),

@@ -616,6 +616,48 @@ int mkhe_crs_expand(mkhe_ctx* ctx, uint64_t seed, int32_t idx, mkhe_swk* out) {
     MKHE_TRY({ mark(ctx, out); if (!out) throw Error("mkhe_crs_expand: null argument"); need(ctx)->crs_expand(seed, idx, out->s.d); })
 }
 
+// ---- public-key encryption / decryption (encdec.hip)
+static void need_aligned(const void* p, const char* what) {
+    if ((uintptr_t)p & 15) throw Error(std::string(what) + ": device buffers must be 16-byte aligned");
+}
+int mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt, const int32_t* samples, mkhe_ct* const* out) {
+    MKHE_TRY({
+        Context* c = need(ctx);
+        if (!dev_pk || !dev_pt || !samples || !out) throw Error("mkhe_encrypt: null argument");
+        if (level < 0 || level >= c->nq) throw Error("mkhe_encrypt: level out of range");
+        if (count < 1 || count > 65535) throw Error("mkhe_encrypt: count must be 1 .. 65535");
+        need_aligned(dev_pk, "mkhe_encrypt"); need_aligned(dev_pt, "mkhe_encrypt");
+        auto o = ct_list_out(ctx, out, count, "mkhe_encrypt");
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            if (o[b]->n != 1) throw Error("mkhe_encrypt: every out must be a ciphertext over exactly one party");
+            if (o[b]->limbs != level + 1) throw Error("mkhe_encrypt: every out must have level+1 limbs");
+            d[b] = o[b]->d;
+        }
+        c->encrypt(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, samples, d.data());
+    })
+}
+int mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out) {
+    MKHE_TRY({ mark(ctx, in, out);
+        if (!in || !dev_sk || !out) throw Error("mkhe_partial_decrypt: null argument");
+        need_aligned(dev_sk, "mkhe_partial_decrypt");
+        need(ctx)->partial_decrypt(in->c, slot, (const u64*)dev_sk, out->c);
+    })
+}
+int mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, void* dev_pt_out) {
+    MKHE_TRY({ mark(ctx, ct);
+        if (!ct || !dev_pt_out || (ct->c.n > 0 && !dev_sk)) throw Error("mkhe_decrypt: null argument");
+        need_aligned(dev_pt_out, "mkhe_decrypt");
+        std::vector<const u64*> sk(ct->c.n);
+        for (int i = 0; i < ct->c.n; ++i) {
+            if (!dev_sk[i]) throw Error("mkhe_decrypt: null secret key in the per-party list");
+            need_aligned(dev_sk[i], "mkhe_decrypt");
+            sk[i] = (const u64*)dev_sk[i];
+        }
+        need(ctx)->decrypt(ct->c, sk.data(), (u64*)dev_pt_out);
+    })
+}
+
 // ---- mkbfv
 int mkhe_ctx_create_bfv(mkhe_ctx** out, int logN, const uint64_t* Q, const uint64_t* QMul, int nQ,
                         const uint64_t* P, int nP, int gamma, uint64_t T, int device) {

@@ -1,0 +1,126 @@
+// encdec.hip -- Context methods for public-key encryption and decryption (mkrlwe/encryptor.go:55-118, mkrlwe/decryptor.go:26-66;
+// mkckks/encryptor.go, mkckks/decryptor.go, mkbfv/encryptor.go and mkbfv/decryptor.go call exactly these).
+//
+// Ciphertexts of this engine are coefficient domain, so Encrypt is the reference's else branch (encryptor.go:95-112).  B plaintexts under
+// one public key are ONE launch set over the work buffer w [3][B][L][N] (L = level + 1):
+//   small_expand of the B polynomials u into w[2]; one forward NTT of B*L limbs; encrypt_mul (w[0], w[1] <- MForm(NTT(u)) * pk0, pk1);
+//   one inverse NTT of 2*B*L limbs (3*B*L when the plaintexts arrive in the NTT domain: they ride along in w[2]); encrypt_finish.
+// Decrypt of a ciphertext over k parties: ONE forward NTT of the k party polynomials, decrypt_mac (all k products summed in the NTT
+// domain), one inverse NTT of a single polynomial, decrypt_finish.  PartialDecrypt is the same with k = 1 and a plain ring.Add at the end.
+// The samples u, e0, e1 are drawn on the host (like the secrets and errors of key generation) and wiped from the device scratch behind
+// their last use, and so is everything computed from u alone.
+#include "engine.h"
+
+namespace mkhe {
+
+// v as a kernel-argument table, or -- longer than ED_INLINE -- staged at ed_tab_ + tab_offset (the caller has sized ed_tab_)
+EdTable Context::ed_table(const std::vector<const u64*>& v, size_t tab_offset) {
+    EdTable t{};
+    if (v.size() <= (size_t)ED_INLINE) { for (size_t i = 0; i < v.size(); ++i) t.p[i] = v[i]; return t; }
+    if (tab_offset + v.size() > ed_tab_n_) throw Error("mkhe: pointer table scratch too small");
+    MKHE_HIP(hipMemcpyAsync(ed_tab_ + tab_offset, v.data(), v.size() * sizeof(const u64*), hipMemcpyHostToDevice, stream));
+    sync();                                             // v is pageable and about to go out of scope
+    t.dev = ed_tab_ + tab_offset;
+    return t;
+}
+
+static void ed_grow_tab(const u64**& tab, size_t& have, size_t want, hipStream_t st) {
+    if (have >= want) return;
+    if (tab) { MKHE_HIP(hipStreamSynchronize(st)); MKHE_HIP(hipFree(tab)); tab = nullptr; have = 0; }
+    MKHE_HIP(hipMalloc(&tab, want * sizeof(const u64*)));
+    have = want;
+}
+
+void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const int32_t* samples, u64* const* outs) {
+    check_level(level);
+    if (masked_) throw Error("mkhe_encrypt: not available on a context that owns a subset of the moduli");
+    const int L = level + 1;
+    const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
+    u64* w = scratch(ed_w_, ed_w_words_, 3 * pw);
+    if (ed_small_n_ < 4 * sn) {
+        if (ed_small_) { MKHE_HIP(hipStreamSynchronize(stream)); MKHE_HIP(hipFree(ed_small_)); ed_small_ = nullptr; ed_small_n_ = 0; }
+        MKHE_HIP(hipMalloc(&ed_small_, 4 * sn * sizeof(int32_t)));
+        ed_small_n_ = 4 * sn;
+    }
+    ed_grow_tab(ed_tab_, ed_tab_n_, (size_t)count, stream);
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0);
+    // the samples as given, [count][3][N], for encrypt_finish; behind them the count rows of u gathered into [count][N] for small_expand
+    int32_t* du = ed_small_ + 3 * sn;
+    MKHE_HIP(hipMemcpyAsync(ed_small_, samples, 3 * sn * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    MKHE_HIP(hipMemcpy2DAsync(du, (size_t)N * sizeof(int32_t), samples, 3 * (size_t)N * sizeof(int32_t), (size_t)N * sizeof(int32_t), count,
+                              hipMemcpyHostToDevice, stream));
+    sync();                                             // the host array may be pageable: do not return before it is consumed
+    {
+        ProfScope ps(this, PROF_OTHER, (double)count * N * (4.0 + 8.0 * L));
+        launch_small_expand(w + 2 * pw, du, d_mods, count, L, N, s_);
+    }
+    MKHE_HIP(hipMemsetAsync(du, 0, sn * sizeof(int32_t), s_));
+    ntt(w + 2 * pw, w + 2 * pw, count, L, 0, false, false);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (count * (pt_is_ntt ? 5.0 : 4.0) + 2.0));
+        launch_encrypt_mul(count, w, pk, pt_is_ntt ? pt : nullptr, d_mods, L, mtot, N, s_);
+    }
+    ntt(w, w, (pt_is_ntt ? 3 : 2) * count, L, 0, true, false);
+    {
+        ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * L * 5.0));
+        launch_encrypt_finish(count, ot, w, ed_small_, pt_is_ntt ? nullptr : pt, d_mods, L, N, s_);
+    }
+    MKHE_HIP(hipMemsetAsync(ed_small_, 0, 3 * sn * sizeof(int32_t), s_));
+    MKHE_HIP(hipMemsetAsync(w, 0, 2 * pw * sizeof(u64), s_));             // u * pk1 gives u away: it does not outlive the call
+    MKHE_HIP(hipGetLastError());
+}
+
+// acc [limbs][N] <- sum_i NTT-domain products of the k polynomials at ch [k][limbs][N] with the secrets sks[i]
+void Context::ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc) {
+    std::vector<const u64*> c(k), s(sks, sks + k);
+    for (int i = 0; i < k; ++i) c[i] = ch + (size_t)i * limbs * N;
+    ed_grow_tab(ed_tab_, ed_tab_n_, 2 * (size_t)k, stream);
+    const EdTable ct = ed_table(c, 0), st = ed_table(s, (size_t)k);
+    ProfScope ps(this, PROF_OTHER, 8.0 * N * limbs * (2.0 * k + 1.0));
+    launch_decrypt_mac(1, k, acc, ct, st, d_mods, limbs, N, s_);
+}
+
+void Context::partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out) {
+    if (masked_) throw Error("mkhe_partial_decrypt: not available on a context that owns a subset of the moduli");
+    if (slot < 1 || slot > in.n) throw Error("mkhe_partial_decrypt: slot out of range (party slots are 1 .. n)");
+    if (out.limbs != in.limbs) throw Error("mkhe_partial_decrypt: out must be at the level of in");
+    std::vector<int> rest(in.ids);
+    rest.erase(rest.begin() + (slot - 1));
+    if (out.n != in.n - 1 || out.ids != rest) throw Error("mkhe_partial_decrypt: out must be over the ids of in without the one at slot");
+    const int L = in.limbs;
+    const size_t pw = (size_t)L * N;
+    u64* w = scratch(ed_w_, ed_w_words_, 2 * pw);
+    ntt(in.d + (size_t)slot * pw, w, 1, L, 0, false, false);
+    ed_mac(1, w, &sk, L, w + pw);
+    ntt(w + pw, w + pw, 1, L, 0, true, false);
+    {
+        ProfScope ps(this, PROF_OTHER, 24.0 * N * L);
+        launch_decrypt_finish(1, out.d, 0, in.d, 0, w + pw, d_mods, L, N, false, s_);
+    }
+    if (slot > 1) MKHE_HIP(hipMemcpyAsync(out.d + pw, in.d + pw, (size_t)(slot - 1) * pw * sizeof(u64), hipMemcpyDeviceToDevice, s_));
+    if (slot < in.n) MKHE_HIP(hipMemcpyAsync(out.d + (size_t)slot * pw, in.d + (size_t)(slot + 1) * pw, (size_t)(in.n - slot) * pw * sizeof(u64),
+                                             hipMemcpyDeviceToDevice, s_));
+    MKHE_HIP(hipMemsetAsync(w + pw, 0, pw * sizeof(u64), s_));            // the decryption share stays in the caller's ciphertext only
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::decrypt(const Ct& ct, const u64* const* sks, u64* pt_out) {
+    if (masked_) throw Error("mkhe_decrypt: not available on a context that owns a subset of the moduli");
+    const int k = ct.n, L = ct.limbs;
+    const size_t pw = (size_t)L * N;
+    u64* w = scratch(ed_w_, ed_w_words_, (size_t)(k + 1) * pw);
+    u64* acc = w + (size_t)k * pw;
+    if (k > 0) {
+        ntt(ct.d + pw, w, k, L, 0, false, false);
+        ed_mac(k, w, sks, L, acc);
+        ntt(acc, acc, 1, L, 0, true, false);
+    } else MKHE_HIP(hipMemsetAsync(acc, 0, pw * sizeof(u64), s_));
+    {
+        ProfScope ps(this, PROF_OTHER, 24.0 * N * L);
+        launch_decrypt_finish(1, pt_out, 0, ct.d, 0, acc, d_mods, L, N, true, s_);
+    }
+    MKHE_HIP(hipMemsetAsync(acc, 0, pw * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
+}
+
+}  // namespace mkhe

@@ -1,0 +1,116 @@
+// encdec_kernels.hip -- see encdec_kernels.h.  Streaming kernels: 256 threads, grid.x strides over PAIRS of coefficients (one 16-byte
+// access per lane), grid.y = limb, grid.z = item of the batch; per-modulus constants are wave-uniform (SGPRs).  No LDS.
+#include "encdec_kernels.h"
+
+namespace mkhe {
+
+constexpr int ED_THREADS = 256;
+static int ed_bx(int N) { return (N / 2 + ED_THREADS - 1) / ED_THREADS; }
+
+typedef ulonglong2 u64x2;
+__device__ __forceinline__ u64x2 ld2(const u64* p, long pair) { return reinterpret_cast<const u64x2*>(p)[pair]; }
+__device__ __forceinline__ void st2(u64* p, long pair, u64 a, u64 b) { reinterpret_cast<u64x2*>(p)[pair] = u64x2{a, b}; }
+__device__ __forceinline__ const u64* ed_entry(const EdTable& t, int i) { return t.dev ? t.dev[i] : t.p[i]; }
+// ExtendBasisSmallNormAndCenter of one sample: e >= 0 ? e : q - |e|
+__device__ __forceinline__ u64 small_q(i32 e, u64 q) { return e < 0 ? q - (u64)(-(i64)e) : (u64)e; }
+
+__global__ void __launch_bounds__(ED_THREADS) encrypt_mul_kernel(int count, u64* w, const u64* pk, const u64* pt_ntt, const Mod* mods, int limbs,
+                                                                 int mtot, int N) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const Mod md = mods[j];
+    const u64 q = md.q;
+    const long half = N / 2, slot = (long)count * limbs * half;          // in pairs
+    const long row = ((long)b * limbs + j) * half;
+    const u64* pk0 = pk + (long)j * N;
+    const u64* pk1 = pk + ((long)mtot + j) * N;
+    for (long n = (long)blockIdx.x * ED_THREADS + threadIdx.x; n < half; n += (long)gridDim.x * ED_THREADS) {
+        const u64x2 uh = ld2(w, 2 * slot + row + n), a0 = ld2(pk0, n), a1 = ld2(pk1, n);
+        const u64 Ux = mont_mul(uh.x, md.r2, q, md.ninv32), Uy = mont_mul(uh.y, md.r2, q, md.ninv32);       // MForm
+        st2(w, row + n, mont_mul(Ux, a0.x, q, md.ninv32), mont_mul(Uy, a0.y, q, md.ninv32));
+        st2(w, slot + row + n, mont_mul(Ux, a1.x, q, md.ninv32), mont_mul(Uy, a1.y, q, md.ninv32));
+        if (pt_ntt) { const u64x2 p = ld2(pt_ntt, row + n); st2(w, 2 * slot + row + n, p.x, p.y); }
+        else st2(w, 2 * slot + row + n, 0, 0);
+    }
+}
+void launch_encrypt_mul(int count, u64* w, const u64* pk, const u64* pt_ntt, const Mod* mods, int limbs, int mtot, int N, hipStream_t st) {
+    hipLaunchKernelGGL(encrypt_mul_kernel, dim3(ed_bx(N), limbs, count), dim3(ED_THREADS), 0, st, count, w, pk, pt_ntt, mods, limbs, mtot, N);
+}
+
+__global__ void __launch_bounds__(ED_THREADS) encrypt_finish_kernel(int count, EdTable out, const u64* w, const i32* smp, const u64* pt_coeff,
+                                                                    const Mod* mods, int limbs, int N) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const u64 q = mods[j].q;
+    const long half = N / 2, slot = (long)count * limbs * half;
+    const long row = ((long)b * limbs + j) * half;
+    const u64* pt = pt_coeff ? pt_coeff : w + 4 * slot;                    // w[2] in words
+    const int2* e0 = reinterpret_cast<const int2*>(smp + ((long)b * 3 + 1) * N);
+    const int2* e1 = reinterpret_cast<const int2*>(smp + ((long)b * 3 + 2) * N);
+    u64* ct = const_cast<u64*>(ed_entry(out, b));
+    u64* c0 = ct + (long)j * N;
+    u64* c1 = ct + ((long)limbs + j) * N;
+    for (long n = (long)blockIdx.x * ED_THREADS + threadIdx.x; n < half; n += (long)gridDim.x * ED_THREADS) {
+        const u64x2 t0 = ld2(w, row + n), t1 = ld2(w, slot + row + n), p = ld2(pt, row + n);
+        const int2 s0 = e0[n], s1 = e1[n];
+        st2(c0, n, csub(csub(t0.x + small_q(s0.x, q), q) + p.x, q), csub(csub(t0.y + small_q(s0.y, q), q) + p.y, q));
+        st2(c1, n, csub(t1.x + small_q(s1.x, q), q), csub(t1.y + small_q(s1.y, q), q));
+    }
+}
+void launch_encrypt_finish(int count, const EdTable& out, const u64* w, const i32* smp, const u64* pt_coeff, const Mod* mods, int limbs, int N, hipStream_t st) {
+    hipLaunchKernelGGL(encrypt_finish_kernel, dim3(ed_bx(N), limbs, count), dim3(ED_THREADS), 0, st, count, out, w, smp, pt_coeff, mods, limbs, N);
+}
+
+// 128-bit accumulator += a * b
+__device__ __forceinline__ void mac128(u64 a, u64 b, u64& hi, u64& lo) {
+    u64 h, l;
+    mul64x64(a, b, h, l);
+    lo += l;
+    hi += h + (lo < l ? 1 : 0);
+}
+// (hi * 2^64 + lo) * 2^-64 mod q, canonical, for hi < 2q (k <= 32 products of residues below q < 2^60: the sum is below 32 q^2 < 2q * 2^64).
+// m = lo * q^-1 mod 2^64 makes the low word of T - m*q vanish, so (T - m*q) / 2^64 = hi - mulhi(m, q) in (-q, 2q).
+__device__ __forceinline__ u64 redc128(u64 hi, u64 lo, const Mod& md) {
+    const u64 mh = mulhi64(lo * md.qinv, md.q);
+    return hi < mh ? hi + md.q - mh : csub(hi - mh, md.q);
+}
+
+__global__ void __launch_bounds__(ED_THREADS) decrypt_mac_kernel(int k, u64* acc, EdTable ch, EdTable sk, const Mod* mods, int limbs, int N) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const Mod md = mods[j];
+    const long half = N / 2;
+    u64* dst = acc + ((long)b * limbs + j) * N;
+    for (long n = (long)blockIdx.x * ED_THREADS + threadIdx.x; n < half; n += (long)gridDim.x * ED_THREADS) {
+        u64 hx = 0, lx = 0, hy = 0, ly = 0;
+        for (int i = 0; i < k; ++i) {
+            const u64x2 c = ld2(ed_entry(ch, b * k + i) + (long)j * N, n), s = ld2(ed_entry(sk, b * k + i) + (long)j * N, n);
+            mac128(c.x, s.x, hx, lx);
+            mac128(c.y, s.y, hy, ly);
+        }
+        st2(dst, n, redc128(hx, lx, md), redc128(hy, ly, md));
+    }
+}
+void launch_decrypt_mac(int count, int k, u64* acc, const EdTable& ch, const EdTable& sk, const Mod* mods, int limbs, int N, hipStream_t st) {
+    hipLaunchKernelGGL(decrypt_mac_kernel, dim3(ed_bx(N), limbs, count), dim3(ED_THREADS), 0, st, k, acc, ch, sk, mods, limbs, N);
+}
+
+__global__ void __launch_bounds__(ED_THREADS) decrypt_finish_kernel(u64* out, long out_stride, const u64* c0, long c0_stride, const u64* acc,
+                                                                    const Mod* mods, int limbs, int N, int reduce) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const u64 q = mods[j].q;
+    const long half = N / 2;
+    const u64* a = acc + ((long)b * limbs + j) * N;
+    const u64* c = c0 + b * c0_stride + (long)j * N;
+    u64* o = out + b * out_stride + (long)j * N;
+    for (long n = (long)blockIdx.x * ED_THREADS + threadIdx.x; n < half; n += (long)gridDim.x * ED_THREADS) {
+        const u64x2 x = ld2(c, n), y = ld2(a, n);
+        u64 vx = csub(x.x + y.x, q), vy = csub(x.y + y.y, q);
+        if (reduce) { vx = csub(csub(vx, q), q); vy = csub(csub(vy, q), q); }
+        st2(o, n, vx, vy);
+    }
+}
+void launch_decrypt_finish(int count, u64* out, long out_stride, const u64* c0, long c0_stride, const u64* acc, const Mod* mods, int limbs, int N,
+                           bool reduce, hipStream_t st) {
+    hipLaunchKernelGGL(decrypt_finish_kernel, dim3(ed_bx(N), limbs, count), dim3(ED_THREADS), 0, st, out, out_stride, c0, c0_stride, acc, mods, limbs, N,
+                       reduce ? 1 : 0);
+}
+
+}  // namespace mkhe

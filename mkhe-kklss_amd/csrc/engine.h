@@ -18,6 +18,7 @@
 #include "ntt_kernels.h"
 #include "poly_kernels.h"
 #include "keygen_kernels.h"
+#include "encdec_kernels.h"
 
 namespace mkhe {
 
@@ -233,6 +234,12 @@ class Context {
                               const u64* crs_a1, const u64* crs_a2, const u64* crs_u, u64* b1, u64* b2, u64* d1, u64* d2, u64* v);
     void crs_expand(u64 seed, int32_t idx, u64* out);                                          // params.go:47-59,91-98
 
+    // ---- public-key encryption and decryption (encdec.hip; mkrlwe/encryptor.go:55-118, decryptor.go:26-66), ring Q at `level`.
+    // samples: host int32 [count][3][N] (u, e0, e1); pk: device [2][nq+np][N]; pt: device [count][level+1][N]; outs[b]: [2][level+1][N]
+    void encrypt(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const int32_t* samples, u64* const* outs);
+    void partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out);                      // decryptor.go:26-43
+    void decrypt(const Ct& ct, const u64* const* sks, u64* pt_out);                            // decryptor.go:48-66
+
     bool overlap = true;               // false: everything on the main stream (clean per-kernel timings)
     u64* ntt_trace = nullptr;          // diagnostic buffer handed to the forward NTT kernels (mkhe_ntt_trace)
     // stream-ordered buffer cache for ciphertext / switching-key handles: freeing a handle does not
@@ -311,6 +318,12 @@ class Context {
     // (P on the limbs of digit i, keygen.go:288-323), 2 the constants last uploaded with kg_upload_g
     void kg_key(const int32_t* e, int gadget, const u64* skA, const u64* crs, const u64* skB, int sign, bool neg, u64* out);
     void kg_upload_g(const u64* g_plain);
+    // encryption / decryption scratch: work polynomials, uploaded samples, staged pointer tables (encdec.hip)
+    u64* ed_w_ = nullptr;  size_t ed_w_words_ = 0;
+    int32_t* ed_small_ = nullptr; size_t ed_small_n_ = 0;
+    const u64** ed_tab_ = nullptr; size_t ed_tab_n_ = 0;
+    EdTable ed_table(const std::vector<const u64*>& v, size_t tab_offset);
+    void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
 
     u64* scratch(u64*& p, size_t& have, size_t want);
     Swk& hoist_slot(int which, int idx);

@@ -254,3 +254,66 @@ class Evaluator:
 
 def NewEvaluator(params):
     return Evaluator(params)
+
+
+# ---- encryptor, decryptor (mkbfv/encryptor.go, mkbfv/decryptor.go); plaintexts are RNS polynomials over Q.  Slot batching over Z_T
+# (lattigo's bfv.Encoder) is not mirrored: ScaleUp / ScaleDown below are the coefficient-wise halves of EncodeInt / DecodeInt.
+def _q_product(params):
+    Q = 1
+    for q in params.Q:
+        Q *= q
+    return Q
+
+
+def ScaleUp(m, params):
+    """coefficients over Z_T -> RNS polynomial uint64 [nQ][N]: round(Q/T * (m mod T)), exact in Python integers"""
+    Q, T = _q_product(params), params.T()
+    c = ((np.asarray(m).astype(object) % T) * Q + T // 2) // T
+    return np.stack([np.array([int(v) for v in c % q], dtype=np.uint64) for q in params.Q])
+
+
+def ScaleDown(poly, params):
+    """RNS polynomial [nQ][N] -> round(T/Q * x) mod T with x the centred CRT lift, centred in (-T/2, T/2], int64"""
+    Q, T = _q_product(params), params.T()
+    poly = np.asarray(poly, dtype=np.uint64)
+    x = np.zeros(poly.shape[1], dtype=object)
+    for l, q in enumerate(params.Q):
+        Mi = Q // q
+        x = x + poly[l].astype(object) * (Mi * pow(Mi, -1, q))
+    x = x % Q
+    out = []
+    for v in x:
+        v = v - Q if v > Q // 2 else v
+        r = ((v * T * 2 + Q) // (2 * Q)) % T
+        out.append(r - T if r > T // 2 else r)
+    return np.array(out, dtype=np.int64)
+
+
+class Encryptor(mkrlwe.Encryptor):
+    """mkbfv.Encryptor (encryptor.go:7-25)"""
+
+    def _new_batch(self, id, level, count, like=None):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [id], level, count)
+
+    def EncryptPtxt(self, pt_rns, pk, samples=None):
+        """encryptor.go:30-32 on a fresh ciphertext over {pk.ID} (EncryptMsgNew :47-51 without the encoder)"""
+        return self.Encrypt(pt_rns, pk, NewCiphertext(self.params, [pk.ID], zero=False), samples)
+
+
+def NewEncryptor(params, sampler=None):
+    return Encryptor(params, sampler)
+
+
+class Decryptor(mkrlwe.Decryptor):
+    """mkbfv.Decryptor (decryptor.go:6-24)"""
+
+    def _like(self, ct, ids):
+        return NewCiphertext(self.params, ids, zero=False)
+
+    def DecryptPtxt(self, ct, skSet):
+        """decryptor.go:34-53 up to the decoder -> RNS polynomial uint64 [nQ][N], canonical"""
+        return self.Decrypt(ct, skSet).download()[0]
+
+
+def NewDecryptor(params):
+    return Decryptor(params)

@@ -537,3 +537,146 @@ class BatchEvaluator:
         out = self._new(cts[0].IDSet(), level - nb, rscale if nb else scale)
         check(lib().mkhe_ct_mul_ptxt_batch(params.ctx, self.B, self._h(ct), pt.devptr(), nb, self._h(out)))
         return out
+
+
+# ---- messages, encoder, encryptor, decryptor (mkckks/elements.go:19-31, encryptor.go, decryptor.go)
+class Message:
+    """mkckks.Message (elements.go:19-21): Value = one complex number per slot"""
+
+    def __init__(self, value):
+        self.Value = np.asarray(value, dtype=np.complex128)
+
+    def Slots(self):
+        return len(self.Value)
+
+
+def NewMessage(params):
+    """elements.go:23-27: 2^logSlots zero slots"""
+    return Message(np.zeros(1 << params.LogSlots(), dtype=np.complex128))
+
+
+class Plaintext:
+    """ckks.Plaintext as the encryptor sees it: an RNS polynomial (host uint64 [level+1][N], coefficient domain) and its scale"""
+
+    def __init__(self, value, scale):
+        self.Value, self.Scale = np.asarray(value, dtype=np.uint64), float(scale)
+
+    def Level(self):
+        return self.Value.shape[0] - 1
+
+
+class Encoder:
+    """The canonical embedding of lattigo's ckks.Encoder on the HOST (numpy): slot j <-> evaluation at zeta^(5^j), zeta = exp(i*pi/N),
+    computed with one FFT of length 2N.  Full packing only (logSlots = logN - 1)."""
+
+    def __init__(self, params):
+        self.params = params
+        self.N = params.N()
+        if params.LogSlots() != params.LogN() - 1:
+            raise MkheError("mkckks.Encoder: only logSlots = logN - 1 is supported")
+        self.n = self.N // 2
+        rot, r = np.empty(self.n, dtype=np.int64), 1
+        for j in range(self.n):
+            rot[j], r = r, r * mkrlwe.GALOIS_GEN % (2 * self.N)
+        self.rot = rot
+
+    def Embed(self, values):
+        """slots -> real coefficients m with sum_k m_k zeta_j^k = z_j:  m_k = (2/N) Re sum_j z_j conj(zeta_j)^k"""
+        z = np.asarray(values, dtype=np.complex128)
+        if z.shape != (self.n,):
+            raise MkheError("mkckks.Encoder: expected %d slots, got %r" % (self.n, z.shape))
+        a = np.zeros(2 * self.N, dtype=np.complex128)
+        a[self.rot] = z
+        return (2.0 / self.N) * np.real(np.fft.fft(a)[: self.N])
+
+    def Encode(self, values, level, scale):
+        """-> RNS plaintext uint64 [level+1][N]: round(m * scale) per coefficient (half to even), reduced exactly whatever its size"""
+        x = self.Embed(values) * float(scale)
+        Q = self.params.Q[: level + 1]
+        if np.abs(x).max(initial=0.0) < 2.0 ** 62:
+            r = np.rint(x).astype(np.int64)
+            return np.stack([np.mod(r, np.int64(q)).astype(np.uint64) for q in Q])
+        r = np.array([int(round(float(v))) for v in x], dtype=object)
+        return np.stack([np.array([int(v) for v in r % q], dtype=np.uint64) for q in Q])
+
+    def Decode(self, poly, scale):
+        """RNS polynomial [limbs][N] (canonical residues) at `scale` -> slots: CRT, centring, then the embedding"""
+        poly = np.asarray(poly, dtype=np.uint64)
+        Q = self.params.Q[: poly.shape[0]]
+        Qp = 1
+        for q in Q:
+            Qp *= q
+        x = np.zeros(self.N, dtype=object)
+        for l, q in enumerate(Q):
+            Mi = Qp // q
+            x = x + poly[l].astype(object) * (Mi * pow(Mi, -1, q))
+        x = x % Qp
+        m = np.array([float(v - Qp if v > Qp // 2 else v) for v in x]) / float(scale)
+        a = np.zeros(2 * self.N, dtype=np.complex128)
+        a[: self.N] = m
+        return (2 * self.N) * np.fft.ifft(a)[self.rot]
+
+
+class Encryptor(mkrlwe.Encryptor):
+    """mkckks.Encryptor (encryptor.go:7-27): mkrlwe.Encryptor + the encoder.  The encoder runs on the host, everything else on the device."""
+
+    def __init__(self, params, sampler=None):
+        super().__init__(params, sampler)
+        self.encoder = Encoder(params)
+
+    def _new_batch(self, id, level, count, like=None):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [id], level, count, Scale=self.params.Scale())
+
+    def EncryptPtxt(self, plaintext, pk, ctOut, samples=None):
+        """encryptor.go:33-36"""
+        self.Encrypt(plaintext.Value, pk, ctOut, samples)
+        ctOut.Scale = plaintext.Scale
+        return ctOut
+
+    def EncodeMsgNew(self, msg):
+        """encryptor.go:60-64: at the maximum level and the default scale"""
+        return Plaintext(self.encoder.Encode(msg.Value, self.params.MaxLevel(), self.params.Scale()), self.params.Scale())
+
+    def EncryptMsg(self, msg, pk, ctOut, samples=None):
+        """encryptor.go:42-45"""
+        return self.EncryptPtxt(self.EncodeMsgNew(msg), pk, ctOut, samples)
+
+    def EncryptMsgNew(self, msg, pk, samples=None):
+        """encryptor.go:51-58"""
+        ctOut = NewCiphertext(self.params, [pk.ID], self.params.MaxLevel(), self.params.Scale(), zero=False)
+        return self.EncryptMsg(msg, pk, ctOut, samples)
+
+    def EncryptPtxtBatch(self, plaintexts, pk, samples=None):
+        """the plaintexts (one level, one scale) under one public key as one engine call (mkrlwe.Encryptor.EncryptBatch)"""
+        cts = self.EncryptBatch([p.Value for p in plaintexts], pk, samples)
+        for c, p in zip(cts, plaintexts):
+            c.Scale = p.Scale
+        return cts
+
+
+def NewEncryptor(params, sampler=None):
+    return Encryptor(params, sampler)
+
+
+class Decryptor(mkrlwe.Decryptor):
+    """mkckks.Decryptor (decryptor.go:6-24)"""
+
+    def __init__(self, params):
+        super().__init__(params)
+        self.encoder = Encoder(params)
+
+    def _like(self, ct, ids):
+        return NewCiphertext(self.params, ids, ct.Level(), ct.ScalingFactor(), zero=False)
+
+    def DecryptPtxt(self, ct, skSet):
+        """the decrypted RNS polynomial with the ciphertext's scale"""
+        return Plaintext(mkrlwe.Decryptor.Decrypt(self, ct, skSet).download()[0], ct.ScalingFactor())
+
+    def Decrypt(self, ct, skSet):
+        """decryptor.go:34-43 -> Message"""
+        pt = self.DecryptPtxt(ct, skSet)
+        return Message(self.encoder.Decode(pt.Value, pt.Scale))
+
+
+def NewDecryptor(params):
+    return Decryptor(params)

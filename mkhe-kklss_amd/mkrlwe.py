@@ -732,3 +732,146 @@ def ntt(params, src, dst, mod_base=0, inverse=False, lazy=False):
     assert src.count == dst.count and src.limbs == dst.limbs
     check(lib().mkhe_ntt(params.ctx, src.devptr(), dst.devptr(), src.count, src.limbs, mod_base,
                          1 if inverse else 0, 1 if lazy else 0))
+
+
+# ---- public-key encryption and decryption (mkrlwe/encryptor.go, mkrlwe/decryptor.go, keys.go:70-121)
+class SecretKeySet:
+    """keys.go:70-94"""
+
+    def __init__(self):
+        self.Value = {}
+
+    def AddSecretKey(self, sk):
+        self.Value[sk.ID] = sk
+
+    def DelSecretKey(self, id):
+        self.Value.pop(id, None)
+
+    def GetSecretKey(self, id):
+        if id not in self.Value:
+            raise MkheError("cannot GetPublicKey: there is no public key with given id")       # keys.go:91 (the reference's own text)
+        return self.Value[id]
+
+
+def NewSecretKeySet():
+    return SecretKeySet()
+
+
+class PublicKeySet:
+    """keys.go:96-122"""
+
+    def __init__(self):
+        self.Value = {}
+
+    def AddPublicKey(self, pk):
+        self.Value[pk.ID] = pk
+
+    def DelPublicKey(self, id):
+        self.Value.pop(id, None)
+
+    def GetPublicKey(self, id):
+        if id not in self.Value:
+            raise MkheError("cannot GetPublicKey: there is no public key with given id")
+        return self.Value[id]
+
+
+def NewPublicKeyKeySet():
+    return PublicKeySet()
+
+
+def _device_plaintexts(params, pts):
+    """plaintexts for the engine: DeviceLimbs [B][limbs][N] as they are; a host array [B][limbs][N] / a list of [limbs][N] is uploaded"""
+    if isinstance(pts, DeviceLimbs):
+        return pts
+    host = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.uint64) for p in pts]) if isinstance(pts, (list, tuple)) else pts, dtype=np.uint64)
+    if host.ndim != 3 or host.shape[0] < 1 or host.shape[2] != params.N():
+        raise MkheError("Cannot Encrypt: expected plaintexts of shape [count][limbs][%d], got %r" % (params.N(), host.shape))
+    return DeviceLimbs(params, host.shape[0], host.shape[1]).upload(host)
+
+
+class Encryptor:
+    """mkrlwe.Encryptor (encryptor.go:8-52) on the device.  u (ternary, P(0) = 1/2) and e0, e1 (Gaussian: the sampler's sigma and bound)
+    are drawn on the HOST from `sampler`, like the secrets and errors of KeyGenerator; given as `samples` (int32 [3][N]: u, e0, e1) the
+    result is a deterministic function of them (parity tests).  Plaintexts are RNS polynomials: DeviceLimbs or host uint64 arrays."""
+
+    def __init__(self, params, sampler=None):
+        self.params = params
+        self.sampler = sampler if sampler is not None else HostSampler()
+
+    def _samples(self, samples, count):
+        N = self.params.N()
+        if samples is None:
+            samples = np.stack([np.concatenate([self.sampler.ternary(N, 0.5)[None], self.sampler.gaussian(2, N)]) for _ in range(count)])
+        return _s32(samples, (count, 3, N))
+
+    def _check_level(self, level):
+        if not 0 <= level <= self.params.MaxLevel():
+            raise MkheError("Cannot Encrypt: level %d out of range" % level)
+
+    def _new_batch(self, id, level, count, like=None):
+        return batch_ciphertexts(Ciphertext, self.params, [id], level, count)
+
+    def Encrypt(self, pt, pk, ctOut, samples=None, pt_is_ntt=False):
+        """encryptor.go:55-118.  pt: one plaintext [limbs][N] (or DeviceLimbs of count 1) with at least ctOut.Level() + 1 limbs; the Go
+        version shortens ctOut to a lower plaintext level, a device ciphertext keeps its shape, so that case raises."""
+        if ctOut.ids != [pk.ID]:
+            raise MkheError("Cannot Encrypt: ctOut must be a ciphertext over the id of pk alone")
+        d = pt if isinstance(pt, DeviceLimbs) else _device_plaintexts(self.params, np.asarray(pt, dtype=np.uint64)[None])
+        if d.count != 1:
+            raise MkheError("Cannot Encrypt: one plaintext expected (EncryptBatch takes several)")
+        level = ctOut.Level()
+        self._check_level(level)
+        if d.limbs < level + 1:
+            raise MkheError("Cannot Encrypt: the plaintext is below the level of ctOut")
+        a, ptr = self._samples(None if samples is None else np.asarray(samples)[None], 1)
+        check(lib().mkhe_encrypt(self.params.ctx, level, 1, pk.Value.devptr(), d.devptr(), 1 if pt_is_ntt else 0, ptr, handle_array([ctOut.h])))
+        return ctOut
+
+    def EncryptBatch(self, pts, pk, samples=None, pt_is_ntt=False):
+        """B plaintexts ([B][level+1][N]) under one public key as ONE engine call (mkhe_encrypt: five launches whatever B is);
+        samples: int32 [B][3][N].  Returns the list of B ciphertexts over {pk.ID} (views of one device block)."""
+        d = _device_plaintexts(self.params, pts)
+        level = d.limbs - 1
+        self._check_level(level)
+        a, ptr = self._samples(samples, d.count)
+        outs = self._new_batch(pk.ID, level, d.count)
+        check(lib().mkhe_encrypt(self.params.ctx, level, d.count, pk.Value.devptr(), d.devptr(), 1 if pt_is_ntt else 0, ptr,
+                                 handle_array([c.h for c in outs])))
+        return outs
+
+
+def NewEncryptor(params, sampler=None):
+    return Encryptor(params, sampler)
+
+
+class Decryptor:
+    """mkrlwe.Decryptor (decryptor.go:8-23) on the device; secret keys never leave it."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def _like(self, ct, ids):
+        return Ciphertext(self.params, ids, ct.Level(), zero=False)
+
+    def PartialDecrypt(self, ct, sk):
+        """decryptor.go:26-43.  The Go version works in place and deletes ct.Value[sk.ID]; a device ciphertext keeps its shape, so the
+        result is a NEW ciphertext over the remaining ids and `ct` is left as it was (the deviation Rescale already makes)."""
+        if sk.ID not in ct.ids:
+            raise MkheError("Cannot PartialDecrypt: the ciphertext has no component for the id of sk")
+        out = self._like(ct, [i for i in ct.ids if i != sk.ID])
+        check(lib().mkhe_partial_decrypt(self.params.ctx, ct.h, ct.slot(sk.ID), sk.Value.devptr(), out.h))
+        return out
+
+    def Decrypt(self, ct, skSet):
+        """decryptor.go:48-66 -> DeviceLimbs [1][level+1][N]: canonical residues, coefficient domain"""
+        for i in ct.ids:
+            if i not in skSet.Value:
+                raise MkheError("Cannot Decrypt: there is a missing secretkey")               # decryptor.go:61-63
+        pt = DeviceLimbs(self.params, 1, ct.Level() + 1)
+        sks = [skSet.Value[i].Value.devptr() for i in ct.ids]
+        check(lib().mkhe_decrypt(self.params.ctx, ct.h, handle_array(sks), pt.devptr()))
+        return pt
+
+
+def NewDecryptor(params):
+    return Decryptor(params)
