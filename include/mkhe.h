@@ -388,6 +388,39 @@ int  mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void
  * coefficient domain */
 int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, void* dev_pt_out);
 
+/* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
+ * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call
+ * lattigo's ckks.Encoder, which is not in the reference tree: what these calls restate is the canonical embedding itself, not
+ * lattigo's code path.  Full packing: n = N/2 slots, slot j = the evaluation of the real coefficient vector at exp(i pi 5^j / N).
+ * Buffers are device buffers (mkhe_buf_alloc; 16-byte aligned); a double is one 8-byte word, so mkhe_buf_upload / mkhe_buf_download
+ * carry them as bit patterns:
+ *   slots   double[count][n][2]  (re, im)
+ *   coeffs  double[count][N]
+ *   pt      uint64[count][limbs][N], coefficient domain, canonical: what mkhe_encrypt takes as dev_pt and mkhe_decrypt writes (count = 1)
+ * `count` messages are one launch set.  Arithmetic is IEEE float64, tables rounded once from long double.  Not available on BFV
+ * contexts, on a context that owns a subset of the moduli, or between mkhe_capture_begin and mkhe_capture_end (the calls
+ * allocate and upload at first use); scale must be finite and > 0; 0 <= level < nQ, 1 <= limbs <= nQ; 1 <= count <= 65535 (one
+ * launch set: the messages are the second grid dimension). */
+/* embed (encoder side of encryptor.go:60-64): coeffs m with sum_k m_k zeta_j^k = z_j:  m_k = (2/N) Re sum_j z_j conj(zeta_j)^k */
+int  mkhe_ckks_embed(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_coeffs);
+/* project (decoder side of decryptor.go:34-43): z_j = sum_{k<N} m_k zeta_j^k */
+int  mkhe_ckks_project(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_slots);
+/* scale_up (encryptor.go:60-64): pt = residues of rint(coeffs * scale) (one IEEE multiply, ties to even) under q_0 .. q_level, exact
+ * for every size of the rounded value.  NaN or +-inf coefficients (or products) are the caller's error: the output is unspecified. */
+int  mkhe_ckks_scale_up(mkhe_ctx* ctx, int level, int count, const void* dev_coeffs, double scale, void* dev_pt);
+/* scale_down (decryptor.go:34-43): coeffs = (centred lift of pt to (-Q/2, Q/2), Q = q_0 .. q_(limbs-1)) / scale, relative error below
+ * 4 limbs 2^-53; the sign is decided exactly.  A magnitude beyond the float64 range gives +-inf, never NaN. */
+int  mkhe_ckks_scale_down(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_coeffs);
+/* EncodeMsgNew encryptor.go:60-64 == scale_up(embed), bit for bit */
+int  mkhe_ckks_encode(mkhe_ctx* ctx, int level, int count, const void* dev_slots, double scale, void* dev_pt);
+/* the decoding of Decrypt decryptor.go:34-43 == project(scale_down), bit for bit */
+int  mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_slots);
+/* log2 of the largest transform (N/2 points) that one workgroup does in LDS: 13 where the runtime grants 128 KiB of dynamic LDS, else 11;
+ * larger transforms take two launches over a work buffer (same bits).  -1 = error.  mkhe_ctx_set_ckks_tile lowers the limit to 11 (or
+ * puts it back: 0, or the granted value), so that the two-launch form of N/2 = 2^12, 2^13 can be run and tested on any machine. */
+int  mkhe_ctx_ckks_tile(mkhe_ctx* ctx);
+int  mkhe_ctx_set_ckks_tile(mkhe_ctx* ctx, int log_points);
+
 /* ---- measurement support (no reference counterpart): HIP-event timing per kernel class on the
  *      context stream, one record per kernel launch.  Classes (mkhe_prof_name gives the kernel symbol
  *      each class corresponds to in a rocprofv3 kernel trace). */

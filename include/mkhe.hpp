@@ -8,6 +8,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -530,6 +531,29 @@ class Evaluator {
         check(fn(params.ctx, a.h, b.h, out->h));
         return out;
     }
+};
+
+// The CKKS encoder on the device (mkhe_ckks_encode / mkhe_ckks_decode): the message layer of mkckks/encryptor.go:42-64 and
+// mkckks/decryptor.go:34-43.  lattigo's ckks.Encoder, which those lines call, is not in the reference tree: this is the canonical
+// embedding with full packing (Slots() = N/2 complex values per message), not lattigo's code path.  Messages cross the bus as slots;
+// plaintexts are device buffers uint64[count][level+1][N], coefficient domain: what mkrlwe::Encryptor takes and Decryptor writes.
+class Encoder {
+  public:
+    explicit Encoder(Parameters& p) : params(p) {}
+    int Slots() const { return params.N() / 2; }
+    // count messages (host: count * Slots() values) at `level` and `scale` -> dev_pt, as one launch set
+    void Encode(int count, const std::complex<double>* values, int level, double scale, void* dev_pt) {
+        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
+        check(mkhe_buf_upload(params.ctx, z.d, reinterpret_cast<const uint64_t*>(values), z.words));
+        check(mkhe_ckks_encode(params.ctx, level, count, z.d, scale, dev_pt));
+    }
+    // count plaintexts of `limbs` limbs at `scale` -> values (host: count * Slots())
+    void Decode(int limbs, int count, const void* dev_pt, double scale, std::complex<double>* values) {
+        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
+        check(mkhe_ckks_decode(params.ctx, limbs, count, dev_pt, scale, z.d));
+        z.download(reinterpret_cast<uint64_t*>(values));
+    }
+    Parameters& params;
 };
 }  // namespace mkckks
 

@@ -111,6 +111,14 @@ SIGNATURES = {
     "mkhe_encrypt": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, s32p, vpp]),
     "mkhe_partial_decrypt": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "mkhe_decrypt": (C.c_int, [vp, vp, vpp, vp]),
+    "mkhe_ckks_embed": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_ckks_project": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_ckks_scale_up": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
+    "mkhe_ckks_scale_down": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
+    "mkhe_ckks_encode": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
+    "mkhe_ckks_decode": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
+    "mkhe_ctx_ckks_tile": (C.c_int, [vp]),
+    "mkhe_ctx_set_ckks_tile": (C.c_int, [vp, C.c_int]),
     "mkhe_prof_enable": (C.c_int, [vp, C.c_int]),
     "mkhe_ntt_trace": (C.c_int, [vp, vp]),
     "mkhe_set_overlap": (C.c_int, [vp, C.c_int]),

@@ -658,6 +658,79 @@ int mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, vo
     })
 }
 
+// ---- CKKS encoder (ckks_encode.hip)
+// the argument checks every encoder call shares; a call refused here leaves the context (and a capture in progress) as it was
+static Context* ck_need(mkhe_ctx* ctx, const char* what, int count, const void* a, const void* b) {
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (!a || !b) throw Error(std::string(what) + ": null argument");
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    need_aligned(a, what); need_aligned(b, what);
+    if (c->is_bfv()) throw Error(std::string(what) + ": the CKKS encoder needs a CKKS context");
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (the call allocates and uploads)");
+    MKHE_HIP(hipSetDevice(c->device));
+    g_last_ctx = c;
+    return c;
+}
+static Context* ck_need_ctx(mkhe_ctx* ctx, const char* what) {
+    alignas(16) static const double dummy[2] = {0, 0};      // (no buffers in these calls)
+    return ck_need(ctx, what, 1, dummy, dummy);
+}
+int mkhe_ctx_ckks_tile(mkhe_ctx* ctx) {
+    g_last_ctx = nullptr;
+    try { return ck_need_ctx(ctx, "mkhe_ctx_ckks_tile")->ckks_tile(); }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    catch (...) { g_err = "mkhe: unknown error"; return -1; }
+}
+int mkhe_ctx_set_ckks_tile(mkhe_ctx* ctx, int log_points) { MKHE_TRY({ ck_need_ctx(ctx, "mkhe_ctx_set_ckks_tile")->ckks_set_tile(log_points); }) }
+static void ck_scale_ok(double scale, const char* what) {
+    if (!(scale > 0.0) || scale > 1.7976931348623157e308) throw Error(std::string(what) + ": scale must be finite and positive");
+}
+static void ck_limbs_ok(const Context* c, int limbs, const char* what, const char* name) {
+    if (limbs < 1 || limbs > c->nq) throw Error(std::string(what) + ": " + name + " out of range");
+}
+int mkhe_ckks_embed(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_coeffs) {
+    MKHE_TRY({ ck_need(ctx, "mkhe_ckks_embed", count, dev_slots, dev_coeffs)->ckks_embed(count, (const double*)dev_slots, (double*)dev_coeffs); })
+}
+int mkhe_ckks_project(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_slots) {
+    MKHE_TRY({ ck_need(ctx, "mkhe_ckks_project", count, dev_coeffs, dev_slots)->ckks_project(count, (const double*)dev_coeffs, (double*)dev_slots); })
+}
+int mkhe_ckks_scale_up(mkhe_ctx* ctx, int level, int count, const void* dev_coeffs, double scale, void* dev_pt) {
+    MKHE_TRY({
+        ck_scale_ok(scale, "mkhe_ckks_scale_up");
+        Context* c = ck_need(ctx, "mkhe_ckks_scale_up", count, dev_coeffs, dev_pt);
+        ck_limbs_ok(c, level + 1, "mkhe_ckks_scale_up", "level");
+        c->ckks_scale_up(level, count, (const double*)dev_coeffs, scale, (u64*)dev_pt);
+    })
+}
+int mkhe_ckks_scale_down(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_coeffs) {
+    MKHE_TRY({
+        ck_scale_ok(scale, "mkhe_ckks_scale_down");
+        Context* c = ck_need(ctx, "mkhe_ckks_scale_down", count, dev_pt, dev_coeffs);
+        ck_limbs_ok(c, limbs, "mkhe_ckks_scale_down", "limbs");
+        c->ckks_scale_down(limbs, count, (const u64*)dev_pt, scale, (double*)dev_coeffs);
+    })
+}
+int mkhe_ckks_encode(mkhe_ctx* ctx, int level, int count, const void* dev_slots, double scale, void* dev_pt) {
+    MKHE_TRY({
+        ck_scale_ok(scale, "mkhe_ckks_encode");
+        Context* c = ck_need(ctx, "mkhe_ckks_encode", count, dev_slots, dev_pt);
+        ck_limbs_ok(c, level + 1, "mkhe_ckks_encode", "level");
+        c->ckks_encode(level, count, (const double*)dev_slots, scale, (u64*)dev_pt);
+    })
+}
+int mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_slots) {
+    MKHE_TRY({
+        ck_scale_ok(scale, "mkhe_ckks_decode");
+        Context* c = ck_need(ctx, "mkhe_ckks_decode", count, dev_pt, dev_slots);
+        ck_limbs_ok(c, limbs, "mkhe_ckks_decode", "limbs");
+        c->ckks_decode(limbs, count, (const u64*)dev_pt, scale, (double*)dev_slots);
+    })
+}
+
 // ---- mkbfv
 int mkhe_ctx_create_bfv(mkhe_ctx** out, int logN, const uint64_t* Q, const uint64_t* QMul, int nQ,
                         const uint64_t* P, int nP, int gamma, uint64_t T, int device) {

@@ -19,6 +19,7 @@
 #include "poly_kernels.h"
 #include "keygen_kernels.h"
 #include "encdec_kernels.h"
+#include "ckks_kernels.h"
 
 namespace mkhe {
 
@@ -240,6 +241,19 @@ class Context {
     void partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out);                      // decryptor.go:26-43
     void decrypt(const Ct& ct, const u64* const* sks, u64* pt_out);                            // decryptor.go:48-66
 
+    // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
+    // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).
+    void ckks_embed(int count, const double* slots, double* coeffs);
+    void ckks_project(int count, const double* coeffs, double* slots);
+    void ckks_scale_up(int level, int count, const double* coeffs, double scale, u64* pt);
+    void ckks_scale_down(int limbs, int count, const u64* pt, double scale, double* coeffs);
+    void ckks_encode(int level, int count, const double* slots, double scale, u64* pt);
+    void ckks_decode(int limbs, int count, const u64* pt, double scale, double* slots);
+    // log2 of the largest transform one workgroup does in LDS (CK_TILE_LOG_BIG, or CK_TILE_LOG when the runtime grants no more LDS), and a way
+    // to lower it to CK_TILE_LOG so that the two-launch form of n = 2^12, 2^13 can be run where the runtime does grant it (0: back to the grant)
+    int ckks_tile();
+    void ckks_set_tile(int log_points);
+
     bool overlap = true;               // false: everything on the main stream (clean per-kernel timings)
     u64* ntt_trace = nullptr;          // diagnostic buffer handed to the forward NTT kernels (mkhe_ntt_trace)
     // stream-ordered buffer cache for ciphertext / switching-key handles: freeing a handle does not
@@ -324,6 +338,18 @@ class Context {
     const u64** ed_tab_ = nullptr; size_t ed_tab_n_ = 0;
     EdTable ed_table(const std::vector<const u64*>& v, size_t tab_offset);
     void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
+    // CKKS encoder: tables built at the first call (twiddles [n/2][2], twist [n][2], permutation [n], Garner constants [nq][nq]), the largest
+    // FFT one workgroup does in LDS, and the scratch for the two-launch FFT, the Garner digits and the coefficients of the fused calls
+    double *d_ck_w = nullptr, *d_ck_twist = nullptr; u32* d_ck_pos = nullptr; u64* d_ck_garner = nullptr;
+    bool ck_ready_ = false;
+    int ck_lds_log_ = CK_TILE_LOG, ck_lds_granted_ = CK_TILE_LOG;
+    u64* ck_work_ = nullptr;  size_t ck_work_words_ = 0;
+    u64* ck_dig_ = nullptr;   size_t ck_dig_words_ = 0;
+    u64* ck_coeff_ = nullptr; size_t ck_coeff_words_ = 0;
+    void ck_init(const char* what);
+    void ck_fft(bool inverse, int count, const double* in, double* out);
+    void ck_scale_up(int level, int count, const double* coeffs, double scale, u64* pt);
+    void ck_scale_down(int limbs, int count, const u64* pt, double scale, double* coeffs);
 
     u64* scratch(u64*& p, size_t& have, size_t want);
     Swk& hoist_slot(int which, int idx);

@@ -510,7 +510,8 @@ void Context::release_all() noexcept {
                     (void*)d_map_r, (void*)d_bq_qoverqiinvqi, (void*)d_bq_qoverqimodp, (void*)d_bq_vtimes,
                     (void*)d_bm_qoverqiinvqi, (void*)d_bm_qoverqimodp, (void*)d_bm_vtimes,
                     (void*)d_down_q_in_m, (void*)d_down_m_in_q, (void*)d_mform_qmul, (void*)d_t_mont,
-                    (void*)kg_small_, (void*)kg_g_, (void*)kg_sk_, (void*)ed_w_, (void*)ed_small_, (void*)ed_tab_})
+                    (void*)kg_small_, (void*)kg_g_, (void*)kg_sk_, (void*)ed_w_, (void*)ed_small_, (void*)ed_tab_,
+                    (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)d_ck_garner, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_})
         if (p) (void)hipFree(p);
     for (auto& v : hoist_pool_) for (auto& s : v) if (s.d) (void)hipFree(s.d);
     for (auto& kv : f2_sched_) if (kv.second.d_segs) (void)hipFree(kv.second.d_segs);

@@ -142,7 +142,7 @@ class Evaluator:
         params = self.params
         level = ct.Level()
         ctOut = NewCiphertext(params, ct.IDSet(), level, ct.Scale * float(pt_scale), zero=False)
-        if isinstance(pt_value, mkrlwe.DeviceLimbs):          # already resident (uploaded once by the caller; required inside a graph capture)
+        if isinstance(pt_value, mkrlwe.DeviceLimbs):          # already resident (uploaded once by the caller, or DeviceEncoder.Encode's; required inside a graph capture)
             pt = pt_value
             if pt.limbs != level + 1:
                 raise MkheError("MulPtxtNew: the resident plaintext must have level + 1 limbs")
@@ -559,10 +559,12 @@ class Plaintext:
     """ckks.Plaintext as the encryptor sees it: an RNS polynomial (host uint64 [level+1][N], coefficient domain) and its scale"""
 
     def __init__(self, value, scale):
-        self.Value, self.Scale = np.asarray(value, dtype=np.uint64), float(scale)
+        """value: host uint64 [level+1][N], or the device plaintext (mkrlwe.DeviceLimbs [1][level+1][N]) of DeviceEncoder.Encode"""
+        self.Value = value if isinstance(value, mkrlwe.DeviceLimbs) else np.asarray(value, dtype=np.uint64)
+        self.Scale = float(scale)
 
     def Level(self):
-        return self.Value.shape[0] - 1
+        return (self.Value.limbs if isinstance(self.Value, mkrlwe.DeviceLimbs) else self.Value.shape[0]) - 1
 
 
 class Encoder:
@@ -611,18 +613,112 @@ class Encoder:
             Mi = Qp // q
             x = x + poly[l].astype(object) * (Mi * pow(Mi, -1, q))
         x = x % Qp
-        m = np.array([float(v - Qp if v > Qp // 2 else v) for v in x]) / float(scale)
+        return self.Project(np.array([float(v - Qp if v > Qp // 2 else v) for v in x]) / float(scale))
+
+    def Project(self, m):
+        """real coefficients -> slots: z_j = sum_k m_k zeta_j^k"""
         a = np.zeros(2 * self.N, dtype=np.complex128)
         a[: self.N] = m
         return (2 * self.N) * np.fft.ifft(a)[self.rot]
 
 
-class Encryptor(mkrlwe.Encryptor):
-    """mkckks.Encryptor (encryptor.go:7-27): mkrlwe.Encryptor + the encoder.  The encoder runs on the host, everything else on the device."""
+def slot_permutation(logN):
+    """t with t[j] = (5^j mod 2N - 1) / 4, a permutation of 0 .. N/2 - 1: slot j of a message is bin t[j] of the N/2-point transform
+    of the twisted coefficient pairs (csrc/ckks_kernels.h)"""
+    n = 1 << (logN - 1)
+    t, g = np.empty(n, dtype=np.int64), 1
+    for j in range(n):
+        t[j], g = (g - 1) // 4, g * mkrlwe.GALOIS_GEN % (4 * n)
+    return t
 
-    def __init__(self, params, sampler=None):
+
+class DeviceEncoder:
+    """The interface of Encoder on the DEVICE (mkhe_ckks_*: csrc/ckks_kernels.hip), plus batch forms.  Messages go up and come down as
+    N/2 complex slots (16 bytes each); plaintexts stay resident as mkrlwe.DeviceLimbs.  Same embedding convention as Encoder; float64
+    arithmetic with another factorisation, so the bits of an encoding differ from the host encoder's in the last places."""
+
+    def __init__(self, params):
+        self.params = params
+        self.N = params.N()
+        if params.LogSlots() != params.LogN() - 1:
+            raise MkheError("mkckks.DeviceEncoder: only logSlots = logN - 1 is supported")
+        self.n = self.N // 2
+
+    # a float64 array of count * N values <-> a raw device buffer (one 8-byte word per double)
+    def _up(self, a, count):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(count, 1, self.N)
+        return mkrlwe.DeviceLimbs(self.params, count, 1).upload(a.view(np.uint64))
+
+    def _slots(self, values):
+        """-> (complex128 [count][n], whether the caller passed one message)"""
+        z = np.asarray(values, dtype=np.complex128)
+        one = z.ndim == 1
+        z = z[None] if one else z
+        if z.ndim != 2 or z.shape[0] < 1 or z.shape[1] != self.n:
+            raise MkheError("mkckks.DeviceEncoder: expected %d slots per message, got %r" % (self.n, np.shape(values)))
+        return np.ascontiguousarray(z), one
+
+    def _down_slots(self, d, one):
+        z = d.download().view(np.float64).reshape(d.count, self.n, 2)
+        z = z[..., 0] + 1j * z[..., 1]
+        return z[0] if one else z
+
+    def Embed(self, values):
+        """slots [n] (or [count][n]) -> real coefficients [N] (or [count][N])"""
+        z, one = self._slots(values)
+        src, dst = self._up(z.view(np.float64), len(z)), mkrlwe.DeviceLimbs(self.params, len(z), 1)
+        check(lib().mkhe_ckks_embed(self.params.ctx, len(z), src.devptr(), dst.devptr()))
+        m = dst.download().view(np.float64).reshape(len(z), self.N)
+        return m[0] if one else m
+
+    def Project(self, coeffs):
+        """real coefficients [N] (or [count][N]) -> slots"""
+        m = np.asarray(coeffs, dtype=np.float64)
+        one = m.ndim == 1
+        m = m[None] if one else m
+        if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] != self.N:
+            raise MkheError("mkckks.DeviceEncoder: expected %d coefficients per message, got %r" % (self.N, np.shape(coeffs)))
+        src, dst = self._up(m, len(m)), mkrlwe.DeviceLimbs(self.params, len(m), 1)
+        check(lib().mkhe_ckks_project(self.params.ctx, len(m), src.devptr(), dst.devptr()))
+        return self._down_slots(dst, one)
+
+    def EncodeBatch(self, values, level, scale):
+        """count messages -> device plaintexts [count][level+1][N] (coefficient domain, canonical) as one launch set"""
+        z, _ = self._slots(values)
+        src, pt = self._up(z.view(np.float64), len(z)), mkrlwe.DeviceLimbs(self.params, len(z), level + 1)
+        check(lib().mkhe_ckks_encode(self.params.ctx, level, len(z), src.devptr(), float(scale), pt.devptr()))
+        return pt
+
+    def Encode(self, values, level, scale):
+        """-> device plaintext [1][level+1][N]: what mkrlwe.Encryptor.Encrypt and MulPtxtNew take as they are"""
+        z, one = self._slots(values)
+        if not one:
+            raise MkheError("mkckks.DeviceEncoder: Encode takes one message (EncodeBatch takes several)")
+        return self.EncodeBatch(z, level, scale)
+
+    def Decode(self, poly, scale):
+        """device plaintext(s) [count][limbs][N] (or a host polynomial [limbs][N]) at `scale` -> slots [n] ([count][n] for count > 1)"""
+        if not isinstance(poly, mkrlwe.DeviceLimbs):
+            poly = np.ascontiguousarray(poly, dtype=np.uint64)
+            poly = mkrlwe.DeviceLimbs(self.params, 1, poly.shape[0]).upload(poly[None])
+        dst = mkrlwe.DeviceLimbs(self.params, poly.count, 1)
+        check(lib().mkhe_ckks_decode(self.params.ctx, poly.limbs, poly.count, poly.devptr(), float(scale), dst.devptr()))
+        return self._down_slots(dst, poly.count == 1)
+
+
+def _encoder(params, which):
+    if which not in ("host", "device"):
+        raise MkheError("mkckks: encoder must be \"host\" or \"device\"")
+    return Encoder(params) if which == "host" else DeviceEncoder(params)
+
+
+class Encryptor(mkrlwe.Encryptor):
+    """mkckks.Encryptor (encryptor.go:7-27): mkrlwe.Encryptor + the encoder.  encoder="host" (default): the numpy Encoder, whose
+    plaintext is uploaded; "device": DeviceEncoder, whose plaintext goes to mkhe_encrypt without touching the host."""
+
+    def __init__(self, params, sampler=None, encoder="host"):
         super().__init__(params, sampler)
-        self.encoder = Encoder(params)
+        self.encoder = _encoder(params, encoder)
 
     def _new_batch(self, id, level, count, like=None):
         return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [id], level, count, Scale=self.params.Scale())
@@ -653,17 +749,30 @@ class Encryptor(mkrlwe.Encryptor):
             c.Scale = p.Scale
         return cts
 
+    def EncryptMsgBatch(self, msgs, pk, samples=None):
+        """EncryptMsgNew (encryptor.go:51-58) for several messages under one public key: one encode (one launch set with the device
+        encoder) and one mkhe_encrypt call"""
+        level, scale = self.params.MaxLevel(), self.params.Scale()
+        if isinstance(self.encoder, DeviceEncoder):
+            pts = self.encoder.EncodeBatch(np.stack([m.Value for m in msgs]), level, scale)
+        else:
+            pts = np.stack([self.encoder.Encode(m.Value, level, scale) for m in msgs])
+        cts = self.EncryptBatch(pts, pk, samples)
+        for c in cts:
+            c.Scale = scale
+        return cts
 
-def NewEncryptor(params, sampler=None):
-    return Encryptor(params, sampler)
+
+def NewEncryptor(params, sampler=None, encoder="host"):
+    return Encryptor(params, sampler, encoder)
 
 
 class Decryptor(mkrlwe.Decryptor):
     """mkckks.Decryptor (decryptor.go:6-24)"""
 
-    def __init__(self, params):
+    def __init__(self, params, encoder="host"):
         super().__init__(params)
-        self.encoder = Encoder(params)
+        self.encoder = _encoder(params, encoder)
 
     def _like(self, ct, ids):
         return NewCiphertext(self.params, ids, ct.Level(), ct.ScalingFactor(), zero=False)
@@ -673,10 +782,13 @@ class Decryptor(mkrlwe.Decryptor):
         return Plaintext(mkrlwe.Decryptor.Decrypt(self, ct, skSet).download()[0], ct.ScalingFactor())
 
     def Decrypt(self, ct, skSet):
-        """decryptor.go:34-43 -> Message"""
+        """decryptor.go:34-43 -> Message.  With the device encoder the output buffer of mkhe_decrypt goes straight to mkhe_ckks_decode:
+        only the slots come down."""
+        if isinstance(self.encoder, DeviceEncoder):
+            return Message(self.encoder.Decode(mkrlwe.Decryptor.Decrypt(self, ct, skSet), ct.ScalingFactor()))
         pt = self.DecryptPtxt(ct, skSet)
         return Message(self.encoder.Decode(pt.Value, pt.Scale))
 
 
-def NewDecryptor(params):
-    return Decryptor(params)
+def NewDecryptor(params, encoder="host"):
+    return Decryptor(params, encoder)
