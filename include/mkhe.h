@@ -421,6 +421,42 @@ int  mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, d
 int  mkhe_ctx_ckks_tile(mkhe_ctx* ctx);
 int  mkhe_ctx_set_ckks_tile(mkhe_ctx* ctx, int log_points);
 
+/* ==== BFV batch encoder: slots over Z_T <-> RNS plaintext ===========================================
+ * The message layer of mkbfv/encryptor.go:38-41 (EncryptMsg = EncodeInt, then Encrypt) and mkbfv/decryptor.go:52-54 (DecodeInt).  Those lines
+ * call lattigo's bfv.Encoder, which is not in the reference tree: what these calls restate is the mathematics of the encoder, not lattigo's
+ * code path.  Definitions (N the ring degree, T the plaintext modulus of the mkhe_ctx_create_bfv context, Q the product of its ciphertext primes):
+ *   psi     the primitive 2N-th root of unity mod T chosen by the rule the engine uses for the ciphertext primes: g the smallest generator
+ *           >= 3 of Z_T*, psi = g^((T-1)/2N).  mkhe_ctx_bfv_slot_psi returns it.
+ *   slots   a message is N values.  Slot i (0 <= i < N/2) of m(X) in Z_T[X]/(X^N+1) is m(psi^(5^i)), slot N/2+i is m(psi^(-5^i)): two rows of
+ *           N/2 (lattigo's index matrix).  A rotation by k moves slot i+k to slot i within each row, the conjugation swaps the rows, the
+ *           ring operations act slot by slot mod T.
+ *   values  int64.  Encoding takes any int64 and uses its residue in [0, T); decoding returns the centred representative in (-T/2, T/2].
+ *   scale_up    pt_l[k] = floor((Q m_k + floor(T/2)) / T) mod q_l for every limb of Q, m_k in [0, T)
+ *   scale_down  floor((T x + floor(Q/2)) / Q) mod T for the residues of x in [0, Q): exact for every x (integer arithmetic only)
+ * The calls need T prime, T = 1 (mod 2N) and T < 2^32 (larger T is out of scope), and T different from every prime of Q; otherwise they return an
+ * error (mkhe_ctx_create_bfv itself accepts any T >= 2).  Buffers are device buffers (mkhe_buf_alloc; 16-byte aligned):
+ *   slots   int64[count][N]
+ *   coeffs  uint64[count][N], written < T (as an input every 64-bit value is taken mod T)
+ *   pt      uint64[count][nQ][N], coefficient domain, canonical, always at the maximum level: what mkhe_encrypt takes as dev_pt and
+ *           mkhe_decrypt writes (count = 1)
+ * `count` messages are one launch set, 1 <= count <= 65535 (the messages are the second grid dimension).  Not available on non-BFV contexts, on a
+ * context that owns a subset of the moduli (mkhe_ctx_set_owned makes none of a BFV context today), or between mkhe_capture_begin and mkhe_capture_end (the calls allocate and upload at first use). */
+int  mkhe_bfv_slots_to_coeffs(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_coeffs);
+int  mkhe_bfv_coeffs_to_slots(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_slots);
+int  mkhe_bfv_scale_up(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_pt);
+int  mkhe_bfv_scale_down(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_coeffs);
+/* EncodeInt of encryptor.go:38-41 == scale_up(slots_to_coeffs), bit for bit */
+int  mkhe_bfv_encode(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_pt);
+/* DecodeInt of decryptor.go:52-54 == coeffs_to_slots(scale_down), bit for bit */
+int  mkhe_bfv_decode(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_slots);
+/* log2 of the largest transform (N points of 32 bits) that one workgroup does in LDS: 15 where the runtime grants 128 KiB of dynamic LDS, else
+ * 14; larger transforms take two launches over a work buffer (same bits).  -1 = error.  mkhe_ctx_set_bfv_tile lowers the limit to any value
+ * from 10 up to the granted one (or puts it back: 0), so that the two-launch form can be run and tested at small N on any machine. */
+int  mkhe_ctx_bfv_tile(mkhe_ctx* ctx);
+int  mkhe_ctx_set_bfv_tile(mkhe_ctx* ctx, int log_points);
+/* psi of the definitions above; 0 = error (the same conditions as the encoder calls) */
+uint64_t mkhe_ctx_bfv_slot_psi(mkhe_ctx* ctx);
+
 /* ---- measurement support (no reference counterpart): HIP-event timing per kernel class on the
  *      context stream, one record per kernel launch.  Classes (mkhe_prof_name gives the kernel symbol
  *      each class corresponds to in a rocprofv3 kernel trace). */

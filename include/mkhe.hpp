@@ -633,4 +633,32 @@ class Evaluator {
   private:
     CiphertextPtr bin(const Ciphertext& a, const Ciphertext& b) { return std::make_unique<Ciphertext>(params, mkrlwe::Union(a.IDSet_(), b.IDSet_()), false); }
 };
+// The batch encoder on the device (mkhe_bfv_encode / mkhe_bfv_decode): EncodeInt of mkbfv/encryptor.go:38-41 and DecodeInt of
+// mkbfv/decryptor.go:52-54.  lattigo's bfv.Encoder, which those lines call, is not in the reference tree: this is the mathematics of slot
+// batching over Z_T (include/mkhe.h: Slots() = N int64 values per message, two rows of N/2), not lattigo's code path.  Messages cross the bus
+// as slots; plaintexts are device buffers uint64[count][nQ][N], coefficient domain: what mkrlwe::Encryptor takes and Decryptor writes.
+class Encoder {
+  public:
+    explicit Encoder(Parameters& p) : params(p) {}
+    int Slots() const { return params.N(); }
+    // the 2N-th root of unity mod T of the slot definition; throws where the plaintext modulus is not supported
+    uint64_t SlotPsi() {
+        const uint64_t psi = mkhe_ctx_bfv_slot_psi(params.ctx);
+        if (!psi) throw Error(mkhe_last_error());
+        return psi;
+    }
+    // count messages (host: count * Slots() values, any int64) -> dev_pt, as one launch set
+    void Encode(int count, const int64_t* values, void* dev_pt) {
+        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
+        check(mkhe_buf_upload(params.ctx, z.d, reinterpret_cast<const uint64_t*>(values), z.words));
+        check(mkhe_bfv_encode(params.ctx, count, z.d, dev_pt));
+    }
+    // count plaintexts -> values (host: count * Slots()), centred in (-T/2, T/2]
+    void Decode(int count, const void* dev_pt, int64_t* values) {
+        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
+        check(mkhe_bfv_decode(params.ctx, count, dev_pt, z.d));
+        z.download(reinterpret_cast<uint64_t*>(values));
+    }
+    Parameters& params;
+};
 }  // namespace mkbfv

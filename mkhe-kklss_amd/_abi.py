@@ -119,6 +119,15 @@ SIGNATURES = {
     "mkhe_ckks_decode": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
     "mkhe_ctx_ckks_tile": (C.c_int, [vp]),
     "mkhe_ctx_set_ckks_tile": (C.c_int, [vp, C.c_int]),
+    "mkhe_bfv_slots_to_coeffs": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_coeffs_to_slots": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_scale_up": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_scale_down": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_encode": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_decode": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_ctx_bfv_tile": (C.c_int, [vp]),
+    "mkhe_ctx_set_bfv_tile": (C.c_int, [vp, C.c_int]),
+    "mkhe_ctx_bfv_slot_psi": (C.c_uint64, [vp]),
     "mkhe_prof_enable": (C.c_int, [vp, C.c_int]),
     "mkhe_ntt_trace": (C.c_int, [vp, vp]),
     "mkhe_set_overlap": (C.c_int, [vp, C.c_int]),

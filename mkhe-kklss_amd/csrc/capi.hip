@@ -731,6 +731,59 @@ int mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, do
     })
 }
 
+// ---- BFV batch encoder (bfv_encode.hip)
+// the argument checks every call shares; a call refused here leaves the context (and a capture in progress) as it was
+static Context* bf_need(mkhe_ctx* ctx, const char* what, int count, const void* a, const void* b) {
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (!a || !b) throw Error(std::string(what) + ": null argument");
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    need_aligned(a, what); need_aligned(b, what);
+    if (!c->is_bfv()) throw Error(std::string(what) + ": the BFV encoder needs a BFV context");
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (the call allocates and uploads)");
+    MKHE_HIP(hipSetDevice(c->device));
+    g_last_ctx = c;
+    return c;
+}
+static Context* bf_need_ctx(mkhe_ctx* ctx, const char* what) {
+    alignas(16) static const u64 dummy[2] = {0, 0};         // (no buffers in these calls)
+    return bf_need(ctx, what, 1, dummy, dummy);
+}
+int mkhe_ctx_bfv_tile(mkhe_ctx* ctx) {
+    g_last_ctx = nullptr;
+    try { return bf_need_ctx(ctx, "mkhe_ctx_bfv_tile")->bfv_tile(); }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    catch (...) { g_err = "mkhe: unknown error"; return -1; }
+}
+int mkhe_ctx_set_bfv_tile(mkhe_ctx* ctx, int log_points) { MKHE_TRY({ bf_need_ctx(ctx, "mkhe_ctx_set_bfv_tile")->bfv_set_tile(log_points); }) }
+uint64_t mkhe_ctx_bfv_slot_psi(mkhe_ctx* ctx) {
+    g_last_ctx = nullptr;
+    try { return bf_need_ctx(ctx, "mkhe_ctx_bfv_slot_psi")->bfv_slot_psi(); }
+    catch (const std::exception& e) { g_err = e.what(); return 0; }
+    catch (...) { g_err = "mkhe: unknown error"; return 0; }
+}
+int mkhe_bfv_slots_to_coeffs(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_coeffs) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_slots_to_coeffs", count, dev_slots, dev_coeffs)->bfv_slots_to_coeffs(count, (const u64*)dev_slots, (u64*)dev_coeffs); })
+}
+int mkhe_bfv_coeffs_to_slots(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_slots) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_coeffs_to_slots", count, dev_coeffs, dev_slots)->bfv_coeffs_to_slots(count, (const u64*)dev_coeffs, (u64*)dev_slots); })
+}
+int mkhe_bfv_scale_up(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_pt) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_scale_up", count, dev_coeffs, dev_pt)->bfv_scale_up(count, (const u64*)dev_coeffs, (u64*)dev_pt); })
+}
+int mkhe_bfv_scale_down(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_coeffs) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_scale_down", count, dev_pt, dev_coeffs)->bfv_scale_down(count, (const u64*)dev_pt, (u64*)dev_coeffs); })
+}
+int mkhe_bfv_encode(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_pt) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_encode", count, dev_slots, dev_pt)->bfv_encode(count, (const u64*)dev_slots, (u64*)dev_pt); })
+}
+int mkhe_bfv_decode(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_slots) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_decode", count, dev_pt, dev_slots)->bfv_decode(count, (const u64*)dev_pt, (u64*)dev_slots); })
+}
+
 // ---- mkbfv
 int mkhe_ctx_create_bfv(mkhe_ctx** out, int logN, const uint64_t* Q, const uint64_t* QMul, int nQ,
                         const uint64_t* P, int nP, int gamma, uint64_t T, int device) {

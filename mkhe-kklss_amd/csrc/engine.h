@@ -20,6 +20,7 @@
 #include "keygen_kernels.h"
 #include "encdec_kernels.h"
 #include "ckks_kernels.h"
+#include "bfv_kernels.h"
 
 namespace mkhe {
 
@@ -29,6 +30,10 @@ int ab_fuse_y();
 int ab_fuse_e();
 
 struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
+// host number theory of engine.hip that the encoders share: Miller-Rabin for 64-bit n, and the engine's choice of a primitive 2N-th root
+// (g the smallest generator >= 3 of Z_q*, psi = g^((q-1)/2N)); q must be a prime = 1 mod 2N
+bool is_prime(u64 n);
+u64 default_psi(u64 q, u64 N);
 
 #define MKHE_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw ::mkhe::Error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
@@ -254,6 +259,20 @@ class Context {
     int ckks_tile();
     void ckks_set_tile(int log_points);
 
+    // ---- BFV batch encoder (bfv_encode.hip, bfv_kernels.h): N slots over Z_T.  Device buffers: slots int64[count][N], coeffs uint64[count][N] (< T),
+    // pt uint64[count][nq][N] (coefficient domain, canonical).  encode = scale_up(slots_to_coeffs), decode = coeffs_to_slots(scale_down).
+    void bfv_slots_to_coeffs(int count, const u64* slots, u64* coeffs);
+    void bfv_coeffs_to_slots(int count, const u64* coeffs, u64* slots);
+    void bfv_scale_up(int count, const u64* coeffs, u64* pt);
+    void bfv_scale_down(int count, const u64* pt, u64* coeffs);
+    void bfv_encode(int count, const u64* slots, u64* pt);
+    void bfv_decode(int count, const u64* pt, u64* slots);
+    // log2 of the largest transform one workgroup does in LDS (BF_TILE_LOG_BIG, or BF_TILE_LOG_DEF when the runtime grants no more LDS), and a way
+    // to lower it (BF_TILE_LOG_MIN .. the grant; 0: back to the grant) so that the two-launch form can be run at small N
+    int bfv_tile();
+    void bfv_set_tile(int log_points);
+    u64 bfv_slot_psi();
+
     bool overlap = true;               // false: everything on the main stream (clean per-kernel timings)
     u64* ntt_trace = nullptr;          // diagnostic buffer handed to the forward NTT kernels (mkhe_ntt_trace)
     // stream-ordered buffer cache for ciphertext / switching-key handles: freeing a handle does not
@@ -350,6 +369,22 @@ class Context {
     void ck_fft(bool inverse, int count, const double* in, double* out);
     void ck_scale_up(int level, int count, const double* coeffs, double scale, u64* pt);
     void ck_scale_down(int limbs, int count, const u64* pt, double scale, double* coeffs);
+    // BFV batch encoder: tables built at the first call (bf_init), scratch that holds message-derived values (zeroed behind its last use)
+    uint2 *d_bf_w = nullptr, *d_bf_winv = nullptr, *d_bf_twist = nullptr, *d_bf_itwist = nullptr, *d_bf_qlt = nullptr;
+    u32* d_bf_pos = nullptr;
+    u64 *d_bf_tinv = nullptr, *d_bf_tmont = nullptr, *d_bf_garner = nullptr;
+    BfvT bf_t_{};
+    u64 bf_psi_ = 0;
+    bool bf_ready_ = false;
+    int bf_lds_log_ = BF_TILE_LOG_DEF, bf_lds_granted_ = BF_TILE_LOG_DEF;
+    u64* bf_work_ = nullptr;  size_t bf_work_words_ = 0;
+    u64* bf_dig_ = nullptr;   size_t bf_dig_words_ = 0;
+    u64* bf_coeff_ = nullptr; size_t bf_coeff_words_ = 0;
+    void bf_init(const char* what);
+    BfvScale bf_scale() const;
+    void bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out);
+    void bf_scale_up(int count, const u64* coeffs, u64* pt);
+    void bf_scale_down(int count, const u64* pt, u64* coeffs);
 
     u64* scratch(u64*& p, size_t& have, size_t want);
     Swk& hoist_slot(int which, int idx);

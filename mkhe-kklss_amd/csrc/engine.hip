@@ -26,7 +26,7 @@ static u64 inv64(u64 q) { u64 x = q; for (int i = 0; i < 6; ++i) x *= 2 - q * x;
 static u64 to_mont(u64 a, u64 q) { return (u64)(((u128)a << 64) % q); }
 static u64 bitrev(u64 x, int bits) { u64 r = 0; for (int i = 0; i < bits; ++i) { r = (r << 1) | (x & 1); x >>= 1; } return r; }
 
-static bool is_prime(u64 n) {
+bool is_prime(u64 n) {
     if (n < 2) return false;
     for (u64 p : {2ull, 3ull, 5ull, 7ull, 11ull, 13ull, 17ull, 19ull, 23ull, 29ull, 31ull, 37ull}) if (n % p == 0) return n == p;
     u64 d = n - 1; int s = 0;
@@ -44,7 +44,7 @@ static bool is_prime(u64 n) {
 // Same choice of 2N-th root as lattigo v2.3.0 NewRing (ring/primes.go primitiveRoot: the scan
 // starts at g = 3), so that key material produced by the Go side (NTT domain) lines up when the
 // caller does not pass its own roots.
-static u64 default_psi(u64 q, u64 N) {
+u64 default_psi(u64 q, u64 N) {
     std::vector<u64> f;
     u64 n = q - 1;
     for (u64 p = 2; p * p <= n; p += (p == 2 ? 1 : 2))
@@ -511,7 +511,9 @@ void Context::release_all() noexcept {
                     (void*)d_bm_qoverqiinvqi, (void*)d_bm_qoverqimodp, (void*)d_bm_vtimes,
                     (void*)d_down_q_in_m, (void*)d_down_m_in_q, (void*)d_mform_qmul, (void*)d_t_mont,
                     (void*)kg_small_, (void*)kg_g_, (void*)kg_sk_, (void*)ed_w_, (void*)ed_small_, (void*)ed_tab_,
-                    (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)d_ck_garner, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_})
+                    (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)d_ck_garner, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_,
+                    (void*)d_bf_w, (void*)d_bf_winv, (void*)d_bf_twist, (void*)d_bf_itwist, (void*)d_bf_qlt, (void*)d_bf_pos, (void*)d_bf_tinv, (void*)d_bf_tmont,
+                    (void*)d_bf_garner, (void*)bf_work_, (void*)bf_dig_, (void*)bf_coeff_})
         if (p) (void)hipFree(p);
     for (auto& v : hoist_pool_) for (auto& s : v) if (s.d) (void)hipFree(s.d);
     for (auto& kv : f2_sched_) if (kv.second.d_segs) (void)hipFree(kv.second.d_segs);

@@ -37,6 +37,11 @@ class Parameters(mkrlwe.Parameters):
     def T(self): return self._T
     def RCount(self): return 2 * len(self.Q)
 
+    def slot_psi(self):
+        """the primitive 2N-th root of unity mod T of the slot definition (include/mkhe.h, "BFV batch encoder"): slot i is m(psi^(5^i)),
+        slot N/2 + i is m(psi^(-5^i))"""
+        return slot_psi(self._T, self.N())
+
 
 class Ciphertext(mkrlwe.Ciphertext):
     """mkbfv.Ciphertext (elements.go:5-11): always at params.MaxLevel()."""
@@ -256,8 +261,10 @@ def NewEvaluator(params):
     return Evaluator(params)
 
 
-# ---- encryptor, decryptor (mkbfv/encryptor.go, mkbfv/decryptor.go); plaintexts are RNS polynomials over Q.  Slot batching over Z_T
-# (lattigo's bfv.Encoder) is not mirrored: ScaleUp / ScaleDown below are the coefficient-wise halves of EncodeInt / DecodeInt.
+# ---- encoder, encryptor, decryptor (mkbfv/encryptor.go, mkbfv/decryptor.go, elements.go:26-28); plaintexts are RNS polynomials over Q.
+# lattigo's bfv.Encoder, which EncodeInt / DecodeInt of those files reach, is not in the reference tree: Encoder / DeviceEncoder restate the
+# mathematics of slot batching over Z_T (include/mkhe.h, "BFV batch encoder"), not lattigo's code path.  ScaleUp / ScaleDown are the
+# coefficient-wise halves of EncodeInt / DecodeInt.
 def _q_product(params):
     Q = 1
     for q in params.Q:
@@ -289,8 +296,235 @@ def ScaleDown(poly, params):
     return np.array(out, dtype=np.int64)
 
 
+def _is_prime(n):
+    if n < 2:
+        return False
+    small = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)
+    for p in small:
+        if n % p == 0:
+            return n == p
+    d, s = n - 1, 0
+    while d % 2 == 0:
+        d, s = d // 2, s + 1
+    for a in small:                                  # deterministic below 2^64
+        x = pow(a, d, n)
+        if x in (1, n - 1):
+            continue
+        for _ in range(s - 1):
+            x = x * x % n
+            if x == n - 1:
+                break
+        else:
+            return False
+    return True
+
+
+def slot_psi(T, N):
+    """the engine's choice of a primitive 2N-th root of unity (csrc/engine.hip default_psi) for the plaintext modulus: g the smallest
+    generator >= 3 of Z_T*, psi = g^((T-1)/2N).  Raises where the encoder calls of the C ABI do."""
+    T, N = int(T), int(N)
+    if T >= 1 << 32:
+        raise MkheError("mkbfv encoder: the plaintext modulus must be below 2^32")
+    if not _is_prime(T):
+        raise MkheError("mkbfv encoder: the plaintext modulus must be prime")
+    if (T - 1) % (2 * N):
+        raise MkheError("mkbfv encoder: the plaintext modulus must be 1 mod 2N")
+    f, n, p = [], T - 1, 2
+    while p * p <= n:
+        if n % p == 0:
+            f.append(p)
+            while n % p == 0:
+                n //= p
+        p += 1 if p == 2 else 2
+    if n > 1:
+        f.append(n)
+    g = 3
+    while any(pow(g, (T - 1) // q, T) == 1 for q in f):
+        g += 1
+    return pow(g, (T - 1) // (2 * N), T)
+
+
+def slot_exponents(logN):
+    """e with slot j = m(psi^e[j]): e[i] = 5^i mod 2N, e[N/2 + i] = 2N - e[i] (two rows of N/2: lattigo's index matrix)"""
+    N = 1 << logN
+    e, g = np.empty(N, dtype=np.int64), 1
+    for i in range(N // 2):
+        e[i], e[N // 2 + i], g = g, 2 * N - g, g * mkrlwe.GALOIS_GEN % (2 * N)
+    return e
+
+
+class Message:
+    """mkbfv.Message (elements.go:26-28): Value []int64, one value per slot"""
+
+    def __init__(self, value):
+        self.Value = np.asarray(value, dtype=np.int64)
+
+    def Slots(self):
+        return len(self.Value)
+
+
+def NewMessage(params):
+    return Message(np.zeros(params.N(), dtype=np.int64))
+
+
+class Encoder:
+    """Exact host model of the batch encoder (numpy, uint64 arithmetic mod T < 2^32): slots <-> coefficients by a negacyclic number-theoretic
+    transform mod T, then ScaleUp / ScaleDown.  `params` needs N(), LogN(), T() and Q only."""
+
+    def __init__(self, params):
+        self.params = params
+        self.N, self.logN, self.T = params.N(), params.LogN(), int(params.T())
+        N, T = self.N, self.T
+        self.psi = slot_psi(T, N)
+        k = np.arange(N, dtype=object)
+        pw = lambda b: np.array([pow(b, int(i), T) for i in k], dtype=np.uint64)      # (N modular powers, once per encoder)
+        psi_inv = pow(self.psi, -1, T)
+        self._twist, self._itwist = pw(self.psi), pw(psi_inv) * np.uint64(pow(N, -1, T)) % np.uint64(T)
+        self._w, self._winv = pw(self.psi * self.psi % T)[: N // 2], pw(psi_inv * psi_inv % T)[: N // 2]
+        self._t = (slot_exponents(self.logN) - 1) // 2                                # slot j is bin t[j] of the cyclic transform
+
+    def _dft(self, a, w):
+        """X[k] = sum_j a_j w^(jk) mod T, natural order in and out: radix-2 decimation in time on a bit-reversed copy"""
+        N, T = self.N, np.uint64(self.T)
+        rev = np.zeros(N, dtype=np.int64)
+        for b in range(self.logN):
+            rev |= ((np.arange(N) >> b) & 1) << (self.logN - 1 - b)
+        a = a[rev].copy()
+        h = 1
+        while h < N:
+            a = a.reshape(-1, 2, h)
+            tw = w[:: N // (2 * h)][:h]
+            x = a[:, 1, :] * tw % T
+            a = np.stack([(a[:, 0, :] + x) % T, (a[:, 0, :] + T - x) % T], axis=1).reshape(-1)
+            h *= 2
+        return a
+
+    def residues(self, values):
+        """int64 message values -> residues in [0, T) as uint64"""
+        v = np.asarray(values, dtype=np.int64)
+        if v.shape != (self.N,):
+            raise MkheError("mkbfv.Encoder: expected %d slots, got %r" % (self.N, v.shape))
+        return np.mod(v, np.int64(self.T)).astype(np.uint64)
+
+    def SlotsToCoeffs(self, values):
+        """slots int64 [N] -> coefficients uint64 [N] in [0, T)"""
+        z = np.zeros(self.N, dtype=np.uint64)
+        z[self._t] = self.residues(values)
+        return self._dft(z, self._winv) * self._itwist % np.uint64(self.T)
+
+    def CoeffsToSlots(self, coeffs):
+        """coefficients mod T [N] -> slots int64 [N], centred in (-T/2, T/2]"""
+        T = np.uint64(self.T)
+        m = np.asarray(coeffs, dtype=np.uint64) % T
+        z = self._dft(m * self._twist % T, self._w)[self._t].astype(np.int64)
+        return np.where(z > self.T // 2, z - self.T, z)
+
+    def Encode(self, values):
+        """slots int64 [N] -> RNS plaintext uint64 [nQ][N] (EncodeInt of encryptor.go:38-41)"""
+        return ScaleUp(self.SlotsToCoeffs(values), self.params)
+
+    def Decode(self, poly):
+        """RNS plaintext [nQ][N] (canonical residues) -> slots int64 [N], centred (DecodeInt of decryptor.go:52-54)"""
+        return self.CoeffsToSlots(np.mod(ScaleDown(poly, self.params), np.int64(self.T)).astype(np.uint64))
+
+
+class DeviceEncoder:
+    """The interface of Encoder on the DEVICE (mkhe_bfv_*: csrc/bfv_kernels.hip), plus batch forms.  Messages go up and come down as N int64
+    slots; plaintexts stay resident as mkrlwe.DeviceLimbs [count][nQ][N].  Integer arithmetic throughout: the same bits as Encoder."""
+
+    def __init__(self, params):
+        self.params = params
+        self.N = params.N()
+
+    def _rows(self, a, dtype, what):
+        """-> (array [count][N] of dtype, whether the caller passed one row)"""
+        a = np.asarray(a, dtype=dtype)
+        one = a.ndim == 1
+        a = a[None] if one else a
+        if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != self.N:
+            raise MkheError("mkbfv.DeviceEncoder: expected %d %s per message, got %r" % (self.N, what, a.shape))
+        return np.ascontiguousarray(a), one
+
+    def _up(self, a):
+        return mkrlwe.DeviceLimbs(self.params, len(a), 1).upload(a.view(np.uint64).reshape(len(a), 1, self.N))
+
+    def _stage(self, fn, src, limbs_out, dtype, one):
+        dst = mkrlwe.DeviceLimbs(self.params, src.count, limbs_out)
+        check(fn(self.params.ctx, src.count, src.devptr(), dst.devptr()))
+        if dtype is None:                                # a plaintext: stays on the device
+            return dst
+        out = dst.download().view(dtype).reshape(src.count, self.N)
+        return out[0] if one else out
+
+    def SlotsToCoeffs(self, values):
+        """slots int64 [N] (or [count][N]) -> coefficients uint64 in [0, T)"""
+        z, one = self._rows(values, np.int64, "slots")
+        return self._stage(lib().mkhe_bfv_slots_to_coeffs, self._up(z), 1, np.uint64, one)
+
+    def CoeffsToSlots(self, coeffs):
+        """coefficients uint64 [N] (or [count][N]) -> slots int64, centred"""
+        m, one = self._rows(coeffs, np.uint64, "coefficients")
+        return self._stage(lib().mkhe_bfv_coeffs_to_slots, self._up(m), 1, np.int64, one)
+
+    def ScaleUp(self, coeffs):
+        """coefficients uint64 [N] (or [count][N]) -> device plaintexts [count][nQ][N]"""
+        m, _ = self._rows(coeffs, np.uint64, "coefficients")
+        return self._stage(lib().mkhe_bfv_scale_up, self._up(m), self.params.QCount(), None, False)
+
+    def _plaintexts(self, poly):
+        if not isinstance(poly, mkrlwe.DeviceLimbs):
+            poly = np.ascontiguousarray(poly, dtype=np.uint64)
+            poly = poly[None] if poly.ndim == 2 else poly
+            poly = mkrlwe.DeviceLimbs(self.params, poly.shape[0], poly.shape[1]).upload(poly)
+        if poly.limbs != self.params.QCount():
+            raise MkheError("mkbfv.DeviceEncoder: a BFV plaintext has %d limbs, got %d" % (self.params.QCount(), poly.limbs))
+        return poly
+
+    def ScaleDown(self, poly):
+        """device plaintext(s) [count][nQ][N] (or a host polynomial) -> coefficients uint64 in [0, T) (not centred)"""
+        poly = self._plaintexts(poly)
+        return self._stage(lib().mkhe_bfv_scale_down, poly, 1, np.uint64, poly.count == 1)
+
+    def EncodeBatch(self, values):
+        """count messages -> device plaintexts [count][nQ][N] (coefficient domain, canonical) as one launch set"""
+        z, _ = self._rows(values, np.int64, "slots")
+        return self._stage(lib().mkhe_bfv_encode, self._up(z), self.params.QCount(), None, False)
+
+    def Encode(self, values):
+        """-> device plaintext [1][nQ][N]: what mkrlwe.Encryptor.Encrypt takes as it is"""
+        z, one = self._rows(values, np.int64, "slots")
+        if not one:
+            raise MkheError("mkbfv.DeviceEncoder: Encode takes one message (EncodeBatch takes several)")
+        return self.EncodeBatch(z)
+
+    def Decode(self, poly):
+        """device plaintext(s) [count][nQ][N] (or a host polynomial [nQ][N]) -> slots int64 [N] ([count][N] for count > 1), centred"""
+        poly = self._plaintexts(poly)
+        return self._stage(lib().mkhe_bfv_decode, poly, 1, np.int64, poly.count == 1)
+
+
+def _encoder(params, which):
+    if which not in ("host", "device"):
+        raise MkheError("mkbfv: encoder must be \"host\" or \"device\"")
+    return Encoder(params) if which == "host" else DeviceEncoder(params)
+
+
 class Encryptor(mkrlwe.Encryptor):
-    """mkbfv.Encryptor (encryptor.go:7-25)"""
+    """mkbfv.Encryptor (encryptor.go:7-25): mkrlwe.Encryptor + the encoder.  encoder="host" (default): the numpy Encoder, whose plaintext
+    is uploaded; "device": DeviceEncoder, whose plaintext goes to mkhe_encrypt without touching the host.  The encoder is built at its
+    first use, so that EncryptPtxt works for every plaintext modulus the context accepts."""
+
+    def __init__(self, params, sampler=None, encoder="host"):
+        super().__init__(params, sampler)
+        if encoder not in ("host", "device"):
+            raise MkheError("mkbfv: encoder must be \"host\" or \"device\"")
+        self._which, self._encoder = encoder, None
+
+    @property
+    def encoder(self):
+        if self._encoder is None:
+            self._encoder = _encoder(self.params, self._which)
+        return self._encoder
 
     def _new_batch(self, id, level, count, like=None):
         return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [id], level, count)
@@ -299,21 +533,57 @@ class Encryptor(mkrlwe.Encryptor):
         """encryptor.go:30-32 on a fresh ciphertext over {pk.ID} (EncryptMsgNew :47-51 without the encoder)"""
         return self.Encrypt(pt_rns, pk, NewCiphertext(self.params, [pk.ID], zero=False), samples)
 
+    def EncryptMsg(self, msg, pk, ctOut, samples=None):
+        """encryptor.go:38-41: EncodeInt, then Encrypt"""
+        return self.Encrypt(self.encoder.Encode(msg.Value), pk, ctOut, samples)
 
-def NewEncryptor(params, sampler=None):
-    return Encryptor(params, sampler)
+    def EncryptMsgNew(self, msg, pk, samples=None):
+        """encryptor.go:47-51"""
+        return self.EncryptMsg(msg, pk, NewCiphertext(self.params, [pk.ID], zero=False), samples)
+
+    def EncryptMsgBatch(self, msgs, pk, samples=None):
+        """EncryptMsgNew for several messages under one public key: one encode (one launch set with the device encoder) and one
+        mkhe_encrypt call"""
+        if isinstance(self.encoder, DeviceEncoder):
+            pts = self.encoder.EncodeBatch(np.stack([m.Value for m in msgs]))
+        else:
+            pts = np.stack([self.encoder.Encode(m.Value) for m in msgs])
+        return self.EncryptBatch(pts, pk, samples)
+
+
+def NewEncryptor(params, sampler=None, encoder="host"):
+    return Encryptor(params, sampler, encoder)
 
 
 class Decryptor(mkrlwe.Decryptor):
-    """mkbfv.Decryptor (decryptor.go:6-24)"""
+    """mkbfv.Decryptor (decryptor.go:6-24); the encoder as for Encryptor"""
+
+    def __init__(self, params, encoder="host"):
+        super().__init__(params)
+        if encoder not in ("host", "device"):
+            raise MkheError("mkbfv: encoder must be \"host\" or \"device\"")
+        self._which, self._encoder = encoder, None
+
+    @property
+    def encoder(self):
+        if self._encoder is None:
+            self._encoder = _encoder(self.params, self._which)
+        return self._encoder
 
     def _like(self, ct, ids):
         return NewCiphertext(self.params, ids, zero=False)
 
     def DecryptPtxt(self, ct, skSet):
         """decryptor.go:34-53 up to the decoder -> RNS polynomial uint64 [nQ][N], canonical"""
-        return self.Decrypt(ct, skSet).download()[0]
+        return mkrlwe.Decryptor.Decrypt(self, ct, skSet).download()[0]
+
+    def Decrypt(self, ct, skSet):
+        """decryptor.go:31-56 -> Message.  With the device encoder the output buffer of mkhe_decrypt goes straight to mkhe_bfv_decode: only
+        the slots come down."""
+        if isinstance(self.encoder, DeviceEncoder):
+            return Message(self.encoder.Decode(mkrlwe.Decryptor.Decrypt(self, ct, skSet)))
+        return Message(self.encoder.Decode(self.DecryptPtxt(ct, skSet)))
 
 
-def NewDecryptor(params):
-    return Decryptor(params)
+def NewDecryptor(params, encoder="host"):
+    return Decryptor(params, encoder)
