@@ -9,30 +9,13 @@
 //   encode, decode    single-workgroup form: ONE launch, scale_up in the store of the inverse transform resp. scale_down in the load of the
 //                     forward one; two-launch form: the stage launches around the coefficient scratch bf_coeff_ [count][N].  The same bits.
 // bf_work_, bf_dig_ and bf_coeff_ hold message-derived values and are zeroed behind their last use.  The tables (twiddles, twists, permutation,
-// Garner and scaling constants) are built at the first call: the calls allocate and upload, so the C ABI refuses them inside a capture.
+// scaling constants; the Garner constants of Context::garner_table) are built at the first call: the calls allocate and upload, so the C ABI refuses them inside a capture.
 #include "engine.h"
+#include "host_modarith.h"
 
 namespace mkhe {
 
-static u64 mulmod(u64 a, u64 b, u64 q) { return (u64)((unsigned __int128)a * b % q); }
-static u64 powmod(u64 a, u64 e, u64 q) { u64 r = 1; for (a %= q; e; e >>= 1, a = mulmod(a, a, q)) if (e & 1) r = mulmod(r, a, q); return r; }
-static u64 to_mont(u64 a, u64 q) { return (u64)((((unsigned __int128)a) << 64) % q); }
 static uint2 shoup(u64 w, u64 T) { return uint2{(u32)w, (u32)((w << 32) / T)}; }
-
-namespace {
-// device tables that are released again when the build fails half way
-struct Uploads {
-    std::vector<void*> p;
-    template <class E> E* add(const std::vector<E>& v) {
-        E* d = nullptr;
-        MKHE_HIP(hipMalloc(&d, v.size() * sizeof(E)));
-        p.push_back(d);
-        MKHE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
-        return d;
-    }
-    void drop() noexcept { for (void* d : p) (void)hipFree(d); p.clear(); }
-};
-}
 
 void Context::bf_init(const char* what) {
     const std::string w(what);
@@ -52,18 +35,8 @@ void Context::bf_init(const char* what) {
     for (u64 k = 0; k < n / 2; ++k, a = mulmod(a, om, T), b = mulmod(b, om_inv, T)) { tw[k] = shoup(a, T); twi[k] = shoup(b, T); }
     a = 1; b = n_inv;
     for (u64 k = 0; k < n; ++k, a = mulmod(a, psi, T), b = mulmod(b, psi_inv, T)) { twist[k] = shoup(a, T); itwist[k] = shoup(b, T); }
-    // position p of the in-place transform holds X[bitrev(p)]; slot j is X[t_j], t_j = (e_j - 1) / 2, e_j = 5^j resp. -5^(j - N/2) mod 2N
-    std::vector<u32> pos(n);
-    u64 g = 1;
-    for (u64 j = 0; j < n / 2; ++j, g = g * 5 % (2 * n))
-        for (int row = 0; row < 2; ++row) {
-            const u32 t = (u32)(((row ? 2 * n - g : g) - 1) / 2);
-            u32 p = 0;
-            for (int bit = 0; bit < logN; ++bit) p |= ((t >> bit) & 1u) << (logN - 1 - bit);
-            pos[p] = (u32)(j + (row ? n / 2 : 0));
-        }
-    // per limb of Q: MForm(T^-1), MForm(T), q_l mod T; MForm(q_i^-1 mod q_j), i < j
-    std::vector<u64> tinv(nq), tmont(nq), garner((size_t)nq * nq, 0);
+    // per limb of Q: MForm(T^-1), MForm(T), q_l mod T
+    std::vector<u64> tinv(nq), tmont(nq);
     std::vector<uint2> qlt(nq);
     u64 qmod = 1;
     for (int l = 0; l < nq; ++l) {
@@ -72,7 +45,6 @@ void Context::bf_init(const char* what) {
         tmont[l] = to_mont(T % q, q);
         qlt[l] = shoup(q % T, T);
         qmod = mulmod(qmod, q % T, T);
-        for (int j = l + 1; j < nq; ++j) garner[(size_t)l * nq + j] = to_mont(powmod(q % moduli[j], moduli[j] - 2, moduli[j]), moduli[j]);
     }
     BfvT t{};
     t.T = (u32)T; t.half = (u32)(T / 2);
@@ -83,29 +55,27 @@ void Context::bf_init(const char* what) {
     const u64 c32 = (1ull << 32) % T;
     t.c32 = (u32)c32; t.c32_s = shoup(c32, T).y;
     t.one_s = shoup(1, T).y;
+    garner_table();
     Uploads up;
     try {
         d_bf_w = up.add(tw); d_bf_winv = up.add(twi); d_bf_twist = up.add(twist); d_bf_itwist = up.add(itwist); d_bf_qlt = up.add(qlt);
-        d_bf_pos = up.add(pos); d_bf_tinv = up.add(tinv); d_bf_tmont = up.add(tmont); d_bf_garner = up.add(garner);
+        d_bf_pos = up.add(slot_positions(logN, 1, true)); d_bf_tinv = up.add(tinv); d_bf_tmont = up.add(tmont);
     } catch (...) {
         up.drop();
-        d_bf_w = d_bf_winv = d_bf_twist = d_bf_itwist = d_bf_qlt = nullptr; d_bf_pos = nullptr; d_bf_tinv = d_bf_tmont = d_bf_garner = nullptr;
+        d_bf_w = d_bf_winv = d_bf_twist = d_bf_itwist = d_bf_qlt = nullptr; d_bf_pos = nullptr; d_bf_tinv = d_bf_tmont = nullptr;
         throw;
     }
     bf_t_ = t; bf_psi_ = psi;
-    bf_lds_log_ = bf_lds_granted_ = bf_ntt_big_lds() ? BF_TILE_LOG_BIG : BF_TILE_LOG_DEF;
+    bf_tile_.log = bf_tile_.granted = bf_ntt_big_lds() ? BF_TILE_LOG_BIG : BF_TILE_LOG_DEF;
     bf_ready_ = true;
 }
 int Context::bfv_tile() {
     bf_init("mkhe_ctx_bfv_tile");
-    return bf_lds_log_;
+    return bf_tile_.log;
 }
 void Context::bfv_set_tile(int log_points) {
     bf_init("mkhe_ctx_set_bfv_tile");
-    if (log_points != 0 && (log_points < BF_TILE_LOG_MIN || log_points > bf_lds_granted_))
-        throw Error("mkhe_ctx_set_bfv_tile: the limit is " + std::to_string(BF_TILE_LOG_MIN) + " .. what the runtime granted (" + std::to_string(bf_lds_granted_) +
-                    "), or 0 for the latter");
-    bf_lds_log_ = log_points ? log_points : bf_lds_granted_;
+    bf_tile_.set(log_points, BF_TILE_LOG_MIN, bf_tile_.granted, "mkhe_ctx_set_bfv_tile: the limit is " + std::to_string(BF_TILE_LOG_MIN) + " .. ");
 }
 u64 Context::bfv_slot_psi() {
     bf_init("mkhe_ctx_bfv_slot_psi");
@@ -113,7 +83,7 @@ u64 Context::bfv_slot_psi() {
 }
 BfvScale Context::bf_scale() const {
     BfvScale sc{};
-    sc.t = bf_t_; sc.mods = d_mods; sc.tinv_mont = d_bf_tinv; sc.t_mont = d_bf_tmont; sc.garner = d_bf_garner; sc.qlt = d_bf_qlt;
+    sc.t = bf_t_; sc.mods = d_mods; sc.tinv_mont = d_bf_tinv; sc.t_mont = d_bf_tmont; sc.garner = d_garner_; sc.qlt = d_bf_qlt;
     sc.limbs = nq; sc.N = N;
     return sc;
 }
@@ -123,11 +93,11 @@ void Context::bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out
     const size_t n = (size_t)N;
     BfvNtt a{};
     a.w = inverse ? d_bf_winv : d_bf_w; a.twist = inverse ? d_bf_itwist : d_bf_twist; a.pos = d_bf_pos;
-    a.logn = logN; a.sc = bf_scale();
+    a.p.logn = logN; a.sc = bf_scale();
     const double tables = 8.0 * n + 4.0 * n + 4.0 * n;                          // twist, twiddles, permutation
-    if (logN <= bf_lds_log_) {
+    if (logN <= bf_tile_.log) {
         a.in = in; a.out = out;
-        a.logt = logN; a.first = a.last = 1; a.fuse = fuse ? 1 : 0;
+        a.p.logt = logN; a.p.first = a.p.last = 1; a.fuse = fuse ? 1 : 0;
         const size_t words = (size_t)count * nq * n;
         if (fuse && !inverse) a.dig = scratch(bf_dig_, bf_dig_words_, words);
         {
@@ -146,15 +116,11 @@ void Context::bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out
     a.in = in; a.out = fuse && inverse ? coeff : out;
     const size_t wwords = (cwords + 1) / 2;                                     // 32-bit words
     a.work = reinterpret_cast<u32*>(scratch(bf_work_, bf_work_words_, wwords));
-    a.logt = std::min(bf_lds_log_, BF_TILE_LOG_MULTI);
-    const int rows_log = logN - a.logt;
-    // forward: the stages that span the rows first; inverse: last
-    for (int pass = 0; pass < 2; ++pass) {
-        a.first = pass == 0; a.last = pass == 1;
-        a.a_log = (pass == 0) != inverse ? rows_log : 0;
+    a.p.logt = std::min(bf_tile_.log, BF_TILE_LOG_MULTI);
+    tile_two_pass(a.p, inverse, logN - a.p.logt, [&] {
         ProfScope ps(this, PROF_OTHER, 8.0 * n * count + 4.0 * n * count + tables / 2);
         launch_bf_ntt(inverse, a, count, s_);
-    }
+    });
     MKHE_HIP(hipMemsetAsync(a.work, 0, wwords * sizeof(u64), s_));
     if (fuse && inverse) bf_scale_up(count, coeff, out);
     if (fuse) MKHE_HIP(hipMemsetAsync(coeff, 0, cwords * sizeof(u64), s_));

@@ -16,12 +16,9 @@
 // sums are formed in 64 bits, differences wrap mod 2^32 (a - b + T is exact for a < b), products are Shoup products: a table entry is the pair
 // (w, floor(w 2^32 / T)), q = hi32(a w'), r = a w - q T in [0, 2T) as a 64-bit value, one conditional subtraction.  Nothing is lazy.
 //
-// One workgroup transforms a TILE of 2^logt words in LDS.  N <= the LDS limit (2^15 words = 128 KiB, or 2^14 when the runtime grants no more than
-// the default): one tile = one message, one launch.  Larger N, or a lowered limit: two launches over a work buffer in global memory; N = A * B,
-// A = 2^a_log:
-//     column tile       A rows x (2^logt / A) adjacent columns of the A x B matrix: the a_log stages that span B and more
-//     contiguous tile   2^logt adjacent points: the stages below
-// The stages of span 8 .. 1 of a contiguous tile run on 16 adjacent elements per thread in registers (four 16-byte LDS accesses each way).
+// The transform itself is the tile transform of tile_transform.h (one workgroup per tile of 2^logt points in LDS, one launch for N up to the LDS limit
+// -- 2^15 words = 128 KiB, or 2^14 when the runtime grants no more than the default -- or a lowered limit, else two) on 32-bit words: 16 elements per
+// thread, the register stages with four 16-byte LDS accesses each way.
 // LDS layout: element l = 16 c + 4 u + e (chunk c, 16-byte unit u < 4) sits in unit u ^ f(c) of its chunk, f(c) = ((c >> 2) & 3) ^ (c & 2).
 //   16-byte reads are served in four groups of 16 lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32) out of the 16 units of a 256-byte
 //   bank row: lane c reads unit 4 (c & 3) + (u ^ f(c)); among the lanes of a group with equal c & 3 (c >> 2 is {0,3,5,6} or {1,2,4,7}) (c >> 2) & 3
@@ -31,6 +28,7 @@
 //   units inside a chunk); the one pass over the spans 32 and 16 of a contiguous tile puts two chunks of equal parity under 32 lanes: two-way.
 #pragma once
 #include "modarith.h"
+#include "tile_pass.h"
 
 namespace mkhe {
 
@@ -54,7 +52,7 @@ struct BfvScale {
     const Mod* mods;
     const u64* tinv_mont;       // [limbs]  MForm(T^-1 mod q_l)
     const u64* t_mont;          // [limbs]  MForm(T mod q_l)
-    const u64* garner;          // [limbs][limbs]  MForm(q_i^-1 mod q_j) at i * limbs + j, i < j
+    const u64* garner;          // [limbs][limbs]  Context::garner_table (limbs = nq)
     const uint2* qlt;           // [limbs]  (q_l mod T, companion)
     int limbs, N;
 };
@@ -67,9 +65,7 @@ struct BfvNtt {
     const uint2* w;         // [N/2]: omega^k (forward) / omega^-k (inverse) with companions
     const uint2* twist;     // [N]: psi^k (forward) / psi^-k N^-1 (inverse) with companions
     const u32* pos;         // [N]: slot index of position p
-    int logn, logt;
-    int a_log;              // > 0: column tiles of 2^a_log rows
-    int first, last;        // this launch reads the caller's input / writes the caller's output
+    TilePass p;             // logn = log2 N
     int fuse;               // single-launch only: scale_down on the load (forward) / scale_up on the store (inverse)
     BfvScale sc;
 };

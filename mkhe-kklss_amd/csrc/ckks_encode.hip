@@ -8,8 +8,9 @@
 //   scale_up          one launch;   scale_down   one launch, with the digit scratch ck_dig_ [count][limbs][N]
 //   encode = scale_up(embed), decode = project(scale_down): the same launches around the coefficient scratch ck_coeff_ [count][N]
 // ck_work_, ck_dig_ and ck_coeff_ hold message-derived values and are zeroed behind their last use.  The tables (twiddles, twist,
-// permutation, Garner constants) are built at the first call: the calls allocate and upload, so the C ABI refuses them inside a capture.
+// permutation; the Garner constants of Context::garner_table) are built at the first call: the calls allocate and upload, so the C ABI refuses them inside a capture.
 #include "engine.h"
+#include "host_modarith.h"
 #include <cmath>
 
 namespace mkhe {
@@ -32,17 +33,6 @@ static void unit_root(long k, long M, double& re, double& im) {
     }
 }
 
-static u64 mulmod(u64 a, u64 b, u64 q) { return (u64)((unsigned __int128)a * b % q); }
-static u64 powmod(u64 a, u64 e, u64 q) { u64 r = 1; for (a %= q; e; e >>= 1, a = mulmod(a, a, q)) if (e & 1) r = mulmod(r, a, q); return r; }
-
-template <class T> static T* ck_upload(const std::vector<T>& v) {
-    T* d = nullptr;
-    MKHE_HIP(hipMalloc(&d, v.size() * sizeof(T)));
-    const hipError_t e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); throw Error(std::string("mkhe: upload of the encoder tables: ") + hipGetErrorString(e)); }
-    return d;
-}
-
 void Context::ck_init(const char* what) {
     if (masked_) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
     if (ck_ready_) return;
@@ -52,38 +42,20 @@ void Context::ck_init(const char* what) {
     std::vector<double> w(n), twist(2 * n);
     for (long k = 0; k < n / 2; ++k) unit_root(k, n, w[2 * k], w[2 * k + 1]);
     for (long k = 0; k < n; ++k) unit_root(k, 4 * n, twist[2 * k], twist[2 * k + 1]);          // xi = exp(i pi / N) = exp(2 pi i / 4n)
-    // position p of the in-place transform holds X[bitrev(p)]; slot j is X[t_j], t_j = (5^j mod 2N - 1) / 4
-    std::vector<u32> pos(n);
-    u64 g = 1;
-    for (long j = 0; j < n; ++j, g = g * 5 % (4 * n)) {
-        u32 t = (u32)((g - 1) / 4), p = 0;
-        for (int b = 0; b < logn; ++b) p |= ((t >> b) & 1u) << (logn - 1 - b);
-        pos[p] = (u32)j;
-    }
-    // MForm(q_i^-1 mod q_j), i < j
-    std::vector<u64> garner((size_t)nq * nq, 0);
-    for (int i = 0; i < nq; ++i)
-        for (int j = i + 1; j < nq; ++j) {
-            const u64 qi = moduli[i], qj = moduli[j], inv = powmod(qi % qj, qj - 2, qj);
-            garner[(size_t)i * nq + j] = (u64)((((unsigned __int128)inv) << 64) % qj);
-        }
-    double *dw = nullptr, *dt = nullptr; u32* dp = nullptr; u64* dg = nullptr;
-    try { dw = ck_upload(w); dt = ck_upload(twist); dp = ck_upload(pos); dg = ck_upload(garner); }
-    catch (...) { for (void* p : {(void*)dw, (void*)dt, (void*)dp, (void*)dg}) if (p) (void)hipFree(p); throw; }
-    d_ck_w = dw; d_ck_twist = dt; d_ck_pos = dp; d_ck_garner = dg;
-    ck_lds_log_ = ck_lds_granted_ = ck_fft_big_lds() ? CK_TILE_LOG_BIG : CK_TILE_LOG;
+    garner_table();
+    Uploads up;
+    try { d_ck_w = up.add(w); d_ck_twist = up.add(twist); d_ck_pos = up.add(slot_positions(logN, 2, false)); }
+    catch (...) { up.drop(); d_ck_w = d_ck_twist = nullptr; d_ck_pos = nullptr; throw; }
+    ck_tile_.log = ck_tile_.granted = ck_fft_big_lds() ? CK_TILE_LOG_BIG : CK_TILE_LOG;
     ck_ready_ = true;
 }
 int Context::ckks_tile() {
     ck_init("mkhe_ctx_ckks_tile");
-    return ck_lds_log_;
+    return ck_tile_.log;
 }
 void Context::ckks_set_tile(int log_points) {
     ck_init("mkhe_ctx_set_ckks_tile");
-    if (log_points != 0 && log_points != CK_TILE_LOG && log_points != ck_lds_granted_)
-        throw Error("mkhe_ctx_set_ckks_tile: the limit is " + std::to_string(CK_TILE_LOG) + ", what the runtime granted (" + std::to_string(ck_lds_granted_) +
-                    "), or 0 for the latter");
-    ck_lds_log_ = log_points ? log_points : ck_lds_granted_;
+    ck_tile_.set(log_points, CK_TILE_LOG, CK_TILE_LOG, "mkhe_ctx_set_ckks_tile: the limit is " + std::to_string(CK_TILE_LOG) + ", ");
 }
 
 // the transform of `count` messages: in / out as CkFft::in / out
@@ -93,24 +65,20 @@ void Context::ck_fft(bool inverse, int count, const double* in, double* out) {
     CkFft a{};
     a.in = in; a.out = out;
     a.w = reinterpret_cast<const double2*>(d_ck_w); a.twist = reinterpret_cast<const double2*>(d_ck_twist); a.pos = d_ck_pos;
-    a.logn = logn;
+    a.p.logn = logn;
     const double io = 32.0 * n * count + 16.0 * n + 8.0 * n + 4.0 * n;        // slots + coefficients; twist, twiddles, permutation
-    if (logn <= ck_lds_log_) {
-        a.logt = logn; a.first = a.last = 1;
+    if (logn <= ck_tile_.log) {
+        a.p.logt = logn; a.p.first = a.p.last = 1;
         ProfScope ps(this, PROF_OTHER, io);
         launch_ck_fft(inverse, a, count, s_);
         return;
     }
     a.work = reinterpret_cast<double2*>(scratch(ck_work_, ck_work_words_, 2 * (size_t)n * count));
-    a.logt = CK_TILE_LOG;
-    const int rows_log = logn - CK_TILE_LOG;
-    // forward: the stages that span the rows first; inverse: last
-    for (int pass = 0; pass < 2; ++pass) {
-        a.first = pass == 0; a.last = pass == 1;
-        a.a_log = (pass == 0) != inverse ? rows_log : 0;
+    a.p.logt = CK_TILE_LOG;
+    tile_two_pass(a.p, inverse, logn - CK_TILE_LOG, [&] {
         ProfScope ps(this, PROF_OTHER, io / 2 + 16.0 * n * count);
         launch_ck_fft(inverse, a, count, s_);
-    }
+    });
     MKHE_HIP(hipMemsetAsync(ck_work_, 0, 2 * (size_t)n * count * sizeof(u64), s_));
 }
 
@@ -135,7 +103,7 @@ void Context::ck_scale_down(int limbs, int count, const u64* pt, double scale, d
     {
         // every digit is written once and read by each later limb, by the sign decision and by the sum
         ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * limbs * (2.0 + (limbs - 1) / 2.0 + 2.0)));
-        launch_ck_scale_down(count, pt, scale, coeffs, dig, d_ck_garner, nq, d_mods, limbs, N, s_);
+        launch_ck_scale_down(count, pt, scale, coeffs, dig, d_garner_, nq, d_mods, limbs, N, s_);
     }
     MKHE_HIP(hipMemsetAsync(dig, 0, words * sizeof(u64), s_));
 }

@@ -11,10 +11,8 @@
 // is folded into the permutation table pos (position p <-> slot pos[p], t_(pos[p]) = bitrev(p)), and twist and permutation are
 // part of the first load and the last store.  Arithmetic is IEEE float64 without contraction; the tables are rounded once from long double.
 //
-// One workgroup transforms a TILE of 2^logt points in LDS (16-byte accesses).  n <= the LDS limit: one tile = one message, one launch.
-// Larger n: two launches over a work buffer in global memory; n = A * B, A = 2^a_log:
-//     column tile   A rows x (2^logt / A) adjacent columns of the A x B matrix: the a_log stages that span B and more
-//     contiguous tile   2^logt adjacent points: the stages below
+// The transform itself is the tile transform of tile_transform.h (one workgroup per tile of 2^logt points in LDS, one launch for n up to the LDS
+// limit, else two) on complex float64 elements: 16-byte LDS accesses, 8 elements per thread.
 // LDS layout: element l = 16 c + k (chunk c, k < 16) sits in 16-byte slot k ^ f(c & 15) of its chunk, f(c) = c ^ ((c & 4) << 1).  The LDS
 // serves a 16-byte read (ds_read_b128) in four groups of 16 lanes, {0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32, each out of
 // the 16 slots of the 256-byte bank row, and a 16-byte write in groups of 8 adjacent lanes out of 8 slots.  Write A for the slots
@@ -29,6 +27,7 @@
 // all conflict-free for the reads; the load phase's writes of stride two are two-way.  The XOR costs no LDS, so 2^13 points fit 128 KiB.
 #pragma once
 #include "modarith.h"
+#include "tile_pass.h"
 
 namespace mkhe {
 
@@ -42,9 +41,7 @@ struct CkFft {
     const double2* w;       // [n/2]: omega^k
     const double2* twist;   // [n]: xi^k
     const u32* pos;         // [n]: slot index of position p
-    int logn, logt;
-    int a_log;              // > 0: column tiles of 2^a_log rows
-    int first, last;        // this launch reads the caller's input / writes the caller's output
+    TilePass p;             // logn = log2 n
 };
 
 // asks for CK_TILE_LOG_BIG tiles (dynamic LDS beyond the default limit); false: the runtime refused, keep to CK_TILE_LOG
@@ -64,7 +61,7 @@ void launch_ck_scale_up(int count, const double* coeffs, double scale, u64* pt, 
 // float64 from the top digit, signed and divided by scale.  Roundings on the largest term: the conversion of the top digit; per lower
 // limb the conversion of q_i (q_i < 2^60 is not a double), the multiply and the add; the + 1 of a negative value; the division: 3 limbs in
 // all (the lower digits' conversions are relative to smaller terms), every term non-negative, so the relative error is below
-// (1 + u)^(3 limbs) - 1 < 4 limbs 2^-53.  A magnitude beyond the range of float64 gives +-inf, never NaN.  garner[i * nq + j] = MForm(q_i^-1 mod q_j).
+// (1 + u)^(3 limbs) - 1 < 4 limbs 2^-53.  A magnitude beyond the range of float64 gives +-inf, never NaN.  garner: Context::garner_table.
 // pt must hold canonical residues.
 void launch_ck_scale_down(int count, const u64* pt, double scale, double* coeffs, u64* dig, const u64* garner, int nq, const Mod* mods, int limbs, int N,
                           hipStream_t st);

@@ -37,6 +37,25 @@ u64 default_psi(u64 q, u64 N);
 
 #define MKHE_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw ::mkhe::Error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
+// device tables of one build step that are released again when the step fails half way: add() every table, drop() in the handler
+struct Uploads {
+    std::vector<void*> p;
+    template <class E> E* add(const std::vector<E>& v) {
+        E* d = nullptr;
+        MKHE_HIP(hipMalloc(&d, v.size() * sizeof(E)));
+        p.push_back(d);
+        MKHE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
+        return d;
+    }
+    void drop() noexcept { for (void* d : p) (void)hipFree(d); p.clear(); }
+};
+// log2 of the largest tile one workgroup of an encoder's transform takes (tile_transform.h): what the runtime granted at the first call, and the
+// limit in force.  set: 0 (back to the grant), the grant itself, or lo .. hi; anything else throws `what` + the closing words on the grant
+struct TileLimit {
+    int log, granted;
+    void set(int log_points, int lo, int hi, const std::string& what);
+};
+
 // device SwitchingKey / hoisted digit vector: uint64[betaMax][nQ+nP][N]
 struct Swk { u64* d = nullptr; bool owned = true; };
 // device ciphertext: uint64[1+n][limbs][N], slot 0 = c_0, slot 1+i = party ids[i]
@@ -357,11 +376,22 @@ class Context {
     const u64** ed_tab_ = nullptr; size_t ed_tab_n_ = 0;
     EdTable ed_table(const std::vector<const u64*>& v, size_t tab_offset);
     void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
-    // CKKS encoder: tables built at the first call (twiddles [n/2][2], twist [n][2], permutation [n], Garner constants [nq][nq]), the largest
+    // both encoders: the Garner constants [nq][nq], built at the first use, and the two launches of a transform that one tile does not hold:
+    // forward the pass over the column tiles (the stages that span the rows) first, inverse last; launch() runs once per pass on the filled-in p
+    u64* d_garner_ = nullptr;
+    const u64* garner_table();
+    template <class F> static void tile_two_pass(TilePass& p, bool inverse, int rows_log, F launch) {
+        for (int pass = 0; pass < 2; ++pass) {
+            p.first = pass == 0; p.last = pass == 1;
+            p.a_log = (pass == 0) != inverse ? rows_log : 0;
+            launch();
+        }
+    }
+    // CKKS encoder: tables built at the first call (twiddles [n/2][2], twist [n][2], permutation [n]), the largest
     // FFT one workgroup does in LDS, and the scratch for the two-launch FFT, the Garner digits and the coefficients of the fused calls
-    double *d_ck_w = nullptr, *d_ck_twist = nullptr; u32* d_ck_pos = nullptr; u64* d_ck_garner = nullptr;
+    double *d_ck_w = nullptr, *d_ck_twist = nullptr; u32* d_ck_pos = nullptr;
     bool ck_ready_ = false;
-    int ck_lds_log_ = CK_TILE_LOG, ck_lds_granted_ = CK_TILE_LOG;
+    TileLimit ck_tile_{CK_TILE_LOG, CK_TILE_LOG};
     u64* ck_work_ = nullptr;  size_t ck_work_words_ = 0;
     u64* ck_dig_ = nullptr;   size_t ck_dig_words_ = 0;
     u64* ck_coeff_ = nullptr; size_t ck_coeff_words_ = 0;
@@ -372,11 +402,11 @@ class Context {
     // BFV batch encoder: tables built at the first call (bf_init), scratch that holds message-derived values (zeroed behind its last use)
     uint2 *d_bf_w = nullptr, *d_bf_winv = nullptr, *d_bf_twist = nullptr, *d_bf_itwist = nullptr, *d_bf_qlt = nullptr;
     u32* d_bf_pos = nullptr;
-    u64 *d_bf_tinv = nullptr, *d_bf_tmont = nullptr, *d_bf_garner = nullptr;
+    u64 *d_bf_tinv = nullptr, *d_bf_tmont = nullptr;
     BfvT bf_t_{};
     u64 bf_psi_ = 0;
     bool bf_ready_ = false;
-    int bf_lds_log_ = BF_TILE_LOG_DEF, bf_lds_granted_ = BF_TILE_LOG_DEF;
+    TileLimit bf_tile_{BF_TILE_LOG_DEF, BF_TILE_LOG_DEF};
     u64* bf_work_ = nullptr;  size_t bf_work_words_ = 0;
     u64* bf_dig_ = nullptr;   size_t bf_dig_words_ = 0;
     u64* bf_coeff_ = nullptr; size_t bf_coeff_words_ = 0;

@@ -1,6 +1,7 @@
 // engine.hip -- Context: host-side table generation, buffer pools, stream plumbing, the NTT launch choice, Decompose and the external-product batch
 // (engine_mulrelin.hip, engine_ops.hip, engine_bfv.hip, batch.hip hold the operations built on them).
 #include "engine.h"
+#include "host_modarith.h"
 #include <atomic>
 #include <mutex>
 #include <algorithm>
@@ -13,19 +14,7 @@ int ab_fuse_x() { static const int v = MKHE_AB_INT("MKHE_FUSE_X", 1); return v; 
 int ab_fuse_y() { static const int v = MKHE_AB_INT("MKHE_FUSE_Y", 1); return v; }
 int ab_fuse_e() { static const int v = MKHE_AB_INT("MKHE_FUSE_E", 1); return v; }
 
-typedef unsigned __int128 u128;
-
-// ------------------------------------------------------------------ host number theory
-static u64 mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
-static u64 powmod(u64 x, u64 e, u64 q) {
-    u64 r = 1 % q; x %= q;
-    for (; e; e >>= 1) { if (e & 1) r = mulmod(r, x, q); x = mulmod(x, x, q); }
-    return r;
-}
-static u64 inv64(u64 q) { u64 x = q; for (int i = 0; i < 6; ++i) x *= 2 - q * x; return x; }   // q^-1 mod 2^64 (Newton)
-static u64 to_mont(u64 a, u64 q) { return (u64)(((u128)a << 64) % q); }
-static u64 bitrev(u64 x, int bits) { u64 r = 0; for (int i = 0; i < bits; ++i) { r = (r << 1) | (x & 1); x >>= 1; } return r; }
-
+// ------------------------------------------------------------------ host number theory (host_modarith.h holds the arithmetic)
 bool is_prime(u64 n) {
     if (n < 2) return false;
     for (u64 p : {2ull, 3ull, 5ull, 7ull, 11ull, 13ull, 17ull, 19ull, 23ull, 29ull, 31ull, 37ull}) if (n % p == 0) return n == p;
@@ -492,6 +481,23 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
     invntt_ = dev_alloc_words((size_t)nq * N);
 }
 
+// MForm(q_i^-1 mod q_j) at i * nq + j, i < j: the constants of the mixed-radix digits (modarith.h garner_digits) both encoders' scale_down use
+const u64* Context::garner_table() {
+    if (d_garner_) return d_garner_;
+    std::vector<u64> g((size_t)nq * nq, 0);
+    for (int i = 0; i < nq; ++i)
+        for (int j = i + 1; j < nq; ++j) g[(size_t)i * nq + j] = to_mont(powmod(moduli[i] % moduli[j], moduli[j] - 2, moduli[j]), moduli[j]);
+    Uploads up;
+    try { d_garner_ = up.add(g); } catch (...) { up.drop(); throw; }
+    return d_garner_;
+}
+
+void TileLimit::set(int log_points, int lo, int hi, const std::string& what) {
+    if (log_points != 0 && log_points != granted && (log_points < lo || log_points > hi))
+        throw Error(what + "what the runtime granted (" + std::to_string(granted) + "), or 0 for the latter");
+    log = log_points ? log_points : granted;
+}
+
 Context::~Context() {
     (void)hipSetDevice(device);
     // both streams: a pool of another context skips its fence for a context that is gone ("its destructor drained its streams")
@@ -511,9 +517,9 @@ void Context::release_all() noexcept {
                     (void*)d_bm_qoverqiinvqi, (void*)d_bm_qoverqimodp, (void*)d_bm_vtimes,
                     (void*)d_down_q_in_m, (void*)d_down_m_in_q, (void*)d_mform_qmul, (void*)d_t_mont,
                     (void*)kg_small_, (void*)kg_g_, (void*)kg_sk_, (void*)ed_w_, (void*)ed_small_, (void*)ed_tab_,
-                    (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)d_ck_garner, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_,
+                    (void*)d_garner_, (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_,
                     (void*)d_bf_w, (void*)d_bf_winv, (void*)d_bf_twist, (void*)d_bf_itwist, (void*)d_bf_qlt, (void*)d_bf_pos, (void*)d_bf_tinv, (void*)d_bf_tmont,
-                    (void*)d_bf_garner, (void*)bf_work_, (void*)bf_dig_, (void*)bf_coeff_})
+                    (void*)bf_work_, (void*)bf_dig_, (void*)bf_coeff_})
         if (p) (void)hipFree(p);
     for (auto& v : hoist_pool_) for (auto& s : v) if (s.d) (void)hipFree(s.d);
     for (auto& kv : f2_sched_) if (kv.second.d_segs) (void)hipFree(kv.second.d_segs);

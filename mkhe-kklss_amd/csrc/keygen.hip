@@ -11,12 +11,9 @@
 // (beta*(nq+np) limbs), ONE keygen_combine pass.  Every stored value is the canonical representative the reference's
 // CRed / MRed sequence produces (Neg writes q - x, 0 -> q, like lattigo).
 #include "engine.h"
+#include "host_modarith.h"
 
 namespace mkhe {
-
-typedef unsigned __int128 u128;
-static u64 kg_mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
-static u64 kg_to_mont(u64 a, u64 q) { return (u64)(((u128)(a % q) << 64) % q); }
 
 void Context::kg_init() {
     if (kg_ready_) return;
@@ -28,8 +25,8 @@ void Context::kg_init() {
     for (int i = 0; i < beta_max; ++i)
         for (int j = i * alpha; j < std::min((i + 1) * alpha, nq); ++j) {
             u64 pm = 1;
-            for (int k = 0; k < np; ++k) pm = kg_mulmod(pm, moduli[nq + k] % moduli[j], moduli[j]);
-            g[(size_t)i * mtot + j] = kg_to_mont(pm, moduli[j]);
+            for (int k = 0; k < np; ++k) pm = mulmod(pm, moduli[nq + k] % moduli[j], moduli[j]);
+            g[(size_t)i * mtot + j] = to_mont(pm, moduli[j]);
         }
     MKHE_HIP(hipMemcpy(kg_g_, g.data(), g.size() * sizeof(u64), hipMemcpyHostToDevice));
     kg_ready_ = true;
@@ -45,7 +42,7 @@ void Context::kg_upload_g(const u64* g_plain) {
     kg_init();
     std::vector<u64> g((size_t)beta_max * mtot);
     for (int i = 0; i < beta_max; ++i)
-        for (int j = 0; j < mtot; ++j) g[(size_t)i * mtot + j] = kg_to_mont(g_plain[(size_t)i * mtot + j], moduli[j]);
+        for (int j = 0; j < mtot; ++j) g[(size_t)i * mtot + j] = to_mont(g_plain[(size_t)i * mtot + j], moduli[j]);
     MKHE_HIP(hipMemcpyAsync(kg_g_ + (size_t)beta_max * mtot, g.data(), g.size() * sizeof(u64), hipMemcpyHostToDevice, stream));
     sync();
 }

@@ -147,4 +147,19 @@ __device__ __forceinline__ void mul64x64(u64 a, u64 b, u64& hi, u64& lo) {
 }
 __device__ __forceinline__ u64 mulhi64(u64 a, u64 b) { u64 h, l; mul64x64(a, b, h, l); return h; }
 
+// Mixed-radix (Garner) digits of the x in [0, Q), Q = q_0 .. q_(limbs-1), whose canonical residue mod q_j is first(j, mods[j]):
+// x = d_0 + d_1 q_0 + d_2 q_0 q_1 + .., d_j = (..((x_j - d_0) q_0^-1 - d_1) q_1^-1 .. - d_(j-1)) q_(j-1)^-1 mod q_j.  d: this coefficient's column of
+// a digit scratch with limb stride N; garner[i * nq + j] = MForm(q_i^-1 mod q_j), i < j (Context::garner_table).
+template <class First> __device__ __forceinline__ void garner_digits(First first, u64* d, const u64* garner, int nq, const Mod* mods, int limbs, long N) {
+    for (int j = 0; j < limbs; ++j) {
+        const Mod md = mods[j];
+        u64 t = first(j, md);
+        for (int i = 0; i < j; ++i) {
+            const u64 di = mont_mul(d[i * N], md.r1, md.q, md.ninv32);                           // d_i mod q_j
+            t = mont_mul(t >= di ? t - di : t + md.q - di, garner[i * nq + j], md.q, md.ninv32);
+        }
+        d[j * N] = t;
+    }
+}
+
 }  // namespace mkhe
