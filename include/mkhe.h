@@ -457,6 +457,35 @@ int  mkhe_ctx_set_bfv_tile(mkhe_ctx* ctx, int log_points);
 /* psi of the definitions above; 0 = error (the same conditions as the encoder calls) */
 uint64_t mkhe_ctx_bfv_slot_psi(mkhe_ctx* ctx);
 
+/* ==== BFV plaintext operands: AddPtxt, SubPtxt, MulPtxt ===============================================
+ * No reference counterpart: mkbfv.Evaluator of the reference has no operation with a plaintext operand; the definitions are this project's own, in
+ * the terms of the "BFV batch encoder" section above, whose preconditions (BFV context, T prime, T = 1 mod 2N, T < 2^32, 1 <= count <= 65535,
+ * non-null 16-byte-aligned device buffers, not inside a capture, not on a context that owns a subset of the moduli) and refusals apply.
+ *   lift      for m = coeffs[b][k] mod T the centred representative c = m (m <= floor(T/2)) or m - T: what mkhe_bfv_decode returns.
+ *             ptmul_coeff[b][l][k] = MForm(c mod q_l): the canonical residue of c under EVERY limb (q_l may be smaller than T), in the engine's
+ *             2^64 Montgomery form (lattigo ring.MForm).  Coefficient domain.
+ *   ptmul     uint64[count][nQ][N], the PREPARED multiplication plaintext: the forward NTT over Q (mkhe_ntt) of the lift, limb by limb, still in
+ *             Montgomery form.  The NTT is Z_q-linear, so it equals MForm(NTT(c mod q_l)).
+ *   pt        uint64[count][nQ][N], the scaled plaintext of mkhe_bfv_encode (coefficient domain, canonical): the operand of add / sub.
+ * Why the product is right: with pt(a) = round(Q a / T) and p the centred lift of b, pt(a) p = (Q/T) [a b]_T + Q k + eps p with |eps| <= 1/2 per
+ * coefficient -- no Q mod T term -- so a ciphertext of noise e decrypts after the product to a b mod T slot by slot as long as
+ * N (T/2) (|e| + 1/2) < Q / (2T).  No key is used and no party is added.
+ * Ciphertext lists: nbatch ciphertexts that share their ids, all at the maximum level (nQ limbs), as one launch set.  out[b] has the ids of
+ * in[b]; out[b] may be in[b]; it must not be the input of another item, and the outputs are distinct.  pt_stride_words = the words between the
+ * plaintexts of consecutive items: nQ * N (one plaintext per item) or 0 (one for all); any other value is an error.  The plaintext is read where it
+ * lies.  Every error message starts with the name of the function. */
+/* stage of mkhe_bfv_encode_mul: coeffs uint64[count][N] (taken mod T) -> ptmul_coeff uint64[count][nQ][N] */
+int  mkhe_bfv_lift(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_ptmul_coeff);
+/* slots int64[count][N] -> ptmul == mkhe_ntt(mkhe_bfv_lift(mkhe_bfv_slots_to_coeffs(slots))), bit for bit: the slot transform with the lift on
+ * its store where one workgroup holds the polynomial (else the lift is a launch of its own), then ONE forward NTT of count * nQ limbs */
+int  mkhe_bfv_encode_mul(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_ptmul);
+/* out[b] = in[b] * plaintext, component by component: one forward NTT of all nbatch (1 + k) components, one product kernel
+ * MRed(component, ptmul) with the batch in its grid, one inverse NTT into the outputs; ptmul is not transformed again.  Canonical residues. */
+int  mkhe_bfv_ct_mul_ptxt(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, const void* dev_ptmul, long pt_stride_words, mkhe_ct* const* out);
+/* op 0: out[b]_0 = CRed(in[b]_0 + pt), op 1: CRed(in[b]_0 - pt); pt canonical.  The other components are copied (nothing is done for them where
+ * out[b] == in[b]).  One launch for as many items as the component list of the elementwise kernel holds (65 components). */
+int  mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out);
+
 /* ---- measurement support (no reference counterpart): HIP-event timing per kernel class on the
  *      context stream, one record per kernel launch.  Classes (mkhe_prof_name gives the kernel symbol
  *      each class corresponds to in a rocprofv3 kernel trace). */

@@ -628,10 +628,26 @@ class Evaluator {
         ksw.Conjugate(ct0, ckSet, *out);
         return out;
     }
+    // Plaintext operands (no reference counterpart; include/mkhe.h, "BFV plaintext operands").  The result carries the ids of ct: no party is added.
+    // dev_ptmul: the prepared plaintext of Encoder::EncodeMul; dev_pt: the scaled plaintext of Encoder::Encode.  uint64[nQ][N] each.
+    CiphertextPtr MulPtxtNew(const Ciphertext& ct, const void* dev_ptmul) {
+        auto out = std::make_unique<Ciphertext>(params, ct.IDSet_(), false);
+        const mkhe_ct* in = ct.h; mkhe_ct* o = out->h;
+        check(mkhe_bfv_ct_mul_ptxt(params.ctx, 1, &in, dev_ptmul, 0, &o));
+        return out;
+    }
+    CiphertextPtr AddPtxtNew(const Ciphertext& ct, const void* dev_pt) { return addPtxt(0, ct, dev_pt); }
+    CiphertextPtr SubPtxtNew(const Ciphertext& ct, const void* dev_pt) { return addPtxt(1, ct, dev_pt); }
     Parameters& params;
     mkrlwe::KeySwitcher ksw;
   private:
     CiphertextPtr bin(const Ciphertext& a, const Ciphertext& b) { return std::make_unique<Ciphertext>(params, mkrlwe::Union(a.IDSet_(), b.IDSet_()), false); }
+    CiphertextPtr addPtxt(int op, const Ciphertext& ct, const void* dev_pt) {
+        auto out = std::make_unique<Ciphertext>(params, ct.IDSet_(), false);
+        const mkhe_ct* in = ct.h; mkhe_ct* o = out->h;
+        check(mkhe_bfv_ct_add_ptxt(params.ctx, op, 1, &in, dev_pt, 0, &o));
+        return out;
+    }
 };
 // The batch encoder on the device (mkhe_bfv_encode / mkhe_bfv_decode): EncodeInt of mkbfv/encryptor.go:38-41 and DecodeInt of
 // mkbfv/decryptor.go:52-54.  lattigo's bfv.Encoder, which those lines call, is not in the reference tree: this is the mathematics of slot
@@ -652,6 +668,13 @@ class Encoder {
         mkrlwe::DeviceWords z(params, (size_t)count * params.N());
         check(mkhe_buf_upload(params.ctx, z.d, reinterpret_cast<const uint64_t*>(values), z.words));
         check(mkhe_bfv_encode(params.ctx, count, z.d, dev_pt));
+    }
+    // count messages -> dev_ptmul uint64[count][nQ][N], the prepared multiplication plaintexts (NTT over Q of the centred lift, Montgomery form):
+    // the operand of Evaluator::MulPtxtNew.  No reference counterpart.
+    void EncodeMul(int count, const int64_t* values, void* dev_ptmul) {
+        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
+        check(mkhe_buf_upload(params.ctx, z.d, reinterpret_cast<const uint64_t*>(values), z.words));
+        check(mkhe_bfv_encode_mul(params.ctx, count, z.d, dev_ptmul));
     }
     // count plaintexts -> values (host: count * Slots()), centred in (-T/2, T/2]
     void Decode(int count, const void* dev_pt, int64_t* values) {

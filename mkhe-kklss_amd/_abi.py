@@ -125,6 +125,10 @@ SIGNATURES = {
     "mkhe_bfv_scale_down": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_bfv_encode": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_bfv_decode": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_lift": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_encode_mul": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_ct_mul_ptxt": (C.c_int, [vp, C.c_int, vpp, vp, C.c_long, vpp]),
+    "mkhe_bfv_ct_add_ptxt": (C.c_int, [vp, C.c_int, C.c_int, vpp, vp, C.c_long, vpp]),
     "mkhe_ctx_bfv_tile": (C.c_int, [vp]),
     "mkhe_ctx_set_bfv_tile": (C.c_int, [vp, C.c_int]),
     "mkhe_ctx_bfv_slot_psi": (C.c_uint64, [vp]),

@@ -523,6 +523,89 @@ void Context::ct_binary_batch(int op, const std::vector<const Ct*>& a, const std
     MKHE_HIP(hipGetLastError());
 }
 
+// ---- mkbfv plaintext operands (include/mkhe.h, "BFV plaintext operands"; no reference counterpart)
+// what every call asks of its lists: one id set, every ciphertext at the maximum level, out[b] never another item's input
+void Context::bf_ptxt_shapes(const char* what, const std::vector<const Ct*>& ins, long pt_stride, const std::vector<Ct*>& outs) {
+    const std::string w(what);
+    if (ins.empty() || outs.size() != ins.size()) throw Error(w + ": one output per input, at least one");
+    if (pt_stride != 0 && pt_stride != (long)nq * N) throw Error(w + ": pt_stride_words must be 0 (one plaintext for all) or nQ * N");
+    for (size_t b = 0; b < ins.size(); ++b) {
+        if (ins[b]->limbs != nq || outs[b]->limbs != nq) throw Error(w + ": BFV ciphertexts sit at the maximum level (nQ limbs)");
+        if (ins[b]->n != ins[0]->n || ins[b]->ids != ins[0]->ids) throw Error(w + ": the ciphertexts of a list must share their ids");
+        if (outs[b]->n != ins[0]->n || outs[b]->ids != ins[0]->ids) throw Error(w + ": an output must carry the ids of the inputs");
+        for (size_t j = 0; j < ins.size(); ++j)
+            if (j != b && ins[j]->d == outs[b]->d) throw Error(w + ": output " + std::to_string(b) + " is input " + std::to_string(j) + " of another item");
+    }
+}
+
+// B plaintext products as ONE launch set: the forward NTT of all B (1 + k) components, one product kernel with the batch in the grid, the
+// inverse NTT into the outputs.  ptmul is the prepared plaintext of bfv_encode_mul (NTT domain, Montgomery form): it is not transformed again.
+void Context::bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& ins, const u64* ptmul, long pt_stride, const std::vector<Ct*>& outs) {
+    bf_init(what);
+    bf_ptxt_shapes(what, ins, pt_stride, outs);
+    const size_t B = ins.size();
+    const int L = nq, np_ = 1 + ins[0]->n;
+    if (B * np_ > 65535) throw Error(std::string(what) + ": more than 65535 polynomials in one call");
+    const size_t PO = (size_t)L * N;
+    Arena ar(this, B * np_ * PO);
+    u64* w = ar.take(B * np_ * PO);
+    for (size_t base = 0; base < B; base += NTT_MAX_ITEMS) {
+        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, B - base);
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
+        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d; b.dst_items[i] = w + (base + i) * np_ * PO; }
+        ntt_fwd_launch(b, false);
+    }
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (2.0 * B * np_ + (pt_stride ? (double)B : 1.0)));
+        launch_bf_mul_prepared(w, ptmul, pt_stride, d_mods, L, N, np_, (int)(B * np_), s_);
+    }
+    for (size_t base = 0; base < B; base += NTT_MAX_ITEMS) {
+        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, B - base);
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
+        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = w + (base + i) * np_ * PO; b.dst_items[i] = outs[base + i]->d; }
+        { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+// out_0 = CRed(c_0 +- pt), the other components copied (nothing where out == in), as components of the ct_binary kernel: the plaintext is the
+// second operand of component 0 where it lies.  As many items per launch as its component list holds.
+void Context::bfv_ct_add_ptxt(const char* what, int op, const std::vector<const Ct*>& ins, const u64* pt, long pt_stride, const std::vector<Ct*>& outs) {
+    bf_init(what);
+    bf_ptxt_shapes(what, ins, pt_stride, outs);
+    const int L = nq, n = ins[0]->n;
+    if (1 + n > CTBIN_MAX) throw Error(std::string(what) + ": too many parties in one ciphertext");
+    const size_t PO = (size_t)L * N;
+    CtBinArgs ba{};
+    ba.mods = d_mods; ba.L = L; ba.N = N;
+    int c = 0;
+    double bytes = 0;
+    auto flush = [&] {
+        if (!c) return;
+        ba.ncomp = c;
+        { ProfScope ps(this, PROF_OTHER, bytes); launch_ct_binary(ba, s_); }
+        c = 0; bytes = 0;
+    };
+    for (size_t b = 0; b < ins.size(); ++b) {
+        const bool copy = outs[b]->d != ins[b]->d;
+        if (c + 1 + (copy ? n : 0) > CTBIN_MAX) flush();
+        ba.a[c] = ins[b]->d; ba.b[c] = pt + b * (size_t)pt_stride; ba.dst[c] = outs[b]->d; ba.mode[c] = op == 0 ? 0 : 1;
+        ++c; bytes += 24.0 * N * L;
+        for (int k = 1; copy && k <= n; ++k, ++c) {
+            ba.a[c] = ins[b]->d + k * PO; ba.b[c] = nullptr; ba.dst[c] = outs[b]->d + k * PO; ba.mode[c] = 2;
+            bytes += 16.0 * N * L;
+        }
+    }
+    flush();
+    MKHE_HIP(hipGetLastError());
+}
+
 // mkckks.Evaluator.MulPtxtNew (mkckks/evaluator.go:465-481) on B inputs: NTT of the plaintext once, of every component of every input in one
 // launch, one product launch, one inverse launch, and the nb divisions of the Rescale that follows (:480) with one launch each for the batch.
 void Context::ct_mul_ptxt_batch(const std::vector<const Ct*>& ins, const u64* dev_pt, int nb, const std::vector<Ct*>& outs) {

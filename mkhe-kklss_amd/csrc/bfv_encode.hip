@@ -8,7 +8,11 @@
 //   scale_up          one launch;   scale_down   one launch, with the digit scratch bf_dig_ [count][nq][N]
 //   encode, decode    single-workgroup form: ONE launch, scale_up in the store of the inverse transform resp. scale_down in the load of the
 //                     forward one; two-launch form: the stage launches around the coefficient scratch bf_coeff_ [count][N].  The same bits.
-// bf_work_, bf_dig_ and bf_coeff_ hold message-derived values and are zeroed behind their last use.  The tables (twiddles, twists, permutation,
+//   encode_mul        the inverse transform with the lift (launch_bf_lift) in its store -- or, two-launch form, the lift as its own launch behind
+//                     bf_coeff_ -- into bf_lift_ [count][nq][N], then ONE forward NTT over Q (Context::ntt) of its count * nq limbs into the caller's
+//                     buffer.  That NTT is Z_q-linear, so the lift is written in Montgomery form at once and the prepared plaintext needs no
+//                     launch of its own for it.
+// bf_work_, bf_dig_, bf_coeff_ and bf_lift_ hold message-derived values and are zeroed behind their last use.  The tables (twiddles, twists, permutation,
 // scaling constants; the Garner constants of Context::garner_table) are built at the first call: the calls allocate and upload, so the C ABI refuses them inside a capture.
 #include "engine.h"
 #include "host_modarith.h"
@@ -88,8 +92,9 @@ BfvScale Context::bf_scale() const {
     return sc;
 }
 
-// the transform of `count` messages: in / out as BfvNtt::in / out.  fuse: in (forward) resp. out (inverse) is the RNS plaintext.
-void Context::bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out) {
+// the transform of `count` messages: in / out as BfvNtt::in / out.  fuse (BF_FUSE_*): in (forward) resp. out (inverse) is the RNS plaintext,
+// BF_FUSE_LIFT (inverse only): out is the multiplication plaintext in the coefficient domain.
+void Context::bf_ntt(bool inverse, int fuse, int count, const u64* in, u64* out) {
     const size_t n = (size_t)N;
     BfvNtt a{};
     a.w = inverse ? d_bf_winv : d_bf_w; a.twist = inverse ? d_bf_itwist : d_bf_twist; a.pos = d_bf_pos;
@@ -97,7 +102,7 @@ void Context::bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out
     const double tables = 8.0 * n + 4.0 * n + 4.0 * n;                          // twist, twiddles, permutation
     if (logN <= bf_tile_.log) {
         a.in = in; a.out = out;
-        a.p.logt = logN; a.p.first = a.p.last = 1; a.fuse = fuse ? 1 : 0;
+        a.p.logt = logN; a.p.first = a.p.last = 1; a.fuse = fuse;
         const size_t words = (size_t)count * nq * n;
         if (fuse && !inverse) a.dig = scratch(bf_dig_, bf_dig_words_, words);
         {
@@ -122,12 +127,17 @@ void Context::bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out
         launch_bf_ntt(inverse, a, count, s_);
     });
     MKHE_HIP(hipMemsetAsync(a.work, 0, wwords * sizeof(u64), s_));
-    if (fuse && inverse) bf_scale_up(count, coeff, out);
+    if (fuse == BF_FUSE_LIFT) bf_lift(count, coeff, out);
+    else if (fuse && inverse) bf_scale_up(count, coeff, out);
     if (fuse) MKHE_HIP(hipMemsetAsync(coeff, 0, cwords * sizeof(u64), s_));
 }
 void Context::bf_scale_up(int count, const u64* coeffs, u64* pt) {
     ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * nq));
     launch_bf_scale_up(count, coeffs, pt, bf_scale(), s_);
+}
+void Context::bf_lift(int count, const u64* coeffs, u64* ptmul) {
+    ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * nq));
+    launch_bf_lift(count, coeffs, ptmul, bf_scale(), s_);
 }
 void Context::bf_scale_down(int count, const u64* pt, u64* coeffs) {
     const size_t words = (size_t)count * nq * N;
@@ -142,12 +152,12 @@ void Context::bf_scale_down(int count, const u64* pt, u64* coeffs) {
 
 void Context::bfv_slots_to_coeffs(int count, const u64* slots, u64* coeffs) {
     bf_init("mkhe_bfv_slots_to_coeffs");
-    bf_ntt(true, false, count, slots, coeffs);
+    bf_ntt(true, BF_FUSE_NONE, count, slots, coeffs);
     MKHE_HIP(hipGetLastError());
 }
 void Context::bfv_coeffs_to_slots(int count, const u64* coeffs, u64* slots) {
     bf_init("mkhe_bfv_coeffs_to_slots");
-    bf_ntt(false, false, count, coeffs, slots);
+    bf_ntt(false, BF_FUSE_NONE, count, coeffs, slots);
     MKHE_HIP(hipGetLastError());
 }
 void Context::bfv_scale_up(int count, const u64* coeffs, u64* pt) {
@@ -162,12 +172,26 @@ void Context::bfv_scale_down(int count, const u64* pt, u64* coeffs) {
 }
 void Context::bfv_encode(int count, const u64* slots, u64* pt) {
     bf_init("mkhe_bfv_encode");
-    bf_ntt(true, true, count, slots, pt);
+    bf_ntt(true, BF_FUSE_SCALE, count, slots, pt);
     MKHE_HIP(hipGetLastError());
 }
 void Context::bfv_decode(int count, const u64* pt, u64* slots) {
     bf_init("mkhe_bfv_decode");
-    bf_ntt(false, true, count, pt, slots);
+    bf_ntt(false, BF_FUSE_SCALE, count, pt, slots);
+    MKHE_HIP(hipGetLastError());
+}
+void Context::bfv_lift(int count, const u64* coeffs, u64* ptmul_coeff) {
+    bf_init("mkhe_bfv_lift");
+    bf_lift(count, coeffs, ptmul_coeff);
+    MKHE_HIP(hipGetLastError());
+}
+void Context::bfv_encode_mul(int count, const u64* slots, u64* ptmul) {
+    bf_init("mkhe_bfv_encode_mul");
+    const size_t words = (size_t)count * nq * N;
+    u64* lift = scratch(bf_lift_, bf_lift_words_, words);                       // (the forward NTT is not asked to run in place)
+    bf_ntt(true, BF_FUSE_LIFT, count, slots, lift);
+    ntt(lift, ptmul, count, nq, 0, false, false);
+    MKHE_HIP(hipMemsetAsync(lift, 0, words * sizeof(u64), s_));
     MKHE_HIP(hipGetLastError());
 }
 

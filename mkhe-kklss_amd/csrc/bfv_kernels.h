@@ -57,6 +57,7 @@ struct BfvScale {
     int limbs, N;
 };
 
+constexpr int BF_FUSE_NONE = 0, BF_FUSE_SCALE = 1, BF_FUSE_LIFT = 2;
 struct BfvNtt {
     const u64* in;          // first launch: inverse: slots int64 [count][N]; forward: coeffs uint64 [count][N] (fuse: pt [count][limbs][N])
     u64* out;               // last launch: inverse: coeffs uint64 [count][N] (fuse: pt); forward: slots int64 [count][N]
@@ -66,7 +67,8 @@ struct BfvNtt {
     const uint2* twist;     // [N]: psi^k (forward) / psi^-k N^-1 (inverse) with companions
     const u32* pos;         // [N]: slot index of position p
     TilePass p;             // logn = log2 N
-    int fuse;               // single-launch only: scale_down on the load (forward) / scale_up on the store (inverse)
+    int fuse;               // single-launch only: BF_FUSE_SCALE = scale_down on the load (forward) / scale_up on the store (inverse);
+                            // BF_FUSE_LIFT (inverse only) = the lift of launch_bf_lift on the store, out = ptmul [count][limbs][N]
     BfvScale sc;
 };
 
@@ -83,5 +85,17 @@ void launch_bf_scale_up(int count, const u64* coeffs, u64* pt, const BfvScale& s
 // mod Q limb by limb (floor(Q/2) = (q_l - 1) / 2 mod q_l as Q is odd), its mixed-radix (Garner) digits d_i into dig [count][limbs][N]
 // (r = d_0 + d_1 q_0 + d_2 q_0 q_1 + ..), r mod T by Horner over the digits, result (floor(Q/2) - r) Q^-1 mod T.  No floating point.
 void launch_bf_scale_down(int count, const u64* pt, u64* coeffs, u64* dig, const BfvScale& sc, hipStream_t st);
+
+
+// ---- plaintext operands (include/mkhe.h, "BFV plaintext operands"; no reference counterpart)
+// ptmul[b][l][n] = MForm(c mod q_l), c the centred representative of m = coeffs[b][n] mod T (c = m for m <= floor(T/2), else m - T): the
+// multiplication plaintext in the coefficient domain, in the engine's 2^64 Montgomery form.  |c| is reduced by the Montgomery product itself
+// (|c| 2^128 2^-64 mod q_l), so q_l may be smaller than T.  One thread per PAIR of coefficients (16-byte accesses), looping over the limbs.
+void launch_bf_lift(int count, const u64* coeffs, u64* ptmul, const BfvScale& sc, hipStream_t st);
+
+// w[z][l][n] = MRed(w[z][l][n], pt[(z / per_item) * pt_stride + l * N + n]) for npolys polynomials w of L limbs, in place: the NTT-domain product
+// of every component of every ciphertext of a batch (per_item = 1 + k components each) with its prepared plaintext; pt_stride = 0: one
+// plaintext for all.  pt is in Montgomery form, so the result is the plain canonical product.  The batch is grid.z: one launch.
+void launch_bf_mul_prepared(u64* w, const u64* pt, long pt_stride, const Mod* mods, int L, int N, int per_item, int npolys, hipStream_t st);
 
 }  // namespace mkhe

@@ -36,6 +36,15 @@ __device__ __forceinline__ void bf_scale_up_one(const BfvScale& sc, u32 m, u64* 
         pt[(long)l * sc.N] = (neg && v) ? md.q - v : v;
     }
 }
+// the lift of one coefficient (bfv_kernels.h): limb l of MForm(centred m)
+__device__ __forceinline__ u64 bf_lift_limb(u32 m, const BfvT& t, const Mod& md) {
+    const bool neg = m > t.half;
+    const u64 v = mont_mul(neg ? t.T - m : m, md.r2, md.q, md.ninv32);    // |c| 2^64 mod q_l, for any size of q_l against T
+    return (neg && v) ? md.q - v : v;
+}
+__device__ __forceinline__ void bf_lift_one(const BfvScale& sc, u32 m, u64* pt) {
+    for (int l = 0; l < sc.limbs; ++l) pt[(long)l * sc.N] = bf_lift_limb(m, sc.t, sc.mods[l]);
+}
 __device__ __forceinline__ u32 bf_scale_down_one(const BfvScale& sc, const u64* x, u64* d) {
     const BfvT& t = sc.t;
     const int L = sc.limbs;
@@ -108,7 +117,8 @@ template <bool INV> __global__ void __launch_bounds__(1024) bf_ntt_kernel(BfvNtt
         if (!a.p.last) work[g] = v;
         else if (INV) {
             const u32 m = bf_mul(v, a.twist[g], T);
-            if (a.fuse) bf_scale_up_one(a.sc, m, a.out + (long)b * a.sc.limbs * n + g);
+            if (a.fuse == BF_FUSE_LIFT) bf_lift_one(a.sc, m, a.out + (long)b * a.sc.limbs * n + g);
+            else if (a.fuse) bf_scale_up_one(a.sc, m, a.out + (long)b * a.sc.limbs * n + g);
             else a.out[(long)b * n + g] = m;
         } else a.out[(long)b * n + a.pos[g]] = (u64)bf_centre(v, a.sc.t);
     }
@@ -141,6 +151,36 @@ __global__ void __launch_bounds__(BF_THREADS) bf_scale_down_kernel(const u64* pt
 }
 void launch_bf_scale_down(int count, const u64* pt, u64* coeffs, u64* dig, const BfvScale& sc, hipStream_t st) {
     hipLaunchKernelGGL(bf_scale_down_kernel, dim3((sc.N + BF_THREADS - 1) / BF_THREADS, count), dim3(BF_THREADS), 0, st, pt, coeffs, dig, sc);
+}
+
+
+__global__ void __launch_bounds__(BF_THREADS) bf_lift_kernel(const u64* coeffs, u64* ptmul, BfvScale sc) {
+    const int n = 2 * (blockIdx.x * BF_THREADS + threadIdx.x), b = blockIdx.y;
+    if (n >= sc.N) return;                                                 // (N is even: a pair never straddles the end)
+    const ulonglong2 c = *reinterpret_cast<const ulonglong2*>(coeffs + (long)b * sc.N + n);
+    const u32 m0 = bf_reduce64(c.x, sc.t), m1 = bf_reduce64(c.y, sc.t);
+    u64* out = ptmul + (long)b * sc.limbs * sc.N + n;
+    for (int l = 0; l < sc.limbs; ++l) {
+        const Mod md = sc.mods[l];
+        *reinterpret_cast<ulonglong2*>(out + (long)l * sc.N) = ulonglong2{bf_lift_limb(m0, sc.t, md), bf_lift_limb(m1, sc.t, md)};
+    }
+}
+void launch_bf_lift(int count, const u64* coeffs, u64* ptmul, const BfvScale& sc, hipStream_t st) {
+    hipLaunchKernelGGL(bf_lift_kernel, dim3((sc.N / 2 + BF_THREADS - 1) / BF_THREADS, count), dim3(BF_THREADS), 0, st, coeffs, ptmul, sc);
+}
+
+__global__ void __launch_bounds__(BF_THREADS) bf_mul_prepared_kernel(u64* w, const u64* pt, long pt_stride, const Mod* mods, int L, int N, int per_item) {
+    const int l = blockIdx.y, z = blockIdx.z;
+    const Mod md = mods[l];
+    ulonglong2* x = reinterpret_cast<ulonglong2*>(w + ((long)z * L + l) * N);
+    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(pt + (long)(z / per_item) * pt_stride + (long)l * N);
+    for (int i = blockIdx.x * BF_THREADS + threadIdx.x; i < N / 2; i += gridDim.x * BF_THREADS) {
+        const ulonglong2 a = x[i], b = p[i];
+        x[i] = ulonglong2{mont_mul(a.x, b.x, md.q, md.ninv32), mont_mul(a.y, b.y, md.q, md.ninv32)};
+    }
+}
+void launch_bf_mul_prepared(u64* w, const u64* pt, long pt_stride, const Mod* mods, int L, int N, int per_item, int npolys, hipStream_t st) {
+    hipLaunchKernelGGL(bf_mul_prepared_kernel, dim3((N / 2 + BF_THREADS - 1) / BF_THREADS, L, npolys), dim3(BF_THREADS), 0, st, w, pt, pt_stride, mods, L, N, per_item);
 }
 
 }  // namespace mkhe

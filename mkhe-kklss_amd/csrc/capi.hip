@@ -783,6 +783,31 @@ int mkhe_bfv_encode(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_p
 int mkhe_bfv_decode(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_slots) {
     MKHE_TRY({ bf_need(ctx, "mkhe_bfv_decode", count, dev_pt, dev_slots)->bfv_decode(count, (const u64*)dev_pt, (u64*)dev_slots); })
 }
+int mkhe_bfv_lift(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_ptmul_coeff) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_lift", count, dev_coeffs, dev_ptmul_coeff)->bfv_lift(count, (const u64*)dev_coeffs, (u64*)dev_ptmul_coeff); })
+}
+int mkhe_bfv_encode_mul(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_ptmul) {
+    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_encode_mul", count, dev_slots, dev_ptmul)->bfv_encode_mul(count, (const u64*)dev_slots, (u64*)dev_ptmul); })
+}
+int mkhe_bfv_ct_mul_ptxt(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, const void* dev_ptmul, long pt_stride_words, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_ct_mul_ptxt";
+        Context* c = bf_need(ctx, what, nbatch, dev_ptmul, dev_ptmul);
+        auto i = ct_list(ctx, in, nbatch, what);
+        auto o = ct_list_out(ctx, out, nbatch, what);
+        c->bfv_ct_mul_ptxt(what, i, (const u64*)dev_ptmul, pt_stride_words, o);
+    })
+}
+int mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_ct_add_ptxt";
+        Context* c = bf_need(ctx, what, nbatch, dev_pt, dev_pt);
+        if (op != 0 && op != 1) throw Error(std::string(what) + ": op must be 0 (add) or 1 (sub)");
+        auto i = ct_list(ctx, in, nbatch, what);
+        auto o = ct_list_out(ctx, out, nbatch, what);
+        c->bfv_ct_add_ptxt(what, op, i, (const u64*)dev_pt, pt_stride_words, o);
+    })
+}
 
 // ---- mkbfv
 int mkhe_ctx_create_bfv(mkhe_ctx** out, int logN, const uint64_t* Q, const uint64_t* QMul, int nQ,

@@ -286,6 +286,14 @@ class Context {
     void bfv_scale_down(int count, const u64* pt, u64* coeffs);
     void bfv_encode(int count, const u64* slots, u64* pt);
     void bfv_decode(int count, const u64* pt, u64* slots);
+    // plaintext operands: ptmul = uint64[count][nQ][N], Montgomery form (bfv_kernels.h); bfv_lift leaves the coefficient domain, bfv_encode_mul the
+    // NTT domain (the prepared plaintext of bfv_ct_mul_ptxt)
+    void bfv_lift(int count, const u64* coeffs, u64* ptmul_coeff);
+    void bfv_encode_mul(int count, const u64* slots, u64* ptmul);
+    // MulPtxt / AddPtxt / SubPtxt on B ciphertexts of one shape at the maximum level (batch.hip); pt_stride = words between the plaintexts of
+    // consecutive items, 0 = one plaintext for all.  what = the C entry point, for the messages.
+    void bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& ins, const u64* ptmul, long pt_stride, const std::vector<Ct*>& outs);
+    void bfv_ct_add_ptxt(const char* what, int op, const std::vector<const Ct*>& ins, const u64* pt, long pt_stride, const std::vector<Ct*>& outs);
     // log2 of the largest transform one workgroup does in LDS (BF_TILE_LOG_BIG, or BF_TILE_LOG_DEF when the runtime grants no more LDS), and a way
     // to lower it (BF_TILE_LOG_MIN .. the grant; 0: back to the grant) so that the two-launch form can be run at small N
     int bfv_tile();
@@ -410,10 +418,13 @@ class Context {
     u64* bf_work_ = nullptr;  size_t bf_work_words_ = 0;
     u64* bf_dig_ = nullptr;   size_t bf_dig_words_ = 0;
     u64* bf_coeff_ = nullptr; size_t bf_coeff_words_ = 0;
+    u64* bf_lift_ = nullptr;  size_t bf_lift_words_ = 0;
     void bf_init(const char* what);
     BfvScale bf_scale() const;
-    void bf_ntt(bool inverse, bool fuse, int count, const u64* in, u64* out);
+    void bf_ntt(bool inverse, int fuse, int count, const u64* in, u64* out);
     void bf_scale_up(int count, const u64* coeffs, u64* pt);
+    void bf_lift(int count, const u64* coeffs, u64* ptmul);
+    void bf_ptxt_shapes(const char* what, const std::vector<const Ct*>& ins, long pt_stride, const std::vector<Ct*>& outs);
     void bf_scale_down(int count, const u64* pt, u64* coeffs);
 
     u64* scratch(u64*& p, size_t& have, size_t want);

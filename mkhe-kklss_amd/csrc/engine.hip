@@ -519,7 +519,7 @@ void Context::release_all() noexcept {
                     (void*)kg_small_, (void*)kg_g_, (void*)kg_sk_, (void*)ed_w_, (void*)ed_small_, (void*)ed_tab_,
                     (void*)d_garner_, (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_,
                     (void*)d_bf_w, (void*)d_bf_winv, (void*)d_bf_twist, (void*)d_bf_itwist, (void*)d_bf_qlt, (void*)d_bf_pos, (void*)d_bf_tinv, (void*)d_bf_tmont,
-                    (void*)bf_work_, (void*)bf_dig_, (void*)bf_coeff_})
+                    (void*)bf_work_, (void*)bf_dig_, (void*)bf_coeff_, (void*)bf_lift_})
         if (p) (void)hipFree(p);
     for (auto& v : hoist_pool_) for (auto& s : v) if (s.d) (void)hipFree(s.d);
     for (auto& kv : f2_sched_) if (kv.second.d_segs) (void)hipFree(kv.second.d_segs);

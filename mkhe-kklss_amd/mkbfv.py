@@ -256,6 +256,73 @@ class Evaluator:
         self.ksw.Conjugate(ct0, ckSet, ctOut)
         return ctOut
 
+    # ---- plaintext operands (no reference counterpart: include/mkhe.h, "BFV plaintext operands").  The result carries the ids of the input: no
+    # party is added and no key is used.
+    def _encoder(self):
+        if getattr(self, "_enc", None) is None:
+            self._enc = DeviceEncoder(self.params)
+        return self._enc
+
+    def _ptmul(self, pt, B):
+        """-> (PlaintextMul, stride in words) for B ciphertexts: one plaintext for all, or one per item"""
+        if isinstance(pt, Message):
+            pt = self._encoder().EncodeMul(pt.Value)
+        elif isinstance(pt, (list, tuple)) and all(isinstance(m, Message) for m in pt):
+            pt = self._encoder().EncodeMulBatch(np.stack([m.Value for m in pt]))
+        if not isinstance(pt, PlaintextMul):
+            raise MkheError("mkbfv.Evaluator: MulPtxt takes a PlaintextMul (Encoder.EncodeMul / DeviceEncoder.EncodeMul) or a Message")
+        return pt, self._stride(pt.Value, B)
+
+    def _ptadd(self, pt, B):
+        if isinstance(pt, Message):
+            pt = self._encoder().Encode(pt.Value)
+        elif isinstance(pt, (list, tuple)) and all(isinstance(m, Message) for m in pt):
+            pt = self._encoder().EncodeBatch(np.stack([m.Value for m in pt]))
+        pt = self._encoder()._plaintexts(pt)
+        return pt, self._stride(pt, B)
+
+    def _stride(self, limbs, B):
+        if limbs.limbs != self.params.QCount() or limbs.count not in (1, B):
+            raise MkheError("mkbfv.Evaluator: %d ciphertexts need 1 or %d plaintexts of %d limbs, got %d of %d"
+                            % (B, B, self.params.QCount(), limbs.count, limbs.limbs))
+        return 0 if limbs.count == 1 and B > 1 else self.params.QCount() * self.params.N()
+
+    def _outputs(self, cts):
+        if len(cts) == 1:
+            return [NewCiphertext(self.params, cts[0].IDSet(), zero=False)]
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, cts[0].IDSet(), self.params.MaxLevel(), len(cts))
+
+    def MulPtxtBatch(self, cts, pts):
+        """ct * plaintext for a list of ciphertexts of one id set as ONE engine call (mkhe_bfv_ct_mul_ptxt).  pts: a PlaintextMul holding one
+        plaintext (shared) or one per ciphertext, or a Message / a list of Messages, which the device encoder prepares first."""
+        pt, stride = self._ptmul(pts, len(cts))
+        outs = self._outputs(cts)
+        check(lib().mkhe_bfv_ct_mul_ptxt(self.params.ctx, len(cts), handle_array([c.h for c in cts]), pt.Value.devptr(), stride,
+                                         handle_array([c.h for c in outs])))
+        return outs
+
+    def AddPtxtBatch(self, cts, pts, sub=False):
+        """ct + plaintext (sub: ct - plaintext) for a list of ciphertexts of one id set as ONE engine call (mkhe_bfv_ct_add_ptxt).  pts: the
+        DeviceLimbs of DeviceEncoder.Encode / EncodeBatch (one plaintext, or one per ciphertext), a host uint64 [nQ][N] / [B][nQ][N], a Message or a
+        list of Messages."""
+        pt, stride = self._ptadd(pts, len(cts))
+        outs = self._outputs(cts)
+        check(lib().mkhe_bfv_ct_add_ptxt(self.params.ctx, 1 if sub else 0, len(cts), handle_array([c.h for c in cts]), pt.devptr(), stride,
+                                         handle_array([c.h for c in outs])))
+        return outs
+
+    def MulPtxtNew(self, ct, pt):
+        """ct * pt slot by slot: pt a PlaintextMul, or a Message (encoded with the device encoder).  Three NTT launches and one elementwise kernel."""
+        return self.MulPtxtBatch([ct], pt)[0]
+
+    def AddPtxtNew(self, ct, pt):
+        """ct + pt: pt the DeviceLimbs of DeviceEncoder.Encode, a host uint64 [nQ][N] (Encoder.Encode), or a Message"""
+        return self.AddPtxtBatch([ct], pt)[0]
+
+    def SubPtxtNew(self, ct, pt):
+        """ct - pt, pt as for AddPtxtNew"""
+        return self.AddPtxtBatch([ct], pt, sub=True)[0]
+
 
 def NewEvaluator(params):
     return Evaluator(params)
@@ -294,6 +361,37 @@ def ScaleDown(poly, params):
         r = ((v * T * 2 + Q) // (2 * Q)) % T
         out.append(r - T if r > T // 2 else r)
     return np.array(out, dtype=np.int64)
+
+
+def Lift(m, params):
+    """coefficients over Z_T -> uint64 [nQ][N]: MForm(c mod q_l) = (c mod q_l) 2^64 mod q_l for the centred representative c of m mod T (c = m for
+    m <= floor(T/2), else m - T), exact in Python integers.  The multiplication plaintext in the coefficient domain (mkhe_bfv_lift)."""
+    T = params.T()
+    c = [int(v) % T for v in np.asarray(m).astype(object)]
+    c = [v - T if v > T // 2 else v for v in c]
+    return np.stack([np.array([((v % q) << 64) % q for v in c], dtype=np.uint64) for q in params.Q])
+
+
+class PlaintextMul:
+    """`count` prepared multiplication plaintexts: Value = mkrlwe.DeviceLimbs [count][nQ][N], the forward NTT over Q of Lift, in Montgomery form
+    (the operand of Evaluator.MulPtxtNew / MulPtxtBatch).  value: such a DeviceLimbs, or the host array of Encoder.EncodeMul ([nQ][N] or
+    [count][nQ][N]), which is uploaded."""
+
+    def __init__(self, params, value):
+        if not isinstance(value, mkrlwe.DeviceLimbs):
+            value = np.ascontiguousarray(value, dtype=np.uint64)
+            value = value[None] if value.ndim == 2 else value
+            value = mkrlwe.DeviceLimbs(params, value.shape[0], value.shape[1]).upload(value)
+        if value.limbs != params.QCount():
+            raise MkheError("mkbfv.PlaintextMul: a BFV plaintext has %d limbs, got %d" % (params.QCount(), value.limbs))
+        self.params, self.Value = params, value
+
+    @property
+    def count(self):
+        return self.Value.count
+
+    def download(self):
+        return self.Value.download()
 
 
 def _is_prime(n):
@@ -427,6 +525,16 @@ class Encoder:
         """RNS plaintext [nQ][N] (canonical residues) -> slots int64 [N], centred (DecodeInt of decryptor.go:52-54)"""
         return self.CoeffsToSlots(np.mod(ScaleDown(poly, self.params), np.int64(self.T)).astype(np.uint64))
 
+    def EncodeMul(self, values):
+        """slots int64 [N] -> the prepared multiplication plaintext uint64 [nQ][N]: the same bits as DeviceEncoder.EncodeMul.  The slot transform and
+        the lift (Lift) run here in numpy / Python integers; the forward NTT over Q is NOT restated: it is the engine's own (mkhe_ntt on the uploaded
+        lift), so `params` must be device parameters (mkbfv.Parameters) for this call."""
+        params = self.params
+        lift = mkrlwe.DeviceLimbs(params, 1, params.QCount()).upload(Lift(self.SlotsToCoeffs(values), params)[None])
+        out = mkrlwe.DeviceLimbs(params, 1, params.QCount())
+        mkrlwe.ntt(params, lift, out)
+        return out.download()[0]
+
 
 class DeviceEncoder:
     """The interface of Encoder on the DEVICE (mkhe_bfv_*: csrc/bfv_kernels.hip), plus batch forms.  Messages go up and come down as N int64
@@ -501,6 +609,23 @@ class DeviceEncoder:
         """device plaintext(s) [count][nQ][N] (or a host polynomial [nQ][N]) -> slots int64 [N] ([count][N] for count > 1), centred"""
         poly = self._plaintexts(poly)
         return self._stage(lib().mkhe_bfv_decode, poly, 1, np.int64, poly.count == 1)
+
+    def Lift(self, coeffs):
+        """coefficients uint64 [N] (or [count][N]) -> device buffer [count][nQ][N]: MForm of the centred lift, coefficient domain (mkhe_bfv_lift)"""
+        m, _ = self._rows(coeffs, np.uint64, "coefficients")
+        return self._stage(lib().mkhe_bfv_lift, self._up(m), self.params.QCount(), None, False)
+
+    def EncodeMulBatch(self, values):
+        """count messages -> PlaintextMul of count prepared plaintexts as one launch set (mkhe_bfv_encode_mul)"""
+        z, _ = self._rows(values, np.int64, "slots")
+        return PlaintextMul(self.params, self._stage(lib().mkhe_bfv_encode_mul, self._up(z), self.params.QCount(), None, False))
+
+    def EncodeMul(self, values):
+        """one message -> PlaintextMul: what Evaluator.MulPtxtNew takes as it is"""
+        z, one = self._rows(values, np.int64, "slots")
+        if not one:
+            raise MkheError("mkbfv.DeviceEncoder: EncodeMul takes one message (EncodeMulBatch takes several)")
+        return self.EncodeMulBatch(z)
 
 
 def _encoder(params, which):
