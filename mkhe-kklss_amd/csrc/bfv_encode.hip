@@ -60,15 +60,11 @@ void Context::bf_init(const char* what) {
     t.c32 = (u32)c32; t.c32_s = shoup(c32, T).y;
     t.one_s = shoup(1, T).y;
     garner_table();
-    Uploads up;
+    const size_t mark = mem_.mark();
     try {
-        d_bf_w = up.add(tw); d_bf_winv = up.add(twi); d_bf_twist = up.add(twist); d_bf_itwist = up.add(itwist); d_bf_qlt = up.add(qlt);
-        d_bf_pos = up.add(slot_positions(logN, 1, true)); d_bf_tinv = up.add(tinv); d_bf_tmont = up.add(tmont);
-    } catch (...) {
-        up.drop();
-        d_bf_w = d_bf_winv = d_bf_twist = d_bf_itwist = d_bf_qlt = nullptr; d_bf_pos = nullptr; d_bf_tinv = d_bf_tmont = nullptr;
-        throw;
-    }
+        d_bf_w = mem_.upload(tw); d_bf_winv = mem_.upload(twi); d_bf_twist = mem_.upload(twist); d_bf_itwist = mem_.upload(itwist); d_bf_qlt = mem_.upload(qlt);
+        d_bf_pos = mem_.upload(slot_positions(logN, 1, true)); d_bf_tinv = mem_.upload(tinv); d_bf_tmont = mem_.upload(tmont);
+    } catch (...) { mem_.rollback(mark); throw; }
     bf_t_ = t; bf_psi_ = psi;
     bf_tile_.log = bf_tile_.granted = bf_ntt_big_lds() ? BF_TILE_LOG_BIG : BF_TILE_LOG_DEF;
     bf_ready_ = true;
@@ -104,7 +100,7 @@ void Context::bf_ntt(bool inverse, int fuse, int count, const u64* in, u64* out)
         a.in = in; a.out = out;
         a.p.logt = logN; a.p.first = a.p.last = 1; a.fuse = fuse;
         const size_t words = (size_t)count * nq * n;
-        if (fuse && !inverse) a.dig = scratch(bf_dig_, bf_dig_words_, words);
+        if (fuse && !inverse) a.dig = scratch(bf_dig_, words);
         {
             // fused forward: every digit is written once and read by each later limb and by the sum
             const double rns = 8.0 * nq * n * count * (fuse && !inverse ? 3.0 + (nq - 1) / 2.0 : 1.0);
@@ -116,11 +112,11 @@ void Context::bf_ntt(bool inverse, int fuse, int count, const u64* in, u64* out)
     }
     // two launches; the scalings run as their own launches around the coefficient scratch
     const size_t cwords = (size_t)count * n;
-    u64* coeff = fuse ? scratch(bf_coeff_, bf_coeff_words_, cwords) : nullptr;
+    u64* coeff = fuse ? scratch(bf_coeff_, cwords) : nullptr;
     if (fuse && !inverse) { bf_scale_down(count, in, coeff); in = coeff; }
     a.in = in; a.out = fuse && inverse ? coeff : out;
     const size_t wwords = (cwords + 1) / 2;                                     // 32-bit words
-    a.work = reinterpret_cast<u32*>(scratch(bf_work_, bf_work_words_, wwords));
+    a.work = reinterpret_cast<u32*>(scratch(bf_work_, wwords));
     a.p.logt = std::min(bf_tile_.log, BF_TILE_LOG_MULTI);
     tile_two_pass(a.p, inverse, logN - a.p.logt, [&] {
         ProfScope ps(this, PROF_OTHER, 8.0 * n * count + 4.0 * n * count + tables / 2);
@@ -141,7 +137,7 @@ void Context::bf_lift(int count, const u64* coeffs, u64* ptmul) {
 }
 void Context::bf_scale_down(int count, const u64* pt, u64* coeffs) {
     const size_t words = (size_t)count * nq * N;
-    u64* dig = scratch(bf_dig_, bf_dig_words_, words);
+    u64* dig = scratch(bf_dig_, words);
     {
         // every digit is written once and read by each later limb and by the sum
         ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * nq * (3.0 + (nq - 1) / 2.0)));
@@ -188,7 +184,7 @@ void Context::bfv_lift(int count, const u64* coeffs, u64* ptmul_coeff) {
 void Context::bfv_encode_mul(int count, const u64* slots, u64* ptmul) {
     bf_init("mkhe_bfv_encode_mul");
     const size_t words = (size_t)count * nq * N;
-    u64* lift = scratch(bf_lift_, bf_lift_words_, words);                       // (the forward NTT is not asked to run in place)
+    u64* lift = scratch(bf_lift_, words);                       // (the forward NTT is not asked to run in place)
     bf_ntt(true, BF_FUSE_LIFT, count, slots, lift);
     ntt(lift, ptmul, count, nq, 0, false, false);
     MKHE_HIP(hipMemsetAsync(lift, 0, words * sizeof(u64), s_));

@@ -43,9 +43,9 @@ void Context::ck_init(const char* what) {
     for (long k = 0; k < n / 2; ++k) unit_root(k, n, w[2 * k], w[2 * k + 1]);
     for (long k = 0; k < n; ++k) unit_root(k, 4 * n, twist[2 * k], twist[2 * k + 1]);          // xi = exp(i pi / N) = exp(2 pi i / 4n)
     garner_table();
-    Uploads up;
-    try { d_ck_w = up.add(w); d_ck_twist = up.add(twist); d_ck_pos = up.add(slot_positions(logN, 2, false)); }
-    catch (...) { up.drop(); d_ck_w = d_ck_twist = nullptr; d_ck_pos = nullptr; throw; }
+    const size_t mark = mem_.mark();
+    try { d_ck_w = mem_.upload(w); d_ck_twist = mem_.upload(twist); d_ck_pos = mem_.upload(slot_positions(logN, 2, false)); }
+    catch (...) { mem_.rollback(mark); throw; }
     ck_tile_.log = ck_tile_.granted = ck_fft_big_lds() ? CK_TILE_LOG_BIG : CK_TILE_LOG;
     ck_ready_ = true;
 }
@@ -73,13 +73,13 @@ void Context::ck_fft(bool inverse, int count, const double* in, double* out) {
         launch_ck_fft(inverse, a, count, s_);
         return;
     }
-    a.work = reinterpret_cast<double2*>(scratch(ck_work_, ck_work_words_, 2 * (size_t)n * count));
+    a.work = reinterpret_cast<double2*>(scratch(ck_work_, 2 * (size_t)n * count));
     a.p.logt = CK_TILE_LOG;
     tile_two_pass(a.p, inverse, logn - CK_TILE_LOG, [&] {
         ProfScope ps(this, PROF_OTHER, io / 2 + 16.0 * n * count);
         launch_ck_fft(inverse, a, count, s_);
     });
-    MKHE_HIP(hipMemsetAsync(ck_work_, 0, 2 * (size_t)n * count * sizeof(u64), s_));
+    MKHE_HIP(hipMemsetAsync(ck_work_.p, 0, 2 * (size_t)n * count * sizeof(u64), s_));
 }
 
 void Context::ckks_embed(int count, const double* slots, double* coeffs) {
@@ -99,7 +99,7 @@ void Context::ck_scale_up(int level, int count, const double* coeffs, double sca
 }
 void Context::ck_scale_down(int limbs, int count, const u64* pt, double scale, double* coeffs) {
     const size_t words = (size_t)count * limbs * N;
-    u64* dig = scratch(ck_dig_, ck_dig_words_, words);
+    u64* dig = scratch(ck_dig_, words);
     {
         // every digit is written once and read by each later limb, by the sign decision and by the sum
         ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * limbs * (2.0 + (limbs - 1) / 2.0 + 2.0)));
@@ -123,7 +123,7 @@ void Context::ckks_encode(int level, int count, const double* slots, double scal
     check_level(level);
     ck_init("mkhe_ckks_encode");
     const size_t words = (size_t)count * N;
-    double* m = reinterpret_cast<double*>(scratch(ck_coeff_, ck_coeff_words_, words));
+    double* m = reinterpret_cast<double*>(scratch(ck_coeff_, words));
     ck_fft(true, count, slots, m);
     ck_scale_up(level, count, m, scale, pt);
     MKHE_HIP(hipMemsetAsync(m, 0, words * sizeof(double), s_));
@@ -133,7 +133,7 @@ void Context::ckks_decode(int limbs, int count, const u64* pt, double scale, dou
     check_level(limbs - 1);
     ck_init("mkhe_ckks_decode");
     const size_t words = (size_t)count * N;
-    double* m = reinterpret_cast<double*>(scratch(ck_coeff_, ck_coeff_words_, words));
+    double* m = reinterpret_cast<double*>(scratch(ck_coeff_, words));
     ck_scale_down(limbs, count, pt, scale, m);
     ck_fft(false, count, m, slots);
     MKHE_HIP(hipMemsetAsync(m, 0, words * sizeof(double), s_));

@@ -13,22 +13,16 @@
 
 namespace mkhe {
 
-// v as a kernel-argument table, or -- longer than ED_INLINE -- staged at ed_tab_ + tab_offset (the caller has sized ed_tab_)
+// v as a kernel-argument table, or -- longer than ED_INLINE -- staged at entry tab_offset of ed_tab_ (the caller has sized ed_tab_: one word per entry)
 EdTable Context::ed_table(const std::vector<const u64*>& v, size_t tab_offset) {
     EdTable t{};
     if (v.size() <= (size_t)ED_INLINE) { for (size_t i = 0; i < v.size(); ++i) t.p[i] = v[i]; return t; }
-    if (tab_offset + v.size() > ed_tab_n_) throw Error("mkhe: pointer table scratch too small");
-    MKHE_HIP(hipMemcpyAsync(ed_tab_ + tab_offset, v.data(), v.size() * sizeof(const u64*), hipMemcpyHostToDevice, stream));
+    if (tab_offset + v.size() > ed_tab_.words) throw Error("mkhe: pointer table scratch too small");
+    const u64** tab = reinterpret_cast<const u64**>(ed_tab_.p) + tab_offset;
+    MKHE_HIP(hipMemcpyAsync(tab, v.data(), v.size() * sizeof(const u64*), hipMemcpyHostToDevice, stream));
     sync();                                             // v is pageable and about to go out of scope
-    t.dev = ed_tab_ + tab_offset;
+    t.dev = tab;
     return t;
-}
-
-static void ed_grow_tab(const u64**& tab, size_t& have, size_t want, hipStream_t st) {
-    if (have >= want) return;
-    if (tab) { MKHE_HIP(hipStreamSynchronize(st)); MKHE_HIP(hipFree(tab)); tab = nullptr; have = 0; }
-    MKHE_HIP(hipMalloc(&tab, want * sizeof(const u64*)));
-    have = want;
 }
 
 void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const int32_t* samples, u64* const* outs) {
@@ -36,17 +30,13 @@ void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool p
     if (masked_) throw Error("mkhe_encrypt: not available on a context that owns a subset of the moduli");
     const int L = level + 1;
     const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
-    u64* w = scratch(ed_w_, ed_w_words_, 3 * pw);
-    if (ed_small_n_ < 4 * sn) {
-        if (ed_small_) { MKHE_HIP(hipStreamSynchronize(stream)); MKHE_HIP(hipFree(ed_small_)); ed_small_ = nullptr; ed_small_n_ = 0; }
-        MKHE_HIP(hipMalloc(&ed_small_, 4 * sn * sizeof(int32_t)));
-        ed_small_n_ = 4 * sn;
-    }
-    ed_grow_tab(ed_tab_, ed_tab_n_, (size_t)count, stream);
+    u64* w = scratch(ed_w_, 3 * pw);
+    int32_t* small = reinterpret_cast<int32_t*>(scratch(ed_small_, 2 * sn));          // 4 sn int32 (N is even)
+    scratch(ed_tab_, (size_t)count);
     const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0);
     // the samples as given, [count][3][N], for encrypt_finish; behind them the count rows of u gathered into [count][N] for small_expand
-    int32_t* du = ed_small_ + 3 * sn;
-    MKHE_HIP(hipMemcpyAsync(ed_small_, samples, 3 * sn * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    int32_t* du = small + 3 * sn;
+    MKHE_HIP(hipMemcpyAsync(small, samples, 3 * sn * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     MKHE_HIP(hipMemcpy2DAsync(du, (size_t)N * sizeof(int32_t), samples, 3 * (size_t)N * sizeof(int32_t), (size_t)N * sizeof(int32_t), count,
                               hipMemcpyHostToDevice, stream));
     sync();                                             // the host array may be pageable: do not return before it is consumed
@@ -63,9 +53,9 @@ void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool p
     ntt(w, w, (pt_is_ntt ? 3 : 2) * count, L, 0, true, false);
     {
         ProfScope ps(this, PROF_OTHER, (double)count * N * (8.0 + 8.0 * L * 5.0));
-        launch_encrypt_finish(count, ot, w, ed_small_, pt_is_ntt ? nullptr : pt, d_mods, L, N, s_);
+        launch_encrypt_finish(count, ot, w, small, pt_is_ntt ? nullptr : pt, d_mods, L, N, s_);
     }
-    MKHE_HIP(hipMemsetAsync(ed_small_, 0, 3 * sn * sizeof(int32_t), s_));
+    MKHE_HIP(hipMemsetAsync(small, 0, 3 * sn * sizeof(int32_t), s_));
     MKHE_HIP(hipMemsetAsync(w, 0, 2 * pw * sizeof(u64), s_));             // u * pk1 gives u away: it does not outlive the call
     MKHE_HIP(hipGetLastError());
 }
@@ -74,7 +64,7 @@ void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool p
 void Context::ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc) {
     std::vector<const u64*> c(k), s(sks, sks + k);
     for (int i = 0; i < k; ++i) c[i] = ch + (size_t)i * limbs * N;
-    ed_grow_tab(ed_tab_, ed_tab_n_, 2 * (size_t)k, stream);
+    scratch(ed_tab_, 2 * (size_t)k);
     const EdTable ct = ed_table(c, 0), st = ed_table(s, (size_t)k);
     ProfScope ps(this, PROF_OTHER, 8.0 * N * limbs * (2.0 * k + 1.0));
     launch_decrypt_mac(1, k, acc, ct, st, d_mods, limbs, N, s_);
@@ -89,7 +79,7 @@ void Context::partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out) {
     if (out.n != in.n - 1 || out.ids != rest) throw Error("mkhe_partial_decrypt: out must be over the ids of in without the one at slot");
     const int L = in.limbs;
     const size_t pw = (size_t)L * N;
-    u64* w = scratch(ed_w_, ed_w_words_, 2 * pw);
+    u64* w = scratch(ed_w_, 2 * pw);
     ntt(in.d + (size_t)slot * pw, w, 1, L, 0, false, false);
     ed_mac(1, w, &sk, L, w + pw);
     ntt(w + pw, w + pw, 1, L, 0, true, false);
@@ -108,7 +98,7 @@ void Context::decrypt(const Ct& ct, const u64* const* sks, u64* pt_out) {
     if (masked_) throw Error("mkhe_decrypt: not available on a context that owns a subset of the moduli");
     const int k = ct.n, L = ct.limbs;
     const size_t pw = (size_t)L * N;
-    u64* w = scratch(ed_w_, ed_w_words_, (size_t)(k + 1) * pw);
+    u64* w = scratch(ed_w_, (size_t)(k + 1) * pw);
     u64* acc = w + (size_t)k * pw;
     if (k > 0) {
         ntt(ct.d + pw, w, k, L, 0, false, false);

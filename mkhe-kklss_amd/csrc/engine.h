@@ -13,7 +13,7 @@
 #include <map>
 #include <memory>
 #include <vector>
-#include <stdexcept>
+#include "device_memory.h"
 #include "modarith.h"
 #include "ntt_kernels.h"
 #include "poly_kernels.h"
@@ -29,26 +29,11 @@ int ab_fuse_x();
 int ab_fuse_y();
 int ab_fuse_e();
 
-struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 // host number theory of engine.hip that the encoders share: Miller-Rabin for 64-bit n, and the engine's choice of a primitive 2N-th root
 // (g the smallest generator >= 3 of Z_q*, psi = g^((q-1)/2N)); q must be a prime = 1 mod 2N
 bool is_prime(u64 n);
 u64 default_psi(u64 q, u64 N);
 
-#define MKHE_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw ::mkhe::Error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-// device tables of one build step that are released again when the step fails half way: add() every table, drop() in the handler
-struct Uploads {
-    std::vector<void*> p;
-    template <class E> E* add(const std::vector<E>& v) {
-        E* d = nullptr;
-        MKHE_HIP(hipMalloc(&d, v.size() * sizeof(E)));
-        p.push_back(d);
-        MKHE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
-        return d;
-    }
-    void drop() noexcept { for (void* d : p) (void)hipFree(d); p.clear(); }
-};
 // log2 of the largest tile one workgroup of an encoder's transform takes (tile_transform.h): what the runtime granted at the first call, and the
 // limit in force.  set: 0 (back to the grant), the grant itself, or lo .. hi; anything else throws `what` + the closing words on the grant
 struct TileLimit {
@@ -351,24 +336,28 @@ class Context {
     u64 *d_down_q_in_m = nullptr, *d_down_m_in_q = nullptr, *d_mform_qmul = nullptr, *d_t_mont = nullptr;
 
   private:
-    // scratch pools
+    // Every table above and every pool, lazily built table and Scratch buffer below is a block of mem_ (device_memory.h): the members are non-owning
+    // pointers into it and release_all names none of them.  (Handles are not in it: pool_free.)  Then the scratch pools:
+    // The tables of a first-use build (kg_*, d_ck_*, d_bf_*) keep stale values after a build that failed and was rolled back: read them only behind
+    // their *_ready_ flag, never test them for null.
+    DeviceMemory mem_;
     u64 *x_ = nullptr, *y_ = nullptr, *swk3_ = nullptr;      // swkPool1..3
     u64* c1_ = nullptr;                                      // ks.Pool[1]  (PolyQP)
     u64* polyq_[3] = {nullptr, nullptr, nullptr};            // polyQPool
     u64* invntt_ = nullptr;                                  // ks.PoolInvNTT
-    u64* nttbuf_ = nullptr; size_t nttbuf_words_ = 0;        // tensor inputs in NTT form
-    u64* ctbuf_ = nullptr;  size_t ctbuf_words_ = 0;         // rotate / rescale staging
+    Scratch nttbuf_;                                         // tensor inputs in NTT form
+    Scratch ctbuf_;                                          // rotate / rescale staging
     std::vector<Swk> hoist_pool_[5];                         // rlkSet.HoistPool[0/1] + h(t_i) of step F; [3],[4]: BFV HoistPool2[0/1]
     u64 *x2_ = nullptr, *y2_ = nullptr;                      // BFV swkPool4 / swkPool6
-    u64* rbuf_ = nullptr;  size_t rbuf_words_ = 0;          // BFV: operands over R, their NTTs, tensor output
-    u64* c1b_ = nullptr;   size_t c1b_words_ = 0;           // batched ks.Pool[1]
-    u64* tbuf_ = nullptr;  size_t tbuf_words_ = 0;          // t_i of step F
+    Scratch rbuf_;                                           // BFV: operands over R, their NTTs, tensor output
+    Scratch c1b_;                                            // batched ks.Pool[1]
+    Scratch tbuf_;                                           // t_i of step F
     // mul_relin_rescale / mul_relin_batch: Rescale folded into the store of the last merged ModDown.  One entry per product that is not to be
     // written: its (unwritten) base, the rescaled output one level down, its polynomials; `done` once a launch has covered all of them
     struct RsMap { const u64* full; u64* out; int npolys; int out_limbs; bool done; };
     std::vector<RsMap> rs_maps_;
-    u64* spreadbuf_ = nullptr; size_t spreadbuf_words_ = 0;  // N = 2^16: staging of the spread digits (decompose_batch), so that the sub-transforms run out of place
-    u64* tens_ = nullptr;  size_t tens_words_ = 0;          // tensor term kept in the NTT domain (times P) for the merged E / F2 batch
+    Scratch spreadbuf_;                                      // N = 2^16: staging of the spread digits (decompose_batch), so that the sub-transforms run out of place
+    Scratch tens_;                                           // tensor term kept in the NTT domain (times P) for the merged E / F2 batch
     // key generation scratch: uploaded samples, gadget constants (slot 0: mkrlwe gadget, 1: caller's), permuted secret
     int32_t* kg_small_ = nullptr; u64 *kg_g_ = nullptr, *kg_sk_ = nullptr;
     void wipe_samples(size_t count);
@@ -379,9 +368,7 @@ class Context {
     void kg_key(const int32_t* e, int gadget, const u64* skA, const u64* crs, const u64* skB, int sign, bool neg, u64* out);
     void kg_upload_g(const u64* g_plain);
     // encryption / decryption scratch: work polynomials, uploaded samples, staged pointer tables (encdec.hip)
-    u64* ed_w_ = nullptr;  size_t ed_w_words_ = 0;
-    int32_t* ed_small_ = nullptr; size_t ed_small_n_ = 0;
-    const u64** ed_tab_ = nullptr; size_t ed_tab_n_ = 0;
+    Scratch ed_w_, ed_small_, ed_tab_;                       // (int32 samples in ed_small_, const u64* entries in ed_tab_: sized in 8-byte words and cast at the use)
     EdTable ed_table(const std::vector<const u64*>& v, size_t tab_offset);
     void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
     // both encoders: the Garner constants [nq][nq], built at the first use, and the two launches of a transform that one tile does not hold:
@@ -400,9 +387,7 @@ class Context {
     double *d_ck_w = nullptr, *d_ck_twist = nullptr; u32* d_ck_pos = nullptr;
     bool ck_ready_ = false;
     TileLimit ck_tile_{CK_TILE_LOG, CK_TILE_LOG};
-    u64* ck_work_ = nullptr;  size_t ck_work_words_ = 0;
-    u64* ck_dig_ = nullptr;   size_t ck_dig_words_ = 0;
-    u64* ck_coeff_ = nullptr; size_t ck_coeff_words_ = 0;
+    Scratch ck_work_, ck_dig_, ck_coeff_;
     void ck_init(const char* what);
     void ck_fft(bool inverse, int count, const double* in, double* out);
     void ck_scale_up(int level, int count, const double* coeffs, double scale, u64* pt);
@@ -415,10 +400,7 @@ class Context {
     u64 bf_psi_ = 0;
     bool bf_ready_ = false;
     TileLimit bf_tile_{BF_TILE_LOG_DEF, BF_TILE_LOG_DEF};
-    u64* bf_work_ = nullptr;  size_t bf_work_words_ = 0;
-    u64* bf_dig_ = nullptr;   size_t bf_dig_words_ = 0;
-    u64* bf_coeff_ = nullptr; size_t bf_coeff_words_ = 0;
-    u64* bf_lift_ = nullptr;  size_t bf_lift_words_ = 0;
+    Scratch bf_work_, bf_dig_, bf_coeff_, bf_lift_;
     void bf_init(const char* what);
     BfvScale bf_scale() const;
     void bf_ntt(bool inverse, int fuse, int count, const u64* in, u64* out);
@@ -427,7 +409,8 @@ class Context {
     void bf_ptxt_shapes(const char* what, const std::vector<const Ct*>& ins, long pt_stride, const std::vector<Ct*>& outs);
     void bf_scale_down(int count, const u64* pt, u64* coeffs);
 
-    u64* scratch(u64*& p, size_t& have, size_t want);
+    u64* alloc_words(size_t words) { return static_cast<u64*>(mem_.alloc(words * sizeof(u64))); }
+    u64* scratch(Scratch& s, size_t want) { return mem_.grow(s, want, stream); }      // grow-only; a larger block waits for the main stream first
     Swk& hoist_slot(int which, int idx);
     const int* map_qp(int level) const { return (masked_ ? d_map_own : d_map_qp) + (size_t)level * mtot; }
     int nslots_qp(int level) const { return masked_ ? own_cnt_[level] : level + 1 + np; }
@@ -490,7 +473,7 @@ class Context {
     hipEvent_t fence_ev_ = nullptr;
     void registry_add();
     void init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP, const u64* QMul, int nqm_, u64 T);     // the constructor's body
-    void release_all() noexcept;                              // frees everything the context owns (destructor; constructor that throws)
+    void release_all() noexcept;                              // mem_, the handle pool, events, streams (destructor; constructor that throws)
     void registry_remove();
     seq_t uid_ = 0;
     std::atomic<seq_t> seq_{1}, completed_{0};

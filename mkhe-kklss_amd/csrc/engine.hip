@@ -49,19 +49,12 @@ u64 default_psi(u64 q, u64 N) {
     return powmod(g, (q - 1) / (2 * N), q);
 }
 
-template <typename T> static T* dev_upload(const std::vector<T>& v) {
-    T* d = nullptr;
-    MKHE_HIP(hipMalloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T)));
-    if (!v.empty()) MKHE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-// Device allocation of the engine's buffers.  The stream-ordered pools (Context::pool_free) keep freed handles' memory for reuse; when the
-// driver runs out, what the pools of this device hold is handed back (one device-wide synchronisation) and the allocation is tried once more,
-// so that a process never fails with most of HBM sitting in free lists.
+// Device allocation of the engine's buffers: what a context's DeviceMemory (mem_) and its handle pool (pool_alloc) both allocate with.  The stream-ordered
+// pools (Context::pool_free) keep freed handles' memory for reuse; when the driver runs out, what the pools of this device hold is handed back (one
+// device-wide synchronisation) and the allocation is tried once more, so that a process never fails with most of HBM sitting in free lists.
 static size_t trim_device_pools();
-static u64* dev_alloc_words(size_t w) {
-    u64* d = nullptr;
-    const size_t bytes = std::max<size_t>(w, 1) * sizeof(u64);
+static void* dev_alloc_bytes(size_t bytes) {
+    void* d = nullptr;
     hipError_t e = hipMalloc(&d, bytes);
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
@@ -74,7 +67,7 @@ static u64* dev_alloc_words(size_t w) {
 // ------------------------------------------------------------------ construction
 Context::Context(int logN_, const u64* Q, int nq_, const u64* P, int np_, int gamma_,
                  const u64* psiQ, const u64* psiP, int device_, const u64* QMul, int nqm_, u64 T)
-    : logN(logN_), N(1 << logN_), nq(nq_), np(np_), mtot(nq_ + np_), gamma(gamma_), device(device_) {
+    : logN(logN_), N(1 << logN_), nq(nq_), np(np_), mtot(nq_ + np_), gamma(gamma_), device(device_), mem_(&dev_alloc_bytes) {
     // The context enters the per-device registry (the pools of the other contexts walk it) only once it is complete: a constructor that
     // throws half way -- a bad root, an unsupported alpha, a failed allocation -- never runs the destructor, so everything built so
     // far is released here and no dangling pointer is ever visible to pool_free / pool_alloc of another context.
@@ -185,7 +178,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
     for (auto& v : psi) v = sd_split(v);
     for (auto& v : psiinv) v = sd_split(v);
     for (auto& v : aux) v = sd_split(v);
-    d_mods = dev_upload(mods); d_psi = dev_upload(psi); d_psiinv = dev_upload(psiinv); d_inv_aux = dev_upload(aux);
+    d_mods = mem_.upload(mods); d_psi = mem_.upload(psi); d_psiinv = mem_.upload(psiinv); d_inv_aux = mem_.upload(aux);
     if (logN >= 14 && !h16_gap_) {
         // one-round product of the H16 kernel: a * w = a0 * u + a1 * u' with u = w 2^31, u' = w 2^63 (mod q, balanced), then ONE Montgomery
         // round of radix 2^31.  psi holds w * 2^64 in signed-split form at this point: w * 2^31 = psi * 2^-33.
@@ -219,7 +212,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                 if (j >= 1 && j <= 3) pair_of(wR ? q - wR : 0, &p31n[8 * (size_t)i + 2 * j]);
             }
         }
-        d_psi31 = dev_upload(p31); d_psi31n = dev_upload(p31n);
+        d_psi31 = mem_.upload(p31); d_psi31n = mem_.upload(p31n);
         if (logN == 15) {
             // H32 (ntt32_kernels.hip): in its last register phase thread t = 64 wave + lane holds the coefficients 32 t .. 32 t + 31, and pair
             // number k = 2^j - 1 + i of the phase (stage 10 + j, i < 2^j) is twiddle ((1024 + t) << j) + i: sixteen consecutive pairs per lane in
@@ -237,7 +230,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                             p31c[o] = p31[2 * ((size_t)i * N + tw)]; p31c[o + 1] = p31[2 * ((size_t)i * N + tw) + 1];
                         }
                     }
-            d_psi31c = dev_upload(p31c);
+            d_psi31c = mem_.upload(p31c);
             // ... and its middle phase (stages 5..9): thread = (bits 14..10, bits 4..0) with wave = bits 14..11, so that a wave uses TWO sets of 31 pairs
             // (bit 10 = lane >> 5).  Per modulus and wave one 1 KiB row [half][31 pairs] (+ 2 unused entries): loaded by ONE coalesced instruction
             // per limb, parked in LDS and read from there by broadcast -- instead of 31 per-lane 16-byte loads with two distinct addresses each
@@ -251,7 +244,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                             const size_t o = 2 * (((size_t)i * 16 + w) * 64 + 31 * h + k);
                             p31b[o] = p31[2 * ((size_t)i * N + tw)]; p31b[o + 1] = p31[2 * ((size_t)i * N + tw) + 1];
                         }
-            d_psi31b = dev_upload(p31b);
+            d_psi31b = mem_.upload(p31b);
         }
         // the inverse kernel of the same family (ntt14_inv_kernel): the inverse twiddles as pairs in the format of the modulus's class, and per
         // modulus and sub-transform root 1..7 the two constants of its last stage, N^-1 and psiinv[root] N^-1 (N = this ring's degree)
@@ -286,7 +279,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
             }
             if (small_q_[i]) small_mods_ |= 1ull << i;
         }
-        d_psiinv31 = dev_upload(pi31); d_inv31c = dev_upload(fin);
+        d_psiinv31 = mem_.upload(pi31); d_inv31c = mem_.upload(fin);
         // F class (N = 2^16 only: the quarter sub-transforms behind the radix-4 producers): moduli with 80 q < 2^52 run double-precision butterflies;
         // their forward twiddles as plain residues in double format (MKHE_H16_FCLASS=0 switches the class off)
         static const int fclass_on = MKHE_AB_INT("MKHE_H16_FCLASS", 1);
@@ -303,7 +296,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                     std::memcpy(&pf[(size_t)i * N + j], &w, 8);
                 }
             }
-            if (f_mods_) d_psif = dev_upload(pf);
+            if (f_mods_) d_psif = mem_.upload(pf);
         }
         // Reduction schedule of the balanced path for inputs below 2^60 (canonical digits of any modulus): the never-reduced values must stay
         // below 2^62.9 (column sums of mm31) and grow by at most 1.03q per one-round stage (q + |x| q / 2^64) and q/2 + |x|/16 per two-round
@@ -332,7 +325,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
         for (int j = 0; j < np; ++j) map[(size_t)l * mtot + l + 1 + j] = nq + j;
     }
     for (int j = 0; j < mtot; ++j) ident[j] = j;
-    d_map_qp = dev_upload(map); d_map_id = dev_upload(ident);
+    d_map_qp = mem_.upload(map); d_map_id = mem_.upload(ident);
 
     // ModUpPtoQ / ModDown constants, basisextenderparameters(P, Q) at full P
     // (mkrlwe/basis_extension.go:34-54, 83-153); all are canonical values -> closed forms.
@@ -356,8 +349,8 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
         t4[j] = qj - to_mont(powmod(pm, qj - 2, qj), qj);
         t5[j] = to_mont(pm, qj);
     }
-    d_pmodq = dev_upload(t5);
-    d_md_qoverqiinvqi = dev_upload(t1); d_md_qoverqimodp = dev_upload(t2); d_md_vtimes = dev_upload(t3); d_md_down = dev_upload(t4);
+    d_pmodq = mem_.upload(t5);
+    d_md_qoverqiinvqi = mem_.upload(t1); d_md_qoverqimodp = mem_.upload(t2); d_md_vtimes = mem_.upload(t3); d_md_down = mem_.upload(t4);
 
     // RescaleParams[L-1][i] = MForm(q_L^-1 mod q_i)  (lattigo ring.go genNTTParams)
     // second half of the table (round 5): BRedAdd((q_L - 1) / 2, q_i) = h mod q_i, the other per-(level, limb) constant of DivRoundByLastModulus -- the
@@ -368,7 +361,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
             rs[(size_t)(L - 1) * nq + i] = to_mont(powmod(Q[L] % Q[i], Q[i] - 2, Q[i]), Q[i]);
             rs[(size_t)nq * nq + (size_t)(L - 1) * nq + i] = ((Q[L] - 1) >> 1) % Q[i];
         }
-    d_rescale = dev_upload(rs);
+    d_rescale = mem_.upload(rs);
 
     if (alpha > 1) {
         // NewDecomposer (mkrlwe/basis_extension.go:368-424) at full P: for digit d and nd = 2..alpha limbs,
@@ -403,7 +396,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                 }
             }
         }
-        d_dec_a = dev_upload(ta); d_dec_b = dev_upload(tb); d_dec_c = dev_upload(tc);
+        d_dec_a = mem_.upload(ta); d_dec_b = mem_.upload(tb); d_dec_c = mem_.upload(tc);
         // Round 3, radix-4 digit spread in front of the N = 2^16 forward NTT (poly_kernels.hip decomp_spread4_kernel): two-limb digits and moduli
         // below 2^57 only; every constant t as the pair (t 2^30 mod p, t 2^62 mod p), radix-2^30 digits in the two halves of a word
         bool all57 = true;
@@ -430,7 +423,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                     tw30[(size_t)m * 8 + 2 * j + 1] = pack30(mulmod(t, c62, tj));
                 }
             }
-            d_tb30 = dev_upload(tb30); d_tw30 = dev_upload(tw30);
+            d_tb30 = mem_.upload(tb30); d_tw30 = mem_.upload(tw30);
         }
     }
 
@@ -456,7 +449,7 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
                 c[(size_t)j * (n + 1)] = 0;
                 for (int i = 1; i <= n; ++i) { u64 sum = c[(size_t)j * (n + 1) + i - 1] + v; c[(size_t)j * (n + 1) + i] = sum >= tj ? sum - tj : sum; }
             }
-            d1 = dev_upload(a); d2 = dev_upload(b); d3 = dev_upload(c);
+            d1 = mem_.upload(a); d2 = mem_.upload(b); d3 = mem_.upload(c);
         };
         conv(Q, QMul, nq, d_bq_qoverqiinvqi, d_bq_qoverqimodp, d_bq_vtimes);
         conv(QMul, Q, nq, d_bm_qoverqiinvqi, d_bm_qoverqimodp, d_bm_vtimes);
@@ -471,14 +464,14 @@ void Context::init(const u64* Q, const u64* P, const u64* psiQ, const u64* psiP,
             tm[i] = to_mont(T % Q[i], Q[i]); tm[nq + i] = to_mont(T % QMul[i], QMul[i]); // MulScalar(t) constants
             mr[i] = i; mr[nq + i] = mtot + i;
         }
-        d_down_q_in_m = dev_upload(dqm); d_down_m_in_q = dev_upload(dmq); d_mform_qmul = dev_upload(mf); d_t_mont = dev_upload(tm);
-        d_map_r = dev_upload(mr);
-        x2_ = dev_alloc_words(swk_words()); y2_ = dev_alloc_words(swk_words());
+        d_down_q_in_m = mem_.upload(dqm); d_down_m_in_q = mem_.upload(dmq); d_mform_qmul = mem_.upload(mf); d_t_mont = mem_.upload(tm);
+        d_map_r = mem_.upload(mr);
+        x2_ = alloc_words(swk_words()); y2_ = alloc_words(swk_words());
     }
-    x_ = dev_alloc_words(swk_words()); y_ = dev_alloc_words(swk_words()); swk3_ = dev_alloc_words(swk_words());
-    c1_ = dev_alloc_words((size_t)mtot * N);
-    for (auto& p : polyq_) p = dev_alloc_words((size_t)nq * N);
-    invntt_ = dev_alloc_words((size_t)nq * N);
+    x_ = alloc_words(swk_words()); y_ = alloc_words(swk_words()); swk3_ = alloc_words(swk_words());
+    c1_ = alloc_words((size_t)mtot * N);
+    for (auto& p : polyq_) p = alloc_words((size_t)nq * N);
+    invntt_ = alloc_words((size_t)nq * N);
 }
 
 // MForm(q_i^-1 mod q_j) at i * nq + j, i < j: the constants of the mixed-radix digits (modarith.h garner_digits) both encoders' scale_down use
@@ -487,9 +480,7 @@ const u64* Context::garner_table() {
     std::vector<u64> g((size_t)nq * nq, 0);
     for (int i = 0; i < nq; ++i)
         for (int j = i + 1; j < nq; ++j) g[(size_t)i * nq + j] = to_mont(powmod(moduli[i] % moduli[j], moduli[j] - 2, moduli[j]), moduli[j]);
-    Uploads up;
-    try { d_garner_ = up.add(g); } catch (...) { up.drop(); throw; }
-    return d_garner_;
+    return d_garner_ = mem_.upload(g);
 }
 
 void TileLimit::set(int log_points, int lo, int hi, const std::string& what) {
@@ -508,26 +499,13 @@ Context::~Context() {
 }
 void Context::release_all() noexcept {
     (void)hipSetDevice(device);
-    for (void* p : {(void*)d_mods, (void*)d_psi, (void*)d_psiinv, (void*)d_inv_aux, (void*)d_map_qp, (void*)d_map_id,
-                    (void*)d_md_qoverqiinvqi, (void*)d_md_qoverqimodp, (void*)d_md_vtimes, (void*)d_md_down, (void*)d_rescale, (void*)d_pmodq, (void*)tens_, (void*)d_psi31, (void*)d_psi31n, (void*)d_psi31c, (void*)d_psi31b, (void*)d_psiinv31, (void*)d_inv31c, (void*)d_psif, (void*)spreadbuf_,
-                    (void*)d_dec_a, (void*)d_dec_b, (void*)d_dec_c, (void*)d_tb30, (void*)d_tw30, (void*)d_map_own, (void*)d_ownq,
-                    (void*)x_, (void*)y_, (void*)swk3_, (void*)c1_, (void*)polyq_[0], (void*)polyq_[1], (void*)polyq_[2],
-                    (void*)invntt_, (void*)nttbuf_, (void*)ctbuf_, (void*)c1b_, (void*)tbuf_, (void*)rbuf_, (void*)x2_, (void*)y2_,
-                    (void*)d_map_r, (void*)d_bq_qoverqiinvqi, (void*)d_bq_qoverqimodp, (void*)d_bq_vtimes,
-                    (void*)d_bm_qoverqiinvqi, (void*)d_bm_qoverqimodp, (void*)d_bm_vtimes,
-                    (void*)d_down_q_in_m, (void*)d_down_m_in_q, (void*)d_mform_qmul, (void*)d_t_mont,
-                    (void*)kg_small_, (void*)kg_g_, (void*)kg_sk_, (void*)ed_w_, (void*)ed_small_, (void*)ed_tab_,
-                    (void*)d_garner_, (void*)d_ck_w, (void*)d_ck_twist, (void*)d_ck_pos, (void*)ck_work_, (void*)ck_dig_, (void*)ck_coeff_,
-                    (void*)d_bf_w, (void*)d_bf_winv, (void*)d_bf_twist, (void*)d_bf_itwist, (void*)d_bf_qlt, (void*)d_bf_pos, (void*)d_bf_tinv, (void*)d_bf_tmont,
-                    (void*)bf_work_, (void*)bf_dig_, (void*)bf_coeff_, (void*)bf_lift_})
-        if (p) (void)hipFree(p);
-    for (auto& v : hoist_pool_) for (auto& s : v) if (s.d) (void)hipFree(s.d);
-    for (auto& kv : f2_sched_) if (kv.second.d_segs) (void)hipFree(kv.second.d_segs);
-    f2_sched_.clear();
+    mem_.release();
     { std::vector<u64*> mine; (void)pool_take_all(mine); for (u64* p : mine) (void)hipFree(p); }
     for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto& kv : ntt_tune_) for (int i = 0; i < NttTune::RING; ++i) if (kv.second.e0[i]) (void)hipEventDestroy(kv.second.e0[i]);
     ntt_tune_.clear();
+    for (auto& r : prof_recs_) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
+    for (hipEvent_t e : prof_pool_) (void)hipEventDestroy(e);
     if (fence_ev_) (void)hipEventDestroy(fence_ev_);
     if (xev_) (void)hipEventDestroy(xev_);
     if (stream2) (void)hipStreamDestroy(stream2);
@@ -612,7 +590,7 @@ u64* Context::pool_alloc(size_t words) {
         }
     }
     MKHE_HIP(hipSetDevice(device));
-    return dev_alloc_words(words);
+    return static_cast<u64*>(dev_alloc_bytes(std::max<size_t>(words, 1) * sizeof(u64)));
 }
 void Context::note_use(HandleUsers& u) {
     touch();
@@ -675,16 +653,9 @@ void Context::pool_free(u64* p, size_t words, const HandleUsers* users) {
     reg.pooled_words.fetch_add(words);
     free_list_.push_back(std::move(e));
 }
-u64* Context::scratch(u64*& p, size_t& have, size_t want) {
-    if (have < want) {
-        if (p) { MKHE_HIP(hipStreamSynchronize(stream)); MKHE_HIP(hipFree(p)); p = nullptr; }
-        p = dev_alloc_words(want); have = want;
-    }
-    return p;
-}
 Swk& Context::hoist_slot(int which, int idx) {
     auto& v = hoist_pool_[which];
-    while ((int)v.size() <= idx) { Swk s; s.d = dev_alloc_words(swk_words()); v.push_back(s); }
+    while ((int)v.size() <= idx) { Swk s; s.d = alloc_words(swk_words()); v.push_back(s); }
     return v[idx];
 }
 void Context::check_level(int level) const {
@@ -771,9 +742,9 @@ void Context::set_owned(const int* mod_idx, int n) {
         for (int k = 0; k < own_cnt_[l]; ++k) map[(size_t)l * mtot + k] = own_list_[l][k];
     }
     for (int j = 0; j < nq; ++j) if (own_[j]) ownq_.push_back(j);
-    if (d_map_own) MKHE_HIP(hipFree(d_map_own));
-    if (d_ownq) MKHE_HIP(hipFree(d_ownq));
-    d_map_own = dev_upload(map); d_ownq = dev_upload(ownq_);
+    mem_.free(d_map_own); d_map_own = nullptr;
+    mem_.free(d_ownq); d_ownq = nullptr;
+    d_map_own = mem_.upload(map); d_ownq = mem_.upload(ownq_);
 }
 // ... or `limbs` consecutive moduli starting at mod_base (plain polynomials)
 void Context::slots_range(NttBatch& b, int mod_base, int limbs) const {
@@ -997,7 +968,7 @@ void Context::decompose_batch(int level, const std::vector<const u64*>& src, con
                 if (((u_mods_ >> m) & 1) && (double)moduli[m] * (22.2 + 70 + 75) >= 4611686018427387904.0) radix4 = false;
             }
             const bool oop = h16 && !radix4;
-            u64* stage = oop ? scratch(spreadbuf_, spreadbuf_words_, (size_t)n * item_words) : nullptr;
+            u64* stage = oop ? scratch(spreadbuf_, (size_t)n * item_words) : nullptr;
             for (int i = 0; i < n; ++i) { da.src[i] = src[base + i]; da.dst[i] = oop ? stage + (size_t)i * item_words : dst[base + i]; }
             da.mods = d_mods; da.map = map_qp(level); da.ta = d_dec_a; da.tb = d_dec_b; da.tc = d_dec_c;
             for (int d = 0; d < nb; ++d) {
@@ -1391,7 +1362,7 @@ void Context::ext_batch(int level, const std::vector<ExtItem>& items, int join_b
         int nf2 = 0;
         for (int i = 0; i < n; ++i) nf2 += items[base + i].f2_party >= 0;
         const int extra = fuse.f2_src.empty() ? 0 : nf2 * (f2_schedule((int)fuse.f2_src.size(), level).parts - 1);
-        u64* c1 = scratch(c1b_, c1b_words_, (size_t)(n + extra) * item_words);
+        u64* c1 = scratch(c1b_, (size_t)(n + extra) * item_words);
         ExtMerge mp;
         const bool merged = stage == 0 && ext_plan_merge(level, items.data() + base, n, mp);
         if (stage != 2) ext_front(level, items.data() + base, n, c1, merged ? &mp : nullptr, fuse);

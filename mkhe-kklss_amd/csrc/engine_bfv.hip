@@ -75,7 +75,7 @@ static void quantize_tail_args(BasisConvArgs& a, const Context& c, u64* polyr, u
 void Context::bfv_quantize(const u64* polyr_ntt, u64* polyq, int npolys) {
     if (!is_bfv()) throw Error("mkhe: not a BFV context");
     const size_t PR = 2 * (size_t)nq * N;
-    u64* tmp = scratch(rbuf_, rbuf_words_, (size_t)npolys * PR);
+    u64* tmp = scratch(rbuf_, (size_t)npolys * PR);
     // scalar multiplication limb by limb: z = x * t  (MRed(x, MForm(t)))
     { ProfScope ps(this, PROF_OTHER, 16.0 * N * npolys * 2 * nq); launch_mul_const(tmp, polyr_ntt, d_mods, d_map_r, d_t_mont, 2 * nq, N, npolys, (long)PR, s_); }
     ntt_r(tmp, tmp, npolys, true);
@@ -164,7 +164,7 @@ void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk
     const size_t PR = 2 * (size_t)nq * N;
     const int np0 = 1 + n0, np1 = 1 + n1, npo = 1 + out.n;
     // rbuf: [ct0R | ct1R | NTT(ct0R) | NTT(ct1R) | tensor out]
-    u64* rb = scratch(rbuf_, rbuf_words_, (size_t)(2 * (np0 + np1) + npo) * PR);
+    u64* rb = scratch(rbuf_, (size_t)(2 * (np0 + np1) + npo) * PR);
     u64 *r0 = rb, *r1 = rb + (size_t)np0 * PR, *f0 = r1 + (size_t)np1 * PR, *f1 = f0 + (size_t)np0 * PR, *tz = f1 + (size_t)np1 * PR;
     bfv_modup_q_to_r(op0.d, r0, np0);
     bfv_rescale(op1.d, r1, np1);
@@ -253,7 +253,7 @@ void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u
     for (int a = 0; a < n0; ++a) if (!rlk_v[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     const size_t PQ = (size_t)nq * N;
     // F1: t_i = <h(c0_i), (y1,y2)>
-    u64* tbuf = scratch(tbuf_, tbuf_words_, (size_t)n0 * PQ);
+    u64* tbuf = scratch(tbuf_, (size_t)n0 * PQ);
     std::vector<ExtItem> items;
     const bool fused = !bp.xk1.empty();
     for (int a = 0; a < n0; ++a) {
@@ -273,7 +273,7 @@ void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u
             // registers of ntt16_f2_kernel, as in Context::mr_finish_head; its parts live behind the tail batch's items in this same allocation)
             f2 = n0 >= 2 && f2_fused_ok(level, n0, n1);
             const int f2_extra = f2 ? 2 * n0 * (f2_schedule(n0, level).parts - 1) : 0;
-            scratch(c1b_, c1b_words_, (size_t)(2 * n0 + n1 + f2_extra) * mtot * N);
+            scratch(c1b_, (size_t)(2 * n0 + n1 + f2_extra) * mtot * N);
             fuse.e_slot = 2 * n0;
         }
     }
@@ -337,7 +337,7 @@ void Context::bfv_mul_relin_unhoisted(const Ct& op0, const Ct& op1, const Swk* c
     for (int a = 0; a < n1; ++a) if (!rlk_b1[a] || !rlk_b2[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     const size_t PR = 2 * (size_t)nq * N, PQ = (size_t)nq * N;
     const int np0 = 1 + n0, np1 = 1 + n1, npo = 1 + out.n;
-    u64* rb = scratch(rbuf_, rbuf_words_, (size_t)(2 * (np0 + np1) + npo) * PR);
+    u64* rb = scratch(rbuf_, (size_t)(2 * (np0 + np1) + npo) * PR);
     u64 *r0 = rb, *r1 = rb + (size_t)np0 * PR, *f0 = r1 + (size_t)np1 * PR, *f1 = f0 + (size_t)np0 * PR, *tz = f1 + (size_t)np1 * PR;
     bfv_modup_q_to_r(op0.d, r0, np0);                  // evaluator.go:102-105
     bfv_rescale(op1.d, r1, np1);                       // evaluator.go:107-110
@@ -384,7 +384,7 @@ void Context::bfv_mul_relin_unhoisted(const Ct& op0, const Ct& op1, const Swk* c
         ext_batch(level, {it});
     }
     // t = ExternalProductBFV(op0_i, y1, y2); ctOut_0 += ExternalProduct(t, v_i); ctOut_i += ExternalProduct(t, u)   (:241-250)
-    u64* t = scratch(tbuf_, tbuf_words_, PQ);
+    u64* t = scratch(tbuf_, PQ);
     for (int a = 0; a < n0; ++a) {
         bfv_decompose_batch({r0 + (size_t)(1 + a) * PR}, {p1}, {p2}, true);
         ExtItem it{p1, y_, t, false}; it.ah2 = p2; it.bg2 = y2_;

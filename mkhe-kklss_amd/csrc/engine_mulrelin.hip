@@ -90,7 +90,7 @@ void Context::mr_prepare(const Ct& op0, const Ct& op1, const Swk* const* hoist0,
     {
         const int level = p.level, L = p.L, n0 = p.n0, n1 = p.n1;
         const size_t PO = (size_t)L * N;
-        u64* nb_ = scratch(nttbuf_, nttbuf_words_, (size_t)(2 + n0 + n1) * PO);
+        u64* nb_ = scratch(nttbuf_, (size_t)(2 + n0 + n1) * PO);
         (void)level;
         fork_side(1);
         s_ = overlap ? stream2 : stream;
@@ -117,7 +117,7 @@ void Context::mr_prepare(const Ct& op0, const Ct& op1, const Swk* const* hoist0,
         // returns it as itself, canonical like everything else -- no inverse NTT for step D.
         const bool fold = n0 >= 1 && !masked_ && 2 * n0 + n1 <= EXT_MAX_ITEMS && ext_merge_members(level) >= 2;
         u64* tout = out.d;
-        if (fold) { tout = scratch(tens_, tens_words_, (size_t)(1 + out.n) * PO); p.tens = tout; }
+        if (fold) { tout = scratch(tens_, (size_t)(1 + out.n) * PO); p.tens = tout; }
         TensorArgs ta{};
         ta.a0 = nb_; ta.b0 = nb_ + (size_t)(1 + n0) * PO; ta.out = tout; ta.mods = d_mods;
         if (fold) ta.scale = d_pmodq;
@@ -199,7 +199,7 @@ void Context::mr_finish_head(const Ct& op0, const Ct& op1, const u64* y, Ct& out
     if (out.limbs != p.L || out.n != p.nout || op0.n != p.n0 || op1.n != p.n1) throw Error("mkhe: mr_finish arguments do not match mr_prepare");
     const int level = p.level, L = p.L, n0 = p.n0;
     const size_t PO = (size_t)L * N;
-    u64* tbuf = scratch(tbuf_, tbuf_words_, (size_t)n0 * PO);
+    u64* tbuf = scratch(tbuf_, (size_t)n0 * PO);
     std::vector<ExtItem> items;
     // F1: t_i = <h(c0_i), y>_P -- the head of the long chain; E (needs x, which may still be accumulating on the side
     // stream) joins the last batch below
@@ -217,14 +217,14 @@ void Context::mr_finish_head(const Ct& op0, const Ct& op1, const u64* y, Ct& out
     const bool will_e = !p.ykeys.empty() && fuse_e_env && 2 * n0 + p.n1 <= EXT_MAX_ITEMS;
     p.f2_fused = n0 > 0 && p.tens != nullptr && f2_fused_ok(level, n0, p.n1);
     const int f2_extra = p.f2_fused ? 2 * n0 * (f2_schedule(n0, level).parts - 1) : 0;
-    if (p.f2_fused && p.ykeys.empty()) scratch(c1b_, c1b_words_, (size_t)(2 * n0 + p.n1 + f2_extra) * mtot * N);
+    if (p.f2_fused && p.ykeys.empty()) scratch(c1b_, (size_t)(2 * n0 + p.n1 + f2_extra) * mtot * N);
     if (!p.ykeys.empty()) {
         fuse.ykeys = p.ykeys; fuse.yh = p.h1;            // ... and y is computed in it
         // ... and step E: the thread holds x[d] and h(c1_j)[d], so <h(c1_j), x> costs it G more accumulators, and x is never stored nor the h(c1_j) read
         // again by the tail batch -- whose c1 slots 2 n0 .. 2 n0 + n1 - 1 (the E items) are filled here: the scratch is sized for the tail now, so
         // that it is the same allocation then (nothing else of a MulAndRelin touches it in between)
         if (will_e) {
-            scratch(c1b_, c1b_words_, (size_t)(2 * n0 + p.n1 + f2_extra) * mtot * N);
+            scratch(c1b_, (size_t)(2 * n0 + p.n1 + f2_extra) * mtot * N);
             fuse.e_slot = 2 * n0;
         }
     }
@@ -401,9 +401,7 @@ const Context::F2Sched& Context::f2_schedule(int np0, int level) {
                          : f2_build_schedule(np0, nb, nslots, w.data(), G, segs.data(), &parts, std::min(3, f2_max_parts(np0)));
     if (nwg > 0) {
         MKHE_HIP(hipSetDevice(device));
-        MKHE_HIP(hipMalloc(&sc.d_segs, segs.size() * sizeof(F2Seg)));
-        const hipError_t e = hipMemcpy(sc.d_segs, segs.data(), segs.size() * sizeof(F2Seg), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(sc.d_segs); sc.d_segs = nullptr; MKHE_HIP(e); }
+        sc.d_segs = mem_.upload(segs);
         sc.nwg = nwg; sc.parts = parts;
     } else { sc.parts = 0; sc.nwg = 0; }
     return f2_sched_.emplace(key, sc).first->second;
@@ -424,12 +422,12 @@ size_t Context::lsh_phase(int phase, const Ct& op0, const Ct& op1, const Swk* co
     const size_t item_words = (size_t)mtot * N, prow = (size_t)np * N * sizeof(u64);
     // P limbs of the c1 pool <-> contiguous staging [item][np][N]; limbs this rank does not own travel as zeros
     auto pack = [&](int n) -> size_t {
-        zero_unowned(c1b_ + (size_t)nq * N, n, (long)item_words, nq, np);
-        if (n) MKHE_HIP(hipMemcpy2DAsync(stage, prow, c1b_ + (size_t)nq * N, item_words * sizeof(u64), prow, n, hipMemcpyDeviceToDevice, s_));
+        zero_unowned(c1b_.p + (size_t)nq * N, n, (long)item_words, nq, np);
+        if (n) MKHE_HIP(hipMemcpy2DAsync(stage, prow, c1b_.p + (size_t)nq * N, item_words * sizeof(u64), prow, n, hipMemcpyDeviceToDevice, s_));
         return (size_t)n * np * N;
     };
     auto unpack = [&](int n) {
-        if (n) MKHE_HIP(hipMemcpy2DAsync(c1b_ + (size_t)nq * N, item_words * sizeof(u64), stage, prow, prow, n, hipMemcpyDeviceToDevice, s_));
+        if (n) MKHE_HIP(hipMemcpy2DAsync(c1b_.p + (size_t)nq * N, item_words * sizeof(u64), stage, prow, prow, n, hipMemcpyDeviceToDevice, s_));
     };
     if (phase == 1) {
         // every rank computes its limbs of the tensor product (c0_0*c1_0 included: the limbs are disjoint), hoists all
@@ -437,10 +435,10 @@ size_t Context::lsh_phase(int phase, const Ct& op0, const Ct& op1, const Swk* co
         mr_prepare(op0, op1, nullptr, nullptr, true, out);
         mr_xy(rlk_b1, rlk_d0, x_, y_, true, false);
         const size_t PO = (size_t)p.L * N;
-        u64* tbuf = scratch(tbuf_, tbuf_words_, (size_t)std::max(p.n0, 1) * PO);
+        u64* tbuf = scratch(tbuf_, (size_t)std::max(p.n0, 1) * PO);
         lsh_items_.clear();
         for (int a = 0; a < p.n0; ++a) lsh_items_.push_back(ExtItem{p.h0[a], y_, tbuf + (size_t)a * PO, false});
-        scratch(c1b_, c1b_words_, (size_t)std::max<size_t>(lsh_items_.size(), 1) * item_words);
+        scratch(c1b_, (size_t)std::max<size_t>(lsh_items_.size(), 1) * item_words);
         ext_batch(p.level, lsh_items_, -1, 1);
         return pack((int)lsh_items_.size());
     }
@@ -450,15 +448,15 @@ size_t Context::lsh_phase(int phase, const Ct& op0, const Ct& op1, const Swk* co
     if (phase == 2) {
         unpack((int)lsh_items_.size());
         ext_batch(level, lsh_items_, -1, 2);                       // t_i, owned limbs
-        zero_unowned(tbuf_, p.n0, (long)PO, 0, L);
-        if (p.n0) MKHE_HIP(hipMemcpyAsync(stage, tbuf_, (size_t)p.n0 * PO * sizeof(u64), hipMemcpyDeviceToDevice, s_));
+        zero_unowned(tbuf_.p, p.n0, (long)PO, 0, L);
+        if (p.n0) MKHE_HIP(hipMemcpyAsync(stage, tbuf_.p, (size_t)p.n0 * PO * sizeof(u64), hipMemcpyDeviceToDevice, s_));
         return (size_t)p.n0 * PO;
     }
     if (phase == 3) {
         if (!crs_u || !rlk_v0) throw Error("mkhe: lsh_phase 3 needs the v keys and the CRS");
-        if (p.n0) MKHE_HIP(hipMemcpyAsync(tbuf_, stage, (size_t)p.n0 * PO * sizeof(u64), hipMemcpyDeviceToDevice, s_));
+        if (p.n0) MKHE_HIP(hipMemcpyAsync(tbuf_.p, stage, (size_t)p.n0 * PO * sizeof(u64), hipMemcpyDeviceToDevice, s_));
         std::vector<const u64*> dsrc; std::vector<u64*> ddst;
-        for (int a = 0; a < p.n0; ++a) { dsrc.push_back(tbuf_ + (size_t)a * PO); ddst.push_back(hoist_slot(2, a).d); }
+        for (int a = 0; a < p.n0; ++a) { dsrc.push_back(tbuf_.p + (size_t)a * PO); ddst.push_back(hoist_slot(2, a).d); }
         if (p.n0) decompose_batch(level, dsrc, ddst, true);
         lsh_items_.clear();
         for (int a = 0; a < p.n1; ++a) lsh_items_.push_back(ExtItem{p.h1[a], x_, out.d + (size_t)(1 + p.slot1[a]) * PO, true});
@@ -467,7 +465,7 @@ size_t Context::lsh_phase(int phase, const Ct& op0, const Ct& op1, const Swk* co
             lsh_items_.push_back(ExtItem{hoist_slot(2, a).d, rlk_v0[a]->d, out.d, true});
             lsh_items_.push_back(ExtItem{hoist_slot(2, a).d, crs_u->d, out.d + (size_t)(1 + p.slot0[a]) * PO, true});
         }
-        scratch(c1b_, c1b_words_, (size_t)std::max<size_t>(lsh_items_.size(), 1) * item_words);
+        scratch(c1b_, (size_t)std::max<size_t>(lsh_items_.size(), 1) * item_words);
         ext_batch(level, lsh_items_, -1, 1);
         return pack((int)lsh_items_.size());
     }

@@ -17,7 +17,7 @@ void Context::rotate(u64 galEl, const Ct& in, const Swk* const* hoist, const Swk
         return;
     }
     Ct tmp; tmp.n = n; tmp.limbs = L; tmp.ids = in.ids;
-    tmp.d = scratch(ctbuf_, ctbuf_words_, (size_t)(1 + n) * L * N);
+    tmp.d = scratch(ctbuf_, (size_t)(1 + n) * L * N);
     rotate_partial(in, hoist, rk, crs, true, tmp);
     automorphism(galEl, tmp, out);
 }
@@ -86,7 +86,7 @@ void Context::conjugate(u64 galEl, const Ct& in, const Swk* const* ck, const Swk
     if (in.limbs < L) throw Error("Cannot Conjugate: ctIn and ctOut have different levels");
     if (out.n != n || out.ids != in.ids) throw Error("mkhe: ctOut must carry the ids of ctIn");
     const size_t PI = (size_t)in.limbs * N, PO = (size_t)L * N;
-    u64* tmp = scratch(ctbuf_, ctbuf_words_, (size_t)(1 + n) * PO);
+    u64* tmp = scratch(ctbuf_, (size_t)(1 + n) * PO);
     if (in.limbs == L) launch_automorphism(tmp, in.d, d_mods, L, logN, galEl, 1 + n, s_);
     else for (int a = 0; a <= n; ++a) launch_automorphism(tmp + a * PO, in.d + a * PI, d_mods, L, logN, galEl, 1, s_);
     if (n == 0) { MKHE_HIP(hipMemcpyAsync(out.d, tmp, PO * sizeof(u64), hipMemcpyDeviceToDevice, s_)); return; }
@@ -133,7 +133,7 @@ void Context::rescale(const Ct& in, int nb, Ct& out) {
     if (nb == 1) {
         launch_div_round_last(out.d, in.d, d_mods, d_rescale + (size_t)(level - 1) * nq, level, N, np_, (long)PI, (long)PO, s_);
     } else {
-        u64* tmp = scratch(ctbuf_, ctbuf_words_, (size_t)np_ * PI);
+        u64* tmp = scratch(ctbuf_, (size_t)np_ * PI);
         launch_div_round_last(tmp, in.d, d_mods, d_rescale + (size_t)(level - 1) * nq, level, N, np_, (long)PI, (long)PI, s_);
         for (int k = 1; k < nb; ++k) {
             const int lv = level - k;
@@ -191,7 +191,7 @@ void Context::ct_mul_ptxt(const Ct& in, const u64* dev_pt, Ct& out) {
     const int L = in.limbs, np_ = 1 + in.n;
     if (out.limbs != L || out.n != in.n || out.ids != in.ids) throw Error("mkhe: ctOut shape does not match ct");
     const size_t PO = (size_t)L * N;
-    u64* tmp = scratch(ctbuf_, ctbuf_words_, (size_t)(1 + np_) * PO);
+    u64* tmp = scratch(ctbuf_, (size_t)(1 + np_) * PO);
     ntt(dev_pt, tmp, 1, L, 0, false, false);
     ntt(in.d, tmp + PO, np_, L, 0, false, false);
     { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (2.0 * np_ + 1)); launch_mul_by_poly(tmp + PO, tmp + PO, tmp, d_mods, L, N, np_, s_); }

@@ -17,9 +17,6 @@ namespace mkhe {
 
 void Context::kg_init() {
     if (kg_ready_) return;
-    MKHE_HIP(hipMalloc(&kg_small_, (size_t)beta_max * N * sizeof(int32_t)));
-    MKHE_HIP(hipMalloc(&kg_g_, 2 * (size_t)beta_max * mtot * sizeof(u64)));
-    MKHE_HIP(hipMalloc(&kg_sk_, (size_t)mtot * N * sizeof(u64)));
     // mkrlwe gadget: MForm(P mod q_j) on the Q limbs [i*alpha, i*alpha + alpha) of digit i, nothing elsewhere
     std::vector<u64> g((size_t)beta_max * mtot, 0);
     for (int i = 0; i < beta_max; ++i)
@@ -28,7 +25,12 @@ void Context::kg_init() {
             for (int k = 0; k < np; ++k) pm = mulmod(pm, moduli[nq + k] % moduli[j], moduli[j]);
             g[(size_t)i * mtot + j] = to_mont(pm, moduli[j]);
         }
-    MKHE_HIP(hipMemcpy(kg_g_, g.data(), g.size() * sizeof(u64), hipMemcpyHostToDevice));
+    const size_t mark = mem_.mark();
+    try {
+        kg_small_ = static_cast<int32_t*>(mem_.alloc((size_t)beta_max * N * sizeof(int32_t)));
+        kg_g_ = alloc_words(2 * (size_t)beta_max * mtot); kg_sk_ = alloc_words((size_t)mtot * N);
+        MKHE_HIP(hipMemcpy(kg_g_, g.data(), g.size() * sizeof(u64), hipMemcpyHostToDevice));
+    } catch (...) { mem_.rollback(mark); throw; }
     kg_ready_ = true;
 }
 
