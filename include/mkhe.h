@@ -229,6 +229,18 @@ int  mkhe_ct_mul_const(mkhe_ctx* ctx, const mkhe_ct* in, const uint64_t* c_first
  * their level): the chain `out = eval.AddNew(out, temp)` over the products of a layer (cnn/cnn.go:19-30,58-62; equal scales: ring.Add per
  * component, mkckks/evaluator.go:316-327) as one launch.  Every partial sum is canonical, so the result is the chain's bit for bit. */
 int  mkhe_ct_sum(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, mkhe_ct* out);
+/* out = sum_k (re_k + i im_k) in[k] + (add_re + i add_im), then nb_rescale (0 or 1) DivRoundByLastModulus steps, as ONE launch: every input limb
+ * is read once, the sum before the division is never stored.  1 <= n <= 16 ciphertexts with the ids of out, each with at least
+ * Lc = limbs(out) + nb_rescale limbs (their first Lc limbs are read: an implicit DropLevel, as in mkhe_ct_sum); out must not alias an input.
+ * dev_consts = device uint64[n + 1][2][Lc] (mkhe_buf_alloc; read when the call executes, so the call is legal inside a capture):
+ * row 0 = (add_re, add_im) as plain canonical residues, rows 1 .. n = (re_k, im_k) in Montgomery form, reduced.
+ * This is NOT the MultByConst convention of the reference (mkhe_ct_mul_const, the half-split of mkckks/evaluator.go:150-196) and has no reference
+ * counterpart: it is defined by i <-> X^(N/2) in the coefficient domain (every slot root zeta^(5^j) raised to N/2 is i, since 5^j = 1 mod 4).  With
+ * h = N/2 and j < h, per limb l < Lc and for every polynomial of the ciphertexts, mod q_l and canonical:
+ *   acc[j]     = sum_k re_k[l] x_k[j]     - im_k[l] x_k[j + h]
+ *   acc[j + h] = sum_k re_k[l] x_k[j + h] + im_k[l] x_k[j]
+ * and on polynomial 0 only acc[0] += add_re[l], acc[h] += add_im[l].  With nb_rescale = 1 out receives what mkhe_rescale(acc, 1) would, bit for bit. */
+int  mkhe_ct_lincomb(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, const void* dev_consts, int nb_rescale, mkhe_ct* out);
 /* mkckks.Evaluator.MulPtxtNew body (evaluator.go:465-478) without its Rescale: every component times the plaintext
  * polynomial dev_pt = uint64[limbs][N] (coefficient domain, device), via NTT / MForm / InvNTT. */
 int  mkhe_ct_mul_ptxt(mkhe_ctx* ctx, const mkhe_ct* in, const void* dev_pt, mkhe_ct* out);

@@ -419,6 +419,8 @@ class Evaluator {
         check(mkhe_ct_mul_const(params.ctx, ct0.h, one.data(), one.data(), out->h));
         return out;
     }
+    // mkhe_ct_lincomb as it is (no reference counterpart): the caller encodes dev_consts [cts.size() + 1][2][ctOut.Level() + 1 + nb_rescale] and sets ctOut.Scale
+    void LinComb(const std::vector<const mkhe_ct*>& cts, const void* dev_consts, int nb_rescale, Ciphertext& ctOut) { check(mkhe_ct_lincomb(params.ctx, (int)cts.size(), cts.data(), dev_consts, nb_rescale, ctOut.h)); }
     // evaluator.go:465-481: dev_pt = the plaintext polynomial uint64[Level()+1][N] resident on the device (mkhe_buf_*), pt_scale its scale
     CiphertextPtr MulPtxtNew(const Ciphertext& ct, const void* dev_pt, double pt_scale) {
         auto out = std::make_unique<Ciphertext>(params, ct.IDSet_(), ct.Level(), ct.Scale * pt_scale, false);

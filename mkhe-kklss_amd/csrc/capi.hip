@@ -478,6 +478,14 @@ int mkhe_ct_sum(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, mkhe_ct* out) {
         need(ctx)->ct_sum(v, out->c);
     })
 }
+int mkhe_ct_lincomb(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, const void* dev_consts, int nb_rescale, mkhe_ct* out) {
+    MKHE_TRY({ mark(ctx, out);
+        if (n < 1 || !in || !dev_consts || !out) throw Error("mkhe_ct_lincomb: bad argument");
+        std::vector<const Ct*> v(n);
+        for (int i = 0; i < n; ++i) { if (!in[i]) throw Error("mkhe_ct_lincomb: null ciphertext"); mark(ctx, in[i]); v[i] = &in[i]->c; }
+        need(ctx)->ct_lincomb(v, (const u64*)dev_consts, nb_rescale, out->c);
+    })
+}
 int mkhe_ct_mul_const(mkhe_ctx* ctx, const mkhe_ct* in, const uint64_t* c_first, const uint64_t* c_second, mkhe_ct* out) {
     MKHE_TRY({ mark(ctx, in, out); if (!in || !out || !c_first || !c_second) throw Error("mkhe_ct_mul_const: null argument"); need(ctx)->ct_mul_const(in->c, c_first, c_second, out->c); })
 }

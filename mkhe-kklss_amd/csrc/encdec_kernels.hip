@@ -59,20 +59,6 @@ void launch_encrypt_finish(int count, const EdTable& out, const u64* w, const i3
     hipLaunchKernelGGL(encrypt_finish_kernel, dim3(ed_bx(N), limbs, count), dim3(ED_THREADS), 0, st, count, out, w, smp, pt_coeff, mods, limbs, N);
 }
 
-// 128-bit accumulator += a * b
-__device__ __forceinline__ void mac128(u64 a, u64 b, u64& hi, u64& lo) {
-    u64 h, l;
-    mul64x64(a, b, h, l);
-    lo += l;
-    hi += h + (lo < l ? 1 : 0);
-}
-// (hi * 2^64 + lo) * 2^-64 mod q, canonical, for hi < 2q (k <= 32 products of residues below q < 2^60: the sum is below 32 q^2 < 2q * 2^64).
-// m = lo * q^-1 mod 2^64 makes the low word of T - m*q vanish, so (T - m*q) / 2^64 = hi - mulhi(m, q) in (-q, 2q).
-__device__ __forceinline__ u64 redc128(u64 hi, u64 lo, const Mod& md) {
-    const u64 mh = mulhi64(lo * md.qinv, md.q);
-    return hi < mh ? hi + md.q - mh : csub(hi - mh, md.q);
-}
-
 __global__ void __launch_bounds__(ED_THREADS) decrypt_mac_kernel(int k, u64* acc, EdTable ch, EdTable sk, const Mod* mods, int limbs, int N) {
     const int j = blockIdx.y, b = blockIdx.z;
     const Mod md = mods[j];

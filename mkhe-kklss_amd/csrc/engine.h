@@ -173,6 +173,9 @@ class Context {
                       const std::vector<const Swk*>& crs, const std::vector<const Ct*>& post_add, const std::vector<Ct*>& outs);
     // out = ins[0] + ... + ins[n-1] (one shape; out at its own level <= theirs): the AddNew chain over the lanes' products as one launch
     void ct_sum(const std::vector<const Ct*>& ins, Ct& out);
+    // out = sum_k (re_k + i im_k) ins[k] + (add_re + i add_im), i = X^(N/2), then nb_rescale (0 or 1) divisions by the last modulus, as one launch
+    // (no reference counterpart).  dev_consts: device uint64[n + 1][2][Lc], Lc = out.limbs + nb_rescale (poly_kernels.h, CtLincombArgs)
+    void ct_lincomb(const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, Ct& out);
     void ct_binary_batch(int op, const std::vector<const Ct*>& a, const std::vector<const Ct*>& b, const std::vector<Ct*>& outs);
     // MulPtxtNew body (ct_mul_ptxt) for the batch, followed by nb >= 0 divisions by the last modulus (outs have limbs(in) - nb limbs)
     void ct_mul_ptxt_batch(const std::vector<const Ct*>& ins, const u64* dev_pt, int nb, const std::vector<Ct*>& outs);

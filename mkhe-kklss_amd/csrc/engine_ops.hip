@@ -187,6 +187,33 @@ void Context::ct_mul_const(const Ct& in, const u64* c_first, const u64* c_second
     MKHE_HIP(hipGetLastError());
 }
 
+// Weighted sum with complex weights, an additive constant and an optional Rescale in ONE pass (launch_ct_lincomb): every input limb is read once and
+// every output limb written once, (n + 1) * 8 * N * Lc * (1 + parties) bytes -- the chain n x ct_mul_const, ct_sum, rescale moves (3n + 3) of them.
+void Context::ct_lincomb(const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, Ct& out) {
+    const int n = (int)ins.size();
+    if (n < 1 || n > CTLIN_MAX) throw Error("mkhe: ct_lincomb takes 1 to " + std::to_string(CTLIN_MAX) + " ciphertexts");
+    if (!dev_consts) throw Error("mkhe: ct_lincomb: null constants");
+    if (nb_rescale != 0 && nb_rescale != 1) throw Error("mkhe: ct_lincomb divides by the last modulus once or not at all");
+    const int Lc = out.limbs + nb_rescale;
+    if (out.limbs < 1) throw Error("cannot Rescale: input Ciphertext already at level 0");          // (Lc = 1 with a division: nothing would be left)
+    check_level(Lc - 1);
+    const size_t PO = (size_t)out.limbs * N, out_words = (size_t)(1 + out.n) * PO;
+    CtLincombArgs a{};
+    for (int k = 0; k < n; ++k) {
+        const Ct& c = *ins[k];
+        if (c.n != out.n || c.ids != out.ids) throw Error("mkhe: ct_lincomb: every summand and ctOut must carry the same ids");
+        if (c.limbs < Lc) throw Error("mkhe: ct_lincomb: a summand has fewer limbs than the sum (limbs(ctOut) + nb_rescale)");
+        // every thread stores limbs of out before it has read all limbs of its inputs: no overlap at all
+        if (c.d < out.d + out_words && out.d < c.d + (size_t)(1 + c.n) * c.limbs * N) throw Error("mkhe: ct_lincomb: ctOut must not alias a summand");
+        a.in[k] = c.d; a.in_poly[k] = (long)c.limbs * N;
+    }
+    a.dst = out.d; a.dst_poly = (long)PO; a.mods = d_mods; a.consts = dev_consts;
+    if (nb_rescale) { a.rescale_row = d_rescale + (size_t)(Lc - 2) * nq; a.rescale_h = a.rescale_row + (size_t)nq * nq; }
+    a.n = n; a.Lc = Lc; a.N = N; a.npolys = 1 + out.n;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * Lc * (n + 1.0) * (1 + out.n)); launch_ct_lincomb(a, s_); }
+    MKHE_HIP(hipGetLastError());
+}
+
 void Context::ct_mul_ptxt(const Ct& in, const u64* dev_pt, Ct& out) {
     const int L = in.limbs, np_ = 1 + in.n;
     if (out.limbs != L || out.n != in.n || out.ids != in.ids) throw Error("mkhe: ctOut shape does not match ct");

@@ -147,6 +147,20 @@ __device__ __forceinline__ void mul64x64(u64 a, u64 b, u64& hi, u64& lo) {
 }
 __device__ __forceinline__ u64 mulhi64(u64 a, u64 b) { u64 h, l; mul64x64(a, b, h, l); return h; }
 
+// 128-bit accumulator += a * b
+__device__ __forceinline__ void mac128(u64 a, u64 b, u64& hi, u64& lo) {
+    u64 h, l;
+    mul64x64(a, b, h, l);
+    lo += l;
+    hi += h + (lo < l ? 1 : 0);
+}
+// (hi * 2^64 + lo) * 2^-64 mod q, canonical, for hi < 2q (k <= 32 products of residues below q < 2^60: the sum is below 32 q^2 < 2q * 2^64).
+// m = lo * q^-1 mod 2^64 makes the low word of T - m*q vanish, so (T - m*q) / 2^64 = hi - mulhi(m, q) in (-q, 2q).
+__device__ __forceinline__ u64 redc128(u64 hi, u64 lo, const Mod& md) {
+    const u64 mh = mulhi64(lo * md.qinv, md.q);
+    return hi < mh ? hi + md.q - mh : csub(hi - mh, md.q);
+}
+
 // Mixed-radix (Garner) digits of the x in [0, Q), Q = q_0 .. q_(limbs-1), whose canonical residue mod q_j is first(j, mods[j]):
 // x = d_0 + d_1 q_0 + d_2 q_0 q_1 + .., d_j = (..((x_j - d_0) q_0^-1 - d_1) q_1^-1 .. - d_(j-1)) q_(j-1)^-1 mod q_j.  d: this coefficient's column of
 // a digit scratch with limb stride N; garner[i * nq + j] = MForm(q_i^-1 mod q_j), i < j (Context::garner_table).

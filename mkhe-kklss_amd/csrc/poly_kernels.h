@@ -345,6 +345,29 @@ struct CtSumArgs {
 };
 void launch_ct_sum(const CtSumArgs& a, hipStream_t st);
 
+// dst = sum_k (re_k + i im_k) in[k] + (add_re + i add_im), optionally followed by ONE DivRoundByLastModulus step, over whole ciphertexts with the same
+// number of polynomials (no reference counterpart).  i is the monomial X^(N/2) of the coefficient domain (every slot root zeta^(5^j) raised to N/2
+// is i, since 5^j = 1 mod 4): with h = N/2 and j < h, per limb l < Lc
+//   acc[j]     = sum_k re_k[l] x_k[j]     - im_k[l] x_k[j + h]        (+ add_re[l] at j = 0 of polynomial 0)
+//   acc[j + h] = sum_k re_k[l] x_k[j + h] + im_k[l] x_k[j]            (+ add_im[l] at j = 0 of polynomial 0)
+// canonical.  consts = [n + 1][2][Lc] on the device: row 0 = (add_re, add_im) as plain residues, rows 1 .. n = (re_k, im_k) in Montgomery form, all
+// below q_l.  rescale_row == NULL: dst has Lc limbs; otherwise it is the RescaleParams row of level Lc - 1 (as div_round_last_kernel takes it) and dst
+// receives the Lc - 1 limbs of DivRoundByLastModulus(acc), the same integers as launch_div_round_last on the stored acc -- which is never stored.
+// Inputs may have more than Lc limbs (in_poly[k] = word stride between the polynomials of input k); dst must not overlap an input.
+constexpr int CTLIN_MAX = CTSUM_MAX < 32 ? CTSUM_MAX : 32;
+struct CtLincombArgs {
+    const u64* in[CTLIN_MAX];
+    long in_poly[CTLIN_MAX];
+    u64* dst;
+    long dst_poly;
+    const Mod* mods;
+    const u64* consts;
+    const u64* rescale_row;
+    const u64* rescale_h;         // [Lc - 1]: (q_(Lc-1) - 1) / 2 mod q_l, as ModDownMergedArgs::rescale_h
+    int n, Lc, N, npolys;
+};
+void launch_ct_lincomb(const CtLincombArgs& a, hipStream_t st);
+
 // dst = CRed(a + b) per limb
 void launch_add(u64* dst, const u64* a, const u64* b, const Mod* mods, int L, int N, hipStream_t st);
 

@@ -1,5 +1,6 @@
 // poly_kernels.hip -- see poly_kernels.h.
 #include "poly_kernels.h"
+#include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
 
@@ -1084,6 +1085,81 @@ void launch_ct_sum(const CtSumArgs& a, hipStream_t st) {
     if (a.n < 1 || a.npolys < 1 || a.L < 1) return;
     const int bx = (a.N + PW_THREADS - 1) / PW_THREADS;
     hipLaunchKernelGGL(ct_sum_kernel, dim3(bx, a.L, a.npolys), dim3(PW_THREADS), 0, st, a);
+}
+// One thread per coefficient pair (j, j + N/2) of one polynomial: lanes walk consecutive j (two coalesced 8-byte streams per input, like the kernels
+// above), and the limb -- with it the modulus, the weights and the input bases -- is wave-uniform (scalar loads).  The limbs are dealt to gridDim.z
+// groups, as many as it takes to fill the chip (launch_ct_lincomb); a thread walks the limbs of its group.  With a rescale it first forms the sum of
+// the dropped limb, whose rounded residue then stays in two registers: one group reads every input limb once, a further group reads the dropped limb
+// again (from the caches: the groups of a coefficient run side by side).  The loads of CH inputs are issued together (CH = 1, 2, 4, 8 by n; the last
+// chunk repeats its last input, whose term is skipped).
+// Reduction: each of the two sums is ONE 128-bit accumulator of at most 2 n <= 2 CTLIN_MAX = 32 products of values below q < 2^60 (inputs canonical,
+// weights reduced, -im enters as q - im), i.e. below 32 q^2 < 2q * 2^64: what redc128 accepts for the widest modulus a Context admits.  One reduction.
+static_assert(CTLIN_MAX <= 16, "ct_lincomb_kernel: 2 * CTLIN_MAX products must stay within the 32 that redc128 accepts for q < 2^60");
+typedef const __attribute__((address_space(4))) CtLincombArgs* ctlin_kargs;
+__device__ __forceinline__ void lincomb_term(u64 xa, u64 xb, u64 re, u64 im, u64 q, u64& h0, u64& l0, u64& h1, u64& l1) {
+    mac128(re, xa, h0, l0); mac128(re, xb, h1, l1);
+    if (im) { mac128(q - im, xb, h0, l0); mac128(im, xa, h1, l1); }      // (wave-uniform: a real weight costs half the products)
+}
+template <int CH>
+__global__ void __launch_bounds__(PW_THREADS) ct_lincomb_kernel(CtLincombArgs a) {
+    ctlin_kargs ka = (ctlin_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    const int half = a.N >> 1, j = blockIdx.x * PW_THREADS + threadIdx.x, p = blockIdx.y, top = a.Lc - 1;
+    if (j >= half) return;
+    const sc_u64 cs = (sc_u64)a.consts;
+    const bool constant_term = p == 0 && j == 0;
+    u64* d = a.dst + (long)p * a.dst_poly;
+    // the canonical sums of limb l for this pair
+    auto sums = [&](int l, const Mod& md, u64& v0, u64& v1) {
+        const long off = (long)l * a.N + j;
+        u64 h0 = 0, l0 = 0, h1 = 0, l1 = 0;
+        for (int k = 0; k < a.n; k += CH) {
+            u64 xa[CH], xb[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int kk = k + u < a.n ? k + u : a.n - 1;
+                const u64* x = ka->in[kk] + (long)p * ka->in_poly[kk] + off;
+                xa[u] = x[0]; xb[u] = x[half];
+            }
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+                if (k + u < a.n) lincomb_term(xa[u], xb[u], cs[(long)(2 * (k + u) + 2) * a.Lc + l], cs[(long)(2 * (k + u) + 3) * a.Lc + l], md.q, h0, l0, h1, l1);
+        }
+        v0 = redc128(h0, l0, md); v1 = redc128(h1, l1, md);
+        if (constant_term) { v0 = csub(v0 + cs[l], md.q); v1 = csub(v1 + cs[a.Lc + l], md.q); }
+    };
+    u64 v0, v1;
+    if (!a.rescale_row) {
+        for (int l = blockIdx.z; l <= top; l += gridDim.z) {
+            const Mod md = load_mod((sc_mod)a.mods + l);
+            sums(l, md, v0, v1);
+            d[(long)l * a.N + j] = v0; d[(long)l * a.N + j + half] = v1;
+        }
+        return;
+    }
+    // DivRoundByLastModulus as div_round_last_kernel restates it; BRedAdd(h, q_l) = h mod q_l comes from the host's table
+    const Mod mt = load_mod((sc_mod)a.mods + top);
+    sums(top, mt, v0, v1);
+    const u64 h = (mt.q - 1) >> 1, t0 = csub(v0 + h, mt.q), t1 = csub(v1 + h, mt.q);
+    for (int l = blockIdx.z; l < top; l += gridDim.z) {
+        const Mod md = load_mod((sc_mod)a.mods + l);
+        sums(l, md, v0, v1);
+        const u64 hneg = md.q - ((sc_u64)a.rescale_h)[l], rp = md.q - ((sc_u64)a.rescale_row)[l];
+        d[(long)l * a.N + j] = mont_mul(t0 + hneg + md.q2 - v0, rp, md.q, md.ninv32);
+        d[(long)l * a.N + j + half] = mont_mul(t1 + hneg + md.q2 - v1, rp, md.q, md.ninv32);
+    }
+}
+void launch_ct_lincomb(const CtLincombArgs& a, hipStream_t st) {
+    const int lout = a.rescale_row ? a.Lc - 1 : a.Lc;
+    if (a.n < 1 || a.n > CTLIN_MAX || a.npolys < 1 || lout < 1) throw std::runtime_error("mkhe: launch_ct_lincomb: bad shape");
+    const int bx = ((a.N >> 1) + PW_THREADS - 1) / PW_THREADS;
+    // limb groups: until every SIMD of the chip (256 CUs x 4) has four waves to hide the load latency behind, at most one group per output limb
+    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys;
+    const int groups = (int)std::min<long>(lout, (fill + threads - 1) / threads);
+    const dim3 grid(bx, a.npolys, groups), blk(PW_THREADS);
+    if (a.n > 4) hipLaunchKernelGGL(ct_lincomb_kernel<8>, grid, blk, 0, st, a);
+    else if (a.n > 2) hipLaunchKernelGGL(ct_lincomb_kernel<4>, grid, blk, 0, st, a);
+    else if (a.n == 2) hipLaunchKernelGGL(ct_lincomb_kernel<2>, grid, blk, 0, st, a);
+    else hipLaunchKernelGGL(ct_lincomb_kernel<1>, grid, blk, 0, st, a);
 }
 // ring.Neg writes q - a, i.e. q for a = 0 (lattigo ring_operations.go Neg), kept literally
 __global__ void __launch_bounds__(PW_THREADS) neg_kernel(u64* dst, const u64* x, const Mod* mods, int N) {

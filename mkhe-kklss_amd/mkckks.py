@@ -3,6 +3,7 @@
 Orchestration and float64 scale bookkeeping stay on the host exactly as in
 mkckks/evaluator.go:359-443,543-617; all polynomial work runs on the device via mkrlwe.KeySwitcher.
 """
+import collections
 import ctypes as C
 import math
 
@@ -306,6 +307,131 @@ class Evaluator:
         if hit is None:
             hit = self._lanes[n] = BatchEvaluator(self.params, n, ev=self)
         return hit
+
+    # ---- weighted sums, additive constants and polynomials (no reference counterpart: its evaluator multiplies by a constant and squares, nothing else).
+    # Everything goes through mkhe_ct_lincomb, where i is the monomial X^(N/2) of the coefficient domain -- NOT MultByConst's half-split.
+    def LinCombNew(self, cts, weights, const=0, scale=None, rescale=True, level=None):
+        """sum_k weights[k] * cts[k] + const (complex weights and constant) as ONE engine call, with an EXACT declared scale: weight k is encoded at
+        S_mid / cts[k].Scale, whatever scales the summands carry, so the sum is at S_mid.  rescale=True: S_mid = scale * Q[l] and the result, one level
+        below the work level l, has Scale == scale; rescale=False: S_mid = scale, the result stays at level l.  l = the lowest level among cts (or the
+        lower `level`: the summands' higher limbs are not read); scale defaults to params.Scale().  A weight that is exactly zero drops its ciphertext.
+        The constants are encoded and uploaded here, once per call: not inside a graph capture."""
+        params = self.params
+        cts, weights, const = list(cts), [complex(w) for w in weights], complex(const)
+        if not cts or len(cts) != len(weights):
+            raise MkheError("LinCombNew: one weight per ciphertext, at least one ciphertext")
+        if any(c.ids != cts[0].ids for c in cts):
+            raise MkheError("LinCombNew: the ciphertexts must carry the same ids")
+        lmin = min(c.Level() for c in cts)
+        l = lmin if level is None else int(level)
+        if l > lmin or l < 0:
+            raise MkheError("LinCombNew: the work level must lie between 0 and the lowest level of the ciphertexts")
+        if rescale and l < 1:
+            raise MkheError("cannot Rescale: input Ciphertext already at level 0")
+        scale = params.Scale() if scale is None else float(scale)
+        terms = [(c, w) for c, w in zip(cts, weights) if w != 0] or [(cts[0], 0j)]
+        if len(terms) > LINCOMB_MAX:
+            raise MkheError("LinCombNew: at most %d non-zero weights per call" % LINCOMB_MAX)
+        s_mid = scale * float(params.Q[l]) if rescale else scale
+        consts = np.zeros((len(terms) + 1, 2, l + 1), dtype=np.uint64)
+        for i, q in enumerate(params.Q[: l + 1]):
+            consts[0, 0, i], consts[0, 1, i] = scaleUpExact(const.real, s_mid, q) % q, scaleUpExact(const.imag, s_mid, q) % q
+            for k, (c, w) in enumerate(terms):
+                ratio = s_mid / c.Scale
+                consts[k + 1, 0, i] = ((scaleUpExact(w.real, ratio, q) % q) << 64) % q              # MForm
+                consts[k + 1, 1, i] = ((scaleUpExact(w.imag, ratio, q) % q) << 64) % q
+        n = params.N()
+        buf = mkrlwe.DeviceLimbs(params, 1, -(-consts.size // n))
+        buf.upload(np.concatenate([consts.ravel(), np.zeros(buf.words - consts.size, dtype=np.uint64)]).reshape(1, buf.limbs, n))
+        out = NewCiphertext(params, cts[0].IDSet(), l - (1 if rescale else 0), scale, zero=False)
+        check(lib().mkhe_ct_lincomb(params.ctx, len(terms), handle_array([c.h for c, _ in terms]), buf.devptr(), 1 if rescale else 0, out.h))
+        return out
+
+    def AddConstNew(self, ct, c):
+        """ct + c for a complex constant c: the weight 1 at ratio 1 is the integer 1, so the ciphertext part is unchanged bit for bit"""
+        return self.LinCombNew([ct], [1], c, scale=ct.Scale, rescale=False)
+
+    def MulRelinOnceNew(self, op0, op1, rlkSet, scale=None):
+        """MulRelinNew where its Rescale count is the usual one; where the scales would make it another number, the product with exactly ONE Rescale all
+        the same (a node of a polynomial evaluation fixes the level).  scale: the declared scale of the result when the caller knows it exactly."""
+        level, prod = min(op0.Level(), op1.Level()), op0.ScalingFactor() * op1.ScalingFactor()
+        if level < 1:
+            raise MkheError("cannot Rescale: input Ciphertext already at level 0")
+        if self._nb_rescales(level, prod, self.params.Scale())[0] == 1:
+            res = self.MulRelinNew(op0, op1, rlkSet)
+        else:
+            res = NewCiphertext(self.params, op0.IDSet() | op1.IDSet(), level - 1, prod / float(self.params.Q[level]), zero=False)
+            self.ksw.MulAndRelinHoisted(op0, op1, None, None, rlkSet, res, rescaled=True)
+        if scale is not None:
+            res.Scale = float(scale)
+        return res
+
+    def EvaluatePolyNew(self, ct, coeffs, rlkSet, scale=None):
+        """sum_k coeffs[k] * ct^k (monomial basis, real or complex coefficients, degree 1 .. 63) by baby steps and giant steps (poly_eval_plan): the result
+        has Scale == scale (default params.Scale()) exactly and level ct.Level() - (ceil(log2(degree + 1)) + 1); MkheError before any engine call when
+        that is below 0."""
+        return evaluate_poly(self, ct, coeffs, rlkSet, scale)
+
+
+LINCOMB_MAX = 16          # ciphertexts per mkhe_ct_lincomb call (csrc/poly_kernels.h, CTLIN_MAX)
+PolyEvalPlan = collections.namedtuple("PolyEvalPlan", "degree m g products depth")
+
+
+def poly_eval_plan(degree):
+    """The baby-step / giant-step schedule of a degree-`degree` polynomial, a pure function: m = 2^ceil(log2(degree + 1) / 2) baby powers X^1 .. X^(m-1),
+    giant powers X^(m i) for 1 <= i < g = ceil((degree + 1) / m).  products = [(k, a, b)]: X^k = X^a * X^b, in an order in which a and b exist already
+    (a = the largest power of two below k, or k / 2, so that depth[k] = ceil(log2 k) multiplications lie under X^k)."""
+    degree = int(degree)
+    if degree < 1:
+        raise MkheError("poly_eval_plan: degree must be at least 1")
+    m = 1 << ((degree.bit_length() + 1) // 2)              # bit_length(d) = ceil(log2(d + 1))
+    g = -(-(degree + 1) // m)
+    products, depth = [], {1: 0}
+    for k in list(range(2, m)) + [m * i for i in range(1, g)]:
+        a = 1 << ((k - 1).bit_length() - 1)                 # 2^(ceil(log2 k) - 1): k / 2 for a power of two
+        products.append((k, a, k - a))
+        depth[k] = depth[a] + 1
+    return PolyEvalPlan(degree, m, g, products, depth)
+
+
+def evaluate_poly(ev, ct, coeffs, rlkSet, scale=None):
+    """Evaluator.EvaluatePolyNew on any evaluator with params, MulRelinOnceNew, LinCombNew and SumNew.  p(X) = sum_i inner_i(X) * X^(m i), inner_i = sum_j
+    coeffs[i m + j] X^j one LinCombNew each.  Scale bookkeeping, with S the target and l_out the level of the result: inner_0 is summed at S * Q[l_out + 1]
+    and rescaled onto (l_out, S); inner_i, i >= 1, is summed at tau_i * Q[l_out + 2] and rescaled to (l_out + 1, tau_i) with tau_i = S * Q[l_out + 1] /
+    scale(X^(m i)), so that its product with the giant power lands on S after that product's single Rescale.  Equal scales, one mkhe_ct_sum."""
+    params = ev.params
+    coeffs = [complex(c) for c in coeffs]
+    d = len(coeffs) - 1
+    if d < 1 or d > 63:
+        raise MkheError("EvaluatePolyNew: the degree must be between 1 and 63")
+    l_out = ct.Level() - (d.bit_length() + 1)
+    if l_out < 0:
+        raise MkheError("EvaluatePolyNew: degree %d needs level %d, the ciphertext is at level %d" % (d, d.bit_length() + 1, ct.Level()))
+    if not any(coeffs):
+        raise MkheError("EvaluatePolyNew: the zero polynomial")
+    S = params.Scale() if scale is None else float(scale)
+    plan = poly_eval_plan(d)
+    m, inner = plan.m, [coeffs[i: i + plan.m] for i in range(0, d + 1, plan.m)]
+    needed = {j for c in inner for j in range(1, len(c)) if c[j] != 0} | {m * i for i in range(1, plan.g) if any(inner[i])}
+    for k, a, b in reversed(plan.products):                 # a power nobody uses is not computed
+        if k in needed:
+            needed |= {a, b}
+    power = {1: ct}
+    for k, a, b in plan.products:
+        if k in needed:
+            power[k] = ev.MulRelinOnceNew(power[a], power[b], rlkSet)
+    babies = lambda c: [power[j] for j in range(1, len(c)) if c[j] != 0] or [ct]
+    weights = lambda c: [w for w in c[1:] if w != 0] or [0]
+    terms = []
+    if any(inner[0]):
+        terms.append(ev.LinCombNew(babies(inner[0]), weights(inner[0]), inner[0][0], scale=S, rescale=True, level=l_out + 1))
+    for i in range(1, plan.g):
+        if any(inner[i]):
+            giant = power[m * i]
+            tau = S * float(params.Q[l_out + 1]) / giant.Scale
+            part = ev.LinCombNew(babies(inner[i]), weights(inner[i]), inner[i][0], scale=tau, rescale=True, level=l_out + 2)
+            terms.append(ev.MulRelinOnceNew(part, giant, rlkSet, scale=S))
+    return ev.SumNew(terms)
 
 
 def NewEvaluator(params):
