@@ -285,6 +285,27 @@ int  mkhe_ct_binary_batch(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* cons
  *      Rescale of :480; the host decides nb_rescale from the scales, :376-384); out has limbs(in) - nb_rescale limbs */
 int  mkhe_ct_mul_ptxt_batch(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, const void* dev_pt, int nb_rescale, mkhe_ct* const* out);
 
+/* ---- Plaintext linear transform M z = sum_k d_k (.) rot_k(z) by baby steps and giant steps: the prepared plaintext and the dot product in the middle
+ *      (no reference counterpart: the reference multiplies by one plaintext at a time, mkckks/evaluator.go:465-481).  mkckks contexts only: a BFV
+ *      context and a context that owns a subset of the moduli are refused.  Every error message starts with the name of the function.
+ *      pt uint64[count][limbs][N] (coefficient domain, canonical: what mkhe_ckks_encode writes) -> ptntt, same shape: MForm(NTT_l(pt_l)) under
+ *      q_0 .. q_(limbs-1), i.e. mkhe_ntt (forward, not lazy) followed by x * 2^64 mod q_l: ONE forward launch of count * limbs limb-NTTs and one pointwise
+ *      launch.  dev_ptntt may be dev_pt.  1 <= limbs <= nQ, 1 <= count <= 65535.  Not for use inside a capture (it may allocate). */
+int  mkhe_ptxt_prepare(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, void* dev_ptntt);
+/*      out[g] = sum over the set bits b of masks[g] of in[b] * P(g, b), g < ngiant: every component of in[b] times the plaintext, negacyclic product
+ *      mod q_l, canonical.  P(g, b) are the prepared plaintexts (mkhe_ptxt_prepare) of pt_limbs limbs each, stored COMPACTLY in (g, b) order: plaintext
+ *      number (set bits of masks[0 .. g-1]) + (set bits of masks[g] below b) lies at dev_ptntt + number * pt_limbs * N words.
+ *      1 <= nin <= 16, 1 <= ngiant <= 64; every mask is non-zero and has no bit >= nin; all in and out handles carry the same ids; L = limbs(out[0])
+ *      for every output; every input has >= L limbs, of which the first L are read (an implicit DropLevel, as in mkhe_ct_sum); pt_limbs >= L; the
+ *      outputs are distinct and alias no input.  masks is a HOST array consumed at call time (it travels in the kernel arguments), the temporaries
+ *      come from the context's pools: after one call of the shape the call is legal between mkhe_capture_begin and mkhe_capture_end.
+ *      Launch set: one forward NTT of all nin * (1 + k) * L limbs, one product kernel that reads every transformed input limb once and every present
+ *      plaintext word once per component, one inverse NTT of ngiant * (1 + k) * L limbs into the outputs.
+ *      Bit-exactness: out[g] equals, bit for bit, mkhe_ct_sum over the set bits b of mkhe_ct_mul_ptxt(in[b] dropped to L limbs, pt(g, b)), pt being the
+ *      coefficient-domain plaintext that mkhe_ptxt_prepare was given: both are the canonical residue of the same integer. */
+int  mkhe_ct_ptxt_dot(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int ngiant, const uint32_t* masks,
+                      const void* dev_ptntt, int pt_limbs, mkhe_ct* const* out);
+
 /* ==== mkbfv ========================================================================================
  * Context for mkbfv.NewParametersFromLiteral (mkbfv/params.go:28-76): rings Q, QMul (same length), R = Q||QMul,
  * P and the plaintext modulus T; replaces mkbfv.NewKeySwitcher (keyswitch.go:31-65) + NewFastBasisExtender

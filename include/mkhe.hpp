@@ -421,6 +421,13 @@ class Evaluator {
     }
     // mkhe_ct_lincomb as it is (no reference counterpart): the caller encodes dev_consts [cts.size() + 1][2][ctOut.Level() + 1 + nb_rescale] and sets ctOut.Scale
     void LinComb(const std::vector<const mkhe_ct*>& cts, const void* dev_consts, int nb_rescale, Ciphertext& ctOut) { check(mkhe_ct_lincomb(params.ctx, (int)cts.size(), cts.data(), dev_consts, nb_rescale, ctOut.h)); }
+    // mkhe_ptxt_prepare / mkhe_ct_ptxt_dot as they are (no reference counterpart): the prepared plaintexts lie compactly in (giant, baby) order; the caller
+    // sets the scales of the outputs
+    void PtxtPrepare(int limbs, int count, const void* dev_pt, void* dev_ptntt) { check(mkhe_ptxt_prepare(params.ctx, limbs, count, dev_pt, dev_ptntt)); }
+    void PtxtDot(const std::vector<const mkhe_ct*>& cts, const std::vector<uint32_t>& masks, const void* dev_ptntt, int pt_limbs, const std::vector<mkhe_ct*>& outs) {
+        if (masks.size() != outs.size()) throw Error("PtxtDot: one mask per output");
+        check(mkhe_ct_ptxt_dot(params.ctx, (int)cts.size(), cts.data(), (int)outs.size(), masks.data(), dev_ptntt, pt_limbs, outs.data()));
+    }
     // evaluator.go:465-481: dev_pt = the plaintext polynomial uint64[Level()+1][N] resident on the device (mkhe_buf_*), pt_scale its scale
     CiphertextPtr MulPtxtNew(const Ciphertext& ct, const void* dev_pt, double pt_scale) {
         auto out = std::make_unique<Ciphertext>(params, ct.IDSet_(), ct.Level(), ct.Scale * pt_scale, false);

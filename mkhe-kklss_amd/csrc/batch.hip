@@ -662,4 +662,93 @@ void Context::ct_mul_ptxt_batch(const std::vector<const Ct*>& ins, const u64* de
     MKHE_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------ plaintext linear transform (no reference counterpart)
+// MForm(NTT(pt)) for count plaintexts of `limbs` limbs: one forward launch, one pointwise launch.  Where source and destination overlap the transform
+// goes through a pooled block (the multi-pass forward kernels read and write different limb-NTT rows of a launch in no order).
+void Context::ptxt_prepare(int limbs, int count, const u64* pt, u64* ptntt) {
+    const char* w = "mkhe_ptxt_prepare: ";
+    if (is_bfv()) throw Error(std::string(w) + "needs a CKKS context");
+    if (masked()) throw Error(std::string(w) + "not available on a context that owns a subset of the moduli");
+    if (!pt || !ptntt) throw Error(std::string(w) + "null buffer");
+    if (limbs < 1 || limbs > nq) throw Error(std::string(w) + "limbs must be between 1 and the number of moduli of Q");
+    if (count < 1 || count > 65535) throw Error(std::string(w) + "count must be between 1 and 65535");
+    const size_t words = (size_t)count * limbs * N;
+    if (pt + words <= ptntt || ptntt + words <= pt) {
+        ntt(pt, ptntt, count, limbs, 0, false, false);
+        launch_mform_polys(ptntt, ptntt, d_mods, limbs, N, count, s_);
+    } else {
+        Arena ar(this, words);
+        u64* t = ar.take(words);
+        ntt(pt, t, count, limbs, 0, false, false);
+        launch_mform_polys(ptntt, t, d_mods, limbs, N, count, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+// outs[g] = sum over the set bits b of masks[g] of ins[b] * P(g, b): one forward launch over every component of every input (their first L limbs),
+// launch_ct_ptxt_dot, one inverse launch into the outputs.  Bytes of the middle kernel: 8 N L [(1 + k) nin + (1 + k) nnz + (1 + k) ngiant], of which
+// 8 N L k nnz are re-reads of plaintext words by the other components (poly_kernels.hip).  The temporaries are one pooled block; masks and offsets
+// are kernel arguments: nothing is allocated from the driver after a first call of the shape and nothing is uploaded, so the call may be captured.
+void Context::ct_ptxt_dot(const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptntt, int pt_limbs, const std::vector<Ct*>& outs) {
+    const std::string w = "mkhe_ct_ptxt_dot: ";
+    if (is_bfv()) throw Error(w + "needs a CKKS context");
+    if (masked()) throw Error(w + "not available on a context that owns a subset of the moduli");
+    const int nin = (int)ins.size(), ngiant = (int)outs.size();
+    if (nin < 1 || nin > CTDOT_MAX_IN) throw Error(w + "takes 1 to " + std::to_string(CTDOT_MAX_IN) + " input ciphertexts");
+    if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT) throw Error(w + "takes 1 to " + std::to_string(CTDOT_MAX_GIANT) + " outputs");
+    if ((int)masks.size() != ngiant) throw Error(w + "one mask per output");
+    if (!ptntt) throw Error(w + "null plaintext block");
+    const Ct& o0 = *outs[0];
+    const int L = o0.limbs, np_ = 1 + o0.n;
+    if (L < 1 || L > nq) throw Error(w + "the outputs' limb count lies outside the moduli of Q");
+    if (pt_limbs < L) throw Error(w + "the prepared plaintexts have fewer limbs than the outputs");
+    const size_t PO = (size_t)L * N;
+    for (const Ct* o : outs)
+        if (o->limbs != L || o->n != o0.n || o->ids != o0.ids) throw Error(w + "the outputs must have one shape");
+    for (int g = 0; g < ngiant; ++g)
+        for (int h = 0; h < g; ++h)
+            if (outs[g]->d < outs[h]->d + np_ * PO && outs[h]->d < outs[g]->d + np_ * PO) throw Error(w + "the outputs must be distinct");
+    for (const Ct* c : ins) {
+        if (c->n != o0.n || c->ids != o0.ids) throw Error(w + "every input and output must carry the same ids");
+        if (c->limbs < L) throw Error(w + "an input has fewer limbs than the outputs");
+        for (const Ct* o : outs)
+            if (c->d < o->d + np_ * PO && o->d < c->d + (size_t)np_ * c->limbs * N) throw Error(w + "an output must not alias an input");
+    }
+    CtPtxtDotArgs a{};
+    int nnz = 0;
+    for (int g = 0; g < ngiant; ++g) {
+        const unsigned int m = masks[g];
+        if (!m) throw Error(w + "a mask is zero");
+        if (m >> nin) throw Error(w + "a mask has a bit at or above the number of inputs");
+        a.mask[g] = m; a.first[g] = (unsigned short)nnz;
+        nnz += __builtin_popcount(m);
+    }
+    Arena ar(this, (size_t)(nin + ngiant) * np_ * PO);
+    u64* x = ar.take((size_t)nin * np_ * PO); u64* y = ar.take((size_t)ngiant * np_ * PO);
+    // inputs above the outputs' level have their own word stride between polynomials: one launch per run of inputs with the same limb count
+    for (int b0 = 0; b0 < nin;) {
+        int b1 = b0 + 1;
+        while (b1 < nin && ins[b1]->limbs == ins[b0]->limbs) ++b1;
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = (long)ins[b0]->limbs * N; b.dst_outer = (long)PO;
+        b.nitems = b1 - b0; b.outers_per_item = np_; b.nouter = (b1 - b0) * np_;
+        for (int i = b0; i < b1; ++i) { b.src_items[i - b0] = ins[i]->d; b.dst_items[i - b0] = x + (size_t)i * np_ * PO; }
+        ntt_fwd_launch(b, false);
+        b0 = b1;
+    }
+    a.x = x; a.y = y; a.pt = ptntt; a.mods = d_mods; a.pt_words = (long)pt_limbs * N;
+    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * (nin + nnz + ngiant)); launch_ct_ptxt_dot(a, s_); }
+    {
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
+        b.nitems = ngiant; b.outers_per_item = np_; b.nouter = ngiant * np_;
+        for (int g = 0; g < ngiant; ++g) { b.src_items[g] = y + (size_t)g * np_ * PO; b.dst_items[g] = outs[g]->d; }
+        { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
 }  // namespace mkhe

@@ -575,6 +575,21 @@ int mkhe_ct_mul_ptxt_batch(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, 
         need(ctx)->ct_mul_ptxt_batch(i, (const u64*)dev_pt, nb_rescale, o);
     })
 }
+int mkhe_ptxt_prepare(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, void* dev_ptntt) {
+    MKHE_TRY({ if (!ctx) throw Error("mkhe_ptxt_prepare: null context"); need(ctx)->ptxt_prepare(limbs, count, (const u64*)dev_pt, (u64*)dev_ptntt); })
+}
+int mkhe_ct_ptxt_dot(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int ngiant, const uint32_t* masks, const void* dev_ptntt, int pt_limbs,
+                     mkhe_ct* const* out) {
+    MKHE_TRY({
+        if (!ctx) throw Error("mkhe_ct_ptxt_dot: null context");
+        if (nin < 1 || nin > CTDOT_MAX_IN) throw Error("mkhe_ct_ptxt_dot: takes 1 to " + std::to_string(CTDOT_MAX_IN) + " input ciphertexts");
+        if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT) throw Error("mkhe_ct_ptxt_dot: takes 1 to " + std::to_string(CTDOT_MAX_GIANT) + " outputs");
+        if (!masks || !dev_ptntt) throw Error("mkhe_ct_ptxt_dot: null argument");
+        auto i = ct_list(ctx, in, nin, "mkhe_ct_ptxt_dot");
+        auto o = ct_list_out(ctx, out, ngiant, "mkhe_ct_ptxt_dot");
+        need(ctx)->ct_ptxt_dot(i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptntt, pt_limbs, o);
+    })
+}
 int mkhe_ct_binary_batch(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* op0, const mkhe_ct* const* op1, mkhe_ct* const* out) {
     MKHE_TRY({
         if (nbatch < 1 || (op != 0 && op != 1)) throw Error("mkhe_ct_binary_batch: bad argument");

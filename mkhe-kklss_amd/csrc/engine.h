@@ -176,6 +176,10 @@ class Context {
     // out = sum_k (re_k + i im_k) ins[k] + (add_re + i add_im), i = X^(N/2), then nb_rescale (0 or 1) divisions by the last modulus, as one launch
     // (no reference counterpart).  dev_consts: device uint64[n + 1][2][Lc], Lc = out.limbs + nb_rescale (poly_kernels.h, CtLincombArgs)
     void ct_lincomb(const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, Ct& out);
+    // plaintext linear transform (no reference counterpart; batch.hip): ptntt = MForm(NTT(pt)) for count plaintexts [limbs][N] (ptntt may be pt), and
+    // outs[g] = sum over the set bits b of masks[g] of ins[b] * P(g, b), the prepared plaintexts compact in (g, b) order at ptntt with pt_limbs limbs each
+    void ptxt_prepare(int limbs, int count, const u64* pt, u64* ptntt);
+    void ct_ptxt_dot(const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptntt, int pt_limbs, const std::vector<Ct*>& outs);
     void ct_binary_batch(int op, const std::vector<const Ct*>& a, const std::vector<const Ct*>& b, const std::vector<Ct*>& outs);
     // MulPtxtNew body (ct_mul_ptxt) for the batch, followed by nb >= 0 divisions by the last modulus (outs have limbs(in) - nb limbs)
     void ct_mul_ptxt_batch(const std::vector<const Ct*>& ins, const u64* dev_pt, int nb, const std::vector<Ct*>& outs);

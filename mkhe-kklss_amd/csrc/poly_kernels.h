@@ -368,6 +368,26 @@ struct CtLincombArgs {
 };
 void launch_ct_lincomb(const CtLincombArgs& a, hipStream_t st);
 
+// y[g] = sum over the set bits b of mask[g] of x[b] * P(g, b), g < ngiant, pointwise in the NTT domain, per polynomial and limb, canonical: the middle of
+// a plaintext linear transform by baby steps and giant steps (no reference counterpart).  x = [nin][npolys][L][N]: the forward transforms of the baby
+// rotations, canonical; y = [ngiant][npolys][L][N]; pt = the prepared plaintexts MForm(NTT(p)), compact in (g, b) order: number first[g] + (set bits of
+// mask[g] below b) lies at pt + index * pt_words (pt_words >= L * N: only the first L limbs of a plaintext are read).  Masks and offsets travel in the
+// kernel arguments: nothing is uploaded, so the launch may be captured.  x and y must not overlap.
+constexpr int CTDOT_MAX_IN = 16, CTDOT_MAX_GIANT = 64;
+struct CtPtxtDotArgs {
+    const u64* x;
+    u64* y;
+    const u64* pt;
+    const Mod* mods;
+    long pt_words;
+    unsigned int mask[CTDOT_MAX_GIANT];
+    unsigned short first[CTDOT_MAX_GIANT];       // (at most 64 * 16 plaintexts)
+    int nin, ngiant, L, N, npolys;
+};
+void launch_ct_ptxt_dot(const CtPtxtDotArgs& a, hipStream_t st);
+// dst = MForm(src) for count polynomials of L limbs each (limb l under mods[l]); dst may be src
+void launch_mform_polys(u64* dst, const u64* src, const Mod* mods, int L, int N, int count, hipStream_t st);
+
 // dst = CRed(a + b) per limb
 void launch_add(u64* dst, const u64* a, const u64* b, const Mod* mods, int L, int N, hipStream_t st);
 

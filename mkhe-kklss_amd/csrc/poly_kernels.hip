@@ -1161,6 +1161,76 @@ void launch_ct_lincomb(const CtLincombArgs& a, hipStream_t st) {
     else if (a.n == 2) hipLaunchKernelGGL(ct_lincomb_kernel<2>, grid, blk, 0, st, a);
     else hipLaunchKernelGGL(ct_lincomb_kernel<1>, grid, blk, 0, st, a);
 }
+// One thread per coefficient j of one polynomial (component) of the ciphertexts, lanes on consecutive j (coalesced 8-byte streams), the limb -- with it
+// the modulus, the masks and every base address -- wave-uniform; limbs dealt to gridDim.z groups as in ct_lincomb_kernel.  The thread loads its
+// coefficient of the nin transformed inputs ONCE into registers (NI = 4, 8 or 16 slots of two VGPRs) and then walks the giants: per giant the prepared
+// plaintext words of the set mask bits are loaded, eight bits at a time (an absent diagonal is a skipped scalar branch: no load, no product), and one
+// 128-bit accumulator takes the products and is reduced once.  At most CTDOT_MAX_IN = 16 products of values below q < 2^60 per sum (inputs canonical,
+// plaintexts MForm'ed and reduced): half of what redc128 accepts.
+// A plaintext word is read once per component, 1 + parties times in all -- from the caches, since the workgroups of one (block of j, limb) run side by
+// side -- and the thread holds 2 NI + 16 VGPRs of operands whatever the number of parties.  Threads that own several components read it once per
+// group at that many times the held inputs; they were measured and not kept.
+static_assert(CTDOT_MAX_IN <= 32, "ct_ptxt_dot_kernel: one sum must stay within the 32 products that redc128 accepts for q < 2^60");
+typedef const __attribute__((address_space(4))) CtPtxtDotArgs* ctdot_kargs;
+template <int NI>
+__global__ void __launch_bounds__(PW_THREADS) ct_ptxt_dot_kernel(CtPtxtDotArgs a) {
+    ctdot_kargs ka = (ctdot_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    const int j = blockIdx.x * PW_THREADS + threadIdx.x, p = blockIdx.y;
+    if (j >= a.N) return;
+    const long PO = (long)a.L * a.N, CO = PO * a.npolys;
+    constexpr int CH = NI < 8 ? NI : 8;
+    for (int l = blockIdx.z; l < a.L; l += gridDim.z) {
+        const Mod md = load_mod((sc_mod)a.mods + l);
+        const long off = (long)l * a.N + j;
+        u64 x[NI];
+        long xi = (long)p * PO + off;              // (walked, not b * CO: sixteen hoisted 64-bit offsets would not fit the scalar registers)
+#pragma unroll
+        for (int b = 0; b < NI; ++b, xi += CO) x[b] = b < a.nin ? a.x[xi] : 0;
+        long yi = (long)p * PO + off;
+        for (int g = 0; g < a.ngiant; ++g, yi += CO) {
+            const unsigned int m = ka->mask[g];
+            const u64* w = a.pt + (long)ka->first[g] * a.pt_words + off;
+            u64 hi = 0, lo = 0;
+#pragma unroll
+            for (int b0 = 0; b0 < NI; b0 += CH) {
+                u64 pw[CH];
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    pw[u] = 0;
+                    if ((m >> (b0 + u)) & 1) { pw[u] = *w; w += a.pt_words; }
+                }
+#pragma unroll
+                for (int u = 0; u < CH; ++u)
+                    if ((m >> (b0 + u)) & 1) mac128(x[b0 + u], pw[u], hi, lo);
+            }
+            a.y[yi] = redc128(hi, lo, md);
+        }
+    }
+}
+void launch_ct_ptxt_dot(const CtPtxtDotArgs& a, hipStream_t st) {
+    if (a.nin < 1 || a.nin > CTDOT_MAX_IN || a.ngiant < 1 || a.ngiant > CTDOT_MAX_GIANT || a.npolys < 1 || a.L < 1 || a.pt_words < (long)a.L * a.N)
+        throw std::runtime_error("mkhe: launch_ct_ptxt_dot: bad shape");
+    for (int g = 0; g < a.ngiant; ++g)
+        if (!a.mask[g] || (a.mask[g] >> a.nin)) throw std::runtime_error("mkhe: launch_ct_ptxt_dot: bad mask");
+    const int bx = (a.N + PW_THREADS - 1) / PW_THREADS;
+    // limb groups as in launch_ct_lincomb: until every SIMD of the chip has four waves, at most one group per limb
+    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys;
+    const int groups = (int)std::min<long>(a.L, (fill + threads - 1) / threads);
+    const dim3 grid(bx, a.npolys, groups), blk(PW_THREADS);
+    if (a.nin > 8) hipLaunchKernelGGL(ct_ptxt_dot_kernel<16>, grid, blk, 0, st, a);
+    else if (a.nin > 4) hipLaunchKernelGGL(ct_ptxt_dot_kernel<8>, grid, blk, 0, st, a);
+    else hipLaunchKernelGGL(ct_ptxt_dot_kernel<4>, grid, blk, 0, st, a);
+}
+__global__ void __launch_bounds__(PW_THREADS) mform_polys_kernel(u64* dst, const u64* src, const Mod* mods, int L, int N) {
+    const int l = blockIdx.y;
+    const Mod md = mods[l];
+    const long base = ((long)blockIdx.z * L + l) * N;
+    for (int n = blockIdx.x * PW_THREADS + threadIdx.x; n < N; n += gridDim.x * PW_THREADS) dst[base + n] = mont_mul(src[base + n], md.r2, md.q, md.ninv32);
+}
+void launch_mform_polys(u64* dst, const u64* src, const Mod* mods, int L, int N, int count, hipStream_t st) {
+    const int bx = (N + PW_THREADS - 1) / PW_THREADS;
+    hipLaunchKernelGGL(mform_polys_kernel, dim3(bx, L, count), dim3(PW_THREADS), 0, st, dst, src, mods, L, N);
+}
 // ring.Neg writes q - a, i.e. q for a = 0 (lattigo ring_operations.go Neg), kept literally
 __global__ void __launch_bounds__(PW_THREADS) neg_kernel(u64* dst, const u64* x, const Mod* mods, int N) {
     const int l = blockIdx.y;

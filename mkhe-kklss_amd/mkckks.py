@@ -372,6 +372,13 @@ class Evaluator:
         that is below 0."""
         return evaluate_poly(self, ct, coeffs, rlkSet, scale)
 
+    def LinearTransformNew(self, ct, lt, rkSet, fused=True):
+        """M z for the cleartext diagonals of `lt` (LinearTransform): sum_g rot_g(sum_b d'_(g,b) (.) rot_b ct) with one Rescale, the result at level
+        lt.level - 1 and at Scale lt.out_scale exactly when ct.Scale == lt.in_scale (ct.Scale * lt.pt_scale / Q[lt.level] otherwise).  MkheError before any
+        engine call when ct lies below lt.level, lt.level < 1 or a CRS / rotation key of lt.Rotations() is missing.  fused=False runs the same schedule
+        through the single-operation entry points (it needs LinearTransform(.., keep_coeff=True)) and gives the same ciphertext bit for bit."""
+        return linear_transform(self, ct, lt, rkSet, fused)
+
 
 LINCOMB_MAX = 16          # ciphertexts per mkhe_ct_lincomb call (csrc/poly_kernels.h, CTLIN_MAX)
 PolyEvalPlan = collections.namedtuple("PolyEvalPlan", "degree m g products depth")
@@ -432,6 +439,185 @@ def evaluate_poly(ev, ct, coeffs, rlkSet, scale=None):
             part = ev.LinCombNew(babies(inner[i]), weights(inner[i]), inner[i][0], scale=tau, rescale=True, level=l_out + 2)
             terms.append(ev.MulRelinOnceNew(part, giant, rlkSet, scale=S))
     return ev.SumNew(terms)
+
+
+# ---- plaintext linear transforms M z = sum_k d_k (.) rot_k(z) (no reference counterpart: the reference has MulPtxtNew and RotateNew, one at a time)
+PTXT_DOT_MAX_IN, PTXT_DOT_MAX_GIANT = 16, 64          # csrc/poly_kernels.h, CTDOT_MAX_IN / CTDOT_MAX_GIANT
+LinTransPlan = collections.namedtuple("LinTransPlan", "n1 babies giants")
+
+
+def linear_transform_plan(indices, n, n1=None):
+    """Baby steps and giant steps for the diagonal indices `indices` (taken mod n = N/2), a pure function: k = b + g with b = k mod n1 and g = k - b.
+    -> (n1, sorted babies, sorted giants).  n1 is a power of two <= 16; the default minimises the number of rotations (non-zero babies + non-zero
+    giants), ties to the smaller n1.  MkheError when the diagonals need more than 64 giants."""
+    n = int(n)
+    idx = sorted({int(k) % n for k in indices})
+    if not idx:
+        raise MkheError("linear_transform_plan: no diagonal")
+    if n1 is not None and (int(n1) != n1 or n1 < 1 or n1 > PTXT_DOT_MAX_IN or n1 & (n1 - 1)):
+        raise MkheError("linear_transform_plan: n1 must be a power of two, at most %d" % PTXT_DOT_MAX_IN)
+    best = None
+    for m in ([int(n1)] if n1 is not None else [1, 2, 4, 8, 16]):
+        babies, giants = sorted({k % m for k in idx}), sorted({k - k % m for k in idx})
+        cost = sum(1 for b in babies if b) + sum(1 for g in giants if g)
+        if len(giants) <= PTXT_DOT_MAX_GIANT and (best is None or cost < best[0]):
+            best = (cost, LinTransPlan(m, babies, giants))
+    if best is None:
+        raise MkheError("linear_transform_plan: more than %d giant steps" % PTXT_DOT_MAX_GIANT)
+    return best[1]
+
+
+class LinearTransform:
+    """The diagonals {k: d_k} of (M z)[j] = sum_k d_k[j] z[(j + k) mod n], n = N/2 slots -- the convention of RotateNew(ct, k), which moves slot j + k to
+    slot j -- encoded once for Evaluator.LinearTransformNew.  Diagonal k = g + b (linear_transform_plan) is stored pre-rotated, np.roll(d_k, g), so that
+    M z = sum_g rot_g(sum_b d'_(g,b) (.) rot_b z).  All of them are encoded on the device in ONE EncodeBatch at `level` and at the scale
+    pt_scale = out_scale * Q[level] / in_scale (both default to params.Scale()), then prepared in ONE mkhe_ptxt_prepare into a compact block in (g, b)
+    order: no plaintext transform is left for the evaluation.  keep_coeff=True also keeps the coefficient-domain plaintexts (LinearTransformNew(..,
+    fused=False))."""
+
+    def __init__(self, params, diagonals, level, in_scale=None, out_scale=None, n1=None, keep_coeff=False):
+        n = params.N() // 2
+        level = int(level)
+        if level < 0 or level > params.MaxLevel():
+            raise MkheError("LinearTransform: the level must lie between 0 and %d" % params.MaxLevel())
+        diag = {}
+        for k, d in dict(diagonals).items():
+            d = np.asarray(d, dtype=np.complex128)
+            if d.shape != (n,):
+                raise MkheError("LinearTransform: diagonal %d must have %d slots, got %r" % (k, n, d.shape))
+            if int(k) % n in diag:
+                raise MkheError("LinearTransform: diagonal %d is given twice (indices are taken mod %d)" % (k, n))
+            diag[int(k) % n] = d
+        self.params, self.level, self.n = params, level, n
+        self.plan = linear_transform_plan(diag, n, n1)
+        self.in_scale = params.Scale() if in_scale is None else float(in_scale)
+        self.out_scale = params.Scale() if out_scale is None else float(out_scale)
+        self.pt_scale = self.out_scale * float(params.Q[level]) / self.in_scale
+        babies, giants = self.plan.babies, self.plan.giants
+        self.order = [(g, b) for g in giants for b in babies if (g + b) in diag]          # (g + b < n: g <= k and b = k - g)
+        self.masks = [sum(1 << i for i, b in enumerate(babies) if (g + b) in diag) for g in giants]
+        self.pt_coeff = DeviceEncoder(params).EncodeBatch(np.stack([np.roll(diag[g + b], g) for g, b in self.order]), level, self.pt_scale)
+        self.pt = mkrlwe.DeviceLimbs(params, len(self.order), level + 1) if keep_coeff else self.pt_coeff
+        check(lib().mkhe_ptxt_prepare(params.ctx, level + 1, len(self.order), self.pt_coeff.devptr(), self.pt.devptr()))
+        if not keep_coeff:
+            self.pt_coeff = None
+
+    @classmethod
+    def FromMatrix(cls, params, M, level, **kw):
+        """the d x d matrix M, d a power of two <= n, as the d diagonals of the d-periodic operator d_k[j] = M[j mod d][(j + k) mod d]: on a vector whose
+        d entries are replicated n / d times it gives M @ v, replicated.  Diagonals that are zero throughout are left out."""
+        M = np.asarray(M, dtype=np.complex128)
+        n, d = params.N() // 2, M.shape[0]
+        if M.ndim != 2 or M.shape != (d, d) or d < 1 or d & (d - 1) or d > n:
+            raise MkheError("LinearTransform.FromMatrix: the matrix must be d x d with d a power of two, at most %d" % n)
+        diags = matrix_diagonals(M, n)
+        if not diags:
+            raise MkheError("LinearTransform.FromMatrix: the zero matrix")
+        return cls(params, diags, level, **kw)
+
+    def Rotations(self):
+        """the sorted non-zero baby and giant indices: what AddCRS / GenRotationKey must have provided"""
+        return sorted({r for r in self.plan.babies + self.plan.giants if r})
+
+
+def matrix_diagonals(M, n):
+    """{k: d_k} with d_k[j] = M[j mod d][(j + k) mod d] over n slots, the all-zero diagonals left out (LinearTransform.FromMatrix)"""
+    M = np.asarray(M, dtype=np.complex128)
+    d, j = M.shape[0], np.arange(n)
+    out = {k: M[j % d, (j + k) % d] for k in range(d)}
+    return {k: v for k, v in out.items() if v.any()}
+
+
+def linear_transform(ev, ct, lt, rkSet, fused=True):
+    """Evaluator.LinearTransformNew.  Launch sets of the fused form: HoistedForm(ct) once; the non-zero baby rotations as lanes of ONE mkhe_rotate_multi that
+    share that hoisted form; ONE mkhe_ct_ptxt_dot; the non-zero giant rotations of the inner sums as lanes of ONE mkhe_rotate_multi; ONE mkhe_ct_lincomb
+    with weights 1 that carries the Rescale (more than 16 summands: first reduced in groups by mkhe_ct_sum).  A ciphertext above lt.level is first
+    dropped to it (DropLevelNew), in both forms: a hoisted form belongs to the level it was made at."""
+    params, level = ev.params, lt.level
+    if lt.params is not params:
+        raise MkheError("LinearTransformNew: the transform was encoded for other parameters")
+    if level < 1:
+        raise MkheError("cannot Rescale: the linear transform is encoded at level 0")
+    if ct.Level() < level:
+        raise MkheError("LinearTransformNew: the ciphertext is at level %d, the transform was encoded at level %d" % (ct.Level(), level))
+    if not fused and lt.pt_coeff is None:
+        raise MkheError("LinearTransformNew: fused=False needs LinearTransform(.., keep_coeff=True)")
+    babies, giants = lt.plan.babies, lt.plan.giants
+    keys = {}
+    for r in lt.Rotations():
+        if r not in params.CRS:
+            raise MkheError("LinearTransformNew: no CRS for rotation index %d" % r)
+        keys[r] = [rkSet.GetRotationKey(i, r).Value.h for i in ct.ids]           # (MkheError when a party has none)
+    L, ctx = lib(), params.ctx
+    if ct.Level() > level:
+        ct = ev.DropLevelNew(ct, ct.Level() - level)
+    mid_scale = ct.Scale * lt.pt_scale
+    new = lambda scale, lv=level: NewCiphertext(params, ct.IDSet(), lv, scale, zero=False)
+    hoisted = ev.HoistedForm(ct) if any(babies) else None
+
+    def rotate_lanes(srcs, rots, hoist):
+        """srcs[i] rotated by rots[i] != 0, as lanes of one mkhe_rotate_multi; hoist: the hoisted form every lane shares, or None"""
+        outs = [new(c.Scale) for c in srcs]
+        gal = (C.c_uint64 * len(rots))(*[params.GaloisElementForColumnRotationBy(r) for r in rots])
+        hs = handle_array([hoist.Value[i].h for i in ct.ids] * len(rots)) if hoist is not None else None
+        check(L.mkhe_rotate_multi(ctx, len(rots), gal, handle_array([c.h for c in srcs]), hs, handle_array([h for r in rots for h in keys[r]]),
+                                  handle_array([params.CRS[r].h for r in rots]), None, handle_array([o.h for o in outs])))
+        return outs
+
+    words = (level + 1) * params.N()
+    if fused:
+        nzb = [b for b in babies if b]
+        rot = dict(zip(nzb, rotate_lanes([ct] * len(nzb), nzb, hoisted))) if nzb else {}
+        rot[0] = ct
+        inner = [new(mid_scale) for _ in giants]
+        masks = (C.c_uint32 * len(giants))(*lt.masks)
+        check(L.mkhe_ct_ptxt_dot(ctx, len(babies), handle_array([rot[b].h for b in babies]), len(giants), masks, lt.pt.devptr(), level + 1,
+                                 handle_array([c.h for c in inner])))
+        nzg = [(g, c) for g, c in zip(giants, inner) if g]
+        terms = [c for g, c in zip(giants, inner) if not g]
+        if nzg:
+            terms += rotate_lanes([c for _, c in nzg], [g for g, _ in nzg], None)
+        while len(terms) > LINCOMB_MAX:
+            groups = [terms[i: i + LINCOMB_MAX] for i in range(0, len(terms), LINCOMB_MAX)]
+            terms = []
+            for grp in groups:
+                terms.append(new(mid_scale))
+                check(L.mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), terms[-1].h))
+        consts = np.zeros((len(terms) + 1, 2, level + 1), dtype=np.uint64)
+        consts[1:, 0, :] = np.array([(1 << 64) % q for q in params.Q[: level + 1]], dtype=np.uint64)              # MForm(1)
+        n = params.N()
+        buf = mkrlwe.DeviceLimbs(params, 1, -(-consts.size // n))
+        buf.upload(np.concatenate([consts.ravel(), np.zeros(buf.words - consts.size, dtype=np.uint64)]).reshape(1, buf.limbs, n))
+        out = new(0.0, level - 1)
+        check(L.mkhe_ct_lincomb(ctx, len(terms), handle_array([c.h for c in terms]), buf.devptr(), 1, out.h))
+    else:
+        rot = {b: ev.RotateHoistedNew(ct, b, hoisted, rkSet) if b else ct for b in babies}
+
+        def summed(cts):
+            if len(cts) == 1:
+                return cts[0]
+            acc = None
+            for i in range(0, len(cts), LINCOMB_MAX - 1):
+                grp = ([acc] if acc is not None else []) + cts[i: i + LINCOMB_MAX - 1]
+                acc = new(mid_scale)
+                check(L.mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), acc.h))
+            return acc
+
+        terms, index = [], 0
+        for g, mask in zip(giants, lt.masks):
+            prods = []
+            for i, b in enumerate(babies):
+                if mask >> i & 1:
+                    prods.append(new(mid_scale))
+                    check(L.mkhe_ct_mul_ptxt(ctx, rot[b].h, C.c_void_p(lt.pt_coeff.devptr().value + 8 * words * index), prods[-1].h))
+                    index += 1
+            part = summed(prods)
+            terms.append(ev.RotateNew(part, g, rkSet) if g else part)
+        total = summed(terms)
+        out = new(0.0, level - 1)
+        check(L.mkhe_rescale(ctx, total.h, 1, out.h))
+    out.Scale = lt.out_scale if ct.Scale == lt.in_scale else mid_scale / float(params.Q[level])
+    return out
 
 
 def NewEvaluator(params):
