@@ -150,6 +150,21 @@ int  mkhe_mul_relin_rescale(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op
                             const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_d0,
                             const mkhe_swk* const* rlk_v0, const mkhe_swk* crs_u, mkhe_ct* out);
 
+/* K products under ONE relinearisation tail (no reference counterpart: the reference relinearises every product, cnn/cnn.go:16-31,51-61):
+ * out = [Rescale] sum_k op0[k] * op1[k].  Step F2 of MulAndRelinHoisted (keyswitch_hoisted.go:156-178) is linear in t_i = <h(c0_i), y>_P up to gadget
+ * noise, so per pair k the engine computes x^k, y^k, the tensor terms, step E (out_j += <h(c1_j^k), x^k>_P) and t_i += <h(c0_i^k), y^k>_P, and then
+ * ONCE per party i of op0: out_0 += <h(t_i), v_i>_P, out_i += <h(t_i), u>_P.  Every sum is a sum of separately ModDown'd products, canonical mod q_l:
+ * K = 1 is mkhe_mul_and_relin bit for bit, and the result does not depend on the order of the pairs.
+ *   1 <= K <= 16; every op0[k] carries the ids of op0[0], every op1[k] those of op1[0]; out carries the union and is distinct from every operand;
+ *   level = limbs(out) - 1 + rescale (rescale: 0 or 1): every operand has at least level + 1 limbs, of which the first level + 1 are read; with
+ *   rescale = 1 out receives what mkhe_rescale(.., 1) of the rescale = 0 result would, bit for bit;
+ *   hoist0: flat [k * |ids0| + a], hoist1: flat [k * |ids1| + a], either NULL (the engine hoists that side itself); keys aligned as for
+ *   mkhe_mul_and_relin.  CKKS / mkrlwe contexts that own every modulus; may allocate from the pools (not for capture). */
+int  mkhe_mul_relin_sum(mkhe_ctx* ctx, int K, const mkhe_ct* const* op0, const mkhe_ct* const* op1,
+                        const mkhe_swk* const* hoist0, const mkhe_swk* const* hoist1,
+                        const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_d0, const mkhe_swk* const* rlk_v0,
+                        const mkhe_swk* crs_u, int rescale, mkhe_ct* out);
+
 /* ---- the same MulAndRelinHoisted split in phases for party-sharded multi-GPU evaluation
  *      (the reference is single-process).  Each rank passes sub-ciphertexts holding c_0
  *      and the party components it owns; x_part / y_part receive the rank's canonical partial sums

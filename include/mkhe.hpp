@@ -421,6 +421,25 @@ class Evaluator {
     }
     // mkhe_ct_lincomb as it is (no reference counterpart): the caller encodes dev_consts [cts.size() + 1][2][ctOut.Level() + 1 + nb_rescale] and sets ctOut.Scale
     void LinComb(const std::vector<const mkhe_ct*>& cts, const void* dev_consts, int nb_rescale, Ciphertext& ctOut) { check(mkhe_ct_lincomb(params.ctx, (int)cts.size(), cts.data(), dev_consts, nb_rescale, ctOut.h)); }
+    // mkhe_mul_relin_sum as it is (no reference counterpart): ctOut = [Rescale] sum_k ops0[k] * ops1[k] under one relinearisation tail.  Every ops0[k]
+    // carries the ids of ops0[0], every ops1[k] those of ops1[0]; hoisted0 / hoisted1: one form per pair, or empty (the engine hoists that side); the
+    // caller sets ctOut.Scale
+    void MulRelinSum(const std::vector<const Ciphertext*>& ops0, const std::vector<const Ciphertext*>& ops1, const std::vector<const mkrlwe::HoistedCiphertext*>& hoisted0,
+                     const std::vector<const mkrlwe::HoistedCiphertext*>& hoisted1, mkrlwe::RelinearizationKeySet& rlkSet, bool rescale, Ciphertext& ctOut) {
+        if (ops0.empty() || ops0.size() != ops1.size()) throw Error("MulRelinSum: as many first operands as second ones, at least one pair");
+        if ((!hoisted0.empty() && hoisted0.size() != ops0.size()) || (!hoisted1.empty() && hoisted1.size() != ops1.size())) throw Error("MulRelinSum: one hoisted form per pair");
+        if (!params.CRS.count(-1)) throw Error("mkhe: CRS[-1] (u) has not been uploaded");
+        std::vector<const mkhe_ct*> a, b;
+        std::vector<const mkhe_swk*> d0, v0, b1, h0, h1;
+        for (auto* c : ops0) a.push_back(c->h);
+        for (auto* c : ops1) b.push_back(c->h);
+        for (auto& i : ops0[0]->ids) { auto& k = rlkSet.GetRelinearizationKey(i); d0.push_back(k.Value[1]->h); v0.push_back(k.Value[2]->h); }
+        for (auto& i : ops1[0]->ids) b1.push_back(rlkSet.GetRelinearizationKey(i).Value[0]->h);
+        for (auto* h : hoisted0) for (auto& i : ops0[0]->ids) h0.push_back(h->Value.at(i)->h);
+        for (auto* h : hoisted1) for (auto& i : ops1[0]->ids) h1.push_back(h->Value.at(i)->h);
+        check(mkhe_mul_relin_sum(params.ctx, (int)a.size(), a.data(), b.data(), hoisted0.empty() ? nullptr : h0.data(), hoisted1.empty() ? nullptr : h1.data(),
+                                 b1.data(), d0.data(), v0.data(), params.CRS[-1]->h, rescale ? 1 : 0, ctOut.h));
+    }
     // mkhe_ptxt_prepare / mkhe_ct_ptxt_dot as they are (no reference counterpart): the prepared plaintexts lie compactly in (giant, baby) order; the caller
     // sets the scales of the outputs
     void PtxtPrepare(int limbs, int count, const void* dev_pt, void* dev_ptntt) { check(mkhe_ptxt_prepare(params.ctx, limbs, count, dev_pt, dev_ptntt)); }

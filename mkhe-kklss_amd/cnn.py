@@ -79,8 +79,30 @@ def _lane_products(eval, rlkSet, rtkSet, ct, ctHoisted, rots, ctOther, ctOtherHo
     return prods.cts
 
 
-def Convolution(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, ctKernels, ctKernelsHoisted, forks=None):
-    """cnn.go:10-39: kernels pre-rotated by 0, 1, 14, 15; the image is hoisted once and reused by the three rotations"""
+def _sum_products(eval, rlkSet, rtkSet, ct, ctHoisted, rots, ctOther, ctOtherHoisted, forks):
+    """sum_i MulRelin(Rot_rots[i](ct), ctOther[i]) as ONE eval.MulRelinSumNew (sum_products=True; no reference counterpart: cnn.go:16-31,51-61 relinearise
+    every summand): rotations and hoisted forms as the reference computes them, one relinearisation tail for the layer"""
+    if forks or not hasattr(eval, "MulRelinSumNew"):
+        from ._abi import MkheError
+        raise MkheError("cnn: sum_products takes the plain Evaluator on one context (no forks, no BatchEvaluator)")
+    ops, hs = [], []
+    for r in rots:
+        if r == 0:
+            ops.append(ct); hs.append(ctHoisted)
+        else:
+            temp = eval.RotateHoistedNew(ct, r, ctHoisted, rtkSet)
+            ops.append(temp); hs.append(eval.HoistedForm(temp))
+    return eval.MulRelinSumNew(ops, list(ctOther), rlkSet, hs, list(ctOtherHoisted))
+
+
+def Convolution(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, ctKernels, ctKernelsHoisted, forks=None, sum_products=False):
+    """cnn.go:10-39: kernels pre-rotated by 0, 1, 14, 15; the image is hoisted once and reused by the three rotations.
+    sum_products (plain Evaluator only, not the default): the four products under one relinearisation tail (_sum_products)"""
+    if sum_products:
+        convOut = _sum_products(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, (0, 1, 14, 15), ctKernels, ctKernelsHoisted, forks)
+        for rot in (2048, 1024):
+            convOut = _rot_add(eval, convOut, rot, rtkSet)
+        return convOut
     if not forks and hasattr(eval, "Lanes"):
         prods = _lane_products(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, (0, 1, 14, 15), ctKernels, ctKernelsHoisted)
         convOut = _sum(eval, prods)
@@ -104,8 +126,14 @@ def Convolution(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, ctKernels, ctKern
     return convOut
 
 
-def FC1Layer(eval, rlkSet, rtkSet, ctVec, ctVecHoisted, ctMat, ctMatHoisted, ctBias, forks=None):
-    """cnn.go:41-71: diagonal-packed 64 x 1024 matrix in 8 ciphertexts, then a log-sum over each 128-slot block"""
+def FC1Layer(eval, rlkSet, rtkSet, ctVec, ctVecHoisted, ctMat, ctMatHoisted, ctBias, forks=None, sum_products=False):
+    """cnn.go:41-71: diagonal-packed 64 x 1024 matrix in 8 ciphertexts, then a log-sum over each 128-slot block.
+    sum_products (plain Evaluator only, not the default): the eight products under one relinearisation tail (_sum_products)"""
+    if sum_products:
+        fc1Out = _sum_products(eval, rlkSet, rtkSet, ctVec, ctVecHoisted, [i * 128 for i in range(len(ctMat))], ctMat, ctMatHoisted, forks)
+        for i in range(7):                                        # log2(128)
+            fc1Out = _rot_add(eval, fc1Out, 1 << i, rtkSet)
+        return eval.AddNew(fc1Out, ctBias)
     def chain(ev, i):
         temp = ev.RotateHoistedNew(ctVec, i * 128, ctVecHoisted, rtkSet)
         tempHoisted = ev.HoistedForm(temp)
@@ -135,17 +163,19 @@ def FC2Layer(eval, rlkSet, rtkSet, ctVec, ctMat, ctBias, ptMask, ptMaskScale):
     return eval.AddNew(fc2Out, ctBias)
 
 
-def Inference(eval, rlkSet, rtkSet, ctImage, ctKernels, ctFC1, ctFC2, ctB1, ctB2, ptMask, ptMaskScale, hoisted=None, forks=None):
+def Inference(eval, rlkSet, rtkSet, ctImage, ctKernels, ctFC1, ctFC2, ctB1, ctB2, ptMask, ptMaskScale, hoisted=None, forks=None, sum_products=False):
     """the evaluation part of TestCNN / BenchmarkCNN (cnn_test.go:153-165): convolution, square, FC1, square, FC2.
-    hoisted: optional (ctImageHoisted, ctKernelsHoisted, ctFC1Hoisted) precomputed by the caller, as the reference does."""
+    hoisted: optional (ctImageHoisted, ctKernelsHoisted, ctFC1Hoisted) precomputed by the caller, as the reference does.
+    sum_products: Convolution and FC1Layer relinearise the SUM of their products (12 of the 15 MulRelins of an inference share two tails); a different
+    ciphertext of the same logits.  Off by default: the default equals the reference bit for bit."""
     if hoisted is None:
         hoisted = (eval.HoistedForm(ctImage), [eval.HoistedForm(c) for c in ctKernels], [eval.HoistedForm(c) for c in ctFC1])
     ctImageHoisted, ctKernelsHoisted, ctFC1Hoisted = hoisted
-    convOut = Convolution(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, ctKernels, ctKernelsHoisted, forks)
+    convOut = Convolution(eval, rlkSet, rtkSet, ctImage, ctImageHoisted, ctKernels, ctKernelsHoisted, forks, sum_products)
     convOutHoisted = eval.HoistedForm(convOut)
     square1Out = eval.MulRelinHoistedNew(convOut, convOut, convOutHoisted, convOutHoisted, rlkSet)
     square1OutHoisted = eval.HoistedForm(square1Out)
-    fc1Out = FC1Layer(eval, rlkSet, rtkSet, square1Out, square1OutHoisted, ctFC1, ctFC1Hoisted, ctB1, forks)
+    fc1Out = FC1Layer(eval, rlkSet, rtkSet, square1Out, square1OutHoisted, ctFC1, ctFC1Hoisted, ctB1, forks, sum_products)
     fc1OutHoisted = eval.HoistedForm(fc1Out)
     square2Out = eval.MulRelinHoistedNew(fc1Out, fc1Out, fc1OutHoisted, fc1OutHoisted, rlkSet)
     return FC2Layer(eval, rlkSet, rtkSet, square2Out, ctFC2, ctB2, ptMask, ptMaskScale)

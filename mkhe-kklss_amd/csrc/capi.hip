@@ -567,6 +567,47 @@ int mkhe_mul_relin_batch(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* op0, c
         need(ctx)->mul_relin_batch(a, b, h0, h1, b1.data(), d0.data(), v0.data(), crs_u->s, rescale != 0, o);
     })
 }
+// (a function of its own: the commas of its declarations would split the argument of MKHE_TRY)
+static void mul_relin_sum_body(mkhe_ctx* ctx, int K, const mkhe_ct* const* op0, const mkhe_ct* const* op1,
+                               const mkhe_swk* const* hoist0, const mkhe_swk* const* hoist1,
+                               const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_d0, const mkhe_swk* const* rlk_v0,
+                               const mkhe_swk* crs_u, int rescale, mkhe_ct* out) {
+    const std::string what = "mkhe_mul_relin_sum";
+    try {
+        if (!ctx) throw Error(what + ": null context");
+        if (K < 1 || K > TSUM_MAX_K) throw Error(what + ": takes 1 to " + std::to_string(TSUM_MAX_K) + " pairs");      // (before the lists are read)
+        if (!out || !crs_u || !rlk_b1 || !rlk_d0 || !rlk_v0) throw Error(what + ": null argument");
+        if (rescale != 0 && rescale != 1) throw Error(what + ": rescale is 0 or 1");
+        auto a = ct_list(ctx, op0, K, what.c_str());
+        auto b = ct_list(ctx, op1, K, what.c_str());
+        const int n0 = a[0]->n;           // (that every pair carries these ids, and that out is none of the operands, is the engine's check)
+        const int n1 = b[0]->n;
+        auto keys = [&](const mkhe_swk* const* v, size_t n, const char* name) {
+            std::vector<const Swk*> r(n);
+            for (size_t i = 0; i < n; ++i) { if (!v[i]) throw Error(what + ": null handle in " + name); mark(ctx, v[i]); r[i] = &v[i]->s; }
+            return r;
+        };
+        std::vector<const Swk*> h0;
+        std::vector<const Swk*> h1;
+        if (hoist0) h0 = keys(hoist0, (size_t)K * n0, "hoist0");
+        if (hoist1) h1 = keys(hoist1, (size_t)K * n1, "hoist1");
+        auto b1 = keys(rlk_b1, n1, "rlk_b1");
+        auto d0 = keys(rlk_d0, n0, "rlk_d0");
+        auto v0 = keys(rlk_v0, n0, "rlk_v0");
+        need(ctx)->mul_relin_sum(a, b, h0, h1, b1.data(), d0.data(), v0.data(), crs_u->s, rescale != 0, out->c);
+    } catch (const std::exception& e) {
+        // every message of this entry point starts with its name, whichever layer raised it
+        const std::string m = e.what();
+        if (m.compare(0, what.size(), what) == 0) throw;
+        throw Error(what + ": " + m);
+    }
+}
+int mkhe_mul_relin_sum(mkhe_ctx* ctx, int K, const mkhe_ct* const* op0, const mkhe_ct* const* op1,
+                       const mkhe_swk* const* hoist0, const mkhe_swk* const* hoist1,
+                       const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_d0, const mkhe_swk* const* rlk_v0,
+                       const mkhe_swk* crs_u, int rescale, mkhe_ct* out) {
+    MKHE_TRY({ mark(ctx, crs_u, out); mul_relin_sum_body(ctx, K, op0, op1, hoist0, hoist1, rlk_b1, rlk_d0, rlk_v0, crs_u, rescale, out); })
+}
 int mkhe_ct_mul_ptxt_batch(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, const void* dev_pt, int nb_rescale, mkhe_ct* const* out) {
     MKHE_TRY({
         if (nbatch < 1 || !dev_pt) throw Error("mkhe_ct_mul_ptxt_batch: bad argument");

@@ -155,6 +155,13 @@ class Context {
     void mr_finish_tail(const Ct& op0, const Ct& op1, const u64* x, const Swk* const* rlk_v0, const Swk& crs_u, Ct& out);
     void mr_finish(const Ct& op0, const Ct& op1, const u64* x, const u64* y, const Swk* const* rlk_v0,
                    const Swk& crs_u, Ct& out);
+    void mr_f2_hoist(bool e_free);     // F2: h(t_i) of plan_.f2_tbuf for the tail batch; e_free: that batch computes no step-E product itself
+    // out = [Rescale] sum_k op0[k] * op1[k] under ONE relinearisation tail (engine_mulrelin_sum.hip; no reference counterpart): per pair the tensor
+    // terms (one launch for all pairs), x^k, y^k, step E into out and t_i += <h(c0_i^k), y^k>_P; then step F2 once on the summed t_i.  Hoisted forms
+    // flat [k * n + a] or empty (the engine hoists that side); 1 <= K <= TSUM_MAX_K; CKKS contexts that own every modulus
+    void mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector<const Ct*>& op1, const std::vector<const Swk*>& hoist0,
+                       const std::vector<const Swk*>& hoist1, const Swk* const* rlk_b1, const Swk* const* rlk_d0, const Swk* const* rlk_v0,
+                       const Swk& crs_u, bool rescale_out, Ct& out);
     void fold(u64* buf, bool qp_shaped, int level, int npolys, long poly_stride, bool mform);
     // the reduce-scatter half of a mesh exchange of x / y (dist.py): limbs [first_limb, first_limb + nlimbs) of a switching-key buffer, summed over
     // npieces pieces, folded and MForm'ed into dst (limb i of the range at dst + i * N)
@@ -456,6 +463,7 @@ class Context {
         bool f2_fused = false;               // N = 2^15: no Decompose launch for the t_i at all -- the tail batch's product kernel is ntt16_f2_kernel
         const u64* f2_tbuf = nullptr;
         bool e_done = false;                 // ... and so was step E: its products sit in the c1 slots 2 n0 .. 2 n0 + n1 - 1 of the scratch, for the tail batch
+        bool e_summed = false;               // mul_relin_sum: step E of every pair (with the tensor terms of those slots) is in `out` already: the tail runs F2 only
     } plan_;
     // bfv_mr_partial -> bfv_mr_finish
     struct BfvPlan {

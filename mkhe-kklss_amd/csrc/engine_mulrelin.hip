@@ -232,16 +232,22 @@ void Context::mr_finish_head(const Ct& op0, const Ct& op1, const u64* y, Ct& out
     p.e_done = fuse.e_slot >= 0;
     // F2: h(t_i) ; out_0 += <h(t_i), v_i>_P ; out_i += <h(t_i), u>_P
     p.f2_tbuf = tbuf;
-    if (!p.f2_fused) {
-        std::vector<const u64*> dsrc; std::vector<u64*> ddst;
-        for (int a = 0; a < n0; ++a) { dsrc.push_back(tbuf + (size_t)a * PO); ddst.push_back(hoist_slot(2, a).d); }
-        // (the digits of the t_i are read once, by the two F2 products of their party: a small launch of the small ring leaves them after the cross
-        // stages and the tail's product kernel finishes the transform -- when step E is not an item that reads other digits in the same launch)
-        p.f2_staged = n0 > 0 && (p.e_done || p.n1 == 0) && ext_fused_ok(level, n0);
-        if (n0) decompose_batch(level, dsrc, ddst, true, p.f2_staged);
-    }
+    mr_f2_hoist(p.e_done || p.n1 == 0);
     p.head_done = true;
     MKHE_HIP(hipGetLastError());
+}
+void Context::mr_f2_hoist(bool e_free) {
+    MrPlan& p = plan_;
+    const int level = p.level, n0 = p.n0;
+    const size_t PO = (size_t)p.L * N;
+    if (!p.f2_fused) {
+        std::vector<const u64*> dsrc; std::vector<u64*> ddst;
+        for (int a = 0; a < n0; ++a) { dsrc.push_back(p.f2_tbuf + (size_t)a * PO); ddst.push_back(hoist_slot(2, a).d); }
+        // (the digits of the t_i are read once, by the two F2 products of their party: a small launch of the small ring leaves them after the cross
+        // stages and the tail's product kernel finishes the transform -- when step E is not an item that reads other digits in the same launch)
+        p.f2_staged = n0 > 0 && e_free && ext_fused_ok(level, n0);
+        if (n0) decompose_batch(level, dsrc, ddst, true, p.f2_staged);
+    }
 }
 void Context::mr_finish_tail(const Ct& op0, const Ct& op1, const u64* x, const Swk* const* rlk_v0, const Swk& crs_u, Ct& out) {
     MrPlan& p = plan_;
@@ -261,7 +267,7 @@ void Context::mr_finish_tail(const Ct& op0, const Ct& op1, const u64* x, const S
         items.push_back(ExtItem{ht, crs_u.d, out.d + (size_t)(1 + p.slot0[a]) * PO, true});
         if (p.f2_fused) { items.back().f2_party = a; items.back().f2_key = 1; }
     }
-    for (int a = 0; a < n1; ++a) { items.push_back(ExtItem{p.h1[a], x, out.d + (size_t)(1 + p.slot1[a]) * PO, true}); items.back().pre = p.e_done; }
+    for (int a = 0; a < n1 && !p.e_summed; ++a) { items.push_back(ExtItem{p.h1[a], x, out.d + (size_t)(1 + p.slot1[a]) * PO, true}); items.back().pre = p.e_done; }
     ExtFuse fuse;
     if (p.f2_fused) for (int a = 0; a < n0; ++a) fuse.f2_src.push_back(p.f2_tbuf + (size_t)a * PO);
     if (p.x_pending) { join_side(2); p.x_pending = false; }
@@ -272,9 +278,11 @@ void Context::mr_finish_tail(const Ct& op0, const Ct& op1, const u64* x, const S
         for (auto& it : items) {
             if (std::find(seen.begin(), seen.end(), it.dst) != seen.end()) continue;
             seen.push_back(it.dst);
+            // (mul_relin_sum: the slots of op1's parties hold their tensor term and the E products of every pair already: F2 adds onto them)
+            if (p.e_summed && std::find(p.slot1.begin(), p.slot1.end(), (int)((it.dst - out.d) / (long)PO) - 1) != p.slot1.end()) continue;
             it.accumulate = false; it.qadd = p.tens + (it.dst - out.d);
         }
-        if ((int)seen.size() != 1 + out.n) throw Error("mkhe: internal: an output slot without an external product");
+        if (!p.e_summed && (int)seen.size() != 1 + out.n) throw Error("mkhe: internal: an output slot without an external product");
         join_side(1);                  // the tensor chain, before the inverse NTT that sums it in
         ext_batch(level, items, -1, 0, 0, fuse);
     } else

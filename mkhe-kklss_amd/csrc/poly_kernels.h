@@ -243,6 +243,25 @@ struct TensorArgs {
 };
 void launch_tensor(const TensorArgs& a, hipStream_t st);
 
+// The tensor terms of K operand pairs summed (Context::mul_relin_sum; no reference counterpart), NTT domain, one launch:
+//   out_0 = sum_k a0^k b0^k ;  out_o = sum_k [ b0^k a_o^k (o in ids0) + a0^k b_o^k (o in ids1) ]
+// in = the forward transforms of the operands, canonical, pair k at in + k * pair_words, polynomial p of a pair ([L][N]) at + p * L * N.  Output o adds
+// up to two products per pair: polynomials t0 x t1 and t2 x t3, term[o] = t0 | t1 << 8 | t2 << 16 | t3 << 24 (t2 = 255: no second product; one 32-bit word per
+// output on purpose, see ModDownMergedArgs).  Each output word is ONE
+// 128-bit accumulator of at most 2 K <= 32 products and one reduction; stored canonical, times scale[l] (Montgomery constants, NULL: none) -- with
+// scale = MForm(P mod q_l) the form ExtItem::qadd takes (engine.h).  out must not overlap in.
+constexpr int TSUM_MAX_K = 16;
+struct TensorSumArgs {
+    const u64* in;
+    u64* out;                  // [1 + nout][L][N]
+    const Mod* mods;
+    const u64* scale;
+    long pair_words;
+    unsigned int term[33];
+    int K, nout, L, N;
+};
+void launch_tensor_sum(const TensorSumArgs& a, hipStream_t st);
+
 // Generic fast basis conversion between two RNS bases S (ns limbs) and T (nt limbs) -- the reference's
 // modUpExact (mkrlwe/basis_extension.go:337-357, reconstructRNS :537-585, multSum :587-646) restated
 // literally per coefficient, with the optional ModDown tail (:192-232 / :292-334):

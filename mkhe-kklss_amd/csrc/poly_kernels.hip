@@ -1021,6 +1021,59 @@ void launch_tensor(const TensorArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(tensor_kernel, dim3(bx, by, a.nbatch > 1 ? a.nbatch : 1), dim3(PW_THREADS), 0, st, a);
 }
 
+// The tensor terms of K pairs, summed (TensorSumArgs).  One thread per coefficient j of one output polynomial o = blockIdx.y, lanes on consecutive j
+// (coalesced 8-byte streams); the limb, and with it the modulus, the scale and the four polynomial offsets of the output, are wave-uniform, limbs dealt
+// to gridDim.z groups as in ct_lincomb_kernel.  The loads of CH pairs are issued together (the last chunk repeats its last pair, whose products are
+// skipped).  c0_0 and c1_0 of a pair are read by every output that uses them -- from the caches: the workgroups of one (block of j, limb) run side by side.
+// Reduction: at most 2 K <= 32 products of canonical residues below q < 2^60 in ONE 128-bit accumulator: what redc128 accepts.  redc128 leaves
+// sum * 2^-64; the Montgomery product with R^2 (times the scale, itself in Montgomery form) returns the sum (times the scale), canonical.
+static_assert(TSUM_MAX_K <= 16, "tensor_sum_kernel: 2 * TSUM_MAX_K products must stay within the 32 that redc128 accepts for q < 2^60");
+typedef const __attribute__((address_space(4))) TensorSumArgs* tsum_kargs;
+template <int CH>
+__global__ void __launch_bounds__(PW_THREADS) tensor_sum_kernel(TensorSumArgs a) {
+    tsum_kargs ka = (tsum_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    const int j = blockIdx.x * PW_THREADS + threadIdx.x, o = blockIdx.y;
+    if (j >= a.N) return;
+    const long PO = (long)a.L * a.N;
+    const unsigned int t = ka->term[o];
+    const bool two = ((t >> 16) & 255) != 255;
+    const long x1 = (long)(t & 255) * PO, y1 = (long)((t >> 8) & 255) * PO, x2 = two ? (long)((t >> 16) & 255) * PO : x1, y2 = two ? (long)(t >> 24) * PO : y1;
+    for (int l = blockIdx.z; l < a.L; l += gridDim.z) {
+        const Mod md = load_mod((sc_mod)a.mods + l);
+        const long off = (long)l * a.N + j;
+        u64 hi = 0, lo = 0;
+        for (int k = 0; k < a.K; k += CH) {
+            u64 v[CH][4];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const u64* p = a.in + (long)(k + u < a.K ? k + u : a.K - 1) * a.pair_words + off;
+                v[u][0] = p[x1]; v[u][1] = p[y1];
+                if (two) { v[u][2] = p[x2]; v[u][3] = p[y2]; }
+            }
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+                if (k + u < a.K) {
+                    mac128(v[u][0], v[u][1], hi, lo);
+                    if (two) mac128(v[u][2], v[u][3], hi, lo);
+                }
+        }
+        u64 w = md.r2;
+        if (a.scale) w = mont_mul(((sc_u64)a.scale)[l], md.r2, md.q, md.ninv32);
+        a.out[(long)o * PO + off] = mont_mul(redc128(hi, lo, md), w, md.q, md.ninv32);
+    }
+}
+void launch_tensor_sum(const TensorSumArgs& a, hipStream_t st) {
+    if (a.K < 1 || a.K > TSUM_MAX_K || a.nout < 0 || a.nout > 32 || a.L < 1) throw std::runtime_error("mkhe: launch_tensor_sum: bad shape");
+    const int bx = (a.N + PW_THREADS - 1) / PW_THREADS, npolys = 1 + a.nout;
+    // limb groups as in launch_ct_lincomb: until every SIMD of the chip has four waves, at most one group per limb
+    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * npolys;
+    const int groups = (int)std::min<long>(a.L, (fill + threads - 1) / threads);
+    const dim3 grid(bx, npolys, groups), blk(PW_THREADS);
+    if (a.K > 2) hipLaunchKernelGGL(tensor_sum_kernel<4>, grid, blk, 0, st, a);
+    else if (a.K == 2) hipLaunchKernelGGL(tensor_sum_kernel<2>, grid, blk, 0, st, a);
+    else hipLaunchKernelGGL(tensor_sum_kernel<1>, grid, blk, 0, st, a);
+}
+
 // ------------------------------------------------------------------ add
 __global__ void __launch_bounds__(PW_THREADS) add_kernel(u64* dst, const u64* x, const u64* y, const Mod* mods, int N) {
     const int l = blockIdx.y;

@@ -214,6 +214,34 @@ class Evaluator:
         check(lib().mkhe_rescale(self.params.ctx, ctOut.h, nb, res.h))
         return res
 
+    # ---- sum_k MulRelin(ops0[k], ops1[k]) under ONE relinearisation tail (no reference counterpart: cnn.Convolution / FC1Layer, cnn/cnn.go:16-31,51-61,
+    # relinearise every summand; mkhe_mul_relin_sum).  A different ciphertext of the same sum: one gadget noise of step F2 instead of K
+    def MulRelinSumNew(self, ops0, ops1, rlkSet, hoisted0=None, hoisted1=None):
+        ops0, ops1 = list(ops0), list(ops1)
+        if len(ops0) != len(ops1) or not ops0:
+            raise MkheError("MulRelinSumNew: as many first operands as second ones, at least one pair")
+        if len(ops0) > MULRELIN_SUM_MAX:
+            raise MkheError("MulRelinSumNew: at most %d pairs per call" % MULRELIN_SUM_MAX)
+        prod_scale = ops0[0].ScalingFactor() * ops1[0].ScalingFactor()
+        for a, b in zip(ops0, ops1):
+            if a.ScalingFactor() * b.ScalingFactor() != prod_scale:
+                raise MkheError("MulRelinSumNew: all products must have one scale")
+        level = min(min(c.Level() for c in ops0), min(c.Level() for c in ops1))
+        ids = ops0[0].IDSet() | ops1[0].IDSet()
+        nb1, scale1 = self._nb_rescales(level, prod_scale, self.params.Scale())          # as MulRelinHoistedNew, fuse_rescale included
+        if nb1 == 1 and level >= 1 and self.fuse_rescale:
+            res = NewCiphertext(self.params, ids, level - 1, scale1, zero=False)
+            self.ksw.MulRelinSum(ops0, ops1, hoisted0, hoisted1, rlkSet, res, rescaled=True)
+            return res
+        ctOut = NewCiphertext(self.params, ids, level, prod_scale, zero=False)
+        self.ksw.MulRelinSum(ops0, ops1, hoisted0, hoisted1, rlkSet, ctOut)
+        nb, scale = self.nbRescales(ctOut, self.params.Scale())
+        if nb == 0 or ctOut.Level() == 0:
+            return ctOut
+        res = NewCiphertext(self.params, ctOut.IDSet(), ctOut.Level() - nb, scale, zero=False)
+        check(lib().mkhe_rescale(self.params.ctx, ctOut.h, nb, res.h))
+        return res
+
     def _norm_rot(self, rotidx):
         n2 = self.params.N() // 2
         return rotidx % n2
@@ -380,6 +408,7 @@ class Evaluator:
         return linear_transform(self, ct, lt, rkSet, fused)
 
 
+MULRELIN_SUM_MAX = 16     # pairs per mkhe_mul_relin_sum call (csrc/poly_kernels.h, TSUM_MAX_K)
 LINCOMB_MAX = 16          # ciphertexts per mkhe_ct_lincomb call (csrc/poly_kernels.h, CTLIN_MAX)
 PolyEvalPlan = collections.namedtuple("PolyEvalPlan", "degree m g products depth")
 

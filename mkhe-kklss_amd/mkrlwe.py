@@ -481,6 +481,28 @@ class KeySwitcher:
         check(fn(self.ctx, op0.h, op1.h, a_h0, a_h1, handle_array(b1), handle_array(d0),
                  handle_array(v0), params.CRS[-1].h, ctOut.h))
 
+    # -- K products under one relinearisation tail (no reference counterpart; mkhe_mul_relin_sum, include/mkhe.h)
+    def MulRelinSum(self, ops0, ops1, hoisted0, hoisted1, rlkSet, ctOut, rescaled=False):
+        """ctOut = [Rescale] sum_k ops0[k] * ops1[k]; every ops0[k] carries the ids of ops0[0], every ops1[k] those of ops1[0];
+        hoisted0 / hoisted1: one HoistedCiphertext per pair, or None (the engine hoists that side)"""
+        if len(ops0) != len(ops1) or not ops0:
+            raise MkheError("MulRelinSum: as many first operands as second ones, at least one pair")
+        params = self.Parameters
+        if -1 not in params.CRS:
+            raise MkheError("mkhe: CRS[-1] (u) has not been uploaded")
+        for side, hs in ((ops0, hoisted0), (ops1, hoisted1)):
+            if hs is not None and len(hs) != len(side):
+                raise MkheError("MulRelinSum: one hoisted form per pair")
+        ids0, ids1 = ops0[0].ids, ops1[0].ids
+        d0 = [rlkSet.GetRelinearizationKey(i).Value[1].h for i in ids0]
+        v0 = [rlkSet.GetRelinearizationKey(i).Value[2].h for i in ids0]
+        b1 = [rlkSet.GetRelinearizationKey(i).Value[0].h for i in ids1]
+        h0 = [h.Value[i].h for h in hoisted0 for i in ids0] if hoisted0 is not None else None
+        h1 = [h.Value[i].h for h in hoisted1 for i in ids1] if hoisted1 is not None else None
+        check(lib().mkhe_mul_relin_sum(self.ctx, len(ops0), handle_array([c.h for c in ops0]), handle_array([c.h for c in ops1]),
+                                       handle_array(h0), handle_array(h1), handle_array(b1), handle_array(d0), handle_array(v0),
+                                       params.CRS[-1].h, 1 if rescaled else 0, ctOut.h))
+
     def _rotidx(self, rotidx):
         n2 = self.Parameters.N() // 2
         while rotidx < 0:
