@@ -421,14 +421,53 @@ int  mkhe_crs_expand(mkhe_ctx* ctx, uint64_t seed, int32_t idx, mkhe_swk* out);
 /* ==== public-key encryption and decryption ==========================================================
  * mkrlwe/encryptor.go:55-118 (ciphertexts are coefficient domain: the branch :95-112) and mkrlwe/decryptor.go:26-66, which
  * mkckks/{encryptor,decryptor}.go and mkbfv/{encryptor,decryptor}.go wrap; ring Q, on mkhe_ctx_create_bfv contexts too.
- * As in key generation the small-norm samples come from the caller (host int32) and are wiped from the device
- * scratch behind their last use.  Public keys are the device buffers of mkhe_keygen_public_key, secret keys those of
+ * As in key generation the small-norm samples come from the caller (host int32) -- or, with mkhe_encrypt_seeded, from a ChaCha20
+ * keystream expanded on the device -- and are wiped from the device scratch behind their last use.  Public keys are the device buffers of mkhe_keygen_public_key, secret keys those of
  * mkhe_keygen_secret; raw device buffers must be 16-byte aligned (mkhe_buf_alloc's are). */
 /* Encrypt encryptor.go:55-118 for `count` plaintexts under one public key as one launch set: dev_pt = uint64[count][level+1][N],
  * coefficient domain or (pt_is_ntt, :107-109) NTT domain; samples = int32[count][3][N], per plaintext u (ternary), e0, e1
  * (Gaussian) in this order; out[b] = a ciphertext over exactly one party with level+1 limbs: c0 = u*pk0 + e0 + pt, c1 = u*pk1 + e1 */
 int  mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt,
                   const int32_t* samples, mkhe_ct* const* out);
+/* ---- device-side sampling: u, e0, e1 drawn on the device from a ChaCha20 key ---------------------------------------
+ * Opt-in: mkhe_encrypt above is unchanged, and key generation keeps taking host samples.  The stream is fully specified, so the
+ * device path is bit-exact against a model (tests/device_sampler_model.py).
+ *
+ * Keystream.  The ChaCha20 block function of RFC 8439 section 2.3 (20 rounds, 32-bit words, feed-forward addition) on the state
+ *   words 0-3  the constants 0x61707865 0x3320646e 0x79622d32 0x6b206574
+ *   words 4-11 key[0..7]
+ *   word 12    the block index c
+ *   word 13    nonce & 0xffffffff
+ *   word 14    nonce >> 32
+ *   word 15    stream
+ * One stream is one polynomial of N coefficients.  Coefficient i uses block c = i / 8 and there the output words w[2 (i % 8)] (low)
+ * and w[2 (i % 8) + 1] (high): the 64-bit value r = lo + 2^32 hi.  Every coefficient consumes 64 bits whatever its kind.  (One GPU
+ * thread computes one block: 8 consecutive coefficients, 32 contiguous bytes of int32.)
+ *
+ * Kinds.
+ *   kind 0  ternary with P(0) = 1/2 (the u of Encrypt): 0 if r & 1, otherwise +1 if r & 2, else -1
+ *   kind 1  table sampling: cdt[0 .. ncdt) are strictly increasing uint64 thresholds, ncdt even, 2 <= ncdt <= 64; the value is
+ *           #{t : r >= cdt[t]} - ncdt/2.  The engine does not know sigma: the distribution is the table (mkrlwe.small_cdt /
+ *           mkhe::mkrlwe::small_cdt build the rounded Gaussian truncated at 6 sigma).  Every threshold is visited for every
+ *           coefficient with a full 64-bit unsigned comparison: no early exit, no sample-dependent branch.
+ *
+ * Rules.
+ *   - A (key, nonce) pair must NEVER serve two calls: the second call would repeat the samples of the first.  The caller keeps a counter.
+ *   - Both calls are refused between mkhe_capture_begin and mkhe_capture_end: a replay of the graph would repeat the keystream.
+ *   - Both calls are refused on a context that owns a subset of the moduli (mkhe_ctx_set_owned).
+ *   - The key travels in the kernel arguments of one launch.  The engine does not write it to device memory it owns, does not keep it in
+ *     the context and does not quote it in an error message.
+ *   - Every error message starts with the function's name; a refused call has enqueued nothing and leaves the context usable. */
+/* dev_out = int32[count][N] (16-byte aligned device buffer); polynomial p is stream first_stream + p; first_stream + count <= 2^32;
+ * 1 <= count <= 196605.  cdt / ncdt are read for kind 1 only (kind 0: NULL / 0).  A diagnostic and test entry point: the caller owns
+ * (and wipes) what it asked for. */
+int  mkhe_sample_small(mkhe_ctx* ctx, int kind, int count, const uint32_t key[8], uint64_t nonce, uint32_t first_stream,
+                       const uint64_t* cdt, int ncdt, void* dev_out);
+/* mkhe_encrypt with samples[b][j] = stream 3 b + j of (key, nonce): j = 0 is u (kind 0), j = 1, 2 are e0, e1 (kind 1) -- bit for bit.
+ * CKKS, mkrlwe and BFV contexts alike.  Nothing but the arguments crosses the bus, and for count <= 16 the call does not synchronise
+ * with the host (above that the output pointers are staged, as in mkhe_encrypt). */
+int  mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt,
+                         const uint32_t key[8], uint64_t nonce, const uint64_t* cdt, int ncdt, mkhe_ct* const* out);
 /* PartialDecrypt decryptor.go:26-43: slot = 1 .. n names the party (the ciphertext slot of its polynomial); out is over the ids of
  * `in` without that one, at the same level: out[0] = in[0] + c_slot*sk (one ring.Add), the other polynomials are copied */
 int  mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out);

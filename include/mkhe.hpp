@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -329,11 +330,67 @@ struct SecretKeySet {
     }
 };
 
+// The table of mkhe_sample_small / mkhe_encrypt_seeded (kind 1) for round(N(0, sigma)) truncated at +-B, B = int(6 sigma) by default (bound < 0):
+// with Phi(x) = erfc(-x / (sigma sqrt 2)) / 2, lo = Phi(-B - 1/2), hi = Phi(B + 1/2):  T_k = min(2^64 - 1, floor((Phi(k + 1/2) - lo) / (hi - lo) * 2^64)),
+// k = -B .. B - 1 (mkrlwe.small_cdt of the Python mirror, float64 like it).
+inline std::vector<uint64_t> small_cdt(double sigma, int bound = -1) {
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) throw Error("small_cdt: sigma must be finite and positive");
+    const int B = bound < 0 ? (int)(6 * sigma) : bound;
+    if (B < 1 || 2 * B > 64) throw Error("small_cdt: the table has 2 * bound entries and holds 2 .. 64");
+    auto phi = [sigma](double x) { return std::erfc(-x / (sigma * std::sqrt(2.0))) / 2.0; };
+    const double lo = phi(-B - 0.5), hi = phi(B + 0.5);
+    std::vector<uint64_t> t;
+    for (int k = -B; k < B; ++k) {
+        const double x = std::floor((phi(k + 0.5) - lo) / (hi - lo) * 18446744073709551616.0);
+        t.push_back(x >= 18446744073709551616.0 ? ~0ull : (uint64_t)x);
+        if (t.size() > 1 && t[t.size() - 1] <= t[t.size() - 2]) throw Error("small_cdt: the table is not strictly increasing (sigma too small for this bound)");
+    }
+    return t;
+}
+
+// Encryption randomness drawn on the device from a ChaCha20 key (include/mkhe.h, "device-side sampling"): the key is 32 bytes from the caller's
+// CSPRNG, like the samples of KeyGenerator; every engine call consumes one nonce of a 64-bit counter, so that a (key, nonce) pair never
+// serves two calls.  For Encryptor only: key generation keeps its host samples.
+class DeviceSampler {
+  public:
+    explicit DeviceSampler(const uint32_t key[8], double sigma = 3.2) : cdt(small_cdt(sigma)) { std::copy(key, key + 8, key_); }
+    ~DeviceSampler() { volatile uint32_t* k = key_; for (int i = 0; i < 8; ++i) k[i] = 0; }
+    DeviceSampler(const DeviceSampler&) = delete;
+    DeviceSampler& operator=(const DeviceSampler&) = delete;
+    uint64_t NextNonce() {
+        std::lock_guard<std::mutex> g(m_);
+        if (counter_ == ~0ull) throw Error("DeviceSampler: the 64-bit call counter is exhausted -- use a fresh key");
+        return counter_++;
+    }
+    uint64_t Counter() const { return counter_; }
+    const uint32_t* Key() const { return key_; }
+    const std::vector<uint64_t> cdt;
+  private:
+    uint32_t key_[8];
+    uint64_t counter_ = 0;
+    std::mutex m_;
+};
+
 // mkrlwe.Encryptor (encryptor.go:8-52) on the device.  Like the samples of KeyGenerator, u (ternary) and e0, e1 (Gaussian) are
-// arguments: samples = int32[count][3][N] from the caller's CSPRNG.  Plaintexts are device buffers uint64[count][level+1][N].
+// arguments: samples = int32[count][3][N] from the caller's CSPRNG -- or a DeviceSampler, from whose key the engine draws them itself
+// (mkhe_encrypt_seeded).  Plaintexts are device buffers uint64[count][level+1][N].
 class Encryptor {
   public:
     explicit Encryptor(Parameters& p) : params(p) {}
+    void Encrypt(const void* dev_pt, const PublicKey& pk, Ciphertext& ctOut, DeviceSampler& sampler, bool ptIsNTT = false) {
+        if (ctOut.ids.size() != 1 || ctOut.ids[0] != pk.ID) throw Error("Cannot Encrypt: ctOut must be a ciphertext over the id of pk alone");
+        mkhe_ct* out[1] = {ctOut.h};
+        check(mkhe_encrypt_seeded(params.ctx, ctOut.Level(), 1, pk.Value.d, dev_pt, ptIsNTT ? 1 : 0, sampler.Key(), sampler.NextNonce(),
+                                  sampler.cdt.data(), (int)sampler.cdt.size(), out));
+    }
+    std::vector<std::shared_ptr<Ciphertext>> EncryptBatch(int level, int count, const void* dev_pt, const PublicKey& pk, DeviceSampler& sampler, bool ptIsNTT = false) {
+        std::vector<std::shared_ptr<Ciphertext>> cts;
+        std::vector<mkhe_ct*> out;
+        for (int b = 0; b < count; ++b) { cts.push_back(std::make_shared<Ciphertext>(params, IDSet{pk.ID}, level, false)); out.push_back(cts.back()->h); }
+        check(mkhe_encrypt_seeded(params.ctx, level, count, pk.Value.d, dev_pt, ptIsNTT ? 1 : 0, sampler.Key(), sampler.NextNonce(),
+                                  sampler.cdt.data(), (int)sampler.cdt.size(), out.data()));
+        return cts;
+    }
     void Encrypt(const void* dev_pt, const PublicKey& pk, Ciphertext& ctOut, const int32_t* samples, bool ptIsNTT = false) {   // encryptor.go:55-118
         if (ctOut.ids.size() != 1 || ctOut.ids[0] != pk.ID) throw Error("Cannot Encrypt: ctOut must be a ciphertext over the id of pk alone");
         mkhe_ct* out[1] = {ctOut.h};

@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("MKHE_LIB") or os.path.join(_HERE, "lib", "libmkhe_hip
 u64p = C.POINTER(C.c_uint64)
 i32p = C.POINTER(C.c_int)
 s32p = C.POINTER(C.c_int32)
+u32p = C.POINTER(C.c_uint32)
 vp = C.c_void_p
 vpp = C.POINTER(C.c_void_p)
 
@@ -113,6 +114,8 @@ SIGNATURES = {
     "mkhe_bfv_keygen_relin_key": (C.c_int, [vp, vp, vp, u64p, u64p, s32p, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mkhe_crs_expand": (C.c_int, [vp, C.c_uint64, C.c_int32, vp]),
     "mkhe_encrypt": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, s32p, vpp]),
+    "mkhe_sample_small": (C.c_int, [vp, C.c_int, C.c_int, u32p, C.c_uint64, C.c_uint32, u64p, C.c_int, vp]),
+    "mkhe_encrypt_seeded": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, u32p, C.c_uint64, u64p, C.c_int, vpp]),
     "mkhe_partial_decrypt": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "mkhe_decrypt": (C.c_int, [vp, vp, vpp, vp]),
     "mkhe_ckks_embed": (C.c_int, [vp, C.c_int, vp, vp]),

@@ -701,6 +701,56 @@ int mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const 
         c->encrypt(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, samples, d.data());
     })
 }
+// device-side sampling: the checks the two calls share.  A call refused here has enqueued nothing and leaves the context (and a capture in
+// progress) as it was.  The key is never quoted.
+static Context* smp_need(mkhe_ctx* ctx, const char* what, const uint32_t* key, bool table, const uint64_t* cdt, int ncdt) {
+    if (!ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (!key) throw Error(std::string(what) + ": null key");
+    if (table) {
+        if (!cdt) throw Error(std::string(what) + ": null table");
+        if (ncdt < 2 || ncdt > SMP_MAX_CDT || (ncdt & 1)) throw Error(std::string(what) + ": ncdt must be even and 2 .. 64");
+        for (int t = 1; t < ncdt; ++t) if (cdt[t] <= cdt[t - 1]) throw Error(std::string(what) + ": the thresholds of the table must be strictly increasing");
+    }
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (a replay would repeat the keystream)");
+    MKHE_HIP(hipSetDevice(c->device));
+    g_last_ctx = c;
+    return c;
+}
+int mkhe_sample_small(mkhe_ctx* ctx, int kind, int count, const uint32_t key[8], uint64_t nonce, uint32_t first_stream, const uint64_t* cdt, int ncdt,
+                      void* dev_out) {
+    MKHE_TRY({
+        if (kind != 0 && kind != 1) throw Error("mkhe_sample_small: kind must be 0 (ternary) or 1 (table)");
+        Context* c = smp_need(ctx, "mkhe_sample_small", key, kind == 1, cdt, ncdt);
+        if (!dev_out) throw Error("mkhe_sample_small: null output");
+        if (count < 1 || count > 3 * 65535) throw Error("mkhe_sample_small: count must be 1 .. 196605");
+        if ((uint64_t)first_stream + (uint64_t)count > (1ull << 32)) throw Error("mkhe_sample_small: first_stream + count exceeds 2^32");
+        need_aligned(dev_out, "mkhe_sample_small");
+        c->sample_small(kind, count, key, nonce, first_stream, cdt, ncdt, (int32_t*)dev_out);
+    })
+}
+int mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt, const uint32_t key[8], uint64_t nonce,
+                        const uint64_t* cdt, int ncdt, mkhe_ct* const* out) {
+    MKHE_TRY({
+        Context* c = smp_need(ctx, "mkhe_encrypt_seeded", key, true, cdt, ncdt);
+        if (!dev_pk || !dev_pt || !out) throw Error("mkhe_encrypt_seeded: null argument");
+        if (level < 0 || level >= c->nq) throw Error("mkhe_encrypt_seeded: level out of range");
+        if (count < 1 || count > 65535) throw Error("mkhe_encrypt_seeded: count must be 1 .. 65535");
+        need_aligned(dev_pk, "mkhe_encrypt_seeded"); need_aligned(dev_pt, "mkhe_encrypt_seeded");
+        auto o = ct_list_out(ctx, out, count, "mkhe_encrypt_seeded");
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            if (o[b]->n != 1) throw Error("mkhe_encrypt_seeded: every out must be a ciphertext over exactly one party");
+            if (o[b]->limbs != level + 1) throw Error("mkhe_encrypt_seeded: every out must have level+1 limbs");
+            d[b] = o[b]->d;
+        }
+        c->encrypt_seeded(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, key, nonce, cdt, ncdt, d.data());
+    })
+}
 int mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out) {
     MKHE_TRY({ mark(ctx, in, out);
         if (!in || !dev_sk || !out) throw Error("mkhe_partial_decrypt: null argument");

@@ -7,8 +7,9 @@
 //   one inverse NTT of 2*B*L limbs (3*B*L when the plaintexts arrive in the NTT domain: they ride along in w[2]); encrypt_finish.
 // Decrypt of a ciphertext over k parties: ONE forward NTT of the k party polynomials, decrypt_mac (all k products summed in the NTT
 // domain), one inverse NTT of a single polynomial, decrypt_finish.  PartialDecrypt is the same with k = 1 and a plain ring.Add at the end.
-// The samples u, e0, e1 are drawn on the host (like the secrets and errors of key generation) and wiped from the device scratch behind
-// their last use, and so is everything computed from u alone.
+// The samples u, e0, e1 are drawn on the host (like the secrets and errors of key generation) or, in encrypt_seeded, on the device from a
+// ChaCha20 keystream (small_sample_kernel); either way they are wiped from the device scratch behind their last use, and so is everything
+// computed from u alone.
 #include "engine.h"
 
 namespace mkhe {
@@ -40,6 +41,13 @@ void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool p
     MKHE_HIP(hipMemcpy2DAsync(du, (size_t)N * sizeof(int32_t), samples, 3 * (size_t)N * sizeof(int32_t), (size_t)N * sizeof(int32_t), count,
                               hipMemcpyHostToDevice, stream));
     sync();                                             // the host array may be pageable: do not return before it is consumed
+    encrypt_core(level, count, pk, pt, pt_is_ntt, w, small, ot);
+}
+
+void Context::encrypt_core(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, u64* w, int32_t* small, const EdTable& ot) {
+    const int L = level + 1;
+    const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
+    int32_t* du = small + 3 * sn;
     {
         ProfScope ps(this, PROF_OTHER, (double)count * N * (4.0 + 8.0 * L));
         launch_small_expand(w + 2 * pw, du, d_mods, count, L, N, s_);
@@ -58,6 +66,51 @@ void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool p
     MKHE_HIP(hipMemsetAsync(small, 0, 3 * sn * sizeof(int32_t), s_));
     MKHE_HIP(hipMemsetAsync(w, 0, 2 * pw * sizeof(u64), s_));             // u * pk1 gives u away: it does not outlive the call
     MKHE_HIP(hipGetLastError());
+}
+
+// key, nonce and table as the arguments of one launch; the host copy is overwritten behind the launch (the runtime has copied the arguments)
+static void sample_args_wipe(SmallSampleArgs& a) {
+    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&a);
+    for (size_t i = 0; i < sizeof(a); ++i) p[i] = 0;
+}
+static void sample_args_fill(SmallSampleArgs& a, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt) {
+    for (int i = 0; i < 8; ++i) a.key[i] = key[i];
+    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32); a.first_stream = first_stream; a.ncdt = ncdt;
+    for (int t = 0; t < SMP_MAX_CDT; ++t) a.cdt[t] = t < ncdt ? cdt[t] : ~0ull;
+}
+
+void Context::sample_small(int kind, int count, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt, int32_t* dev_out) {
+    if (masked_) throw Error("mkhe_sample_small: not available on a context that owns a subset of the moduli");
+    SmallSampleArgs a;
+    sample_args_fill(a, key, nonce, first_stream, kind == 1 ? cdt : nullptr, kind == 1 ? ncdt : 0);
+    {
+        ProfScope ps(this, PROF_OTHER, 4.0 * count * N);
+        launch_small_sample(a, kind, count, dev_out, nullptr, N, s_);
+    }
+    sample_args_wipe(a);
+    MKHE_HIP(hipGetLastError());
+}
+
+// The sampler writes [count][3][N] straight into ed_small_ and, in the same launch, the rows of u a second time behind it (the layout the two
+// copies of encrypt() produce): no upload, no extra launch, and nothing for the host to wait for.
+void Context::encrypt_seeded(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const u32* key, u64 nonce, const u64* cdt, int ncdt,
+                             u64* const* outs) {
+    check_level(level);
+    if (masked_) throw Error("mkhe_encrypt_seeded: not available on a context that owns a subset of the moduli");
+    const int L = level + 1;
+    const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
+    u64* w = scratch(ed_w_, 3 * pw);
+    int32_t* small = reinterpret_cast<int32_t*>(scratch(ed_small_, 2 * sn));
+    scratch(ed_tab_, (size_t)count);
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0);     // count > ED_INLINE: staged, which synchronises
+    SmallSampleArgs a;
+    sample_args_fill(a, key, nonce, 0, cdt, ncdt);
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
+        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * sn, N, s_);
+    }
+    sample_args_wipe(a);
+    encrypt_core(level, count, pk, pt, pt_is_ntt, w, small, ot);
 }
 
 // acc [limbs][N] <- sum_i NTT-domain products of the k polynomials at ch [k][limbs][N] with the secrets sks[i]

@@ -42,4 +42,19 @@ void launch_decrypt_mac(int count, int k, u64* acc, const EdTable& ch, const EdT
 void launch_decrypt_finish(int count, u64* out, long out_stride, const u64* c0, long c0_stride, const u64* acc, const Mod* mods, int limbs, int N,
                            bool reduce, hipStream_t st);
 
+// ---- small-norm samples from a ChaCha20 keystream (include/mkhe.h, "device-side sampling": the definition of the stream and of the kinds)
+constexpr int SMP_MAX_CDT = 64;    // thresholds of a table (kind 1)
+constexpr int SMP_KIND_ENCRYPT = 2;    // launch_small_sample only: polynomial p is kind (p % 3 != 0), the layout u, e0, e1 of mkhe_encrypt's samples
+// Everything secret the kernel reads travels here, in the kernel arguments: the key is never stored in device memory the engine owns.
+struct SmallSampleArgs {
+    u32 key[8];
+    u32 nonce_lo, nonce_hi, first_stream;
+    int ncdt;
+    u64 cdt[SMP_MAX_CDT];
+};
+// out [polys][N] int32: polynomial p = stream first_stream + p of (key, nonce).  kind 0 / 1 for every polynomial, or SMP_KIND_ENCRYPT; with
+// u_rows != null (SMP_KIND_ENCRYPT only) polynomial 3 b is stored a second time at u_rows [b][N]: the gathered rows small_expand reads.
+// N is a multiple of 8; out and u_rows are 16-byte aligned.
+void launch_small_sample(const SmallSampleArgs& a, int kind, int polys, i32* out, i32* u_rows, int N, hipStream_t st);
+
 }  // namespace mkhe

@@ -261,6 +261,12 @@ class Context {
     // ---- public-key encryption and decryption (encdec.hip; mkrlwe/encryptor.go:55-118, decryptor.go:26-66), ring Q at `level`.
     // samples: host int32 [count][3][N] (u, e0, e1); pk: device [2][nq+np][N]; pt: device [count][level+1][N]; outs[b]: [2][level+1][N]
     void encrypt(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const int32_t* samples, u64* const* outs);
+    // the same with samples[b][j] = stream 3 b + j of the ChaCha20 keystream (key, nonce), drawn on the device (encdec_kernels.h small_sample_kernel;
+    // include/mkhe.h "device-side sampling"); cdt: host, ncdt thresholds.  No host synchronisation for count <= ED_INLINE.
+    void encrypt_seeded(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const u32* key, u64 nonce, const u64* cdt, int ncdt,
+                        u64* const* outs);
+    // dev_out int32 [count][N] <- streams first_stream .. first_stream + count - 1 of (key, nonce), all of one kind
+    void sample_small(int kind, int count, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt, int32_t* dev_out);
     void partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out);                      // decryptor.go:26-43
     void decrypt(const Ct& ct, const u64* const* sks, u64* pt_out);                            // decryptor.go:48-66
 
@@ -385,6 +391,9 @@ class Context {
     Scratch ed_w_, ed_small_, ed_tab_;                       // (int32 samples in ed_small_, const u64* entries in ed_tab_: sized in 8-byte words and cast at the use)
     EdTable ed_table(const std::vector<const u64*>& v, size_t tab_offset);
     void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
+    // Encrypt behind "the samples are on the device": small = int32 [count][3][N] + the count rows of u gathered behind it, w = [3][count][L][N];
+    // small_expand .. encrypt_finish and the three wipes
+    void encrypt_core(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, u64* w, int32_t* small, const EdTable& ot);
     // both encoders: the Garner constants [nq][nq], built at the first use, and the two launches of a transform that one tile does not hold:
     // forward the pass over the column tiles (the stages that span the rows) first, inverse last; launch() runs once per pass on the filled-in p
     u64* d_garner_ = nullptr;

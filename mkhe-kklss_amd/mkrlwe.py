@@ -606,6 +606,76 @@ class HostSampler:
         return e.astype(np.int32)
 
 
+def small_cdt(sigma, bound=None):
+    """The table of mkhe_sample_small / mkhe_encrypt_seeded (kind 1) for the rounded Gaussian of HostSampler.gaussian: round(N(0, sigma))
+    truncated at +-B, B = int(6 sigma) by default.  With Phi(x) = erfc(-x / (sigma sqrt 2)) / 2, lo = Phi(-B - 1/2), hi = Phi(B + 1/2):
+    T_k = min(2^64 - 1, floor((Phi(k + 1/2) - lo) / (hi - lo) * 2^64)) for k = -B .. B - 1, so that #{k : r >= T_k} - B has the
+    probabilities of the truncated rounded Gaussian to float64 precision.  A pure function -> list of 2B Python ints."""
+    sigma = float(sigma)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise MkheError("small_cdt: sigma must be finite and positive")
+    B = int(6 * sigma) if bound is None else int(bound)
+    if B < 1 or 2 * B > 64:
+        raise MkheError("small_cdt: the table has 2 * bound entries and holds 2 .. 64 (bound = %d)" % B)
+    phi = lambda x: math.erfc(-x / (sigma * math.sqrt(2.0))) / 2.0
+    lo, hi = phi(-B - 0.5), phi(B + 0.5)
+    # (p * 2^64 as an exact integer: a float64 in [0, 1] times 2^64 is an integer or has an exact floor)
+    table = [min((1 << 64) - 1, int(math.floor((phi(k + 0.5) - lo) / (hi - lo) * 18446744073709551616.0))) for k in range(-B, B)]
+    if any(b <= a for a, b in zip(table, table[1:])):
+        raise MkheError("small_cdt: the table is not strictly increasing (sigma too small for this bound)")
+    return table
+
+
+class DeviceSampler:
+    """Encryption randomness drawn ON THE DEVICE: u, e0, e1 are expanded by the engine from a ChaCha20 key (include/mkhe.h, "device-side
+    sampling"), so that an Encrypt moves 32 + 8 bytes of key and nonce instead of 12 N bytes of samples.  For Encryptor only: keys are
+    long-term and one-off, KeyGenerator keeps its host sampler.
+
+    key=None (default): 32 bytes from os.urandom.  A given key (32 bytes, or 8 uint32 words) makes every draw reproducible and must be
+    acknowledged with insecure_test_only=True -- the policy of HostSampler(rng=...).  Every engine call consumes one nonce of a 64-bit
+    counter (advanced under a lock): a (key, nonce) pair never serves two calls.  The Gaussian is the table small_cdt(sigma)."""
+
+    def __init__(self, key=None, sigma=3.2, insecure_test_only=False):
+        import os
+        import threading
+        if key is not None and not insecure_test_only:
+            raise MkheError("DeviceSampler: a given key makes the samples reproducible -- pass insecure_test_only=True "
+                            "(tests / benchmarks), or no key at all for os.urandom")
+        if key is None:
+            key = os.urandom(32)
+        if isinstance(key, (bytes, bytearray)):
+            if len(key) != 32:
+                raise MkheError("DeviceSampler: the key is 32 bytes")
+            words = [int.from_bytes(key[4 * i: 4 * i + 4], "little") for i in range(8)]
+        else:
+            words = [int(w) for w in key]
+            if len(words) != 8 or any(not 0 <= w < (1 << 32) for w in words):
+                raise MkheError("DeviceSampler: the key is 8 words of 32 bits")
+        self._key = (C.c_uint32 * 8)(*words)
+        self.sigma = float(sigma)
+        self.cdt = small_cdt(self.sigma)
+        self._cdt = (C.c_uint64 * len(self.cdt))(*self.cdt)
+        self._lock = threading.Lock()
+        self._counter = 0
+
+    @property
+    def counter(self):
+        """the nonce the next engine call will use"""
+        return self._counter
+
+    def _next_nonce(self):
+        with self._lock:
+            if self._counter >= (1 << 64) - 1:
+                raise MkheError("DeviceSampler: the 64-bit call counter is exhausted -- use a fresh key")
+            n = self._counter
+            self._counter += 1
+            return n
+
+    def encrypt_args(self):
+        """(key, nonce, cdt, ncdt) for ONE mkhe_encrypt_seeded call"""
+        return self._key, self._next_nonce(), self._cdt, len(self.cdt)
+
+
 def _s32(a, shape):
     a = np.ascontiguousarray(a, dtype=np.int32)
     if a.shape != tuple(shape):
@@ -619,6 +689,8 @@ class KeyGenerator:
     omitted, they come from `sampler`."""
 
     def __init__(self, params, sampler=None):
+        if isinstance(sampler, DeviceSampler):
+            raise MkheError("KeyGenerator: keys are long-term and one-off, their samples stay host-drawn -- a DeviceSampler serves Encryptor only")
         self.params = params
         self.sampler = sampler if sampler is not None else HostSampler()
 
@@ -814,7 +886,9 @@ def _device_plaintexts(params, pts):
 class Encryptor:
     """mkrlwe.Encryptor (encryptor.go:8-52) on the device.  u (ternary, P(0) = 1/2) and e0, e1 (Gaussian: the sampler's sigma and bound)
     are drawn on the HOST from `sampler`, like the secrets and errors of KeyGenerator; given as `samples` (int32 [3][N]: u, e0, e1) the
-    result is a deterministic function of them (parity tests).  Plaintexts are RNS polynomials: DeviceLimbs or host uint64 arrays."""
+    result is a deterministic function of them (parity tests).  With a DeviceSampler (and no explicit `samples`) they are drawn on the
+    DEVICE instead: mkhe_encrypt_seeded, one nonce of the sampler's counter per call, nothing but key and nonce crossing the bus.
+    Plaintexts are RNS polynomials: DeviceLimbs or host uint64 arrays."""
 
     def __init__(self, params, sampler=None):
         self.params = params
@@ -833,6 +907,20 @@ class Encryptor:
     def _new_batch(self, id, level, count, like=None):
         return batch_ciphertexts(Ciphertext, self.params, [id], level, count)
 
+    def _draw(self, samples, count):
+        """the host samples of one engine call as (array, pointer); None where the engine draws them itself (a DeviceSampler and no `samples`)"""
+        if samples is None and isinstance(self.sampler, DeviceSampler):
+            return None
+        return self._samples(samples, count)
+
+    def _engine_encrypt(self, level, pk, d, pt_is_ntt, smp, outs):
+        """one engine call over the plaintexts d: mkhe_encrypt on host samples, mkhe_encrypt_seeded (one nonce of the sampler) without"""
+        args = (self.params.ctx, level, d.count, pk.Value.devptr(), d.devptr(), 1 if pt_is_ntt else 0)
+        if smp is None:
+            check(lib().mkhe_encrypt_seeded(*args, *self.sampler.encrypt_args(), handle_array([c.h for c in outs])))
+        else:
+            check(lib().mkhe_encrypt(*args, smp[1], handle_array([c.h for c in outs])))
+
     def Encrypt(self, pt, pk, ctOut, samples=None, pt_is_ntt=False):
         """encryptor.go:55-118.  pt: one plaintext [limbs][N] (or DeviceLimbs of count 1) with at least ctOut.Level() + 1 limbs; the Go
         version shortens ctOut to a lower plaintext level, a device ciphertext keeps its shape, so that case raises."""
@@ -845,8 +933,7 @@ class Encryptor:
         self._check_level(level)
         if d.limbs < level + 1:
             raise MkheError("Cannot Encrypt: the plaintext is below the level of ctOut")
-        a, ptr = self._samples(None if samples is None else np.asarray(samples)[None], 1)
-        check(lib().mkhe_encrypt(self.params.ctx, level, 1, pk.Value.devptr(), d.devptr(), 1 if pt_is_ntt else 0, ptr, handle_array([ctOut.h])))
+        self._engine_encrypt(level, pk, d, pt_is_ntt, self._draw(None if samples is None else np.asarray(samples)[None], 1), [ctOut])
         return ctOut
 
     def EncryptBatch(self, pts, pk, samples=None, pt_is_ntt=False):
@@ -855,10 +942,9 @@ class Encryptor:
         d = _device_plaintexts(self.params, pts)
         level = d.limbs - 1
         self._check_level(level)
-        a, ptr = self._samples(samples, d.count)
+        smp = self._draw(samples, d.count)
         outs = self._new_batch(pk.ID, level, d.count)
-        check(lib().mkhe_encrypt(self.params.ctx, level, d.count, pk.Value.devptr(), d.devptr(), 1 if pt_is_ntt else 0, ptr,
-                                 handle_array([c.h for c in outs])))
+        self._engine_encrypt(level, pk, d, pt_is_ntt, smp, outs)
         return outs
 
 
