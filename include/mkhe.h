@@ -469,11 +469,48 @@ int  mkhe_sample_small(mkhe_ctx* ctx, int kind, int count, const uint32_t key[8]
 int  mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt,
                          const uint32_t key[8], uint64_t nonce, const uint64_t* cdt, int ncdt, mkhe_ct* const* out);
 /* PartialDecrypt decryptor.go:26-43: slot = 1 .. n names the party (the ciphertext slot of its polynomial); out is over the ids of
- * `in` without that one, at the same level: out[0] = in[0] + c_slot*sk (one ring.Add), the other polynomials are copied */
+ * `in` without that one, at the same level: out[0] = in[0] + c_slot*sk (one ring.Add), the other polynomials are copied.
+ * WARNING: the output REVEALS THE SECRET KEY of whoever ran the call to anyone who sees it: in[0] and c_slot are public and c_slot is
+ * invertible with overwhelming probability, so sk = (out[0] - in[0]) / c_slot.  The reference uses it only where one process holds every
+ * key (its tests).  Between parties use mkhe_decrypt_share / mkhe_decrypt_merge below. */
 int  mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out);
 /* Decrypt decryptor.go:48-66: dev_sk[i] = the secret of the party at slot 1+i; dev_pt_out = uint64[limbs][N], canonical residues,
  * coefficient domain */
 int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, void* dev_pt_out);
+/* ---- distributed decryption: flooded decryption shares and their merge (eprint 2022/347) ----------------------------
+ * mkhe_decrypt needs every secret key in one place, and the output of mkhe_partial_decrypt gives the key away.  In the protocol of the
+ * scheme party i publishes a SHARE mu_i = c_i * s_i + e_i, where e_i is a flooding ("smudging") noise much wider than the noise of the
+ * ciphertext, and anyone forms c_0 + sum_i mu_i.
+ *
+ * Kind 2 of the keystream above: uniform, `bits` wide.  For 1 <= bits <= 62 coefficient i of stream s takes the same 64-bit r as kinds 0 and 1
+ * (block i / 8, words 2 (i % 8) and 2 (i % 8) + 1) and
+ *     e = (r >> (64 - bits)) - 2^(bits-1),   so that e is uniform on [-2^(bits-1), 2^(bits-1)).
+ * bits = 0 means e = 0: no stream is read and the key may be NULL (tests only: such a share is PartialDecrypt's product and reveals the key).
+ * The smudging lemma is stated for this uniform distribution; a wide Gaussian has no bit-exact definition from 64 bits per coefficient.
+ * The sample is formed in registers by the kernel that adds it (one thread = one ChaCha20 block = 8 coefficients, reduced per limb without a
+ * sample-dependent branch): it never exists in memory.  The engine does not choose `bits`: that depends on the noise of the ciphertext.
+ *
+ * Noise budget.  The merge adds sum_i e_i with |sum_i e_i| <= k 2^(bits-1) per coefficient (k parties).  CKKS: every slot moves by at most
+ * N k 2^(bits-1) / scale (triangle inequality over the N unit-modulus roots of the embedding).  BFV: the message stays exact as long as
+ * k 2^(bits-1) plus the noise of the ciphertext is below Q / (2 T).
+ *
+ * Rules: those of the seeded encryption.  A (key, nonce) pair serves ONE call; mkhe_decrypt_share with flood_bits > 0 is refused between
+ * mkhe_capture_begin and mkhe_capture_end; both calls are refused on a context that owns a subset of the moduli; the key travels only in
+ * the kernel arguments of one launch and its host copy there is overwritten behind the launch; messages start with the function's name;
+ * a refused call has enqueued nothing and leaves the context usable.  Also refused: flood_bits outside 0 .. 62, a slot out of range,
+ * ciphertexts at different levels, ciphertexts over different ids in the merge, a misaligned buffer, a NULL key with flood_bits > 0. */
+/* dev_shares = uint64[count][limbs][N]: share[b][j][n] = (InvNTT(NTT(c_slot) * sk)[j][n] + (e_b[n] mod q_j)) mod q_j, canonical, where c_slot is
+ * polynomial slots[b] (1 .. n_b) of in[b] and e_b is stream b of (key, nonce), kind 2 with flood_bits bits.  All in[b] are at one level; their id
+ * sets may differ.  One launch set whatever count is (one forward NTT of count polynomials, one product kernel, one inverse NTT, one finish
+ * kernel); the unflooded product is wiped from the engine's scratch behind the finish kernel.  1 <= count <= 65535; count > 16 stages a
+ * pointer table, which synchronises. */
+int  mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8],
+                        uint64_t nonce, int flood_bits, void* dev_shares);
+/* dev_pt_out = uint64[count][limbs][N]: pt[b] = (c_0[b] + sum_i share_i[b]) mod q_j, canonical.  All in[b] are over the same ids and at the same
+ * level; nshares = the number of parties, dev_shares[i] = the buffer uint64[count][limbs][N] of the party at slot 1 + i (what that party's
+ * mkhe_decrypt_share wrote for the same batch).  One streaming launch.  With flood_bits = 0 shares the result is mkhe_decrypt's, bit for bit.
+ * nshares = 0 on ciphertexts without parties reduces c_0. */
+int  mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, void* dev_pt_out);
 
 /* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
  * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call

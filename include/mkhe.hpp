@@ -124,6 +124,7 @@ class DeviceWords {
     DeviceWords(const DeviceWords&) = delete;
     DeviceWords& operator=(const DeviceWords&) = delete;
     void download(uint64_t* host) const { check(mkhe_buf_download(params.ctx, d, host, words)); }
+    void upload(const uint64_t* host) { check(mkhe_buf_upload(params.ctx, d, host, words)); }
     Parameters& params;
     size_t words;
     void* d = nullptr;
@@ -407,11 +408,60 @@ class Encryptor {
     Parameters& params;
 };
 
-// mkrlwe.Decryptor (decryptor.go:8-23) on the device
+// What one party publishes in distributed decryption (include/mkhe.h, "distributed decryption"): mu = c_id * s_id + e for `count` ciphertexts at
+// `level`, uint64[count][level+1][N] on the device.  Shares travel between parties: Value.download on one side, Value.upload on the other.
+struct DecryptionShare {
+    DecryptionShare(Parameters& p, std::string id, int level, int count = 1)
+        : ID(std::move(id)), Level(level), Count(count), Value(p, (size_t)count * (level + 1) * p.N()) {}
+    std::string ID;
+    int Level, Count;
+    DeviceWords Value;
+};
+
+// mkrlwe.Decryptor (decryptor.go:8-23) on the device.  Between parties, decryption is ShareNew (each party, on its own key) and MergeShares (anyone):
+// Decrypt needs every key in one place, and the output of PartialDecrypt gives the key away.
 class Decryptor {
   public:
     explicit Decryptor(Parameters& p) : params(p) {}
-    // decryptor.go:26-43; the Go version works in place and deletes ct.Value[sk.ID]: here the result is a new ciphertext over the remaining ids
+    // The shares of the party of sk for the ciphertexts cts (one level; their id sets may differ) as one engine call.  floodBits = 1 .. 62: the width of
+    // the flooding noise, drawn on the device under one nonce of `sampler`; no default -- it must exceed the noise of the ciphertext by the statistical
+    // security parameter, which the engine cannot know.  floodBits = 0 (sampler may be null) is for tests only: such a share reveals sk.
+    std::shared_ptr<DecryptionShare> ShareBatch(const std::vector<const Ciphertext*>& cts, const SecretKey& sk, int floodBits, DeviceSampler* sampler) {
+        if (cts.empty()) throw Error("Cannot ShareBatch: no ciphertext");
+        if (floodBits > 0 && !sampler) throw Error("Cannot Share: the flooding noise is drawn on the device -- pass a DeviceSampler");
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        auto out = std::make_shared<DecryptionShare>(params, sk.ID, cts[0]->Level(), (int)cts.size());
+        check(mkhe_decrypt_share(params.ctx, (int)cts.size(), in.data(), slots.data(), sk.Value.d, floodBits > 0 ? sampler->Key() : nullptr,
+                                 floodBits > 0 ? sampler->NextNonce() : 0, floodBits, out->Value.d));
+        return out;
+    }
+    std::shared_ptr<DecryptionShare> ShareNew(const Ciphertext& ct, const SecretKey& sk, int floodBits, DeviceSampler* sampler) {
+        return ShareBatch({&ct}, sk, floodBits, sampler);
+    }
+    // dev_pt_out = uint64[count][level+1][N] <- c_0 + the shares of ALL parties (one DecryptionShare of count cts.size() per party, in any order), for
+    // ciphertexts over the same ids at one level: what Decrypt gives, plus the sum of the flooding noises
+    void MergeSharesBatch(const std::vector<const Ciphertext*>& cts, const std::vector<const DecryptionShare*>& shares, void* dev_pt_out) {
+        if (cts.empty()) throw Error("Cannot MergeShares: no ciphertext");
+        std::vector<const mkhe_ct*> in;
+        for (auto* ct : cts) in.push_back(ct->h);
+        std::vector<const void*> ordered;
+        for (auto& id : cts[0]->ids) {
+            const DecryptionShare* found = nullptr;
+            for (auto* sh : shares)
+                if (sh->ID == id) { if (found) throw Error("Cannot MergeShares: two shares of one party"); found = sh; }
+            if (!found) throw Error("Cannot MergeShares: the share of a party is missing");
+            if (found->Level != cts[0]->Level() || found->Count != (int)cts.size()) throw Error("Cannot MergeShares: a share is at another level or for another batch size");
+            ordered.push_back(found->Value.d);
+        }
+        if (shares.size() != ordered.size()) throw Error("Cannot MergeShares: a share of a party the ciphertext does not have");
+        check(mkhe_decrypt_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), dev_pt_out));
+    }
+    void MergeShares(const Ciphertext& ct, const std::vector<const DecryptionShare*>& shares, void* dev_pt_out) { MergeSharesBatch({&ct}, shares, dev_pt_out); }
+    // decryptor.go:26-43; the Go version works in place and deletes ct.Value[sk.ID]: here the result is a new ciphertext over the remaining ids.
+    // WARNING: the result REVEALS sk to anyone who sees it (c_0 and c_id are public, c_id is invertible with overwhelming probability): it is for a
+    // process that holds every key, as in the reference's tests.  Between parties use ShareNew / MergeShares.
     std::shared_ptr<Ciphertext> PartialDecrypt(const Ciphertext& ct, const SecretKey& sk) {
         IDSet rest = ct.IDSet_();
         rest.erase(sk.ID);

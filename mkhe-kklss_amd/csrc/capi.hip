@@ -771,6 +771,62 @@ int mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, vo
         need(ctx)->decrypt(ct->c, sk.data(), (u64*)dev_pt_out);
     })
 }
+// distributed decryption: the checks the two calls share, under the rules of the seeded encryption -- a call refused here has enqueued nothing
+// and leaves the context (and a capture in progress) as it was; the key is never quoted
+static Context* ds_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const void* out, bool keystream) {
+    if (!ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    if (!in || !out) throw Error(std::string(what) + ": null argument");
+    need_aligned(out, what);
+    for (int b = 0; b < count; ++b) {
+        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
+        if (in[b]->c.limbs != in[0]->c.limbs) throw Error(std::string(what) + ": every ciphertext must be at the same level");
+    }
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    if (keystream) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(c->stream, &cs);
+        if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (a replay would repeat the keystream)");
+    }
+    return c;
+}
+int mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8], uint64_t nonce,
+                       int flood_bits, void* dev_shares) {
+    MKHE_TRY({
+        if (flood_bits < 0 || flood_bits > SHF_MAX_BITS) throw Error("mkhe_decrypt_share: flood_bits must be 0 .. 62");
+        if (flood_bits > 0 && !key) throw Error("mkhe_decrypt_share: null key");
+        Context* c = ds_need(ctx, "mkhe_decrypt_share", count, in, dev_shares, flood_bits > 0);
+        if (!slots || !dev_sk) throw Error("mkhe_decrypt_share: null argument");
+        need_aligned(dev_sk, "mkhe_decrypt_share");
+        for (int b = 0; b < count; ++b)
+            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_decrypt_share: slot out of range (party slots are 1 .. n)");
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, "mkhe_decrypt_share");
+        c->decrypt_share(i, slots, (const u64*)dev_sk, key, nonce, flood_bits, (u64*)dev_shares);
+    })
+}
+int mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, void* dev_pt_out) {
+    MKHE_TRY({
+        Context* c = ds_need(ctx, "mkhe_decrypt_merge", count, in, dev_pt_out, false);
+        for (int b = 0; b < count; ++b)
+            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_decrypt_merge: every ciphertext must be over the same ids");
+        if (nshares != in[0]->c.n) throw Error("mkhe_decrypt_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+        if (nshares > 0 && !dev_shares) throw Error("mkhe_decrypt_merge: null argument");
+        std::vector<const u64*> sh(nshares);
+        for (int i = 0; i < nshares; ++i) {
+            if (!dev_shares[i]) throw Error("mkhe_decrypt_merge: null share in the per-party list");
+            need_aligned(dev_shares[i], "mkhe_decrypt_merge");
+            sh[i] = (const u64*)dev_shares[i];
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, "mkhe_decrypt_merge");
+        c->decrypt_merge(i, sh, (u64*)dev_pt_out);
+    })
+}
 
 // ---- CKKS encoder (ckks_encode.hip)
 // the argument checks every encoder call shares; a call refused here leaves the context (and a capture in progress) as it was

@@ -166,4 +166,59 @@ void Context::decrypt(const Ct& ct, const u64* const* sks, u64* pt_out) {
     MKHE_HIP(hipGetLastError());
 }
 
+// ---- distributed decryption.  A share is PartialDecrypt's product with the flooding noise added before it leaves the scratch: one launch set
+// for count ciphertexts -- the forward NTT gathers polynomial slots[b] of every input into w [count][L][N], decrypt_mac (k = 1) and the inverse
+// NTT run in place, share_finish_kernel adds e_b and writes the caller's buffer.  The unflooded product c_i * s_i gives the key away (c_i is
+// public): it is wiped from w behind the finish kernel.
+void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares) {
+    if (masked_) throw Error("mkhe_decrypt_share: not available on a context that owns a subset of the moduli");
+    const int count = (int)ins.size(), L = ins[0]->limbs;
+    const size_t pw = (size_t)L * N;
+    u64* w = scratch(ed_w_, (size_t)count * pw);
+    scratch(ed_tab_, 2 * (size_t)count);
+    std::vector<const u64*> c(count), s(count, sk);
+    for (int b = 0; b < count; ++b) c[b] = w + (size_t)b * pw;
+    const EdTable ct = ed_table(c, 0), st = ed_table(s, (size_t)count);    // count > ED_INLINE: staged, which synchronises
+    for (int base = 0; base < count; base += NTT_MAX_ITEMS) {
+        const int cnt = std::min(NTT_MAX_ITEMS, count - base);
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)pw;
+        b.nitems = cnt; b.outers_per_item = 1; b.nouter = cnt;
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d + (size_t)slots[base + i] * pw; b.dst_items[i] = w + (size_t)(base + i) * pw; }
+        ntt_fwd_launch(b, false);
+    }
+    {
+        ProfScope ps(this, PROF_OTHER, 24.0 * N * L * count);
+        launch_decrypt_mac(count, 1, w, ct, st, d_mods, L, N, s_);
+    }
+    ntt(w, w, count, L, 0, true, false);
+    ShareFloodArgs a;
+    for (int i = 0; i < 8; ++i) a.key[i] = bits > 0 ? key[i] : 0;
+    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32); a.bits = bits;
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * N * L * count);
+        // one limb per grid row: the ChaCha20 block is recomputed per limb, and every launch has limbs times the waves (profiles/README.md)
+        launch_share_finish(a, count, shares, w, d_mods, L, MKHE_AB_INT("MKHE_SHARE_ROWS", L), N, s_);
+    }
+    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&a);      // the runtime has copied the arguments
+    for (size_t i = 0; i < sizeof(a); ++i) p[i] = 0;
+    MKHE_HIP(hipMemsetAsync(w, 0, (size_t)count * pw * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::decrypt_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* pt) {
+    if (masked_) throw Error("mkhe_decrypt_merge: not available on a context that owns a subset of the moduli");
+    const int count = (int)ins.size(), L = ins[0]->limbs;
+    std::vector<const u64*> c(count);
+    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
+    scratch(ed_tab_, (size_t)count + shares.size());
+    const EdTable ct = ed_table(c, 0), st = ed_table(shares, (size_t)count);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * L * count * (2.0 + (double)shares.size()));
+        launch_share_merge(count, (int)shares.size(), pt, ct, st, d_mods, L, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
 }  // namespace mkhe

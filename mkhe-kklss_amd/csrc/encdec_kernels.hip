@@ -1,16 +1,10 @@
 // encdec_kernels.hip -- see encdec_kernels.h.  Streaming kernels: 256 threads, grid.x strides over PAIRS of coefficients (one 16-byte
 // access per lane), grid.y = limb, grid.z = item of the batch; per-modulus constants are wave-uniform (SGPRs).  No LDS.
-#include "encdec_kernels.h"
+#include "ed_access.h"
+#include "chacha.h"
 
 namespace mkhe {
 
-constexpr int ED_THREADS = 256;
-static int ed_bx(int N) { return (N / 2 + ED_THREADS - 1) / ED_THREADS; }
-
-typedef ulonglong2 u64x2;
-__device__ __forceinline__ u64x2 ld2(const u64* p, long pair) { return reinterpret_cast<const u64x2*>(p)[pair]; }
-__device__ __forceinline__ void st2(u64* p, long pair, u64 a, u64 b) { reinterpret_cast<u64x2*>(p)[pair] = u64x2{a, b}; }
-__device__ __forceinline__ const u64* ed_entry(const EdTable& t, int i) { return t.dev ? t.dev[i] : t.p[i]; }
 // ExtendBasisSmallNormAndCenter of one sample: e >= 0 ? e : q - |e|
 __device__ __forceinline__ u64 small_q(i32 e, u64 q) { return e < 0 ? q - (u64)(-(i64)e) : (u64)e; }
 
@@ -105,14 +99,6 @@ void launch_decrypt_finish(int count, u64* out, long out_stride, const u64* c0, 
 // key are read from the kernel arguments (scalar loads).
 constexpr int SMP_THREADS = 128;
 constexpr int SMP_MAX_GRID_Y = 65535;
-
-__device__ __forceinline__ u32 rotl32(u32 x, int n) { return (x << n) | (x >> (32 - n)); }
-__device__ __forceinline__ void chacha_qr(u32& a, u32& b, u32& c, u32& d) {
-    a += b; d = rotl32(d ^ a, 16);
-    c += d; b = rotl32(b ^ c, 12);
-    a += b; d = rotl32(d ^ a, 8);
-    c += d; b = rotl32(b ^ c, 7);
-}
 
 __global__ void __launch_bounds__(SMP_THREADS) small_sample_kernel(SmallSampleArgs a, int kind, int polys, i32* out, i32* u_rows, int N) {
     const u32 blk = blockIdx.x * SMP_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7

@@ -19,6 +19,7 @@
 #include "poly_kernels.h"
 #include "keygen_kernels.h"
 #include "encdec_kernels.h"
+#include "decshare_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -269,6 +270,11 @@ class Context {
     void sample_small(int kind, int count, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt, int32_t* dev_out);
     void partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out);                      // decryptor.go:26-43
     void decrypt(const Ct& ct, const u64* const* sks, u64* pt_out);                            // decryptor.go:48-66
+    // distributed decryption (include/mkhe.h): shares [count][limbs][N] <- NTT^-1(NTT(ins[b] polynomial slots[b]) * sk) + e_b, e_b = kind 2 of the
+    // keystream (bits wide; 0: none, key unread) on stream b of (key, nonce).  The caller (capi.hip) has checked slots, levels and the capture.
+    void decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares);
+    // pt [count][limbs][N] <- ins[b] polynomial 0 + sum_i shares[i][b], canonical; ins are over the same ids (shares.size() of them) at one level
+    void decrypt_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* pt);
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).

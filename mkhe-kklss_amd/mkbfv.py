@@ -709,6 +709,21 @@ class Decryptor(mkrlwe.Decryptor):
             return Message(self.encoder.Decode(mkrlwe.Decryptor.Decrypt(self, ct, skSet)))
         return Message(self.encoder.Decode(self.DecryptPtxt(ct, skSet)))
 
+    def MaxFloodBits(self, parties):
+        """floor(log2(Q / (2 T parties))): with flood_bits up to this, parties * 2^(flood_bits - 1) <= Q / (4 T), which leaves the other half of
+        the decryption margin Q / (2 T) to the noise of the ciphertext (the message is exact while the two together stay below Q / (2 T))"""
+        Q = 1
+        for q in self.params.Q:
+            Q *= int(q)
+        return (Q // (2 * int(self.params.T()) * int(parties))).bit_length() - 1
+
+    def MergeSharesMsg(self, ct, shares):
+        """the merge of the shares of all parties -> Message.  With the device encoder the merged buffer goes straight to mkhe_bfv_decode."""
+        pt = self.MergeShares(ct, shares)
+        if isinstance(self.encoder, DeviceEncoder):
+            return Message(self.encoder.Decode(pt))
+        return Message(self.encoder.Decode(pt.download()[0]))
+
 
 def NewDecryptor(params, encoder="host"):
     return Decryptor(params, encoder)

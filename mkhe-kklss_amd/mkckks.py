@@ -1130,6 +1130,18 @@ class Decryptor(mkrlwe.Decryptor):
         pt = self.DecryptPtxt(ct, skSet)
         return Message(self.encoder.Decode(pt.Value, pt.Scale))
 
+    def FloodSlotBound(self, parties, flood_bits, scale):
+        """how far a merge of `parties` shares with flood_bits bits moves a slot, at most: N * parties * 2^(flood_bits - 1) / scale (the sum of
+        the flooding noises is below parties * 2^(flood_bits - 1) per coefficient, and a slot is a sum of N coefficients times unit-modulus roots)"""
+        return self.params.N() * self.FloodBound(parties, flood_bits) / float(scale)
+
+    def MergeSharesMsg(self, ct, shares):
+        """the merge of the shares of all parties -> Message.  With the device encoder the merged buffer goes straight to mkhe_ckks_decode."""
+        pt = self.MergeShares(ct, shares)
+        if isinstance(self.encoder, DeviceEncoder):
+            return Message(self.encoder.Decode(pt, ct.ScalingFactor()))
+        return Message(self.encoder.Decode(pt.download()[0], ct.ScalingFactor()))
+
 
 def NewDecryptor(params, encoder="host"):
     return Decryptor(params, encoder)

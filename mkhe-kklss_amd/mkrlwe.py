@@ -675,6 +675,10 @@ class DeviceSampler:
         """(key, nonce, cdt, ncdt) for ONE mkhe_encrypt_seeded call"""
         return self._key, self._next_nonce(), self._cdt, len(self.cdt)
 
+    def share_args(self):
+        """(key, nonce) for ONE mkhe_decrypt_share call: the same counter as encrypt_args, so that no nonce serves two calls of either kind"""
+        return self._key, self._next_nonce()
+
 
 def _s32(a, shape):
     a = np.ascontiguousarray(a, dtype=np.int32)
@@ -952,8 +956,49 @@ def NewEncryptor(params, sampler=None):
     return Encryptor(params, sampler)
 
 
+class DecryptionShare:
+    """What one party publishes in distributed decryption (include/mkhe.h, "distributed decryption"): mu = c_id * s_id + e for `count`
+    ciphertexts at `level`, uint64 [count][level+1][N] on the device.  Shares travel between parties: download() gives the host array,
+    upload() takes it on the receiving side (DecryptionShare(params, id, level, count).upload(host))."""
+
+    def __init__(self, params, id, level, count=1):
+        self.ID, self._level, self.count = id, int(level), int(count)
+        self.Value = DeviceLimbs(params, self.count, self._level + 1)
+
+    def Level(self):
+        return self._level
+
+    def download(self):
+        return self.Value.download()
+
+    def upload(self, host):
+        self.Value.upload(host)
+        return self
+
+
+def order_shares(ids, level, count, shares):
+    """the shares of a merge in the slot order of a ciphertext over `ids`; raises on a missing or duplicate share, on one of a party the
+    ciphertext does not have, at another level or for another batch size.  Pure: no engine call."""
+    by_id = {}
+    for sh in shares:
+        if sh.ID in by_id:
+            raise MkheError("Cannot MergeShares: two shares of party %r" % (sh.ID,))
+        if sh.ID not in ids:
+            raise MkheError("Cannot MergeShares: a share of party %r, which the ciphertext does not have" % (sh.ID,))
+        if sh.Level() != level:
+            raise MkheError("Cannot MergeShares: the share of party %r is at level %d, the ciphertext at level %d" % (sh.ID, sh.Level(), level))
+        if sh.count != count:
+            raise MkheError("Cannot MergeShares: the share of party %r is for %d ciphertexts, the merge for %d" % (sh.ID, sh.count, count))
+        by_id[sh.ID] = sh
+    for i in ids:
+        if i not in by_id:
+            raise MkheError("Cannot MergeShares: the share of party %r is missing" % (i,))
+    return [by_id[i] for i in ids]
+
+
 class Decryptor:
-    """mkrlwe.Decryptor (decryptor.go:8-23) on the device; secret keys never leave it."""
+    """mkrlwe.Decryptor (decryptor.go:8-23) on the device; secret keys never leave it.  Between parties, decryption is ShareNew (each party, on
+    its own key) and MergeShares (anyone): Decrypt needs every key in one place, and the output of PartialDecrypt gives the key away."""
 
     def __init__(self, params):
         self.params = params
@@ -961,9 +1006,68 @@ class Decryptor:
     def _like(self, ct, ids):
         return Ciphertext(self.params, ids, ct.Level(), zero=False)
 
+    @staticmethod
+    def FloodBound(parties, flood_bits):
+        """what a merge of `parties` shares with flood_bits bits adds to a coefficient, at most: parties * 2^(flood_bits - 1) (exact integer; 0 bits: 0)"""
+        return 0 if flood_bits == 0 else int(parties) << (int(flood_bits) - 1)
+
+    def ShareBatch(self, cts, sk, flood_bits, sampler):
+        """The decryption shares of the party of `sk` for B ciphertexts at one level (their id sets may differ) as ONE engine call
+        (mkhe_decrypt_share) -> one DecryptionShare of count B.  flood_bits = 1 .. 62: the width of the flooding noise, uniform on
+        [-2^(bits-1), 2^(bits-1)), drawn on the device under one nonce of `sampler` (a DeviceSampler); it must exceed the noise of the ciphertext
+        by the statistical security parameter, which the engine cannot know -- so there is no default.  flood_bits = 0 (no noise, sampler
+        unused) is for TESTS ONLY: such a share is PartialDecrypt's product and reveals sk."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot ShareBatch: no ciphertext")
+        level = cts[0].Level()
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot Share: the ciphertext has no component for the id of sk")
+            if ct.Level() != level:
+                raise MkheError("Cannot Share: the ciphertexts of one call must be at the same level")
+        if not isinstance(flood_bits, int) or not 0 <= flood_bits <= 62:
+            raise MkheError("Cannot Share: flood_bits must be an integer 0 .. 62")
+        key, nonce = None, 0
+        if flood_bits > 0:
+            if not isinstance(sampler, DeviceSampler):
+                raise MkheError("Cannot Share: the flooding noise is drawn on the device -- pass a DeviceSampler")
+            key, nonce = sampler.share_args()
+        out = DecryptionShare(self.params, sk.ID, level, len(cts))
+        slots = (C.c_int * len(cts))(*[ct.slot(sk.ID) for ct in cts])
+        check(lib().mkhe_decrypt_share(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), key, nonce,
+                                       flood_bits, out.Value.devptr()))
+        return out
+
+    def ShareNew(self, ct, sk, flood_bits, sampler):
+        """ShareBatch of one ciphertext"""
+        return self.ShareBatch([ct], sk, flood_bits, sampler)
+
+    def MergeSharesBatch(self, cts, shares):
+        """c_0 + the shares of ALL parties, for B ciphertexts over the same ids at one level -> DeviceLimbs [B][level+1][N], canonical,
+        coefficient domain (what Decrypt gives, plus the sum of the flooding noises).  shares: one DecryptionShare of count B per party,
+        in any order."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot MergeShares: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids or ct.Level() != cts[0].Level():
+                raise MkheError("Cannot MergeShares: the ciphertexts of one call must be over the same ids and at the same level")
+        ordered = order_shares(cts[0].ids, cts[0].Level(), len(cts), shares)
+        pt = DeviceLimbs(self.params, len(cts), cts[0].Level() + 1)
+        check(lib().mkhe_decrypt_merge(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), len(ordered),
+                                       handle_array([sh.Value.devptr() for sh in ordered]), pt.devptr()))
+        return pt
+
+    def MergeShares(self, ct, shares):
+        """MergeSharesBatch of one ciphertext -> DeviceLimbs [1][level+1][N]"""
+        return self.MergeSharesBatch([ct], shares)
+
     def PartialDecrypt(self, ct, sk):
         """decryptor.go:26-43.  The Go version works in place and deletes ct.Value[sk.ID]; a device ciphertext keeps its shape, so the
-        result is a NEW ciphertext over the remaining ids and `ct` is left as it was (the deviation Rescale already makes)."""
+        result is a NEW ciphertext over the remaining ids and `ct` is left as it was (the deviation Rescale already makes).
+        WARNING: the result REVEALS sk to anyone who sees it (c_0 and c_id are public and c_id is invertible with overwhelming probability):
+        it is for a process that holds every key, as in the reference's tests.  Between parties use ShareNew / MergeShares."""
         if sk.ID not in ct.ids:
             raise MkheError("Cannot PartialDecrypt: the ciphertext has no component for the id of sk")
         out = self._like(ct, [i for i in ct.ids if i != sk.ID])
