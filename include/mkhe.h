@@ -356,6 +356,32 @@ int  mkhe_bfv_mul_relin(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1,
                         const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_b2,
                         const mkhe_swk* const* rlk_d1, const mkhe_swk* const* rlk_d2,
                         const mkhe_swk* const* rlk_v, const mkhe_swk* crs_u, mkhe_ct* out);
+/* K MK-BFV products under ONE Quantize and ONE relinearisation tail (no reference counterpart; the MK-BFV twin of mkhe_mul_relin_sum):
+ * out = sum_k op0[k] * op1[k], an encrypted inner product mod T.  With ExtB = ExternalProductBFVHoisted, ExtH = ExternalProductHoisted,
+ * (h1, h2) = DecomposeBFV and every + over Q or R canonical, for every pair k
+ *   r0 = ModUpQtoR(every polynomial of op0[k]) ;  r1 = Rescale(every polynomial of op1[k])                 (evaluator.go:118-140)
+ *   f0 = NTT_R(r0) ;  f1 = NTT_R(r1)
+ *   z_0 += f0_0 * f1_0 ;  z_i += f1_0 * f0_i (i in ids0) ;  z_j += f0_0 * f1_j (j in ids1)                 (mod the primes of R, NTT domain)
+ *   x1 = MForm(sum_i d1_i (.) h1(r0_i)), x2 with d2, h2 ;  y1, y2 with b1, b2 over the r1_j               (keyswitch_hoisted.go:86-134)
+ *   e_j += ExtB(h1(r1_j), h2(r1_j), x1, x2)                                                               (step E, :176-183)
+ *   t_i += ExtB(h1(r0_i), h2(r0_i), y1, y2)                                                               (step F1, :190-197)
+ * and then ONCE
+ *   out_o = Quantize(z_o) for every output slot ;  out_j += e_j
+ *   per party i of op0:  out_0 += ExtH(h(t_i), v_i) ;  out_i += ExtH(h(t_i), u)                            (step F2, :199-205)
+ * Quantize(sum z) and sum Quantize(z) differ by the rounding only, and a wrap of the sum mod R = Q * QMul is a multiple of T * Q after the
+ * scaling: the same message mod T, one rounding and one gadget noise of F2 instead of K.  K = 1 is mkhe_bfv_mul_relin
+ * bit for bit, and the result does not depend on the order of the pairs.
+ *   1 <= K <= 16; ciphertexts at the maximum level, coefficient domain; every op0[k] carries the ids of op0[0], every op1[k] those of op1[0];
+ *   out carries exactly the union and is distinct from every operand; keys aligned as for mkhe_bfv_mul_relin; every prime of Q and QMul below
+ *   2^60 (one 128-bit accumulator of 2 K <= 32 products per word of z).  BFV contexts that own every modulus.
+ *   Scratch, in 8-byte words: ((K + 1) (2 + |ids0| + |ids1|) + 1 + |ids_out|) * 2 nQ N -- the pairs over R in the NTT domain, ONE pair in the
+ *   coefficient domain (reused) and z -- beside what mkhe_bfv_mul_relin keeps ((|ids0| + |ids1|) nQ N more for the t_i and e_j).  Grow-only and
+ *   allocated by the first call of a shape: inside a capture a call that would have to allocate is refused.
+ * Every message starts with the name of the call; a refused call enqueues nothing and leaves the context usable. */
+int  mkhe_bfv_mul_relin_sum(mkhe_ctx* ctx, int K, const mkhe_ct* const* op0, const mkhe_ct* const* op1,
+                            const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_b2,
+                            const mkhe_swk* const* rlk_d1, const mkhe_swk* const* rlk_d2,
+                            const mkhe_swk* const* rlk_v, const mkhe_swk* crs_u, mkhe_ct* out);
 /* Evaluator.mulRelin (mkbfv/evaluator.go:95-113) -> KeySwitcher.MulAndRelinBFV (mkbfv/keyswitch.go:115-251): the reference's NON-hoisted
  * twin as its own device path, in the reference's order and with its pool discipline -- one pair of digit vectors that every
  * DecomposeBFV overwrites (each party component is decomposed twice), x / y accumulated party by party, every ExternalProductBFV /

@@ -753,6 +753,28 @@ class Evaluator {
         check((hoisted ? mkhe_bfv_mul_relin : mkhe_bfv_mul_relin_unhoisted)(params.ctx, op0.h, op1.h, b1.data(), b2.data(), d1.data(), d2.data(), v.data(), params.CRS[-1]->h, out->h));
         return out;
     }
+    // mkhe_bfv_mul_relin_sum as it is (no reference counterpart): ctOut = sum_k ops0[k] * ops1[k] under one Quantize and one relinearisation tail.
+    // Every ops0[k] carries the ids of ops0[0], every ops1[k] those of ops1[0]; 1 to 16 pairs; ctOut carries the union of the ids
+    void MulRelinSum(const std::vector<const Ciphertext*>& ops0, const std::vector<const Ciphertext*>& ops1, RelinearizationKeySet& rlkSet, Ciphertext& ctOut) {
+        if (ops0.empty() || ops0.size() != ops1.size()) throw Error("MulRelinSum: as many first operands as second ones, at least one pair");
+        if (!params.CRS.count(-1)) throw Error("mkhe: CRS[-1] (u) has not been uploaded");
+        std::vector<const mkhe_ct*> a, b;
+        std::vector<const mkhe_swk*> b1, b2, d1, d2, v;
+        for (auto* c : ops0) a.push_back(c->h);
+        for (auto* c : ops1) b.push_back(c->h);
+        for (auto& i : ops1[0]->ids) { auto& k = rlkSet.GetRelinearizationKey(i); b1.push_back(k.Value[0]->Value[0]->h); b2.push_back(k.Value[1]->Value[0]->h); }
+        for (auto& i : ops0[0]->ids) {
+            auto& k = rlkSet.GetRelinearizationKey(i);
+            d1.push_back(k.Value[0]->Value[1]->h); d2.push_back(k.Value[1]->Value[1]->h); v.push_back(k.Value[0]->Value[2]->h);
+        }
+        check(mkhe_bfv_mul_relin_sum(params.ctx, (int)a.size(), a.data(), b.data(), b1.data(), b2.data(), d1.data(), d2.data(), v.data(), params.CRS[-1]->h, ctOut.h));
+    }
+    CiphertextPtr MulRelinSumNew(const std::vector<const Ciphertext*>& ops0, const std::vector<const Ciphertext*>& ops1, RelinearizationKeySet& rlkSet) {
+        if (ops0.empty() || ops0.size() != ops1.size()) throw Error("MulRelinSum: as many first operands as second ones, at least one pair");
+        auto out = bin(*ops0[0], *ops1[0]);
+        MulRelinSum(ops0, ops1, rlkSet, *out);
+        return out;
+    }
     CiphertextPtr RotateNew(const Ciphertext& ct0, int rotidx, mkrlwe::RotationKeySet& rkSet) {                                    // evaluator.go:142-180 (precomputed indices)
         auto out = std::make_unique<Ciphertext>(params, ct0.IDSet_(), false);
         ksw.Rotate(ct0, rotidx, rkSet, *out);

@@ -103,6 +103,7 @@ SIGNATURES = {
     "mkhe_bfv_mr_partial": (C.c_int, [vp, vp, vp, vpp, vpp, vpp, vpp, C.c_int, vp, vp, vp, vp, vp]),
     "mkhe_bfv_mr_finish": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vpp, vp, vp]),
     "mkhe_bfv_mul_relin": (C.c_int, [vp, vp, vp, vpp, vpp, vpp, vpp, vpp, vp, vp]),
+    "mkhe_bfv_mul_relin_sum": (C.c_int, [vp, C.c_int, vpp, vpp, vpp, vpp, vpp, vpp, vpp, vp, vp]),
     "mkhe_bfv_mul_relin_unhoisted": (C.c_int, [vp, vp, vp, vpp, vpp, vpp, vpp, vpp, vp, vp]),
     "mkhe_keygen_secret": (C.c_int, [vp, s32p, vp]),
     "mkhe_keygen_switching_key": (C.c_int, [vp, vp, s32p, vp]),

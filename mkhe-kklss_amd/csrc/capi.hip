@@ -1030,6 +1030,42 @@ int mkhe_bfv_mul_relin(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1,
     })
 }
 
+// (a function of its own, as mul_relin_sum_body)
+static void bfv_mul_relin_sum_body(mkhe_ctx* ctx, int K, const mkhe_ct* const* op0, const mkhe_ct* const* op1,
+                                   const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_b2,
+                                   const mkhe_swk* const* rlk_d1, const mkhe_swk* const* rlk_d2,
+                                   const mkhe_swk* const* rlk_v, const mkhe_swk* crs_u, mkhe_ct* out) {
+    const std::string what = "mkhe_bfv_mul_relin_sum";
+    try {
+        if (!ctx) throw Error(what + ": null context");
+        if (K < 1 || K > TSUM_MAX_K) throw Error(what + ": takes 1 to " + std::to_string(TSUM_MAX_K) + " pairs");      // (before the lists are read)
+        if (!out || !crs_u || !rlk_b1 || !rlk_b2 || !rlk_d1 || !rlk_d2 || !rlk_v) throw Error(what + ": null argument");
+        auto a = ct_list(ctx, op0, K, what.c_str());
+        auto b = ct_list(ctx, op1, K, what.c_str());
+        const int n0 = a[0]->n, n1 = b[0]->n;      // (that every pair carries these ids, and that out is none of the operands, is the engine's check)
+        auto keys = [&](const mkhe_swk* const* v, size_t n, const char* name) {
+            std::vector<const Swk*> r(n);
+            for (size_t i = 0; i < n; ++i) { if (!v[i]) throw Error(what + ": null handle in " + name); mark(ctx, v[i]); r[i] = &v[i]->s; }
+            return r;
+        };
+        auto b1 = keys(rlk_b1, n1, "rlk_b1"); auto b2 = keys(rlk_b2, n1, "rlk_b2");
+        auto d1 = keys(rlk_d1, n0, "rlk_d1"); auto d2 = keys(rlk_d2, n0, "rlk_d2");
+        auto v = keys(rlk_v, n0, "rlk_v");
+        need(ctx)->bfv_mul_relin_sum(a, b, b1.data(), b2.data(), d1.data(), d2.data(), v.data(), crs_u->s, out->c);
+    } catch (const std::exception& e) {
+        // every message of this entry point starts with its name, whichever layer raised it
+        const std::string m = e.what();
+        if (m.compare(0, what.size() + 1, what + ":") == 0) throw;
+        throw Error(what + ": " + m);
+    }
+}
+int mkhe_bfv_mul_relin_sum(mkhe_ctx* ctx, int K, const mkhe_ct* const* op0, const mkhe_ct* const* op1,
+                           const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_b2,
+                           const mkhe_swk* const* rlk_d1, const mkhe_swk* const* rlk_d2,
+                           const mkhe_swk* const* rlk_v, const mkhe_swk* crs_u, mkhe_ct* out) {
+    MKHE_TRY({ mark(ctx, crs_u, out); bfv_mul_relin_sum_body(ctx, K, op0, op1, rlk_b1, rlk_b2, rlk_d1, rlk_d2, rlk_v, crs_u, out); })
+}
+
 int mkhe_bfv_mul_relin_unhoisted(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1,
                                  const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_b2,
                                  const mkhe_swk* const* rlk_d1, const mkhe_swk* const* rlk_d2,

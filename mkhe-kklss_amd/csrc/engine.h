@@ -136,6 +136,11 @@ class Context {
     void bfv_mul_relin(const Ct& op0, const Ct& op1, const Swk* const* rlk_b1, const Swk* const* rlk_b2,
                        const Swk* const* rlk_d1, const Swk* const* rlk_d2, const Swk* const* rlk_v,
                        const Swk& crs_u, Ct& out);                            // Evaluator.MulRelinNew
+    // out = sum_k op0[k] * op1[k] under ONE Quantize and ONE relinearisation tail (engine_bfv_sum.hip; no reference counterpart): per pair the
+    // conversions, the transforms over R, x, y, t_i += ExtB(h(c0_i), y) and e_j += ExtB(h(c1_j), x); then one tensor_sum_kernel over R, one Quantize,
+    // out_j += e_j and step F2 on the summed t_i.  1 <= K <= TSUM_MAX_K; BFV contexts that own every modulus
+    void bfv_mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector<const Ct*>& op1, const Swk* const* rlk_b1, const Swk* const* rlk_b2,
+                           const Swk* const* rlk_d1, const Swk* const* rlk_d2, const Swk* const* rlk_v, const Swk& crs_u, Ct& out);
     // elementwise evaluator ops (mkckks/evaluator.go:41-300, mkbfv/evaluator.go:27-76): op 0 add, 1 sub
     void ct_binary(int op, const Ct& a, const Ct& b, Ct& out);
     // mkckks MultByConst body (evaluator.go:150-196) and MulPtxtNew body without its Rescale (:471-478)

@@ -250,6 +250,8 @@ void launch_tensor(const TensorArgs& a, hipStream_t st);
 // output on purpose, see ModDownMergedArgs).  Each output word is ONE
 // 128-bit accumulator of at most 2 K <= 32 products and one reduction; stored canonical, times scale[l] (Montgomery constants, NULL: none) -- with
 // scale = MForm(P mod q_l) the form ExtItem::qadd takes (engine.h).  out must not overlap in.
+// map (NULL: limb l under modulus l): [L] modulus index of limb l, as TensorArgs::map -- ring R of mkbfv (Context::bfv_mul_relin_sum), where
+// scale = MForm(t) per limb of R is the MulScalar(t) of Quantize.  Every modulus of the launch must be below 2^60 (the caller's check).
 constexpr int TSUM_MAX_K = 16;
 struct TensorSumArgs {
     const u64* in;
@@ -259,6 +261,7 @@ struct TensorSumArgs {
     long pair_words;
     unsigned int term[33];
     int K, nout, L, N;
+    const int* map;
 };
 void launch_tensor_sum(const TensorSumArgs& a, hipStream_t st);
 

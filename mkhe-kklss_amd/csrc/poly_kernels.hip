@@ -1027,6 +1027,8 @@ void launch_tensor(const TensorArgs& a, hipStream_t st) {
 // skipped).  c0_0 and c1_0 of a pair are read by every output that uses them -- from the caches: the workgroups of one (block of j, limb) run side by side.
 // Reduction: at most 2 K <= 32 products of canonical residues below q < 2^60 in ONE 128-bit accumulator: what redc128 accepts.  redc128 leaves
 // sum * 2^-64; the Montgomery product with R^2 (times the scale, itself in Montgomery form) returns the sum (times the scale), canonical.
+// The modulus of limb l is mods[map[l]] where a map is given (ring R = Q || QMul of mkbfv, scale = MForm(t): the MulScalar of Quantize); the scale
+// stays indexed by the limb.
 static_assert(TSUM_MAX_K <= 16, "tensor_sum_kernel: 2 * TSUM_MAX_K products must stay within the 32 that redc128 accepts for q < 2^60");
 typedef const __attribute__((address_space(4))) TensorSumArgs* tsum_kargs;
 template <int CH>
@@ -1039,7 +1041,7 @@ __global__ void __launch_bounds__(PW_THREADS) tensor_sum_kernel(TensorSumArgs a)
     const bool two = ((t >> 16) & 255) != 255;
     const long x1 = (long)(t & 255) * PO, y1 = (long)((t >> 8) & 255) * PO, x2 = two ? (long)((t >> 16) & 255) * PO : x1, y2 = two ? (long)(t >> 24) * PO : y1;
     for (int l = blockIdx.z; l < a.L; l += gridDim.z) {
-        const Mod md = load_mod((sc_mod)a.mods + l);
+        const Mod md = load_mod((sc_mod)a.mods + (a.map ? ((sc_int)a.map)[l] : l));
         const long off = (long)l * a.N + j;
         u64 hi = 0, lo = 0;
         for (int k = 0; k < a.K; k += CH) {

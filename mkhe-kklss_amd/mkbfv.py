@@ -229,6 +229,31 @@ class Evaluator:
                  handle_array(d2), handle_array(v), params.CRS[-1].h, ctOut.h))
         return ctOut
 
+    def MulRelinSumNew(self, ops0, ops1, rlkSet):
+        """sum_k MulRelin(ops0[k], ops1[k]) under ONE Quantize and ONE relinearisation tail (no reference counterpart; mkhe_bfv_mul_relin_sum,
+        DESIGN.md 4.5j): an encrypted inner product mod T.  Every ops0[k] carries the ids of ops0[0], every ops1[k] those of ops1[0]; 1 to 16
+        pairs.  Another ciphertext of the same sum than the chain of MulRelinNew and AddNew: one rounding and one gadget noise of step F2."""
+        ops0, ops1 = list(ops0), list(ops1)
+        if len(ops0) != len(ops1) or not ops0:
+            raise MkheError("MulRelinSumNew: as many first operands as second ones, at least one pair")
+        if len(ops0) > MULRELIN_SUM_MAX:
+            raise MkheError("MulRelinSumNew: at most %d pairs per call" % MULRELIN_SUM_MAX)
+        params = self.params
+        if -1 not in params.CRS:
+            raise MkheError("mkhe: CRS[-1] (u) has not been uploaded")
+        ctOut = NewCiphertext(params, ops0[0].IDSet() | ops1[0].IDSet(), zero=False)      # every limb is written by the engine
+        k0 = [rlkSet.GetRelinearizationKey(i) for i in ops0[0].ids]
+        k1 = [rlkSet.GetRelinearizationKey(i) for i in ops1[0].ids]
+        b1 = [k.Value[0].Value[0].h for k in k1]
+        b2 = [k.Value[1].Value[0].h for k in k1]
+        d1 = [k.Value[0].Value[1].h for k in k0]
+        d2 = [k.Value[1].Value[1].h for k in k0]
+        v = [k.Value[0].Value[2].h for k in k0]
+        check(lib().mkhe_bfv_mul_relin_sum(params.ctx, len(ops0), handle_array([c.h for c in ops0]), handle_array([c.h for c in ops1]),
+                                           handle_array(b1), handle_array(b2), handle_array(d1), handle_array(d2), handle_array(v),
+                                           params.CRS[-1].h, ctOut.h))
+        return ctOut
+
     def RotateNew(self, ct0, rotidx, rkSet):
         """evaluator.go:142-180"""
         n2 = self.params.N() // 2
@@ -322,6 +347,9 @@ class Evaluator:
     def SubPtxtNew(self, ct, pt):
         """ct - pt, pt as for AddPtxtNew"""
         return self.AddPtxtBatch([ct], pt, sub=True)[0]
+
+
+MULRELIN_SUM_MAX = 16     # pairs per mkhe_bfv_mul_relin_sum call (csrc/poly_kernels.h, TSUM_MAX_K)
 
 
 def NewEvaluator(params):
