@@ -537,6 +537,55 @@ int  mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, cons
  * mkhe_decrypt_share wrote for the same batch).  One streaming launch.  With flood_bits = 0 shares the result is mkhe_decrypt's, bit for bit.
  * nshares = 0 on ciphertexts without parties reduces c_0. */
 int  mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, void* dev_pt_out);
+/* ---- collective refresh: masked shares, re-encryption, exact lift (the interactive bootstrapping of multiparty RLWE) -----------------
+ * Every MulRelin drops a level and at level 0 the evaluator stops; there is no bootstrapping here.  Parties that publish decryption shares
+ * are online anyway, and can REFRESH a ciphertext instead: every party masks its share with a secret uniform polynomial M_i and encrypts
+ * -M_i under its own public key at the output level; anyone adds c_0 and the shares, lifts the sum -- the message plus sum_i M_i, which
+ * hides it -- exactly to the output moduli and adds the re-encryptions, which cancel the masks.  The result encrypts the same message over
+ * the same parties at the output level, and nobody has seen the message.
+ *
+ * Notation.  ct = (c_0, c_1 .. c_k) over ids, at level l, with Lin = l + 1 limbs and Q_l = q_0 .. q_l; Lout = the limbs of the output,
+ * 1 <= Lout <= nQ.
+ *
+ * Kind 3 of the keystream: wide uniform, `bits` wide, 1 <= bits <= 120.  A mask polynomial uses TWO streams of (key, nonce_mask): coefficient n
+ * takes the 64-bit value lo from stream 2 b under the block and word rule of kinds 0-2 (block n / 8, words 2 (n % 8) and 2 (n % 8) + 1) and hi
+ * the same way from stream 2 b + 1.  With r = hi 2^64 + lo:
+ *     M[n] = (r >> (128 - bits)) - 2^(bits-1),   uniform on [-2^(bits-1), 2^(bits-1)).
+ * bits = 0 means M = 0: no mask stream is read (tests only: such a share is PartialDecrypt's product and reveals the key).  Every stream still
+ * yields 64 bits per coefficient.  (Why two streams: at scale 2^54 a 62-bit flood hides the message by 8 bits only.)
+ *
+ * What the caller must ensure.  The engine cannot check that k 2^(bits-1) + |m + e| < Q_l / 2 for every coefficient (k parties, m + e the
+ * message with its noise); otherwise the lift wraps.  bits minus the bit size of the message is the statistical hiding the caller gets.  The
+ * engine does not choose bits.
+ *
+ * Rules: those of distributed decryption, on mkrlwe / CKKS contexts that own every modulus.  Refused: BFV contexts (a mask mod T is another
+ * protocol); contexts with mkhe_ctx_set_owned; both calls between mkhe_capture_begin and mkhe_capture_end (the share would repeat its
+ * keystream, the merge builds tables at its first use); mask_bits outside 0 .. 120; a slot out of range; inputs at different levels; in the
+ * merge different ids, or a reenc that is not over exactly the id of its slot or has other than Lout limbs; an output that aliases an input; a
+ * NULL key (mask_bits = 0 reads no mask stream, but the encryption draws its samples from the key all the same); a misaligned buffer; count
+ * outside 1 .. 65535; mask_bits > 0 with nonce_mask == nonce_enc.  Each of the two nonces obeys the one-call rule of the seeded calls.
+ * Messages start with the function's name; a refused call has enqueued nothing and leaves the context usable. */
+/* Party side.  dev_shares = uint64[count][Lin][N]: share[b][j][n] = (InvNTT(NTT(c_slot) * sk)[j][n] + (M_b[n] mod q_j)) mod q_j, canonical: what
+ * mkhe_decrypt_share computes, with M_b (kind 3, mask_bits bits, streams 2 b and 2 b + 1 of (key, nonce_mask)) in the place of the flood.
+ * reenc[b] = a ciphertext over exactly the one id at slots[b] of in[b], with Lout limbs (its shape says what Lout is; the same for every b):
+ * bit for bit what mkhe_encrypt_seeded(level = Lout - 1, count, dev_pk, pt, 0, key, nonce_enc, cdt, ncdt) writes for the plaintext
+ * pt[b][j][n] = (-M_b[n]) mod q_j, canonical, coefficient domain (encryption streams 3 b, 3 b + 1, 3 b + 2 of nonce_enc).  Behind their last
+ * use the engine wipes from its scratch the unmasked product (as mkhe_decrypt_share does), the plaintext -M and the samples; the key travels in
+ * kernel arguments only.  count > 16 stages pointer tables, which synchronises. */
+int  mkhe_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk,
+                        const uint32_t key[8], uint64_t nonce_mask, uint64_t nonce_enc, int mask_bits, const uint64_t* cdt, int ncdt,
+                        void* dev_shares, mkhe_ct* const* reenc);
+/* Anyone.  out[b] is over the ids of in[b] with Lout limbs (its shape says what Lout is); all in[b] have the same ids and level; nshares = the
+ * number of parties, dev_shares[i] and reenc[i * count + b] those of the party at slot 1 + i.
+ *   1. R = (c_0 + sum_i share_i) mod Q_l: the residues mkhe_decrypt_merge gives.
+ *   2. R~ = R if R <= (Q_l - 1) / 2, else R - Q_l: the exact centred integer.
+ *   3. out_0[j] = ((R~ mod q_j) + sum_i reenc_i.c0[j]) mod q_j for j < Lout.
+ *   4. out_(1+i) = reenc_i.c1.
+ * Everything is canonical, and every limb of every component of out is written.  For j < Lin, R~ mod q_j is the residue of R itself.  With all
+ * reenc zero and Lout = Lin the result is mkhe_decrypt_merge's plaintext in slot 0.  One streaming launch; the tables of the lift are built
+ * at the first call. */
+int  mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares,
+                        const mkhe_ct* const* reenc /* [i * count + b] */, mkhe_ct* const* out);
 
 /* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
  * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call

@@ -363,6 +363,13 @@ class DeviceSampler {
         if (counter_ == ~0ull) throw Error("DeviceSampler: the 64-bit call counter is exhausted -- use a fresh key");
         return counter_++;
     }
+    // two consecutive nonces for ONE mkhe_refresh_share call (mask, encryption): the first of the pair
+    uint64_t NextNoncePair() {
+        std::lock_guard<std::mutex> g(m_);
+        if (counter_ >= ~0ull - 1) throw Error("DeviceSampler: the 64-bit call counter is exhausted -- use a fresh key");
+        counter_ += 2;
+        return counter_ - 2;
+    }
     uint64_t Counter() const { return counter_; }
     const uint32_t* Key() const { return key_; }
     const std::vector<uint64_t> cdt;
@@ -479,6 +486,76 @@ class Decryptor {
         }
         check(mkhe_decrypt(params.ctx, ct.h, sks.data(), dev_pt_out));
     }
+    Parameters& params;
+};
+
+// What one party publishes in a collective refresh (include/mkhe.h, "collective refresh") of `count` ciphertexts: Share, the MASKED products
+// c_id * s_id + M at levelIn, and Reenc, `count` ciphertexts over the party's id alone at levelOut that encrypt -M.  Both travel between parties
+// (Share.Value.download / upload, Ciphertext::download / upload).
+struct RefreshShare {
+    RefreshShare(Parameters& p, const std::string& id, int levelIn, int levelOut, int count = 1) : ID(id), LevelOut(levelOut), Share(p, id, levelIn, count) {
+        for (int b = 0; b < count; ++b) Reenc.push_back(std::make_shared<Ciphertext>(p, IDSet{id}, levelOut, false));
+    }
+    std::string ID;
+    int LevelOut;
+    DecryptionShare Share;
+    std::vector<std::shared_ptr<Ciphertext>> Reenc;
+};
+
+// The collective refresh between parties: ShareNew (each party, on its own keys and its own DeviceSampler) and MergeNew (anyone) give a ciphertext of
+// the same message over the same parties at levelOut.  The caller chooses maskBits: maskBits minus the bit size of the message is the statistical
+// hiding it gets, and parties * 2^(maskBits-1) plus the message must stay below Q_level / 2 (the Python mirror's Refresher.MaxMaskBits).
+class Refresher {
+  public:
+    explicit Refresher(Parameters& p) : params(p) {}
+    // maskBits = 1 .. 120; 0 (no mask) is for tests only: such a share reveals sk.  Two nonces of `sampler` serve the call.
+    std::shared_ptr<RefreshShare> ShareBatch(const std::vector<const Ciphertext*>& cts, const SecretKey& sk, const PublicKey& pk, int maskBits,
+                                             DeviceSampler& sampler, int levelOut = -1) {
+        if (cts.empty()) throw Error("Cannot RefreshShare: no ciphertext");
+        if (sk.ID != pk.ID) throw Error("Cannot RefreshShare: sk and pk belong to different parties");
+        if (maskBits < 0 || maskBits > 120) throw Error("Cannot RefreshShare: maskBits must be 0 .. 120");
+        if (levelOut < 0) levelOut = params.MaxLevel();
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        auto out = std::make_shared<RefreshShare>(params, sk.ID, cts[0]->Level(), levelOut, (int)cts.size());
+        std::vector<mkhe_ct*> re;
+        for (auto& c : out->Reenc) re.push_back(c->h);
+        const uint64_t nonce = sampler.NextNoncePair();
+        check(mkhe_refresh_share(params.ctx, (int)cts.size(), in.data(), slots.data(), sk.Value.d, pk.Value.d, sampler.Key(), nonce, nonce + 1, maskBits,
+                                 sampler.cdt.data(), (int)sampler.cdt.size(), out->Share.Value.d, re.data()));
+        return out;
+    }
+    std::shared_ptr<RefreshShare> ShareNew(const Ciphertext& ct, const SecretKey& sk, const PublicKey& pk, int maskBits, DeviceSampler& sampler, int levelOut = -1) {
+        return ShareBatch({&ct}, sk, pk, maskBits, sampler, levelOut);
+    }
+    // one RefreshShare of count cts.size() per party, in any order, for ciphertexts over the same ids at one level -> the refreshed ciphertexts
+    std::vector<std::shared_ptr<Ciphertext>> MergeBatch(const std::vector<const Ciphertext*>& cts, const std::vector<const RefreshShare*>& shares) {
+        if (cts.empty()) throw Error("Cannot RefreshMerge: no ciphertext");
+        std::vector<const mkhe_ct*> in;
+        for (auto* ct : cts) in.push_back(ct->h);
+        std::vector<const void*> ordered;
+        std::vector<const mkhe_ct*> re;
+        int levelOut = params.MaxLevel();
+        for (auto& id : cts[0]->ids) {
+            const RefreshShare* found = nullptr;
+            for (auto* sh : shares)
+                if (sh->ID == id) { if (found) throw Error("Cannot MergeShares: two shares of one party"); found = sh; }
+            if (!found) throw Error("Cannot MergeShares: the share of a party is missing");
+            if (found->Share.Level != cts[0]->Level() || found->Share.Count != (int)cts.size()) throw Error("Cannot MergeShares: a share is at another level or for another batch size");
+            if (!ordered.empty() && found->LevelOut != levelOut) throw Error("Cannot RefreshMerge: the shares are for different output levels");
+            levelOut = found->LevelOut;
+            ordered.push_back(found->Share.Value.d);
+            for (auto& c : found->Reenc) re.push_back(c->h);
+        }
+        if (shares.size() != ordered.size()) throw Error("Cannot MergeShares: a share of a party the ciphertext does not have");
+        std::vector<std::shared_ptr<Ciphertext>> outs;
+        std::vector<mkhe_ct*> oh;
+        for (size_t b = 0; b < cts.size(); ++b) { outs.push_back(std::make_shared<Ciphertext>(params, cts[0]->IDSet_(), levelOut, false)); oh.push_back(outs.back()->h); }
+        check(mkhe_refresh_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), re.data(), oh.data()));
+        return outs;
+    }
+    std::shared_ptr<Ciphertext> MergeNew(const Ciphertext& ct, const std::vector<const RefreshShare*>& shares) { return MergeBatch({&ct}, shares)[0]; }
     Parameters& params;
 };
 }  // namespace mkrlwe

@@ -121,6 +121,8 @@ SIGNATURES = {
     "mkhe_decrypt": (C.c_int, [vp, vp, vpp, vp]),
     "mkhe_decrypt_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, u32p, C.c_uint64, C.c_int, vp]),
     "mkhe_decrypt_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vp]),
+    "mkhe_refresh_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, vp, u32p, C.c_uint64, C.c_uint64, C.c_int, u64p, C.c_int, vp, vpp]),
+    "mkhe_refresh_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp, vpp]),
     "mkhe_ckks_embed": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_project": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_scale_up": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),

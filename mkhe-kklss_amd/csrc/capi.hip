@@ -703,16 +703,17 @@ int mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const 
 }
 // device-side sampling: the checks the two calls share.  A call refused here has enqueued nothing and leaves the context (and a capture in
 // progress) as it was.  The key is never quoted.
+static void smp_table_ok(const char* what, const uint64_t* cdt, int ncdt) {
+    if (!cdt) throw Error(std::string(what) + ": null table");
+    if (ncdt < 2 || ncdt > SMP_MAX_CDT || (ncdt & 1)) throw Error(std::string(what) + ": ncdt must be even and 2 .. 64");
+    for (int t = 1; t < ncdt; ++t) if (cdt[t] <= cdt[t - 1]) throw Error(std::string(what) + ": the thresholds of the table must be strictly increasing");
+}
 static Context* smp_need(mkhe_ctx* ctx, const char* what, const uint32_t* key, bool table, const uint64_t* cdt, int ncdt) {
     if (!ctx) throw Error(std::string(what) + ": null context");
     Context* c = need(ctx);
     g_last_ctx = nullptr;
     if (!key) throw Error(std::string(what) + ": null key");
-    if (table) {
-        if (!cdt) throw Error(std::string(what) + ": null table");
-        if (ncdt < 2 || ncdt > SMP_MAX_CDT || (ncdt & 1)) throw Error(std::string(what) + ": ncdt must be even and 2 .. 64");
-        for (int t = 1; t < ncdt; ++t) if (cdt[t] <= cdt[t - 1]) throw Error(std::string(what) + ": the thresholds of the table must be strictly increasing");
-    }
+    if (table) smp_table_ok(what, cdt, ncdt);
     if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(c->stream, &cs);
@@ -825,6 +826,104 @@ int mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int n
         g_last_ctx = c;
         auto i = ct_list(ctx, in, count, "mkhe_decrypt_merge");
         c->decrypt_merge(i, sh, (u64*)dev_pt_out);
+    })
+}
+// collective refresh: the checks the two calls share, under the rules of distributed decryption; why_capture closes the capture message
+static Context* rf_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const char* why_capture) {
+    if (!ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    if (!in) throw Error(std::string(what) + ": null argument");
+    for (int b = 0; b < count; ++b) {
+        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
+        if (in[b]->c.limbs != in[0]->c.limbs) throw Error(std::string(what) + ": every ciphertext must be at the same level");
+    }
+    if (c->is_bfv()) throw Error(std::string(what) + ": not available on a BFV context (a mask mod T is another protocol)");
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (" + why_capture + ")");
+    return c;
+}
+// the outputs of a refresh call: present, distinct, none of them an input
+static void rf_outputs(const char* what, int count, const mkhe_ct* const* in, int nin, mkhe_ct* const* out) {
+    for (int b = 0; b < count; ++b) {
+        if (!out[b]) throw Error(std::string(what) + ": null output in the batch");
+        for (int k = 0; k < b; ++k) if (out[k] == out[b] || out[k]->c.d == out[b]->c.d) throw Error(std::string(what) + ": the outputs of a batch must be distinct");
+        for (int k = 0; k < nin; ++k) if (in[k] == out[b] || in[k]->c.d == out[b]->c.d) throw Error(std::string(what) + ": an output aliases an input");
+    }
+}
+int mkhe_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk, const uint32_t key[8],
+                       uint64_t nonce_mask, uint64_t nonce_enc, int mask_bits, const uint64_t* cdt, int ncdt, void* dev_shares, mkhe_ct* const* reenc) {
+    MKHE_TRY({
+        const char* what = "mkhe_refresh_share";
+        if (mask_bits < 0 || mask_bits > RF_MAX_BITS) throw Error("mkhe_refresh_share: mask_bits must be 0 .. 120");
+        if (!key) throw Error("mkhe_refresh_share: null key");                  // (mask_bits = 0 reads no mask stream, the encryption still draws its samples)
+        if (mask_bits > 0 && nonce_mask == nonce_enc) throw Error("mkhe_refresh_share: nonce_mask and nonce_enc must differ (the mask and the encryption would share streams)");
+        Context* c = rf_need(ctx, what, count, in, "a replay would repeat the keystream");
+        if (!slots || !dev_sk || !dev_pk || !dev_shares || !reenc) throw Error("mkhe_refresh_share: null argument");
+        smp_table_ok(what, cdt, ncdt);
+        need_aligned(dev_sk, what); need_aligned(dev_pk, what); need_aligned(dev_shares, what);
+        for (int b = 0; b < count; ++b)
+            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_refresh_share: slot out of range (party slots are 1 .. n)");
+        rf_outputs(what, count, in, count, reenc);
+        const int lout = reenc[0]->c.limbs;
+        if (lout < 1 || lout > c->nq) throw Error("mkhe_refresh_share: the limbs of reenc are out of range");
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            const Ct& o = reenc[b]->c;
+            if (o.n != 1 || o.ids[0] != in[b]->c.ids[slots[b] - 1]) throw Error("mkhe_refresh_share: every reenc must be a ciphertext over exactly the id at the slot of its input");
+            if (o.limbs != lout) throw Error("mkhe_refresh_share: every reenc must have the same number of limbs");
+            d[b] = o.d;
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, what);
+        ct_list_out(ctx, reenc, count, what);
+        c->refresh_share(i, slots, (const u64*)dev_sk, (const u64*)dev_pk, key, nonce_mask, nonce_enc, mask_bits, cdt, ncdt, (u64*)dev_shares, lout, d.data());
+    })
+}
+int mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, const mkhe_ct* const* reenc,
+                       mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_refresh_merge";
+        Context* c = rf_need(ctx, what, count, in, "the call allocates and uploads");
+        if (!out) throw Error("mkhe_refresh_merge: null argument");
+        for (int b = 0; b < count; ++b)
+            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_refresh_merge: every ciphertext must be over the same ids");
+        if (nshares != in[0]->c.n) throw Error("mkhe_refresh_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+        if (nshares > 0 && (!dev_shares || !reenc)) throw Error("mkhe_refresh_merge: null argument");
+        rf_outputs(what, count, in, count, out);
+        const int lout = out[0]->c.limbs;
+        if (lout < 1 || lout > c->nq) throw Error("mkhe_refresh_merge: the limbs of out are out of range");
+        std::vector<const u64*> sh(nshares);
+        std::vector<const u64*> re((size_t)nshares * count);
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            if (out[b]->c.ids != in[0]->c.ids) throw Error("mkhe_refresh_merge: every out must be over the ids of the inputs");
+            if (out[b]->c.limbs != lout) throw Error("mkhe_refresh_merge: every out must have the same number of limbs");
+            d[b] = out[b]->c.d;
+        }
+        for (int i = 0; i < nshares; ++i) {
+            if (!dev_shares[i]) throw Error("mkhe_refresh_merge: null share in the per-party list");
+            need_aligned(dev_shares[i], what);
+            sh[i] = (const u64*)dev_shares[i];
+            for (int b = 0; b < count; ++b) {
+                const mkhe_ct* r = reenc[(size_t)i * count + b];
+                if (!r) throw Error("mkhe_refresh_merge: null reenc in the list");
+                if (r->c.n != 1 || r->c.ids[0] != in[0]->c.ids[i]) throw Error("mkhe_refresh_merge: reenc[i * count + b] must be a ciphertext over exactly the id at slot 1 + i");
+                if (r->c.limbs != lout) throw Error("mkhe_refresh_merge: every reenc must have the limbs of out");
+                for (int k = 0; k < count; ++k) if (out[k] == r || out[k]->c.d == r->c.d) throw Error("mkhe_refresh_merge: an output aliases an input");
+                re[(size_t)i * count + b] = r->c.d;
+            }
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, what);
+        if (nshares > 0) ct_list(ctx, reenc, nshares * count, what);
+        ct_list_out(ctx, out, count, what);
+        c->refresh_merge(i, sh, re, lout, d.data());
     })
 }
 

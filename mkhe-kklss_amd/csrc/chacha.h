@@ -1,5 +1,5 @@
 // chacha.h -- the quarter round of the ChaCha20 block function (RFC 8439 section 2.1), shared by the kernels that expand the keystream of
-// include/mkhe.h ("device-side sampling"): small_sample_kernel (encdec_kernels.hip) and share_finish_kernel (decshare_kernels.hip).
+// include/mkhe.h ("device-side sampling"): small_sample_kernel (encdec_kernels.hip), share_finish_kernel (decshare_kernels.hip) and refresh_finish_kernel (refresh_kernels.hip).
 #pragma once
 #include "modarith.h"
 

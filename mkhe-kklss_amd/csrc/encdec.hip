@@ -11,6 +11,7 @@
 // ChaCha20 keystream (small_sample_kernel); either way they are wiped from the device scratch behind their last use, and so is everything
 // computed from u alone.
 #include "engine.h"
+#include "host_modarith.h"
 
 namespace mkhe {
 
@@ -170,11 +171,9 @@ void Context::decrypt(const Ct& ct, const u64* const* sks, u64* pt_out) {
 // for count ciphertexts -- the forward NTT gathers polynomial slots[b] of every input into w [count][L][N], decrypt_mac (k = 1) and the inverse
 // NTT run in place, share_finish_kernel adds e_b and writes the caller's buffer.  The unflooded product c_i * s_i gives the key away (c_i is
 // public): it is wiped from w behind the finish kernel.
-void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares) {
-    if (masked_) throw Error("mkhe_decrypt_share: not available on a context that owns a subset of the moduli");
+void Context::share_product(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, u64* w) {
     const int count = (int)ins.size(), L = ins[0]->limbs;
     const size_t pw = (size_t)L * N;
-    u64* w = scratch(ed_w_, (size_t)count * pw);
     scratch(ed_tab_, 2 * (size_t)count);
     std::vector<const u64*> c(count), s(count, sk);
     for (int b = 0; b < count; ++b) c[b] = w + (size_t)b * pw;
@@ -193,6 +192,14 @@ void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots,
         launch_decrypt_mac(count, 1, w, ct, st, d_mods, L, N, s_);
     }
     ntt(w, w, count, L, 0, true, false);
+}
+
+void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares) {
+    if (masked_) throw Error("mkhe_decrypt_share: not available on a context that owns a subset of the moduli");
+    const int count = (int)ins.size(), L = ins[0]->limbs;
+    const size_t pw = (size_t)L * N;
+    u64* w = scratch(ed_w_, (size_t)count * pw);
+    share_product(ins, slots, sk, w);
     ShareFloodArgs a;
     for (int i = 0; i < 8; ++i) a.key[i] = bits > 0 ? key[i] : 0;
     a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32); a.bits = bits;
@@ -217,6 +224,78 @@ void Context::decrypt_merge(const std::vector<const Ct*>& ins, const std::vector
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * N * L * count * (2.0 + (double)shares.size()));
         launch_share_merge(count, (int)shares.size(), pt, ct, st, d_mods, L, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+// ---- collective refresh.  The party side is the share chain with refresh_finish_kernel in the place of share_finish_kernel, then the chain of
+// encrypt_seeded on the plaintext -M that kernel left in the scratch.  ed_w_ holds, in this order, the work buffer of encrypt_core
+// [3][count][Lout][N], the plaintext [count][Lout][N] and the product [count][Lin][N]; ed_tab_ the two tables of the product and the outputs'.
+// Sized once, in front: a scratch that grows moves.  The product, the plaintext and the samples are wiped behind their last use.
+void Context::refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask,
+                            u64 nonce_enc, int bits, const u64* cdt, int ncdt, u64* shares, int lout, u64* const* outs) {
+    if (masked_) throw Error("mkhe_refresh_share: not available on a context that owns a subset of the moduli");
+    check_level(lout - 1);
+    const int count = (int)ins.size(), lin = ins[0]->limbs;
+    const size_t pin = (size_t)count * lin * N, pout = (size_t)count * lout * N, sn = (size_t)count * N;
+    u64* w = scratch(ed_w_, 4 * pout + pin);
+    u64 *pt = w + 3 * pout, *prod = pt + pout;
+    int32_t* small = reinterpret_cast<int32_t*>(scratch(ed_small_, 2 * sn));
+    scratch(ed_tab_, 3 * (size_t)count);
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 2 * (size_t)count);
+    share_product(ins, slots, sk, prod);
+    RefreshMaskArgs m;
+    for (int i = 0; i < 8; ++i) m.key[i] = bits > 0 ? key[i] : 0;
+    m.nonce_lo = (u32)nonce_mask; m.nonce_hi = (u32)(nonce_mask >> 32); m.bits = bits;
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (2.0 * lin + lout));
+        launch_refresh_finish(m, count, shares, prod, pt, d_mods, lin, lout, N, s_);
+    }
+    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&m);      // the runtime has copied the arguments
+    for (size_t i = 0; i < sizeof(m); ++i) p[i] = 0;
+    MKHE_HIP(hipMemsetAsync(prod, 0, pin * sizeof(u64), s_));
+    SmallSampleArgs a;
+    sample_args_fill(a, key, nonce_enc, 0, cdt, ncdt);
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
+        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * sn, N, s_);
+    }
+    sample_args_wipe(a);
+    encrypt_core(lout - 1, count, pk, pt, false, w, small, ot);             // wipes the samples and u * pk
+    MKHE_HIP(hipMemsetAsync(pt, 0, pout * sizeof(u64), s_));                // -M with the public share gives the product away
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
+                            u64* const* outs) {
+    if (masked_) throw Error("mkhe_refresh_merge: not available on a context that owns a subset of the moduli");
+    check_level(lout - 1);
+    const int count = (int)ins.size(), lin = ins[0]->limbs, k = (int)shares.size();
+    if (!d_rf_tab_) {
+        std::vector<u64> t(2 * (size_t)nq * nq, 0);
+        for (int j = 0; j < nq; ++j) {
+            u64 prod = 1;
+            for (int i = 0; i < nq; ++i) {
+                t[(size_t)i * nq + j] = to_mont(moduli[i] % moduli[j], moduli[j]);
+                prod = mulmod(prod, moduli[i] % moduli[j], moduli[j]);
+                t[(size_t)(nq + i) * nq + j] = prod;
+            }
+        }
+        garner_table();
+        d_rf_tab_ = mem_.upload(t);
+    }
+    RefreshMergeArgs a;
+    a.garner = garner_table(); a.qmont = d_rf_tab_; a.qprod = d_rf_tab_ + (size_t)nq * nq;
+    a.dig = scratch(rf_dig_, (size_t)count * lin * N);
+    a.mods = d_mods; a.nq = nq; a.lin = lin; a.lout = lout; a.nshares = k; a.count = count; a.N = N;
+    std::vector<const u64*> c(count);
+    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
+    scratch(ed_tab_, 2 * (size_t)count + (size_t)k + reenc.size());
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0), ct = ed_table(c, (size_t)count);
+    const EdTable st = ed_table(shares, 2 * (size_t)count), rt = ed_table(reenc, 2 * (size_t)count + (size_t)k);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (lin * (1.0 + k) + (lout > lin ? 2.0 * lin : 0.0) + lout * (1.0 + 3.0 * k)));
+        launch_refresh_merge(a, ot, ct, st, rt, s_);
     }
     MKHE_HIP(hipGetLastError());
 }

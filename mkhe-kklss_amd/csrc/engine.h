@@ -20,6 +20,7 @@
 #include "keygen_kernels.h"
 #include "encdec_kernels.h"
 #include "decshare_kernels.h"
+#include "refresh_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -280,6 +281,15 @@ class Context {
     void decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares);
     // pt [count][limbs][N] <- ins[b] polynomial 0 + sum_i shares[i][b], canonical; ins are over the same ids (shares.size() of them) at one level
     void decrypt_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* pt);
+    // collective refresh (include/mkhe.h; refresh_kernels.h): shares [count][Lin][N] <- the product of decrypt_share + M_b, M_b = kind 3 of the
+    // keystream (bits wide; 0: none, key unread) on the streams 2 b, 2 b + 1 of (key, nonce_mask); outs[b] [2][lout][N] <- encrypt_seeded of the
+    // plaintext -M_b at level lout - 1 under (key, nonce_enc).  The caller (capi.hip) has checked slots, levels, shapes and the capture.
+    void refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask, u64 nonce_enc,
+                       int bits, const u64* cdt, int ncdt, u64* shares, int lout, u64* const* outs);
+    // outs[b] [1 + k][lout][N] <- the exact centred lift of ins[b] polynomial 0 + sum_i shares[i][b] from Q_l to the first lout moduli, plus
+    // polynomial 0 of reenc[i * count + b]; polynomial 1 + i = polynomial 1 of reenc[i * count + b].  Builds its tables at the first use.
+    void refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
+                       u64* const* outs);
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).
@@ -402,6 +412,11 @@ class Context {
     Scratch ed_w_, ed_small_, ed_tab_;                       // (int32 samples in ed_small_, const u64* entries in ed_tab_: sized in 8-byte words and cast at the use)
     EdTable ed_table(const std::vector<const u64*>& v, size_t tab_offset);
     void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
+    // the product chain of a share: w [count][L][N] <- InvNTT(NTT(polynomial slots[b] of ins[b]) * sk); stages its tables at entries 0 .. 2 count of ed_tab_
+    void share_product(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, u64* w);
+    // collective refresh: MForm(q_i mod q_j) and (q_0 .. q_l) mod q_j, [nq][nq] each in one block, built at the first merge; the digits of R
+    u64* d_rf_tab_ = nullptr;
+    Scratch rf_dig_;
     // Encrypt behind "the samples are on the device": small = int32 [count][3][N] + the count rows of u gathered behind it, w = [3][count][L][N];
     // small_expand .. encrypt_finish and the three wipes
     void encrypt_core(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, u64* w, int32_t* small, const EdTable& ot);

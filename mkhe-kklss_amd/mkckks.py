@@ -1145,3 +1145,32 @@ class Decryptor(mkrlwe.Decryptor):
 
 def NewDecryptor(params, encoder="host"):
     return Decryptor(params, encoder)
+
+
+class Refresher(mkrlwe.Refresher):
+    """The collective refresh of mkrlwe.Refresher on mkckks ciphertexts: the result keeps the input's Scale (the lift is exact and the
+    re-encryptions cancel the masks, so the message and its scale are untouched; only fresh encryption noise is added: RefreshSlotBound)."""
+
+    def _out(self, like, count, level_out):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, like.ids, level_out, count, Scale=like.ScalingFactor())
+
+    def MaxMaskBits(self, parties, level, scale, max_abs_slot=1.0):
+        """mkrlwe.Refresher.MaxMaskBits for ciphertexts at `level` whose slots are at most max_abs_slot in modulus: msg_bits =
+        ceil(log2(scale * max_abs_slot)) + 1 -- a coefficient of the embedding is at most max|z| * scale in magnitude, and one more bit is
+        for the noise."""
+        q = 1
+        for m in self.params.Q[: level + 1]:
+            q *= int(m)
+        msg_bits = int(math.ceil(math.log2(float(scale) * float(max_abs_slot)))) + 1
+        return mkrlwe.Refresher.MaxMaskBits(q, parties, msg_bits)
+
+    def RefreshSlotBound(self, parties, scale, sigma=3.2):
+        """how far a refresh moves a slot, at most: N * parties * (2N + 1) * floor(6 sigma) / scale.  Each party's fresh encryption adds
+        |u e_pk + e0 + e1 s| <= (2N + 1) floor(6 sigma) per coefficient (u and s ternary, the table truncated at floor(6 sigma)); a slot moves
+        by at most N times the coefficient error over the scale."""
+        N = self.params.N()
+        return N * int(parties) * (2 * N + 1) * int(6 * float(sigma)) / float(scale)
+
+
+def NewRefresher(params):
+    return Refresher(params)

@@ -679,6 +679,15 @@ class DeviceSampler:
         """(key, nonce) for ONE mkhe_decrypt_share call: the same counter as encrypt_args, so that no nonce serves two calls of either kind"""
         return self._key, self._next_nonce()
 
+    def refresh_args(self):
+        """(key, nonce_mask, nonce_enc) for ONE mkhe_refresh_share call: two values of the same counter, taken under the lock"""
+        with self._lock:
+            if self._counter >= (1 << 64) - 2:
+                raise MkheError("DeviceSampler: the 64-bit call counter is exhausted -- use a fresh key")
+            n = self._counter
+            self._counter += 2
+        return self._key, n, n + 1
+
 
 def _s32(a, shape):
     a = np.ascontiguousarray(a, dtype=np.int32)
@@ -1087,3 +1096,125 @@ class Decryptor:
 
 def NewDecryptor(params):
     return Decryptor(params)
+
+
+# ---- collective refresh (include/mkhe.h, "collective refresh")
+class RefreshShare:
+    """What one party publishes in a collective refresh of `count` ciphertexts: .Share, a DecryptionShare at level_in that carries the MASKED
+    products c_id * s_id + M, and .Reenc, `count` ciphertexts over the party's id alone at level_out that encrypt -M.  Both travel:
+    download() gives (share array, [reenc arrays]), upload() takes them on the receiving side."""
+
+    def __init__(self, params, id, level_in, level_out, count=1):
+        self.ID, self.count, self._level_out = id, int(count), int(level_out)
+        self.Share = DecryptionShare(params, id, level_in, count)
+        self.Reenc = batch_ciphertexts(Ciphertext, params, [id], level_out, self.count)
+
+    def Level(self):
+        """the level of the ciphertexts the share was made for"""
+        return self.Share.Level()
+
+    def LevelOut(self):
+        return self._level_out
+
+    def download(self):
+        return self.Share.download(), [c.download() for c in self.Reenc]
+
+    def upload(self, host):
+        share, reenc = host
+        if len(reenc) != self.count:
+            raise MkheError("RefreshShare: expected %d re-encryptions, got %d" % (self.count, len(reenc)))
+        self.Share.upload(share)
+        for c, h in zip(self.Reenc, reenc):
+            c.upload(h)
+        return self
+
+
+class Refresher:
+    """The collective refresh between parties: ShareNew (each party, on its own keys and its own DeviceSampler) and MergeNew (anyone) give a
+    ciphertext of the same message over the same parties at level_out (default: the maximum level).  The caller chooses mask_bits
+    (MaxMaskBits): mask_bits minus the bit size of the message is the statistical hiding it gets."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def _out(self, like, count, level_out):
+        """the `count` outputs of a merge over the ids of `like`"""
+        return batch_ciphertexts(Ciphertext, self.params, like.ids, level_out, count)
+
+    @staticmethod
+    def MaxMaskBits(q_product, parties, msg_bits):
+        """the largest bits <= 120 with parties * 2^(bits-1) + 2^msg_bits <= (Q - 1) / 2: the lift of a merge cannot wrap.  Pure; raises when
+        not even one bit fits."""
+        q_product, parties, msg_bits = int(q_product), int(parties), int(msg_bits)
+        if parties < 1 or msg_bits < 0:
+            raise MkheError("MaxMaskBits: parties must be positive and msg_bits non-negative")
+        room = (q_product - 1) // 2 - (1 << msg_bits)
+        bits = 0
+        while bits < 120 and (parties << bits) <= room:         # bits + 1 fits: parties * 2^((bits+1)-1) <= room
+            bits += 1
+        if bits == 0:
+            raise MkheError("MaxMaskBits: no mask fits: %d parties and a message of %d bits leave no room below Q / 2" % (parties, msg_bits))
+        return bits
+
+    def ShareBatch(self, cts, sk, pk, mask_bits, sampler, level_out=None):
+        """The refresh shares of the party of (sk, pk) for B ciphertexts at one level (their id sets may differ) as ONE engine call
+        (mkhe_refresh_share) -> one RefreshShare of count B.  mask_bits = 1 .. 120; 0 (no mask) is for TESTS ONLY: such a share reveals sk.
+        Two nonces of `sampler` (a DeviceSampler) serve the call: one for the mask, one for the encryption."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot RefreshShare: no ciphertext")
+        if sk.ID != pk.ID:
+            raise MkheError("Cannot RefreshShare: sk and pk belong to different parties")
+        level = cts[0].Level()
+        level_out = self.params.MaxLevel() if level_out is None else int(level_out)
+        if not 0 <= level_out <= self.params.MaxLevel():
+            raise MkheError("Cannot RefreshShare: level_out %d out of range" % level_out)
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot RefreshShare: the ciphertext has no component for the id of sk")
+            if ct.Level() != level:
+                raise MkheError("Cannot RefreshShare: the ciphertexts of one call must be at the same level")
+        if not isinstance(mask_bits, int) or not 0 <= mask_bits <= 120:
+            raise MkheError("Cannot RefreshShare: mask_bits must be an integer 0 .. 120")
+        if not isinstance(sampler, DeviceSampler):
+            raise MkheError("Cannot RefreshShare: mask and encryption samples are drawn on the device -- pass a DeviceSampler")
+        key, nonce_mask, nonce_enc = sampler.refresh_args()
+        out = RefreshShare(self.params, sk.ID, level, level_out, len(cts))
+        slots = (C.c_int * len(cts))(*[ct.slot(sk.ID) for ct in cts])
+        check(lib().mkhe_refresh_share(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), pk.Value.devptr(),
+                                       key, nonce_mask, nonce_enc, mask_bits, sampler._cdt, len(sampler.cdt), out.Share.Value.devptr(),
+                                       handle_array([c.h for c in out.Reenc])))
+        return out
+
+    def ShareNew(self, ct, sk, pk, mask_bits, sampler, level_out=None):
+        """ShareBatch of one ciphertext"""
+        return self.ShareBatch([ct], sk, pk, mask_bits, sampler, level_out)
+
+    def MergeBatch(self, cts, shares):
+        """The refreshed ciphertexts of B ciphertexts over the same ids at one level: one RefreshShare of count B per party, in any order
+        (ordering and errors: order_shares) -> B ciphertexts over the same ids at the shares' level_out.  ONE engine call (mkhe_refresh_merge)."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot RefreshMerge: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids or ct.Level() != cts[0].Level():
+                raise MkheError("Cannot RefreshMerge: the ciphertexts of one call must be over the same ids and at the same level")
+        ordered = order_shares(cts[0].ids, cts[0].Level(), len(cts), shares)
+        levels = {sh.LevelOut() for sh in ordered}
+        if len(levels) > 1:
+            raise MkheError("Cannot RefreshMerge: the shares are for different output levels %r" % sorted(levels))
+        level_out = levels.pop() if levels else self.params.MaxLevel()
+        outs = self._out(cts[0], len(cts), level_out)
+        reenc = [c.h for sh in ordered for c in sh.Reenc]
+        check(lib().mkhe_refresh_merge(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), len(ordered),
+                                       handle_array([sh.Share.Value.devptr() for sh in ordered]), handle_array(reenc) if reenc else None,
+                                       handle_array([c.h for c in outs])))
+        return outs
+
+    def MergeNew(self, ct, shares):
+        """MergeBatch of one ciphertext -> the refreshed ciphertext"""
+        return self.MergeBatch([ct], shares)[0]
+
+
+def NewRefresher(params):
+    return Refresher(params)
