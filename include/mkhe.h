@@ -559,7 +559,7 @@ int  mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int 
  * engine does not choose bits.
  *
  * Rules: those of distributed decryption, on mkrlwe / CKKS contexts that own every modulus.  Refused: BFV contexts (a mask mod T is another
- * protocol); contexts with mkhe_ctx_set_owned; both calls between mkhe_capture_begin and mkhe_capture_end (the share would repeat its
+ * protocol: "collective refresh for MK-BFV" below); contexts with mkhe_ctx_set_owned; both calls between mkhe_capture_begin and mkhe_capture_end (the share would repeat its
  * keystream, the merge builds tables at its first use); mask_bits outside 0 .. 120; a slot out of range; inputs at different levels; in the
  * merge different ids, or a reenc that is not over exactly the id of its slot or has other than Lout limbs; an output that aliases an input; a
  * NULL key (mask_bits = 0 reads no mask stream, but the encryption draws its samples from the key all the same); a misaligned buffer; count
@@ -586,6 +586,63 @@ int  mkhe_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, cons
  * at the first call. */
 int  mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares,
                         const mkhe_ct* const* reenc /* [i * count + b] */, mkhe_ct* const* out);
+/* ---- collective refresh for MK-BFV: masked shares mod T, a wide flood, re-encryption, rounding -------------------------------------------
+ * Every mkbfv ciphertext lives at the maximum level: depth is bounded by noise alone, and after a few MulRelin on a small ring the message is
+ * gone.  The parties that publish decryption shares can reset the noise to that of a fresh encryption instead, and nobody sees the message.
+ * Unlike the refresh above, which only moves a ciphertext up the modulus chain, this one REMOVES noise: the merge rounds to Z_T and scales up
+ * again.  Every party masks its share with up(A_i), A_i secret and uniform mod T, floods it with e_i, and encrypts up(-A_i) under its own public
+ * key; anyone adds c_0 and the shares, rounds the sum down to Z_T -- which gives (m + sum_i A_i) mod T, uniform -- scales that up and adds the
+ * re-encryptions, which cancel the masks.
+ *
+ * Notation.  BFV context with Q = q_0 .. q_(nQ-1), plaintext modulus T, h = floor(T / 2), under the preconditions of the "BFV batch encoder"
+ * section below (T prime, T = 1 mod 2N, T < 2^32, T not a prime of Q); the scaling tables are the encoder's.
+ *     up(x)   = mkhe_bfv_scale_up of one coefficient:   floor((Q x + h) / T) mod q_l          for x in [0, T)
+ *     down(R) = mkhe_bfv_scale_down:                    floor((T R + floor(Q / 2)) / Q) mod T for R in [0, Q)
+ * ct = (c_0, c_1 .. c_k) over ids, nQ limbs, coefficient domain.
+ *
+ * Two more kinds of the keystream, under the block and word rule of kinds 0-3 (coefficient n of a stream takes block n / 8, words 2 (n % 8) and
+ * 2 (n % 8) + 1; every stream yields 64 bits per coefficient).  Under (key, nonce_mask), item b of a call owns S = 2 + W consecutive streams
+ * starting at b S, W = ceil(flood_bits / 64) (W = 0 for flood_bits = 0).
+ *   Kind 4, uniform mod T (the mask): lo from stream b S, hi from stream b S + 1; with r = hi 2^64 + lo, A[n] = (r T) >> 128.  A is in [0, T) and
+ *     uniform to within T / 2^128; no division, no sample-dependent branch.
+ *   Kind 5, wide uniform (the flood): v_w = the 64-bit value of stream b S + 2 + w, w < W, the top word masked to its low flood_bits - 64 (W - 1)
+ *     bits; F = sum_w v_w 2^(64 w), e[n] = F - 2^(flood_bits-1), uniform on [-2^(flood_bits-1), 2^(flood_bits-1)).  flood_bits = 0: e = 0, no
+ *     flood stream is read.  (mkhe_decrypt_share keeps kind 2 and its 62 bits: the noise of a ciphertext worth refreshing has hundreds of bits
+ *     and depends on the keys, so the flood here is as wide as the decryption margin allows.)
+ *
+ * Why it is right.  up(x) = Q x / T + eps with |eps| <= 1/2, so R = c_0 + sum_i share_i = (Q / T)(m + sum_i A_i) + delta mod Q with
+ * delta = e_ct + sum_i e_i + sum eps, e_ct the noise of the input.  down gives w = (m + sum_i A_i) mod T exactly as long as
+ *     |e_ct| + k 2^(flood_bits-1) + k / 2 < Q / (2 T),
+ * and the output then decrypts to (Q / T) m plus the k fresh encryption noises plus at most (k + 1) / 2.  The engine cannot check the
+ * condition and does not choose flood_bits: flood_bits minus the bit size of e_ct is the statistical hiding of the noise the caller gets.
+ *
+ * Rules: those of mkhe_refresh_share / mkhe_refresh_merge.  Refused: a context that is not a BFV context, or one with mkhe_ctx_set_owned; T
+ * outside the encoder's preconditions; both calls between mkhe_capture_begin and mkhe_capture_end; mask other than 0 or 1; flood_bits < 0,
+ * > 1024 or > bitlen(Q div 2T) - 1 (such a flood alone destroys the message); a slot out of range; an input, reenc or out that does not have nQ
+ * limbs; in the merge inputs over different ids, or a reenc that is not over exactly the id of its slot; an output that aliases an input; a
+ * NULL key (the encryption draws its samples from it whatever mask and flood_bits are); a misaligned buffer; count outside 1 .. 65535;
+ * nonce_mask == nonce_enc when mask = 1 or flood_bits > 0.  Each of the two nonces obeys the one-call rule of the seeded calls.  Messages
+ * start with the function's name; a refused call has enqueued nothing and leaves the context usable. */
+/* Party side.  For item b, with c_slot the polynomial slots[b] of in[b], dev_shares = uint64[count][nQ][N]:
+ *     share[b][j][n] = (InvNTT(NTT(c_slot) * sk)[j][n] + up(A_b[n])[j] + (e_b[n] mod q_j)) mod q_j,   canonical.
+ * reenc[b] = a ciphertext over exactly the one id at slots[b] of in[b]: bit for bit what mkhe_encrypt_seeded(level = nQ - 1, count, dev_pk, pt, 0,
+ * key, nonce_enc, cdt, ncdt) writes for pt[b][j][n] = up((T - A_b[n]) mod T)[j] (encryption streams 3 b, 3 b + 1, 3 b + 2 of nonce_enc).
+ * mask is 1 in normal use; mask = 0 sets A = 0, reads no mask stream and is for tests only: with flood_bits = 0 such a share is PartialDecrypt's
+ * product and reveals the key.  A and e are formed in registers and never exist in memory; behind their last use the engine wipes from its
+ * scratch the unmasked product, the plaintext and the samples; the key travels in kernel arguments only.  count > 16 stages pointer tables,
+ * which synchronises. */
+int  mkhe_bfv_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk,
+                            const uint32_t key[8], uint64_t nonce_mask, uint64_t nonce_enc, int mask, int flood_bits,
+                            const uint64_t* cdt, int ncdt, void* dev_shares /* uint64[count][nQ][N] */, mkhe_ct* const* reenc);
+/* Anyone.  out[b] is over the ids of in[b]; all in[b] have the same ids; nshares = the number of parties, dev_shares[i] and
+ * reenc[i * count + b] those of the party at slot 1 + i.
+ *   1. R = (c_0 + sum_i share_i) mod Q: the residues mkhe_decrypt_merge gives.
+ *   2. w = down(R), in [0, T).
+ *   3. out_0[j] = (up(w)[j] + sum_i reenc_i.c0[j]) mod q_j for every j < nQ.
+ *   4. out_(1+i) = reenc_i.c1.
+ * Everything is canonical, and every limb of every component of out is written.  One streaming launch; w never reaches memory. */
+int  mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares,
+                            const mkhe_ct* const* reenc /* [i * count + b] */, mkhe_ct* const* out);
 
 /* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
  * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call

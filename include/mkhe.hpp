@@ -918,4 +918,61 @@ class Encoder {
     }
     Parameters& params;
 };
+
+// The collective refresh of MK-BFV between parties (include/mkhe.h, "collective refresh for MK-BFV"): ShareNew (each party, on its own keys and its
+// own DeviceSampler) and MergeNew (anyone) give a ciphertext of the same message over the same parties with the noise of a fresh encryption.  What
+// travels is mkrlwe::RefreshShare, with both levels the maximum level.  The caller chooses floodBits: floodBits minus the bit size of the
+// ciphertext's noise is the statistical hiding of that noise, and the noise plus parties * 2^(floodBits-1) must stay below Q / (2T) (the Python
+// mirror's Refresher.MaxFloodBits).  The mask is always on.
+class Refresher {
+  public:
+    explicit Refresher(Parameters& p) : params(p) {}
+    // floodBits = 0 .. 1024, at most bitlen(Q div 2T) - 1.  Two nonces of `sampler` serve the call.
+    std::shared_ptr<mkrlwe::RefreshShare> ShareBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const mkrlwe::SecretKey& sk, const mkrlwe::PublicKey& pk,
+                                                     int floodBits, mkrlwe::DeviceSampler& sampler) {
+        if (cts.empty()) throw Error("Cannot RefreshShare: no ciphertext");
+        if (sk.ID != pk.ID) throw Error("Cannot RefreshShare: sk and pk belong to different parties");
+        if (floodBits < 0 || floodBits > 1024) throw Error("Cannot RefreshShare: floodBits must be 0 .. 1024");
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        const int level = params.MaxLevel();
+        auto out = std::make_shared<mkrlwe::RefreshShare>(params, sk.ID, level, level, (int)cts.size());
+        std::vector<mkhe_ct*> re;
+        for (auto& c : out->Reenc) re.push_back(c->h);
+        const uint64_t nonce = sampler.NextNoncePair();
+        check(mkhe_bfv_refresh_share(params.ctx, (int)cts.size(), in.data(), slots.data(), sk.Value.d, pk.Value.d, sampler.Key(), nonce, nonce + 1, 1, floodBits,
+                                     sampler.cdt.data(), (int)sampler.cdt.size(), out->Share.Value.d, re.data()));
+        return out;
+    }
+    std::shared_ptr<mkrlwe::RefreshShare> ShareNew(const mkrlwe::Ciphertext& ct, const mkrlwe::SecretKey& sk, const mkrlwe::PublicKey& pk, int floodBits,
+                                                   mkrlwe::DeviceSampler& sampler) {
+        return ShareBatch({&ct}, sk, pk, floodBits, sampler);
+    }
+    // one RefreshShare of count cts.size() per party, in any order, for ciphertexts over the same ids -> the refreshed ciphertexts
+    std::vector<std::shared_ptr<Ciphertext>> MergeBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const std::vector<const mkrlwe::RefreshShare*>& shares) {
+        if (cts.empty()) throw Error("Cannot RefreshMerge: no ciphertext");
+        std::vector<const mkhe_ct*> in;
+        for (auto* ct : cts) in.push_back(ct->h);
+        std::vector<const void*> ordered;
+        std::vector<const mkhe_ct*> re;
+        for (auto& id : cts[0]->ids) {
+            const mkrlwe::RefreshShare* found = nullptr;
+            for (auto* sh : shares)
+                if (sh->ID == id) { if (found) throw Error("Cannot MergeShares: two shares of one party"); found = sh; }
+            if (!found) throw Error("Cannot MergeShares: the share of a party is missing");
+            if (found->Share.Count != (int)cts.size()) throw Error("Cannot MergeShares: a share is for another batch size");
+            ordered.push_back(found->Share.Value.d);
+            for (auto& c : found->Reenc) re.push_back(c->h);
+        }
+        if (shares.size() != ordered.size()) throw Error("Cannot MergeShares: a share of a party the ciphertext does not have");
+        std::vector<std::shared_ptr<Ciphertext>> outs;
+        std::vector<mkhe_ct*> oh;
+        for (size_t b = 0; b < cts.size(); ++b) { outs.push_back(std::make_shared<Ciphertext>(params, cts[0]->IDSet_(), false)); oh.push_back(outs.back()->h); }
+        check(mkhe_bfv_refresh_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), re.data(), oh.data()));
+        return outs;
+    }
+    std::shared_ptr<Ciphertext> MergeNew(const mkrlwe::Ciphertext& ct, const std::vector<const mkrlwe::RefreshShare*>& shares) { return MergeBatch({&ct}, shares)[0]; }
+    Parameters& params;
+};
 }  // namespace mkbfv

@@ -1,21 +1,11 @@
 // bfv_kernels.hip -- see bfv_kernels.h.
 #include "bfv_kernels.h"
+#include "bfv_arith.h"
 #include "tile_transform.h"
 
 namespace mkhe {
 
-// ---- arithmetic mod T < 2^32 on canonical residues
-__device__ __forceinline__ u32 bf_mul(u32 a, uint2 w, u32 T) {            // a * w.x mod T for any 32-bit a; w.y = floor(w.x 2^32 / T)
-    const u32 q = hi32((u64)a * w.y);
-    const u64 r = (u64)a * w.x - (u64)q * T;                              // in [0, 2T)
-    return (u32)(r >= T ? r - T : r);
-}
-__device__ __forceinline__ u32 bf_add(u32 a, u32 b, u32 T) { const u64 s = (u64)a + b; return (u32)(s >= T ? s - T : s); }
-__device__ __forceinline__ u32 bf_sub(u32 a, u32 b, u32 T) { return a >= b ? a - b : a - b + T; }
-// any 64-bit value mod T: hi * (2^32 mod T) + lo
-__device__ __forceinline__ u32 bf_reduce64(u64 a, const BfvT& t) {
-    return bf_add(bf_mul(hi32(a), uint2{t.c32, t.c32_s}, t.T), bf_mul(lo32(a), uint2{1u, t.one_s}, t.T), t.T);
-}
+// ---- arithmetic mod T and the scalings of one coefficient: bfv_arith.h
 // an int64 message value -> its residue in [0, T)
 __device__ __forceinline__ u32 bf_from_i64(i64 v, const BfvT& t) {
     const bool neg = v < 0;
@@ -24,18 +14,6 @@ __device__ __forceinline__ u32 bf_from_i64(i64 v, const BfvT& t) {
 }
 __device__ __forceinline__ i64 bf_centre(u32 r, const BfvT& t) { return r > t.half ? (i64)r - (i64)t.T : (i64)r; }
 
-// ---- scale_up / scale_down of one coefficient (bfv_kernels.h); pt, dig: the coefficient's column, limb stride N
-__device__ __forceinline__ void bf_scale_up_one(const BfvScale& sc, u32 m, u64* pt) {
-    const BfvT& t = sc.t;
-    const u32 r = bf_add(bf_mul(m, uint2{t.qmod, t.qmod_s}, t.T), t.half, t.T);
-    const bool neg = r > t.half;
-    const u64 mag = neg ? r - t.half : t.half - r;                        // |floor(T/2) - r| <= T
-    for (int l = 0; l < sc.limbs; ++l) {
-        const Mod md = sc.mods[l];
-        const u64 v = mont_mul(mag, sc.tinv_mont[l], md.q, md.ninv32);
-        pt[(long)l * sc.N] = (neg && v) ? md.q - v : v;
-    }
-}
 // the lift of one coefficient (bfv_kernels.h): limb l of MForm(centred m)
 __device__ __forceinline__ u64 bf_lift_limb(u32 m, const BfvT& t, const Mod& md) {
     const bool neg = m > t.half;
@@ -44,16 +22,6 @@ __device__ __forceinline__ u64 bf_lift_limb(u32 m, const BfvT& t, const Mod& md)
 }
 __device__ __forceinline__ void bf_lift_one(const BfvScale& sc, u32 m, u64* pt) {
     for (int l = 0; l < sc.limbs; ++l) pt[(long)l * sc.N] = bf_lift_limb(m, sc.t, sc.mods[l]);
-}
-__device__ __forceinline__ u32 bf_scale_down_one(const BfvScale& sc, const u64* x, u64* d) {
-    const BfvT& t = sc.t;
-    const int L = sc.limbs;
-    const long N = sc.N;
-    // the digits of r, r_j = T x_j + (q_j - 1) / 2 mod q_j
-    garner_digits([&](int j, const Mod& md) { return csub(mont_mul(x[j * N], sc.t_mont[j], md.q, md.ninv32) + (md.q >> 1), md.q); }, d, sc.garner, L, sc.mods, L, N);
-    u32 acc = bf_reduce64(d[(L - 1) * N], t);
-    for (int i = L - 2; i >= 0; --i) acc = bf_add(bf_mul(acc, sc.qlt[i], t.T), bf_reduce64(d[i * N], t), t.T);
-    return bf_mul(bf_sub(t.hq, acc, t.T), uint2{t.qinv, t.qinv_s}, t.T);
 }
 
 // what tile_transform.h needs to know about the NTT

@@ -1,0 +1,130 @@
+// bfv_refresh_kernels.hip -- see bfv_refresh_kernels.h.  No LDS, no scratch.
+#include "bfv_refresh_kernels.h"
+#include "bfv_arith.h"
+#include "chacha.h"
+#include "ed_access.h"
+
+namespace mkhe {
+
+// v mod q for ANY 64-bit v.  mont_mul(a, r1) reduces only a < 2^62, so the word is split: (v >> 32) 2^32 + (v mod 2^32), the high half times
+// c32 = MForm(2^32 mod q) (the same reduction with the constant folded in), the low half times r1.
+__device__ __forceinline__ u64 brf_reduce64(u64 v, u64 c32, const Mod& md) {
+    return csub(mont_mul(hi32(v), c32, md.q, md.ninv32) + mont_mul(lo32(v), md.r1, md.q, md.ninv32), md.q);
+}
+
+// ---- bfv_refresh_finish_kernel: grid.x = ChaCha20 blocks of a polynomial (8 coefficients, 64 bytes of a limb per thread), grid.y = the limb,
+// grid.z = the item, so that every stream and every per-modulus constant is wave-uniform and key and nonce are read from the kernel arguments
+// (scalar loads).  Per coefficient: A = ((hi 2^64 + lo) T) >> 128 from two 96-bit products -- no division, no sample-dependent branch -- and
+// (T - A) mod T by a select; scale_up of both is the sign and magnitude of floor(T/2) - (Q x + floor(T/2)) mod T, formed once, times
+// MForm(T^-1 mod q_j).  The flood is reduced by Horner over its words, high to low: f <- f 2^64 + v_w mod q_j, the first as a Montgomery product
+// with r2 = 2^128 mod q_j, one block of one stream at a time (8 accumulators and 8 words live, whatever W is); 2^(flood_bits-1) mod q_j, which
+// centres it, is wave-uniform.  The blocks are recomputed for every limb: W <= 16 blocks against the 8 W words a thread would otherwise hold.
+constexpr int BRF_THREADS = 128;
+
+__global__ void __launch_bounds__(BRF_THREADS) bfv_refresh_finish_kernel(BfvRefreshArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
+                                                                         BfvScale sc) {
+    const u32 blk = blockIdx.x * BRF_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+    if (blk >= (u32)(sc.N / 8)) return;
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int W = (a.flood_bits + 63) >> 6;                                 // words of the flood, 0 .. 16
+    const u32 s0 = (u32)b * (u32)(2 + W);                                   // the first stream of item b
+    const Mod md = sc.mods[j];
+    const u64 q = md.q;
+    // kind 4 and the two scalings
+    u64 lo[8], hi[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) lo[i] = hi[i] = 0;
+    if (a.mask) {                                                           // (wave-uniform)
+        chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0, lo);
+        chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 1, hi);
+    }
+    const u64 tinv = sc.tinv_mont[j];
+    const u32 T = sc.t.T;
+    u64 up[8], dn[8];                                                       // up(A) and up((T - A) mod T) under q_j
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const unsigned __int128 ph = (unsigned __int128)hi[i] * T;          // below 2^96
+        const u64 pl = (u64)(((unsigned __int128)lo[i] * T) >> 64);
+        const u32 A = (u32)((ph + pl) >> 64);                               // in [0, T)
+        const u32 An = A ? T - A : 0;
+        bool neg;
+        u64 mag = bf_scale_up_mag(sc.t, A, neg);
+        up[i] = bf_scale_up_limb(mag, neg, tinv, md);
+        mag = bf_scale_up_mag(sc.t, An, neg);
+        dn[i] = bf_scale_up_limb(mag, neg, tinv, md);
+    }
+    // kind 5 mod q_j
+    u64 f[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = 0;
+    if (W > 0) {                                                            // (wave-uniform)
+        const u64 c32 = mont_mul(1ull << 32, md.r2, q, md.ninv32);          // MForm(2^32 mod q)
+        const int tb = a.flood_bits - 64 * (W - 1);                         // bits of the top word, 1 .. 64
+        const u64 topmask = tb == 64 ? ~0ull : (1ull << tb) - 1;
+#pragma unroll 1
+        for (int w = W - 1; w >= 0; --w) {
+            u64 v[8];
+            chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 2 + (u32)w, v);
+            const u64 m = w == W - 1 ? topmask : ~0ull;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) f[i] = csub(mont_mul(f[i], md.r2, q, md.ninv32) + brf_reduce64(v[i] & m, c32, md), q);
+        }
+        const int hb = a.flood_bits - 1;                                    // 2^hb = 2^(hb mod 64) (2^64)^(hb / 64)
+        u64 half = brf_reduce64(1ull << (hb & 63), c32, md);
+        for (int t = 0; t < (hb >> 6); ++t) half = mont_mul(half, md.r2, q, md.ninv32);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) f[i] = f[i] >= half ? f[i] - half : f[i] + q - half;
+    }
+    const long row = (((long)b * sc.limbs + j) * sc.N) / 2 + 4 * (long)blk; // in pairs
+    const u64x2 v0 = ld2(acc, row), v1 = ld2(acc, row + 1), v2 = ld2(acc, row + 2), v3 = ld2(acc, row + 3);
+    const u64 v[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
+    u64 o[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = csub(csub(v[i] + up[i], q) + f[i], q);
+    st2(share, row, o[0], o[1]); st2(share, row + 1, o[2], o[3]); st2(share, row + 2, o[4], o[5]); st2(share, row + 3, o[6], o[7]);
+    st2(pt, row, dn[0], dn[1]); st2(pt, row + 1, dn[2], dn[3]); st2(pt, row + 2, dn[4], dn[5]); st2(pt, row + 3, dn[6], dn[7]);
+}
+void launch_bfv_refresh_finish(const BfvRefreshArgs& a, int count, u64* share, const u64* acc, u64* pt, const BfvScale& sc, hipStream_t st) {
+    const int bx = (sc.N / 8 + BRF_THREADS - 1) / BRF_THREADS;
+    hipLaunchKernelGGL(bfv_refresh_finish_kernel, dim3(bx, sc.limbs, count), dim3(BRF_THREADS), 0, st, a, share, acc, pt, sc);
+}
+
+// ---- bfv_refresh_merge_kernel: grid.x over the coefficients, grid.y = the item.  One thread owns coefficient n of item b through every modulus:
+// the sums of the input limbs feed bf_scale_down_of (whose Garner digits go to this thread's column of the digit scratch), the result w in [0, T)
+// stays in a register and is scaled up under each modulus on the store, with the re-encryptions added there.
+constexpr int BRM_THREADS = 256;
+
+__global__ void __launch_bounds__(BRM_THREADS) bfv_refresh_merge_kernel(int count, int nshares, u64* dig, BfvScale sc, EdTable out, EdTable c0, EdTable sh, EdTable re) {
+    const long n = (long)blockIdx.x * BRM_THREADS + threadIdx.x;
+    if (n >= sc.N) return;
+    const int b = blockIdx.y, L = sc.limbs;
+    const long N = sc.N;
+    u64* o = const_cast<u64*>(ed_entry(out, b));
+    const u64* c = ed_entry(c0, b);
+    // the residue of R under q_j
+    const u32 w = bf_scale_down_of(sc, [&](int j, const Mod& md) {
+        const u64 q = md.q;
+        u64 v = csub(csub(c[j * N + n], q), q);
+        for (int i = 0; i < nshares; ++i) v = csub(v + ed_entry(sh, i)[((long)b * L + j) * N + n], q);
+        return v;
+    }, dig + (long)b * L * N + n);
+    bool neg;
+    const u64 mag = bf_scale_up_mag(sc.t, w, neg);
+    for (int j = 0; j < L; ++j) {
+        const Mod md = sc.mods[j];
+        u64 v = bf_scale_up_limb(mag, neg, sc.tinv_mont[j], md);
+        for (int i = 0; i < nshares; ++i) v = csub(v + ed_entry(re, i * count + b)[j * N + n], md.q);
+        o[j * N + n] = v;
+    }
+    for (int i = 0; i < nshares; ++i) {
+        const u64* r1 = ed_entry(re, i * count + b) + (long)L * N;
+        u64* o1 = o + (long)(1 + i) * L * N;
+        for (int j = 0; j < L; ++j) o1[j * N + n] = r1[j * N + n];
+    }
+}
+void launch_bfv_refresh_merge(int count, int nshares, u64* dig, const BfvScale& sc, const EdTable& out, const EdTable& c0, const EdTable& sh, const EdTable& re,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(bfv_refresh_merge_kernel, dim3((sc.N + BRM_THREADS - 1) / BRM_THREADS, count), dim3(BRM_THREADS), 0, st, count, nshares, dig, sc, out, c0, sh, re);
+}
+
+}  // namespace mkhe

@@ -926,6 +926,100 @@ int mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int n
         c->refresh_merge(i, sh, re, lout, d.data());
     })
 }
+// collective refresh for MK-BFV: the checks the two calls share.  Every ciphertext of a BFV context that the calls take has nq limbs.
+static Context* brf_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const char* why_capture) {
+    if (!ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    if (!in) throw Error(std::string(what) + ": null argument");
+    if (!c->is_bfv()) throw Error(std::string(what) + ": needs a BFV context (mkhe_refresh_share / mkhe_refresh_merge serve the others)");
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    for (int b = 0; b < count; ++b) {
+        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
+        if (in[b]->c.limbs != c->nq) throw Error(std::string(what) + ": every ciphertext must have the nQ limbs of the context");
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (" + why_capture + ")");
+    return c;
+}
+int mkhe_bfv_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk, const uint32_t key[8],
+                           uint64_t nonce_mask, uint64_t nonce_enc, int mask, int flood_bits, const uint64_t* cdt, int ncdt, void* dev_shares,
+                           mkhe_ct* const* reenc) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_refresh_share";
+        if (mask != 0 && mask != 1) throw Error("mkhe_bfv_refresh_share: mask must be 0 or 1");
+        if (flood_bits < 0 || flood_bits > BRF_MAX_FLOOD) throw Error("mkhe_bfv_refresh_share: flood_bits must be 0 .. 1024");
+        if (!key) throw Error("mkhe_bfv_refresh_share: null key");              // (mask = 0 and flood_bits = 0 read no stream of nonce_mask, the encryption still draws its samples)
+        if ((mask || flood_bits > 0) && nonce_mask == nonce_enc)
+            throw Error("mkhe_bfv_refresh_share: nonce_mask and nonce_enc must differ (the mask and the encryption would share streams)");
+        Context* c = brf_need(ctx, what, count, in, "a replay would repeat the keystream");
+        if (!slots || !dev_sk || !dev_pk || !dev_shares || !reenc) throw Error("mkhe_bfv_refresh_share: null argument");
+        smp_table_ok(what, cdt, ncdt);
+        need_aligned(dev_sk, what); need_aligned(dev_pk, what); need_aligned(dev_shares, what);
+        for (int b = 0; b < count; ++b)
+            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_bfv_refresh_share: slot out of range (party slots are 1 .. n)");
+        rf_outputs(what, count, in, count, reenc);
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            const Ct& o = reenc[b]->c;
+            if (o.n != 1 || o.ids[0] != in[b]->c.ids[slots[b] - 1]) throw Error("mkhe_bfv_refresh_share: every reenc must be a ciphertext over exactly the id at the slot of its input");
+            if (o.limbs != c->nq) throw Error("mkhe_bfv_refresh_share: every reenc must have the nQ limbs of the context");
+            d[b] = o.d;
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        c->bfv_refresh_prepare(what);                                           // T outside the encoder's preconditions: refused here
+        const int most = c->bfv_refresh_max_flood();
+        if (flood_bits > most)
+            throw Error("mkhe_bfv_refresh_share: flood_bits must be at most bitlen(Q div 2T) - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, what);
+        ct_list_out(ctx, reenc, count, what);
+        c->bfv_refresh_share(i, slots, (const u64*)dev_sk, (const u64*)dev_pk, key, nonce_mask, nonce_enc, mask, flood_bits, cdt, ncdt, (u64*)dev_shares, d.data());
+    })
+}
+int mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, const mkhe_ct* const* reenc,
+                           mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_refresh_merge";
+        Context* c = brf_need(ctx, what, count, in, "the call allocates and uploads");
+        if (!out) throw Error("mkhe_bfv_refresh_merge: null argument");
+        for (int b = 0; b < count; ++b)
+            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_bfv_refresh_merge: every ciphertext must be over the same ids");
+        if (nshares != in[0]->c.n) throw Error("mkhe_bfv_refresh_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+        if (nshares > 0 && (!dev_shares || !reenc)) throw Error("mkhe_bfv_refresh_merge: null argument");
+        rf_outputs(what, count, in, count, out);
+        std::vector<const u64*> sh(nshares);
+        std::vector<const u64*> re((size_t)nshares * count);
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            if (out[b]->c.ids != in[0]->c.ids) throw Error("mkhe_bfv_refresh_merge: every out must be over the ids of the inputs");
+            if (out[b]->c.limbs != c->nq) throw Error("mkhe_bfv_refresh_merge: every out must have the nQ limbs of the context");
+            d[b] = out[b]->c.d;
+        }
+        for (int i = 0; i < nshares; ++i) {
+            if (!dev_shares[i]) throw Error("mkhe_bfv_refresh_merge: null share in the per-party list");
+            need_aligned(dev_shares[i], what);
+            sh[i] = (const u64*)dev_shares[i];
+            for (int b = 0; b < count; ++b) {
+                const mkhe_ct* r = reenc[(size_t)i * count + b];
+                if (!r) throw Error("mkhe_bfv_refresh_merge: null reenc in the list");
+                if (r->c.n != 1 || r->c.ids[0] != in[0]->c.ids[i]) throw Error("mkhe_bfv_refresh_merge: reenc[i * count + b] must be a ciphertext over exactly the id at slot 1 + i");
+                if (r->c.limbs != c->nq) throw Error("mkhe_bfv_refresh_merge: every reenc must have the nQ limbs of the context");
+                for (int k = 0; k < count; ++k) if (out[k] == r || out[k]->c.d == r->c.d) throw Error("mkhe_bfv_refresh_merge: an output aliases an input");
+                re[(size_t)i * count + b] = r->c.d;
+            }
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        c->bfv_refresh_prepare(what);
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, what);
+        if (nshares > 0) ct_list(ctx, reenc, nshares * count, what);
+        ct_list_out(ctx, out, count, what);
+        c->bfv_refresh_merge(i, sh, re, d.data());
+    })
+}
 
 // ---- CKKS encoder (ckks_encode.hip)
 // the argument checks every encoder call shares; a call refused here leaves the context (and a capture in progress) as it was

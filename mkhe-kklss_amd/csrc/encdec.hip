@@ -300,4 +300,88 @@ void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector
     MKHE_HIP(hipGetLastError());
 }
 
+// ---- collective refresh for MK-BFV: the same two chains at the maximum level (Lin = Lout = nq), with bfv_refresh_finish_kernel behind the product
+// and bfv_refresh_merge_kernel as the merge.  The scaling tables are the encoder's (bf_init); ed_w_ and ed_tab_ are laid out as in refresh_share.
+int Context::bfv_refresh_max_flood() const {
+    // Q div 2 T in 32-bit words, little endian: the product of the moduli, then one long division (2 T < 2^33)
+    std::vector<u32> w{1};
+    for (int l = 0; l < nq; ++l) {
+        const u64 m[2] = {moduli[l] & 0xffffffffull, moduli[l] >> 32};
+        std::vector<u32> r(w.size() + 2, 0);
+        for (int h = 0; h < 2; ++h) {
+            u64 carry = 0;
+            for (size_t i = 0; i < w.size(); ++i) {
+                const u64 t = (u64)w[i] * m[h] + r[i + h] + carry;
+                r[i + h] = (u32)t;
+                carry = t >> 32;
+            }
+            r[w.size() + h] += (u32)carry;          // (the word is still zero in the first round and takes no carry out in the second: the product fits)
+        }
+        w.swap(r);
+    }
+    const unsigned __int128 d = 2 * (unsigned __int128)bfv_t;
+    unsigned __int128 rem = 0;
+    int bits = 0;
+    for (size_t i = w.size(); i-- > 0;) {
+        rem = (rem << 32) | w[i];
+        const u32 qd = (u32)(rem / d);
+        rem %= d;
+        if (!bits && qd) bits = (int)i * 32 + (64 - __builtin_clzll((u64)qd));
+    }
+    return bits - 1;
+}
+
+void Context::bfv_refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask,
+                                u64 nonce_enc, int mask, int flood_bits, const u64* cdt, int ncdt, u64* shares, u64* const* outs) {
+    bf_init("mkhe_bfv_refresh_share");
+    const int count = (int)ins.size();
+    const size_t pw = (size_t)count * nq * N, sn = (size_t)count * N;
+    u64* w = scratch(ed_w_, 5 * pw);
+    u64 *pt = w + 3 * pw, *prod = pt + pw;
+    int32_t* small = reinterpret_cast<int32_t*>(scratch(ed_small_, 2 * sn));
+    scratch(ed_tab_, 3 * (size_t)count);
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 2 * (size_t)count);
+    share_product(ins, slots, sk, prod);
+    BfvRefreshArgs m;
+    const bool reads = mask || flood_bits > 0;
+    for (int i = 0; i < 8; ++i) m.key[i] = reads ? key[i] : 0;
+    m.nonce_lo = (u32)nonce_mask; m.nonce_hi = (u32)(nonce_mask >> 32); m.mask = mask; m.flood_bits = flood_bits;
+    {
+        const int W = (flood_bits + 63) / 64;
+        ProfScope ps(this, PROF_OTHER, 24.0 * N * count * nq + 64.0 * (N / 8) * count * nq * (2.0 + W));
+        launch_bfv_refresh_finish(m, count, shares, prod, pt, bf_scale(), s_);
+    }
+    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&m);      // the runtime has copied the arguments
+    for (size_t i = 0; i < sizeof(m); ++i) p[i] = 0;
+    MKHE_HIP(hipMemsetAsync(prod, 0, pw * sizeof(u64), s_));
+    SmallSampleArgs a;
+    sample_args_fill(a, key, nonce_enc, 0, cdt, ncdt);
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
+        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * sn, N, s_);
+    }
+    sample_args_wipe(a);
+    encrypt_core(nq - 1, count, pk, pt, false, w, small, ot);                // wipes the samples and u * pk
+    MKHE_HIP(hipMemsetAsync(pt, 0, pw * sizeof(u64), s_));                   // up(-A) with the public share gives the product away
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,
+                                u64* const* outs) {
+    bf_init("mkhe_bfv_refresh_merge");
+    const int count = (int)ins.size(), k = (int)shares.size();
+    u64* dig = scratch(rf_dig_, (size_t)count * nq * N);
+    std::vector<const u64*> c(count);
+    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
+    scratch(ed_tab_, 2 * (size_t)count + (size_t)k + reenc.size());
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0), ct = ed_table(c, (size_t)count);
+    const EdTable st = ed_table(shares, 2 * (size_t)count), rt = ed_table(reenc, 2 * (size_t)count + (size_t)k);
+    {
+        // every digit is written once and read by each later limb and by the sum
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * nq * ((1.0 + k) + (2.0 + (nq - 1) / 2.0) + (1.0 + 3.0 * k)));
+        launch_bfv_refresh_merge(count, k, dig, bf_scale(), ot, ct, st, rt, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
 }  // namespace mkhe

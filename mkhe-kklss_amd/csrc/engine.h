@@ -21,6 +21,7 @@
 #include "encdec_kernels.h"
 #include "decshare_kernels.h"
 #include "refresh_kernels.h"
+#include "bfv_refresh_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -290,6 +291,19 @@ class Context {
     // polynomial 0 of reenc[i * count + b]; polynomial 1 + i = polynomial 1 of reenc[i * count + b].  Builds its tables at the first use.
     void refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
                        u64* const* outs);
+    // collective refresh for MK-BFV (include/mkhe.h; bfv_refresh_kernels.h), every ciphertext with nq limbs: shares [count][nq][N] <- the product of
+    // decrypt_share + up(A_b) + e_b, A_b = kind 4 (mask = 0: none) and e_b = kind 5 (flood_bits wide; 0: none) of the keystream on the streams
+    // b S .. b S + S - 1 of (key, nonce_mask), S = 2 + ceil(flood_bits / 64); outs[b] [2][nq][N] <- encrypt_seeded of the plaintext up(-A_b) at the
+    // maximum level under (key, nonce_enc).  The caller (capi.hip) has checked slots, shapes, flood_bits and the capture.
+    void bfv_refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask, u64 nonce_enc,
+                           int mask, int flood_bits, const u64* cdt, int ncdt, u64* shares, u64* const* outs);
+    // outs[b] [1 + k][nq][N] <- polynomial 0 = up(down(ins[b] polynomial 0 + sum_i shares[i][b])) + polynomial 0 of reenc[i * count + b];
+    // polynomial 1 + i = polynomial 1 of reenc[i * count + b]
+    void bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, u64* const* outs);
+    // the tables of the BFV encoder, which both calls read, built here if no encoder call has built them (what = the C entry point: T outside the
+    // encoder's preconditions is refused under its name), and the widest flood a share takes: bitlen(Q div 2 T) - 1
+    void bfv_refresh_prepare(const char* what) { bf_init(what); }
+    int bfv_refresh_max_flood() const;
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).

@@ -5,20 +5,9 @@
 
 namespace mkhe {
 
-// the 64-bit values of the 8 coefficients of block blk of one stream (include/mkhe.h, "device-side sampling")
+// block blk of one stream of the mask's (key, nonce): chacha.h
 __device__ __forceinline__ void chacha_block8(const RefreshMaskArgs& a, u32 blk, u32 stream, u64 (&r)[8]) {
-    const u32 in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, a.key[0], a.key[1], a.key[2], a.key[3],
-                        a.key[4],    a.key[5],    a.key[6],    a.key[7],    blk,      a.nonce_lo, a.nonce_hi, stream};
-    u32 x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] = in[i];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        chacha_qr(x[0], x[4], x[8], x[12]); chacha_qr(x[1], x[5], x[9], x[13]); chacha_qr(x[2], x[6], x[10], x[14]); chacha_qr(x[3], x[7], x[11], x[15]);
-        chacha_qr(x[0], x[5], x[10], x[15]); chacha_qr(x[1], x[6], x[11], x[12]); chacha_qr(x[2], x[7], x[8], x[13]); chacha_qr(x[3], x[4], x[9], x[14]);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = (u64)(x[2 * i] + in[2 * i]) | ((u64)(x[2 * i + 1] + in[2 * i + 1]) << 32);
+    chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, stream, r);
 }
 
 // ---- refresh_finish_kernel: grid.x = ChaCha20 blocks of a polynomial (8 coefficients, 64 bytes of a limb per thread), grid.y = the item, so that

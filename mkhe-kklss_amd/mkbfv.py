@@ -755,3 +755,84 @@ class Decryptor(mkrlwe.Decryptor):
 
 def NewDecryptor(params, encoder="host"):
     return Decryptor(params, encoder)
+
+
+# ---- collective refresh (include/mkhe.h, "collective refresh for MK-BFV")
+class Refresher:
+    """The collective refresh of MK-BFV between parties: ShareNew (each party, on its own keys and its own DeviceSampler) and MergeNew (anyone)
+    give a ciphertext of the same message over the same parties whose noise is that of a fresh encryption (RefreshNoiseBound); nobody sees the
+    message.  A share is c_id * s_id + up(A) + e with A uniform mod T and e a flood of flood_bits bits, and comes with Encrypt(up(-A)); the
+    merge rounds c_0 + the shares to Z_T, scales up again and adds the re-encryptions.  The caller chooses flood_bits (at most MaxFloodBits):
+    flood_bits minus the bit size of the ciphertext's noise is the statistical hiding of that noise, which depends on the keys."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def _q(self):
+        return _q_product(self.params)
+
+    def MaxFloodBits(self, parties):
+        """floor(log2(Q / (2 T parties))), capped at the 1024 bits the engine draws: the formula of Decryptor.MaxFloodBits.  With flood_bits up
+        to this, parties * 2^(flood_bits - 1) <= Q / (4 T), which leaves the other half of the margin Q / (2 T) to the noise of the input"""
+        return min(1024, (self._q() // (2 * int(self.params.T()) * int(parties))).bit_length() - 1)
+
+    def RefreshNoiseBound(self, parties, sigma=3.2):
+        """the noise of a refreshed ciphertext, at most: parties * (2N + 1) * floor(6 sigma) + (parties + 1) / 2 per coefficient.  Each party's
+        fresh encryption adds |u e_pk + e0 + e1 s| <= (2N + 1) floor(6 sigma) (u and s ternary, the table truncated at floor(6 sigma)); the
+        roundings of up add (parties + 1) / 2"""
+        N, k = self.params.N(), int(parties)
+        return k * (2 * N + 1) * int(6 * float(sigma)) + (k + 1) / 2
+
+    def ShareBatch(self, cts, sk, pk, flood_bits, sampler):
+        """The refresh shares of the party of (sk, pk) for B ciphertexts (their id sets may differ) as ONE engine call (mkhe_bfv_refresh_share,
+        mask = 1) -> one mkrlwe.RefreshShare of count B.  Two nonces of `sampler` (a DeviceSampler) serve the call: one for mask and flood,
+        one for the encryption."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot RefreshShare: no ciphertext")
+        if sk.ID != pk.ID:
+            raise MkheError("Cannot RefreshShare: sk and pk belong to different parties")
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot RefreshShare: the ciphertext has no component for the id of sk")
+        if not isinstance(flood_bits, int) or not 0 <= flood_bits <= self.MaxFloodBits(1):
+            raise MkheError("Cannot RefreshShare: flood_bits must be an integer 0 .. %d" % self.MaxFloodBits(1))
+        if not isinstance(sampler, mkrlwe.DeviceSampler):
+            raise MkheError("Cannot RefreshShare: mask, flood and encryption samples are drawn on the device -- pass a DeviceSampler")
+        level = self.params.MaxLevel()
+        key, nonce_mask, nonce_enc = sampler.refresh_args()
+        out = mkrlwe.RefreshShare(self.params, sk.ID, level, level, len(cts))
+        slots = (C.c_int * len(cts))(*[ct.slot(sk.ID) for ct in cts])
+        check(lib().mkhe_bfv_refresh_share(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), pk.Value.devptr(),
+                                           key, nonce_mask, nonce_enc, 1, flood_bits, sampler._cdt, len(sampler.cdt), out.Share.Value.devptr(),
+                                           handle_array([c.h for c in out.Reenc])))
+        return out
+
+    def ShareNew(self, ct, sk, pk, flood_bits, sampler):
+        """ShareBatch of one ciphertext"""
+        return self.ShareBatch([ct], sk, pk, flood_bits, sampler)
+
+    def MergeBatch(self, cts, shares):
+        """The refreshed ciphertexts of B ciphertexts over the same ids: one RefreshShare of count B per party, in any order (ordering and
+        errors: mkrlwe.order_shares) -> B ciphertexts over the same ids.  ONE engine call (mkhe_bfv_refresh_merge)."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot RefreshMerge: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids:
+                raise MkheError("Cannot RefreshMerge: the ciphertexts of one call must be over the same ids")
+        ordered = mkrlwe.order_shares(cts[0].ids, self.params.MaxLevel(), len(cts), shares)
+        outs = mkrlwe.batch_ciphertexts(Ciphertext, self.params, cts[0].ids, self.params.MaxLevel(), len(cts))
+        reenc = [c.h for sh in ordered for c in sh.Reenc]
+        check(lib().mkhe_bfv_refresh_merge(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), len(ordered),
+                                           handle_array([sh.Share.Value.devptr() for sh in ordered]), handle_array(reenc) if reenc else None,
+                                           handle_array([c.h for c in outs])))
+        return outs
+
+    def MergeNew(self, ct, shares):
+        """MergeBatch of one ciphertext -> the refreshed ciphertext"""
+        return self.MergeBatch([ct], shares)[0]
+
+
+def NewRefresher(params):
+    return Refresher(params)
