@@ -643,6 +643,58 @@ int  mkhe_bfv_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, 
  * Everything is canonical, and every limb of every component of out is written.  One streaming launch; w never reaches memory. */
 int  mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares,
                             const mkhe_ct* const* reenc /* [i * count + b] */, mkhe_ct* const* out);
+/* ---- collective public-key switch: shares under a recipient's public key and their merge (PCKS of multiparty RLWE) ------------------------
+ * mkhe_decrypt_merge gives the plaintext in the clear to whoever merges and to everyone who sees the shares.  With this protocol a result goes to
+ * ONE recipient -- a client who is not among the computing parties, or one of them alone: every party publishes one share made from its secret key
+ * and the recipient's PUBLIC key, anyone adds the shares to c_0, and the result is an ordinary ciphertext over exactly the recipient's id, which the
+ * recipient decrypts with mkhe_decrypt on its own key or goes on computing with.  Nobody else learns the message, and the recipient need not be
+ * online.  No reference counterpart.
+ *
+ * Notation.  ct = (c_0, c_1 .. c_k) over ids, coefficient domain, L = level + 1 limbs, Q_l = q_0 .. q_l.  pk_R = (pk0, pk1) is the recipient's
+ * public key as mkhe_keygen_public_key writes it: uint64[2][nQ+nP][N], NTT, Montgomery form; limb j of pk0 is row j, limb j of pk1 row nQ+nP + j.
+ * Party i, for item b of a call, with c_slot the polynomial slots[b] of in[b]:
+ *     h0 = InvNTT(NTT(c_slot) * sk_i + NTT(u) * pk0) + E      (mod q_j, canonical)
+ *     h1 = InvNTT(                     NTT(u) * pk1) + e1     (mod q_j, canonical)
+ *   u   kind 0 (ternary), stream b of the call's (key, nonce)
+ *   e1  kind 1 (table cdt / ncdt), stream count + b
+ *   E   kind 5 (wide uniform, flood_bits wide: "collective refresh for MK-BFV" above), W = ceil(flood_bits / 64) words: word w is stream
+ *       2 count + b W + w, the top word masked to its low flood_bits - 64 (W - 1) bits, E = sum_w v_w 2^(64 w) - 2^(flood_bits-1).  The flood takes
+ *       the place of the e0 of an encryption: there is no separate e0.  flood_bits = 0: E = 0 and no flood stream is read (TESTS ONLY: such a share is
+ *       PartialDecrypt's product plus an encryption of zero without e0, and gives the key away to the recipient at least).
+ *   The block and word rule is that of kinds 0-5 (coefficient n takes block n / 8, words 2 (n % 8) and 2 (n % 8) + 1).  u * pk0 and u * pk1 are bit
+ *   for bit the two products of mkhe_encrypt on the same u; c_slot * sk_i is the product of mkhe_decrypt_share.
+ * Merge, by anyone:   out.c0 = c_0 + sum_i h0_i,   out.c1 = sum_i h1_i   (mod q_j, canonical), a ciphertext over one id with the limbs of the input.
+ * For CKKS the scale is that of the input.
+ *
+ * Noise budget.  With pk_R = (-a s_R + e_R, a), the result decrypts under s_R to the phase of ct plus sum_i (u_i e_R + E_i + e1_i s_R): per
+ * coefficient at most k (2^(flood_bits-1) + 2 N B), k parties, B the truncation bound of the samplers (ncdt / 2 for e1; the bound of e_R is the key
+ * generator's), s_R ternary.  The engine does not choose flood_bits: flood_bits minus the bit size of the noise of ct is the statistical hiding of
+ * that noise (and with it of the secret keys) the parties get.  The engine cannot check whose key dev_pk_recipient is: the caller must know it
+ * is the intended recipient's -- a share under another key delivers the message to that key's owner.
+ *
+ * Rules: those of the seeded encryption and of distributed decryption.  A (key, nonce) pair serves ONE call; the key travels only in kernel
+ * arguments and its host copy there is overwritten behind the launch; it never appears in a message.  CKKS, mkrlwe and BFV contexts alike; on a BFV
+ * context every input has nQ limbs.  Refused: a context with mkhe_ctx_set_owned; mkhe_pcks_share between mkhe_capture_begin and mkhe_capture_end
+ * (a replay would repeat the keystream) -- mkhe_pcks_merge MAY be captured as long as count and nshares are at most 16 (above that it stages pointer
+ * tables and is refused in a capture); flood_bits < 0, > 1024 or > bitlen(Q_l div 2T') - 1 with T' = T on BFV contexts and 1 otherwise (such a flood
+ * alone destroys the message); a NULL key whatever flood_bits is (u and e1 are drawn from it); a NULL or bad table (ncdt odd or outside 2 .. 64,
+ * thresholds not increasing); a slot out of range; inputs at different levels; in the merge inputs over different ids, nshares other than the
+ * number of parties, an out that is not over exactly one id or does not have the limbs of the input, outputs that are not distinct, an output that
+ * aliases an input; a NULL or misaligned buffer; count outside 1 .. 65535.  Messages start with the function's name; a refused call has enqueued
+ * nothing and leaves the context usable. */
+/* Party side.  dev_shares = uint64[count][2][L][N]: (h0, h1) of item b as defined above.  All in[b] are at one level; their id sets may differ.
+ * One launch set whatever count is: the sampler of u, small_expand and its forward NTT, the gathering forward NTT of the c_slot, ONE product kernel
+ * for both halves, one inverse NTT of 2 count polynomials, one finish kernel that forms E and e1 in registers (they never exist in memory).
+ * Behind their last use the engine wipes from its scratch u (as int32 and expanded), c_slot * sk + u * pk0 and u * pk1.  The call stages no
+ * pointer table and does not synchronise with the host, whatever count is. */
+int  mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk_recipient,
+                     const uint32_t key[8], uint64_t nonce, int flood_bits, const uint64_t* cdt, int ncdt,
+                     void* dev_shares /* uint64[count][2][L][N] */);
+/* Anyone.  All in[b] are over the same ids and at the same level; nshares = the number of parties, dev_shares[i] = the buffer of the party at slot
+ * 1 + i (what that party's mkhe_pcks_share wrote for the same batch); out[b] = a ciphertext over exactly one id -- the recipient's: the engine
+ * cannot check which -- with the limbs of the input.  Every limb of both polynomials of out is written.  One streaming launch; count > 16 or
+ * nshares > 16 stages pointer tables, which synchronises.  nshares = 0 on ciphertexts without parties gives (c_0 reduced, 0). */
+int  mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, mkhe_ct* const* out);
 
 /* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
  * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call

@@ -558,6 +558,78 @@ class Refresher {
     std::shared_ptr<Ciphertext> MergeNew(const Ciphertext& ct, const std::vector<const RefreshShare*>& shares) { return MergeBatch({&ct}, shares)[0]; }
     Parameters& params;
 };
+// What one party publishes in a collective key switch to a recipient's public key (include/mkhe.h, "collective public-key switch") of `count`
+// ciphertexts at `level`: the pairs (h0, h1), uint64[count][2][level+1][N] on the device.  Shares travel between parties: Value.download on one
+// side, Value.upload on the other.
+struct PublicKeySwitchShare {
+    PublicKeySwitchShare(Parameters& p, std::string id, int level, int count = 1)
+        : ID(std::move(id)), Level(level), Count(count), Value(p, (size_t)count * 2 * (level + 1) * p.N()) {}
+    std::string ID;
+    int Level, Count;
+    DeviceWords Value;
+};
+
+// The collective key switch to a recipient's public key between parties: ShareNew (each party, on its own secret key, the RECIPIENT's public key and
+// its own DeviceSampler) and MergeNew (anyone) give an ordinary ciphertext of the same message over the recipient's id alone.  The caller chooses
+// floodBits: floodBits minus the bit size of the ciphertext's noise is the statistical hiding of that noise, and NoiseBound plus that noise must
+// stay below the decryption margin.  The engine cannot check whose key pkRecipient is.
+class PublicKeySwitcher {
+  public:
+    explicit PublicKeySwitcher(Parameters& p) : params(p) {}
+    // what a switch adds to a coefficient of the phase, at most: parties * (2^(floodBits-1) + 2 N bound) (the Python mirror gives the exact integer)
+    static long double NoiseBound(int parties, int floodBits, int N, int bound = 19) {
+        return (long double)parties * ((floodBits > 0 ? std::ldexp(1.0L, floodBits - 1) : 0.0L) + 2.0L * N * bound);
+    }
+    // floodBits = 0 .. 1024, at most bitlen(Q_level div 2T') - 1; 0 (no flood) is for tests only: such a share gives sk away.  One nonce of `sampler`.
+    std::shared_ptr<PublicKeySwitchShare> ShareBatch(const std::vector<const Ciphertext*>& cts, const SecretKey& sk, const PublicKey& pkRecipient, int floodBits,
+                                                     DeviceSampler& sampler) {
+        if (cts.empty()) throw Error("Cannot SwitchShare: no ciphertext");
+        if (floodBits < 0 || floodBits > 1024) throw Error("Cannot SwitchShare: floodBits must be 0 .. 1024");
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        auto out = std::make_shared<PublicKeySwitchShare>(params, sk.ID, cts[0]->Level(), (int)cts.size());
+        check(mkhe_pcks_share(params.ctx, (int)cts.size(), in.data(), slots.data(), sk.Value.d, pkRecipient.Value.d, sampler.Key(), sampler.NextNonce(), floodBits,
+                              sampler.cdt.data(), (int)sampler.cdt.size(), out->Value.d));
+        return out;
+    }
+    std::shared_ptr<PublicKeySwitchShare> ShareNew(const Ciphertext& ct, const SecretKey& sk, const PublicKey& pkRecipient, int floodBits, DeviceSampler& sampler) {
+        return ShareBatch({&ct}, sk, pkRecipient, floodBits, sampler);
+    }
+    // one PublicKeySwitchShare of count cts.size() per party, in any order, for ciphertexts over the same ids at one level -> ciphertexts over {recipient}
+    std::vector<std::shared_ptr<Ciphertext>> MergeBatch(const std::vector<const Ciphertext*>& cts, const std::vector<const PublicKeySwitchShare*>& shares,
+                                                        const std::string& recipient) {
+        std::vector<std::shared_ptr<Ciphertext>> outs;
+        for (size_t b = 0; b < cts.size(); ++b) outs.push_back(std::make_shared<Ciphertext>(params, IDSet{recipient}, cts[0]->Level(), false));
+        merge(cts, shares, outs);
+        return outs;
+    }
+    std::shared_ptr<Ciphertext> MergeNew(const Ciphertext& ct, const std::vector<const PublicKeySwitchShare*>& shares, const std::string& recipient) {
+        return MergeBatch({&ct}, shares, recipient)[0];
+    }
+    Parameters& params;
+  protected:
+    // the engine call of a merge into ready outputs (any subclass of Ciphertext)
+    template <class Ct> void merge(const std::vector<const Ciphertext*>& cts, const std::vector<const PublicKeySwitchShare*>& shares,
+                                   const std::vector<std::shared_ptr<Ct>>& outs) {
+        if (cts.empty()) throw Error("Cannot SwitchMerge: no ciphertext");
+        std::vector<const mkhe_ct*> in;
+        for (auto* ct : cts) in.push_back(ct->h);
+        std::vector<const void*> ordered;
+        for (auto& id : cts[0]->ids) {
+            const PublicKeySwitchShare* found = nullptr;
+            for (auto* sh : shares)
+                if (sh->ID == id) { if (found) throw Error("Cannot MergeShares: two shares of one party"); found = sh; }
+            if (!found) throw Error("Cannot MergeShares: the share of a party is missing");
+            if (found->Level != cts[0]->Level() || found->Count != (int)cts.size()) throw Error("Cannot MergeShares: a share is at another level or for another batch size");
+            ordered.push_back(found->Value.d);
+        }
+        if (shares.size() != ordered.size()) throw Error("Cannot MergeShares: a share of a party the ciphertext does not have");
+        std::vector<mkhe_ct*> oh;
+        for (auto& o : outs) oh.push_back(o->h);
+        check(mkhe_pcks_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), oh.data()));
+    }
+};
 }  // namespace mkrlwe
 
 namespace mkckks {
@@ -767,6 +839,28 @@ class Encoder {
     }
     Parameters& params;
 };
+// The collective key switch of mkrlwe::PublicKeySwitcher on mkckks ciphertexts: the result keeps the input's Scale.
+class PublicKeySwitcher : public mkrlwe::PublicKeySwitcher {
+  public:
+    explicit PublicKeySwitcher(Parameters& p) : mkrlwe::PublicKeySwitcher(p), ckks(p) {}
+    // how far a switch moves a slot, at most: N * NoiseBound / scale
+    long double SwitchSlotBound(int parties, int floodBits, double scale, int bound = 19) const {
+        return (long double)ckks.N() * NoiseBound(parties, floodBits, ckks.N(), bound) / scale;
+    }
+    std::vector<std::shared_ptr<Ciphertext>> MergeBatch(const std::vector<const Ciphertext*>& cts, const std::vector<const mkrlwe::PublicKeySwitchShare*>& shares,
+                                                        const std::string& recipient) {
+        std::vector<std::shared_ptr<Ciphertext>> outs;
+        std::vector<const mkrlwe::Ciphertext*> base(cts.begin(), cts.end());
+        for (size_t b = 0; b < cts.size(); ++b) outs.push_back(std::make_shared<Ciphertext>(ckks, mkrlwe::IDSet{recipient}, cts[0]->Level(), cts[0]->Scale, false));
+        merge(base, shares, outs);
+        return outs;
+    }
+    std::shared_ptr<Ciphertext> MergeNew(const Ciphertext& ct, const std::vector<const mkrlwe::PublicKeySwitchShare*>& shares, const std::string& recipient) {
+        return MergeBatch({&ct}, shares, recipient)[0];
+    }
+  private:
+    Parameters& ckks;
+};
 }  // namespace mkckks
 
 namespace mkbfv {
@@ -974,5 +1068,23 @@ class Refresher {
     }
     std::shared_ptr<Ciphertext> MergeNew(const mkrlwe::Ciphertext& ct, const std::vector<const mkrlwe::RefreshShare*>& shares) { return MergeBatch({&ct}, shares)[0]; }
     Parameters& params;
+};
+// The collective key switch of mkrlwe::PublicKeySwitcher on mkbfv ciphertexts: the message stays exact as long as NoiseBound plus the noise of
+// the input is below Q / (2T).
+class PublicKeySwitcher : public mkrlwe::PublicKeySwitcher {
+  public:
+    explicit PublicKeySwitcher(Parameters& p) : mkrlwe::PublicKeySwitcher(p), bfv(p) {}
+    std::vector<std::shared_ptr<Ciphertext>> MergeBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const std::vector<const mkrlwe::PublicKeySwitchShare*>& shares,
+                                                        const std::string& recipient) {
+        std::vector<std::shared_ptr<Ciphertext>> outs;
+        for (size_t b = 0; b < cts.size(); ++b) outs.push_back(std::make_shared<Ciphertext>(bfv, mkrlwe::IDSet{recipient}, false));
+        merge(cts, shares, outs);
+        return outs;
+    }
+    std::shared_ptr<Ciphertext> MergeNew(const mkrlwe::Ciphertext& ct, const std::vector<const mkrlwe::PublicKeySwitchShare*>& shares, const std::string& recipient) {
+        return MergeBatch({&ct}, shares, recipient)[0];
+    }
+  private:
+    Parameters& bfv;
 };
 }  // namespace mkbfv

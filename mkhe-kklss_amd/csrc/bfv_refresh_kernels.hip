@@ -1,16 +1,10 @@
 // bfv_refresh_kernels.hip -- see bfv_refresh_kernels.h.  No LDS, no scratch.
 #include "bfv_refresh_kernels.h"
 #include "bfv_arith.h"
-#include "chacha.h"
+#include "flood_arith.h"
 #include "ed_access.h"
 
 namespace mkhe {
-
-// v mod q for ANY 64-bit v.  mont_mul(a, r1) reduces only a < 2^62, so the word is split: (v >> 32) 2^32 + (v mod 2^32), the high half times
-// c32 = MForm(2^32 mod q) (the same reduction with the constant folded in), the low half times r1.
-__device__ __forceinline__ u64 brf_reduce64(u64 v, u64 c32, const Mod& md) {
-    return csub(mont_mul(hi32(v), c32, md.q, md.ninv32) + mont_mul(lo32(v), md.r1, md.q, md.ninv32), md.q);
-}
 
 // ---- bfv_refresh_finish_kernel: grid.x = ChaCha20 blocks of a polynomial (8 coefficients, 64 bytes of a limb per thread), grid.y = the limb,
 // grid.z = the item, so that every stream and every per-modulus constant is wave-uniform and key and nonce are read from the kernel arguments
@@ -53,28 +47,9 @@ __global__ void __launch_bounds__(BRF_THREADS) bfv_refresh_finish_kernel(BfvRefr
         mag = bf_scale_up_mag(sc.t, An, neg);
         dn[i] = bf_scale_up_limb(mag, neg, tinv, md);
     }
-    // kind 5 mod q_j
+    // kind 5 mod q_j (flood_arith.h)
     u64 f[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = 0;
-    if (W > 0) {                                                            // (wave-uniform)
-        const u64 c32 = mont_mul(1ull << 32, md.r2, q, md.ninv32);          // MForm(2^32 mod q)
-        const int tb = a.flood_bits - 64 * (W - 1);                         // bits of the top word, 1 .. 64
-        const u64 topmask = tb == 64 ? ~0ull : (1ull << tb) - 1;
-#pragma unroll 1
-        for (int w = W - 1; w >= 0; --w) {
-            u64 v[8];
-            chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 2 + (u32)w, v);
-            const u64 m = w == W - 1 ? topmask : ~0ull;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) f[i] = csub(mont_mul(f[i], md.r2, q, md.ninv32) + brf_reduce64(v[i] & m, c32, md), q);
-        }
-        const int hb = a.flood_bits - 1;                                    // 2^hb = 2^(hb mod 64) (2^64)^(hb / 64)
-        u64 half = brf_reduce64(1ull << (hb & 63), c32, md);
-        for (int t = 0; t < (hb >> 6); ++t) half = mont_mul(half, md.r2, q, md.ninv32);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) f[i] = f[i] >= half ? f[i] - half : f[i] + q - half;
-    }
+    flood_mod_q(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 2, a.flood_bits, md, f);
     const long row = (((long)b * sc.limbs + j) * sc.N) / 2 + 4 * (long)blk; // in pairs
     const u64x2 v0 = ld2(acc, row), v1 = ld2(acc, row + 1), v2 = ld2(acc, row + 2), v3 = ld2(acc, row + 3);
     const u64 v[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};

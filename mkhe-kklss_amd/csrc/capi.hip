@@ -1020,6 +1020,85 @@ int mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, i
         c->bfv_refresh_merge(i, sh, re, d.data());
     })
 }
+// collective key switch to a recipient's public key: the checks the two calls share, under the rules of distributed decryption.  The share
+// draws from the keystream and is refused inside a capture; the merge allocates nothing, uploads nothing that outlives the call and may be captured
+// as long as it stages no table (count and nshares at most 16).
+static Context* pcks_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, bool keystream) {
+    if (!ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    if (!in) throw Error(std::string(what) + ": null argument");
+    for (int b = 0; b < count; ++b) {
+        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
+        if (c->is_bfv() && in[b]->c.limbs != c->nq) throw Error(std::string(what) + ": on a BFV context every ciphertext must have the nQ limbs of the context");
+        if (in[b]->c.limbs != in[0]->c.limbs) throw Error(std::string(what) + ": every ciphertext must be at the same level");
+    }
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) {
+        if (keystream) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (a replay would repeat the keystream)");
+        if (count > ED_INLINE) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end with more than 16 ciphertexts or shares (the pointer tables are staged)");
+    }
+    return c;
+}
+int mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk_recipient,
+                    const uint32_t key[8], uint64_t nonce, int flood_bits, const uint64_t* cdt, int ncdt, void* dev_shares) {
+    MKHE_TRY({
+        const char* what = "mkhe_pcks_share";
+        if (flood_bits < 0 || flood_bits > PCKS_MAX_FLOOD) throw Error("mkhe_pcks_share: flood_bits must be 0 .. 1024");
+        if (!key) throw Error("mkhe_pcks_share: null key");                     // (flood_bits = 0 reads no flood stream, u and e1 are drawn from the key all the same)
+        Context* c = pcks_need(ctx, what, count, in, true);
+        if (!slots || !dev_sk || !dev_pk_recipient || !dev_shares) throw Error("mkhe_pcks_share: null argument");
+        smp_table_ok(what, cdt, ncdt);
+        need_aligned(dev_sk, what); need_aligned(dev_pk_recipient, what); need_aligned(dev_shares, what);
+        for (int b = 0; b < count; ++b)
+            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_pcks_share: slot out of range (party slots are 1 .. n)");
+        const int most = c->flood_room(in[0]->c.limbs, c->is_bfv() ? c->bfv_t : 1);
+        if (flood_bits > most)
+            throw Error("mkhe_pcks_share: flood_bits must be at most bitlen(Q_l div 2T') - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, what);
+        c->pcks_share(i, slots, (const u64*)dev_sk, (const u64*)dev_pk_recipient, key, nonce, flood_bits, cdt, ncdt, (u64*)dev_shares);
+    })
+}
+int mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_pcks_merge";
+        Context* c = pcks_need(ctx, what, count, in, false);
+        if (!out) throw Error("mkhe_pcks_merge: null argument");
+        for (int b = 0; b < count; ++b)
+            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_pcks_merge: every ciphertext must be over the same ids");
+        if (nshares != in[0]->c.n) throw Error("mkhe_pcks_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+        if (nshares > 0 && !dev_shares) throw Error("mkhe_pcks_merge: null argument");
+        rf_outputs(what, count, in, count, out);
+        std::vector<const u64*> sh(nshares);
+        std::vector<u64*> d(count);
+        for (int b = 0; b < count; ++b) {
+            if (out[b]->c.n != 1) throw Error("mkhe_pcks_merge: every out must be a ciphertext over exactly one id (the recipient's)");
+            if (out[b]->c.limbs != in[0]->c.limbs) throw Error("mkhe_pcks_merge: every out must have the limbs of the inputs");
+            d[b] = out[b]->c.d;
+        }
+        for (int i = 0; i < nshares; ++i) {
+            if (!dev_shares[i]) throw Error("mkhe_pcks_merge: null share in the per-party list");
+            need_aligned(dev_shares[i], what);
+            sh[i] = (const u64*)dev_shares[i];
+        }
+        if (nshares > ED_INLINE) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            (void)hipStreamIsCapturing(c->stream, &cs);
+            if (cs != hipStreamCaptureStatusNone)
+                throw Error("mkhe_pcks_merge: not available inside mkhe_capture_begin .. mkhe_capture_end with more than 16 ciphertexts or shares (the pointer tables are staged)");
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto i = ct_list(ctx, in, count, what);
+        ct_list_out(ctx, out, count, what);
+        c->pcks_merge(i, sh, d.data());
+    })
+}
 
 // ---- CKKS encoder (ckks_encode.hip)
 // the argument checks every encoder call shares; a call refused here leaves the context (and a capture in progress) as it was

@@ -178,6 +178,17 @@ void Context::share_product(const std::vector<const Ct*>& ins, const int* slots,
     std::vector<const u64*> c(count), s(count, sk);
     for (int b = 0; b < count; ++b) c[b] = w + (size_t)b * pw;
     const EdTable ct = ed_table(c, 0), st = ed_table(s, (size_t)count);    // count > ED_INLINE: staged, which synchronises
+    share_gather_ntt(ins, slots, w);
+    {
+        ProfScope ps(this, PROF_OTHER, 24.0 * N * L * count);
+        launch_decrypt_mac(count, 1, w, ct, st, d_mods, L, N, s_);
+    }
+    ntt(w, w, count, L, 0, true, false);
+}
+
+void Context::share_gather_ntt(const std::vector<const Ct*>& ins, const int* slots, u64* w) {
+    const int count = (int)ins.size(), L = ins[0]->limbs;
+    const size_t pw = (size_t)L * N;
     for (int base = 0; base < count; base += NTT_MAX_ITEMS) {
         const int cnt = std::min(NTT_MAX_ITEMS, count - base);
         NttBatch b{};
@@ -187,11 +198,6 @@ void Context::share_product(const std::vector<const Ct*>& ins, const int* slots,
         for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d + (size_t)slots[base + i] * pw; b.dst_items[i] = w + (size_t)(base + i) * pw; }
         ntt_fwd_launch(b, false);
     }
-    {
-        ProfScope ps(this, PROF_OTHER, 24.0 * N * L * count);
-        launch_decrypt_mac(count, 1, w, ct, st, d_mods, L, N, s_);
-    }
-    ntt(w, w, count, L, 0, true, false);
 }
 
 void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares) {
@@ -302,10 +308,10 @@ void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector
 
 // ---- collective refresh for MK-BFV: the same two chains at the maximum level (Lin = Lout = nq), with bfv_refresh_finish_kernel behind the product
 // and bfv_refresh_merge_kernel as the merge.  The scaling tables are the encoder's (bf_init); ed_w_ and ed_tab_ are laid out as in refresh_share.
-int Context::bfv_refresh_max_flood() const {
+int Context::flood_room(int limbs, u64 t) const {
     // Q div 2 T in 32-bit words, little endian: the product of the moduli, then one long division (2 T < 2^33)
     std::vector<u32> w{1};
-    for (int l = 0; l < nq; ++l) {
+    for (int l = 0; l < limbs; ++l) {
         const u64 m[2] = {moduli[l] & 0xffffffffull, moduli[l] >> 32};
         std::vector<u32> r(w.size() + 2, 0);
         for (int h = 0; h < 2; ++h) {
@@ -319,7 +325,7 @@ int Context::bfv_refresh_max_flood() const {
         }
         w.swap(r);
     }
-    const unsigned __int128 d = 2 * (unsigned __int128)bfv_t;
+    const unsigned __int128 d = 2 * (unsigned __int128)t;
     unsigned __int128 rem = 0;
     int bits = 0;
     for (size_t i = w.size(); i-- > 0;) {
@@ -380,6 +386,61 @@ void Context::bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::ve
         // every digit is written once and read by each later limb and by the sum
         ProfScope ps(this, PROF_OTHER, 8.0 * N * count * nq * ((1.0 + k) + (2.0 + (nq - 1) / 2.0) + (1.0 + 3.0 * k)));
         launch_bfv_refresh_merge(count, k, dig, bf_scale(), ot, ct, st, rt, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+// ---- collective key switch to a recipient's public key.  One launch set over the work buffer w [3][count][L][N]: u sampled (kind 0) into
+// ed_small_, small_expand into w[2] and its forward NTT; the gathering forward NTT of the c_slot into w[0]; pcks_mac (w[0] <- c^ sk + u^ pk0,
+// w[1] <- u^ pk1, w[2] <- 0); one inverse NTT of 2 count polynomials; pcks_finish adds the flood and e1 from registers and writes the caller's
+// buffer.  No pointer table: nothing is staged and the call never waits for the host.  c_i s_i gives the key away and u pk1 gives u away: the int32
+// u, w[0] and w[1] are wiped behind their last use (w[2] by the product kernel).
+void Context::pcks_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce, int flood_bits,
+                         const u64* cdt, int ncdt, u64* shares) {
+    if (masked_) throw Error("mkhe_pcks_share: not available on a context that owns a subset of the moduli");
+    const int count = (int)ins.size(), L = ins[0]->limbs;
+    const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
+    u64* w = scratch(ed_w_, 3 * pw);
+    int32_t* du = reinterpret_cast<int32_t*>(scratch(ed_small_, (sn + 1) / 2));
+    SmallSampleArgs a;
+    sample_args_fill(a, key, nonce, 0, cdt, ncdt);
+    {
+        ProfScope ps(this, PROF_OTHER, 4.0 * count * N);
+        launch_small_sample(a, 0, count, du, nullptr, N, s_);
+    }
+    {
+        ProfScope ps(this, PROF_OTHER, (double)count * N * (4.0 + 8.0 * L));
+        launch_small_expand(w + 2 * pw, du, d_mods, count, L, N, s_);
+    }
+    MKHE_HIP(hipMemsetAsync(du, 0, sn * sizeof(int32_t), s_));
+    ntt(w + 2 * pw, w + 2 * pw, count, L, 0, false, false);
+    share_gather_ntt(ins, slots, w);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (count * 5.0 + 3.0));
+        launch_pcks_mac(count, w, sk, pk, d_mods, L, mtot, N, s_);
+    }
+    ntt(w, w, 2 * count, L, 0, true, false);
+    {
+        const int W = (flood_bits + 63) / 64;
+        ProfScope ps(this, PROF_OTHER, 32.0 * N * L * count + 64.0 * (N / 8) * count * L * (1.0 + W));
+        launch_pcks_finish(a, flood_bits, count, shares, w, d_mods, L, N, s_);
+    }
+    sample_args_wipe(a);                                                    // the runtime has copied the arguments
+    MKHE_HIP(hipMemsetAsync(w, 0, 2 * pw * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::pcks_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* const* outs) {
+    if (masked_) throw Error("mkhe_pcks_merge: not available on a context that owns a subset of the moduli");
+    const int count = (int)ins.size(), L = ins[0]->limbs;
+    std::vector<const u64*> c(count);
+    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
+    scratch(ed_tab_, 2 * (size_t)count + shares.size());
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0), ct = ed_table(c, (size_t)count);
+    const EdTable st = ed_table(shares, 2 * (size_t)count);                 // count or nshares > ED_INLINE: staged, which synchronises
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * L * count * (3.0 + 2.0 * (double)shares.size()));
+        launch_pcks_merge(count, (int)shares.size(), ot, ct, st, d_mods, L, N, s_);
     }
     MKHE_HIP(hipGetLastError());
 }

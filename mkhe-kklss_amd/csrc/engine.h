@@ -22,6 +22,7 @@
 #include "decshare_kernels.h"
 #include "refresh_kernels.h"
 #include "bfv_refresh_kernels.h"
+#include "pcks_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -303,7 +304,17 @@ class Context {
     // the tables of the BFV encoder, which both calls read, built here if no encoder call has built them (what = the C entry point: T outside the
     // encoder's preconditions is refused under its name), and the widest flood a share takes: bitlen(Q div 2 T) - 1
     void bfv_refresh_prepare(const char* what) { bf_init(what); }
-    int bfv_refresh_max_flood() const;
+    int bfv_refresh_max_flood() const { return flood_room(nq, bfv_t); }
+    // bitlen((q_0 .. q_(limbs-1)) div 2 t) - 1: the widest flood that alone leaves a message scaled by Q / t standing (t = 1: a CKKS / mkrlwe ring)
+    int flood_room(int limbs, u64 t) const;
+    // collective key switch to a recipient's public key (include/mkhe.h; pcks_kernels.h): shares [count][2][L][N] <- (h0_b, h1_b), h0 = the product
+    // of decrypt_share + u_b * pk0 + E_b, h1 = u_b * pk1 + e1_b, with u_b = kind 0 on stream b, e1_b = kind 1 on stream count + b and E_b = kind 5
+    // (flood_bits wide; 0: none) on the streams 2 count + b W .. of (key, nonce), W = ceil(flood_bits / 64); pk: the recipient's [2][nq+np][N].  One
+    // launch set, no host synchronisation whatever count is.  The caller (capi.hip) has checked slots, levels, flood_bits and the capture.
+    void pcks_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce, int flood_bits,
+                    const u64* cdt, int ncdt, u64* shares);
+    // outs[b] [2][L][N] <- (ins[b] polynomial 0 + sum_i shares[i][b][0], sum_i shares[i][b][1]), canonical
+    void pcks_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* const* outs);
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).
@@ -428,6 +439,8 @@ class Context {
     void ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64* acc);
     // the product chain of a share: w [count][L][N] <- InvNTT(NTT(polynomial slots[b] of ins[b]) * sk); stages its tables at entries 0 .. 2 count of ed_tab_
     void share_product(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, u64* w);
+    // w [count][L][N] <- NTT(polynomial slots[b] of ins[b]): one gathering forward transform (per NTT_MAX_ITEMS items)
+    void share_gather_ntt(const std::vector<const Ct*>& ins, const int* slots, u64* w);
     // collective refresh: MForm(q_i mod q_j) and (q_0 .. q_l) mod q_j, [nq][nq] each in one block, built at the first merge; the digits of R
     u64* d_rf_tab_ = nullptr;
     Scratch rf_dig_;

@@ -836,3 +836,24 @@ class Refresher:
 
 def NewRefresher(params):
     return Refresher(params)
+
+
+class PublicKeySwitcher(mkrlwe.PublicKeySwitcher):
+    """The collective key switch of mkrlwe.PublicKeySwitcher on mkbfv ciphertexts: the result is a mkbfv.Ciphertext over the recipient's id.  The
+    message stays exact as long as NoiseBound plus the noise of the input is below Q / (2 T)."""
+
+    def _t(self):
+        return int(self.params.T())
+
+    def _out(self, like, count, recipient_id):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [recipient_id], self.params.MaxLevel(), count)
+
+    def MaxFloodBits(self, parties=1):
+        """floor(log2(Q / (2 T parties))), capped at the 1024 bits the engine draws: the formula of Refresher.MaxFloodBits.  With flood_bits up
+        to this, parties * 2^(flood_bits - 1) <= Q / (4 T), which leaves the other half of the margin Q / (2 T) to the noise of the input
+        (parties = 1: the widest flood the engine takes)"""
+        return min(1024, (_q_product(self.params) // (2 * int(self.params.T()) * int(parties))).bit_length() - 1)
+
+
+def NewPublicKeySwitcher(params):
+    return PublicKeySwitcher(params)

@@ -1174,3 +1174,21 @@ class Refresher(mkrlwe.Refresher):
 
 def NewRefresher(params):
     return Refresher(params)
+
+
+class PublicKeySwitcher(mkrlwe.PublicKeySwitcher):
+    """The collective key switch of mkrlwe.PublicKeySwitcher on mkckks ciphertexts: the result is a mkckks.Ciphertext over the recipient's id with
+    the input's Scale (the message and its scale are untouched; only the noise of the shares is added: SwitchSlotBound)."""
+
+    def _out(self, like, count, recipient_id):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [recipient_id], like.Level(), count, Scale=like.ScalingFactor())
+
+    def SwitchSlotBound(self, parties, flood_bits, scale, bound=19):
+        """how far a switch moves a slot, at most: N * NoiseBound(parties, flood_bits, N, bound) / scale (a slot is a sum of N coefficients times
+        unit-modulus roots)"""
+        N = self.params.N()
+        return N * self.NoiseBound(parties, flood_bits, N, bound) / float(scale)
+
+
+def NewPublicKeySwitcher(params):
+    return PublicKeySwitcher(params)

@@ -679,6 +679,10 @@ class DeviceSampler:
         """(key, nonce) for ONE mkhe_decrypt_share call: the same counter as encrypt_args, so that no nonce serves two calls of either kind"""
         return self._key, self._next_nonce()
 
+    def switch_args(self):
+        """(key, nonce, cdt, ncdt) for ONE mkhe_pcks_share call: the same counter as the other calls"""
+        return self._key, self._next_nonce(), self._cdt, len(self.cdt)
+
     def refresh_args(self):
         """(key, nonce_mask, nonce_enc) for ONE mkhe_refresh_share call: two values of the same counter, taken under the lock"""
         with self._lock:
@@ -1218,3 +1222,118 @@ class Refresher:
 
 def NewRefresher(params):
     return Refresher(params)
+
+
+# ---- collective public-key switch (include/mkhe.h, "collective public-key switch")
+class PublicKeySwitchShare:
+    """What one party publishes in a collective key switch of `count` ciphertexts at `level` to a recipient's public key: the pairs (h0, h1),
+    uint64 [count][2][level+1][N] on the device.  Shares travel between parties: download() gives the host array, upload() takes it on the
+    receiving side (PublicKeySwitchShare(params, id, level, count).upload(host))."""
+
+    def __init__(self, params, id, level, count=1):
+        self.ID, self._level, self.count = id, int(level), int(count)
+        self.Value = DeviceLimbs(params, 2 * self.count, self._level + 1)
+
+    def Level(self):
+        return self._level
+
+    def download(self):
+        h = self.Value.download()
+        return h.reshape(self.count, 2, h.shape[1], h.shape[2])
+
+    def upload(self, host):
+        host = np.ascontiguousarray(host, dtype=np.uint64)
+        if host.ndim != 4 or host.shape[:2] != (self.count, 2):
+            raise MkheError("PublicKeySwitchShare: expected an array of shape [%d][2][limbs][N], got %r" % (self.count, host.shape))
+        self.Value.upload(host.reshape(2 * self.count, host.shape[2], host.shape[3]))
+        return self
+
+
+class PublicKeySwitcher:
+    """The collective key switch to a recipient's public key between parties: ShareNew (each party, on its own secret key, the RECIPIENT's public
+    key and its own DeviceSampler) and MergeNew (anyone) give an ordinary ciphertext of the same message over the recipient's id alone, which the
+    recipient decrypts with Decrypt on its own key or goes on computing with.  Nobody else learns the message; the recipient need not be online
+    and need not be one of the parties.  The caller chooses flood_bits (at most MaxFloodBits): flood_bits minus the bit size of the ciphertext's
+    noise is the statistical hiding of that noise.  The engine cannot check whose key pk_recipient is."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def _t(self):
+        """T' of the flood bound: the plaintext modulus of a BFV ring, 1 otherwise"""
+        return 1
+
+    def _out(self, like, count, recipient_id):
+        """the `count` outputs of a merge: ciphertexts over [recipient_id] at the level of `like`"""
+        return batch_ciphertexts(Ciphertext, self.params, [recipient_id], like.Level(), count)
+
+    @staticmethod
+    def NoiseBound(parties, flood_bits, N, bound=19):
+        """what a switch adds to a coefficient of the phase, at most: parties * (2^(flood_bits - 1) + 2 N bound) (exact integer).  Under the
+        recipient's secret the result decrypts to the phase of the input plus sum_i (u_i e_R + E_i + e1_i s_R): u_i and s_R ternary, e_R and
+        e1_i truncated at `bound` (floor(6 sigma): 19 at sigma 3.2), E_i in [-2^(flood_bits-1), 2^(flood_bits-1))."""
+        flood = 0 if int(flood_bits) == 0 else 1 << (int(flood_bits) - 1)
+        return int(parties) * (flood + 2 * int(N) * int(bound))
+
+    def MaxFloodBits(self, level=None):
+        """the widest flood the engine takes for ciphertexts at `level` (default: the maximum): bitlen(Q_l div 2T') - 1, capped at the 1024
+        bits the engine draws; T' = T on a BFV ring, 1 otherwise.  Such a flood alone would still leave the message standing; what the noise of
+        the ciphertext and the number of parties leave of it is the caller's budget (NoiseBound)."""
+        return self._most(self.params.MaxLevel() if level is None else int(level))
+
+    def _most(self, level):
+        q = 1
+        for m in self.params.Q[: level + 1]:
+            q *= int(m)
+        return min(1024, (q // (2 * self._t())).bit_length() - 1)
+
+    def ShareBatch(self, cts, sk, pk_recipient, flood_bits, sampler):
+        """The key-switch shares of the party of `sk` for B ciphertexts at one level (their id sets may differ) as ONE engine call
+        (mkhe_pcks_share) -> one PublicKeySwitchShare of count B whose .ID is sk.ID.  One nonce of `sampler` (a DeviceSampler) serves the call.
+        flood_bits = 0 (no flood) is for TESTS ONLY: such a share gives sk away."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot SwitchShare: no ciphertext")
+        level = cts[0].Level()
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot SwitchShare: the ciphertext has no component for the id of sk")
+            if ct.Level() != level:
+                raise MkheError("Cannot SwitchShare: the ciphertexts of one call must be at the same level")
+        if not isinstance(flood_bits, int) or not 0 <= flood_bits <= self._most(level):
+            raise MkheError("Cannot SwitchShare: flood_bits must be an integer 0 .. %d" % self._most(level))
+        if not isinstance(sampler, DeviceSampler):
+            raise MkheError("Cannot SwitchShare: u, e1 and the flood are drawn on the device -- pass a DeviceSampler")
+        key, nonce, cdt, ncdt = sampler.switch_args()
+        out = PublicKeySwitchShare(self.params, sk.ID, level, len(cts))
+        slots = (C.c_int * len(cts))(*[ct.slot(sk.ID) for ct in cts])
+        check(lib().mkhe_pcks_share(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), pk_recipient.Value.devptr(),
+                                    key, nonce, flood_bits, cdt, ncdt, out.Value.devptr()))
+        return out
+
+    def ShareNew(self, ct, sk, pk_recipient, flood_bits, sampler):
+        """ShareBatch of one ciphertext"""
+        return self.ShareBatch([ct], sk, pk_recipient, flood_bits, sampler)
+
+    def MergeBatch(self, cts, shares, recipient_id):
+        """The switched ciphertexts of B ciphertexts over the same ids at one level: one PublicKeySwitchShare of count B per party, in any order
+        (ordering and errors: order_shares) -> B ciphertexts over [recipient_id] at the same level.  ONE engine call (mkhe_pcks_merge)."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot SwitchMerge: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids or ct.Level() != cts[0].Level():
+                raise MkheError("Cannot SwitchMerge: the ciphertexts of one call must be over the same ids and at the same level")
+        ordered = order_shares(cts[0].ids, cts[0].Level(), len(cts), shares)
+        outs = self._out(cts[0], len(cts), recipient_id)
+        check(lib().mkhe_pcks_merge(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), len(ordered),
+                                    handle_array([sh.Value.devptr() for sh in ordered]) if ordered else None, handle_array([c.h for c in outs])))
+        return outs
+
+    def MergeNew(self, ct, shares, recipient_id):
+        """MergeBatch of one ciphertext -> the ciphertext over [recipient_id]"""
+        return self.MergeBatch([ct], shares, recipient_id)[0]
+
+
+def NewPublicKeySwitcher(params):
+    return PublicKeySwitcher(params)
