@@ -494,6 +494,51 @@ int  mkhe_sample_small(mkhe_ctx* ctx, int kind, int count, const uint32_t key[8]
  * with the host (above that the output pointers are staged, as in mkhe_encrypt). */
 int  mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt,
                          const uint32_t key[8], uint64_t nonce, const uint64_t* cdt, int ncdt, mkhe_ct* const* out);
+/* ---- secret-key encryption with a seeded c1: half-size fresh ciphertexts ------------------------------------------------------------
+ * No reference counterpart (lattigo: NewEncryptor(params, sk), NewPRNGEncryptor); the definitions are this project's own.  A party that
+ * encrypts its OWN data holds a secret key and needs no public key: c1 is a uniform polynomial a expanded from a PUBLIC 32-byte seed, and
+ * c0 = pt + e - a s.  Only c0 and the seed travel (limbs * N * 8 + 40 bytes against 2 * limbs * N * 8), the phase error is e alone
+ * (|e| <= ncdt / 2, against about sigma sqrt(N) of the public-key form), and one forward and one inverse NTT are run per ciphertext.
+ *
+ * Kind 6 of the keystream above: uniform mod q_j, keyed by a PUBLIC pair (a_key, a_nonce).  Row (b, j) is item b, limb j < limbs of Q; it owns
+ * the streams 2 (b nQ + j) (lo) and 2 (b nQ + j) + 1 (hi), with nQ the context's number of Q primes -- NOT limbs: the rows of an item do not
+ * depend on the level they are expanded at, and expanding fewer limbs is an implicit DropLevel.  Coefficient n takes the 64-bit values lo, hi of
+ * coefficient n of the two streams (block n / 8, words 2 (n % 8) and 2 (n % 8) + 1) and, with r = hi 2^64 + lo,
+ *     a[b][j][n] = (r q_j) >> 128,
+ * which lies in [0, q_j) and is uniform to within q_j / 2^128 (< 2^-67).  No division, no rejection, no sample-dependent branch.  The value is
+ * canonical and in the coefficient domain: a IS the c1 of the ciphertext.
+ *
+ * Ciphertext.  For item b, with s the party's secret (a mkhe_keygen_secret buffer, Q limbs read), out[b] is a ciphertext over exactly one
+ * party with level + 1 limbs:
+ *     c1[j][n] = a[b][j][n]
+ *     c0[j][n] = (pt[b][j][n] + (e_b[n] mod q_j) - InvNTT(NTT(c1_j) * s_j)[n]) mod q_j        canonical
+ * pt = uint64[count][level+1][N], canonical, coefficient domain or (pt_is_ntt) NTT domain: it then rides in the one inverse NTT, as in
+ * mkhe_encrypt.  Consequently mkhe_decrypt(out[b], s) returns (pt + e) mod q_j EXACTLY: the phase error is e and nothing else.
+ * One launch set whatever count is: sample, one forward NTT of count * limbs rows, product, one inverse NTT, finish.
+ *
+ * Rules: those of the seeded encryption for the two encrypt calls -- refused between mkhe_capture_begin and mkhe_capture_end and on a context
+ * that owns a subset of the moduli; 1 <= count <= 65535; raw buffers 16-byte aligned; the ncdt rules of kind 1; outputs distinct, over one
+ * party, with level + 1 limbs; messages start with the function's name; a refused call has enqueued nothing.  In addition:
+ *   - An (a_key, a_nonce) pair serves ONE encrypt call under a given secret key: a repeated a with two plaintexts gives c0 - c0' =
+ *     pt - pt' + e - e', which REVEALS THE DIFFERENCE of the plaintexts.  The caller keeps a counter.  (a_key, a_nonce) are public all the same.
+ *   - a_key equal to e_key word for word is refused: the public seed would publish the key of the secret stream.
+ *   - e_key travels in the kernel arguments of one launch only.  The work buffer that held NTT(c1) * s -- which gives s away, c1 being public --
+ *     and the staged e are wiped behind the finish kernel.
+ *   - CKKS, mkrlwe and BFV contexts alike. */
+/* diagnostic / test: dev_out = uint64[count][limbs][N], rows (b, j) as defined above; 1 <= limbs <= nQ.  count > 16 stages a pointer table,
+ * which synchronises (and is refused inside a capture). */
+int  mkhe_sample_uniform(mkhe_ctx* ctx, int limbs, int count, const uint32_t a_key[8], uint64_t a_nonce, void* dev_out);
+/* e = host int32[count][N] (as mkhe_encrypt takes its samples): e_b is row b */
+int  mkhe_encrypt_sk(mkhe_ctx* ctx, int level, int count, const void* dev_sk, const void* dev_pt, int pt_is_ntt,
+                     const uint32_t a_key[8], uint64_t a_nonce, const int32_t* e, mkhe_ct* const* out);
+/* e_b = stream b of the SECRET (e_key, e_nonce), kind 1 on cdt: formed in registers by the finish kernel, never in memory -- bit for bit
+ * mkhe_encrypt_sk on those samples.  Nothing but the arguments crosses the bus, and for count <= 16 the call does not synchronise with the host. */
+int  mkhe_encrypt_sk_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_sk, const void* dev_pt, int pt_is_ntt,
+                            const uint32_t a_key[8], uint64_t a_nonce, const uint32_t e_key[8], uint64_t e_nonce,
+                            const uint64_t* cdt, int ncdt, mkhe_ct* const* out);
+/* receiver: writes polynomial 1 of out[b] (one party, any limb count <= nQ, the same for every out of the call) = rows (b, j), j < limbs(out[b]);
+ * polynomial 0 is left untouched.  One launch; count > 16 stages a pointer table, which synchronises (and is refused inside a capture). */
+int  mkhe_ct_expand_seeded(mkhe_ctx* ctx, int count, const uint32_t a_key[8], uint64_t a_nonce, mkhe_ct* const* out);
 /* PartialDecrypt decryptor.go:26-43: slot = 1 .. n names the party (the ciphertext slot of its polynomial); out is over the ids of
  * `in` without that one, at the same level: out[0] = in[0] + c_slot*sk (one ring.Add), the other polynomials are copied.
  * WARNING: the output REVEALS THE SECRET KEY of whoever ran the call to anyone who sees it: in[0] and c_slot are public and c_slot is

@@ -415,6 +415,138 @@ class Encryptor {
     Parameters& params;
 };
 
+// `count` fresh ciphertexts of party `id` at `level` in their half-size form (include/mkhe.h, "secret-key encryption"): the c0 polynomials -- polynomial 0
+// of `count` device ciphertexts whose polynomial 1 is not yet written -- plus the PUBLIC (Key, Nonce) that c1 is expanded from.  download gives what
+// travels (uint64[count][level+1][N] and the seed); the receiver builds one with upload and calls Expand.  Only fresh ciphertexts have a seed.
+class SeededCiphertext {
+  public:
+    // over ready (uninitialised) ciphertexts of one party at one level: what the scheme wrappers pass in their own Ciphertext type
+    SeededCiphertext(Parameters& p, std::string id, int level, std::vector<std::shared_ptr<Ciphertext>> cts_)
+        : params(p), ID(std::move(id)), Level(level), Count((int)cts_.size()), cts(std::move(cts_)) {
+        if (Count < 1 || Count > 65535) throw Error("SeededCiphertext: count must be 1 .. 65535");
+    }
+    SeededCiphertext(Parameters& p, std::string id, int level, int count = 1) : SeededCiphertext(p, id, level, fresh(p, id, level, count)) {}
+    void SetSeed(const uint32_t key[8], uint64_t nonce) { std::copy(key, key + 8, Key); Nonce = nonce; seeded_ = true; }
+    size_t words() const { return (size_t)Count * (Level + 1) * params.N(); }
+    void download(uint64_t* c0) const {
+        if (!seeded_) throw Error("SeededCiphertext: nothing to download (no seed yet)");
+        for (int b = 0; b < Count; ++b) { auto rows = limbs(c0, b); check(mkhe_ct_download_poly_limbs(params.ctx, cts[b]->h, 0, rows.data())); }
+    }
+    void upload(const uint64_t* c0, const uint32_t key[8], uint64_t nonce) {
+        if (expanded_) throw Error("SeededCiphertext: already expanded");
+        SetSeed(key, nonce);
+        for (int b = 0; b < Count; ++b) { auto rows = limbs(const_cast<uint64_t*>(c0), b); check(mkhe_ct_upload_poly_limbs(params.ctx, cts[b]->h, 0, rows.data())); }
+    }
+    // mkhe_ct_expand_seeded writes polynomial 1: the ciphertexts that hold c0 become ordinary ciphertexts over {ID}, no copy
+    const std::vector<std::shared_ptr<Ciphertext>>& Expand() {
+        if (!seeded_) throw Error("SeededCiphertext: nothing to expand (no seed yet)");
+        if (!expanded_) {
+            std::vector<mkhe_ct*> out;
+            for (auto& c : cts) out.push_back(c->h);
+            check(mkhe_ct_expand_seeded(params.ctx, Count, Key, Nonce, out.data()));
+            expanded_ = true;
+        }
+        return cts;
+    }
+    void MarkExpanded() { expanded_ = true; }             // (an encrypt call has written polynomial 1 as well)
+    static std::vector<std::shared_ptr<Ciphertext>> fresh(Parameters& p, const std::string& id, int level, int count) {
+        std::vector<std::shared_ptr<Ciphertext>> v;
+        for (int b = 0; b < count; ++b) v.push_back(std::make_shared<Ciphertext>(p, IDSet{id}, level, false));
+        return v;
+    }
+    // what a fresh ciphertext costs on the wire: c0 + 32 bytes of seed + 8 of nonce, or both polynomials
+    static size_t WireBytes(int limbs, int N, bool seeded) { return seeded ? (size_t)limbs * N * 8 + 40 : 2 * (size_t)limbs * N * 8; }
+    Parameters& params;
+    std::string ID;
+    int Level, Count;
+    uint32_t Key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t Nonce = 0;
+    std::vector<std::shared_ptr<Ciphertext>> cts;
+  private:
+    template <class T> std::vector<T*> limbs(T* c0, int b) const {
+        std::vector<T*> rows;
+        for (int l = 0; l <= Level; ++l) rows.push_back(c0 + ((size_t)b * (Level + 1) + l) * params.N());
+        return rows;
+    }
+    bool seeded_ = false, expanded_ = false;
+};
+
+// Encryption under the party's OWN secret key with c1 expanded from a public seed: c1 = a, c0 = pt + e - a s (include/mkhe.h, "secret-key
+// encryption"; no reference counterpart).  seed: 32 PUBLIC bytes from the caller's CSPRNG; every engine call takes one value of the encryptor's own
+// locked 64-bit counter as the nonce of a, so that an (a_key, a_nonce) pair serves one call.  e: int32[count][N] from the caller's CSPRNG -- or a
+// DeviceSampler, from whose key the engine forms it in registers (mkhe_encrypt_sk_seeded).  Plaintexts are device buffers uint64[count][level+1][N].
+class SecretKeyEncryptor {
+  public:
+    SecretKeyEncryptor(Parameters& p, const SecretKey& sk_, const uint32_t seed[8]) : params(p), sk(sk_) { std::copy(seed, seed + 8, seed_); }
+    SecretKeyEncryptor(const SecretKeyEncryptor&) = delete;
+    SecretKeyEncryptor& operator=(const SecretKeyEncryptor&) = delete;
+    uint64_t NextNonce() {
+        std::lock_guard<std::mutex> g(m_);
+        if (counter_ == ~0ull) throw Error("SecretKeyEncryptor: the 64-bit call counter is exhausted -- use a fresh seed");
+        return counter_++;
+    }
+    uint64_t Counter() const { return counter_; }
+    const uint32_t* Seed() const { return seed_; }
+    void Encrypt(const void* dev_pt, Ciphertext& ctOut, DeviceSampler& sampler, bool ptIsNTT = false) {
+        own(ctOut);
+        mkhe_ct* out[1] = {ctOut.h};
+        call(ctOut.Level(), 1, dev_pt, ptIsNTT, &sampler, nullptr, out);
+    }
+    void Encrypt(const void* dev_pt, Ciphertext& ctOut, const int32_t* e, bool ptIsNTT = false) {
+        own(ctOut);
+        mkhe_ct* out[1] = {ctOut.h};
+        call(ctOut.Level(), 1, dev_pt, ptIsNTT, nullptr, e, out);
+    }
+    std::vector<std::shared_ptr<Ciphertext>> EncryptBatch(int level, int count, const void* dev_pt, DeviceSampler& sampler, bool ptIsNTT = false) {
+        auto cts = SeededCiphertext::fresh(params, sk.ID, level, count);
+        into(cts, level, dev_pt, ptIsNTT, &sampler, nullptr);
+        return cts;
+    }
+    std::vector<std::shared_ptr<Ciphertext>> EncryptBatch(int level, int count, const void* dev_pt, const int32_t* e, bool ptIsNTT = false) {
+        auto cts = SeededCiphertext::fresh(params, sk.ID, level, count);
+        into(cts, level, dev_pt, ptIsNTT, nullptr, e);
+        return cts;
+    }
+    // the same call, returned in the half-size form
+    std::shared_ptr<SeededCiphertext> EncryptSeededBatch(int level, int count, const void* dev_pt, DeviceSampler& sampler, bool ptIsNTT = false) {
+        return seeded(std::make_shared<SeededCiphertext>(params, sk.ID, level, count), dev_pt, ptIsNTT, &sampler, nullptr);
+    }
+    std::shared_ptr<SeededCiphertext> EncryptSeededBatch(int level, int count, const void* dev_pt, const int32_t* e, bool ptIsNTT = false) {
+        return seeded(std::make_shared<SeededCiphertext>(params, sk.ID, level, count), dev_pt, ptIsNTT, nullptr, e);
+    }
+    Parameters& params;
+    const SecretKey& sk;
+  protected:
+    // one engine call into ready ciphertexts (any subclass of Ciphertext); returns the nonce of a it used
+    template <class Ct> uint64_t into(const std::vector<std::shared_ptr<Ct>>& cts, int level, const void* dev_pt, bool ptIsNTT, DeviceSampler* sampler, const int32_t* e) {
+        std::vector<mkhe_ct*> out;
+        for (auto& c : cts) out.push_back(c->h);
+        return call(level, (int)cts.size(), dev_pt, ptIsNTT, sampler, e, out.data());
+    }
+    std::shared_ptr<SeededCiphertext> seeded(std::shared_ptr<SeededCiphertext> sc, const void* dev_pt, bool ptIsNTT, DeviceSampler* sampler, const int32_t* e) {
+        const uint64_t nonce = into(sc->cts, sc->Level, dev_pt, ptIsNTT, sampler, e);
+        sc->SetSeed(seed_, nonce);
+        sc->MarkExpanded();
+        return sc;
+    }
+  private:
+    void own(const Ciphertext& ct) const {
+        if (ct.ids.size() != 1 || ct.ids[0] != sk.ID) throw Error("Cannot Encrypt: ctOut must be a ciphertext over the id of sk alone");
+    }
+    uint64_t call(int level, int count, const void* dev_pt, bool ptIsNTT, DeviceSampler* sampler, const int32_t* e, mkhe_ct* const* out) {
+        const uint64_t nonce = NextNonce();
+        if (sampler)
+            check(mkhe_encrypt_sk_seeded(params.ctx, level, count, sk.Value.d, dev_pt, ptIsNTT ? 1 : 0, seed_, nonce, sampler->Key(), sampler->NextNonce(),
+                                         sampler->cdt.data(), (int)sampler->cdt.size(), out));
+        else
+            check(mkhe_encrypt_sk(params.ctx, level, count, sk.Value.d, dev_pt, ptIsNTT ? 1 : 0, seed_, nonce, e, out));
+        return nonce;
+    }
+    uint32_t seed_[8];
+    uint64_t counter_ = 0;
+    std::mutex m_;
+};
+
 // What one party publishes in distributed decryption (include/mkhe.h, "distributed decryption"): mu = c_id * s_id + e for `count` ciphertexts at
 // `level`, uint64[count][level+1][N] on the device.  Shares travel between parties: Value.download on one side, Value.upload on the other.
 struct DecryptionShare {
@@ -861,6 +993,42 @@ class PublicKeySwitcher : public mkrlwe::PublicKeySwitcher {
   private:
     Parameters& ckks;
 };
+// mkrlwe::SeededCiphertext over mkckks ciphertexts with `scale`: ExpandCkks gives them in their own type
+class SeededCiphertext : public mkrlwe::SeededCiphertext {
+  public:
+    SeededCiphertext(Parameters& p, const std::string& id, int level, int count, double scale)
+        : mkrlwe::SeededCiphertext(p, id, level, fresh_ckks(p, id, level, count, scale)), Scale(scale) {}
+    std::vector<std::shared_ptr<Ciphertext>> ExpandCkks() {
+        std::vector<std::shared_ptr<Ciphertext>> out;
+        for (auto& c : Expand()) out.push_back(std::static_pointer_cast<Ciphertext>(c));
+        return out;
+    }
+    double Scale;
+  private:
+    static std::vector<std::shared_ptr<mkrlwe::Ciphertext>> fresh_ckks(Parameters& p, const std::string& id, int level, int count, double scale) {
+        std::vector<std::shared_ptr<mkrlwe::Ciphertext>> v;
+        for (int b = 0; b < count; ++b) v.push_back(std::make_shared<Ciphertext>(p, mkrlwe::IDSet{id}, level, scale, false));
+        return v;
+    }
+};
+// mkrlwe::SecretKeyEncryptor on mkckks ciphertexts (plaintexts at `level` with `scale`: the output of Encoder::Encode on the device)
+class SecretKeyEncryptor : public mkrlwe::SecretKeyEncryptor {
+  public:
+    SecretKeyEncryptor(Parameters& p, const mkrlwe::SecretKey& sk_, const uint32_t seed[8]) : mkrlwe::SecretKeyEncryptor(p, sk_, seed), ckks(p) {}
+    std::vector<std::shared_ptr<Ciphertext>> EncryptPtxtBatch(int level, int count, const void* dev_pt, double scale, mkrlwe::DeviceSampler& sampler) {
+        std::vector<std::shared_ptr<Ciphertext>> cts;
+        for (int b = 0; b < count; ++b) cts.push_back(std::make_shared<Ciphertext>(ckks, mkrlwe::IDSet{sk.ID}, level, scale, false));
+        into(cts, level, dev_pt, false, &sampler, nullptr);
+        return cts;
+    }
+    std::shared_ptr<SeededCiphertext> EncryptPtxtSeeded(int level, int count, const void* dev_pt, double scale, mkrlwe::DeviceSampler& sampler) {
+        auto sc = std::make_shared<SeededCiphertext>(ckks, sk.ID, level, count, scale);
+        seeded(sc, dev_pt, false, &sampler, nullptr);
+        return sc;
+    }
+  private:
+    Parameters& ckks;
+};
 }  // namespace mkckks
 
 namespace mkbfv {
@@ -1083,6 +1251,40 @@ class PublicKeySwitcher : public mkrlwe::PublicKeySwitcher {
     }
     std::shared_ptr<Ciphertext> MergeNew(const mkrlwe::Ciphertext& ct, const std::vector<const mkrlwe::PublicKeySwitchShare*>& shares, const std::string& recipient) {
         return MergeBatch({&ct}, shares, recipient)[0];
+    }
+  private:
+    Parameters& bfv;
+};
+// mkrlwe::SeededCiphertext over mkbfv ciphertexts (always at the maximum level): ExpandBfv gives them in their own type
+class SeededCiphertext : public mkrlwe::SeededCiphertext {
+  public:
+    SeededCiphertext(Parameters& p, const std::string& id, int count = 1) : mkrlwe::SeededCiphertext(p, id, p.MaxLevel(), fresh_bfv(p, id, count)) {}
+    std::vector<std::shared_ptr<Ciphertext>> ExpandBfv() {
+        std::vector<std::shared_ptr<Ciphertext>> out;
+        for (auto& c : Expand()) out.push_back(std::static_pointer_cast<Ciphertext>(c));
+        return out;
+    }
+  private:
+    static std::vector<std::shared_ptr<mkrlwe::Ciphertext>> fresh_bfv(Parameters& p, const std::string& id, int count) {
+        std::vector<std::shared_ptr<mkrlwe::Ciphertext>> v;
+        for (int b = 0; b < count; ++b) v.push_back(std::make_shared<Ciphertext>(p, mkrlwe::IDSet{id}, false));
+        return v;
+    }
+};
+// mkrlwe::SecretKeyEncryptor on mkbfv ciphertexts (plaintexts: the output of Encoder::Encode on the device)
+class SecretKeyEncryptor : public mkrlwe::SecretKeyEncryptor {
+  public:
+    SecretKeyEncryptor(Parameters& p, const mkrlwe::SecretKey& sk_, const uint32_t seed[8]) : mkrlwe::SecretKeyEncryptor(p, sk_, seed), bfv(p) {}
+    std::vector<std::shared_ptr<Ciphertext>> EncryptPtxtBatch(int count, const void* dev_pt, mkrlwe::DeviceSampler& sampler) {
+        std::vector<std::shared_ptr<Ciphertext>> cts;
+        for (int b = 0; b < count; ++b) cts.push_back(std::make_shared<Ciphertext>(bfv, mkrlwe::IDSet{sk.ID}, false));
+        into(cts, bfv.MaxLevel(), dev_pt, false, &sampler, nullptr);
+        return cts;
+    }
+    std::shared_ptr<SeededCiphertext> EncryptPtxtSeeded(int count, const void* dev_pt, mkrlwe::DeviceSampler& sampler) {
+        auto sc = std::make_shared<SeededCiphertext>(bfv, sk.ID, count);
+        seeded(sc, dev_pt, false, &sampler, nullptr);
+        return sc;
     }
   private:
     Parameters& bfv;

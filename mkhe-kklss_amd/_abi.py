@@ -117,6 +117,10 @@ SIGNATURES = {
     "mkhe_encrypt": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, s32p, vpp]),
     "mkhe_sample_small": (C.c_int, [vp, C.c_int, C.c_int, u32p, C.c_uint64, C.c_uint32, u64p, C.c_int, vp]),
     "mkhe_encrypt_seeded": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, u32p, C.c_uint64, u64p, C.c_int, vpp]),
+    "mkhe_sample_uniform": (C.c_int, [vp, C.c_int, C.c_int, u32p, C.c_uint64, vp]),
+    "mkhe_encrypt_sk": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, u32p, C.c_uint64, s32p, vpp]),
+    "mkhe_encrypt_sk_seeded": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, u32p, C.c_uint64, u32p, C.c_uint64, u64p, C.c_int, vpp]),
+    "mkhe_ct_expand_seeded": (C.c_int, [vp, C.c_int, u32p, C.c_uint64, vpp]),
     "mkhe_partial_decrypt": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "mkhe_decrypt": (C.c_int, [vp, vp, vpp, vp]),
     "mkhe_decrypt_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, u32p, C.c_uint64, C.c_int, vp]),

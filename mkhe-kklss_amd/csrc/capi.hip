@@ -752,6 +752,90 @@ int mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk,
         c->encrypt_seeded(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, key, nonce, cdt, ncdt, d.data());
     })
 }
+// secret-key encryption with a seeded c1.  The two encrypt calls are under the rules of the seeded encryption (smp_need); the sampler and the
+// expansion read a PUBLIC stream and may be captured as long as they stage no pointer table (count at most 16).
+static Context* sku_need(mkhe_ctx* ctx, const char* what, int count, const uint32_t* key) {
+    if (!ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    if (!key) throw Error(std::string(what) + ": null key");
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone && count > ED_INLINE)
+        throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end with more than 16 items (the pointer table is staged)");
+    return c;
+}
+static std::vector<u64*> sk_outputs(mkhe_ctx* ctx, const char* what, int count, int limbs, mkhe_ct* const* out) {
+    auto o = ct_list_out(ctx, out, count, what);
+    std::vector<u64*> d(count);
+    for (int b = 0; b < count; ++b) {
+        if (o[b]->n != 1) throw Error(std::string(what) + ": every out must be a ciphertext over exactly one party");
+        if (o[b]->limbs != (limbs ? limbs : o[0]->limbs)) throw Error(std::string(what) + (limbs ? ": every out must have level+1 limbs" : ": every out must be at the same level"));
+        for (int k = 0; k < b; ++k) if (d[k] == o[b]->d) throw Error(std::string(what) + ": the outputs of a batch must be distinct");
+        d[b] = o[b]->d;
+    }
+    return d;
+}
+int mkhe_sample_uniform(mkhe_ctx* ctx, int limbs, int count, const uint32_t a_key[8], uint64_t a_nonce, void* dev_out) {
+    MKHE_TRY({
+        const char* what = "mkhe_sample_uniform";
+        Context* c = sku_need(ctx, what, count, a_key);
+        if (!dev_out) throw Error("mkhe_sample_uniform: null output");
+        if (limbs < 1 || limbs > c->nq) throw Error("mkhe_sample_uniform: limbs must be 1 .. nQ");
+        need_aligned(dev_out, what);
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        c->sample_uniform(limbs, count, a_key, a_nonce, (u64*)dev_out);
+    })
+}
+int mkhe_ct_expand_seeded(mkhe_ctx* ctx, int count, const uint32_t a_key[8], uint64_t a_nonce, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_ct_expand_seeded";
+        Context* c = sku_need(ctx, what, count, a_key);
+        if (!out) throw Error("mkhe_ct_expand_seeded: null argument");
+        for (int b = 0; b < count; ++b) if (!out[b]) throw Error("mkhe_ct_expand_seeded: null output in the batch");
+        for (int b = 0; b < count; ++b) {
+            if (out[b]->c.n != 1) throw Error("mkhe_ct_expand_seeded: every out must be a ciphertext over exactly one party");
+            if (out[b]->c.limbs != out[0]->c.limbs) throw Error("mkhe_ct_expand_seeded: every out must be at the same level");
+        }
+        MKHE_HIP(hipSetDevice(c->device));
+        g_last_ctx = c;
+        auto d = sk_outputs(ctx, what, count, 0, out);
+        c->ct_expand_seeded(count, out[0]->c.limbs, a_key, a_nonce, d.data());
+    })
+}
+static void sk_encrypt_args_ok(Context* c, const char* what, int level, int count, const void* dev_sk, const void* dev_pt, const uint32_t* a_key, mkhe_ct* const* out) {
+    if (!dev_sk || !dev_pt || !a_key || !out) throw Error(std::string(what) + ": null argument");
+    if (level < 0 || level >= c->nq) throw Error(std::string(what) + ": level out of range");
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    need_aligned(dev_sk, what); need_aligned(dev_pt, what);
+}
+int mkhe_encrypt_sk(mkhe_ctx* ctx, int level, int count, const void* dev_sk, const void* dev_pt, int pt_is_ntt, const uint32_t a_key[8], uint64_t a_nonce,
+                    const int32_t* e, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_encrypt_sk";
+        Context* c = smp_need(ctx, what, a_key, false, nullptr, 0);
+        if (!e) throw Error("mkhe_encrypt_sk: null argument");
+        sk_encrypt_args_ok(c, what, level, count, dev_sk, dev_pt, a_key, out);
+        auto d = sk_outputs(ctx, what, count, level + 1, out);
+        c->encrypt_sk(level, count, (const u64*)dev_sk, (const u64*)dev_pt, pt_is_ntt != 0, a_key, a_nonce, e, nullptr, 0, nullptr, 0, d.data(), what);
+    })
+}
+int mkhe_encrypt_sk_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_sk, const void* dev_pt, int pt_is_ntt, const uint32_t a_key[8],
+                           uint64_t a_nonce, const uint32_t e_key[8], uint64_t e_nonce, const uint64_t* cdt, int ncdt, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_encrypt_sk_seeded";
+        Context* c = smp_need(ctx, what, e_key, true, cdt, ncdt);
+        sk_encrypt_args_ok(c, what, level, count, dev_sk, dev_pt, a_key, out);
+        bool same = true;
+        for (int i = 0; i < 8; ++i) same = same && a_key[i] == e_key[i];
+        if (same) throw Error("mkhe_encrypt_sk_seeded: a_key must differ from e_key (the public seed would publish the key of the secret stream)");
+        auto d = sk_outputs(ctx, what, count, level + 1, out);
+        c->encrypt_sk(level, count, (const u64*)dev_sk, (const u64*)dev_pt, pt_is_ntt != 0, a_key, a_nonce, nullptr, e_key, e_nonce, cdt, ncdt, d.data(), what);
+    })
+}
 int mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out) {
     MKHE_TRY({ mark(ctx, in, out);
         if (!in || !dev_sk || !out) throw Error("mkhe_partial_decrypt: null argument");

@@ -1,7 +1,7 @@
 // chacha.h -- the quarter round of the ChaCha20 block function (RFC 8439 section 2.1), shared by the kernels that expand the keystream of
 // include/mkhe.h ("device-side sampling"): small_sample_kernel (encdec_kernels.hip), share_finish_kernel (decshare_kernels.hip), refresh_finish_kernel
-// (refresh_kernels.hip), bfv_refresh_finish_kernel (bfv_refresh_kernels.hip) and pcks_finish_kernel (pcks_kernels.hip); and the block as the 64-bit values
-// of its 8 coefficients, for the three last.
+// (refresh_kernels.hip), bfv_refresh_finish_kernel (bfv_refresh_kernels.hip), pcks_finish_kernel (pcks_kernels.hip) and the two sampling kernels of
+// skenc_kernels.hip; and the block as the 64-bit values of its 8 coefficients, for the four last.
 #pragma once
 #include "modarith.h"
 

@@ -1,6 +1,6 @@
-// ed_access.h -- what the streaming kernels of encdec_kernels.hip, decshare_kernels.hip, refresh_kernels.hip, bfv_refresh_kernels.hip and pcks_kernels.hip
-// share: the launch shape (256 threads, grid.x over PAIRS of coefficients), the 16-byte accesses and the lookup of a pointer table.  Included by those
-// five files only (the names are short).
+// ed_access.h -- what the streaming kernels of encdec_kernels.hip, decshare_kernels.hip, refresh_kernels.hip, bfv_refresh_kernels.hip, pcks_kernels.hip
+// and skenc_kernels.hip share: the launch shape (256 threads, grid.x over PAIRS of coefficients), the 16-byte accesses and the lookup of a pointer
+// table.  Included by those six files only (the names are short).
 #pragma once
 #include "encdec_kernels.h"
 

@@ -188,6 +188,13 @@ void Context::share_product(const std::vector<const Ct*>& ins, const int* slots,
 
 void Context::share_gather_ntt(const std::vector<const Ct*>& ins, const int* slots, u64* w) {
     const int count = (int)ins.size(), L = ins[0]->limbs;
+    std::vector<const u64*> src(count);
+    for (int b = 0; b < count; ++b) src[b] = ins[b]->d + (size_t)slots[b] * L * N;
+    gather_ntt(src, L, w);
+}
+
+void Context::gather_ntt(const std::vector<const u64*>& src, int L, u64* w) {
+    const int count = (int)src.size();
     const size_t pw = (size_t)L * N;
     for (int base = 0; base < count; base += NTT_MAX_ITEMS) {
         const int cnt = std::min(NTT_MAX_ITEMS, count - base);
@@ -195,7 +202,7 @@ void Context::share_gather_ntt(const std::vector<const Ct*>& ins, const int* slo
         b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
         b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)pw;
         b.nitems = cnt; b.outers_per_item = 1; b.nouter = cnt;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d + (size_t)slots[base + i] * pw; b.dst_items[i] = w + (size_t)(base + i) * pw; }
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = src[base + i]; b.dst_items[i] = w + (size_t)(base + i) * pw; }
         ntt_fwd_launch(b, false);
     }
 }
@@ -442,6 +449,84 @@ void Context::pcks_merge(const std::vector<const Ct*>& ins, const std::vector<co
         ProfScope ps(this, PROF_OTHER, 8.0 * N * L * count * (3.0 + 2.0 * (double)shares.size()));
         launch_pcks_merge(count, (int)shares.size(), ot, ct, st, d_mods, L, N, s_);
     }
+    MKHE_HIP(hipGetLastError());
+}
+
+// ---- secret-key encryption with a seeded c1 (include/mkhe.h; skenc_kernels.h).  One launch set whatever count is: uniform_sample writes a_b
+// straight into polynomial 1 of outs[b]; the gathering forward NTT reads it into w [count][L][N]; skenc_mul (w <- w * sk, or pt - w * sk for a
+// plaintext in the NTT domain); one inverse NTT; skenc_finish writes polynomial 0.  NTT(c1) * s gives s away (c1 is public and invertible with
+// overwhelming probability): w, and the staged e of the host-sample call, are wiped behind the finish kernel.
+static void uniform_args_fill(UniformArgs& a, const u32* key, u64 nonce) {
+    for (int i = 0; i < 8; ++i) a.key[i] = key[i];
+    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32);
+}
+
+void Context::sample_uniform(int limbs, int count, const u32* key, u64 nonce, u64* dev_out) {
+    if (masked_) throw Error("mkhe_sample_uniform: not available on a context that owns a subset of the moduli");
+    std::vector<const u64*> o(count);
+    for (int b = 0; b < count; ++b) o[b] = dev_out + (size_t)b * limbs * N;
+    scratch(ed_tab_, (size_t)count);
+    const EdTable ot = ed_table(o, 0);                                      // count > ED_INLINE: staged, which synchronises
+    UniformArgs a;
+    uniform_args_fill(a, key, nonce);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * count * limbs * N);
+        launch_uniform_sample(a, count, ot, 0, d_mods, limbs, nq, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::ct_expand_seeded(int count, int limbs, const u32* key, u64 nonce, u64* const* outs) {
+    if (masked_) throw Error("mkhe_ct_expand_seeded: not available on a context that owns a subset of the moduli");
+    scratch(ed_tab_, (size_t)count);
+    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0);
+    UniformArgs a;
+    uniform_args_fill(a, key, nonce);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * count * limbs * N);
+        launch_uniform_sample(a, count, ot, (long)limbs * N, d_mods, limbs, nq, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::encrypt_sk(int level, int count, const u64* sk, const u64* pt, bool pt_is_ntt, const u32* a_key, u64 a_nonce, const int32_t* e,
+                         const u32* e_key, u64 e_nonce, const u64* cdt, int ncdt, u64* const* outs, const char* what) {
+    check_level(level);
+    if (masked_) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    const int L = level + 1;
+    const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
+    u64* w = scratch(ed_w_, pw);
+    int32_t* small = e ? reinterpret_cast<int32_t*>(scratch(ed_small_, (sn + 1) / 2)) : nullptr;
+    scratch(ed_tab_, (size_t)count);
+    const std::vector<const u64*> o(outs, outs + count);
+    const EdTable ot = ed_table(o, 0);                                      // count > ED_INLINE: staged, which synchronises
+    if (e) {
+        MKHE_HIP(hipMemcpyAsync(small, e, sn * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        sync();                                                             // the host array may be pageable: do not return before it is consumed
+    }
+    UniformArgs ua;
+    uniform_args_fill(ua, a_key, a_nonce);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * count * L * N);
+        launch_uniform_sample(ua, count, ot, (long)L * N, d_mods, L, nq, N, s_);
+    }
+    std::vector<const u64*> c1(count);
+    for (int b = 0; b < count; ++b) c1[b] = o[b] + (size_t)L * N;
+    gather_ntt(c1, L, w);
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (count * (pt_is_ntt ? 3.0 : 2.0) + 1.0));
+        launch_skenc_mul(count, w, sk, pt_is_ntt ? pt : nullptr, d_mods, L, N, s_);
+    }
+    ntt(w, w, count, L, 0, true, false);
+    SmallSampleArgs a{};                                                    // (not read when the samples are in memory)
+    if (!e) sample_args_fill(a, e_key, e_nonce, 0, cdt, ncdt);
+    {
+        ProfScope ps(this, PROF_OTHER, (double)count * N * L * (pt_is_ntt ? 16.0 : 24.0) + (e ? 4.0 * count * N * L : 64.0 * (N / 8) * count * L));
+        launch_skenc_finish(a, small, count, ot, w, pt_is_ntt ? nullptr : pt, d_mods, L, N, s_);
+    }
+    sample_args_wipe(a);                                                    // the runtime has copied the arguments
+    if (e) MKHE_HIP(hipMemsetAsync(small, 0, sn * sizeof(int32_t), s_));
+    MKHE_HIP(hipMemsetAsync(w, 0, pw * sizeof(u64), s_));
     MKHE_HIP(hipGetLastError());
 }
 

@@ -23,6 +23,7 @@
 #include "refresh_kernels.h"
 #include "bfv_refresh_kernels.h"
 #include "pcks_kernels.h"
+#include "skenc_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -315,6 +316,16 @@ class Context {
                     const u64* cdt, int ncdt, u64* shares);
     // outs[b] [2][L][N] <- (ins[b] polynomial 0 + sum_i shares[i][b][0], sum_i shares[i][b][1]), canonical
     void pcks_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* const* outs);
+    // secret-key encryption with a seeded c1 (include/mkhe.h; skenc_kernels.h): polynomial 1 of outs[b] [2][level+1][N] <- the rows (b, j) of kind 6
+    // of the keystream under the PUBLIC (a_key, a_nonce), polynomial 0 <- pt + e_b - c1 * sk.  e != null: host int32 [count][N] (e_key, cdt unread);
+    // e == null: e_b = kind 1 on stream b of the SECRET (e_key, e_nonce), formed in registers.  what = the C entry point (for messages).  No host
+    // synchronisation for count <= ED_INLINE and e == null.  The caller (capi.hip) has checked shapes, keys and the capture.
+    void encrypt_sk(int level, int count, const u64* sk, const u64* pt, bool pt_is_ntt, const u32* a_key, u64 a_nonce, const int32_t* e,
+                    const u32* e_key, u64 e_nonce, const u64* cdt, int ncdt, u64* const* outs, const char* what);
+    // dev_out [count][limbs][N] <- the rows (b, j), j < limbs, of kind 6 under (key, nonce)
+    void sample_uniform(int limbs, int count, const u32* key, u64 nonce, u64* dev_out);
+    // polynomial 1 of outs[b] [2][limbs][N] <- the rows (b, j), j < limbs; polynomial 0 is not touched
+    void ct_expand_seeded(int count, int limbs, const u32* key, u64 nonce, u64* const* outs);
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).
@@ -441,6 +452,8 @@ class Context {
     void share_product(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, u64* w);
     // w [count][L][N] <- NTT(polynomial slots[b] of ins[b]): one gathering forward transform (per NTT_MAX_ITEMS items)
     void share_gather_ntt(const std::vector<const Ct*>& ins, const int* slots, u64* w);
+    // w [count][L][N] <- NTT(src[b] [L][N]), the same gathering transform on bare polynomials
+    void gather_ntt(const std::vector<const u64*>& src, int L, u64* w);
     // collective refresh: MForm(q_i mod q_j) and (q_0 .. q_l) mod q_j, [nq][nq] each in one block, built at the first merge; the digits of R
     u64* d_rf_tab_ = nullptr;
     Scratch rf_dig_;

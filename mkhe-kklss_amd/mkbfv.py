@@ -708,6 +708,60 @@ def NewEncryptor(params, sampler=None, encoder="host"):
     return Encryptor(params, sampler, encoder)
 
 
+class SeededCiphertext(mkrlwe.SeededCiphertext):
+    """mkrlwe.SeededCiphertext at the maximum level whose Expand() returns mkbfv Ciphertexts"""
+
+    def __init__(self, params, id, count=1):
+        super().__init__(params, id, params.MaxLevel(), count, cls=Ciphertext)
+
+    def Expand(self, level=None):
+        if level is not None and level != self._level:
+            raise MkheError("mkbfv.SeededCiphertext: a BFV ciphertext is always at the maximum level")
+        return super().Expand()
+
+
+class SecretKeyEncryptor(mkrlwe.SecretKeyEncryptor):
+    """mkrlwe.SecretKeyEncryptor + the encoder (no reference counterpart): a party encrypts its own slots under its secret key.
+    EncryptMsgSeeded returns the half-size form that travels; its Expand() gives what EncryptMsgBatch gives.  The encoder as for Encryptor."""
+
+    def __init__(self, params, sk, sampler=None, encoder="host", seed=None, insecure_test_only=False):
+        super().__init__(params, sk, sampler, seed, insecure_test_only)
+        if encoder not in ("host", "device"):
+            raise MkheError("mkbfv: encoder must be \"host\" or \"device\"")
+        self._which, self._encoder = encoder, None
+
+    @property
+    def encoder(self):
+        if self._encoder is None:
+            self._encoder = _encoder(self.params, self._which)
+        return self._encoder
+
+    def _new_batch(self, level, count):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [self.sk.ID], level, count)
+
+    def _new_seeded(self, level, count):
+        return SeededCiphertext(self.params, self.sk.ID, count)
+
+    def _encode(self, msgs):
+        if isinstance(self.encoder, DeviceEncoder):
+            return self.encoder.EncodeBatch(np.stack([m.Value for m in msgs]))
+        return np.stack([self.encoder.Encode(m.Value) for m in msgs])
+
+    def EncryptMsgBatch(self, msgs, e=None):
+        """one encode (one launch set with the device encoder) and one mkhe_encrypt_sk / mkhe_encrypt_sk_seeded call"""
+        return self.EncryptBatch(self._encode(msgs), e)
+
+    def EncryptMsgNew(self, msg, e=None):
+        return self.EncryptMsgBatch([msg], None if e is None else np.asarray(e)[None])[0]
+
+    def EncryptMsgSeeded(self, msgs, e=None):
+        return self.EncryptSeededBatch(self._encode(msgs), e)
+
+
+def NewSecretKeyEncryptor(params, sk, sampler=None, encoder="host", seed=None, insecure_test_only=False):
+    return SecretKeyEncryptor(params, sk, sampler, encoder, seed, insecure_test_only)
+
+
 class Decryptor(mkrlwe.Decryptor):
     """mkbfv.Decryptor (decryptor.go:6-24); the encoder as for Encryptor"""
 

@@ -1108,6 +1108,49 @@ def NewEncryptor(params, sampler=None, encoder="host"):
     return Encryptor(params, sampler, encoder)
 
 
+class SeededCiphertext(mkrlwe.SeededCiphertext):
+    """mkrlwe.SeededCiphertext whose Expand() returns mkckks Ciphertexts with `scale` (default: the scale of the parameters)"""
+
+    def __init__(self, params, id, level=None, count=1, scale=None):
+        self.Scale = params.Scale() if scale is None else float(scale)
+        super().__init__(params, id, params.MaxLevel() if level is None else level, count, cls=Ciphertext, Scale=self.Scale)
+
+
+class SecretKeyEncryptor(mkrlwe.SecretKeyEncryptor):
+    """mkrlwe.SecretKeyEncryptor + the encoder (no reference counterpart): a party encrypts its own slots under its secret key, at the maximum
+    level and the default scale.  EncryptMsgSeeded returns the half-size form that travels; its Expand() gives what EncryptMsgBatch gives."""
+
+    def __init__(self, params, sk, sampler=None, encoder="host", seed=None, insecure_test_only=False):
+        super().__init__(params, sk, sampler, seed, insecure_test_only)
+        self.encoder = _encoder(params, encoder)
+
+    def _new_batch(self, level, count):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, [self.sk.ID], level, count, Scale=self.params.Scale())
+
+    def _new_seeded(self, level, count):
+        return SeededCiphertext(self.params, self.sk.ID, level, count, self.params.Scale())
+
+    def _encode(self, msgs):
+        level, scale = self.params.MaxLevel(), self.params.Scale()
+        if isinstance(self.encoder, DeviceEncoder):
+            return self.encoder.EncodeBatch(np.stack([m.Value for m in msgs]), level, scale)
+        return np.stack([self.encoder.Encode(m.Value, level, scale) for m in msgs])
+
+    def EncryptMsgBatch(self, msgs, e=None):
+        """one encode (one launch set with the device encoder) and one mkhe_encrypt_sk / mkhe_encrypt_sk_seeded call"""
+        return self.EncryptBatch(self._encode(msgs), e)
+
+    def EncryptMsgNew(self, msg, e=None):
+        return self.EncryptMsgBatch([msg], None if e is None else np.asarray(e)[None])[0]
+
+    def EncryptMsgSeeded(self, msgs, e=None):
+        return self.EncryptSeededBatch(self._encode(msgs), e)
+
+
+def NewSecretKeyEncryptor(params, sk, sampler=None, encoder="host", seed=None, insecure_test_only=False):
+    return SecretKeyEncryptor(params, sk, sampler, encoder, seed, insecure_test_only)
+
+
 class Decryptor(mkrlwe.Decryptor):
     """mkckks.Decryptor (decryptor.go:6-24)"""
 

@@ -626,6 +626,19 @@ def small_cdt(sigma, bound=None):
     return table
 
 
+def _key_words(key, who):
+    """32 bytes or 8 words of 32 bits -> (uint32 * 8)"""
+    if isinstance(key, (bytes, bytearray)):
+        if len(key) != 32:
+            raise MkheError("%s: the key is 32 bytes" % who)
+        words = [int.from_bytes(key[4 * i: 4 * i + 4], "little") for i in range(8)]
+    else:
+        words = [int(w) for w in key]
+        if len(words) != 8 or any(not 0 <= w < (1 << 32) for w in words):
+            raise MkheError("%s: the key is 8 words of 32 bits" % who)
+    return (C.c_uint32 * 8)(*words)
+
+
 class DeviceSampler:
     """Encryption randomness drawn ON THE DEVICE: u, e0, e1 are expanded by the engine from a ChaCha20 key (include/mkhe.h, "device-side
     sampling"), so that an Encrypt moves 32 + 8 bytes of key and nonce instead of 12 N bytes of samples.  For Encryptor only: keys are
@@ -643,15 +656,7 @@ class DeviceSampler:
                             "(tests / benchmarks), or no key at all for os.urandom")
         if key is None:
             key = os.urandom(32)
-        if isinstance(key, (bytes, bytearray)):
-            if len(key) != 32:
-                raise MkheError("DeviceSampler: the key is 32 bytes")
-            words = [int.from_bytes(key[4 * i: 4 * i + 4], "little") for i in range(8)]
-        else:
-            words = [int(w) for w in key]
-            if len(words) != 8 or any(not 0 <= w < (1 << 32) for w in words):
-                raise MkheError("DeviceSampler: the key is 8 words of 32 bits")
-        self._key = (C.c_uint32 * 8)(*words)
+        self._key = _key_words(key, "DeviceSampler")
         self.sigma = float(sigma)
         self.cdt = small_cdt(self.sigma)
         self._cdt = (C.c_uint64 * len(self.cdt))(*self.cdt)
@@ -681,6 +686,10 @@ class DeviceSampler:
 
     def switch_args(self):
         """(key, nonce, cdt, ncdt) for ONE mkhe_pcks_share call: the same counter as the other calls"""
+        return self._key, self._next_nonce(), self._cdt, len(self.cdt)
+
+    def sk_encrypt_args(self):
+        """(e_key, e_nonce, cdt, ncdt) for ONE mkhe_encrypt_sk_seeded call: the same counter as the other calls"""
         return self._key, self._next_nonce(), self._cdt, len(self.cdt)
 
     def refresh_args(self):
@@ -967,6 +976,178 @@ class Encryptor:
 
 def NewEncryptor(params, sampler=None):
     return Encryptor(params, sampler)
+
+
+# ---- secret-key encryption with a seeded c1 (include/mkhe.h, "secret-key encryption"; no reference counterpart)
+class SeededCiphertext:
+    """`count` fresh ciphertexts of party `id` at `level` in their half-size form: the c0 polynomials plus the PUBLIC (Key, Nonce) that c1 is
+    expanded from (kind 6 of the keystream).  c0 lives in polynomial 0 of `count` device ciphertexts whose polynomial 1 is not yet written.
+    download() -> (c0 uint64 [count][level+1][N], key 32 bytes, nonce) is what travels; the receiver builds
+    SeededCiphertext(params, id, level, count).upload(c0, key, nonce) and calls Expand().  Only fresh ciphertexts have a seed."""
+
+    def __init__(self, params, id, level, count=1, cls=Ciphertext, **attrs):
+        if not 0 <= int(level) <= params.MaxLevel():
+            raise MkheError("SeededCiphertext: level %d out of range" % level)
+        if not 1 <= int(count) <= 65535:
+            raise MkheError("SeededCiphertext: count must be 1 .. 65535")
+        self.params, self.ID, self._level, self.count = params, id, int(level), int(count)
+        self._cls, self._attrs = cls, dict(attrs)
+        self._cts = batch_ciphertexts(cls, params, [id], self._level, self.count, **attrs)
+        self.Key, self.Nonce = None, None
+        self._expanded = False
+
+    def Level(self):
+        return self._level
+
+    def _set_seed(self, key, nonce):
+        self._key = _key_words(key, "SeededCiphertext")
+        self.Key = b"".join(int(w).to_bytes(4, "little") for w in self._key)
+        self.Nonce = int(nonce)
+        if not 0 <= self.Nonce < (1 << 64):
+            raise MkheError("SeededCiphertext: the nonce is 64 bits")
+        return self
+
+    def _limb_ptrs(self, rows):
+        return (C.c_void_p * len(rows))(*[r.ctypes.data for r in rows])
+
+    def download(self):
+        if self.Key is None:
+            raise MkheError("SeededCiphertext: nothing to download (no seed yet)")
+        N = self.params.N()
+        c0 = np.empty((self.count, self._level + 1, N), dtype=np.uint64)
+        for b, ct in enumerate(self._cts):
+            check(lib().mkhe_ct_download_poly_limbs(self.params.ctx, ct.h, 0, self._limb_ptrs(list(c0[b]))))
+        return c0, self.Key, self.Nonce
+
+    def upload(self, c0, key, nonce):
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64)
+        if c0.shape != (self.count, self._level + 1, self.params.N()):
+            raise MkheError("SeededCiphertext: expected c0 of shape %r, got %r" % ((self.count, self._level + 1, self.params.N()), c0.shape))
+        if self._expanded:
+            raise MkheError("SeededCiphertext: already expanded")
+        self._set_seed(key, nonce)
+        for b, ct in enumerate(self._cts):
+            check(lib().mkhe_ct_upload_poly_limbs(self.params.ctx, ct.h, 0, self._limb_ptrs(list(c0[b]))))
+        return self
+
+    def Expand(self, level=None):
+        """-> `count` ordinary ciphertexts over {ID}: mkhe_ct_expand_seeded writes polynomial 1.  level=None (or the level of c0): the
+        ciphertexts that hold c0 themselves, no copy.  A lower level: new ciphertexts with the first level + 1 limbs of c0 (through the host)
+        and the same rows of a -- they do not depend on the level they are expanded at."""
+        if self.Key is None:
+            raise MkheError("SeededCiphertext: nothing to expand (no seed yet)")
+        level = self._level if level is None else int(level)
+        if not 0 <= level <= self._level:
+            raise MkheError("SeededCiphertext: cannot expand at level %d (c0 is at level %d)" % (level, self._level))
+        if level == self._level:
+            outs = self._cts
+            if self._expanded:
+                return outs
+        else:
+            c0 = self.download()[0]
+            outs = batch_ciphertexts(self._cls, self.params, [self.ID], level, self.count, **self._attrs)
+            for b, ct in enumerate(outs):
+                check(lib().mkhe_ct_upload_poly_limbs(self.params.ctx, ct.h, 0, self._limb_ptrs(list(c0[b][: level + 1]))))
+        check(lib().mkhe_ct_expand_seeded(self.params.ctx, self.count, self._key, self.Nonce, handle_array([c.h for c in outs])))
+        if level == self._level:
+            self._expanded = True
+        return outs
+
+
+class SecretKeyEncryptor:
+    """Encryption under the party's OWN secret key with c1 expanded from a public seed: c1 = a, c0 = pt + e - a s (include/mkhe.h,
+    "secret-key encryption").  The phase error is e alone, and a fresh ciphertext travels as c0 plus 40 bytes (EncryptSeededBatch).
+
+    sampler: a HostSampler (default; e is drawn on the host, mkhe_encrypt_sk) or a DeviceSampler (mkhe_encrypt_sk_seeded: e is formed in
+    registers from one nonce of the sampler's counter).  seed: 32 PUBLIC bytes (default os.urandom(32)); every engine call takes one value
+    of the encryptor's own locked 64-bit counter as the nonce of a -- an (a_key, a_nonce) pair serves one call.  A given seed makes a
+    reproducible and must be acknowledged with insecure_test_only=True, the policy of DeviceSampler."""
+
+    def __init__(self, params, sk, sampler=None, seed=None, insecure_test_only=False):
+        import os
+        import threading
+        if seed is not None and not insecure_test_only:
+            raise MkheError("SecretKeyEncryptor: a given seed makes c1 reproducible -- pass insecure_test_only=True "
+                            "(tests / benchmarks), or no seed at all for os.urandom")
+        self.params, self.sk = params, sk
+        self.sampler = sampler if sampler is not None else HostSampler()
+        self._seed = _key_words(os.urandom(32) if seed is None else seed, "SecretKeyEncryptor")
+        self._lock = threading.Lock()
+        self._counter = 0
+
+    @property
+    def counter(self):
+        """the nonce of a the next engine call will use"""
+        return self._counter
+
+    def _next_nonce(self):
+        with self._lock:
+            if self._counter >= (1 << 64) - 1:
+                raise MkheError("SecretKeyEncryptor: the 64-bit call counter is exhausted -- use a fresh seed")
+            n = self._counter
+            self._counter += 1
+            return n
+
+    def _check_level(self, level):
+        if not 0 <= level <= self.params.MaxLevel():
+            raise MkheError("Cannot Encrypt: level %d out of range" % level)
+
+    def _engine_encrypt(self, level, d, pt_is_ntt, e, outs):
+        """one engine call over the plaintexts d into outs; returns the nonce of a it used"""
+        nonce = self._next_nonce()
+        args = (self.params.ctx, level, d.count, self.sk.Value.devptr(), d.devptr(), 1 if pt_is_ntt else 0, self._seed, nonce)
+        hs = handle_array([c.h for c in outs])
+        if e is None and isinstance(self.sampler, DeviceSampler):
+            check(lib().mkhe_encrypt_sk_seeded(*args, *self.sampler.sk_encrypt_args(), hs))
+        else:
+            N = self.params.N()
+            smp = _s32(self.sampler.gaussian(d.count, N) if e is None else e, (d.count, N))
+            check(lib().mkhe_encrypt_sk(*args, smp[1], hs))
+        return nonce
+
+    def _new_batch(self, level, count):
+        return batch_ciphertexts(Ciphertext, self.params, [self.sk.ID], level, count)
+
+    def _new_seeded(self, level, count):
+        return SeededCiphertext(self.params, self.sk.ID, level, count)
+
+    def Encrypt(self, pt, ctOut, e=None, pt_is_ntt=False):
+        """pt: one plaintext [limbs][N] (or DeviceLimbs of count 1) with at least ctOut.Level() + 1 limbs; e: int32 [N] (parity tests)"""
+        if ctOut.ids != [self.sk.ID]:
+            raise MkheError("Cannot Encrypt: ctOut must be a ciphertext over the id of sk alone")
+        d = pt if isinstance(pt, DeviceLimbs) else _device_plaintexts(self.params, np.asarray(pt, dtype=np.uint64)[None])
+        if d.count != 1:
+            raise MkheError("Cannot Encrypt: one plaintext expected (EncryptBatch takes several)")
+        level = ctOut.Level()
+        self._check_level(level)
+        if d.limbs != level + 1:
+            raise MkheError("Cannot Encrypt: the plaintext must have the limbs of ctOut")
+        self._engine_encrypt(level, d, pt_is_ntt, None if e is None else np.asarray(e)[None], [ctOut])
+        return ctOut
+
+    def EncryptBatch(self, pts, e=None, pt_is_ntt=False):
+        """B plaintexts ([B][level+1][N]) as ONE engine call; e: int32 [B][N].  Returns the list of B ciphertexts over {sk.ID}."""
+        d = _device_plaintexts(self.params, pts)
+        level = d.limbs - 1
+        self._check_level(level)
+        outs = self._new_batch(level, d.count)
+        self._engine_encrypt(level, d, pt_is_ntt, e, outs)
+        return outs
+
+    def EncryptSeededBatch(self, pts, e=None, pt_is_ntt=False):
+        """the same call, returned in the half-size form: a SeededCiphertext (c0 on the device, the seed and the nonce of this call)"""
+        d = _device_plaintexts(self.params, pts)
+        level = d.limbs - 1
+        self._check_level(level)
+        sc = self._new_seeded(level, d.count)
+        nonce = self._engine_encrypt(level, d, pt_is_ntt, e, sc._cts)
+        sc._set_seed(self._seed, nonce)
+        sc._expanded = True                                 # (the engine has written polynomial 1 as well: Expand() has nothing left to do)
+        return sc
+
+
+def NewSecretKeyEncryptor(params, sk, sampler=None, seed=None, insecure_test_only=False):
+    return SecretKeyEncryptor(params, sk, sampler, seed, insecure_test_only)
 
 
 class DecryptionShare:

@@ -1,0 +1,38 @@
+"""The three kernels of secret-key encryption with a seeded c1 on the ISA hipcc makes for gfx950 (no GPU): uniform_sample_kernel forms kind 6 of
+the keystream in registers, skenc_mul_kernel streams, skenc_finish_kernel forms e in registers, so none may spill, use scratch or touch LDS; each
+fits eight waves per SIMD (at most 64 VGPRs: the occupancy step the printed counts fall under).  The register counts are printed (DESIGN.md 4.5n
+quotes them)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def asm():
+    src = os.path.join(ROOT, "mkhe-kklss_amd", "csrc", "skenc_kernels.hip")
+    r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S", "--cuda-device-only",
+                        src, "-o", "-"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-1500:]
+    return r.stdout
+
+
+def resources(asm, kernel):
+    meta = [b for b in asm.split("- .agpr_count:")[1:] if kernel in b]
+    assert len(meta) == 1, kernel
+    keys = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
+    return {k: int(re.search(r"\.%s:\s+(\d+)" % k, meta[0]).group(1)) for k in keys}
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.parametrize("kernel,vgprs", [("uniform_sample_kernel", 64), ("skenc_mul_kernel", 64), ("skenc_finish_kernel", 64)])
+def test_no_spill_no_scratch_no_lds(asm, kernel, vgprs):
+    res = resources(asm, kernel)
+    print("%s: %d VGPRs, %d SGPRs" % (kernel, res["vgpr_count"], res["sgpr_count"]))
+    assert res["vgpr_spill_count"] == 0 and res["sgpr_spill_count"] == 0
+    assert res["private_segment_fixed_size"] == 0 and res["group_segment_fixed_size"] == 0
+    assert res["vgpr_count"] <= vgprs                           # eight waves per SIMD
