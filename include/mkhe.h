@@ -179,12 +179,19 @@ int  mkhe_mr_partial(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1,
                      const mkhe_swk* const* hoist0, const mkhe_swk* const* hoist1,
                      const mkhe_swk* const* rlk_b1, const mkhe_swk* const* rlk_d0,
                      int with_c0, mkhe_ct* out, mkhe_swk* x_part, mkhe_swk* y_part);
+/* In place on the active digits / moduli of `level`: word <- (word mod q) [* 2^64 mod q with mform != 0]; inactive limbs are not touched.  Exact for
+ * every word < 2^63 (the domain of the engine's Montgomery product), which a sum over `ranks` canonical residues satisfies while ranks * (q - 1) < 2^63:
+ * 8 ranks for 60-bit primes, 16 for 59-bit ones (mkhe_kklss_amd.dist.exact_sum_ok).  Words >= 2^63 give unspecified residues. */
 int  mkhe_swk_fold(mkhe_ctx* ctx, mkhe_swk* swk, int level, int mform);
 /* The reduction of x / y on a point-to-point mesh (xGMI: 7 links per GPU; SURVEY.md 8e(2) "prefer reduce-scatter + all-gather"): rank r receives slice
  * r of every rank's partial sum (one all-to-all), sums, folds and MForm's ITS slice -- this call: limbs [first_limb, first_limb + nlimbs) of a
  * switching-key buffer ([digit][modulus][N]: limb l = digit l / (nQ + nP), modulus l % (nQ + nP)), summand p of limb i at the device address
  * pieces + (p * piece_stride_words + i * N) words, result at dst + i * N words; limbs of inactive digits / moduli are skipped -- and the folded slices
- * are all-gathered.  Same integers as the all-reduce + mkhe_swk_fold (a sum of canonical residues, then MFormLvl: keyswitch_hoisted.go:94-96,115-117). */
+ * are all-gathered.  Same integers as the all-reduce + mkhe_swk_fold (a sum of canonical residues, then MFormLvl: keyswitch_hoisted.go:94-96,115-117).
+ *   The summands of active limbs are canonical (< q, as mkhe_mr_partial writes them); the sum is reduced per summand, so the result is exact for every
+ *   accepted npieces, with no ranks * q bound.  1 <= npieces <= 64; 0 <= first_limb, 0 <= nlimbs, first_limb + nlimbs <= digits * (nQ + nP);
+ *   piece_stride_words >= 0, and >= nlimbs * N when npieces > 1; pieces, dst non-null; level in range.  Anything else is refused before any launch
+ *   (non-zero return, mkhe_last_error names fold_pieces) and dst is not written.  pieces is only read; nlimbs == 0 does nothing. */
 int  mkhe_swk_fold_pieces(mkhe_ctx* ctx, const void* pieces, int npieces, long piece_stride_words, long first_limb, long nlimbs, int level, int mform, void* dst);
 int  mkhe_mr_finish(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1, const mkhe_swk* x, const mkhe_swk* y,
                     const mkhe_swk* const* rlk_v0, const mkhe_swk* crs_u, mkhe_ct* out);
@@ -195,6 +202,7 @@ int  mkhe_mr_finish(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1, const
 int  mkhe_mr_finish_head(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1, const mkhe_swk* y, mkhe_ct* out);
 int  mkhe_mr_finish_tail(mkhe_ctx* ctx, const mkhe_ct* op0, const mkhe_ct* op1, const mkhe_swk* x,
                          const mkhe_swk* const* rlk_v0, const mkhe_swk* crs_u, mkhe_ct* out);
+/* In place on every limb of every polynomial of ct: word <- word mod q_limb.  Exact for every word < 2^63, as for mkhe_swk_fold. */
 int  mkhe_ct_fold(mkhe_ctx* ctx, mkhe_ct* ct);
 
 /* ---- limb-sharded multi-GPU MulAndRelin (no reference counterpart; mkhe_kklss_amd/dist.py LimbShardedMulRelin).

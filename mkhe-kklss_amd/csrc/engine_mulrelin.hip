@@ -500,9 +500,13 @@ void Context::fold(u64* buf, bool qp_shaped, int level, int npolys, long poly_st
 }
 
 void Context::fold_pieces(const u64* pieces, int npieces, long piece_stride, long first_limb, long nlimbs, int level, bool mform, u64* dst) {
-    check_level(level);
-    if (!pieces || !dst || npieces < 1 || npieces > 64 || first_limb < 0 || nlimbs < 0 || first_limb + nlimbs > (long)beta_max * mtot || mtot > 64)
+    const long total = (long)beta_max * mtot;
+    if (level < 0 || level >= nq) throw Error("mkhe: fold_pieces: level out of range");
+    if (!pieces || !dst || npieces < 1 || npieces > 64 || first_limb < 0 || nlimbs < 0 || first_limb > total || nlimbs > total - first_limb || mtot > 64)
         throw Error("mkhe: fold_pieces outside a switching key");
+    // summand p of limb i is read at pieces + p * piece_stride + i * N: a stride below the range's own width makes the pieces overlap (or, negative, leave the buffer)
+    if (piece_stride < 0 || (npieces > 1 && piece_stride < nlimbs * N))
+        throw Error("mkhe: fold_pieces: piece_stride_words below nlimbs * N");
     FoldPiecesArgs fa{};
     fa.pieces = pieces; fa.dst = dst; fa.mods = d_mods; fa.piece_stride = piece_stride; fa.first_limb = first_limb;
     for (int j = 0; j <= level; ++j) fa.active |= 1ull << j;

@@ -53,9 +53,13 @@ __device__ __forceinline__ u32 hi32(u64 x) { return (u32)(x >> 32); }
 // and is back to widening adds.
 template <int K> __device__ __forceinline__ u32 opaque_one() { u32 o; asm("s_mov_b32 %0, 1 ; %1" : "=s"(o) : "i"(K)); return o; }
 
-// a*w*R^-1 mod q, result in [0, 2q).  Requires a < 2^62, w < q < 2^61.
+// a*w*R^-1 mod q, result in [0, 2q).  Requires a < 2^63, w < q < 2^61.
 // Word-serial Montgomery (radix 2^32, two rounds), 14 v_mad_u64_u32 + 2 v_mul_lo_u32 and nothing else:
 // every addition rides on a mad's 64-bit addend.
+// The bound on a (a = a0 + a1 2^32): round 0 gives T = (a0 w + m q) / 2^32 < 2q < 2^62 for any a0; round 1 starts with s0 = a1 w0 + T, the one
+// accumulator that can wrap: a1 < 2^31 keeps it below 2^63 + 2^62, whereas a1 = 2^32 - 1 with w0 near 2^32 does not fit.  The result is
+// (T + a1 w + m2 q) / 2^32 < (2 + 2^31 + 2^32) q / 2^32 < 2q.  (The fold epilogues of the sharded paths rely on it: sums of residues < 2^63,
+// pinned at 2^63 - 1 by tests/test_gpu_fold.py; most callers stay below 2^62.)
 __device__ __forceinline__ u64 mont_mul_lazy(u64 a, u64 w, u64 q, u32 ninv32) {
     const u32 a0 = lo32(a), a1 = hi32(a), w0 = lo32(w), w1 = hi32(w), q0 = lo32(q), q1 = hi32(q);
     const u32 one_a = opaque_one<0>(), one_b = opaque_one<1>(), one_c = opaque_one<2>();

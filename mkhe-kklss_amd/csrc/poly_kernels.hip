@@ -1752,7 +1752,9 @@ void launch_fold(const FoldArgs& a, hipStream_t st) {
 
 // The same epilogue for a limb RANGE whose summands arrive as separate pieces (the reduce-scatter half of a mesh exchange, mkhe_kklss_amd/dist.py): limb l of
 // the range = sum over the pieces, folded [and MForm'ed], written to dst.  Limb l of a switching-key buffer belongs to digit l / mtot and modulus l % mtot;
-// limbs outside the active digits / moduli of the level are left alone.
+// limbs outside the active digits / moduli of the level are left alone.  The summands are canonical (mkhe_mr_partial writes residues < q), so the running
+// sum is kept in [0, q) with one conditional subtraction per summand: exact for any number of pieces, where a plain u64 sum of 60-bit residues wraps 2^64
+// from 17 pieces on.  mont_mul of the reduced sum is the canonical product of a value congruent to the plain sum: the bits of all-reduce + fold_kernel.
 __global__ void __launch_bounds__(PW_THREADS) fold_pieces_kernel(FoldPiecesArgs a) {
     const long l = a.first_limb + blockIdx.y;
     const int digit = (int)(l / a.mtot), m = (int)(l % a.mtot);
@@ -1763,7 +1765,7 @@ __global__ void __launch_bounds__(PW_THREADS) fold_pieces_kernel(FoldPiecesArgs 
     u64* dst = a.dst + (long)blockIdx.y * a.N;
     for (int n = blockIdx.x * PW_THREADS + threadIdx.x; n < a.N; n += gridDim.x * PW_THREADS) {
         u64 v = 0;
-        for (int p = 0; p < a.npieces; ++p) v += src[(long)p * a.piece_stride + n];
+        for (int p = 0; p < a.npieces; ++p) v = csub(v + src[(long)p * a.piece_stride + n], md.q);
         dst[n] = mont_mul(v, w, md.q, md.ninv32);
     }
 }

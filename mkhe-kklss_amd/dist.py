@@ -12,8 +12,9 @@ components of its units.  Exchange steps (the only collectives):
      payload buffer / world on the point-to-point xGMI mesh, SURVEY.md 8e(2) -- then an all-gather of the folded slices), else an all-reduce
   2. all-reduce(out_0) + all-gather(out_i)    out_0 is a sum over ranks; out_i comes from party i's owner (ranks that own whole
                                               parties in equal numbers; otherwise one all-reduce of the whole ciphertext)
-All sums are exact (ranks * q < 2^63) and order independent, so the result is bit-identical to the
-single-device evaluation.
+All sums are exact and order independent, so the result is bit-identical to the single-device evaluation: the mesh form of step 1 reduces
+per summand (mkhe_swk_fold_pieces, any world size); every sum formed inside a collective (the all-reduces of x / y, of the outputs, the BFV
+and rotate variants) needs world * (q - 1) < 2^63, which the orchestrators check before they start (exact_sum_ok).
 
 Ordering of the collectives (every Hip*Backend, `sync`): "stream" (default under RCCL) makes the engine's own stream torch's
 current stream (torch.cuda.ExternalStream) for every collective and every torch copy, so RCCL orders itself against the
@@ -24,6 +25,26 @@ before every collective and waits for it afterwards (gloo, which moves device te
 """
 import contextlib
 import numpy as np
+
+
+MAX_ENGINE_MODULUS = (1 << 60) - 1          # the Context constructor takes primes below 2^60
+
+
+def exact_sum_ok(world, moduli):
+    """a uint64 sum of `world` canonical residues stays in the domain of the fold epilogues (mkhe_swk_fold / mkhe_ct_fold: words < 2^63) for every
+    modulus of `moduli`: 8 ranks for 60-bit primes, 16 for 59-bit ones"""
+    return world * (max(moduli) - 1) < 2 ** 63
+
+
+def _require_exact_sum(backend, dist, group, out=False):
+    """before an all-reduce of partial sums: the engine cannot reduce per summand there.  out: the output ciphertext (Q limbs only).
+    A backend that does not say which moduli it carries (no `moduli`) is held to the largest one an engine context admits (q < 2^60, csrc/engine.hip):
+    it is refused past 8 ranks whatever its primes are."""
+    accessor = getattr(backend, "moduli", None)
+    world, moduli = dist.get_world_size(group), accessor(out=out) if accessor is not None else [MAX_ENGINE_MODULUS]
+    if not exact_sum_ok(world, moduli):
+        raise ValueError("all-reduce over %d ranks is not exact for the modulus %#x: world * (q - 1) must stay below 2^63 (mkhe_swk_fold, mkhe_ct_fold)"
+                         % (world, max(moduli)))
 
 
 def assign_units(names, world):
@@ -121,9 +142,14 @@ class ShardedMulRelin:
 
     def run(self):
         b = self.b
+        if self._active():
+            _require_exact_sum(b, self.dist, self.group, out=True)      # the outputs are always summed by a collective
         x, y = b.partial_xy()                 # torch int64 views of the rank's partial sums
         self.used_mesh = False
-        if self._mesh_ok(x) and hasattr(b, "finish_head"):
+        mesh = self._mesh_ok(x) and hasattr(b, "finish_head")
+        if self._active() and not mesh:
+            _require_exact_sum(b, self.dist, self.group)                # x / y as all-reduces (the mesh form reduces per summand: exempt)
+        if mesh:
             self.used_mesh = True
             # y first (F1 -> Decompose(t_i), the long chain); x's slices travel while the head runs
             stream = getattr(b, "sync", "host") == "stream"
@@ -201,8 +227,11 @@ class ShardedRotate:
 
     def run(self):
         b = self.b
+        active = self.dist is not None and (self.force or self.dist.get_world_size(self.group) > 1)
+        if active:
+            _require_exact_sum(b, self.dist, self.group, out=True)
         full = b.partial()                    # torch int64 view [1+k][L][N]
-        if self.dist is not None and (self.force or self.dist.get_world_size(self.group) > 1):
+        if active:
             with _section(b):
                 self.dist.all_reduce(full, op=self.dist.ReduceOp.SUM, group=self.group)
         return b.finish()                     # fold + permutation -> the rotated ciphertext
@@ -252,6 +281,10 @@ class HipShardBackend(_TorchOnEngineStream):
     def _arr(self, hs):
         from ._abi import handle_array
         return handle_array(hs)
+
+    def moduli(self, out=False):
+        """the moduli of the words this rank hands to a collective: x / y (active Q limbs and P), or the output ciphertext (out: Q limbs only)"""
+        return self.params.Q[:self.level + 1] + ([] if out else self.params.P)
 
     def partial_xy(self):
         b1 = [self.keys[n][0].h for n in self.op1.ids]
@@ -339,6 +372,10 @@ class HipRotateBackend(_TorchOnEngineStream):
         self.tfull = torch.as_tensor(_DevView(self.full.devptr(), (1 + len(self.names)) * L * N), device=dev).view(1 + len(self.names), L, N)
         self.tpart = torch.as_tensor(_DevView(self.part.devptr(), (1 + len(self.ids)) * L * N), device=dev).view(1 + len(self.ids), L, N)
         self._init_sync(params, torch, dev, sync)
+
+    def moduli(self, out=False):
+        """the moduli of the words this rank hands to a collective: x / y (active Q limbs and P), or the output ciphertext (out: Q limbs only)"""
+        return self.params.Q[:self.level + 1] + ([] if out else self.params.P)
 
     def partial(self):
         self.check(self.lib().mkhe_rotate_partial(self.params.ctx, self.sub.h, self.harr([h.h for h in self.hoist]) if self.hoist else None,
@@ -470,6 +507,8 @@ class HipLimbBackend:
 class ShardedBfvMulRelin(ShardedMulRelin):
     def run(self):
         b = self.b
+        if self._active():
+            _require_exact_sum(b, self.dist, self.group)                # x1, x2, y1, y2 (Q and P limbs) and the outputs (Q limbs)
         parts = b.partial_xy()                # four torch int64 views: x1, x2, y1, y2
         for t in parts:
             self._all_reduce(t)
@@ -512,6 +551,10 @@ class HipBfvShardBackend(_TorchOnEngineStream):
 
     def _k(self, j):
         return self.harr([self.keys[n][j].h for n in self.ids])
+
+    def moduli(self, out=False):
+        """the moduli of the words this rank hands to a collective: x / y (active Q limbs and P), or the output ciphertext (out: Q limbs only)"""
+        return self.params.Q[:self.level + 1] + ([] if out else self.params.P)
 
     def partial_xy(self):
         x1, x2, y1, y2 = self.xy

@@ -21,6 +21,10 @@ class OracleShardBackend:
         nq = len(self.ks.Q)
         return (self.ks.ringQ, j) if j < nq else (self.ks.ringP, j - nq)
 
+    def moduli(self, out=False):
+        """as HipShardBackend.moduli: the moduli of x / y, or of the output ciphertext"""
+        return self.ks.Q[:self.level + 1] + ([] if out else self.ks.P)
+
     def partial_xy(self):
         x, y = self.ks.mr_xy(self.level, self.ids0, self.op0, self.ids1, self.op1, self.rlk, mform=False)
         self.x, self.y = x, y
@@ -52,8 +56,10 @@ class OracleShardBackend:
             if d >= self.ks.beta(self.level) or j not in self.act:
                 continue
             r, k = self._ring(j)
-            tot = pieces[:, i * N:(i + 1) * N].sum(axis=0, dtype=np.uint64)
-            flat[l * N:(l + 1) * N] = r.mform(k, r.reduce(k, tot))
+            tot = r.reduce(k, pieces[0, i * N:(i + 1) * N])            # reduced per piece: a uint64 sum of 60-bit residues wraps from 17 pieces on
+            for p in range(1, npieces):
+                tot = r.add(k, tot, r.reduce(k, pieces[p, i * N:(i + 1) * N]))
+            flat[l * N:(l + 1) * N] = r.mform(k, tot)
 
     def finish_head(self):
         pass                                                  # (the oracle has no split finish: everything happens in finish_tail)
@@ -86,6 +92,9 @@ class OracleRotateBackend:
         self.ids = [self.names.index(n) for n in assign_parties(self.names, world)[rank]]
         self.with_c0 = rank == 0
         self.ct, self.rk, self.crs = ct_host, rk_host, crs
+
+    def moduli(self, out=False):
+        return self.ks.Q[:self.level + 1] + ([] if out else self.ks.P)
 
     def partial(self):
         ks, L = self.ks, self.level + 1
@@ -171,6 +180,9 @@ class OracleBfvShardBackend:
         self.rlk = {self.idx[n]: rlk_host[n] for n in rlk_host}
         self.u = crs_u
         self.level = bfv.nq - 1
+
+    def moduli(self, out=False):
+        return self.bfv.Q + ([] if out else self.bfv.P)
 
     def _rings(self, m):                       # limbs of a switching key: Q then P
         nq = self.bfv.nq

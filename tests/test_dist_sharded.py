@@ -44,6 +44,78 @@ def test_assign_units():
         assert sorted(sum((u[0] for u in au), [])) == names and sorted(sum((u[1] for u in au), [])) == names
 
 
+def test_exact_sum_ok():
+    """a sum formed inside a collective stays below 2^63 (the domain of mkhe_swk_fold / mkhe_ct_fold): 8 ranks of 60-bit residues, 16 of 59-bit ones"""
+    from mkhe_kklss_amd.dist import exact_sum_ok
+    q60, q59 = H.PN15QP880["Q"][0], H.PN15QP880["P"][0]
+    assert q60.bit_length() == 60 and q59.bit_length() == 59
+    assert exact_sum_ok(8, [q60]) and not exact_sum_ok(9, [q60])
+    assert exact_sum_ok(16, [q59]) and not exact_sum_ok(17, [q59])
+    assert exact_sum_ok(8, [q59, q60, 3]) and not exact_sum_ok(9, [3, q60, q59])          # the largest modulus decides
+    assert exact_sum_ok(16, H.PN15QP880["Q"][1:] + H.PN15QP880["P"]) and not exact_sum_ok(16, H.PN15QP880["Q"] + H.PN15QP880["P"])
+
+
+class _NineRanks:
+    """stub of torch.distributed: a world of 9, and no collective may be reached"""
+
+    class ReduceOp:
+        SUM = "sum"
+
+    def get_world_size(self, group=None):
+        return 9
+
+    def get_rank(self, group=None):
+        return 0
+
+    def __getattr__(self, name):
+        raise AssertionError("collective %s reached" % name)
+
+
+def test_all_reduce_refused_past_the_exact_sum_bound(oracle_lib):
+    """small_ckks(10, 3) carries the 60-bit prime: nine ranks' sum of its residues can pass 2^63, so the all-reduce forms refuse before any work"""
+    import torch
+    from dist_oracle_backend import OracleRotateBackend, OracleShardBackend
+    from mkhe_kklss_amd.dist import ShardedMulRelin, ShardedRotate
+    names = ["u0", "u1"]
+    pset = H.small_ckks(10, 3)
+    ks, level, op0, op1, rlk, u, ref = make_case(pset, names, 3)
+    b = OracleShardBackend(ks, names, 0, 9, op0, op1, rlk, u, level, torch)
+    b.partial_xy = None                                                # refused before the rank's own arithmetic
+    assert b.moduli() == pset["Q"] + pset["P"] and b.moduli(out=True) == pset["Q"]
+    for mesh in (False, True):                                         # 15 limbs do not divide by 9, and the outputs are all-reduced either way
+        with pytest.raises(ValueError) as e:
+            ShardedMulRelin(b, _NineRanks(), mesh=mesh).run()
+        assert "9 ranks" in str(e.value) and "%#x" % pset["Q"][0] in str(e.value)
+    rb = OracleRotateBackend(ks, names, 0, 9, op0, {}, u, 5, level, torch)
+    with pytest.raises(ValueError) as e:
+        ShardedRotate(rb, _NineRanks()).run()
+    assert "9 ranks" in str(e.value) and "%#x" % pset["Q"][0] in str(e.value)
+
+
+def test_backend_without_moduli_is_held_to_the_largest_engine_modulus():
+    """a backend that does not expose its moduli is checked against 2^60 - 1, the largest modulus an engine context admits: refused at 9 ranks,
+    let through to its own arithmetic at 8"""
+    from mkhe_kklss_amd.dist import MAX_ENGINE_MODULUS, ShardedRotate, exact_sum_ok
+
+    class Reached(Exception):
+        pass
+
+    class Bare:
+        def partial(self):
+            raise Reached
+
+    class EightRanks(_NineRanks):
+        def get_world_size(self, group=None):
+            return 8
+
+    assert MAX_ENGINE_MODULUS == 2 ** 60 - 1 and exact_sum_ok(8, [MAX_ENGINE_MODULUS]) and not exact_sum_ok(9, [MAX_ENGINE_MODULUS])
+    with pytest.raises(ValueError) as e:
+        ShardedRotate(Bare(), _NineRanks()).run()
+    assert "9 ranks" in str(e.value)
+    with pytest.raises(Reached):
+        ShardedRotate(Bare(), EightRanks()).run()
+
+
 def _worker(rank, world, port, names, seed, out_path):
     import torch
     import torch.distributed as dist
@@ -165,6 +237,57 @@ def test_sharded_mulrelin_device_emulated_ranks(world, names):
         torch.cuda.synchronize()
         b.fold_xy()
         outs.append(b.finish().clone())
+    tot = sum(outs[1:], outs[0])
+    b = bs[0]
+    b.tfull.copy_(tot)
+    torch.cuda.synchronize()
+    b.fold_out()
+    assert (b.full.download() == ref).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world,names", [(2, ["u0", "u1"]), (4, ["u0", "u1", "u2"]), (8, ["u0", "u1", "u2", "u3"])])        # 8: half-party units
+def test_sharded_mulrelin_device_emulated_ranks_mesh(world, names):
+    """the mesh exchange of ShardedMulRelin.run on the device: x and y as all-to-all of limb slices + mkhe_swk_fold_pieces on the rank's own slice
+    (first_limb = rank * 24 / world > 0, `world` pieces) + all-gather, the collectives done by hand in run's order.  24 switching-key limbs."""
+    import torch
+    from mkhe_kklss_amd import mkckks
+    from mkhe_kklss_amd.dist import HipShardBackend
+    pset = H.small_ckks(11, 4)
+    ks, level, op0, op1, rlk, u, ref = make_case(pset, names, 29)
+    bs = []
+    for r in range(world):
+        params = mkckks.Parameters(pset["logN"], pset["Q"], pset["P"], pset["scale"])
+        params.AddCRS(-1, u)
+        bs.append(HipShardBackend(params, names, r, world, op0, op1, rlk, level, torch, 0))
+    xs, ys = [], []
+    for b in bs:
+        x, y = b.partial_xy()
+        b.before_collective()
+        xs.append(x.clone()); ys.append(y.clone())
+    words = xs[0].numel()
+    per = words // world
+    assert words == 24 * ks.N and per * world == words and per % bs[0].limb_words() == 0
+
+    def mesh_finish(which, parts):
+        folded = []
+        for r, b in enumerate(bs):
+            recv = torch.cat([p[r * per:(r + 1) * per] for p in parts])       # all-to-all: piece p = rank p's slice r
+            torch.cuda.synchronize()
+            b.fold_pieces(which, recv, world, per, r * per, per)              # into the rank's own slice of x / y
+            b.before_collective()
+            t = b.tx if which == "x" else b.ty
+            folded.append(t[r * per:(r + 1) * per].clone())
+        whole = torch.cat(folded)                                             # all-gather
+        for b in bs:
+            (b.tx if which == "x" else b.ty).copy_(whole)
+        torch.cuda.synchronize()
+
+    mesh_finish("y", ys)
+    for b in bs:
+        b.finish_head()
+    mesh_finish("x", xs)
+    outs = [b.finish_tail().clone() for b in bs]
     tot = sum(outs[1:], outs[0])
     b = bs[0]
     b.tfull.copy_(tot)
