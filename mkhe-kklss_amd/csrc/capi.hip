@@ -65,6 +65,75 @@ static std::vector<const Swk*> swk_list(const mkhe_ctx* ctx, const mkhe_swk* con
     return r;
 }
 
+// ---- the guard of the sampler, protocol and encoder entry points: whether a call may run at all -- off a limb-sharded context, outside a
+// capture whose replay would draw the same stream again or that cannot hold what the call does, and without recover()ing a context (or ending a
+// capture) that the call never touched.  Every step is written once, here; an entry calls the steps it needs in its own order.  enter() leaves g_last_ctx null, so that a refusal is reported with nothing drained; commit() arms it behind the last check that can
+// refuse with nothing enqueued.  A key is never quoted in a message.  enter(ctx, null) reports a null context with need()'s own message.
+static Context* enter(const mkhe_ctx* ctx, const char* what) {
+    if (what && !ctx) throw Error(std::string(what) + ": null context");
+    Context* c = need(ctx);
+    g_last_ctx = nullptr;
+    return c;
+}
+// last(): the refusals that need the device selected (tables built at the first use)
+template <class F> static void commit(Context* c, F last) {
+    MKHE_HIP(hipSetDevice(c->device));
+    last();
+    g_last_ctx = c;
+}
+static void commit(Context* c) { commit(c, [] {}); }
+static void count_ok(const char* what, int count) {
+    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+}
+static void need_aligned(const void* p, const char* what) {
+    if ((uintptr_t)p & 15) throw Error(std::string(what) + ": device buffers must be 16-byte aligned");
+}
+static void scheme_ok(const Context* c, const char* what, bool bfv, const char* why) {
+    if (c->is_bfv() != bfv) throw Error(std::string(what) + why);
+}
+static void unmasked(const Context* c, const char* what) {
+    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+}
+// why closes the message: what a replay would do, or what the call does that a capture cannot hold
+static const char* const REPLAYS = "(a replay would repeat the keystream)";
+static const char* const UPLOADS = "(the call allocates and uploads)";
+static const char* const STAGES = "with more than 16 ciphertexts or shares (the pointer tables are staged)";
+static void not_captured(const Context* c, const char* what, const char* why) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(c->stream, &cs);
+    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end " + why);
+}
+// the inputs of a batch: present and at one level -- `limbs` of them (why_limbs says so), or (limbs = 0) as many as the first has
+static const Ct& ct_at(const mkhe_ct* const* v, int i, const char* what) {
+    if (!v[i]) throw Error(std::string(what) + ": null ciphertext in the batch");
+    return v[i]->c;
+}
+static void batch_ok(const char* what, int count, const mkhe_ct* const* in, int limbs = 0, const char* why_limbs = nullptr) {
+    for (int b = 0; b < count; ++b)
+        if (ct_at(in, b, what).limbs != (limbs ? limbs : in[0]->c.limbs))
+            throw Error(std::string(what) + (limbs ? why_limbs : ": every ciphertext must be at the same level"));
+}
+static void slots_ok(const char* what, int count, const mkhe_ct* const* in, const int* slots) {
+    for (int b = 0; b < count; ++b)
+        if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error(std::string(what) + ": slot out of range (party slots are 1 .. n)");
+}
+// the inputs of a merge are over the same ids, with one share per party
+static void merge_shape(const char* what, int count, const mkhe_ct* const* in, int nshares) {
+    for (int b = 0; b < count; ++b)
+        if (in[b]->c.ids != in[0]->c.ids) throw Error(std::string(what) + ": every ciphertext must be over the same ids");
+    if (nshares != in[0]->c.n) throw Error(std::string(what) + ": nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+}
+static const u64* share_at(const void* const* v, int i, const char* what) {
+    if (!v[i]) throw Error(std::string(what) + ": null share in the per-party list");
+    need_aligned(v[i], what);
+    return (const u64*)v[i];
+}
+static std::vector<const u64*> share_list(const void* const* v, int n, const char* what) {
+    std::vector<const u64*> r(n);
+    for (int i = 0; i < n; ++i) r[i] = share_at(v, i, what);
+    return r;
+}
+
 extern "C" {
 
 const char* mkhe_last_error(void) { return g_err.c_str(); }
@@ -497,7 +566,7 @@ int mkhe_ct_mul_ptxt(mkhe_ctx* ctx, const mkhe_ct* in, const void* dev_pt, mkhe_
 static std::vector<const Ct*> ct_list(const mkhe_ctx* ctx, const mkhe_ct* const* v, int n, const char* what) {
     if (!v) throw Error(std::string(what) + ": null ciphertext list");
     std::vector<const Ct*> r(n);
-    for (int i = 0; i < n; ++i) { if (!v[i]) throw Error(std::string(what) + ": null ciphertext in the batch"); mark(ctx, v[i]); r[i] = &v[i]->c; }
+    for (int i = 0; i < n; ++i) { r[i] = &ct_at(v, i, what); mark(ctx, v[i]); }
     return r;
 }
 static std::vector<Ct*> ct_list_out(const mkhe_ctx* ctx, mkhe_ct* const* v, int n, const char* what) {
@@ -681,93 +750,8 @@ int mkhe_crs_expand(mkhe_ctx* ctx, uint64_t seed, int32_t idx, mkhe_swk* out) {
 }
 
 // ---- public-key encryption / decryption (encdec.hip)
-static void need_aligned(const void* p, const char* what) {
-    if ((uintptr_t)p & 15) throw Error(std::string(what) + ": device buffers must be 16-byte aligned");
-}
-int mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt, const int32_t* samples, mkhe_ct* const* out) {
-    MKHE_TRY({
-        Context* c = need(ctx);
-        if (!dev_pk || !dev_pt || !samples || !out) throw Error("mkhe_encrypt: null argument");
-        if (level < 0 || level >= c->nq) throw Error("mkhe_encrypt: level out of range");
-        if (count < 1 || count > 65535) throw Error("mkhe_encrypt: count must be 1 .. 65535");
-        need_aligned(dev_pk, "mkhe_encrypt"); need_aligned(dev_pt, "mkhe_encrypt");
-        auto o = ct_list_out(ctx, out, count, "mkhe_encrypt");
-        std::vector<u64*> d(count);
-        for (int b = 0; b < count; ++b) {
-            if (o[b]->n != 1) throw Error("mkhe_encrypt: every out must be a ciphertext over exactly one party");
-            if (o[b]->limbs != level + 1) throw Error("mkhe_encrypt: every out must have level+1 limbs");
-            d[b] = o[b]->d;
-        }
-        c->encrypt(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, samples, d.data());
-    })
-}
-// device-side sampling: the checks the two calls share.  A call refused here has enqueued nothing and leaves the context (and a capture in
-// progress) as it was.  The key is never quoted.
-static void smp_table_ok(const char* what, const uint64_t* cdt, int ncdt) {
-    if (!cdt) throw Error(std::string(what) + ": null table");
-    if (ncdt < 2 || ncdt > SMP_MAX_CDT || (ncdt & 1)) throw Error(std::string(what) + ": ncdt must be even and 2 .. 64");
-    for (int t = 1; t < ncdt; ++t) if (cdt[t] <= cdt[t - 1]) throw Error(std::string(what) + ": the thresholds of the table must be strictly increasing");
-}
-static Context* smp_need(mkhe_ctx* ctx, const char* what, const uint32_t* key, bool table, const uint64_t* cdt, int ncdt) {
-    if (!ctx) throw Error(std::string(what) + ": null context");
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (!key) throw Error(std::string(what) + ": null key");
-    if (table) smp_table_ok(what, cdt, ncdt);
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (a replay would repeat the keystream)");
-    MKHE_HIP(hipSetDevice(c->device));
-    g_last_ctx = c;
-    return c;
-}
-int mkhe_sample_small(mkhe_ctx* ctx, int kind, int count, const uint32_t key[8], uint64_t nonce, uint32_t first_stream, const uint64_t* cdt, int ncdt,
-                      void* dev_out) {
-    MKHE_TRY({
-        if (kind != 0 && kind != 1) throw Error("mkhe_sample_small: kind must be 0 (ternary) or 1 (table)");
-        Context* c = smp_need(ctx, "mkhe_sample_small", key, kind == 1, cdt, ncdt);
-        if (!dev_out) throw Error("mkhe_sample_small: null output");
-        if (count < 1 || count > 3 * 65535) throw Error("mkhe_sample_small: count must be 1 .. 196605");
-        if ((uint64_t)first_stream + (uint64_t)count > (1ull << 32)) throw Error("mkhe_sample_small: first_stream + count exceeds 2^32");
-        need_aligned(dev_out, "mkhe_sample_small");
-        c->sample_small(kind, count, key, nonce, first_stream, cdt, ncdt, (int32_t*)dev_out);
-    })
-}
-int mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt, const uint32_t key[8], uint64_t nonce,
-                        const uint64_t* cdt, int ncdt, mkhe_ct* const* out) {
-    MKHE_TRY({
-        Context* c = smp_need(ctx, "mkhe_encrypt_seeded", key, true, cdt, ncdt);
-        if (!dev_pk || !dev_pt || !out) throw Error("mkhe_encrypt_seeded: null argument");
-        if (level < 0 || level >= c->nq) throw Error("mkhe_encrypt_seeded: level out of range");
-        if (count < 1 || count > 65535) throw Error("mkhe_encrypt_seeded: count must be 1 .. 65535");
-        need_aligned(dev_pk, "mkhe_encrypt_seeded"); need_aligned(dev_pt, "mkhe_encrypt_seeded");
-        auto o = ct_list_out(ctx, out, count, "mkhe_encrypt_seeded");
-        std::vector<u64*> d(count);
-        for (int b = 0; b < count; ++b) {
-            if (o[b]->n != 1) throw Error("mkhe_encrypt_seeded: every out must be a ciphertext over exactly one party");
-            if (o[b]->limbs != level + 1) throw Error("mkhe_encrypt_seeded: every out must have level+1 limbs");
-            d[b] = o[b]->d;
-        }
-        c->encrypt_seeded(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, key, nonce, cdt, ncdt, d.data());
-    })
-}
-// secret-key encryption with a seeded c1.  The two encrypt calls are under the rules of the seeded encryption (smp_need); the sampler and the
-// expansion read a PUBLIC stream and may be captured as long as they stage no pointer table (count at most 16).
-static Context* sku_need(mkhe_ctx* ctx, const char* what, int count, const uint32_t* key) {
-    if (!ctx) throw Error(std::string(what) + ": null context");
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (!key) throw Error(std::string(what) + ": null key");
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone && count > ED_INLINE)
-        throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end with more than 16 items (the pointer table is staged)");
-    return c;
-}
-static std::vector<u64*> sk_outputs(mkhe_ctx* ctx, const char* what, int count, int limbs, mkhe_ct* const* out) {
+// the outputs of an encryption: present, distinct, each over exactly one party, with `limbs` limbs or (limbs = 0) all at one level
+static std::vector<u64*> fresh_outputs(mkhe_ctx* ctx, const char* what, int count, int limbs, mkhe_ct* const* out) {
     auto o = ct_list_out(ctx, out, count, what);
     std::vector<u64*> d(count);
     for (int b = 0; b < count; ++b) {
@@ -778,48 +762,101 @@ static std::vector<u64*> sk_outputs(mkhe_ctx* ctx, const char* what, int count, 
     }
     return d;
 }
+int mkhe_encrypt(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt, const int32_t* samples, mkhe_ct* const* out) {
+    MKHE_TRY({
+        Context* c = need(ctx);
+        if (!dev_pk || !dev_pt || !samples || !out) throw Error("mkhe_encrypt: null argument");
+        if (level < 0 || level >= c->nq) throw Error("mkhe_encrypt: level out of range");
+        count_ok("mkhe_encrypt", count);
+        need_aligned(dev_pk, "mkhe_encrypt"); need_aligned(dev_pt, "mkhe_encrypt");
+        auto d = fresh_outputs(ctx, "mkhe_encrypt", count, level + 1, out);
+        c->encrypt(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, samples, d.data());
+    })
+}
+// device-side sampling from a SECRET key: refused inside a capture, armed before the arguments are looked at
+static void smp_table_ok(const char* what, const uint64_t* cdt, int ncdt) {
+    if (!cdt) throw Error(std::string(what) + ": null table");
+    if (ncdt < 2 || ncdt > SMP_MAX_CDT || (ncdt & 1)) throw Error(std::string(what) + ": ncdt must be even and 2 .. 64");
+    for (int t = 1; t < ncdt; ++t) if (cdt[t] <= cdt[t - 1]) throw Error(std::string(what) + ": the thresholds of the table must be strictly increasing");
+}
+static Context* smp_enter(mkhe_ctx* ctx, const char* what, const uint32_t* key, bool table, const uint64_t* cdt, int ncdt) {
+    Context* c = enter(ctx, what);
+    if (!key) throw Error(std::string(what) + ": null key");
+    if (table) smp_table_ok(what, cdt, ncdt);
+    unmasked(c, what);
+    not_captured(c, what, REPLAYS);
+    commit(c);
+    return c;
+}
+int mkhe_sample_small(mkhe_ctx* ctx, int kind, int count, const uint32_t key[8], uint64_t nonce, uint32_t first_stream, const uint64_t* cdt, int ncdt,
+                      void* dev_out) {
+    MKHE_TRY({
+        if (kind != 0 && kind != 1) throw Error("mkhe_sample_small: kind must be 0 (ternary) or 1 (table)");
+        Context* c = smp_enter(ctx, "mkhe_sample_small", key, kind == 1, cdt, ncdt);
+        if (!dev_out) throw Error("mkhe_sample_small: null output");
+        if (count < 1 || count > 3 * 65535) throw Error("mkhe_sample_small: count must be 1 .. 196605");
+        if ((uint64_t)first_stream + (uint64_t)count > (1ull << 32)) throw Error("mkhe_sample_small: first_stream + count exceeds 2^32");
+        need_aligned(dev_out, "mkhe_sample_small");
+        c->sample_small(kind, count, key, nonce, first_stream, cdt, ncdt, (int32_t*)dev_out);
+    })
+}
+int mkhe_encrypt_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_pk, const void* dev_pt, int pt_is_ntt, const uint32_t key[8], uint64_t nonce,
+                        const uint64_t* cdt, int ncdt, mkhe_ct* const* out) {
+    MKHE_TRY({
+        Context* c = smp_enter(ctx, "mkhe_encrypt_seeded", key, true, cdt, ncdt);
+        if (!dev_pk || !dev_pt || !out) throw Error("mkhe_encrypt_seeded: null argument");
+        if (level < 0 || level >= c->nq) throw Error("mkhe_encrypt_seeded: level out of range");
+        count_ok("mkhe_encrypt_seeded", count);
+        need_aligned(dev_pk, "mkhe_encrypt_seeded"); need_aligned(dev_pt, "mkhe_encrypt_seeded");
+        auto d = fresh_outputs(ctx, "mkhe_encrypt_seeded", count, level + 1, out);
+        c->encrypt_seeded(level, count, (const u64*)dev_pk, (const u64*)dev_pt, pt_is_ntt != 0, key, nonce, cdt, ncdt, d.data());
+    })
+}
+// secret-key encryption with a seeded c1.  The two encrypt calls are under the rules of the seeded encryption (smp_enter); the sampler and the
+// expansion read a PUBLIC stream and may be captured as long as they stage no pointer table (count at most 16).
+static Context* sku_enter(mkhe_ctx* ctx, const char* what, int count, const uint32_t* key) {
+    Context* c = enter(ctx, what);
+    if (!key) throw Error(std::string(what) + ": null key");
+    count_ok(what, count);
+    unmasked(c, what);
+    if (count > ED_INLINE) not_captured(c, what, "with more than 16 items (the pointer table is staged)");
+    return c;
+}
 int mkhe_sample_uniform(mkhe_ctx* ctx, int limbs, int count, const uint32_t a_key[8], uint64_t a_nonce, void* dev_out) {
     MKHE_TRY({
         const char* what = "mkhe_sample_uniform";
-        Context* c = sku_need(ctx, what, count, a_key);
+        Context* c = sku_enter(ctx, what, count, a_key);
         if (!dev_out) throw Error("mkhe_sample_uniform: null output");
         if (limbs < 1 || limbs > c->nq) throw Error("mkhe_sample_uniform: limbs must be 1 .. nQ");
         need_aligned(dev_out, what);
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
+        commit(c);
         c->sample_uniform(limbs, count, a_key, a_nonce, (u64*)dev_out);
     })
 }
 int mkhe_ct_expand_seeded(mkhe_ctx* ctx, int count, const uint32_t a_key[8], uint64_t a_nonce, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_ct_expand_seeded";
-        Context* c = sku_need(ctx, what, count, a_key);
+        Context* c = sku_enter(ctx, what, count, a_key);
         if (!out) throw Error("mkhe_ct_expand_seeded: null argument");
-        for (int b = 0; b < count; ++b) if (!out[b]) throw Error("mkhe_ct_expand_seeded: null output in the batch");
-        for (int b = 0; b < count; ++b) {
-            if (out[b]->c.n != 1) throw Error("mkhe_ct_expand_seeded: every out must be a ciphertext over exactly one party");
-            if (out[b]->c.limbs != out[0]->c.limbs) throw Error("mkhe_ct_expand_seeded: every out must be at the same level");
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
-        auto d = sk_outputs(ctx, what, count, 0, out);
+        auto d = fresh_outputs(ctx, what, count, 0, out);
+        commit(c);
         c->ct_expand_seeded(count, out[0]->c.limbs, a_key, a_nonce, d.data());
     })
 }
 static void sk_encrypt_args_ok(Context* c, const char* what, int level, int count, const void* dev_sk, const void* dev_pt, const uint32_t* a_key, mkhe_ct* const* out) {
     if (!dev_sk || !dev_pt || !a_key || !out) throw Error(std::string(what) + ": null argument");
     if (level < 0 || level >= c->nq) throw Error(std::string(what) + ": level out of range");
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    count_ok(what, count);
     need_aligned(dev_sk, what); need_aligned(dev_pt, what);
 }
 int mkhe_encrypt_sk(mkhe_ctx* ctx, int level, int count, const void* dev_sk, const void* dev_pt, int pt_is_ntt, const uint32_t a_key[8], uint64_t a_nonce,
                     const int32_t* e, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_encrypt_sk";
-        Context* c = smp_need(ctx, what, a_key, false, nullptr, 0);
+        Context* c = smp_enter(ctx, what, a_key, false, nullptr, 0);
         if (!e) throw Error("mkhe_encrypt_sk: null argument");
         sk_encrypt_args_ok(c, what, level, count, dev_sk, dev_pt, a_key, out);
-        auto d = sk_outputs(ctx, what, count, level + 1, out);
+        auto d = fresh_outputs(ctx, what, count, level + 1, out);
         c->encrypt_sk(level, count, (const u64*)dev_sk, (const u64*)dev_pt, pt_is_ntt != 0, a_key, a_nonce, e, nullptr, 0, nullptr, 0, d.data(), what);
     })
 }
@@ -827,12 +864,12 @@ int mkhe_encrypt_sk_seeded(mkhe_ctx* ctx, int level, int count, const void* dev_
                            uint64_t a_nonce, const uint32_t e_key[8], uint64_t e_nonce, const uint64_t* cdt, int ncdt, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_encrypt_sk_seeded";
-        Context* c = smp_need(ctx, what, e_key, true, cdt, ncdt);
+        Context* c = smp_enter(ctx, what, e_key, true, cdt, ncdt);
         sk_encrypt_args_ok(c, what, level, count, dev_sk, dev_pt, a_key, out);
         bool same = true;
         for (int i = 0; i < 8; ++i) same = same && a_key[i] == e_key[i];
         if (same) throw Error("mkhe_encrypt_sk_seeded: a_key must differ from e_key (the public seed would publish the key of the secret stream)");
-        auto d = sk_outputs(ctx, what, count, level + 1, out);
+        auto d = fresh_outputs(ctx, what, count, level + 1, out);
         c->encrypt_sk(level, count, (const u64*)dev_sk, (const u64*)dev_pt, pt_is_ntt != 0, a_key, a_nonce, nullptr, e_key, e_nonce, cdt, ncdt, d.data(), what);
     })
 }
@@ -856,25 +893,15 @@ int mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, vo
         need(ctx)->decrypt(ct->c, sk.data(), (u64*)dev_pt_out);
     })
 }
-// distributed decryption: the checks the two calls share, under the rules of the seeded encryption -- a call refused here has enqueued nothing
-// and leaves the context (and a capture in progress) as it was; the key is never quoted
-static Context* ds_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const void* out, bool keystream) {
-    if (!ctx) throw Error(std::string(what) + ": null context");
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+// distributed decryption: a share with a flood draws from the keystream and is refused inside a capture
+static Context* ds_enter(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const void* out, bool keystream) {
+    Context* c = enter(ctx, what);
+    count_ok(what, count);
     if (!in || !out) throw Error(std::string(what) + ": null argument");
     need_aligned(out, what);
-    for (int b = 0; b < count; ++b) {
-        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
-        if (in[b]->c.limbs != in[0]->c.limbs) throw Error(std::string(what) + ": every ciphertext must be at the same level");
-    }
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    if (keystream) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(c->stream, &cs);
-        if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (a replay would repeat the keystream)");
-    }
+    batch_ok(what, count, in);
+    unmasked(c, what);
+    if (keystream) not_captured(c, what, REPLAYS);
     return c;
 }
 int mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8], uint64_t nonce,
@@ -882,52 +909,38 @@ int mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const
     MKHE_TRY({
         if (flood_bits < 0 || flood_bits > SHF_MAX_BITS) throw Error("mkhe_decrypt_share: flood_bits must be 0 .. 62");
         if (flood_bits > 0 && !key) throw Error("mkhe_decrypt_share: null key");
-        Context* c = ds_need(ctx, "mkhe_decrypt_share", count, in, dev_shares, flood_bits > 0);
+        Context* c = ds_enter(ctx, "mkhe_decrypt_share", count, in, dev_shares, flood_bits > 0);
         if (!slots || !dev_sk) throw Error("mkhe_decrypt_share: null argument");
         need_aligned(dev_sk, "mkhe_decrypt_share");
-        for (int b = 0; b < count; ++b)
-            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_decrypt_share: slot out of range (party slots are 1 .. n)");
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
+        slots_ok("mkhe_decrypt_share", count, in, slots);
+        commit(c);
         auto i = ct_list(ctx, in, count, "mkhe_decrypt_share");
         c->decrypt_share(i, slots, (const u64*)dev_sk, key, nonce, flood_bits, (u64*)dev_shares);
     })
 }
 int mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, void* dev_pt_out) {
     MKHE_TRY({
-        Context* c = ds_need(ctx, "mkhe_decrypt_merge", count, in, dev_pt_out, false);
-        for (int b = 0; b < count; ++b)
-            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_decrypt_merge: every ciphertext must be over the same ids");
-        if (nshares != in[0]->c.n) throw Error("mkhe_decrypt_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+        Context* c = ds_enter(ctx, "mkhe_decrypt_merge", count, in, dev_pt_out, false);
+        merge_shape("mkhe_decrypt_merge", count, in, nshares);
         if (nshares > 0 && !dev_shares) throw Error("mkhe_decrypt_merge: null argument");
-        std::vector<const u64*> sh(nshares);
-        for (int i = 0; i < nshares; ++i) {
-            if (!dev_shares[i]) throw Error("mkhe_decrypt_merge: null share in the per-party list");
-            need_aligned(dev_shares[i], "mkhe_decrypt_merge");
-            sh[i] = (const u64*)dev_shares[i];
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
+        auto sh = share_list(dev_shares, nshares, "mkhe_decrypt_merge");
+        commit(c);
         auto i = ct_list(ctx, in, count, "mkhe_decrypt_merge");
         c->decrypt_merge(i, sh, (u64*)dev_pt_out);
     })
 }
-// collective refresh: the checks the two calls share, under the rules of distributed decryption; why_capture closes the capture message
-static Context* rf_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const char* why_capture) {
-    if (!ctx) throw Error(std::string(what) + ": null context");
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+// collective refresh, for the CKKS side and for MK-BFV (every ciphertext of a BFV context that the calls take has nq limbs): under the rules of
+// distributed decryption; why_capture closes the capture message
+static Context* refresh_enter(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, const char* why_capture) {
+    Context* c = enter(ctx, what);
+    count_ok(what, count);
     if (!in) throw Error(std::string(what) + ": null argument");
-    for (int b = 0; b < count; ++b) {
-        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
-        if (in[b]->c.limbs != in[0]->c.limbs) throw Error(std::string(what) + ": every ciphertext must be at the same level");
-    }
-    if (c->is_bfv()) throw Error(std::string(what) + ": not available on a BFV context (a mask mod T is another protocol)");
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (" + why_capture + ")");
+    if (!bfv) batch_ok(what, count, in);
+    scheme_ok(c, what, bfv, bfv ? ": needs a BFV context (mkhe_refresh_share / mkhe_refresh_merge serve the others)"
+                                : ": not available on a BFV context (a mask mod T is another protocol)");
+    unmasked(c, what);
+    if (bfv) batch_ok(what, count, in, c->nq, ": every ciphertext must have the nQ limbs of the context");
+    not_captured(c, what, why_capture);
     return c;
 }
 // the outputs of a refresh call: present, distinct, none of them an input
@@ -938,193 +951,120 @@ static void rf_outputs(const char* what, int count, const mkhe_ct* const* in, in
         for (int k = 0; k < nin; ++k) if (in[k] == out[b] || in[k]->c.d == out[b]->c.d) throw Error(std::string(what) + ": an output aliases an input");
     }
 }
+// the limbs of the outputs: on a BFV context the nQ limbs of the context, else those of the first output, 1 .. nQ
+static int refresh_limbs(const Context* c, const std::string& w, bool bfv, const mkhe_ct* first, const char* name) {
+    if (bfv) return c->nq;
+    if (first->c.limbs < 1 || first->c.limbs > c->nq) throw Error(w + ": the limbs of " + name + " are out of range");
+    return first->c.limbs;
+}
+// both refresh shares; bits: mask_bits, or (bfv) mask with flood_bits behind it
+static void refresh_share_entry(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk,
+                                const void* dev_pk, const uint32_t* key, uint64_t nonce_mask, uint64_t nonce_enc, int bits, int flood_bits,
+                                const uint64_t* cdt, int ncdt, void* dev_shares, mkhe_ct* const* reenc) {
+    const std::string w(what);
+    Context* c = refresh_enter(ctx, what, bfv, count, in, REPLAYS);
+    if (!slots || !dev_sk || !dev_pk || !dev_shares || !reenc) throw Error(w + ": null argument");
+    smp_table_ok(what, cdt, ncdt);
+    need_aligned(dev_sk, what); need_aligned(dev_pk, what); need_aligned(dev_shares, what);
+    slots_ok(what, count, in, slots);
+    rf_outputs(what, count, in, count, reenc);
+    const int lout = refresh_limbs(c, w, bfv, reenc[0], "reenc");
+    std::vector<u64*> d(count);
+    for (int b = 0; b < count; ++b) {
+        const Ct& o = reenc[b]->c;
+        if (o.n != 1 || o.ids[0] != in[b]->c.ids[slots[b] - 1]) throw Error(w + ": every reenc must be a ciphertext over exactly the id at the slot of its input");
+        if (o.limbs != lout) throw Error(w + (bfv ? ": every reenc must have the nQ limbs of the context" : ": every reenc must have the same number of limbs"));
+        d[b] = o.d;
+    }
+    commit(c, [&] {
+        if (!bfv) return;
+        c->bfv_refresh_prepare(what);                                           // T outside the encoder's preconditions: refused here
+        const int most = c->bfv_refresh_max_flood();
+        if (flood_bits > most)
+            throw Error(w + ": flood_bits must be at most bitlen(Q div 2T) - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
+    });
+    auto i = ct_list(ctx, in, count, what);
+    ct_list_out(ctx, reenc, count, what);
+    const u64 *sk = (const u64*)dev_sk, *pk = (const u64*)dev_pk;
+    if (bfv) c->bfv_refresh_share(i, slots, sk, pk, key, nonce_mask, nonce_enc, bits, flood_bits, cdt, ncdt, (u64*)dev_shares, d.data());
+    else c->refresh_share(i, slots, sk, pk, key, nonce_mask, nonce_enc, bits, cdt, ncdt, (u64*)dev_shares, lout, d.data());
+}
 int mkhe_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk, const uint32_t key[8],
                        uint64_t nonce_mask, uint64_t nonce_enc, int mask_bits, const uint64_t* cdt, int ncdt, void* dev_shares, mkhe_ct* const* reenc) {
     MKHE_TRY({
-        const char* what = "mkhe_refresh_share";
         if (mask_bits < 0 || mask_bits > RF_MAX_BITS) throw Error("mkhe_refresh_share: mask_bits must be 0 .. 120");
         if (!key) throw Error("mkhe_refresh_share: null key");                  // (mask_bits = 0 reads no mask stream, the encryption still draws its samples)
         if (mask_bits > 0 && nonce_mask == nonce_enc) throw Error("mkhe_refresh_share: nonce_mask and nonce_enc must differ (the mask and the encryption would share streams)");
-        Context* c = rf_need(ctx, what, count, in, "a replay would repeat the keystream");
-        if (!slots || !dev_sk || !dev_pk || !dev_shares || !reenc) throw Error("mkhe_refresh_share: null argument");
-        smp_table_ok(what, cdt, ncdt);
-        need_aligned(dev_sk, what); need_aligned(dev_pk, what); need_aligned(dev_shares, what);
-        for (int b = 0; b < count; ++b)
-            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_refresh_share: slot out of range (party slots are 1 .. n)");
-        rf_outputs(what, count, in, count, reenc);
-        const int lout = reenc[0]->c.limbs;
-        if (lout < 1 || lout > c->nq) throw Error("mkhe_refresh_share: the limbs of reenc are out of range");
-        std::vector<u64*> d(count);
-        for (int b = 0; b < count; ++b) {
-            const Ct& o = reenc[b]->c;
-            if (o.n != 1 || o.ids[0] != in[b]->c.ids[slots[b] - 1]) throw Error("mkhe_refresh_share: every reenc must be a ciphertext over exactly the id at the slot of its input");
-            if (o.limbs != lout) throw Error("mkhe_refresh_share: every reenc must have the same number of limbs");
-            d[b] = o.d;
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
-        auto i = ct_list(ctx, in, count, what);
-        ct_list_out(ctx, reenc, count, what);
-        c->refresh_share(i, slots, (const u64*)dev_sk, (const u64*)dev_pk, key, nonce_mask, nonce_enc, mask_bits, cdt, ncdt, (u64*)dev_shares, lout, d.data());
+        refresh_share_entry(ctx, "mkhe_refresh_share", false, count, in, slots, dev_sk, dev_pk, key, nonce_mask, nonce_enc, mask_bits, 0, cdt, ncdt, dev_shares, reenc);
     })
-}
-int mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, const mkhe_ct* const* reenc,
-                       mkhe_ct* const* out) {
-    MKHE_TRY({
-        const char* what = "mkhe_refresh_merge";
-        Context* c = rf_need(ctx, what, count, in, "the call allocates and uploads");
-        if (!out) throw Error("mkhe_refresh_merge: null argument");
-        for (int b = 0; b < count; ++b)
-            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_refresh_merge: every ciphertext must be over the same ids");
-        if (nshares != in[0]->c.n) throw Error("mkhe_refresh_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
-        if (nshares > 0 && (!dev_shares || !reenc)) throw Error("mkhe_refresh_merge: null argument");
-        rf_outputs(what, count, in, count, out);
-        const int lout = out[0]->c.limbs;
-        if (lout < 1 || lout > c->nq) throw Error("mkhe_refresh_merge: the limbs of out are out of range");
-        std::vector<const u64*> sh(nshares);
-        std::vector<const u64*> re((size_t)nshares * count);
-        std::vector<u64*> d(count);
-        for (int b = 0; b < count; ++b) {
-            if (out[b]->c.ids != in[0]->c.ids) throw Error("mkhe_refresh_merge: every out must be over the ids of the inputs");
-            if (out[b]->c.limbs != lout) throw Error("mkhe_refresh_merge: every out must have the same number of limbs");
-            d[b] = out[b]->c.d;
-        }
-        for (int i = 0; i < nshares; ++i) {
-            if (!dev_shares[i]) throw Error("mkhe_refresh_merge: null share in the per-party list");
-            need_aligned(dev_shares[i], what);
-            sh[i] = (const u64*)dev_shares[i];
-            for (int b = 0; b < count; ++b) {
-                const mkhe_ct* r = reenc[(size_t)i * count + b];
-                if (!r) throw Error("mkhe_refresh_merge: null reenc in the list");
-                if (r->c.n != 1 || r->c.ids[0] != in[0]->c.ids[i]) throw Error("mkhe_refresh_merge: reenc[i * count + b] must be a ciphertext over exactly the id at slot 1 + i");
-                if (r->c.limbs != lout) throw Error("mkhe_refresh_merge: every reenc must have the limbs of out");
-                for (int k = 0; k < count; ++k) if (out[k] == r || out[k]->c.d == r->c.d) throw Error("mkhe_refresh_merge: an output aliases an input");
-                re[(size_t)i * count + b] = r->c.d;
-            }
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
-        auto i = ct_list(ctx, in, count, what);
-        if (nshares > 0) ct_list(ctx, reenc, nshares * count, what);
-        ct_list_out(ctx, out, count, what);
-        c->refresh_merge(i, sh, re, lout, d.data());
-    })
-}
-// collective refresh for MK-BFV: the checks the two calls share.  Every ciphertext of a BFV context that the calls take has nq limbs.
-static Context* brf_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const char* why_capture) {
-    if (!ctx) throw Error(std::string(what) + ": null context");
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
-    if (!in) throw Error(std::string(what) + ": null argument");
-    if (!c->is_bfv()) throw Error(std::string(what) + ": needs a BFV context (mkhe_refresh_share / mkhe_refresh_merge serve the others)");
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    for (int b = 0; b < count; ++b) {
-        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
-        if (in[b]->c.limbs != c->nq) throw Error(std::string(what) + ": every ciphertext must have the nQ limbs of the context");
-    }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (" + why_capture + ")");
-    return c;
 }
 int mkhe_bfv_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk, const uint32_t key[8],
                            uint64_t nonce_mask, uint64_t nonce_enc, int mask, int flood_bits, const uint64_t* cdt, int ncdt, void* dev_shares,
                            mkhe_ct* const* reenc) {
     MKHE_TRY({
-        const char* what = "mkhe_bfv_refresh_share";
         if (mask != 0 && mask != 1) throw Error("mkhe_bfv_refresh_share: mask must be 0 or 1");
         if (flood_bits < 0 || flood_bits > BRF_MAX_FLOOD) throw Error("mkhe_bfv_refresh_share: flood_bits must be 0 .. 1024");
         if (!key) throw Error("mkhe_bfv_refresh_share: null key");              // (mask = 0 and flood_bits = 0 read no stream of nonce_mask, the encryption still draws its samples)
         if ((mask || flood_bits > 0) && nonce_mask == nonce_enc)
             throw Error("mkhe_bfv_refresh_share: nonce_mask and nonce_enc must differ (the mask and the encryption would share streams)");
-        Context* c = brf_need(ctx, what, count, in, "a replay would repeat the keystream");
-        if (!slots || !dev_sk || !dev_pk || !dev_shares || !reenc) throw Error("mkhe_bfv_refresh_share: null argument");
-        smp_table_ok(what, cdt, ncdt);
-        need_aligned(dev_sk, what); need_aligned(dev_pk, what); need_aligned(dev_shares, what);
-        for (int b = 0; b < count; ++b)
-            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_bfv_refresh_share: slot out of range (party slots are 1 .. n)");
-        rf_outputs(what, count, in, count, reenc);
-        std::vector<u64*> d(count);
-        for (int b = 0; b < count; ++b) {
-            const Ct& o = reenc[b]->c;
-            if (o.n != 1 || o.ids[0] != in[b]->c.ids[slots[b] - 1]) throw Error("mkhe_bfv_refresh_share: every reenc must be a ciphertext over exactly the id at the slot of its input");
-            if (o.limbs != c->nq) throw Error("mkhe_bfv_refresh_share: every reenc must have the nQ limbs of the context");
-            d[b] = o.d;
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        c->bfv_refresh_prepare(what);                                           // T outside the encoder's preconditions: refused here
-        const int most = c->bfv_refresh_max_flood();
-        if (flood_bits > most)
-            throw Error("mkhe_bfv_refresh_share: flood_bits must be at most bitlen(Q div 2T) - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
-        g_last_ctx = c;
-        auto i = ct_list(ctx, in, count, what);
-        ct_list_out(ctx, reenc, count, what);
-        c->bfv_refresh_share(i, slots, (const u64*)dev_sk, (const u64*)dev_pk, key, nonce_mask, nonce_enc, mask, flood_bits, cdt, ncdt, (u64*)dev_shares, d.data());
+        refresh_share_entry(ctx, "mkhe_bfv_refresh_share", true, count, in, slots, dev_sk, dev_pk, key, nonce_mask, nonce_enc, mask, flood_bits, cdt, ncdt, dev_shares, reenc);
     })
+}
+// both refresh merges
+static void refresh_merge_entry(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares,
+                                const mkhe_ct* const* reenc, mkhe_ct* const* out) {
+    const std::string w(what);
+    Context* c = refresh_enter(ctx, what, bfv, count, in, UPLOADS);
+    if (!out) throw Error(w + ": null argument");
+    merge_shape(what, count, in, nshares);
+    if (nshares > 0 && (!dev_shares || !reenc)) throw Error(w + ": null argument");
+    rf_outputs(what, count, in, count, out);
+    const int lout = refresh_limbs(c, w, bfv, out[0], "out");
+    std::vector<const u64*> sh(nshares);
+    std::vector<const u64*> re((size_t)nshares * count);
+    std::vector<u64*> d(count);
+    for (int b = 0; b < count; ++b) {
+        if (out[b]->c.ids != in[0]->c.ids) throw Error(w + ": every out must be over the ids of the inputs");
+        if (out[b]->c.limbs != lout) throw Error(w + (bfv ? ": every out must have the nQ limbs of the context" : ": every out must have the same number of limbs"));
+        d[b] = out[b]->c.d;
+    }
+    for (int i = 0; i < nshares; ++i) {
+        sh[i] = share_at(dev_shares, i, what);
+        for (int b = 0; b < count; ++b) {
+            const mkhe_ct* r = reenc[(size_t)i * count + b];
+            if (!r) throw Error(w + ": null reenc in the list");
+            if (r->c.n != 1 || r->c.ids[0] != in[0]->c.ids[i]) throw Error(w + ": reenc[i * count + b] must be a ciphertext over exactly the id at slot 1 + i");
+            if (r->c.limbs != lout) throw Error(w + (bfv ? ": every reenc must have the nQ limbs of the context" : ": every reenc must have the limbs of out"));
+            for (int k = 0; k < count; ++k) if (out[k] == r || out[k]->c.d == r->c.d) throw Error(w + ": an output aliases an input");
+            re[(size_t)i * count + b] = r->c.d;
+        }
+    }
+    commit(c, [&] { if (bfv) c->bfv_refresh_prepare(what); });
+    auto i = ct_list(ctx, in, count, what);
+    if (nshares > 0) ct_list(ctx, reenc, nshares * count, what);
+    ct_list_out(ctx, out, count, what);
+    if (bfv) c->bfv_refresh_merge(i, sh, re, d.data());
+    else c->refresh_merge(i, sh, re, lout, d.data());
+}
+int mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, const mkhe_ct* const* reenc,
+                       mkhe_ct* const* out) {
+    MKHE_TRY(refresh_merge_entry(ctx, "mkhe_refresh_merge", false, count, in, nshares, dev_shares, reenc, out))
 }
 int mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, const mkhe_ct* const* reenc,
                            mkhe_ct* const* out) {
-    MKHE_TRY({
-        const char* what = "mkhe_bfv_refresh_merge";
-        Context* c = brf_need(ctx, what, count, in, "the call allocates and uploads");
-        if (!out) throw Error("mkhe_bfv_refresh_merge: null argument");
-        for (int b = 0; b < count; ++b)
-            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_bfv_refresh_merge: every ciphertext must be over the same ids");
-        if (nshares != in[0]->c.n) throw Error("mkhe_bfv_refresh_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
-        if (nshares > 0 && (!dev_shares || !reenc)) throw Error("mkhe_bfv_refresh_merge: null argument");
-        rf_outputs(what, count, in, count, out);
-        std::vector<const u64*> sh(nshares);
-        std::vector<const u64*> re((size_t)nshares * count);
-        std::vector<u64*> d(count);
-        for (int b = 0; b < count; ++b) {
-            if (out[b]->c.ids != in[0]->c.ids) throw Error("mkhe_bfv_refresh_merge: every out must be over the ids of the inputs");
-            if (out[b]->c.limbs != c->nq) throw Error("mkhe_bfv_refresh_merge: every out must have the nQ limbs of the context");
-            d[b] = out[b]->c.d;
-        }
-        for (int i = 0; i < nshares; ++i) {
-            if (!dev_shares[i]) throw Error("mkhe_bfv_refresh_merge: null share in the per-party list");
-            need_aligned(dev_shares[i], what);
-            sh[i] = (const u64*)dev_shares[i];
-            for (int b = 0; b < count; ++b) {
-                const mkhe_ct* r = reenc[(size_t)i * count + b];
-                if (!r) throw Error("mkhe_bfv_refresh_merge: null reenc in the list");
-                if (r->c.n != 1 || r->c.ids[0] != in[0]->c.ids[i]) throw Error("mkhe_bfv_refresh_merge: reenc[i * count + b] must be a ciphertext over exactly the id at slot 1 + i");
-                if (r->c.limbs != c->nq) throw Error("mkhe_bfv_refresh_merge: every reenc must have the nQ limbs of the context");
-                for (int k = 0; k < count; ++k) if (out[k] == r || out[k]->c.d == r->c.d) throw Error("mkhe_bfv_refresh_merge: an output aliases an input");
-                re[(size_t)i * count + b] = r->c.d;
-            }
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        c->bfv_refresh_prepare(what);
-        g_last_ctx = c;
-        auto i = ct_list(ctx, in, count, what);
-        if (nshares > 0) ct_list(ctx, reenc, nshares * count, what);
-        ct_list_out(ctx, out, count, what);
-        c->bfv_refresh_merge(i, sh, re, d.data());
-    })
+    MKHE_TRY(refresh_merge_entry(ctx, "mkhe_bfv_refresh_merge", true, count, in, nshares, dev_shares, reenc, out))
 }
-// collective key switch to a recipient's public key: the checks the two calls share, under the rules of distributed decryption.  The share
-// draws from the keystream and is refused inside a capture; the merge allocates nothing, uploads nothing that outlives the call and may be captured
-// as long as it stages no table (count and nshares at most 16).
-static Context* pcks_need(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, bool keystream) {
-    if (!ctx) throw Error(std::string(what) + ": null context");
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+// collective key switch to a recipient's public key, under the rules of distributed decryption.  The share draws from the keystream and is refused
+// inside a capture; the merge allocates nothing, uploads nothing that outlives the call and may be captured as long as it stages no table (count
+// and nshares at most 16).
+static Context* pcks_enter(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, bool keystream) {
+    Context* c = enter(ctx, what);
+    count_ok(what, count);
     if (!in) throw Error(std::string(what) + ": null argument");
-    for (int b = 0; b < count; ++b) {
-        if (!in[b]) throw Error(std::string(what) + ": null ciphertext in the batch");
-        if (c->is_bfv() && in[b]->c.limbs != c->nq) throw Error(std::string(what) + ": on a BFV context every ciphertext must have the nQ limbs of the context");
-        if (in[b]->c.limbs != in[0]->c.limbs) throw Error(std::string(what) + ": every ciphertext must be at the same level");
-    }
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) {
-        if (keystream) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (a replay would repeat the keystream)");
-        if (count > ED_INLINE) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end with more than 16 ciphertexts or shares (the pointer tables are staged)");
-    }
+    batch_ok(what, count, in, c->is_bfv() ? c->nq : 0, ": on a BFV context every ciphertext must have the nQ limbs of the context");
+    unmasked(c, what);
+    if (keystream) not_captured(c, what, REPLAYS);
+    else if (count > ED_INLINE) not_captured(c, what, STAGES);
     return c;
 }
 int mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const void* dev_pk_recipient,
@@ -1133,17 +1073,15 @@ int mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const in
         const char* what = "mkhe_pcks_share";
         if (flood_bits < 0 || flood_bits > PCKS_MAX_FLOOD) throw Error("mkhe_pcks_share: flood_bits must be 0 .. 1024");
         if (!key) throw Error("mkhe_pcks_share: null key");                     // (flood_bits = 0 reads no flood stream, u and e1 are drawn from the key all the same)
-        Context* c = pcks_need(ctx, what, count, in, true);
+        Context* c = pcks_enter(ctx, what, count, in, true);
         if (!slots || !dev_sk || !dev_pk_recipient || !dev_shares) throw Error("mkhe_pcks_share: null argument");
         smp_table_ok(what, cdt, ncdt);
         need_aligned(dev_sk, what); need_aligned(dev_pk_recipient, what); need_aligned(dev_shares, what);
-        for (int b = 0; b < count; ++b)
-            if (slots[b] < 1 || slots[b] > in[b]->c.n) throw Error("mkhe_pcks_share: slot out of range (party slots are 1 .. n)");
+        slots_ok(what, count, in, slots);
         const int most = c->flood_room(in[0]->c.limbs, c->is_bfv() ? c->bfv_t : 1);
         if (flood_bits > most)
             throw Error("mkhe_pcks_share: flood_bits must be at most bitlen(Q_l div 2T') - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
+        commit(c);
         auto i = ct_list(ctx, in, count, what);
         c->pcks_share(i, slots, (const u64*)dev_sk, (const u64*)dev_pk_recipient, key, nonce, flood_bits, cdt, ncdt, (u64*)dev_shares);
     })
@@ -1151,33 +1089,20 @@ int mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const in
 int mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_pcks_merge";
-        Context* c = pcks_need(ctx, what, count, in, false);
+        Context* c = pcks_enter(ctx, what, count, in, false);
         if (!out) throw Error("mkhe_pcks_merge: null argument");
-        for (int b = 0; b < count; ++b)
-            if (in[b]->c.ids != in[0]->c.ids) throw Error("mkhe_pcks_merge: every ciphertext must be over the same ids");
-        if (nshares != in[0]->c.n) throw Error("mkhe_pcks_merge: nshares must be the number of parties of the ciphertexts (one share per party, in slot order)");
+        merge_shape(what, count, in, nshares);
         if (nshares > 0 && !dev_shares) throw Error("mkhe_pcks_merge: null argument");
         rf_outputs(what, count, in, count, out);
-        std::vector<const u64*> sh(nshares);
         std::vector<u64*> d(count);
         for (int b = 0; b < count; ++b) {
             if (out[b]->c.n != 1) throw Error("mkhe_pcks_merge: every out must be a ciphertext over exactly one id (the recipient's)");
             if (out[b]->c.limbs != in[0]->c.limbs) throw Error("mkhe_pcks_merge: every out must have the limbs of the inputs");
             d[b] = out[b]->c.d;
         }
-        for (int i = 0; i < nshares; ++i) {
-            if (!dev_shares[i]) throw Error("mkhe_pcks_merge: null share in the per-party list");
-            need_aligned(dev_shares[i], what);
-            sh[i] = (const u64*)dev_shares[i];
-        }
-        if (nshares > ED_INLINE) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(c->stream, &cs);
-            if (cs != hipStreamCaptureStatusNone)
-                throw Error("mkhe_pcks_merge: not available inside mkhe_capture_begin .. mkhe_capture_end with more than 16 ciphertexts or shares (the pointer tables are staged)");
-        }
-        MKHE_HIP(hipSetDevice(c->device));
-        g_last_ctx = c;
+        auto sh = share_list(dev_shares, nshares, what);
+        if (nshares > ED_INLINE) not_captured(c, what, STAGES);
+        commit(c);
         auto i = ct_list(ctx, in, count, what);
         ct_list_out(ctx, out, count, what);
         c->pcks_merge(i, sh, d.data());
@@ -1185,33 +1110,29 @@ int mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nsha
 }
 
 // ---- CKKS encoder (ckks_encode.hip)
-// the argument checks every encoder call shares; a call refused here leaves the context (and a capture in progress) as it was
-static Context* ck_need(mkhe_ctx* ctx, const char* what, int count, const void* a, const void* b) {
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
+// the argument checks every call of the two encoders shares (the BFV batch encoder is bfv_encode.hip); their null context is need()'s
+static Context* encoder_enter(mkhe_ctx* ctx, bool bfv, const char* what, int count, const void* a, const void* b) {
+    Context* c = enter(ctx, nullptr);
     if (!a || !b) throw Error(std::string(what) + ": null argument");
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
+    count_ok(what, count);
     need_aligned(a, what); need_aligned(b, what);
-    if (c->is_bfv()) throw Error(std::string(what) + ": the CKKS encoder needs a CKKS context");
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (the call allocates and uploads)");
-    MKHE_HIP(hipSetDevice(c->device));
-    g_last_ctx = c;
+    scheme_ok(c, what, bfv, bfv ? ": the BFV encoder needs a BFV context" : ": the CKKS encoder needs a CKKS context");
+    unmasked(c, what);
+    not_captured(c, what, UPLOADS);
+    commit(c);
     return c;
 }
-static Context* ck_need_ctx(mkhe_ctx* ctx, const char* what) {
-    alignas(16) static const double dummy[2] = {0, 0};      // (no buffers in these calls)
-    return ck_need(ctx, what, 1, dummy, dummy);
+static Context* encoder_enter(mkhe_ctx* ctx, bool bfv, const char* what) {
+    alignas(16) static const u64 dummy[2] = {0, 0};         // (no buffers in these calls)
+    return encoder_enter(ctx, bfv, what, 1, dummy, dummy);
 }
 int mkhe_ctx_ckks_tile(mkhe_ctx* ctx) {
     g_last_ctx = nullptr;
-    try { return ck_need_ctx(ctx, "mkhe_ctx_ckks_tile")->ckks_tile(); }
+    try { return encoder_enter(ctx, false, "mkhe_ctx_ckks_tile")->ckks_tile(); }
     catch (const std::exception& e) { g_err = e.what(); return -1; }
     catch (...) { g_err = "mkhe: unknown error"; return -1; }
 }
-int mkhe_ctx_set_ckks_tile(mkhe_ctx* ctx, int log_points) { MKHE_TRY({ ck_need_ctx(ctx, "mkhe_ctx_set_ckks_tile")->ckks_set_tile(log_points); }) }
+int mkhe_ctx_set_ckks_tile(mkhe_ctx* ctx, int log_points) { MKHE_TRY({ encoder_enter(ctx, false, "mkhe_ctx_set_ckks_tile")->ckks_set_tile(log_points); }) }
 static void ck_scale_ok(double scale, const char* what) {
     if (!(scale > 0.0) || scale > 1.7976931348623157e308) throw Error(std::string(what) + ": scale must be finite and positive");
 }
@@ -1219,15 +1140,15 @@ static void ck_limbs_ok(const Context* c, int limbs, const char* what, const cha
     if (limbs < 1 || limbs > c->nq) throw Error(std::string(what) + ": " + name + " out of range");
 }
 int mkhe_ckks_embed(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_coeffs) {
-    MKHE_TRY({ ck_need(ctx, "mkhe_ckks_embed", count, dev_slots, dev_coeffs)->ckks_embed(count, (const double*)dev_slots, (double*)dev_coeffs); })
+    MKHE_TRY({ encoder_enter(ctx, false, "mkhe_ckks_embed", count, dev_slots, dev_coeffs)->ckks_embed(count, (const double*)dev_slots, (double*)dev_coeffs); })
 }
 int mkhe_ckks_project(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_slots) {
-    MKHE_TRY({ ck_need(ctx, "mkhe_ckks_project", count, dev_coeffs, dev_slots)->ckks_project(count, (const double*)dev_coeffs, (double*)dev_slots); })
+    MKHE_TRY({ encoder_enter(ctx, false, "mkhe_ckks_project", count, dev_coeffs, dev_slots)->ckks_project(count, (const double*)dev_coeffs, (double*)dev_slots); })
 }
 int mkhe_ckks_scale_up(mkhe_ctx* ctx, int level, int count, const void* dev_coeffs, double scale, void* dev_pt) {
     MKHE_TRY({
         ck_scale_ok(scale, "mkhe_ckks_scale_up");
-        Context* c = ck_need(ctx, "mkhe_ckks_scale_up", count, dev_coeffs, dev_pt);
+        Context* c = encoder_enter(ctx, false, "mkhe_ckks_scale_up", count, dev_coeffs, dev_pt);
         ck_limbs_ok(c, level + 1, "mkhe_ckks_scale_up", "level");
         c->ckks_scale_up(level, count, (const double*)dev_coeffs, scale, (u64*)dev_pt);
     })
@@ -1235,7 +1156,7 @@ int mkhe_ckks_scale_up(mkhe_ctx* ctx, int level, int count, const void* dev_coef
 int mkhe_ckks_scale_down(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_coeffs) {
     MKHE_TRY({
         ck_scale_ok(scale, "mkhe_ckks_scale_down");
-        Context* c = ck_need(ctx, "mkhe_ckks_scale_down", count, dev_pt, dev_coeffs);
+        Context* c = encoder_enter(ctx, false, "mkhe_ckks_scale_down", count, dev_pt, dev_coeffs);
         ck_limbs_ok(c, limbs, "mkhe_ckks_scale_down", "limbs");
         c->ckks_scale_down(limbs, count, (const u64*)dev_pt, scale, (double*)dev_coeffs);
     })
@@ -1243,7 +1164,7 @@ int mkhe_ckks_scale_down(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt
 int mkhe_ckks_encode(mkhe_ctx* ctx, int level, int count, const void* dev_slots, double scale, void* dev_pt) {
     MKHE_TRY({
         ck_scale_ok(scale, "mkhe_ckks_encode");
-        Context* c = ck_need(ctx, "mkhe_ckks_encode", count, dev_slots, dev_pt);
+        Context* c = encoder_enter(ctx, false, "mkhe_ckks_encode", count, dev_slots, dev_pt);
         ck_limbs_ok(c, level + 1, "mkhe_ckks_encode", "level");
         c->ckks_encode(level, count, (const double*)dev_slots, scale, (u64*)dev_pt);
     })
@@ -1251,74 +1172,54 @@ int mkhe_ckks_encode(mkhe_ctx* ctx, int level, int count, const void* dev_slots,
 int mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_slots) {
     MKHE_TRY({
         ck_scale_ok(scale, "mkhe_ckks_decode");
-        Context* c = ck_need(ctx, "mkhe_ckks_decode", count, dev_pt, dev_slots);
+        Context* c = encoder_enter(ctx, false, "mkhe_ckks_decode", count, dev_pt, dev_slots);
         ck_limbs_ok(c, limbs, "mkhe_ckks_decode", "limbs");
         c->ckks_decode(limbs, count, (const u64*)dev_pt, scale, (double*)dev_slots);
     })
 }
 
 // ---- BFV batch encoder (bfv_encode.hip)
-// the argument checks every call shares; a call refused here leaves the context (and a capture in progress) as it was
-static Context* bf_need(mkhe_ctx* ctx, const char* what, int count, const void* a, const void* b) {
-    Context* c = need(ctx);
-    g_last_ctx = nullptr;
-    if (!a || !b) throw Error(std::string(what) + ": null argument");
-    if (count < 1 || count > 65535) throw Error(std::string(what) + ": count must be 1 .. 65535");
-    need_aligned(a, what); need_aligned(b, what);
-    if (!c->is_bfv()) throw Error(std::string(what) + ": the BFV encoder needs a BFV context");
-    if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) throw Error(std::string(what) + ": not available inside mkhe_capture_begin .. mkhe_capture_end (the call allocates and uploads)");
-    MKHE_HIP(hipSetDevice(c->device));
-    g_last_ctx = c;
-    return c;
-}
-static Context* bf_need_ctx(mkhe_ctx* ctx, const char* what) {
-    alignas(16) static const u64 dummy[2] = {0, 0};         // (no buffers in these calls)
-    return bf_need(ctx, what, 1, dummy, dummy);
-}
 int mkhe_ctx_bfv_tile(mkhe_ctx* ctx) {
     g_last_ctx = nullptr;
-    try { return bf_need_ctx(ctx, "mkhe_ctx_bfv_tile")->bfv_tile(); }
+    try { return encoder_enter(ctx, true, "mkhe_ctx_bfv_tile")->bfv_tile(); }
     catch (const std::exception& e) { g_err = e.what(); return -1; }
     catch (...) { g_err = "mkhe: unknown error"; return -1; }
 }
-int mkhe_ctx_set_bfv_tile(mkhe_ctx* ctx, int log_points) { MKHE_TRY({ bf_need_ctx(ctx, "mkhe_ctx_set_bfv_tile")->bfv_set_tile(log_points); }) }
+int mkhe_ctx_set_bfv_tile(mkhe_ctx* ctx, int log_points) { MKHE_TRY({ encoder_enter(ctx, true, "mkhe_ctx_set_bfv_tile")->bfv_set_tile(log_points); }) }
 uint64_t mkhe_ctx_bfv_slot_psi(mkhe_ctx* ctx) {
     g_last_ctx = nullptr;
-    try { return bf_need_ctx(ctx, "mkhe_ctx_bfv_slot_psi")->bfv_slot_psi(); }
+    try { return encoder_enter(ctx, true, "mkhe_ctx_bfv_slot_psi")->bfv_slot_psi(); }
     catch (const std::exception& e) { g_err = e.what(); return 0; }
     catch (...) { g_err = "mkhe: unknown error"; return 0; }
 }
 int mkhe_bfv_slots_to_coeffs(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_coeffs) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_slots_to_coeffs", count, dev_slots, dev_coeffs)->bfv_slots_to_coeffs(count, (const u64*)dev_slots, (u64*)dev_coeffs); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_slots_to_coeffs", count, dev_slots, dev_coeffs)->bfv_slots_to_coeffs(count, (const u64*)dev_slots, (u64*)dev_coeffs); })
 }
 int mkhe_bfv_coeffs_to_slots(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_slots) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_coeffs_to_slots", count, dev_coeffs, dev_slots)->bfv_coeffs_to_slots(count, (const u64*)dev_coeffs, (u64*)dev_slots); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_coeffs_to_slots", count, dev_coeffs, dev_slots)->bfv_coeffs_to_slots(count, (const u64*)dev_coeffs, (u64*)dev_slots); })
 }
 int mkhe_bfv_scale_up(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_pt) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_scale_up", count, dev_coeffs, dev_pt)->bfv_scale_up(count, (const u64*)dev_coeffs, (u64*)dev_pt); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_scale_up", count, dev_coeffs, dev_pt)->bfv_scale_up(count, (const u64*)dev_coeffs, (u64*)dev_pt); })
 }
 int mkhe_bfv_scale_down(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_coeffs) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_scale_down", count, dev_pt, dev_coeffs)->bfv_scale_down(count, (const u64*)dev_pt, (u64*)dev_coeffs); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_scale_down", count, dev_pt, dev_coeffs)->bfv_scale_down(count, (const u64*)dev_pt, (u64*)dev_coeffs); })
 }
 int mkhe_bfv_encode(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_pt) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_encode", count, dev_slots, dev_pt)->bfv_encode(count, (const u64*)dev_slots, (u64*)dev_pt); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_encode", count, dev_slots, dev_pt)->bfv_encode(count, (const u64*)dev_slots, (u64*)dev_pt); })
 }
 int mkhe_bfv_decode(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_slots) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_decode", count, dev_pt, dev_slots)->bfv_decode(count, (const u64*)dev_pt, (u64*)dev_slots); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_decode", count, dev_pt, dev_slots)->bfv_decode(count, (const u64*)dev_pt, (u64*)dev_slots); })
 }
 int mkhe_bfv_lift(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_ptmul_coeff) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_lift", count, dev_coeffs, dev_ptmul_coeff)->bfv_lift(count, (const u64*)dev_coeffs, (u64*)dev_ptmul_coeff); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_lift", count, dev_coeffs, dev_ptmul_coeff)->bfv_lift(count, (const u64*)dev_coeffs, (u64*)dev_ptmul_coeff); })
 }
 int mkhe_bfv_encode_mul(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_ptmul) {
-    MKHE_TRY({ bf_need(ctx, "mkhe_bfv_encode_mul", count, dev_slots, dev_ptmul)->bfv_encode_mul(count, (const u64*)dev_slots, (u64*)dev_ptmul); })
+    MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_encode_mul", count, dev_slots, dev_ptmul)->bfv_encode_mul(count, (const u64*)dev_slots, (u64*)dev_ptmul); })
 }
 int mkhe_bfv_ct_mul_ptxt(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, const void* dev_ptmul, long pt_stride_words, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_bfv_ct_mul_ptxt";
-        Context* c = bf_need(ctx, what, nbatch, dev_ptmul, dev_ptmul);
+        Context* c = encoder_enter(ctx, true, what, nbatch, dev_ptmul, dev_ptmul);
         auto i = ct_list(ctx, in, nbatch, what);
         auto o = ct_list_out(ctx, out, nbatch, what);
         c->bfv_ct_mul_ptxt(what, i, (const u64*)dev_ptmul, pt_stride_words, o);
@@ -1327,7 +1228,7 @@ int mkhe_bfv_ct_mul_ptxt(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, co
 int mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_bfv_ct_add_ptxt";
-        Context* c = bf_need(ctx, what, nbatch, dev_pt, dev_pt);
+        Context* c = encoder_enter(ctx, true, what, nbatch, dev_pt, dev_pt);
         if (op != 0 && op != 1) throw Error(std::string(what) + ": op must be 0 (add) or 1 (sub)");
         auto i = ct_list(ctx, in, nbatch, what);
         auto o = ct_list_out(ctx, out, nbatch, what);

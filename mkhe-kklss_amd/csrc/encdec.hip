@@ -27,9 +27,29 @@ EdTable Context::ed_table(const std::vector<const u64*>& v, size_t tab_offset) {
     return t;
 }
 
+void Context::need_unmasked(const char* what) const {
+    if (masked_) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+}
+
+// Key-bearing arguments of one launch.  stream_fill writes the prefix every such struct starts with (the key words are zero when the launch reads
+// no stream); wipe overwrites the host copy behind the launch (the runtime has copied the arguments).
+template <class T> static void stream_fill(T& a, const u32* key, u64 nonce, bool reads = true) {
+    for (int i = 0; i < 8; ++i) a.key[i] = reads ? key[i] : 0;
+    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32);
+}
+template <class T> static void wipe(T& a) {
+    auto* p = reinterpret_cast<volatile unsigned char*>(&a);
+    for (size_t i = 0; i < sizeof(a); ++i) p[i] = 0;
+}
+static void sample_args_fill(SmallSampleArgs& a, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt) {
+    stream_fill(a, key, nonce);
+    a.first_stream = first_stream; a.ncdt = ncdt;
+    for (int t = 0; t < SMP_MAX_CDT; ++t) a.cdt[t] = t < ncdt ? cdt[t] : ~0ull;
+}
+
 void Context::encrypt(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const int32_t* samples, u64* const* outs) {
     check_level(level);
-    if (masked_) throw Error("mkhe_encrypt: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_encrypt");
     const int L = level + 1;
     const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
     u64* w = scratch(ed_w_, 3 * pw);
@@ -69,49 +89,44 @@ void Context::encrypt_core(int level, int count, const u64* pk, const u64* pt, b
     MKHE_HIP(hipGetLastError());
 }
 
-// key, nonce and table as the arguments of one launch; the host copy is overwritten behind the launch (the runtime has copied the arguments)
-static void sample_args_wipe(SmallSampleArgs& a) {
-    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&a);
-    for (size_t i = 0; i < sizeof(a); ++i) p[i] = 0;
-}
-static void sample_args_fill(SmallSampleArgs& a, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt) {
-    for (int i = 0; i < 8; ++i) a.key[i] = key[i];
-    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32); a.first_stream = first_stream; a.ncdt = ncdt;
-    for (int t = 0; t < SMP_MAX_CDT; ++t) a.cdt[t] = t < ncdt ? cdt[t] : ~0ull;
+// u, e0, e1 of count encryptions from the keystream, then encrypt_core.  The sampler writes [count][3][N] straight into small and, in the same
+// launch, the rows of u a second time behind it (the layout the two copies of encrypt() produce): no upload, no extra launch, and nothing for the
+// host to wait for.
+void Context::encrypt_sampled(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const u32* key, u64 nonce, const u64* cdt, int ncdt,
+                              u64* w, int32_t* small, const EdTable& ot) {
+    SmallSampleArgs a;
+    sample_args_fill(a, key, nonce, 0, cdt, ncdt);
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
+        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * (size_t)count * N, N, s_);
+    }
+    wipe(a);
+    encrypt_core(level, count, pk, pt, pt_is_ntt, w, small, ot);
 }
 
 void Context::sample_small(int kind, int count, const u32* key, u64 nonce, u32 first_stream, const u64* cdt, int ncdt, int32_t* dev_out) {
-    if (masked_) throw Error("mkhe_sample_small: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_sample_small");
     SmallSampleArgs a;
     sample_args_fill(a, key, nonce, first_stream, kind == 1 ? cdt : nullptr, kind == 1 ? ncdt : 0);
     {
         ProfScope ps(this, PROF_OTHER, 4.0 * count * N);
         launch_small_sample(a, kind, count, dev_out, nullptr, N, s_);
     }
-    sample_args_wipe(a);
+    wipe(a);
     MKHE_HIP(hipGetLastError());
 }
 
-// The sampler writes [count][3][N] straight into ed_small_ and, in the same launch, the rows of u a second time behind it (the layout the two
-// copies of encrypt() produce): no upload, no extra launch, and nothing for the host to wait for.
 void Context::encrypt_seeded(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const u32* key, u64 nonce, const u64* cdt, int ncdt,
                              u64* const* outs) {
     check_level(level);
-    if (masked_) throw Error("mkhe_encrypt_seeded: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_encrypt_seeded");
     const int L = level + 1;
     const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
     u64* w = scratch(ed_w_, 3 * pw);
     int32_t* small = reinterpret_cast<int32_t*>(scratch(ed_small_, 2 * sn));
     scratch(ed_tab_, (size_t)count);
     const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0);     // count > ED_INLINE: staged, which synchronises
-    SmallSampleArgs a;
-    sample_args_fill(a, key, nonce, 0, cdt, ncdt);
-    {
-        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
-        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * sn, N, s_);
-    }
-    sample_args_wipe(a);
-    encrypt_core(level, count, pk, pt, pt_is_ntt, w, small, ot);
+    encrypt_sampled(level, count, pk, pt, pt_is_ntt, key, nonce, cdt, ncdt, w, small, ot);
 }
 
 // acc [limbs][N] <- sum_i NTT-domain products of the k polynomials at ch [k][limbs][N] with the secrets sks[i]
@@ -125,7 +140,7 @@ void Context::ed_mac(int k, const u64* ch, const u64* const* sks, int limbs, u64
 }
 
 void Context::partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out) {
-    if (masked_) throw Error("mkhe_partial_decrypt: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_partial_decrypt");
     if (slot < 1 || slot > in.n) throw Error("mkhe_partial_decrypt: slot out of range (party slots are 1 .. n)");
     if (out.limbs != in.limbs) throw Error("mkhe_partial_decrypt: out must be at the level of in");
     std::vector<int> rest(in.ids);
@@ -149,7 +164,7 @@ void Context::partial_decrypt(const Ct& in, int slot, const u64* sk, Ct& out) {
 }
 
 void Context::decrypt(const Ct& ct, const u64* const* sks, u64* pt_out) {
-    if (masked_) throw Error("mkhe_decrypt: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_decrypt");
     const int k = ct.n, L = ct.limbs;
     const size_t pw = (size_t)L * N;
     u64* w = scratch(ed_w_, (size_t)(k + 1) * pw);
@@ -208,27 +223,26 @@ void Context::gather_ntt(const std::vector<const u64*>& src, int L, u64* w) {
 }
 
 void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares) {
-    if (masked_) throw Error("mkhe_decrypt_share: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_decrypt_share");
     const int count = (int)ins.size(), L = ins[0]->limbs;
     const size_t pw = (size_t)L * N;
     u64* w = scratch(ed_w_, (size_t)count * pw);
     share_product(ins, slots, sk, w);
     ShareFloodArgs a;
-    for (int i = 0; i < 8; ++i) a.key[i] = bits > 0 ? key[i] : 0;
-    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32); a.bits = bits;
+    stream_fill(a, key, nonce, bits > 0);
+    a.bits = bits;
     {
         ProfScope ps(this, PROF_OTHER, 16.0 * N * L * count);
         // one limb per grid row: the ChaCha20 block is recomputed per limb, and every launch has limbs times the waves (profiles/README.md)
         launch_share_finish(a, count, shares, w, d_mods, L, MKHE_AB_INT("MKHE_SHARE_ROWS", L), N, s_);
     }
-    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&a);      // the runtime has copied the arguments
-    for (size_t i = 0; i < sizeof(a); ++i) p[i] = 0;
+    wipe(a);
     MKHE_HIP(hipMemsetAsync(w, 0, (size_t)count * pw * sizeof(u64), s_));
     MKHE_HIP(hipGetLastError());
 }
 
 void Context::decrypt_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* pt) {
-    if (masked_) throw Error("mkhe_decrypt_merge: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_decrypt_merge");
     const int count = (int)ins.size(), L = ins[0]->limbs;
     std::vector<const u64*> c(count);
     for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
@@ -245,10 +259,9 @@ void Context::decrypt_merge(const std::vector<const Ct*>& ins, const std::vector
 // encrypt_seeded on the plaintext -M that kernel left in the scratch.  ed_w_ holds, in this order, the work buffer of encrypt_core
 // [3][count][Lout][N], the plaintext [count][Lout][N] and the product [count][Lin][N]; ed_tab_ the two tables of the product and the outputs'.
 // Sized once, in front: a scratch that grows moves.  The product, the plaintext and the samples are wiped behind their last use.
-void Context::refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask,
-                            u64 nonce_enc, int bits, const u64* cdt, int ncdt, u64* shares, int lout, u64* const* outs) {
-    if (masked_) throw Error("mkhe_refresh_share: not available on a context that owns a subset of the moduli");
-    check_level(lout - 1);
+// finish(prod, pt) launches the kernel that turns the product into the public share and the plaintext; finish_bytes is what its ProfScope counts
+template <class F> void Context::refresh_share_chain(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key,
+                                                     u64 nonce_enc, const u64* cdt, int ncdt, int lout, u64* const* outs, double finish_bytes, F finish) {
     const int count = (int)ins.size(), lin = ins[0]->limbs;
     const size_t pin = (size_t)count * lin * N, pout = (size_t)count * lout * N, sn = (size_t)count * N;
     u64* w = scratch(ed_w_, 4 * pout + pin);
@@ -257,31 +270,46 @@ void Context::refresh_share(const std::vector<const Ct*>& ins, const int* slots,
     scratch(ed_tab_, 3 * (size_t)count);
     const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 2 * (size_t)count);
     share_product(ins, slots, sk, prod);
-    RefreshMaskArgs m;
-    for (int i = 0; i < 8; ++i) m.key[i] = bits > 0 ? key[i] : 0;
-    m.nonce_lo = (u32)nonce_mask; m.nonce_hi = (u32)(nonce_mask >> 32); m.bits = bits;
     {
-        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (2.0 * lin + lout));
-        launch_refresh_finish(m, count, shares, prod, pt, d_mods, lin, lout, N, s_);
+        ProfScope ps(this, PROF_OTHER, finish_bytes);
+        finish(prod, pt);
     }
-    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&m);      // the runtime has copied the arguments
-    for (size_t i = 0; i < sizeof(m); ++i) p[i] = 0;
     MKHE_HIP(hipMemsetAsync(prod, 0, pin * sizeof(u64), s_));
-    SmallSampleArgs a;
-    sample_args_fill(a, key, nonce_enc, 0, cdt, ncdt);
-    {
-        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
-        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * sn, N, s_);
-    }
-    sample_args_wipe(a);
-    encrypt_core(lout - 1, count, pk, pt, false, w, small, ot);             // wipes the samples and u * pk
-    MKHE_HIP(hipMemsetAsync(pt, 0, pout * sizeof(u64), s_));                // -M with the public share gives the product away
+    encrypt_sampled(lout - 1, count, pk, pt, false, key, nonce_enc, cdt, ncdt, w, small, ot);      // wipes the samples and u * pk
+    MKHE_HIP(hipMemsetAsync(pt, 0, pout * sizeof(u64), s_));                // the plaintext with the public share gives the product away
     MKHE_HIP(hipGetLastError());
+}
+
+void Context::refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask,
+                            u64 nonce_enc, int bits, const u64* cdt, int ncdt, u64* shares, int lout, u64* const* outs) {
+    need_unmasked("mkhe_refresh_share");
+    check_level(lout - 1);
+    const int count = (int)ins.size(), lin = ins[0]->limbs;
+    refresh_share_chain(ins, slots, sk, pk, key, nonce_enc, cdt, ncdt, lout, outs, 8.0 * N * count * (2.0 * lin + lout), [&](u64* prod, u64* pt) {
+        RefreshMaskArgs m;
+        stream_fill(m, key, nonce_mask, bits > 0);
+        m.bits = bits;
+        launch_refresh_finish(m, count, shares, prod, pt, d_mods, lin, lout, N, s_);
+        wipe(m);
+    });
+}
+
+// the pointer tables of a merge in ed_tab_: [outs][polynomial 0 of ins][shares][reenc]
+Context::MergeTables Context::merge_tables(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,
+                                           u64* const* outs) {
+    const size_t count = ins.size(), k = shares.size();
+    std::vector<const u64*> c(count);
+    for (size_t b = 0; b < count; ++b) c[b] = ins[b]->d;
+    scratch(ed_tab_, 2 * count + k + reenc.size());
+    MergeTables t;
+    t.ot = ed_table(std::vector<const u64*>(outs, outs + count), 0); t.ct = ed_table(c, count);     // count or nshares > ED_INLINE: staged, which synchronises
+    t.st = ed_table(shares, 2 * count); t.rt = ed_table(reenc, 2 * count + k);
+    return t;
 }
 
 void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
                             u64* const* outs) {
-    if (masked_) throw Error("mkhe_refresh_merge: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_refresh_merge");
     check_level(lout - 1);
     const int count = (int)ins.size(), lin = ins[0]->limbs, k = (int)shares.size();
     if (!d_rf_tab_) {
@@ -301,14 +329,10 @@ void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector
     a.garner = garner_table(); a.qmont = d_rf_tab_; a.qprod = d_rf_tab_ + (size_t)nq * nq;
     a.dig = scratch(rf_dig_, (size_t)count * lin * N);
     a.mods = d_mods; a.nq = nq; a.lin = lin; a.lout = lout; a.nshares = k; a.count = count; a.N = N;
-    std::vector<const u64*> c(count);
-    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
-    scratch(ed_tab_, 2 * (size_t)count + (size_t)k + reenc.size());
-    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0), ct = ed_table(c, (size_t)count);
-    const EdTable st = ed_table(shares, 2 * (size_t)count), rt = ed_table(reenc, 2 * (size_t)count + (size_t)k);
+    const MergeTables t = merge_tables(ins, shares, reenc, outs);
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (lin * (1.0 + k) + (lout > lin ? 2.0 * lin : 0.0) + lout * (1.0 + 3.0 * k)));
-        launch_refresh_merge(a, ot, ct, st, rt, s_);
+        launch_refresh_merge(a, t.ot, t.ct, t.st, t.rt, s_);
     }
     MKHE_HIP(hipGetLastError());
 }
@@ -347,36 +371,15 @@ int Context::flood_room(int limbs, u64 t) const {
 void Context::bfv_refresh_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce_mask,
                                 u64 nonce_enc, int mask, int flood_bits, const u64* cdt, int ncdt, u64* shares, u64* const* outs) {
     bf_init("mkhe_bfv_refresh_share");
-    const int count = (int)ins.size();
-    const size_t pw = (size_t)count * nq * N, sn = (size_t)count * N;
-    u64* w = scratch(ed_w_, 5 * pw);
-    u64 *pt = w + 3 * pw, *prod = pt + pw;
-    int32_t* small = reinterpret_cast<int32_t*>(scratch(ed_small_, 2 * sn));
-    scratch(ed_tab_, 3 * (size_t)count);
-    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 2 * (size_t)count);
-    share_product(ins, slots, sk, prod);
-    BfvRefreshArgs m;
-    const bool reads = mask || flood_bits > 0;
-    for (int i = 0; i < 8; ++i) m.key[i] = reads ? key[i] : 0;
-    m.nonce_lo = (u32)nonce_mask; m.nonce_hi = (u32)(nonce_mask >> 32); m.mask = mask; m.flood_bits = flood_bits;
-    {
-        const int W = (flood_bits + 63) / 64;
-        ProfScope ps(this, PROF_OTHER, 24.0 * N * count * nq + 64.0 * (N / 8) * count * nq * (2.0 + W));
+    const int count = (int)ins.size(), W = (flood_bits + 63) / 64;
+    refresh_share_chain(ins, slots, sk, pk, key, nonce_enc, cdt, ncdt, nq, outs, 24.0 * N * count * nq + 64.0 * (N / 8) * count * nq * (2.0 + W),
+                        [&](u64* prod, u64* pt) {
+        BfvRefreshArgs m;
+        stream_fill(m, key, nonce_mask, mask || flood_bits > 0);
+        m.mask = mask; m.flood_bits = flood_bits;
         launch_bfv_refresh_finish(m, count, shares, prod, pt, bf_scale(), s_);
-    }
-    volatile unsigned char* p = reinterpret_cast<volatile unsigned char*>(&m);      // the runtime has copied the arguments
-    for (size_t i = 0; i < sizeof(m); ++i) p[i] = 0;
-    MKHE_HIP(hipMemsetAsync(prod, 0, pw * sizeof(u64), s_));
-    SmallSampleArgs a;
-    sample_args_fill(a, key, nonce_enc, 0, cdt, ncdt);
-    {
-        ProfScope ps(this, PROF_OTHER, 16.0 * count * N);
-        launch_small_sample(a, SMP_KIND_ENCRYPT, 3 * count, small, small + 3 * sn, N, s_);
-    }
-    sample_args_wipe(a);
-    encrypt_core(nq - 1, count, pk, pt, false, w, small, ot);                // wipes the samples and u * pk
-    MKHE_HIP(hipMemsetAsync(pt, 0, pw * sizeof(u64), s_));                   // up(-A) with the public share gives the product away
-    MKHE_HIP(hipGetLastError());
+        wipe(m);
+    });
 }
 
 void Context::bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,
@@ -384,15 +387,11 @@ void Context::bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::ve
     bf_init("mkhe_bfv_refresh_merge");
     const int count = (int)ins.size(), k = (int)shares.size();
     u64* dig = scratch(rf_dig_, (size_t)count * nq * N);
-    std::vector<const u64*> c(count);
-    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
-    scratch(ed_tab_, 2 * (size_t)count + (size_t)k + reenc.size());
-    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0), ct = ed_table(c, (size_t)count);
-    const EdTable st = ed_table(shares, 2 * (size_t)count), rt = ed_table(reenc, 2 * (size_t)count + (size_t)k);
+    const MergeTables t = merge_tables(ins, shares, reenc, outs);
     {
         // every digit is written once and read by each later limb and by the sum
         ProfScope ps(this, PROF_OTHER, 8.0 * N * count * nq * ((1.0 + k) + (2.0 + (nq - 1) / 2.0) + (1.0 + 3.0 * k)));
-        launch_bfv_refresh_merge(count, k, dig, bf_scale(), ot, ct, st, rt, s_);
+        launch_bfv_refresh_merge(count, k, dig, bf_scale(), t.ot, t.ct, t.st, t.rt, s_);
     }
     MKHE_HIP(hipGetLastError());
 }
@@ -404,7 +403,7 @@ void Context::bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::ve
 // u, w[0] and w[1] are wiped behind their last use (w[2] by the product kernel).
 void Context::pcks_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key, u64 nonce, int flood_bits,
                          const u64* cdt, int ncdt, u64* shares) {
-    if (masked_) throw Error("mkhe_pcks_share: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_pcks_share");
     const int count = (int)ins.size(), L = ins[0]->limbs;
     const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
     u64* w = scratch(ed_w_, 3 * pw);
@@ -432,22 +431,18 @@ void Context::pcks_share(const std::vector<const Ct*>& ins, const int* slots, co
         ProfScope ps(this, PROF_OTHER, 32.0 * N * L * count + 64.0 * (N / 8) * count * L * (1.0 + W));
         launch_pcks_finish(a, flood_bits, count, shares, w, d_mods, L, N, s_);
     }
-    sample_args_wipe(a);                                                    // the runtime has copied the arguments
+    wipe(a);
     MKHE_HIP(hipMemsetAsync(w, 0, 2 * pw * sizeof(u64), s_));
     MKHE_HIP(hipGetLastError());
 }
 
 void Context::pcks_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* const* outs) {
-    if (masked_) throw Error("mkhe_pcks_merge: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_pcks_merge");
     const int count = (int)ins.size(), L = ins[0]->limbs;
-    std::vector<const u64*> c(count);
-    for (int b = 0; b < count; ++b) c[b] = ins[b]->d;
-    scratch(ed_tab_, 2 * (size_t)count + shares.size());
-    const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0), ct = ed_table(c, (size_t)count);
-    const EdTable st = ed_table(shares, 2 * (size_t)count);                 // count or nshares > ED_INLINE: staged, which synchronises
+    const MergeTables t = merge_tables(ins, shares, {}, outs);
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * N * L * count * (3.0 + 2.0 * (double)shares.size()));
-        launch_pcks_merge(count, (int)shares.size(), ot, ct, st, d_mods, L, N, s_);
+        launch_pcks_merge(count, (int)shares.size(), t.ot, t.ct, t.st, d_mods, L, N, s_);
     }
     MKHE_HIP(hipGetLastError());
 }
@@ -456,19 +451,14 @@ void Context::pcks_merge(const std::vector<const Ct*>& ins, const std::vector<co
 // straight into polynomial 1 of outs[b]; the gathering forward NTT reads it into w [count][L][N]; skenc_mul (w <- w * sk, or pt - w * sk for a
 // plaintext in the NTT domain); one inverse NTT; skenc_finish writes polynomial 0.  NTT(c1) * s gives s away (c1 is public and invertible with
 // overwhelming probability): w, and the staged e of the host-sample call, are wiped behind the finish kernel.
-static void uniform_args_fill(UniformArgs& a, const u32* key, u64 nonce) {
-    for (int i = 0; i < 8; ++i) a.key[i] = key[i];
-    a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32);
-}
-
 void Context::sample_uniform(int limbs, int count, const u32* key, u64 nonce, u64* dev_out) {
-    if (masked_) throw Error("mkhe_sample_uniform: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_sample_uniform");
     std::vector<const u64*> o(count);
     for (int b = 0; b < count; ++b) o[b] = dev_out + (size_t)b * limbs * N;
     scratch(ed_tab_, (size_t)count);
     const EdTable ot = ed_table(o, 0);                                      // count > ED_INLINE: staged, which synchronises
     UniformArgs a;
-    uniform_args_fill(a, key, nonce);
+    stream_fill(a, key, nonce);
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * count * limbs * N);
         launch_uniform_sample(a, count, ot, 0, d_mods, limbs, nq, N, s_);
@@ -477,11 +467,11 @@ void Context::sample_uniform(int limbs, int count, const u32* key, u64 nonce, u6
 }
 
 void Context::ct_expand_seeded(int count, int limbs, const u32* key, u64 nonce, u64* const* outs) {
-    if (masked_) throw Error("mkhe_ct_expand_seeded: not available on a context that owns a subset of the moduli");
+    need_unmasked("mkhe_ct_expand_seeded");
     scratch(ed_tab_, (size_t)count);
     const EdTable ot = ed_table(std::vector<const u64*>(outs, outs + count), 0);
     UniformArgs a;
-    uniform_args_fill(a, key, nonce);
+    stream_fill(a, key, nonce);
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * count * limbs * N);
         launch_uniform_sample(a, count, ot, (long)limbs * N, d_mods, limbs, nq, N, s_);
@@ -492,7 +482,7 @@ void Context::ct_expand_seeded(int count, int limbs, const u32* key, u64 nonce, 
 void Context::encrypt_sk(int level, int count, const u64* sk, const u64* pt, bool pt_is_ntt, const u32* a_key, u64 a_nonce, const int32_t* e,
                          const u32* e_key, u64 e_nonce, const u64* cdt, int ncdt, u64* const* outs, const char* what) {
     check_level(level);
-    if (masked_) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
+    need_unmasked(what);
     const int L = level + 1;
     const size_t pw = (size_t)count * L * N, sn = (size_t)count * N;
     u64* w = scratch(ed_w_, pw);
@@ -505,7 +495,7 @@ void Context::encrypt_sk(int level, int count, const u64* sk, const u64* pt, boo
         sync();                                                             // the host array may be pageable: do not return before it is consumed
     }
     UniformArgs ua;
-    uniform_args_fill(ua, a_key, a_nonce);
+    stream_fill(ua, a_key, a_nonce);
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * count * L * N);
         launch_uniform_sample(ua, count, ot, (long)L * N, d_mods, L, nq, N, s_);
@@ -524,7 +514,7 @@ void Context::encrypt_sk(int level, int count, const u64* sk, const u64* pt, boo
         ProfScope ps(this, PROF_OTHER, (double)count * N * L * (pt_is_ntt ? 16.0 : 24.0) + (e ? 4.0 * count * N * L : 64.0 * (N / 8) * count * L));
         launch_skenc_finish(a, small, count, ot, w, pt_is_ntt ? nullptr : pt, d_mods, L, N, s_);
     }
-    sample_args_wipe(a);                                                    // the runtime has copied the arguments
+    wipe(a);
     if (e) MKHE_HIP(hipMemsetAsync(small, 0, sn * sizeof(int32_t), s_));
     MKHE_HIP(hipMemsetAsync(w, 0, pw * sizeof(u64), s_));
     MKHE_HIP(hipGetLastError());

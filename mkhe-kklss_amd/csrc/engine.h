@@ -460,6 +460,18 @@ class Context {
     // Encrypt behind "the samples are on the device": small = int32 [count][3][N] + the count rows of u gathered behind it, w = [3][count][L][N];
     // small_expand .. encrypt_finish and the three wipes
     void encrypt_core(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, u64* w, int32_t* small, const EdTable& ot);
+    // the same behind "the samples are streams 3 b + j of (key, nonce)": one sampler launch into small, then encrypt_core
+    void encrypt_sampled(int level, int count, const u64* pk, const u64* pt, bool pt_is_ntt, const u32* key, u64 nonce, const u64* cdt, int ncdt,
+                         u64* w, int32_t* small, const EdTable& ot);
+    // the party side of both refreshes: scratch and output table, share_product, the caller's finish kernel (product -> public share and plaintext),
+    // the wipe of the product, encrypt_sampled of the plaintext at lout limbs, the wipe of the plaintext
+    template <class F> void refresh_share_chain(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key,
+                                                u64 nonce_enc, const u64* cdt, int ncdt, int lout, u64* const* outs, double finish_bytes, F finish);
+    struct MergeTables { EdTable ot, ct, st, rt; };
+    MergeTables merge_tables(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,
+                             u64* const* outs);
+    // the entry points of encdec.hip refuse a context that owns a subset of the moduli under their own name
+    void need_unmasked(const char* what) const;
     // both encoders: the Garner constants [nq][nq], built at the first use, and the two launches of a transform that one tile does not hold:
     // forward the pass over the column tiles (the stages that span the rows) first, inverse last; launch() runs once per pass on the filled-in p
     u64* d_garner_ = nullptr;

@@ -500,16 +500,43 @@ def test_refused_for_a_plaintext_modulus_outside_the_preconditions_of_the_encode
 
 
 def test_refused_on_a_context_that_owns_a_subset_of_the_moduli(w3):
-    """Both calls refuse such a context (capi.hip: brf_need), but no BFV context can become one: mkhe_ctx_set_owned itself refuses BFV contexts.
-    That refusal is what keeps the two calls off a subset of the moduli, so it is what is checked, with a call that works behind it."""
+    """Both calls refuse such a context (capi.hip: the step of the shared guard that holds the refusal), but no BFV context can become one:
+    mkhe_ctx_set_owned itself refuses BFV contexts.  That refusal is what keeps the two calls off a subset of the moduli, so it is what is checked,
+    with a call that works behind it; the source is read for the rest: the step holds the refusal, and both entry points reach it, through the
+    functions they call, before they arm g_last_ctx."""
     w = w3
     own = (C.c_int * 2)(0, 2)
     assert w.lib.mkhe_ctx_set_owned(w.params.ctx, own, 2) != 0 and "limb sharding is wired for the mkckks path" in error()
     good_call(w)
     import os
+    import re
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mkhe-kklss_amd", "csrc", "capi.hip")).read()
-    need = src[src.index("static Context* brf_need("):src.index("int mkhe_bfv_refresh_share(")]
-    assert 'if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");' in need
+    refusal = 'if (c->masked()) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");'
+    # every function defined at the start of a line: name -> its text from the name to the closing brace in column 0
+    bodies = {m.group(1): src[m.start():src.index("\n}\n", m.start())] for m in re.finditer(r"^[A-Za-z].*?\b(\w+)\([^;{}]*\) \{$", src, flags=re.M)}
+    holders = [name for name, body in bodies.items() if "owns a subset of the moduli" in body]
+    assert len(holders) == 1 and refusal in bodies[holders[0]], holders
+
+    def arms(name):
+        """the last value the function itself gives g_last_ctx is a context"""
+        values = re.findall(r"g_last_ctx = (\w+)", bodies[name])
+        return bool(values) and values[-1] != "nullptr"
+
+    def reached(name, seen):
+        """the functions of the file that `name` calls, and those call in turn, each up to the first place where it sets g_last_ctx or calls a
+        function that arms it"""
+        if name in seen:
+            return seen
+        seen.add(name)
+        for m in re.finditer(r"g_last_ctx = |\b(\w+)\(", bodies[name].split("{", 1)[1]):
+            if m.group(1) is None or (m.group(1) in bodies and arms(m.group(1))):
+                break
+            if m.group(1) in bodies:
+                reached(m.group(1), seen)
+        return seen
+
+    for entry in ("mkhe_bfv_refresh_share", "mkhe_bfv_refresh_merge"):
+        assert holders[0] in reached(entry, set()), entry
 
 
 def test_refused_inside_a_capture(w3):
