@@ -13,10 +13,8 @@ namespace mkhe {
 
 constexpr int BRF_MAX_FLOOD = 1024;     // widest flood: 16 streams of 64 bits per coefficient
 
-// Everything secret the finish kernel reads travels here, in the kernel arguments (as RefreshMaskArgs does for the CKKS mask).
-struct BfvRefreshArgs {
-    u32 key[8];
-    u32 nonce_lo, nonce_hi;
+// Everything secret the finish kernel reads travels here, in the kernel arguments (StreamKey, chacha.h).
+struct BfvRefreshArgs : StreamKey {
     int mask;                      // 0: A = 0, the mask streams are not read (tests only)
     int flood_bits;                // 0: e = 0, no flood stream is read
 };

@@ -1,8 +1,7 @@
 // bfv_refresh_kernels.hip -- see bfv_refresh_kernels.h.  No LDS, no scratch.
 #include "bfv_refresh_kernels.h"
 #include "bfv_arith.h"
-#include "flood_arith.h"
-#include "ed_access.h"
+#include "sample_arith.h"
 
 namespace mkhe {
 
@@ -13,11 +12,9 @@ namespace mkhe {
 // MForm(T^-1 mod q_j).  The flood is reduced by Horner over its words, high to low: f <- f 2^64 + v_w mod q_j, the first as a Montgomery product
 // with r2 = 2^128 mod q_j, one block of one stream at a time (8 accumulators and 8 words live, whatever W is); 2^(flood_bits-1) mod q_j, which
 // centres it, is wave-uniform.  The blocks are recomputed for every limb: W <= 16 blocks against the 8 W words a thread would otherwise hold.
-constexpr int BRF_THREADS = 128;
-
-__global__ void __launch_bounds__(BRF_THREADS) bfv_refresh_finish_kernel(BfvRefreshArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
+__global__ void __launch_bounds__(BLK_THREADS) bfv_refresh_finish_kernel(BfvRefreshArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
                                                                          BfvScale sc) {
-    const u32 blk = blockIdx.x * BRF_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+    const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(sc.N / 8)) return;
     const int j = blockIdx.y, b = blockIdx.z;
     const int W = (a.flood_bits + 63) >> 6;                                 // words of the flood, 0 .. 16
@@ -29,8 +26,8 @@ __global__ void __launch_bounds__(BRF_THREADS) bfv_refresh_finish_kernel(BfvRefr
 #pragma unroll
     for (int i = 0; i < 8; ++i) lo[i] = hi[i] = 0;
     if (a.mask) {                                                           // (wave-uniform)
-        chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0, lo);
-        chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 1, hi);
+        chacha_block8(a, blk, s0, lo);
+        chacha_block8(a, blk, s0 + 1, hi);
     }
     const u64 tinv = sc.tinv_mont[j];
     const u32 T = sc.t.T;
@@ -47,21 +44,19 @@ __global__ void __launch_bounds__(BRF_THREADS) bfv_refresh_finish_kernel(BfvRefr
         mag = bf_scale_up_mag(sc.t, An, neg);
         dn[i] = bf_scale_up_limb(mag, neg, tinv, md);
     }
-    // kind 5 mod q_j (flood_arith.h)
+    // kind 5 mod q_j
     u64 f[8];
-    flood_mod_q(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 2, a.flood_bits, md, f);
+    flood_mod_q(a, blk, s0 + 2, a.flood_bits, md, f);
     const long row = (((long)b * sc.limbs + j) * sc.N) / 2 + 4 * (long)blk; // in pairs
-    const u64x2 v0 = ld2(acc, row), v1 = ld2(acc, row + 1), v2 = ld2(acc, row + 2), v3 = ld2(acc, row + 3);
-    const u64 v[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-    u64 o[8];
+    u64 v[8];
+    ld8(acc, row, v);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = csub(csub(v[i] + up[i], q) + f[i], q);
-    st2(share, row, o[0], o[1]); st2(share, row + 1, o[2], o[3]); st2(share, row + 2, o[4], o[5]); st2(share, row + 3, o[6], o[7]);
-    st2(pt, row, dn[0], dn[1]); st2(pt, row + 1, dn[2], dn[3]); st2(pt, row + 2, dn[4], dn[5]); st2(pt, row + 3, dn[6], dn[7]);
+    for (int i = 0; i < 8; ++i) v[i] = csub(csub(v[i] + up[i], q) + f[i], q);
+    st8(share, row, v);
+    st8(pt, row, dn);
 }
 void launch_bfv_refresh_finish(const BfvRefreshArgs& a, int count, u64* share, const u64* acc, u64* pt, const BfvScale& sc, hipStream_t st) {
-    const int bx = (sc.N / 8 + BRF_THREADS - 1) / BRF_THREADS;
-    hipLaunchKernelGGL(bfv_refresh_finish_kernel, dim3(bx, sc.limbs, count), dim3(BRF_THREADS), 0, st, a, share, acc, pt, sc);
+    hipLaunchKernelGGL(bfv_refresh_finish_kernel, dim3(blk_bx(sc.N), sc.limbs, count), dim3(BLK_THREADS), 0, st, a, share, acc, pt, sc);
 }
 
 // ---- bfv_refresh_merge_kernel: grid.x over the coefficients, grid.y = the item.  One thread owns coefficient n of item b through every modulus:
@@ -77,12 +72,8 @@ __global__ void __launch_bounds__(BRM_THREADS) bfv_refresh_merge_kernel(int coun
     u64* o = const_cast<u64*>(ed_entry(out, b));
     const u64* c = ed_entry(c0, b);
     // the residue of R under q_j
-    const u32 w = bf_scale_down_of(sc, [&](int j, const Mod& md) {
-        const u64 q = md.q;
-        u64 v = csub(csub(c[j * N + n], q), q);
-        for (int i = 0; i < nshares; ++i) v = csub(v + ed_entry(sh, i)[((long)b * L + j) * N + n], q);
-        return v;
-    }, dig + (long)b * L * N + n);
+    const u32 w = bf_scale_down_of(sc, [&](int j, const Mod& md) { return sum_shares(c[j * N + n], sh, nshares, ((long)b * L + j) * N + n, md.q); },
+                                   dig + (long)b * L * N + n);
     bool neg;
     const u64 mag = bf_scale_up_mag(sc.t, w, neg);
     for (int j = 0; j < L; ++j) {

@@ -9,10 +9,8 @@ namespace mkhe {
 
 constexpr int SHF_MAX_BITS = 62;   // widest flooding sample: |e| <= 2^61 keeps the reduction's operand below 2^62 (mont_mul_lazy)
 
-// Everything secret the finish kernel reads travels here, in the kernel arguments (as SmallSampleArgs does for the sampler).
-struct ShareFloodArgs {
-    u32 key[8];
-    u32 nonce_lo, nonce_hi;
+// Everything secret the finish kernel reads travels here, in the kernel arguments (StreamKey, chacha.h).
+struct ShareFloodArgs : StreamKey {
     int bits;                      // 0: no flood, the keystream is not read
 };
 

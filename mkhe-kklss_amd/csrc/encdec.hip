@@ -31,9 +31,9 @@ void Context::need_unmasked(const char* what) const {
     if (masked_) throw Error(std::string(what) + ": not available on a context that owns a subset of the moduli");
 }
 
-// Key-bearing arguments of one launch.  stream_fill writes the prefix every such struct starts with (the key words are zero when the launch reads
-// no stream); wipe overwrites the host copy behind the launch (the runtime has copied the arguments).
-template <class T> static void stream_fill(T& a, const u32* key, u64 nonce, bool reads = true) {
+// Key-bearing arguments of one launch.  stream_fill writes the StreamKey every such struct derives from (the key words are zero when the launch
+// reads no stream); wipe overwrites the host copy behind the launch (the runtime has copied the arguments).
+static void stream_fill(StreamKey& a, const u32* key, u64 nonce, bool reads = true) {
     for (int i = 0; i < 8; ++i) a.key[i] = reads ? key[i] : 0;
     a.nonce_lo = (u32)nonce; a.nonce_hi = (u32)(nonce >> 32);
 }

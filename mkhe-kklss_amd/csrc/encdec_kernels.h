@@ -11,7 +11,7 @@
 //            Summing the k products in the NTT domain and doing ONE inverse transform gives the same canonical residues:
 //            InvNTT(sum_i x_i) = sum_i InvNTT(x_i) mod q.
 #pragma once
-#include "modarith.h"
+#include "chacha.h"
 
 namespace mkhe {
 
@@ -45,10 +45,9 @@ void launch_decrypt_finish(int count, u64* out, long out_stride, const u64* c0, 
 // ---- small-norm samples from a ChaCha20 keystream (include/mkhe.h, "device-side sampling": the definition of the stream and of the kinds)
 constexpr int SMP_MAX_CDT = 64;    // thresholds of a table (kind 1)
 constexpr int SMP_KIND_ENCRYPT = 2;    // launch_small_sample only: polynomial p is kind (p % 3 != 0), the layout u, e0, e1 of mkhe_encrypt's samples
-// Everything secret the kernel reads travels here, in the kernel arguments: the key is never stored in device memory the engine owns.
-struct SmallSampleArgs {
-    u32 key[8];
-    u32 nonce_lo, nonce_hi, first_stream;
+// Everything secret the kernel reads travels here, in the kernel arguments (StreamKey, chacha.h).
+struct SmallSampleArgs : StreamKey {
+    u32 first_stream;
     int ncdt;
     u64 cdt[SMP_MAX_CDT];
 };

@@ -1,12 +1,8 @@
 // encdec_kernels.hip -- see encdec_kernels.h.  Streaming kernels: 256 threads, grid.x strides over PAIRS of coefficients (one 16-byte
 // access per lane), grid.y = limb, grid.z = item of the batch; per-modulus constants are wave-uniform (SGPRs).  No LDS.
-#include "ed_access.h"
-#include "chacha.h"
+#include "sample_arith.h"
 
 namespace mkhe {
-
-// ExtendBasisSmallNormAndCenter of one sample: e >= 0 ? e : q - |e|
-__device__ __forceinline__ u64 small_q(i32 e, u64 q) { return e < 0 ? q - (u64)(-(i64)e) : (u64)e; }
 
 __global__ void __launch_bounds__(ED_THREADS) encrypt_mul_kernel(int count, u64* w, const u64* pk, const u64* pt_ntt, const Mod* mods, int limbs,
                                                                  int mtot, int N) {
@@ -97,54 +93,29 @@ void launch_decrypt_finish(int count, u64* out, long out_stride, const u64* c0, 
 // (20 rounds of 16 add / xor / rotate, then ncdt 64-bit compares per coefficient for a table); no LDS, no scratch, two 16-byte stores.
 // grid.x = blocks of a polynomial, grid.y strides over the polynomials: stream, kind and the table are wave-uniform, the table and the
 // key are read from the kernel arguments (scalar loads).
-constexpr int SMP_THREADS = 128;
 constexpr int SMP_MAX_GRID_Y = 65535;
 
-__global__ void __launch_bounds__(SMP_THREADS) small_sample_kernel(SmallSampleArgs a, int kind, int polys, i32* out, i32* u_rows, int N) {
-    const u32 blk = blockIdx.x * SMP_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+__global__ void __launch_bounds__(BLK_THREADS) small_sample_kernel(SmallSampleArgs a, int kind, int polys, i32* out, i32* u_rows, int N) {
+    const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(N / 8)) return;
     for (int p = blockIdx.y; p < polys; p += gridDim.y) {
         const int k = kind == SMP_KIND_ENCRYPT ? (p % 3 != 0) : kind;
-        const u32 in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, a.key[0], a.key[1], a.key[2], a.key[3],
-                            a.key[4],    a.key[5],    a.key[6],    a.key[7],    blk,      a.nonce_lo, a.nonce_hi, a.first_stream + (u32)p};
-        u32 x[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) x[i] = in[i];
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            chacha_qr(x[0], x[4], x[8], x[12]); chacha_qr(x[1], x[5], x[9], x[13]); chacha_qr(x[2], x[6], x[10], x[14]); chacha_qr(x[3], x[7], x[11], x[15]);
-            chacha_qr(x[0], x[5], x[10], x[15]); chacha_qr(x[1], x[6], x[11], x[12]); chacha_qr(x[2], x[7], x[8], x[13]); chacha_qr(x[3], x[4], x[9], x[14]);
-        }
         u64 r64[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r64[i] = (u64)(x[2 * i] + in[2 * i]) | ((u64)(x[2 * i + 1] + in[2 * i + 1]) << 32);
+        chacha_block8(a, blk, a.first_stream + (u32)p, r64);
         i32 v[8];
         if (k == 0) {                                                       // ternary, P(0) = 1/2
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = (r64[i] & 1) ? 0 : ((r64[i] & 2) ? 1 : -1);
-        } else {                                                            // #{t : r >= cdt[t]} - ncdt/2: every threshold, whatever r is
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = -(a.ncdt >> 1);
-            for (int t = 0; t < a.ncdt; ++t) {
-                const u64 T = a.cdt[t];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] += (r64[i] >= T) ? 1 : 0;
-            }
+        } else {
+            cdt_sample8(a, r64, v);
         }
-        int4* dst = reinterpret_cast<int4*>(out + (long)p * N) + 2 * (long)blk;
-        dst[0] = int4{v[0], v[1], v[2], v[3]};
-        dst[1] = int4{v[4], v[5], v[6], v[7]};
-        if (u_rows && kind == SMP_KIND_ENCRYPT && k == 0) {
-            int4* du = reinterpret_cast<int4*>(u_rows + (long)(p / 3) * N) + 2 * (long)blk;
-            du[0] = int4{v[0], v[1], v[2], v[3]};
-            du[1] = int4{v[4], v[5], v[6], v[7]};
-        }
+        st8(out + (long)p * N, 2 * (long)blk, v);
+        if (u_rows && kind == SMP_KIND_ENCRYPT && k == 0) st8(u_rows + (long)(p / 3) * N, 2 * (long)blk, v);
     }
 }
 void launch_small_sample(const SmallSampleArgs& a, int kind, int polys, i32* out, i32* u_rows, int N, hipStream_t st) {
-    const int bx = (N / 8 + SMP_THREADS - 1) / SMP_THREADS;
-    hipLaunchKernelGGL(small_sample_kernel, dim3(bx, polys < SMP_MAX_GRID_Y ? polys : SMP_MAX_GRID_Y), dim3(SMP_THREADS), 0, st, a, kind, polys, out,
-                       u_rows, N);
+    hipLaunchKernelGGL(small_sample_kernel, dim3(blk_bx(N), polys < SMP_MAX_GRID_Y ? polys : SMP_MAX_GRID_Y), dim3(BLK_THREADS), 0, st, a, kind, polys,
+                       out, u_rows, N);
 }
 
 }  // namespace mkhe

@@ -1,7 +1,6 @@
 // pcks_kernels.hip -- see pcks_kernels.h.  No LDS, no scratch.
 #include "pcks_kernels.h"
-#include "flood_arith.h"
-#include "ed_access.h"
+#include "sample_arith.h"
 
 namespace mkhe {
 
@@ -33,13 +32,11 @@ void launch_pcks_mac(int count, u64* w, const u64* sk, const u64* pk, const Mod*
 
 // ---- pcks_finish_kernel: grid.x = ChaCha20 blocks of a polynomial (8 coefficients, 64 bytes of a limb per thread), grid.y = the 2 limbs rows,
 // grid.z = the item, so that the half, every stream and every per-modulus constant are wave-uniform and key, nonce and table are read from the
-// kernel arguments (scalar loads).  h0 rows: the flood by flood_mod_q.  h1 rows: #{t : r >= cdt[t]} - ncdt/2 with every threshold visited and a
-// full 64-bit unsigned compare, then e >= 0 ? e : q - |e| by a select -- no sample-dependent branch.
-constexpr int PKF_THREADS = 128;
-
-__global__ void __launch_bounds__(PKF_THREADS) pcks_finish_kernel(SmallSampleArgs a, int flood_bits, int count, u64* __restrict__ shares, const u64* __restrict__ w,
+// kernel arguments (scalar loads).  h0 rows: the flood by flood_mod_q.  h1 rows: the table scan (cdt_sample8), then e >= 0 ? e : q - |e| by a
+// select (small_q) -- no sample-dependent branch.
+__global__ void __launch_bounds__(BLK_THREADS) pcks_finish_kernel(SmallSampleArgs a, int flood_bits, int count, u64* __restrict__ shares, const u64* __restrict__ w,
                                                                   const Mod* __restrict__ mods, int limbs, int N) {
-    const u32 blk = blockIdx.x * PKF_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+    const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(N / 8)) return;
     const int r = blockIdx.y, b = blockIdx.z;
     const int h = r >= limbs ? 1 : 0, j = r - h * limbs;                    // (wave-uniform)
@@ -48,33 +45,25 @@ __global__ void __launch_bounds__(PKF_THREADS) pcks_finish_kernel(SmallSampleArg
     u64 f[8];                                                               // what the row adds, mod q_j
     if (h == 0) {
         const int W = (flood_bits + 63) >> 6;
-        flood_mod_q(a.key, a.nonce_lo, a.nonce_hi, blk, 2u * (u32)count + (u32)b * (u32)W, flood_bits, md, f);
+        flood_mod_q(a, blk, 2u * (u32)count + (u32)b * (u32)W, flood_bits, md, f);
     } else {
         u64 r64[8];
-        chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, (u32)count + (u32)b, r64);
+        chacha_block8(a, blk, (u32)count + (u32)b, r64);
         i32 e[8];
+        cdt_sample8(a, r64, e);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = -(a.ncdt >> 1);
-        for (int t = 0; t < a.ncdt; ++t) {
-            const u64 T = a.cdt[t];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) e[i] += (r64[i] >= T) ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) f[i] = e[i] < 0 ? q - (u64)(-(i64)e[i]) : (u64)e[i];
+        for (int i = 0; i < 8; ++i) f[i] = small_q(e[i], q);
     }
     const long src = ((((long)h * count + b) * limbs + j) * N) / 2 + 4 * (long)blk;        // in pairs: w [2][count][limbs][N]
     const long dst = ((((long)b * 2 + h) * limbs + j) * N) / 2 + 4 * (long)blk;            // shares [count][2][limbs][N]
-    const u64x2 v0 = ld2(w, src), v1 = ld2(w, src + 1), v2 = ld2(w, src + 2), v3 = ld2(w, src + 3);
-    const u64 v[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-    u64 o[8];
+    u64 v[8];
+    ld8(w, src, v);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = csub(v[i] + f[i], q);
-    st2(shares, dst, o[0], o[1]); st2(shares, dst + 1, o[2], o[3]); st2(shares, dst + 2, o[4], o[5]); st2(shares, dst + 3, o[6], o[7]);
+    for (int i = 0; i < 8; ++i) v[i] = csub(v[i] + f[i], q);
+    st8(shares, dst, v);
 }
 void launch_pcks_finish(const SmallSampleArgs& a, int flood_bits, int count, u64* shares, const u64* w, const Mod* mods, int limbs, int N, hipStream_t st) {
-    const int bx = (N / 8 + PKF_THREADS - 1) / PKF_THREADS;
-    hipLaunchKernelGGL(pcks_finish_kernel, dim3(bx, 2 * limbs, count), dim3(PKF_THREADS), 0, st, a, flood_bits, count, shares, w, mods, limbs, N);
+    hipLaunchKernelGGL(pcks_finish_kernel, dim3(blk_bx(N), 2 * limbs, count), dim3(BLK_THREADS), 0, st, a, flood_bits, count, shares, w, mods, limbs, N);
 }
 
 // ---- pcks_merge_kernel: the shape of share_merge_kernel with 2 limbs rows; c_0 enters the rows of polynomial 0 only
@@ -87,18 +76,8 @@ __global__ void __launch_bounds__(ED_THREADS) pcks_merge_kernel(int nshares, EdT
     const u64* c = ed_entry(c0, b) + (long)j * N;
     u64* o = const_cast<u64*>(ed_entry(out, b)) + (long)r * N;
     for (long n = (long)blockIdx.x * ED_THREADS + threadIdx.x; n < half; n += (long)gridDim.x * ED_THREADS) {
-        u64 vx = 0, vy = 0;
-        if (h == 0) {
-            const u64x2 x = ld2(c, n);
-            vx = csub(csub(x.x, q), q);
-            vy = csub(csub(x.y, q), q);
-        }
-        for (int i = 0; i < nshares; ++i) {
-            const u64x2 s = ld2(ed_entry(sh, i), row + n);
-            vx = csub(vx + s.x, q);
-            vy = csub(vy + s.y, q);
-        }
-        st2(o, n, vx, vy);
+        const u64x2 v = sum_shares(h == 0 ? ld2(c, n) : u64x2{0, 0}, sh, nshares, row + n, q);
+        st2(o, n, v.x, v.y);
     }
 }
 void launch_pcks_merge(int count, int nshares, const EdTable& out, const EdTable& c0, const EdTable& sh, const Mod* mods, int limbs, int N, hipStream_t st) {

@@ -10,10 +10,8 @@ namespace mkhe {
 
 constexpr int RF_MAX_BITS = 120;   // widest mask: |M| <= 2^119 = two words below 2^60, each a legal operand of mont_mul
 
-// Everything secret the finish kernel reads travels here, in the kernel arguments (as ShareFloodArgs does for the flood).
-struct RefreshMaskArgs {
-    u32 key[8];
-    u32 nonce_lo, nonce_hi;
+// Everything secret the finish kernel reads travels here, in the kernel arguments (StreamKey, chacha.h).
+struct RefreshMaskArgs : StreamKey {
     int bits;                      // 0: no mask, the keystream is not read
 };
 

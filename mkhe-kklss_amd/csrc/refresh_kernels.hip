@@ -1,14 +1,8 @@
 // refresh_kernels.hip -- see refresh_kernels.h.  No LDS, no scratch.
 #include "refresh_kernels.h"
-#include "chacha.h"
-#include "ed_access.h"
+#include "sample_arith.h"
 
 namespace mkhe {
-
-// block blk of one stream of the mask's (key, nonce): chacha.h
-__device__ __forceinline__ void chacha_block8(const RefreshMaskArgs& a, u32 blk, u32 stream, u64 (&r)[8]) {
-    chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, stream, r);
-}
 
 // ---- refresh_finish_kernel: grid.x = ChaCha20 blocks of a polynomial (8 coefficients, 64 bytes of a limb per thread), grid.y = the item, so that
 // both streams are wave-uniform and key and nonce are read from the kernel arguments (scalar loads).  The mask never exists in memory: per
@@ -17,11 +11,9 @@ __device__ __forceinline__ void chacha_block8(const RefreshMaskArgs& a, u32 blk,
 // word (the same reduction with the constant 2^60 folded in; the constant is wave-uniform, from r2), the sign folded in afterwards by a select --
 // no sample-dependent branch or address.  One thread walks every modulus: M is formed once, and the share (j < lin) and the plaintext -M
 // (j < lout) come out of the same registers and the same reduction.
-constexpr int RFF_THREADS = 128;
-
-__global__ void __launch_bounds__(RFF_THREADS) refresh_finish_kernel(RefreshMaskArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
+__global__ void __launch_bounds__(BLK_THREADS) refresh_finish_kernel(RefreshMaskArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
                                                                      const Mod* __restrict__ mods, int lin, int lout, int N) {
-    const u32 blk = blockIdx.x * RFF_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+    const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(N / 8)) return;
     const int b = blockIdx.y;
     u64 w0[8], w1[8];
@@ -56,29 +48,24 @@ __global__ void __launch_bounds__(RFF_THREADS) refresh_finish_kernel(RefreshMask
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const u64 m = csub(mont_mul(w0[i], md.r1, q, md.ninv32) + mont_mul(w1[i], c60, q, md.ninv32), q);      // |M| mod q
-            const u64 o = csub(q - m, q);                                   // -|M| mod q
             const bool n = (neg >> i) & 1;
-            pos[i] = n ? o : m;
-            ngt[i] = n ? m : o;
+            pos[i] = signed_mod_q(m, n, q);
+            ngt[i] = signed_mod_q(m, !n, q);
         }
         if (j < lin) {
             const long row = (((long)b * lin + j) * N) / 2 + 4 * (long)blk;      // in pairs
-            const u64x2 v0 = ld2(acc, row), v1 = ld2(acc, row + 1), v2 = ld2(acc, row + 2), v3 = ld2(acc, row + 3);
-            st2(share, row, csub(v0.x + pos[0], q), csub(v0.y + pos[1], q));
-            st2(share, row + 1, csub(v1.x + pos[2], q), csub(v1.y + pos[3], q));
-            st2(share, row + 2, csub(v2.x + pos[4], q), csub(v2.y + pos[5], q));
-            st2(share, row + 3, csub(v3.x + pos[6], q), csub(v3.y + pos[7], q));
+            u64 v[8];
+            ld8(acc, row, v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = csub(v[i] + pos[i], q);
+            st8(share, row, v);
         }
-        if (j < lout) {
-            const long row = (((long)b * lout + j) * N) / 2 + 4 * (long)blk;
-            st2(pt, row, ngt[0], ngt[1]); st2(pt, row + 1, ngt[2], ngt[3]); st2(pt, row + 2, ngt[4], ngt[5]); st2(pt, row + 3, ngt[6], ngt[7]);
-        }
+        if (j < lout) st8(pt, (((long)b * lout + j) * N) / 2 + 4 * (long)blk, ngt);
     }
 }
 void launch_refresh_finish(const RefreshMaskArgs& a, int count, u64* share, const u64* acc, u64* pt, const Mod* mods, int lin, int lout, int N,
                            hipStream_t st) {
-    const int bx = (N / 8 + RFF_THREADS - 1) / RFF_THREADS;
-    hipLaunchKernelGGL(refresh_finish_kernel, dim3(bx, count), dim3(RFF_THREADS), 0, st, a, share, acc, pt, mods, lin, lout, N);
+    hipLaunchKernelGGL(refresh_finish_kernel, dim3(blk_bx(N), count), dim3(BLK_THREADS), 0, st, a, share, acc, pt, mods, lin, lout, N);
 }
 
 // ---- refresh_merge_kernel: grid.x over the coefficients, grid.y = the item.  One thread owns coefficient n of item b through every modulus: the
@@ -97,8 +84,7 @@ __global__ void __launch_bounds__(RFM_THREADS) refresh_merge_kernel(RefreshMerge
     // the residue of R under q_j, j < lin; behind it polynomial 0 of the output under that modulus
     auto residue = [&](int j, const Mod& md) {
         const u64 q = md.q;
-        u64 v = csub(csub(c[j * N + n], q), q);
-        for (int i = 0; i < a.nshares; ++i) v = csub(v + ed_entry(sh, i)[((long)b * lin + j) * N + n], q);
+        const u64 v = sum_shares(c[j * N + n], sh, a.nshares, ((long)b * lin + j) * N + n, q);
         if (j < lout) {
             u64 w = v;
             for (int i = 0; i < a.nshares; ++i) w = csub(w + ed_entry(re, i * a.count + b)[j * N + n], q);

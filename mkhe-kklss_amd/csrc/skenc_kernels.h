@@ -9,10 +9,7 @@
 namespace mkhe {
 
 // the PUBLIC seed of kind 6: nothing here is secret, but it travels like the secret keys do (kernel arguments, scalar loads)
-struct UniformArgs {
-    u32 key[8];
-    u32 nonce_lo, nonce_hi;
-};
+struct UniformArgs : StreamKey {};
 
 // Row (b, j), b < count, j < limbs: out[b][poly_off + j N + n] = ((hi 2^64 + lo) q_j) >> 128, lo / hi = the 64-bit values of coefficient n of the
 // streams 2 (b nq + j) and 2 (b nq + j) + 1 of (a.key, a.nonce): nq, the context's number of Q primes, NOT limbs, so that a row does not depend on

@@ -1,26 +1,23 @@
 // skenc_kernels.hip -- see skenc_kernels.h.  No LDS, no scratch.
 #include "skenc_kernels.h"
-#include "chacha.h"
-#include "ed_access.h"
+#include "sample_arith.h"
 
 namespace mkhe {
 
 // ---- uniform_sample_kernel: grid.x = ChaCha20 blocks of a row (8 coefficients, 64 bytes per thread), grid.y = the limb, grid.z = the item, so
 // that both streams and q_j are wave-uniform and key and nonce are read from the kernel arguments (scalar loads).  Per coefficient
 // ((hi 2^64 + lo) q) >> 128 = (hi q + ((lo q) >> 64)) >> 64: one full 64 x 64 product, the high word of a second and a carry.
-constexpr int USM_THREADS = 128;
-
-__global__ void __launch_bounds__(USM_THREADS) uniform_sample_kernel(UniformArgs a, EdTable out, long poly_off, const Mod* __restrict__ mods, int nq, int N) {
-    const u32 blk = blockIdx.x * USM_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+__global__ void __launch_bounds__(BLK_THREADS) uniform_sample_kernel(UniformArgs a, EdTable out, long poly_off, const Mod* __restrict__ mods, int nq, int N) {
+    const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(N / 8)) return;
     const int j = blockIdx.y, b = blockIdx.z;
     const u64 q = mods[j].q;
     const u32 s0 = 2u * ((u32)b * (u32)nq + (u32)j);
     u64 lo[8], hi[8], v[8];
-    chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0, lo);
+    chacha_block8(a, blk, s0, lo);
 #pragma unroll
     for (int i = 0; i < 8; ++i) lo[i] = mulhi64(lo[i], q);                  // only (lo q) >> 64 is needed
-    chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, s0 + 1, hi);
+    chacha_block8(a, blk, s0 + 1, hi);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         u64 ph, pl;
@@ -28,13 +25,10 @@ __global__ void __launch_bounds__(USM_THREADS) uniform_sample_kernel(UniformArgs
         const u64 s = pl + lo[i];
         v[i] = ph + (s < pl ? 1 : 0);                                       // below q: (r q) >> 128 with r < 2^128
     }
-    u64* o = const_cast<u64*>(ed_entry(out, b)) + poly_off + (long)j * N;
-    const long p = 4 * (long)blk;                                           // in pairs
-    st2(o, p, v[0], v[1]); st2(o, p + 1, v[2], v[3]); st2(o, p + 2, v[4], v[5]); st2(o, p + 3, v[6], v[7]);
+    st8(const_cast<u64*>(ed_entry(out, b)) + poly_off + (long)j * N, 4 * (long)blk, v);
 }
 void launch_uniform_sample(const UniformArgs& a, int count, const EdTable& out, long poly_off, const Mod* mods, int limbs, int nq, int N, hipStream_t st) {
-    const int bx = (N / 8 + USM_THREADS - 1) / USM_THREADS;
-    hipLaunchKernelGGL(uniform_sample_kernel, dim3(bx, limbs, count), dim3(USM_THREADS), 0, st, a, out, poly_off, mods, nq, N);
+    hipLaunchKernelGGL(uniform_sample_kernel, dim3(blk_bx(N), limbs, count), dim3(BLK_THREADS), 0, st, a, out, poly_off, mods, nq, N);
 }
 
 // ---- skenc_mul_kernel: the shape of encrypt_mul_kernel (256 threads, grid.x strides over pairs, grid.y = limb, grid.z = item)
@@ -61,55 +55,40 @@ void launch_skenc_mul(int count, u64* w, const u64* sk, const u64* pt_ntt, const
 }
 
 // ---- skenc_finish_kernel: the shape of pcks_finish_kernel with one polynomial.  e from the int32 samples (two 16-byte loads) or kind 1 in
-// registers: #{t : r >= cdt[t]} - ncdt/2 with every threshold visited and a full 64-bit unsigned compare, then e >= 0 ? e : q - |e| by a select --
-// no sample-dependent branch.
-constexpr int SKF_THREADS = 128;
-
-__global__ void __launch_bounds__(SKF_THREADS) skenc_finish_kernel(SmallSampleArgs a, const i32* __restrict__ smp, EdTable out, const u64* __restrict__ w,
+// registers: the table scan (cdt_sample8), then e >= 0 ? e : q - |e| by a select (small_q) -- no sample-dependent branch.
+__global__ void __launch_bounds__(BLK_THREADS) skenc_finish_kernel(SmallSampleArgs a, const i32* __restrict__ smp, EdTable out, const u64* __restrict__ w,
                                                                    const u64* __restrict__ pt_coeff, const Mod* __restrict__ mods, int limbs, int N) {
-    const u32 blk = blockIdx.x * SKF_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
+    const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(N / 8)) return;
     const int j = blockIdx.y, b = blockIdx.z;
     const u64 q = mods[j].q;
     i32 e[8];
     if (smp) {                                                              // (wave-uniform)
-        const int4* src = reinterpret_cast<const int4*>(smp + (long)b * N) + 2 * (long)blk;
-        const int4 s0 = src[0], s1 = src[1];
-        e[0] = s0.x; e[1] = s0.y; e[2] = s0.z; e[3] = s0.w; e[4] = s1.x; e[5] = s1.y; e[6] = s1.z; e[7] = s1.w;
+        ld8(smp + (long)b * N, 2 * (long)blk, e);
     } else {
         u64 r64[8];
-        chacha_block8(a.key, a.nonce_lo, a.nonce_hi, blk, (u32)b, r64);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = -(a.ncdt >> 1);
-        for (int t = 0; t < a.ncdt; ++t) {
-            const u64 T = a.cdt[t];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) e[i] += (r64[i] >= T) ? 1 : 0;
-        }
+        chacha_block8(a, blk, (u32)b, r64);
+        cdt_sample8(a, r64, e);
     }
     const long row = (((long)b * limbs + j) * N) / 2 + 4 * (long)blk;       // in pairs: w and pt_coeff [count][limbs][N]
-    const u64x2 t0 = ld2(w, row), t1 = ld2(w, row + 1), t2 = ld2(w, row + 2), t3 = ld2(w, row + 3);
-    const u64 t[8] = {t0.x, t0.y, t1.x, t1.y, t2.x, t2.y, t3.x, t3.y};
-    u64 o[8];
+    u64 t[8], o[8];
+    ld8(w, row, t);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = e[i] < 0 ? q - (u64)(-(i64)e[i]) : (u64)e[i];
+    for (int i = 0; i < 8; ++i) o[i] = small_q(e[i], q);
     if (pt_coeff) {                                                         // (wave-uniform)
-        const u64x2 p0 = ld2(pt_coeff, row), p1 = ld2(pt_coeff, row + 1), p2 = ld2(pt_coeff, row + 2), p3 = ld2(pt_coeff, row + 3);
-        const u64 p[8] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
+        u64 p[8];
+        ld8(pt_coeff, row, p);
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = csub(csub(p[i] + o[i], q) + q - t[i], q);
     } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = csub(t[i] + o[i], q);
     }
-    u64* c0 = const_cast<u64*>(ed_entry(out, b)) + (long)j * N;
-    const long d = 4 * (long)blk;
-    st2(c0, d, o[0], o[1]); st2(c0, d + 1, o[2], o[3]); st2(c0, d + 2, o[4], o[5]); st2(c0, d + 3, o[6], o[7]);
+    st8(const_cast<u64*>(ed_entry(out, b)) + (long)j * N, 4 * (long)blk, o);
 }
 void launch_skenc_finish(const SmallSampleArgs& a, const i32* smp, int count, const EdTable& out, const u64* w, const u64* pt_coeff, const Mod* mods,
                          int limbs, int N, hipStream_t st) {
-    const int bx = (N / 8 + SKF_THREADS - 1) / SKF_THREADS;
-    hipLaunchKernelGGL(skenc_finish_kernel, dim3(bx, limbs, count), dim3(SKF_THREADS), 0, st, a, smp, out, w, pt_coeff, mods, limbs, N);
+    hipLaunchKernelGGL(skenc_finish_kernel, dim3(blk_bx(N), limbs, count), dim3(BLK_THREADS), 0, st, a, smp, out, w, pt_coeff, mods, limbs, N);
 }
 
 }  // namespace mkhe

@@ -2,37 +2,15 @@
 registers and share_merge_kernel streams, so neither may spill, use scratch or touch LDS; the finish kernel fits eight waves per SIMD.  The
 register counts are printed (DESIGN.md 4.5i quotes them)."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from isa_static import HIPCC, compile_asm, ops, resources
 
 
 @pytest.fixture(scope="module")
 def asm():
-    src = os.path.join(ROOT, "mkhe-kklss_amd", "csrc", "decshare_kernels.hip")
-    r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S", "--cuda-device-only",
-                        src, "-o", "-"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-1500:]
-    return r.stdout
-
-
-def resources(asm, kernel):
-    meta = [b for b in asm.split("- .agpr_count:")[1:] if kernel in b]
-    assert len(meta) == 1, kernel
-    keys = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
-    return {k: int(re.search(r"\.%s:\s+(\d+)" % k, meta[0]).group(1)) for k in keys}
-
-
-def ops(asm, kernel):
-    name = re.findall(r"^(\S*%s\S*):" % kernel, asm, re.M)
-    assert len(name) == 1, name
-    body = asm.split(name[0] + ":", 1)[1].split("s_endpgm", 1)[0]
-    code = [l.strip() for l in body.splitlines() if l.strip() and not l.strip().startswith((";", ".", "//")) and not l.strip().endswith(":")]
-    return [l.split()[0] for l in code]
+    return compile_asm("decshare_kernels.hip")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")

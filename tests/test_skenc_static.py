@@ -3,29 +3,15 @@ the keystream in registers, skenc_mul_kernel streams, skenc_finish_kernel forms 
 fits eight waves per SIMD (at most 64 VGPRs: the occupancy step the printed counts fall under).  The register counts are printed (DESIGN.md 4.5n
 quotes them)."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from isa_static import HIPCC, compile_asm, resources
 
 
 @pytest.fixture(scope="module")
 def asm():
-    src = os.path.join(ROOT, "mkhe-kklss_amd", "csrc", "skenc_kernels.hip")
-    r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S", "--cuda-device-only",
-                        src, "-o", "-"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-1500:]
-    return r.stdout
-
-
-def resources(asm, kernel):
-    meta = [b for b in asm.split("- .agpr_count:")[1:] if kernel in b]
-    assert len(meta) == 1, kernel
-    keys = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
-    return {k: int(re.search(r"\.%s:\s+(\d+)" % k, meta[0]).group(1)) for k in keys}
+    return compile_asm("skenc_kernels.hip")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
