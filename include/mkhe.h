@@ -567,7 +567,7 @@ int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, v
  * bits = 0 means e = 0: no stream is read and the key may be NULL (tests only: such a share is PartialDecrypt's product and reveals the key).
  * The smudging lemma is stated for this uniform distribution; a wide Gaussian has no bit-exact definition from 64 bits per coefficient.
  * The sample is formed in registers by the kernel that adds it (one thread = one ChaCha20 block = 8 coefficients, reduced per limb without a
- * sample-dependent branch): it never exists in memory.  The engine does not choose `bits`: that depends on the noise of the ciphertext.
+ * sample-dependent branch): it never exists in memory.  The engine does not choose `bits`: that depends on the noise of the ciphertext (mkhe_noise_norm measures it).
  *
  * Noise budget.  The merge adds sum_i e_i with |sum_i e_i| <= k 2^(bits-1) per coefficient (k parties).  CKKS: every slot moves by at most
  * N k 2^(bits-1) / scale (triangle inequality over the N unit-modulus roots of the embedding).  BFV: the message stays exact as long as
@@ -748,6 +748,43 @@ int  mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const i
  * cannot check which -- with the limbs of the input.  Every limb of both polynomials of out is written.  One streaming launch; count > 16 or
  * nshares > 16 stages pointer tables, which synchronises.  nshares = 0 on ciphertexts without parties gives (c_0 reduced, 0). */
 int  mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, mkhe_ct* const* out);
+/* ---- noise measurement: the exact centred max norm of a phase (no reference counterpart) --------------------------------------------
+ * Every share call above takes a width that the caller must put above the noise of the ciphertext.  This call measures that noise on the device,
+ * from a phase: what mkhe_decrypt writes for whoever holds every key, or what mkhe_decrypt_merge writes for parties that hold only their own
+ * (with unflooded shares, or up to the flood otherwise).  Nothing is estimated: without the keys or their shares there is nothing to measure.
+ *
+ * Definitions (integers only).  For item b and limbs q_0 .. q_(L-1), L = limbs, Q = q_0 * .. * q_(L-1), and for coefficient n:
+ *   kind 0, residual       x = (phase[b][.][n] - ref[b][.][n]) mod Q, given by its residues; with dev_ref == NULL, x = phase.
+ *   kind 1, BFV invariant  x = (T * phase[b][.][n]) mod Q: every limb times T mod q_l (a q_l may be smaller than T).
+ *   r[n] = min(x, Q - x), the magnitude of the centred representative; the result for item b is max_n r[n] and the SMALLEST n that attains it.
+ * The result is in mixed-radix form: out[b] = d_0 .. d_(L-1), then n, with r = d_0 + d_1 q_0 + d_2 q_0 q_1 + .. and d_i < q_i -- the host multiplies
+ * it out; no big integer exists on the device.  There x > (Q-1)/2 is a comparison of digits, top digit first; the digits of Q - x are
+ * q_i - 1 - d_i plus one with carry from digit 0; the maximum over n is the lexicographic one.
+ *
+ * The invariant value and the noise.  A BFV phase is up(m) + e with up(m) = floor((Q m + floor(T/2)) / T), so T phase = Q m + T e + rem with |rem| < T (the
+ * rounding of up), and r = |T e + rem| as long as the noise has not wrapped (T |e| + T < Q / 2).  Then
+ *     |e| <= floor((r + floor(T/2)) / T) + 1 <= |e| + 2,
+ * which needs no message.  The noise budget of a BFV ciphertext is bitlen(Q) - bitlen(r) - 1 >= 0 (r <= (Q-1)/2): it falls to 0 as T |e| comes
+ * near Q / 2, where decryption starts to fail.  With the message at hand, kind 0 against mkhe_bfv_encode(m) gives |e| itself; for CKKS the
+ * reference is mkhe_ckks_encode of the expected slots at the level and scale of the ciphertext.
+ *
+ * Buffers: dev_phase uint64[count][limbs][N], canonical, coefficient domain; dev_ref the same shape, ref_stride_words = limbs * N words between
+ * the references of consecutive items or 0 for one reference for all (the rule of mkhe_bfv_ct_add_ptxt); dev_out uint64[count][limbs + 1].
+ * 1 <= limbs <= nQ, 1 <= count <= 65535 (the items are the second grid dimension).  Kind 1: a BFV context whose T meets the encoder's
+ * preconditions (T prime, T = 1 mod 2N, T < 2^32, T not a prime of Q), limbs == nQ, dev_ref == NULL.
+ * Bytes: the call reads 8 * count * limbs * N bytes of dev_phase once and, with a reference, as many of dev_ref (8 * limbs * N with stride 0), and
+ * writes 8 * count * (limbs + 1).  Two launches: one thread per coefficient forms the digits in a scratch of the context's pool (each digit is read
+ * again by every later limb), centres them, and every workgroup of 256 selects its candidate; one workgroup per item selects among the N / 256
+ * candidates.  No atomics and no dependence on the order in which workgroups run: the result is a pure function of the inputs.  The digit scratch
+ * and the candidates are the noise itself, which depends on the keys: both are wiped behind the second launch.  dev_out is the caller's to guard.
+ *
+ * Refused, with a message that starts with `mkhe_noise_norm: `, nothing enqueued and the context left usable: kind other than 0 or 1; count outside
+ * 1 .. 65535; limbs outside 1 .. nQ; kind 1 with a reference, off a BFV context or with limbs != nQ; a NULL context (after the checks above that
+ * need none); a NULL dev_phase or dev_out; a misaligned buffer; ref_stride_words other than 0 or limbs * N; a context with mkhe_ctx_set_owned.
+ * NOT legal between mkhe_capture_begin and mkhe_capture_end (refused there): the call grows a scratch and builds tables at its first use, and its
+ * result is for the host to read. */
+int  mkhe_noise_norm(mkhe_ctx* ctx, int kind, int limbs, int count, const void* dev_phase, const void* dev_ref, long ref_stride_words,
+                     void* dev_out /* uint64[count][limbs + 1] */);
 
 /* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
  * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call

@@ -557,11 +557,67 @@ struct DecryptionShare {
     DeviceWords Value;
 };
 
+// A noise norm as mkhe_noise_norm measures it (include/mkhe.h, "noise measurement"): the integer itself as its digit vector -- Words, little endian,
+// base 2^64, no leading zero word (empty = 0) -- with a long double beside it (Value(): the words summed from the top in long double arithmetic, so
+// exact up to its 64-bit mantissa) and its exact bit length (Bits(), Python's int.bit_length()); Index = the smallest coefficient that attains it
+// (-1 for a value derived from one).
+struct NoiseValue {
+    std::vector<uint64_t> Words;
+    long Index = -1;
+    int Bits() const { return Words.empty() ? 0 : (int)(64 * (Words.size() - 1)) + 64 - __builtin_clzll(Words.back()); }
+    long double Value() const {
+        long double v = 0;
+        for (size_t i = Words.size(); i-- > 0;) v = v * 18446744073709551616.0L + (long double)Words[i];
+        return v;
+    }
+    // this * m + a, and floor(this / d) (m, a, d < 2^64, d > 0)
+    NoiseValue& MulAdd(uint64_t m, uint64_t a) {
+        unsigned __int128 carry = a;
+        for (auto& w : Words) { carry += (unsigned __int128)w * m; w = (uint64_t)carry; carry >>= 64; }
+        if (carry) Words.push_back((uint64_t)carry);
+        return *this;
+    }
+    NoiseValue& Div(uint64_t d) {
+        unsigned __int128 rem = 0;
+        for (size_t i = Words.size(); i-- > 0;) { rem = (rem << 64) | Words[i]; Words[i] = (uint64_t)(rem / d); rem %= d; }
+        while (!Words.empty() && !Words.back()) Words.pop_back();
+        return *this;
+    }
+    // r = d_0 + d_1 q_0 + d_2 q_0 q_1 + .. by Horner from the top digit
+    static NoiseValue FromMixedRadix(const uint64_t* digits, const uint64_t* q, int limbs, long index) {
+        NoiseValue v;
+        v.Index = index;
+        for (int i = limbs - 1; i >= 0; --i) v.MulAdd(i + 1 < limbs ? q[i] : 1, digits[i]);
+        while (!v.Words.empty() && !v.Words.back()) v.Words.pop_back();
+        return v;
+    }
+};
+
 // mkrlwe.Decryptor (decryptor.go:8-23) on the device.  Between parties, decryption is ShareNew (each party, on its own key) and MergeShares (anyone):
 // Decrypt needs every key in one place, and the output of PartialDecrypt gives the key away.
 class Decryptor {
   public:
     explicit Decryptor(Parameters& p) : params(p) {}
+    // The exact centred max norm of `count` phases uint64[count][limbs][N] (what Decrypt or MergeSharesBatch wrote) as ONE engine call
+    // (mkhe_noise_norm).  kind 0: of phase - ref (dev_ref the same shape, refStrideWords = limbs * N, or one reference for all with 0; null: of the
+    // phase); kind 1 (BFV contexts, limbs = nQ, no reference): of T * phase, the invariant noise.  Only the digits and the index come down.
+    std::vector<NoiseValue> NoiseNormBatch(int limbs, int count, const void* dev_phase, const void* dev_ref = nullptr, long refStrideWords = 0, int kind = 0) {
+        const size_t row = (size_t)limbs + 1;
+        DeviceWords out(params, (size_t)(count > 0 ? count : 1) * row);
+        check(mkhe_noise_norm(params.ctx, kind, limbs, count, dev_phase, dev_ref, refStrideWords, out.d));
+        std::vector<uint64_t> host(out.words);
+        out.download(host.data());
+        std::vector<NoiseValue> res;
+        for (int b = 0; b < count; ++b) res.push_back(NoiseValue::FromMixedRadix(&host[b * row], params.Q().data(), limbs, (long)host[b * row + limbs]));
+        return res;
+    }
+    // Decrypt, then the norm of the residual against dev_ref uint64[level+1][N] (the plaintext ct is expected to hold; null: of the phase itself).
+    // Its Bits() is what the floodBits of ShareNew must exceed.
+    NoiseValue NoiseNorm(const Ciphertext& ct, const SecretKeySet& skSet, const void* dev_ref = nullptr, int kind = 0) {
+        DeviceWords pt(params, (size_t)(ct.Level() + 1) * params.N());
+        Decrypt(ct, skSet, pt.d);
+        return NoiseNormBatch(ct.Level() + 1, 1, pt.d, dev_ref, 0, kind)[0];
+    }
     // The shares of the party of sk for the ciphertexts cts (one level; their id sets may differ) as one engine call.  floodBits = 1 .. 62: the width of
     // the flooding noise, drawn on the device under one nonce of `sampler`; no default -- it must exceed the noise of the ciphertext by the statistical
     // security parameter, which the engine cannot know.  floodBits = 0 (sampler may be null) is for tests only: such a share reveals sk.
@@ -971,6 +1027,21 @@ class Encoder {
     }
     Parameters& params;
 };
+// mkrlwe::Decryptor with the noise of a ciphertext against the message it should hold: the residual of the phase against the device encoder's plaintext
+// of msg (Slots() values) at the level and scale of ct.  NoiseBits is what the floodBits of a ShareNew must exceed.
+class Decryptor : public mkrlwe::Decryptor {
+  public:
+    explicit Decryptor(Parameters& p) : mkrlwe::Decryptor(p), ckks(p) {}
+    using mkrlwe::Decryptor::NoiseNorm;
+    mkrlwe::NoiseValue NoiseNorm(const Ciphertext& ct, const mkrlwe::SecretKeySet& skSet, const std::complex<double>* msg) {
+        mkrlwe::DeviceWords ref(ckks, (size_t)(ct.Level() + 1) * ckks.N());
+        Encoder(ckks).Encode(1, msg, ct.Level(), ct.Scale, ref.d);
+        return mkrlwe::Decryptor::NoiseNorm(ct, skSet, ref.d);
+    }
+    int NoiseBits(const Ciphertext& ct, const mkrlwe::SecretKeySet& skSet, const std::complex<double>* msg) { return NoiseNorm(ct, skSet, msg).Bits(); }
+  private:
+    Parameters& ckks;
+};
 // The collective key switch of mkrlwe::PublicKeySwitcher on mkckks ciphertexts: the result keeps the input's Scale.
 class PublicKeySwitcher : public mkrlwe::PublicKeySwitcher {
   public:
@@ -1179,6 +1250,34 @@ class Encoder {
         z.download(reinterpret_cast<uint64_t*>(values));
     }
     Parameters& params;
+};
+// mkrlwe::Decryptor with the noise measures of BFV (include/mkhe.h, "noise measurement").  InvariantNoise: r = max |[T phase]_Q| (kind 1), no message
+// needed.  NoiseBudget = bitlen(Q) - bitlen(r) - 1 >= 0.  NoiseNorm with a message (Slots() values): max |e| exactly, the residual against
+// mkhe_bfv_encode(msg); without: the bound (r + T / 2) / T + 1, which lies in [max |e|, max |e| + 2] while the noise has not wrapped.  NoiseBits is
+// what the floodBits of a ShareNew must exceed.
+class Decryptor : public mkrlwe::Decryptor {
+  public:
+    explicit Decryptor(Parameters& p) : mkrlwe::Decryptor(p), bfv(p) {}
+    mkrlwe::NoiseValue InvariantNoise(const mkrlwe::Ciphertext& ct, const mkrlwe::SecretKeySet& skSet) { return mkrlwe::Decryptor::NoiseNorm(ct, skSet, nullptr, 1); }
+    int NoiseBudget(const mkrlwe::Ciphertext& ct, const mkrlwe::SecretKeySet& skSet) {
+        mkrlwe::NoiseValue q;
+        q.Words.push_back(1);
+        for (uint64_t m : bfv.Q()) q.MulAdd(m, 0);
+        return q.Bits() - InvariantNoise(ct, skSet).Bits() - 1;
+    }
+    mkrlwe::NoiseValue NoiseNorm(const mkrlwe::Ciphertext& ct, const mkrlwe::SecretKeySet& skSet, const int64_t* msg = nullptr) {
+        if (msg) {
+            mkrlwe::DeviceWords ref(bfv, (size_t)bfv.QCount() * bfv.N());
+            Encoder(bfv).Encode(1, msg, ref.d);
+            return mkrlwe::Decryptor::NoiseNorm(ct, skSet, ref.d);
+        }
+        mkrlwe::NoiseValue r = InvariantNoise(ct, skSet);
+        r.Index = -1;
+        return r.MulAdd(1, bfv.T() / 2).Div(bfv.T()).MulAdd(1, 1);
+    }
+    int NoiseBits(const mkrlwe::Ciphertext& ct, const mkrlwe::SecretKeySet& skSet, const int64_t* msg = nullptr) { return NoiseNorm(ct, skSet, msg).Bits(); }
+  private:
+    Parameters& bfv;
 };
 
 // The collective refresh of MK-BFV between parties (include/mkhe.h, "collective refresh for MK-BFV"): ShareNew (each party, on its own keys and its

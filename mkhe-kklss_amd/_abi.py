@@ -131,6 +131,7 @@ SIGNATURES = {
     "mkhe_bfv_refresh_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp, vpp]),
     "mkhe_pcks_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, vp, u32p, C.c_uint64, C.c_int, u64p, C.c_int, vp]),
     "mkhe_pcks_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp]),
+    "mkhe_noise_norm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_long, vp]),
     "mkhe_ckks_embed": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_project": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_scale_up": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),

@@ -929,6 +929,31 @@ int mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int n
         c->decrypt_merge(i, sh, (u64*)dev_pt_out);
     })
 }
+// noise measurement: the scalars that need no context first, then the guard of the protocol family; the tables (and, kind 1, the encoder's
+// preconditions on T) behind the last refusal that needs no device
+int mkhe_noise_norm(mkhe_ctx* ctx, int kind, int limbs, int count, const void* dev_phase, const void* dev_ref, long ref_stride_words, void* dev_out) {
+    MKHE_TRY({
+        const char* what = "mkhe_noise_norm";
+        const std::string w(what);
+        if (kind != 0 && kind != 1) throw Error(w + ": kind must be 0 (residual) or 1 (BFV invariant)");
+        count_ok(what, count);
+        if (limbs < 1) throw Error(w + ": limbs out of range");
+        if (kind == 1 && dev_ref) throw Error(w + ": kind 1 takes no reference (dev_ref must be NULL)");
+        Context* c = enter(ctx, what);
+        if (!dev_phase || !dev_out) throw Error(w + ": null argument");
+        need_aligned(dev_phase, what); need_aligned(dev_ref, what); need_aligned(dev_out, what);
+        if (limbs > c->nq) throw Error(w + ": limbs out of range");
+        if (ref_stride_words != 0 && ref_stride_words != (long)limbs * c->N) throw Error(w + ": ref_stride_words must be 0 (one reference for all) or limbs * N");
+        if (kind == 1) {
+            scheme_ok(c, what, true, ": kind 1 (BFV invariant) needs a BFV context");
+            if (limbs != c->nq) throw Error(w + ": kind 1 takes the nQ limbs of the context");
+        }
+        unmasked(c, what);
+        not_captured(c, what, UPLOADS);
+        commit(c, [&] { c->noise_norm_prepare(kind); });
+        c->noise_norm(kind, limbs, count, (const u64*)dev_phase, (const u64*)dev_ref, ref_stride_words, (u64*)dev_out);
+    })
+}
 // collective refresh, for the CKKS side and for MK-BFV (every ciphertext of a BFV context that the calls take has nq limbs): under the rules of
 // distributed decryption; why_capture closes the capture message
 static Context* refresh_enter(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, const char* why_capture) {

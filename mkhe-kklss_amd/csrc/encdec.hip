@@ -520,4 +520,27 @@ void Context::encrypt_sk(int level, int count, const u64* sk, const u64* pt, boo
     MKHE_HIP(hipGetLastError());
 }
 
+// ---- noise measurement (include/mkhe.h; noise_kernels.h).  rf_dig_ holds the digit scratch [count][limbs][N] and behind it the candidates of the
+// workgroups [count][blocks][limbs + 1].  Both are the noise of the ciphertext, which depends on the keys: wiped behind the second launch, as
+// decrypt_share wipes its unflooded product.  The result itself is the caller's.
+void Context::noise_norm(int kind, int limbs, int count, const u64* phase, const u64* ref, long ref_stride, u64* out) {
+    need_unmasked("mkhe_noise_norm");
+    NoiseArgs a{};
+    a.phase = phase; a.ref = ref; a.ref_stride = ref_stride;
+    a.tmont = kind == 1 ? d_bf_tmont : nullptr;
+    a.garner = garner_table(); a.mods = d_mods; a.out = out;
+    a.nq = nq; a.limbs = limbs; a.N = N; a.blocks = nz_blocks(N);
+    const size_t dw = (size_t)count * limbs * N, pw = (size_t)count * a.blocks * (limbs + 1);
+    a.dig = scratch(rf_dig_, dw + pw);
+    a.part = a.dig + dw;
+    {
+        // the inputs once; every digit is written once, read by each later limb, by the sign, by the complement (which writes it again) and by the selection
+        const double refs = ref ? (ref_stride ? (double)count : 1.0) : 0.0;
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * limbs * (count * (1.0 + 5.0 + (limbs - 1) / 2.0) + refs));
+        launch_noise_norm(a, count, s_);
+    }
+    MKHE_HIP(hipMemsetAsync(a.dig, 0, (dw + pw) * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
+}
+
 }  // namespace mkhe

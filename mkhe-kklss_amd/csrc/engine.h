@@ -24,6 +24,7 @@
 #include "bfv_refresh_kernels.h"
 #include "pcks_kernels.h"
 #include "skenc_kernels.h"
+#include "noise_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -316,6 +317,12 @@ class Context {
                     const u64* cdt, int ncdt, u64* shares);
     // outs[b] [2][L][N] <- (ins[b] polynomial 0 + sum_i shares[i][b][0], sum_i shares[i][b][1]), canonical
     void pcks_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, u64* const* outs);
+    // noise measurement (include/mkhe.h; noise_kernels.h): out [count][limbs + 1] <- the mixed-radix digits of max_n min(x, Q - x) and the smallest n
+    // that attains it, x = phase - ref (kind 0; ref null: phase; ref_stride 0: one reference for all) or T phase (kind 1: BFV context, limbs = nq)
+    // mod Q = q_0 .. q_(limbs-1).  Two launches; the digits and the candidates, which are the noise itself, are wiped behind them.  The caller
+    // (capi.hip) has checked kind, shapes and the capture, and has had noise_norm_prepare build the tables the kernels read.
+    void noise_norm_prepare(int kind) { if (kind == 1) bf_init("mkhe_noise_norm"); garner_table(); }
+    void noise_norm(int kind, int limbs, int count, const u64* phase, const u64* ref, long ref_stride, u64* out);
     // secret-key encryption with a seeded c1 (include/mkhe.h; skenc_kernels.h): polynomial 1 of outs[b] [2][level+1][N] <- the rows (b, j) of kind 6
     // of the keystream under the PUBLIC (a_key, a_nonce), polynomial 0 <- pt + e_b - c1 * sk.  e != null: host int32 [count][N] (e_key, cdt unread);
     // e == null: e_b = kind 1 on stream b of the SECRET (e_key, e_nonce), formed in registers.  what = the C entry point (for messages).  No host

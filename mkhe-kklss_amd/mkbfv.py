@@ -799,6 +799,29 @@ class Decryptor(mkrlwe.Decryptor):
             Q *= int(q)
         return (Q // (2 * int(self.params.T()) * int(parties))).bit_length() - 1
 
+    def InvariantNoise(self, ct, skSet):
+        """r = max_n |[T * phase(ct)]_Q| as a Python integer, measured on the device (mkhe_noise_norm, kind 1): with phase = up(m) + e it is
+        T |e| up to the rounding of up, and needs no message.  r <= (Q - 1) / 2."""
+        return self.NoiseNormBatch(mkrlwe.Decryptor.Decrypt(self, ct, skSet), kind=1)[0][0]
+
+    def NoiseBudget(self, ct, skSet):
+        """bitlen(Q) - bitlen(InvariantNoise) - 1, in bits: never negative, and 0 where the noise has reached Q / (2 T) and decryption fails"""
+        return int(_q_product(self.params)).bit_length() - self.InvariantNoise(ct, skSet).bit_length() - 1
+
+    def NoiseNorm(self, ct, skSet, msg=None):
+        """The noise of ct, max_n |e_n| with phase(ct) = up(m) + e, as a Python integer.  With msg (a Message): exactly, as the residual
+        against the DEVICE encoder's plaintext of msg (mkhe_bfv_encode), whichever encoder this Decryptor decodes with.  Without: the bound
+        (r + T // 2) // T + 1 from r = InvariantNoise, which lies in [|e|, |e| + 2] as long as the noise has not wrapped (NoiseBudget > 0)."""
+        if msg is not None:
+            return mkrlwe.Decryptor.NoiseNorm(self, ct, skSet, DeviceEncoder(self.params).Encode(msg.Value))
+        T = int(self.params.T())
+        return (self.InvariantNoise(ct, skSet) + T // 2) // T + 1
+
+    def NoiseBits(self, ct, skSet, msg=None):
+        """NoiseNorm(ct, skSet, msg).bit_length(): what the flood_bits of ShareNew (Decryptor, Refresher, PublicKeySwitcher) must exceed,
+        by the statistical security parameter"""
+        return self.NoiseNorm(ct, skSet, msg).bit_length()
+
     def MergeSharesMsg(self, ct, shares):
         """the merge of the shares of all parties -> Message.  With the device encoder the merged buffer goes straight to mkhe_bfv_decode."""
         pt = self.MergeShares(ct, shares)
@@ -817,7 +840,7 @@ class Refresher:
     give a ciphertext of the same message over the same parties whose noise is that of a fresh encryption (RefreshNoiseBound); nobody sees the
     message.  A share is c_id * s_id + up(A) + e with A uniform mod T and e a flood of flood_bits bits, and comes with Encrypt(up(-A)); the
     merge rounds c_0 + the shares to Z_T, scales up again and adds the re-encryptions.  The caller chooses flood_bits (at most MaxFloodBits):
-    flood_bits minus the bit size of the ciphertext's noise is the statistical hiding of that noise, which depends on the keys."""
+    flood_bits minus the bit size of the ciphertext's noise (Decryptor.NoiseBits) is the statistical hiding of that noise, which depends on the keys."""
 
     def __init__(self, params):
         self.params = params

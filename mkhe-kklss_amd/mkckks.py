@@ -1178,6 +1178,18 @@ class Decryptor(mkrlwe.Decryptor):
         the flooding noises is below parties * 2^(flood_bits - 1) per coefficient, and a slot is a sum of N coefficients times unit-modulus roots)"""
         return self.params.N() * self.FloodBound(parties, flood_bits) / float(scale)
 
+    def NoiseNorm(self, ct, skSet, msg):
+        """The largest coefficient, centred, of phase(ct) - plaintext(msg) as a Python integer, measured on the device (mkhe_noise_norm): the
+        reference is the DEVICE encoder's plaintext of msg at ct.Level() and ct.Scale, whichever encoder this Decryptor decodes with.  It is
+        the noise of ct plus what the encoding of msg differs by from the encoding ct was made with (nothing for a ciphertext encrypted
+        from the device encoder's plaintext of the same message)."""
+        ref = DeviceEncoder(self.params).Encode(msg.Value, ct.Level(), ct.ScalingFactor())
+        return mkrlwe.Decryptor.NoiseNorm(self, ct, skSet, ref)
+
+    def NoiseBits(self, ct, skSet, msg):
+        """NoiseNorm(ct, skSet, msg).bit_length(): what the flood_bits of ShareNew (Decryptor, Refresher, PublicKeySwitcher) must exceed"""
+        return self.NoiseNorm(ct, skSet, msg).bit_length()
+
     def MergeSharesMsg(self, ct, shares):
         """the merge of the shares of all parties -> Message.  With the device encoder the merged buffer goes straight to mkhe_ckks_decode."""
         pt = self.MergeShares(ct, shares)

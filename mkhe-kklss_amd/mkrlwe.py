@@ -1209,7 +1209,8 @@ class Decryptor:
         """The decryption shares of the party of `sk` for B ciphertexts at one level (their id sets may differ) as ONE engine call
         (mkhe_decrypt_share) -> one DecryptionShare of count B.  flood_bits = 1 .. 62: the width of the flooding noise, uniform on
         [-2^(bits-1), 2^(bits-1)), drawn on the device under one nonce of `sampler` (a DeviceSampler); it must exceed the noise of the ciphertext
-        by the statistical security parameter, which the engine cannot know -- so there is no default.  flood_bits = 0 (no noise, sampler
+        by the statistical security parameter, which the engine cannot know -- so there is no default (NoiseNorm / NoiseBits of the scheme's
+        Decryptor measure that noise).  flood_bits = 0 (no noise, sampler
         unused) is for TESTS ONLY: such a share is PartialDecrypt's product and reveals sk."""
         cts = list(cts)
         if not cts:
@@ -1277,6 +1278,42 @@ class Decryptor:
         sks = [skSet.Value[i].Value.devptr() for i in ct.ids]
         check(lib().mkhe_decrypt(self.params.ctx, ct.h, handle_array(sks), pt.devptr()))
         return pt
+
+    def NoiseNormBatch(self, phases, refs=None, kind=0):
+        """The exact centred max norm of B phases as ONE engine call (mkhe_noise_norm; include/mkhe.h, "noise measurement") ->
+        [(r, n)] per item: r = max_n min(x_n, Q - x_n) as a Python integer, Q the product of the first `limbs` moduli, and the smallest n that
+        attains it.  phases: DeviceLimbs [B][limbs][N], canonical, coefficient domain -- what Decrypt gives, or MergeSharesBatch, so parties
+        that hold only their own key can measure too (with flood_bits = 0 shares; otherwise the flood is measured with the noise).
+        kind 0: x = phases - refs (refs: DeviceLimbs [B][limbs][N], or [1][limbs][N] for one reference for all; None: x = phases).
+        kind 1 (BFV contexts, limbs = nQ, no refs): x = T * phases, the invariant noise.  Only the digits and n come down; the host
+        multiplies the mixed-radix digits out."""
+        if not isinstance(phases, DeviceLimbs):
+            raise MkheError("Cannot NoiseNorm: the phases must be DeviceLimbs [count][limbs][N]")
+        count, limbs, N = phases.count, phases.limbs, self.params.N()
+        ref, stride = None, 0
+        if refs is not None:
+            if not isinstance(refs, DeviceLimbs) or refs.limbs != limbs or refs.count not in (1, count):
+                raise MkheError("Cannot NoiseNorm: the references must be DeviceLimbs [count][limbs][N] or [1][limbs][N] with the limbs of the phases")
+            ref, stride = refs.devptr(), (0 if refs.count == 1 else limbs * N)
+        words = count * (limbs + 1)
+        out = DeviceLimbs(self.params, -(-words // N), 1)
+        check(lib().mkhe_noise_norm(self.params.ctx, int(kind), limbs, count, phases.devptr(), ref, stride, out.devptr()))
+        rows = out.download().reshape(-1)[:words].reshape(count, limbs + 1)
+        res = []
+        for row in rows:
+            r, w = 0, 1
+            for d, q in zip(row[:limbs], self.params.Q):
+                r, w = r + int(d) * w, w * int(q)
+            res.append((r, int(row[limbs])))
+        return res
+
+    def NoiseNorm(self, ct, skSet, ref=None):
+        """Decrypt, then NoiseNormBatch against `ref` (DeviceLimbs [1][level+1][N], or a host polynomial [level+1][N]: the plaintext the
+        ciphertext is expected to hold) -> the largest coefficient of the residual, centred, as a Python integer: the noise of ct when ref is
+        its plaintext.  Its bit_length() is the size that the flood_bits of ShareNew must exceed."""
+        if ref is not None and not isinstance(ref, DeviceLimbs):
+            ref = _device_plaintexts(self.params, np.asarray(ref, dtype=np.uint64)[None])
+        return self.NoiseNormBatch(Decryptor.Decrypt(self, ct, skSet), ref)[0][0]
 
 
 def NewDecryptor(params):
@@ -1459,7 +1496,7 @@ class PublicKeySwitcher:
     def MaxFloodBits(self, level=None):
         """the widest flood the engine takes for ciphertexts at `level` (default: the maximum): bitlen(Q_l div 2T') - 1, capped at the 1024
         bits the engine draws; T' = T on a BFV ring, 1 otherwise.  Such a flood alone would still leave the message standing; what the noise of
-        the ciphertext and the number of parties leave of it is the caller's budget (NoiseBound)."""
+        the ciphertext (NoiseNorm / NoiseBits of the scheme's Decryptor) and the number of parties leave of it is the caller's budget (NoiseBound)."""
         return self._most(self.params.MaxLevel() if level is None else int(level))
 
     def _most(self, level):
