@@ -884,6 +884,30 @@ int  mkhe_bfv_ct_mul_ptxt(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, c
  * out[b] == in[b]).  One launch for as many items as the component list of the elementwise kernel holds (65 components). */
 int  mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out);
 
+/* ==== BFV plaintext linear transform: the batched diagonal dot product ================================
+ * No reference counterpart; the preconditions and refusals of "BFV plaintext operands" apply.  Let n = N/2.  A message is z[r][j], r in {0, 1},
+ * j < n (the two slot rows of the "BFV batch encoder").  rot_k moves slot j + k to slot j in each row (a rotation by galEl 5^k); swap exchanges the
+ * rows (the conjugation, galEl 2N - 1).  A Z_T-linear map is two sets of diagonals, int64 [2][n] each, taken mod T, indices mod n:
+ *   (M z)[r][j] = sum_k d_k[r][j] z[r][(j + k) mod n] + sum_k e_k[r][j] z[1 - r][(j + k) mod n]      (mod T).
+ * swap commutes with rot_k and with slot-wise products, so with e~_k[r] = e_k[1 - r]:  M z = LT_d(z) + swap(LT_e~(z)).  Each part is evaluated as
+ * sum_g rot_g(sum_b d'_(g,b) (.) rot_b z) with k = g + b and d'_(g,b) = roll(d_(g+b), g) along the slot axis of each row; both parts share the baby
+ * rotations rot_b z, and the row-swapping part costs one conjugation of its sum.  The call below is the middle of that schedule: every inner sum of
+ * every part for nbatch encrypted vectors, as one launch set.
+ *   out[b * ngiant + g] = sum over the set bits i of masks[g] of in[b * nin + i] * P(g, i),      b < nbatch, g < ngiant
+ * component by component as a negacyclic product mod q_l, canonical.  P(g, i) are prepared multiplication plaintexts of nQ * N words each
+ * (mkhe_bfv_encode_mul), stored COMPACTLY in (g, i) order with the numbering of mkhe_ct_ptxt_dot: plaintext number (set bits of masks[0 .. g-1]) +
+ * (set bits of masks[g] below i) lies at dev_ptmul + number * nQ * N words.  The block is exactly what ONE mkhe_bfv_encode_mul(count = nnz) writes;
+ * it is shared by all nbatch items and read where it lies.  1 <= nbatch <= 16, 1 <= nin <= 16, 1 <= ngiant <= 64; every mask is non-zero and has no
+ * bit at or above nin; masks is a host array consumed at call time; all handles carry the same ids and nQ limbs; the outputs are distinct and
+ * alias no input.  Launch set: the forward NTT of all nbatch * nin * (1 + k) components (64 ciphertexts per launch), ONE product kernel with the
+ * item in its grid, the inverse NTT into the outputs; the temporaries are one pooled block.  out[b][g] equals, bit for bit, mkhe_ct_sum over the
+ * set bits i of mkhe_bfv_ct_mul_ptxt(in[b][i], P(g, i)): both are the canonical residue of the same integer.  A refused call enqueues nothing and
+ * leaves the context usable; it is refused between mkhe_capture_begin and mkhe_capture_end like the other calls of this family.
+ * Noise of the whole transform: a baby rotation adds one key-switch error; the product multiplies the noise by at most N * T/2 per diagonal (above);
+ * each giant rotation and the conjugation add one key-switch error.  The result decrypts exactly while the total stays below Q / (2T). */
+int  mkhe_bfv_ct_ptxt_dot(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* const* in, int ngiant, const uint32_t* masks,
+                          const void* dev_ptmul, mkhe_ct* const* out);
+
 /* ---- measurement support (no reference counterpart): HIP-event timing per kernel class on the
  *      context stream, one record per kernel launch.  Classes (mkhe_prof_name gives the kernel symbol
  *      each class corresponds to in a rocprofv3 kernel trace). */

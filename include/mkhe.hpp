@@ -1143,6 +1143,78 @@ struct RelinearizationKeySet {                                                  
     }
     std::map<std::string, std::shared_ptr<RelinearizationKey>> Value;
 };
+// A Z_T-linear map on the two slot rows of a BFV message, encoded once for Evaluator::LinearTransformNew (no reference counterpart; include/mkhe.h,
+// "BFV plaintext linear transform"; the Python mirror's mkbfv.LinearTransform).  With n = N/2: (M z)[r][j] = sum_k d_k[r][j] z[r][(j+k) mod n] +
+// sum_k e_k[r][j] z[1-r][(j+k) mod n].  A diagonal is 2 n values, row 0 then row 1, taken mod T; indices are taken mod n.  diagonals keep the rows,
+// swapped exchange them.  n1 = 0: the power of two <= 16 with the fewest rotations over the union of both index sets (ties to the smaller).  All
+// pre-rotated diagonals of both parts go through ONE mkhe_bfv_encode_mul into the compact block of mkhe_bfv_ct_ptxt_dot; masks holds the giants of
+// the row-preserving part, then those of the row-swapping part.
+class LinearTransform {
+  public:
+    typedef std::map<int, std::vector<int64_t>> Diagonals;
+    LinearTransform(Parameters& p, const Diagonals& diagonals, const Diagonals& swapped = Diagonals(), int n1_ = 0) : params(p), n(p.N() / 2) {
+        if (diagonals.empty() && swapped.empty()) throw Error("mkbfv::LinearTransform: no diagonal");
+        if (n1_ < 0 || n1_ > 16 || (n1_ & (n1_ - 1))) throw Error("mkbfv::LinearTransform: n1 must be a power of two, at most 16");
+        std::map<int, const std::vector<int64_t>*> part[2];
+        const Diagonals* src[2] = {&diagonals, &swapped};
+        std::set<int> idx;
+        for (int s = 0; s < 2; ++s)
+            for (auto& kv : *src[s]) {
+                const int k = ((kv.first % n) + n) % n;
+                if (kv.second.size() != 2 * (size_t)n) throw Error("mkbfv::LinearTransform: a diagonal holds 2 * N/2 values (row 0, then row 1)");
+                if (!part[s].emplace(k, &kv.second).second) throw Error("mkbfv::LinearTransform: a diagonal is given twice (indices are taken mod N/2)");
+                idx.insert(k);
+            }
+        long best = -1;
+        for (int m = n1_ ? n1_ : 1; m <= (n1_ ? n1_ : 16); m *= 2) {
+            std::set<int> b, g;
+            for (int k : idx) { b.insert(k % m); g.insert(k - k % m); }
+            const long cost = (long)(b.size() - b.count(0) + g.size() - g.count(0));
+            if (g.size() <= 64 && (best < 0 || cost < best)) { best = cost; n1 = m; babies.assign(b.begin(), b.end()); }
+        }
+        if (best < 0) throw Error("mkbfv::LinearTransform: more than 64 giant steps");
+        std::vector<uint64_t> rows;
+        for (int s = 0; s < 2; ++s) {
+            std::set<int> g;
+            for (auto& kv : part[s]) g.insert(kv.first - kv.first % n1);
+            (s ? giantsE : giantsD).assign(g.begin(), g.end());
+            for (int gi : g) {
+                uint32_t mask = 0;
+                for (size_t i = 0; i < babies.size(); ++i) {
+                    auto it = part[s].find(gi + babies[i]);
+                    if (it == part[s].end()) continue;
+                    mask |= 1u << i;
+                    // roll(d_(g+b), g) along each row; the swapped part with its rows exchanged (e~_k[r] = e_k[1 - r])
+                    for (int r = 0; r < 2; ++r) {
+                        const int64_t* d = it->second->data() + (size_t)(s ? 1 - r : r) * n;
+                        for (int j = 0; j < n; ++j) rows.push_back((uint64_t)d[(j - gi + n) % n]);
+                    }
+                }
+                masks.push_back(mask);
+            }
+        }
+        if (masks.size() > 64) throw Error("mkbfv::LinearTransform: more than 64 giant steps over the two parts");
+        nnz = (int)(rows.size() / (2 * (size_t)n));
+        mkrlwe::DeviceWords z(p, rows.size());
+        z.upload(rows.data());
+        pt = std::make_unique<mkrlwe::DeviceWords>(p, (size_t)nnz * p.QCount() * p.N());
+        check(mkhe_bfv_encode_mul(p.ctx, nnz, z.d, pt->d));
+    }
+    // the sorted non-zero baby and giant indices: what AddCRS and the rotation keys must cover
+    std::vector<int> Rotations() const {
+        std::set<int> r(babies.begin(), babies.end());
+        r.insert(giantsD.begin(), giantsD.end()); r.insert(giantsE.begin(), giantsE.end());
+        r.erase(0);
+        return std::vector<int>(r.begin(), r.end());
+    }
+    // whether a conjugation key per party and CRS[-2] are needed
+    bool NeedsConjugation() const { return !giantsE.empty(); }
+    Parameters& params;
+    int n, n1 = 1, nnz = 0;
+    std::vector<int> babies, giantsD, giantsE;
+    std::vector<uint32_t> masks;
+    std::unique_ptr<mkrlwe::DeviceWords> pt;
+};
 // mkbfv.Evaluator (evaluator.go:7-20)
 class Evaluator {
   public:
@@ -1205,9 +1277,102 @@ class Evaluator {
     }
     CiphertextPtr AddPtxtNew(const Ciphertext& ct, const void* dev_pt) { return addPtxt(0, ct, dev_pt); }
     CiphertextPtr SubPtxtNew(const Ciphertext& ct, const void* dev_pt) { return addPtxt(1, ct, dev_pt); }
+    // Hoisted rotations, as mkckks::Evaluator has them: every mkrlwe-level call works on a BFV context.  The same ciphertext as RotateNew, bit for bit.
+    std::unique_ptr<mkrlwe::HoistedCiphertext> HoistedForm(const Ciphertext& ct) {
+        auto h = std::make_unique<mkrlwe::HoistedCiphertext>();
+        std::vector<mkhe_swk*> outs;
+        for (auto& id : ct.ids) { h->Value[id] = mkrlwe::NewSwitchingKey(params); outs.push_back(h->Value[id]->h); }
+        check(mkhe_hoisted_form(params.ctx, ct.Level(), ct.h, outs.data()));
+        return h;
+    }
+    CiphertextPtr RotateHoistedNew(const Ciphertext& ct0, int rotidx, const mkrlwe::HoistedCiphertext& hoisted, mkrlwe::RotationKeySet& rkSet) {
+        const int n2 = params.N() / 2;
+        rotidx = ((rotidx % n2) + n2) % n2;
+        auto out = std::make_unique<Ciphertext>(params, ct0.IDSet_(), false);
+        if (rotidx == 0) { check(mkhe_ct_copy(params.ctx, ct0.h, out->h)); return out; }
+        if (!params.CRS.count(rotidx)) throw Error("Hoisted rotation only works for precomputed rotation keys");
+        ksw.RotateHoisted(ct0, rotidx, &hoisted, rkSet, *out);
+        return out;
+    }
+    // M z for the diagonals of lt (no reference counterpart; the fused form of the Python mirror's LinearTransformNew): HoistedForm, the non-zero baby
+    // rotations as lanes of one mkhe_rotate_multi, ONE mkhe_bfv_ct_ptxt_dot, the non-zero giant rotations as lanes of one mkhe_rotate_multi, mkhe_ct_sum
+    // per part in groups of 16, mkhe_conjugate of the row-swapping sum, mkhe_ct_add.  Throws before any engine call when a CRS or a key is missing.
+    CiphertextPtr LinearTransformNew(const Ciphertext& ct, const LinearTransform& lt, mkrlwe::RotationKeySet& rkSet, mkrlwe::ConjugationKeySet* ckSet = nullptr) {
+        if (&lt.params != &params) throw Error("LinearTransform: the transform was encoded for other parameters");
+        for (int r : lt.Rotations()) {
+            if (!params.CRS.count(r)) throw Error("LinearTransform: no CRS for rotation index " + std::to_string(r));
+            for (auto& i : ct.ids) rkSet.GetRotationKey(i, r);
+        }
+        if (lt.NeedsConjugation()) {
+            if (!ckSet) throw Error("LinearTransform: the transform swaps the slot rows: pass the conjugation keys (ckSet)");
+            if (!params.CRS.count(-2)) throw Error("LinearTransform: no CRS for the conjugation (CRS[-2])");
+            for (auto& i : ct.ids) ckSet->GetConjugationKey(i);
+        }
+        std::vector<int> nzb;
+        for (int b : lt.babies) if (b) nzb.push_back(b);
+        std::vector<CiphertextPtr> rotated;
+        if (!nzb.empty()) {
+            auto hoisted = HoistedForm(ct);
+            rotated = rotateLanes(std::vector<const Ciphertext*>(nzb.size(), &ct), nzb, hoisted.get(), rkSet);
+        }
+        std::vector<const mkhe_ct*> in;
+        for (size_t i = 0, k = 0; i < lt.babies.size(); ++i) in.push_back(lt.babies[i] ? rotated[k++]->h : ct.h);
+        std::vector<CiphertextPtr> inner;
+        std::vector<mkhe_ct*> outs;
+        for (size_t g = 0; g < lt.masks.size(); ++g) { inner.push_back(std::make_unique<Ciphertext>(params, ct.IDSet_(), false)); outs.push_back(inner.back()->h); }
+        check(mkhe_bfv_ct_ptxt_dot(params.ctx, 1, (int)in.size(), in.data(), (int)outs.size(), lt.masks.data(), lt.pt->d, outs.data()));
+        std::vector<int> giants(lt.giantsD);
+        giants.insert(giants.end(), lt.giantsE.begin(), lt.giantsE.end());
+        std::vector<const Ciphertext*> gsrc;
+        std::vector<int> grot;
+        for (size_t g = 0; g < giants.size(); ++g) if (giants[g]) { gsrc.push_back(inner[g].get()); grot.push_back(giants[g]); }
+        if (!grot.empty()) {
+            auto moved = rotateLanes(gsrc, grot, nullptr, rkSet);
+            for (size_t g = 0, k = 0; g < giants.size(); ++g) if (giants[g]) inner[g] = std::move(moved[k++]);
+        }
+        CiphertextPtr total;
+        const size_t nd = lt.giantsD.size();
+        if (nd) total = summed(std::vector<CiphertextPtr>(std::make_move_iterator(inner.begin()), std::make_move_iterator(inner.begin() + nd)));
+        if (lt.NeedsConjugation()) {
+            auto sw = ConjugateNew(*summed(std::vector<CiphertextPtr>(std::make_move_iterator(inner.begin() + nd), std::make_move_iterator(inner.end()))), *ckSet);
+            total = total ? AddNew(*total, *sw) : std::move(sw);
+        }
+        return total;
+    }
     Parameters& params;
     mkrlwe::KeySwitcher ksw;
   private:
+    // srcs[i] rotated by rots[i] != 0 as lanes of one mkhe_rotate_multi; hoist: the hoisted form every lane shares, or null
+    std::vector<CiphertextPtr> rotateLanes(const std::vector<const Ciphertext*>& srcs, const std::vector<int>& rots, const mkrlwe::HoistedCiphertext* hoist,
+                                           mkrlwe::RotationKeySet& rkSet) {
+        std::vector<CiphertextPtr> res;
+        std::vector<uint64_t> gal;
+        std::vector<const mkhe_ct*> in;
+        std::vector<mkhe_ct*> out;
+        std::vector<const mkhe_swk*> hs, rk, crs;
+        for (size_t l = 0; l < srcs.size(); ++l) {
+            res.push_back(std::make_unique<Ciphertext>(params, srcs[l]->IDSet_(), false));
+            gal.push_back(params.GaloisElementForColumnRotationBy(rots[l]));
+            in.push_back(srcs[l]->h); out.push_back(res.back()->h); crs.push_back(params.CRS.at(rots[l])->h);
+            for (auto& i : srcs[l]->ids) { rk.push_back(rkSet.GetRotationKey(i, rots[l]).Value->h); if (hoist) hs.push_back(hoist->Value.at(i)->h); }
+        }
+        check(mkhe_rotate_multi(params.ctx, (int)srcs.size(), gal.data(), in.data(), hoist ? hs.data() : nullptr, rk.data(), crs.data(), nullptr, out.data()));
+        return res;
+    }
+    // the sum of 1 .. 64 ciphertexts of one shape: mkhe_ct_sum in groups of 16
+    CiphertextPtr summed(std::vector<CiphertextPtr> terms) {
+        while (terms.size() > 1) {
+            std::vector<CiphertextPtr> next;
+            for (size_t i = 0; i < terms.size(); i += 16) {
+                std::vector<const mkhe_ct*> grp;
+                for (size_t k = i; k < std::min(terms.size(), i + 16); ++k) grp.push_back(terms[k]->h);
+                next.push_back(std::make_unique<Ciphertext>(params, terms[i]->IDSet_(), false));
+                check(mkhe_ct_sum(params.ctx, (int)grp.size(), grp.data(), next.back()->h));
+            }
+            terms = std::move(next);
+        }
+        return std::move(terms[0]);
+    }
     CiphertextPtr bin(const Ciphertext& a, const Ciphertext& b) { return std::make_unique<Ciphertext>(params, mkrlwe::Union(a.IDSet_(), b.IDSet_()), false); }
     CiphertextPtr addPtxt(int op, const Ciphertext& ct, const void* dev_pt) {
         auto out = std::make_unique<Ciphertext>(params, ct.IDSet_(), false);

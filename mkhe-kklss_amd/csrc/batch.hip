@@ -574,6 +574,71 @@ void Context::bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& in
     MKHE_HIP(hipGetLastError());
 }
 
+// outs[b * ngiant + g] = sum over the set bits i of masks[g] of ins[b * nin + i] * P(g, i) for B items that share masks and plaintexts: the forward NTT
+// of all B nin (1 + k) components (64 ciphertexts per launch), launch_ct_ptxt_dot with the item in its grid, the inverse NTT into the outputs.  ptmul is
+// the block of ONE bfv_encode_mul(count = nnz), read where it lies.  Bytes of the middle kernel: 8 N nQ (1 + k) B (nin + nnz + ngiant), of which
+// 8 N nQ nnz are first reads of the plaintexts and the other ((1 + k) B - 1) of them re-reads (poly_kernels.hip).  Every refusal comes before the
+// first launch.
+void Context::bfv_ct_ptxt_dot(const char* what, int nbatch, const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptmul,
+                              const std::vector<Ct*>& outs) {
+    bf_init(what);
+    const std::string w = std::string(what) + ": ";
+    const int B = nbatch, ngiant = (int)masks.size(), nin = B > 0 ? (int)ins.size() / B : 0;
+    if (B < 1 || B > CTDOT_MAX_BATCH) throw Error(w + "nbatch must be 1 .. " + std::to_string(CTDOT_MAX_BATCH));
+    if (nin < 1 || nin > CTDOT_MAX_IN || (size_t)nin * B != ins.size()) throw Error(w + "nin must be 1 .. " + std::to_string(CTDOT_MAX_IN));
+    if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT || (size_t)ngiant * B != outs.size()) throw Error(w + "ngiant must be 1 .. " + std::to_string(CTDOT_MAX_GIANT));
+    if (!ptmul) throw Error(w + "null argument");
+    CtPtxtDotArgs a{};
+    int nnz = 0;
+    for (int g = 0; g < ngiant; ++g) {
+        const unsigned int m = masks[g];
+        if (!m) throw Error(w + "a mask is zero");
+        if (m >> nin) throw Error(w + "a mask has a bit at or above nin");
+        a.mask[g] = m; a.first[g] = (unsigned short)nnz;
+        nnz += __builtin_popcount(m);
+    }
+    const Ct& c0 = *ins[0];
+    const int L = nq, np_ = 1 + c0.n;
+    const size_t PO = (size_t)L * N, CO = (size_t)np_ * PO;
+    for (const Ct* c : ins) {
+        if (c->limbs != nq) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
+        if (c->n != c0.n || c->ids != c0.ids) throw Error(w + "the ciphertexts of a list must share their ids");
+    }
+    for (size_t o = 0; o < outs.size(); ++o) {
+        if (outs[o]->limbs != nq) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
+        if (outs[o]->n != c0.n || outs[o]->ids != c0.ids) throw Error(w + "an output must carry the ids of the inputs");
+        for (size_t h = 0; h < o; ++h)
+            if (outs[o]->d < outs[h]->d + CO && outs[h]->d < outs[o]->d + CO) throw Error(w + "the outputs must be distinct");
+        for (const Ct* c : ins)
+            if (c->d < outs[o]->d + CO && outs[o]->d < c->d + CO) throw Error(w + "an output must not alias an input");
+    }
+    if ((size_t)B * np_ > 65535) throw Error(w + "more than 65535 polynomials in one call");
+    Arena ar(this, (ins.size() + outs.size()) * CO);
+    u64* x = ar.take(ins.size() * CO); u64* y = ar.take(outs.size() * CO);
+    for (size_t base = 0; base < ins.size(); base += NTT_MAX_ITEMS) {
+        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, ins.size() - base);
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
+        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d; b.dst_items[i] = x + (base + i) * CO; }
+        ntt_fwd_launch(b, false);
+    }
+    a.x = x; a.y = y; a.pt = ptmul; a.mods = d_mods; a.pt_words = (long)PO;
+    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_; a.nbatch = B;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * B * (nin + nnz + ngiant)); launch_ct_ptxt_dot(a, s_); }
+    for (size_t base = 0; base < outs.size(); base += NTT_MAX_ITEMS) {
+        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, outs.size() - base);
+        NttBatch b{};
+        b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
+        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = y + (base + i) * CO; b.dst_items[i] = outs[base + i]->d; }
+        { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
 // out_0 = CRed(c_0 +- pt), the other components copied (nothing where out == in), as components of the ct_binary kernel: the plaintext is the
 // second operand of component 0 where it lies.  As many items per launch as its component list holds.
 void Context::bfv_ct_add_ptxt(const char* what, int op, const std::vector<const Ct*>& ins, const u64* pt, long pt_stride, const std::vector<Ct*>& outs) {
@@ -738,7 +803,7 @@ void Context::ct_ptxt_dot(const std::vector<const Ct*>& ins, const std::vector<u
         b0 = b1;
     }
     a.x = x; a.y = y; a.pt = ptntt; a.mods = d_mods; a.pt_words = (long)pt_limbs * N;
-    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_;
+    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_; a.nbatch = 1;
     { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * (nin + nnz + ngiant)); launch_ct_ptxt_dot(a, s_); }
     {
         NttBatch b{};

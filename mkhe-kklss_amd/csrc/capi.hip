@@ -1250,6 +1250,33 @@ int mkhe_bfv_ct_mul_ptxt(mkhe_ctx* ctx, int nbatch, const mkhe_ct* const* in, co
         c->bfv_ct_mul_ptxt(what, i, (const u64*)dev_ptmul, pt_stride_words, o);
     })
 }
+// the counts are checked before the context is looked at, so that they can be refused without a device; the masks before anything is armed
+int mkhe_bfv_ct_ptxt_dot(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* const* in, int ngiant, const uint32_t* masks, const void* dev_ptmul,
+                         mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_ct_ptxt_dot";
+        const std::string w = std::string(what) + ": ";
+        if (nbatch < 1 || nbatch > CTDOT_MAX_BATCH) throw Error(w + "nbatch must be 1 .. " + std::to_string(CTDOT_MAX_BATCH));
+        if (nin < 1 || nin > CTDOT_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(CTDOT_MAX_IN));
+        if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT) throw Error(w + "ngiant must be 1 .. " + std::to_string(CTDOT_MAX_GIANT));
+        Context* c = enter(ctx, what);
+        if (!in || !masks || !dev_ptmul || !out) throw Error(w + "null argument");
+        need_aligned(dev_ptmul, what);
+        scheme_ok(c, what, true, ": needs a BFV context");
+        unmasked(c, what);
+        not_captured(c, what, "(the call may allocate or stage)");
+        for (int g = 0; g < ngiant; ++g) {
+            if (!masks[g]) throw Error(w + "a mask is zero");
+            if (masks[g] >> nin) throw Error(w + "a mask has a bit at or above nin");
+        }
+        for (int i = 0; i < nbatch * nin; ++i) ct_at(in, i, what);
+        for (int i = 0; i < nbatch * ngiant; ++i) if (!out[i]) throw Error(w + "null output in the batch");
+        commit(c);
+        auto i = ct_list(ctx, in, nbatch * nin, what);
+        auto o = ct_list_out(ctx, out, nbatch * ngiant, what);
+        c->bfv_ct_ptxt_dot(what, nbatch, i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptmul, o);
+    })
+}
 int mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_bfv_ct_add_ptxt";

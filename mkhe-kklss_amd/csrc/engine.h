@@ -363,6 +363,10 @@ class Context {
     // consecutive items, 0 = one plaintext for all.  what = the C entry point, for the messages.
     void bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& ins, const u64* ptmul, long pt_stride, const std::vector<Ct*>& outs);
     void bfv_ct_add_ptxt(const char* what, int op, const std::vector<const Ct*>& ins, const u64* pt, long pt_stride, const std::vector<Ct*>& outs);
+    // the middle of a BFV plaintext linear transform for nbatch items that share masks and plaintexts: ins = [nbatch][nin], outs = [nbatch][masks.size()],
+    // ptmul = the compact block of prepared plaintexts in (giant, input) order (the numbering of ct_ptxt_dot), nQ * N words each
+    void bfv_ct_ptxt_dot(const char* what, int nbatch, const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptmul,
+                         const std::vector<Ct*>& outs);
     // log2 of the largest transform one workgroup does in LDS (BF_TILE_LOG_BIG, or BF_TILE_LOG_DEF when the runtime grants no more LDS), and a way
     // to lower it (BF_TILE_LOG_MIN .. the grant; 0: back to the grant) so that the two-launch form can be run at small N
     int bfv_tile();

@@ -395,7 +395,9 @@ void launch_ct_lincomb(const CtLincombArgs& a, hipStream_t st);
 // rotations, canonical; y = [ngiant][npolys][L][N]; pt = the prepared plaintexts MForm(NTT(p)), compact in (g, b) order: number first[g] + (set bits of
 // mask[g] below b) lies at pt + index * pt_words (pt_words >= L * N: only the first L limbs of a plaintext are read).  Masks and offsets travel in the
 // kernel arguments: nothing is uploaded, so the launch may be captured.  x and y must not overlap.
-constexpr int CTDOT_MAX_IN = 16, CTDOT_MAX_GIANT = 64;
+// nbatch >= 1 items share masks and plaintexts (mkhe_bfv_ct_ptxt_dot): x = [nbatch][nin][npolys][L][N], y = [nbatch][ngiant][npolys][L][N], the item
+// a grid dimension next to the polynomial.  nbatch = 1 is the launch above, with the same grid.
+constexpr int CTDOT_MAX_IN = 16, CTDOT_MAX_GIANT = 64, CTDOT_MAX_BATCH = 16;
 struct CtPtxtDotArgs {
     const u64* x;
     u64* y;
@@ -404,7 +406,7 @@ struct CtPtxtDotArgs {
     long pt_words;
     unsigned int mask[CTDOT_MAX_GIANT];
     unsigned short first[CTDOT_MAX_GIANT];       // (at most 64 * 16 plaintexts)
-    int nin, ngiant, L, N, npolys;
+    int nin, ngiant, L, N, npolys, nbatch;
 };
 void launch_ct_ptxt_dot(const CtPtxtDotArgs& a, hipStream_t st);
 // dst = MForm(src) for count polynomials of L limbs each (limb l under mods[l]); dst may be src

@@ -1225,12 +1225,15 @@ void launch_ct_lincomb(const CtLincombArgs& a, hipStream_t st) {
 // A plaintext word is read once per component, 1 + parties times in all -- from the caches, since the workgroups of one (block of j, limb) run side by
 // side -- and the thread holds 2 NI + 16 VGPRs of operands whatever the number of parties.  Threads that own several components read it once per
 // group at that many times the held inputs; they were measured and not kept.
+// nbatch items that share masks and plaintexts (mkhe_bfv_ct_ptxt_dot) are further rows of the grid: blockIdx.y = item * npolys + polynomial, so that a
+// plaintext word is read (1 + parties) * nbatch times, again from the caches (not measured).
 static_assert(CTDOT_MAX_IN <= 32, "ct_ptxt_dot_kernel: one sum must stay within the 32 products that redc128 accepts for q < 2^60");
 typedef const __attribute__((address_space(4))) CtPtxtDotArgs* ctdot_kargs;
 template <int NI>
 __global__ void __launch_bounds__(PW_THREADS) ct_ptxt_dot_kernel(CtPtxtDotArgs a) {
     ctdot_kargs ka = (ctdot_kargs)__builtin_amdgcn_kernarg_segment_ptr();
-    const int j = blockIdx.x * PW_THREADS + threadIdx.x, p = blockIdx.y;
+    const int j = blockIdx.x * PW_THREADS + threadIdx.x;
+    const int item = blockIdx.y / a.npolys, p = blockIdx.y - item * a.npolys;      // (wave-uniform; item 0 throughout where nbatch = 1)
     if (j >= a.N) return;
     const long PO = (long)a.L * a.N, CO = PO * a.npolys;
     constexpr int CH = NI < 8 ? NI : 8;
@@ -1238,10 +1241,10 @@ __global__ void __launch_bounds__(PW_THREADS) ct_ptxt_dot_kernel(CtPtxtDotArgs a
         const Mod md = load_mod((sc_mod)a.mods + l);
         const long off = (long)l * a.N + j;
         u64 x[NI];
-        long xi = (long)p * PO + off;              // (walked, not b * CO: sixteen hoisted 64-bit offsets would not fit the scalar registers)
+        long xi = (long)item * a.nin * CO + (long)p * PO + off;     // (walked, not b * CO: sixteen hoisted 64-bit offsets would not fit the scalar registers)
 #pragma unroll
         for (int b = 0; b < NI; ++b, xi += CO) x[b] = b < a.nin ? a.x[xi] : 0;
-        long yi = (long)p * PO + off;
+        long yi = (long)item * a.ngiant * CO + (long)p * PO + off;
         for (int g = 0; g < a.ngiant; ++g, yi += CO) {
             const unsigned int m = ka->mask[g];
             const u64* w = a.pt + (long)ka->first[g] * a.pt_words + off;
@@ -1263,15 +1266,16 @@ __global__ void __launch_bounds__(PW_THREADS) ct_ptxt_dot_kernel(CtPtxtDotArgs a
     }
 }
 void launch_ct_ptxt_dot(const CtPtxtDotArgs& a, hipStream_t st) {
-    if (a.nin < 1 || a.nin > CTDOT_MAX_IN || a.ngiant < 1 || a.ngiant > CTDOT_MAX_GIANT || a.npolys < 1 || a.L < 1 || a.pt_words < (long)a.L * a.N)
+    if (a.nin < 1 || a.nin > CTDOT_MAX_IN || a.ngiant < 1 || a.ngiant > CTDOT_MAX_GIANT || a.npolys < 1 || a.L < 1 || a.pt_words < (long)a.L * a.N ||
+        a.nbatch < 1 || a.nbatch > CTDOT_MAX_BATCH || (long)a.npolys * a.nbatch > 65535)
         throw std::runtime_error("mkhe: launch_ct_ptxt_dot: bad shape");
     for (int g = 0; g < a.ngiant; ++g)
         if (!a.mask[g] || (a.mask[g] >> a.nin)) throw std::runtime_error("mkhe: launch_ct_ptxt_dot: bad mask");
     const int bx = (a.N + PW_THREADS - 1) / PW_THREADS;
     // limb groups as in launch_ct_lincomb: until every SIMD of the chip has four waves, at most one group per limb
-    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys;
+    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys * a.nbatch;
     const int groups = (int)std::min<long>(a.L, (fill + threads - 1) / threads);
-    const dim3 grid(bx, a.npolys, groups), blk(PW_THREADS);
+    const dim3 grid(bx, a.npolys * a.nbatch, groups), blk(PW_THREADS);
     if (a.nin > 8) hipLaunchKernelGGL(ct_ptxt_dot_kernel<16>, grid, blk, 0, st, a);
     else if (a.nin > 4) hipLaunchKernelGGL(ct_ptxt_dot_kernel<8>, grid, blk, 0, st, a);
     else hipLaunchKernelGGL(ct_ptxt_dot_kernel<4>, grid, blk, 0, st, a);

@@ -4,13 +4,16 @@ Same names and argument meaning as mkbfv/{params,keys,elements,evaluator,basis_e
 polynomial work runs on the device through the C ABI (include/mkhe.h, mkhe_bfv_* and mkhe_ct_*).
 BFV ciphertexts live at the maximum level in the coefficient domain (elements.go:9-11).
 """
+import collections
 import ctypes as C
+import functools
 import math
 
 import numpy as np
 
 from . import _abi, mkrlwe
 from ._abi import MkheError, check, handle_array, lib
+from .mkckks import PTXT_DOT_MAX_GIANT, linear_transform_plan
 
 
 class Parameters(mkrlwe.Parameters):
@@ -281,6 +284,39 @@ class Evaluator:
         self.ksw.Conjugate(ct0, ckSet, ctOut)
         return ctOut
 
+    # ---- hoisted rotations (the mirror of mkckks.Evaluator.HoistedForm / RotateHoistedNew: every mkrlwe-level call works on a BFV context)
+    def HoistedForm(self, ct):
+        h = mkrlwe.NewHoistedCiphertext()
+        for id in ct.ids:
+            h.Value[id] = mkrlwe.SwitchingKey(self.params, zero=False)          # every digit is written below
+        check(lib().mkhe_hoisted_form(self.params.ctx, ct.Level(), ct.h, handle_array([h.Value[id].h for id in ct.ids])))
+        return h
+
+    def RotateHoistedNew(self, ct0, rotidx, ct0Hoisted, rkSet):
+        """RotateNew from the hoisted form of ct0 (HoistedForm), shared by every rotation of ct0: the same ciphertext bit for bit"""
+        rotidx %= self.params.N() // 2
+        ctOut = NewCiphertext(self.params, ct0.IDSet(), zero=False)
+        if rotidx == 0:
+            check(lib().mkhe_ct_copy(self.params.ctx, ct0.h, ctOut.h))
+            return ctOut
+        if rotidx not in self.params.CRS:
+            raise MkheError("Hoisted rotation only works for precomputed rotation keys")
+        self.ksw.RotateHoisted(ct0, rotidx, ct0Hoisted, rkSet, ctOut)
+        return ctOut
+
+    # ---- plaintext linear transform (no reference counterpart: include/mkhe.h, "BFV plaintext linear transform")
+    def LinearTransformBatch(self, cts, lt, rkSet, ckSet=None, fused=True):
+        """M z for every ciphertext of `cts` (one id set, at most 16) and the cleartext diagonals of `lt` (LinearTransform), by baby steps and giant
+        steps: LT_d(z) + swap(LT_e~(z)), the baby rotations shared by both parts and ONE mkhe_bfv_ct_ptxt_dot for the whole batch.  Keys for
+        lt.Rotations(), and ckSet where lt.NeedsConjugation().  MkheError before any engine call when a CRS, a rotation key or a conjugation key is
+        missing, the id sets differ or lt was built for other parameters.  fused=False runs the same schedule through the single-operation entry
+        points and gives the same ciphertexts bit for bit."""
+        return linear_transform_batch(self, cts, lt, rkSet, ckSet, fused)
+
+    def LinearTransformNew(self, ct, lt, rkSet, ckSet=None, fused=True):
+        """LinearTransformBatch of one ciphertext"""
+        return self.LinearTransformBatch([ct], lt, rkSet, ckSet, fused)[0]
+
     # ---- plaintext operands (no reference counterpart: include/mkhe.h, "BFV plaintext operands").  The result carries the ids of the input: no
     # party is added and no key is used.
     def _encoder(self):
@@ -354,6 +390,225 @@ MULRELIN_SUM_MAX = 16     # pairs per mkhe_bfv_mul_relin_sum call (csrc/poly_ker
 
 def NewEvaluator(params):
     return Evaluator(params)
+
+
+# ---- plaintext linear transforms over Z_T (no reference counterpart; include/mkhe.h, "BFV plaintext linear transform").  A message is two rows of
+# n = N/2 slots, z[r][j]; (M z)[r][j] = sum_k d_k[r][j] z[r][(j+k) mod n] + sum_k e_k[r][j] z[1-r][(j+k) mod n] = LT_d(z) + swap(LT_e~(z)) with
+# e~_k[r] = e_k[1-r].  The construction below is pure (numpy only), so that it can be checked against the defining sum without a context.
+PTXT_DOT_MAX_BATCH = 16                                   # csrc/poly_kernels.h, CTDOT_MAX_BATCH
+CT_SUM_MAX = 16                                           # ciphertexts per mkhe_ct_sum call the transform issues
+LinTransLayout = collections.namedtuple("LinTransLayout", "plan giants_d giants_e order masks rows")
+
+
+def diagonal_rows(diagonals, n, what="diagonals"):
+    """{k: int64 [2][n] or [n]} -> {k mod n: int64 [2][n]}: a [n] array is the same diagonal in both rows"""
+    out = {}
+    for k, d in dict(diagonals or {}).items():
+        d = np.asarray(d)
+        if d.dtype.kind not in "iu":
+            raise MkheError("mkbfv.LinearTransform: %s[%d] must be integers (they are taken mod T)" % (what, k))
+        d = d.astype(np.int64)
+        if d.shape == (n,):
+            d = np.stack([d, d])
+        if d.shape != (2, n):
+            raise MkheError("mkbfv.LinearTransform: %s[%d] must have shape (2, %d) or (%d,), got %r" % (what, k, n, n, d.shape))
+        if int(k) % n in out:
+            raise MkheError("mkbfv.LinearTransform: %s[%d] is given twice (indices are taken mod %d)" % (what, k, n))
+        out[int(k) % n] = d
+    return out
+
+
+def linear_transform_layout(n, diagonals, swapped=None, n1=None):
+    """The plan, the masks and the pre-rotated diagonals of a transform, a pure function.  The plan (mkckks.linear_transform_plan) is taken over the
+    union of both index sets, so that both parts share n1 and the babies.  -> LinTransLayout: giants_d / giants_e the giants of each part, order =
+    [(part, g, b)] and rows = [int64 [2][n]] in the order of the plaintext block (part 0 = d, part 1 = e~; roll(d_(g+b), g) along the slots of each
+    row), masks for [giants of d] + [giants of e~] over the babies of the plan."""
+    d, e = diagonal_rows(diagonals, n), diagonal_rows(swapped, n, "swapped")
+    if not d and not e:
+        raise MkheError("mkbfv.LinearTransform: no diagonal")
+    plan = linear_transform_plan(set(d) | set(e), n, n1)
+    parts = [d, {k: v[::-1] for k, v in e.items()}]                                  # e~_k[r] = e_k[1 - r]
+    giants = [sorted({k - k % plan.n1 for k in p}) for p in parts]
+    if len(giants[0]) + len(giants[1]) > PTXT_DOT_MAX_GIANT:
+        raise MkheError("mkbfv.LinearTransform: more than %d giant steps over the two parts" % PTXT_DOT_MAX_GIANT)
+    order, masks, rows = [], [], []
+    for part, p in enumerate(parts):
+        for g in giants[part]:
+            masks.append(sum(1 << i for i, b in enumerate(plan.babies) if (g + b) in p))
+            for b in plan.babies:
+                if (g + b) in p:
+                    order.append((part, g, b))
+                    rows.append(np.roll(p[g + b], g, axis=1))
+    return LinTransLayout(plan, giants[0], giants[1], order, masks, rows)
+
+
+def matrix_layout(M, n, blocks=False):
+    """(diagonals, swapped) of an integer matrix for n slots per row, the all-zero diagonals left out.  blocks=False: M is d x d and acts on each
+    row, d_k[r][j] = M[j mod d][(j + k) mod d].  blocks=True: M = [[A, B], [C, D]] is 2d x 2d; A and D act within rows 0 and 1, B takes row 1 into
+    row 0 and C row 0 into row 1 (the swapped diagonals).  d a power of two <= n."""
+    M = np.asarray(M)
+    if M.dtype.kind not in "iu":
+        raise MkheError("mkbfv.LinearTransform.FromMatrix: the matrix must hold integers")
+    M = M.astype(np.int64)
+    d = M.shape[0] // 2 if blocks else M.shape[0]
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or (blocks and M.shape[0] != 2 * d) or d < 1 or d & (d - 1) or d > n:
+        raise MkheError("mkbfv.LinearTransform.FromMatrix: the matrix must be d x d (blocks: 2d x 2d) with d a power of two, at most %d" % n)
+    j = np.arange(n)
+    diag = lambda A, k: A[j % d, (j + k) % d]
+    if blocks:
+        A, B, Cm, D = M[:d, :d], M[:d, d:], M[d:, :d], M[d:, d:]
+    else:
+        A, B, Cm, D = M, None, None, M
+    diags = {k: np.stack([diag(A, k), diag(D, k)]) for k in range(d)}
+    swapped = {k: np.stack([diag(B, k), diag(Cm, k)]) for k in range(d)} if blocks else {}
+    diags = {k: v for k, v in diags.items() if v.any()}
+    swapped = {k: v for k, v in swapped.items() if v.any()}
+    if not diags and not swapped:
+        raise MkheError("mkbfv.LinearTransform.FromMatrix: the zero matrix")
+    return diags, swapped
+
+
+class _PlaintextInBlock(mkrlwe.DeviceLimbs):
+    """plaintext `index` of a block of prepared plaintexts, where it lies: what MulPtxtNew takes as a PlaintextMul.  Holds the block, owns nothing."""
+
+    def __init__(self, block, index):
+        self.params, self.count, self.limbs = block.params, 1, block.limbs
+        self.words = block.limbs * block.params.N()
+        self._block = block
+        self.d = C.c_void_p(block.devptr().value + 8 * self.words * index)
+
+    def __del__(self):
+        pass
+
+
+class LinearTransform:
+    """The diagonals of a Z_T-linear map on the two slot rows, encoded once for Evaluator.LinearTransformNew / LinearTransformBatch.  diagonals
+    {k: d_k} keep the rows, swapped {k: e_k} exchange them: (M z)[r][j] = sum_k d_k[r][j] z[r][(j+k) mod n] + sum_k e_k[r][j] z[1-r][(j+k) mod n] --
+    the convention of RotateNew(ct, k), which moves slot j + k to slot j in each row, and of ConjugateNew, which swaps the rows.  Each d_k / e_k is
+    an int64 [2][n] array, or [n] for the same diagonal in both rows.  All pre-rotated diagonals of both parts are encoded in ONE
+    DeviceEncoder.EncodeMulBatch into the compact block of mkhe_bfv_ct_ptxt_dot.  keep_single is accepted for symmetry with mkckks (keep_coeff):
+    the single calls of fused=False address a plaintext inside the block (Plaintext(i)), so nothing more is kept."""
+
+    def __init__(self, params, diagonals, swapped=None, n1=None, keep_single=False):
+        self.params, self.n = params, params.N() // 2
+        lay = linear_transform_layout(self.n, diagonals, swapped, n1)
+        self.plan, self.giants_d, self.giants_e, self.order, self.masks = lay.plan, lay.giants_d, lay.giants_e, lay.order, lay.masks
+        self.keep_single = bool(keep_single)
+        self.pt = DeviceEncoder(params).EncodeMulBatch(np.stack([r.reshape(-1) for r in lay.rows]))
+
+    @classmethod
+    def FromMatrix(cls, params, M, blocks=False, **kw):
+        """blocks=False: the d x d integer matrix M applied to each slot row, as its d-periodic diagonals: on rows whose d entries are replicated
+        n / d times it gives M @ v mod T, replicated.  blocks=True: the 2d x 2d matrix [[A, B], [C, D]] on the pair of rows (matrix_layout)."""
+        diags, swapped = matrix_layout(M, params.N() // 2, blocks)
+        return cls(params, diags, swapped, **kw)
+
+    def Rotations(self):
+        """the sorted non-zero baby and giant indices: what AddCRS / GenRotationKey must have provided"""
+        return sorted({r for r in self.plan.babies + self.giants_d + self.giants_e if r})
+
+    def NeedsConjugation(self):
+        """whether the transform has a row-swapping part: a conjugation key per party and CRS[-2]"""
+        return bool(self.giants_e)
+
+    def Plaintext(self, index):
+        """prepared plaintext `index` of the block (the order of self.order) as a PlaintextMul, read where it lies"""
+        return PlaintextMul(self.params, _PlaintextInBlock(self.pt.Value, index))
+
+
+def linear_transform_batch(ev, cts, lt, rkSet, ckSet=None, fused=True):
+    """Evaluator.LinearTransformBatch.  Launch sets of the fused form for B items: HoistedForm of each item; the non-zero baby rotations of all items
+    as lanes of mkhe_rotate_multi; ONE mkhe_bfv_ct_ptxt_dot; the non-zero giant rotations as lanes of mkhe_rotate_multi; mkhe_ct_sum per part in groups
+    of 16; mkhe_conjugate of the swapped sum; mkhe_ct_add."""
+    params, cts = ev.params, list(cts)
+    if lt.params is not params:
+        raise MkheError("LinearTransform: the transform was encoded for other parameters")
+    if not cts or len(cts) > PTXT_DOT_MAX_BATCH:
+        raise MkheError("LinearTransformBatch: takes 1 to %d ciphertexts" % PTXT_DOT_MAX_BATCH)
+    ids = cts[0].ids
+    for ct in cts:
+        if ct.ids != ids:
+            raise MkheError("LinearTransformBatch: the ciphertexts of one call must be over the same ids")
+    keys = {}
+    for r in lt.Rotations():
+        if r not in params.CRS:
+            raise MkheError("LinearTransform: no CRS for rotation index %d" % r)
+        keys[r] = [rkSet.GetRotationKey(i, r).Value.h for i in ids]           # (MkheError when a party has none)
+    if lt.NeedsConjugation():
+        if ckSet is None:
+            raise MkheError("LinearTransform: the transform swaps the slot rows: pass the conjugation keys (ckSet)")
+        if -2 not in params.CRS:
+            raise MkheError("LinearTransform: no CRS for the conjugation (CRS[-2])")
+        for i in ids:
+            ckSet.GetConjugationKey(i)
+    L, ctx, B = lib(), params.ctx, len(cts)
+    babies, giants = lt.plan.babies, lt.giants_d + lt.giants_e
+    nd = len(lt.giants_d)
+    new = lambda: NewCiphertext(params, ids, zero=False)
+    hoisted = [ev.HoistedForm(ct) if any(babies) else None for ct in cts]
+
+    def summed(terms):
+        while len(terms) > 1:
+            groups = [terms[i: i + CT_SUM_MAX] for i in range(0, len(terms), CT_SUM_MAX)]
+            terms = []
+            for grp in groups:
+                terms.append(new())
+                check(L.mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), terms[-1].h))
+        return terms[0]
+
+    def finish(part_d, part_e, add_all):
+        """LT_d + swap(LT_e~) from the rotated inner sums of each part"""
+        total = add_all(part_d) if part_d else None
+        if part_e:
+            sw = ev.ConjugateNew(add_all(part_e), ckSet)
+            total = sw if total is None else ev.AddNew(total, sw)
+        return total
+
+    if not fused:
+        outs = []
+        for ct, h in zip(cts, hoisted):
+            rot = {b: ev.RotateHoistedNew(ct, b, h, rkSet) if b else ct for b in babies}
+            terms, index = [], 0
+            for g, mask in zip(giants, lt.masks):
+                part = None
+                for i, b in enumerate(babies):
+                    if mask >> i & 1:
+                        prod = ev.MulPtxtNew(rot[b], lt.Plaintext(index))
+                        part = prod if part is None else ev.AddNew(part, prod)
+                        index += 1
+                terms.append(ev.RotateNew(part, g, rkSet) if g else part)
+            outs.append(finish(terms[:nd], terms[nd:], lambda t: functools.reduce(ev.AddNew, t)))
+        return outs
+
+    def rotate_lanes(srcs, rots, hoists):
+        """srcs[i] rotated by rots[i] != 0 as lanes of one mkhe_rotate_multi; hoists: one hoisted form per lane, or None"""
+        outs = mkrlwe.batch_ciphertexts(Ciphertext, params, ids, params.MaxLevel(), len(srcs)) if len(srcs) > 1 else [new()]
+        gal = (C.c_uint64 * len(rots))(*[params.GaloisElementForColumnRotationBy(r) for r in rots])
+        hs = handle_array([h.Value[i].h for h in hoists for i in ids]) if hoists is not None else None
+        check(L.mkhe_rotate_multi(ctx, len(rots), gal, handle_array([c.h for c in srcs]), hs, handle_array([h for r in rots for h in keys[r]]),
+                                  handle_array([params.CRS[r].h for r in rots]), None, handle_array([o.h for o in outs])))
+        return outs
+
+    nzb = [b for b in babies if b]
+    rot = [{0: ct} for ct in cts]
+    if nzb:
+        lanes = rotate_lanes([ct for ct in cts for _ in nzb], nzb * B, [h for h in hoisted for _ in nzb])
+        for k in range(B):
+            rot[k].update(zip(nzb, lanes[k * len(nzb): (k + 1) * len(nzb)]))
+    inner = mkrlwe.batch_ciphertexts(Ciphertext, params, ids, params.MaxLevel(), B * len(giants)) if B * len(giants) > 1 else [new()]
+    masks = (C.c_uint32 * len(giants))(*lt.masks)
+    check(L.mkhe_bfv_ct_ptxt_dot(ctx, B, len(babies), handle_array([rot[k][b].h for k in range(B) for b in babies]), len(giants), masks,
+                                 lt.pt.Value.devptr(), handle_array([c.h for c in inner])))
+    nz = [(k, j) for k in range(B) for j, g in enumerate(giants) if g]
+    if nz:
+        lanes = rotate_lanes([inner[k * len(giants) + j] for k, j in nz], [giants[j] for _, j in nz], None)
+        for (k, j), c in zip(nz, lanes):
+            inner[k * len(giants) + j] = c
+    outs = []
+    for k in range(B):
+        terms = inner[k * len(giants): (k + 1) * len(giants)]
+        outs.append(finish(terms[:nd], terms[nd:], summed))
+    return outs
 
 
 # ---- encoder, encryptor, decryptor (mkbfv/encryptor.go, mkbfv/decryptor.go, elements.go:26-28); plaintexts are RNS polynomials over Q.
