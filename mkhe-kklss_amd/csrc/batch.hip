@@ -43,6 +43,17 @@ void no_cross_alias(const std::vector<const Ct*>& ins, const std::vector<Ct*>& o
             if (j != k && ins[j] && outs[k] && ins[j]->d == outs[k]->d)
                 throw Error(std::string("mkhe: output ") + std::to_string(k) + " of the batch is input " + std::to_string(j) + " of another item (" + what + ")");
 }
+// the two sides of a staged list transform (Context::ntt_items): the ciphertexts of a list, and n items `stride` words apart in a staging block
+template <class P, class C> std::vector<P> data(const std::vector<C*>& v) {
+    std::vector<P> r;
+    for (const C* c : v) r.push_back(c->d);
+    return r;
+}
+template <class P> std::vector<P> strided(P w, size_t n, size_t stride) {
+    std::vector<P> r(n);
+    for (size_t i = 0; i < n; ++i) r[i] = w + i * stride;
+    return r;
+}
 }  // namespace
 
 void Context::hoisted_form_batch(int level, const std::vector<const Ct*>& cts, const std::vector<Swk*>& outs) {
@@ -233,14 +244,8 @@ void Context::mul_relin_batch(const std::vector<const Ct*>& op0, const std::vect
     if (!hoist0.empty() && hoist0.size() != B * (size_t)n0) throw Error("mkhe: mul_relin_batch: one hoisted form per party component of op0");
     if (!hoist1.empty() && hoist1.size() != B * (size_t)n1) throw Error("mkhe: mul_relin_batch: one hoisted form per party component of op1");
     // out ids = the union of the operand id sets (newCiphertextBinary, mkckks/evaluator.go:306-313)
-    std::vector<int> slot0(n0), slot1(n1);
-    {
-        auto find = [&](int id) { for (int o = 0; o < nout; ++o) if (o0.ids[o] == id) return o; return -1; };
-        std::vector<char> seen(nout, 0);
-        for (int a = 0; a < n0; ++a) { const int o = find(op0[0]->ids[a]); if (o < 0) throw Error("mkhe: ctOut lacks an id of op0"); slot0[a] = o; seen[o] = 1; }
-        for (int a = 0; a < n1; ++a) { const int o = find(op1[0]->ids[a]); if (o < 0) throw Error("mkhe: ctOut lacks an id of op1"); slot1[a] = o; seen[o] = 1; }
-        for (int o = 0; o < nout; ++o) if (!seen[o]) throw Error("mkhe: ctOut has an id that neither operand has");
-    }
+    std::vector<int> slot0, slot1;
+    union_slots(*op0[0], *op1[0], o0, "mkhe: ctOut", slot0, slot1);
     for (int a = 0; a < n0; ++a) if (!rlk_d0[a] || !rlk_v0[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     for (int a = 0; a < n1; ++a) if (!rlk_b1[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     // N >= 2^15: one evaluation fills the chip with every big kernel, and B of them in lock step only lengthen those kernels (PN15QP880, four parties:
@@ -312,23 +317,15 @@ void Context::mul_relin_batch(const std::vector<const Ct*>& op0, const std::vect
         // (both sides as the items of ONE launch when they have one shape: twice the limbs per launch -- on the small rings that is what
         // takes it over the threshold of the H16-class kernel, one launch for both modulus classes instead of four of the round-1 kernel)
         const bool both = !same && P0 == P1 && nn0 == nn1;
-        struct It { const u64* s; u64* d; };
         for (int side = 0; side < (same || both ? 1 : 2); ++side) {
             const int n = side ? nn1 : nn0;
-            std::vector<It> its;
+            std::vector<const u64*> src; std::vector<u64*> dst;
             for (size_t b = 0; b < B; ++b) {
-                if (both || side == 0) its.push_back(It{op0[b]->d, nb_[b]});
-                if (both || side == 1) its.push_back(It{op1[b]->d, nb_[b] + (size_t)(1 + n0) * PO});
+                if (both || side == 0) { src.push_back(op0[b]->d); dst.push_back(nb_[b]); }
+                if (both || side == 1) { src.push_back(op1[b]->d); dst.push_back(nb_[b] + (size_t)(1 + n0) * PO); }
             }
-            for (size_t base = 0; base < its.size(); base += NTT_MAX_ITEMS) {
-                const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, its.size() - base);
-                NttBatch b{};
-                b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_q_owned(b, L);
-                b.src_inner = b.dst_inner = N; b.src_outer = (long)(side ? P1 : P0); b.dst_outer = (long)PO;
-                b.nitems = cnt; b.outers_per_item = 1 + n; b.nouter = cnt * (1 + n);
-                for (int i = 0; i < cnt; ++i) { b.src_items[i] = its[base + i].s; b.dst_items[i] = its[base + i].d; }
-                ntt_fwd_launch(b, false);
-            }
+            // (this function refuses a context that owns a subset of the moduli: the owned Q limbs below L are all of them)
+            ntt_items(false, src, (long)(side ? P1 : P0), dst, (long)PO, 1 + n, L);
         }
     }
     {
@@ -377,13 +374,9 @@ void Context::mul_relin_batch(const std::vector<const Ct*>& op0, const std::vect
                 }
                 continue;
             }
-            for (size_t b = 0; b < B; ++b) {
-                InnerProductArgs ip{};
-                for (int a = 0; a < n; ++a) { ip.a[a] = (side ? rlk_b1[a] : rlk_d0[a])->d; ip.b[a] = side ? h1[b * n1 + a] : h0[b * n0 + a]; }
-                ip.out = side ? y[b] : x[b]; ip.mods = d_mods; ip.map = map_qp(level);
-                ip.term_outer = ip.out_outer = (long)mtot * N; ip.nterms = n; ip.nslots = nslots; ip.nouter = nbt; ip.N = N; ip.mform_out = 1;
-                { ProfScope ps(this, PROF_INNER, 8.0 * N * nslots * nbt * (2.0 * n + 1)); launch_inner_product(ip, s_); }
-            }
+            std::vector<const u64*> keys(n);
+            for (int a = 0; a < n; ++a) keys[a] = (side ? rlk_b1[a] : rlk_d0[a])->d;
+            for (size_t b = 0; b < B; ++b) key_inner_product(keys.data(), side ? &h1[b * n1] : &h0[b * n0], n, side ? y[b] : x[b], level, nbt, true);
         }
     }
     // ---- step F1: t_i = <h(c0_i), y>_P (:165-169), every input in one batch (whole inputs per launch: with fuse_x the thread that holds input
@@ -549,93 +542,12 @@ void Context::bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& in
     const size_t PO = (size_t)L * N;
     Arena ar(this, B * np_ * PO);
     u64* w = ar.take(B * np_ * PO);
-    for (size_t base = 0; base < B; base += NTT_MAX_ITEMS) {
-        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, B - base);
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d; b.dst_items[i] = w + (base + i) * np_ * PO; }
-        ntt_fwd_launch(b, false);
-    }
+    ntt_items(false, data<const u64*>(ins), (long)PO, strided(w, B, np_ * PO), (long)PO, np_, L);
     {
         ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (2.0 * B * np_ + (pt_stride ? (double)B : 1.0)));
         launch_bf_mul_prepared(w, ptmul, pt_stride, d_mods, L, N, np_, (int)(B * np_), s_);
     }
-    for (size_t base = 0; base < B; base += NTT_MAX_ITEMS) {
-        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, B - base);
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = w + (base + i) * np_ * PO; b.dst_items[i] = outs[base + i]->d; }
-        { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
-    }
-    MKHE_HIP(hipGetLastError());
-}
-
-// outs[b * ngiant + g] = sum over the set bits i of masks[g] of ins[b * nin + i] * P(g, i) for B items that share masks and plaintexts: the forward NTT
-// of all B nin (1 + k) components (64 ciphertexts per launch), launch_ct_ptxt_dot with the item in its grid, the inverse NTT into the outputs.  ptmul is
-// the block of ONE bfv_encode_mul(count = nnz), read where it lies.  Bytes of the middle kernel: 8 N nQ (1 + k) B (nin + nnz + ngiant), of which
-// 8 N nQ nnz are first reads of the plaintexts and the other ((1 + k) B - 1) of them re-reads (poly_kernels.hip).  Every refusal comes before the
-// first launch.
-void Context::bfv_ct_ptxt_dot(const char* what, int nbatch, const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptmul,
-                              const std::vector<Ct*>& outs) {
-    bf_init(what);
-    const std::string w = std::string(what) + ": ";
-    const int B = nbatch, ngiant = (int)masks.size(), nin = B > 0 ? (int)ins.size() / B : 0;
-    if (B < 1 || B > CTDOT_MAX_BATCH) throw Error(w + "nbatch must be 1 .. " + std::to_string(CTDOT_MAX_BATCH));
-    if (nin < 1 || nin > CTDOT_MAX_IN || (size_t)nin * B != ins.size()) throw Error(w + "nin must be 1 .. " + std::to_string(CTDOT_MAX_IN));
-    if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT || (size_t)ngiant * B != outs.size()) throw Error(w + "ngiant must be 1 .. " + std::to_string(CTDOT_MAX_GIANT));
-    if (!ptmul) throw Error(w + "null argument");
-    CtPtxtDotArgs a{};
-    int nnz = 0;
-    for (int g = 0; g < ngiant; ++g) {
-        const unsigned int m = masks[g];
-        if (!m) throw Error(w + "a mask is zero");
-        if (m >> nin) throw Error(w + "a mask has a bit at or above nin");
-        a.mask[g] = m; a.first[g] = (unsigned short)nnz;
-        nnz += __builtin_popcount(m);
-    }
-    const Ct& c0 = *ins[0];
-    const int L = nq, np_ = 1 + c0.n;
-    const size_t PO = (size_t)L * N, CO = (size_t)np_ * PO;
-    for (const Ct* c : ins) {
-        if (c->limbs != nq) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
-        if (c->n != c0.n || c->ids != c0.ids) throw Error(w + "the ciphertexts of a list must share their ids");
-    }
-    for (size_t o = 0; o < outs.size(); ++o) {
-        if (outs[o]->limbs != nq) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
-        if (outs[o]->n != c0.n || outs[o]->ids != c0.ids) throw Error(w + "an output must carry the ids of the inputs");
-        for (size_t h = 0; h < o; ++h)
-            if (outs[o]->d < outs[h]->d + CO && outs[h]->d < outs[o]->d + CO) throw Error(w + "the outputs must be distinct");
-        for (const Ct* c : ins)
-            if (c->d < outs[o]->d + CO && outs[o]->d < c->d + CO) throw Error(w + "an output must not alias an input");
-    }
-    if ((size_t)B * np_ > 65535) throw Error(w + "more than 65535 polynomials in one call");
-    Arena ar(this, (ins.size() + outs.size()) * CO);
-    u64* x = ar.take(ins.size() * CO); u64* y = ar.take(outs.size() * CO);
-    for (size_t base = 0; base < ins.size(); base += NTT_MAX_ITEMS) {
-        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, ins.size() - base);
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d; b.dst_items[i] = x + (base + i) * CO; }
-        ntt_fwd_launch(b, false);
-    }
-    a.x = x; a.y = y; a.pt = ptmul; a.mods = d_mods; a.pt_words = (long)PO;
-    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_; a.nbatch = B;
-    { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * B * (nin + nnz + ngiant)); launch_ct_ptxt_dot(a, s_); }
-    for (size_t base = 0; base < outs.size(); base += NTT_MAX_ITEMS) {
-        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, outs.size() - base);
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = y + (base + i) * CO; b.dst_items[i] = outs[base + i]->d; }
-        { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
-    }
+    ntt_items(true, strided<const u64*>(w, B, np_ * PO), (long)PO, data<u64*>(outs), (long)PO, np_, L);
     MKHE_HIP(hipGetLastError());
 }
 
@@ -687,26 +599,10 @@ void Context::ct_mul_ptxt_batch(const std::vector<const Ct*>& ins, const u64* de
     Arena ar(this, (1 + 2 * B * np_) * PO);
     u64* pt = ar.take(PO); u64* w = ar.take(B * np_ * PO); u64* w2 = ar.take(B * np_ * PO);
     ntt(dev_pt, pt, 1, L, 0, false, false);
-    for (size_t base = 0; base < B; base += NTT_MAX_ITEMS) {
-        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, B - base);
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-        b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = ins[base + i]->d; b.dst_items[i] = w + (base + i) * np_ * PO; }
-        ntt_fwd_launch(b, false);
-    }
+    ntt_items(false, data<const u64*>(ins), (long)PO, strided(w, B, np_ * PO), (long)PO, np_, L);
     { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * (2.0 * B * np_ + 1)); launch_mul_by_poly(w, w, pt, d_mods, L, N, (int)(B * np_), s_); }
     if (nb == 0) {
-        for (size_t base = 0; base < B; base += NTT_MAX_ITEMS) {
-            const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, B - base);
-            NttBatch b{};
-            b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
-            b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-            b.nitems = cnt; b.outers_per_item = np_; b.nouter = cnt * np_;
-            for (int i = 0; i < cnt; ++i) { b.src_items[i] = w + (base + i) * np_ * PO; b.dst_items[i] = outs[base + i]->d; }
-            { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
-        }
+        ntt_items(true, strided<const u64*>(w, B, np_ * PO), (long)PO, data<u64*>(outs), (long)PO, np_, L);
         return;
     }
     ntt(w, w, (int)(B * np_), L, 0, true, false);
@@ -750,69 +646,59 @@ void Context::ptxt_prepare(int limbs, int count, const u64* pt, u64* ptntt) {
     MKHE_HIP(hipGetLastError());
 }
 
-// outs[g] = sum over the set bits b of masks[g] of ins[b] * P(g, b): one forward launch over every component of every input (their first L limbs),
-// launch_ct_ptxt_dot, one inverse launch into the outputs.  Bytes of the middle kernel: 8 N L [(1 + k) nin + (1 + k) nnz + (1 + k) ngiant], of which
-// 8 N L k nnz are re-reads of plaintext words by the other components (poly_kernels.hip).  The temporaries are one pooled block; masks and offsets
-// are kernel arguments: nothing is allocated from the driver after a first call of the shape and nothing is uploaded, so the call may be captured.
-void Context::ct_ptxt_dot(const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptntt, int pt_limbs, const std::vector<Ct*>& outs) {
-    const std::string w = "mkhe_ct_ptxt_dot: ";
-    if (is_bfv()) throw Error(w + "needs a CKKS context");
-    if (masked()) throw Error(w + "not available on a context that owns a subset of the moduli");
-    const int nin = (int)ins.size(), ngiant = (int)outs.size();
-    if (nin < 1 || nin > CTDOT_MAX_IN) throw Error(w + "takes 1 to " + std::to_string(CTDOT_MAX_IN) + " input ciphertexts");
-    if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT) throw Error(w + "takes 1 to " + std::to_string(CTDOT_MAX_GIANT) + " outputs");
-    if ((int)masks.size() != ngiant) throw Error(w + "one mask per output");
-    if (!ptntt) throw Error(w + "null plaintext block");
-    const Ct& o0 = *outs[0];
-    const int L = o0.limbs, np_ = 1 + o0.n;
-    if (L < 1 || L > nq) throw Error(w + "the outputs' limb count lies outside the moduli of Q");
-    if (pt_limbs < L) throw Error(w + "the prepared plaintexts have fewer limbs than the outputs");
-    const size_t PO = (size_t)L * N;
-    for (const Ct* o : outs)
-        if (o->limbs != L || o->n != o0.n || o->ids != o0.ids) throw Error(w + "the outputs must have one shape");
-    for (int g = 0; g < ngiant; ++g)
-        for (int h = 0; h < g; ++h)
-            if (outs[g]->d < outs[h]->d + np_ * PO && outs[h]->d < outs[g]->d + np_ * PO) throw Error(w + "the outputs must be distinct");
-    for (const Ct* c : ins) {
-        if (c->n != o0.n || c->ids != o0.ids) throw Error(w + "every input and output must carry the same ids");
-        if (c->limbs < L) throw Error(w + "an input has fewer limbs than the outputs");
-        for (const Ct* o : outs)
-            if (c->d < o->d + np_ * PO && o->d < c->d + (size_t)np_ * c->limbs * N) throw Error(w + "an output must not alias an input");
-    }
+// outs[b * ngiant + g] = sum over the set bits i of masks[g] of ins[b * nin + i] * P(g, i) for nbatch items that share masks and plaintexts
+// (mkhe_ct_ptxt_dot: one item; mkhe_bfv_ct_ptxt_dot): the forward NTT of the first L limbs of every component of every input (64 ciphertexts per
+// launch), launch_ct_ptxt_dot with the item in its grid, the inverse NTT into the outputs.  Bytes of the middle kernel: 8 N L (1 + k) nbatch
+// (nin + nnz + ngiant), of which 8 N L nnz are first reads of the plaintexts and the other ((1 + k) nbatch - 1) of them re-reads (poly_kernels.hip).
+// The temporaries are one pooled block; masks and offsets are kernel arguments: nothing is allocated from the driver after a first call of the shape
+// and nothing is uploaded, so the call may be captured.  Every refusal comes before the first launch.
+void Context::ct_ptxt_dot(const char* what, int nbatch, const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* pt,
+                          long pt_words, int L, const std::vector<Ct*>& outs) {
+    const std::string w = std::string(what) + ": ";
+    const int B = nbatch, ngiant = (int)masks.size(), nin = B > 0 ? (int)ins.size() / B : 0;
+    if (B < 1 || B > CTDOT_MAX_BATCH) throw Error(w + "nbatch must be 1 .. " + std::to_string(CTDOT_MAX_BATCH));
+    if (nin < 1 || nin > CTDOT_MAX_IN || (size_t)nin * B != ins.size()) throw Error(w + "nin must be 1 .. " + std::to_string(CTDOT_MAX_IN));
+    if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT || (size_t)ngiant * B != outs.size()) throw Error(w + "ngiant must be 1 .. " + std::to_string(CTDOT_MAX_GIANT));
+    if (!pt) throw Error(w + "null argument");
     CtPtxtDotArgs a{};
     int nnz = 0;
     for (int g = 0; g < ngiant; ++g) {
         const unsigned int m = masks[g];
         if (!m) throw Error(w + "a mask is zero");
-        if (m >> nin) throw Error(w + "a mask has a bit at or above the number of inputs");
+        if (m >> nin) throw Error(w + "a mask has a bit at or above nin");
         a.mask[g] = m; a.first[g] = (unsigned short)nnz;
         nnz += __builtin_popcount(m);
     }
-    Arena ar(this, (size_t)(nin + ngiant) * np_ * PO);
-    u64* x = ar.take((size_t)nin * np_ * PO); u64* y = ar.take((size_t)ngiant * np_ * PO);
-    // inputs above the outputs' level have their own word stride between polynomials: one launch per run of inputs with the same limb count
-    for (int b0 = 0; b0 < nin;) {
-        int b1 = b0 + 1;
-        while (b1 < nin && ins[b1]->limbs == ins[b0]->limbs) ++b1;
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = (long)ins[b0]->limbs * N; b.dst_outer = (long)PO;
-        b.nitems = b1 - b0; b.outers_per_item = np_; b.nouter = (b1 - b0) * np_;
-        for (int i = b0; i < b1; ++i) { b.src_items[i - b0] = ins[i]->d; b.dst_items[i - b0] = x + (size_t)i * np_ * PO; }
-        ntt_fwd_launch(b, false);
+    const Ct& c0 = *ins[0];
+    const int np_ = 1 + c0.n;
+    const size_t PO = (size_t)L * N, CO = (size_t)np_ * PO;
+    for (const Ct* c : ins) {
+        if (c->n != c0.n || c->ids != c0.ids) throw Error(w + "the ciphertexts of a list must share their ids");
+        if (c->limbs < L) throw Error(w + "an input has fewer limbs than the outputs");
+    }
+    for (size_t o = 0; o < outs.size(); ++o) {
+        if (outs[o]->n != c0.n || outs[o]->ids != c0.ids) throw Error(w + "an output must carry the ids of the inputs");
+        if (outs[o]->limbs != L) throw Error(w + "the outputs must have one shape");
+        for (size_t h = 0; h < o; ++h)
+            if (outs[o]->d < outs[h]->d + CO && outs[h]->d < outs[o]->d + CO) throw Error(w + "the outputs must be distinct");
+        for (const Ct* c : ins)         // (an input above the outputs' level is longer than they are)
+            if (c->d < outs[o]->d + CO && outs[o]->d < c->d + (size_t)np_ * c->limbs * N) throw Error(w + "an output must not alias an input");
+    }
+    if ((size_t)B * np_ > 65535) throw Error(w + "more than 65535 polynomials in one call");
+    Arena ar(this, (ins.size() + outs.size()) * CO);
+    u64* x = ar.take(ins.size() * CO); u64* y = ar.take(outs.size() * CO);
+    // inputs above the outputs' level have their own word stride between polynomials: one list transform per run of inputs with the same limb count
+    for (size_t b0 = 0; b0 < ins.size();) {
+        size_t b1 = b0 + 1;
+        while (b1 < ins.size() && ins[b1]->limbs == ins[b0]->limbs) ++b1;
+        const std::vector<const Ct*> run(ins.begin() + b0, ins.begin() + b1);
+        ntt_items(false, data<const u64*>(run), (long)ins[b0]->limbs * N, strided(x + b0 * CO, b1 - b0, CO), (long)PO, np_, L);
         b0 = b1;
     }
-    a.x = x; a.y = y; a.pt = ptntt; a.mods = d_mods; a.pt_words = (long)pt_limbs * N;
-    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_; a.nbatch = 1;
-    { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * (nin + nnz + ngiant)); launch_ct_ptxt_dot(a, s_); }
-    {
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psiinv; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)PO;
-        b.nitems = ngiant; b.outers_per_item = np_; b.nouter = ngiant * np_;
-        for (int g = 0; g < ngiant; ++g) { b.src_items[g] = y + (size_t)g * np_ * PO; b.dst_items[g] = outs[g]->d; }
-        { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
-    }
+    a.x = x; a.y = y; a.pt = pt; a.mods = d_mods; a.pt_words = pt_words;
+    a.nin = nin; a.ngiant = ngiant; a.L = L; a.N = N; a.npolys = np_; a.nbatch = B;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * B * (nin + nnz + ngiant)); launch_ct_ptxt_dot(a, s_); }
+    ntt_items(true, strided<const u64*>(y, outs.size(), CO), (long)PO, data<u64*>(outs), (long)PO, np_, L);
     MKHE_HIP(hipGetLastError());
 }
 

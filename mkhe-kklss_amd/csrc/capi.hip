@@ -691,13 +691,22 @@ int mkhe_ptxt_prepare(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, v
 int mkhe_ct_ptxt_dot(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int ngiant, const uint32_t* masks, const void* dev_ptntt, int pt_limbs,
                      mkhe_ct* const* out) {
     MKHE_TRY({
-        if (!ctx) throw Error("mkhe_ct_ptxt_dot: null context");
-        if (nin < 1 || nin > CTDOT_MAX_IN) throw Error("mkhe_ct_ptxt_dot: takes 1 to " + std::to_string(CTDOT_MAX_IN) + " input ciphertexts");
-        if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT) throw Error("mkhe_ct_ptxt_dot: takes 1 to " + std::to_string(CTDOT_MAX_GIANT) + " outputs");
-        if (!masks || !dev_ptntt) throw Error("mkhe_ct_ptxt_dot: null argument");
-        auto i = ct_list(ctx, in, nin, "mkhe_ct_ptxt_dot");
-        auto o = ct_list_out(ctx, out, ngiant, "mkhe_ct_ptxt_dot");
-        need(ctx)->ct_ptxt_dot(i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptntt, pt_limbs, o);
+        const char* what = "mkhe_ct_ptxt_dot";
+        const std::string w = std::string(what) + ": ";
+        if (!ctx) throw Error(w + "null context");
+        if (nin < 1 || nin > CTDOT_MAX_IN) throw Error(w + "takes 1 to " + std::to_string(CTDOT_MAX_IN) + " input ciphertexts");
+        if (ngiant < 1 || ngiant > CTDOT_MAX_GIANT) throw Error(w + "takes 1 to " + std::to_string(CTDOT_MAX_GIANT) + " outputs");
+        if (!masks || !dev_ptntt) throw Error(w + "null argument");
+        auto i = ct_list(ctx, in, nin, what);
+        auto o = ct_list_out(ctx, out, ngiant, what);
+        Context* c = need(ctx);
+        scheme_ok(c, what, false, ": needs a CKKS context");
+        unmasked(c, what);
+        // the outputs set the level; inputs and plaintexts may sit above it (the call may be captured: nothing here allocates, stages or synchronises)
+        const int L = o[0]->limbs;
+        if (L < 1 || L > c->nq) throw Error(w + "the outputs' limb count lies outside the moduli of Q");
+        if (pt_limbs < L) throw Error(w + "the prepared plaintexts have fewer limbs than the outputs");
+        c->ct_ptxt_dot(what, 1, i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptntt, (long)pt_limbs * c->N, L, o);
     })
 }
 int mkhe_ct_binary_batch(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* op0, const mkhe_ct* const* op1, mkhe_ct* const* out) {
@@ -1003,7 +1012,7 @@ static void refresh_share_entry(mkhe_ctx* ctx, const char* what, bool bfv, int c
     }
     commit(c, [&] {
         if (!bfv) return;
-        c->bfv_refresh_prepare(what);                                           // T outside the encoder's preconditions: refused here
+        c->bfv_prepare(what);                                           // T outside the encoder's preconditions: refused here
         const int most = c->bfv_refresh_max_flood();
         if (flood_bits > most)
             throw Error(w + ": flood_bits must be at most bitlen(Q div 2T) - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
@@ -1064,7 +1073,7 @@ static void refresh_merge_entry(mkhe_ctx* ctx, const char* what, bool bfv, int c
             re[(size_t)i * count + b] = r->c.d;
         }
     }
-    commit(c, [&] { if (bfv) c->bfv_refresh_prepare(what); });
+    commit(c, [&] { if (bfv) c->bfv_prepare(what); });
     auto i = ct_list(ctx, in, count, what);
     if (nshares > 0) ct_list(ctx, reenc, nshares * count, what);
     ct_list_out(ctx, out, count, what);
@@ -1274,7 +1283,10 @@ int mkhe_bfv_ct_ptxt_dot(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* cons
         commit(c);
         auto i = ct_list(ctx, in, nbatch * nin, what);
         auto o = ct_list_out(ctx, out, nbatch * ngiant, what);
-        c->bfv_ct_ptxt_dot(what, nbatch, i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptmul, o);
+        c->bfv_prepare(what);
+        for (const Ct* x : i) if (x->limbs != c->nq) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
+        for (const Ct* x : o) if (x->limbs != c->nq) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
+        c->ct_ptxt_dot(what, nbatch, i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptmul, (long)c->nq * c->N, c->nq, o);
     })
 }
 int mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out) {

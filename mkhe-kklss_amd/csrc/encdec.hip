@@ -209,17 +209,10 @@ void Context::share_gather_ntt(const std::vector<const Ct*>& ins, const int* slo
 }
 
 void Context::gather_ntt(const std::vector<const u64*>& src, int L, u64* w) {
-    const int count = (int)src.size();
     const size_t pw = (size_t)L * N;
-    for (int base = 0; base < count; base += NTT_MAX_ITEMS) {
-        const int cnt = std::min(NTT_MAX_ITEMS, count - base);
-        NttBatch b{};
-        b.mods = d_mods; b.psi = d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
-        b.src_inner = b.dst_inner = N; b.src_outer = b.dst_outer = (long)pw;
-        b.nitems = cnt; b.outers_per_item = 1; b.nouter = cnt;
-        for (int i = 0; i < cnt; ++i) { b.src_items[i] = src[base + i]; b.dst_items[i] = w + (size_t)(base + i) * pw; }
-        ntt_fwd_launch(b, false);
-    }
+    std::vector<u64*> dst(src.size());
+    for (size_t b = 0; b < dst.size(); ++b) dst[b] = w + b * pw;
+    ntt_items(false, src, (long)pw, dst, (long)pw, 1, L);
 }
 
 void Context::decrypt_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce, int bits, u64* shares) {

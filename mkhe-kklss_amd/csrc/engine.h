@@ -133,7 +133,6 @@ class Context {
                         u64* x1, u64* x2, u64* y1, u64* y2, bool fuse_x = false, bool fuse_y = false);
     void bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u64* x2, const u64* y1, const u64* y2,
                        const Swk* const* rlk_v, const Swk& crs_u, Ct& out);
-    void bfv_slots(const Ct& op0, const Ct& op1, const Ct& out, std::vector<int>& slot0, std::vector<int>& slot1) const;
     void mul_relin_rescale(const Ct& op0, const Ct& op1, const Swk* const* hoist0, const Swk* const* hoist1, const Swk* const* rlk_b1,
                            const Swk* const* rlk_d0, const Swk* const* rlk_v0, const Swk& crs_u, Ct& out);
     void bfv_mul_relin_unhoisted(const Ct& op0, const Ct& op1, const Swk* const* rlk_b1, const Swk* const* rlk_b2,
@@ -195,9 +194,12 @@ class Context {
     // (no reference counterpart).  dev_consts: device uint64[n + 1][2][Lc], Lc = out.limbs + nb_rescale (poly_kernels.h, CtLincombArgs)
     void ct_lincomb(const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, Ct& out);
     // plaintext linear transform (no reference counterpart; batch.hip): ptntt = MForm(NTT(pt)) for count plaintexts [limbs][N] (ptntt may be pt), and
-    // outs[g] = sum over the set bits b of masks[g] of ins[b] * P(g, b), the prepared plaintexts compact in (g, b) order at ptntt with pt_limbs limbs each
+    // the dot of both schemes for nbatch items that share masks and plaintexts: outs[b][g] = sum over the set bits i of masks[g] of ins[b][i] * P(g, i),
+    // ins = [nbatch][nin] with at least L limbs, outs = [nbatch][masks.size()] with L limbs, pt = the compact block of prepared plaintexts in (g, i)
+    // order, pt_words apart.  Every refusal is under `what` (the C entry point) and comes before the first launch
     void ptxt_prepare(int limbs, int count, const u64* pt, u64* ptntt);
-    void ct_ptxt_dot(const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptntt, int pt_limbs, const std::vector<Ct*>& outs);
+    void ct_ptxt_dot(const char* what, int nbatch, const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* pt, long pt_words,
+                     int L, const std::vector<Ct*>& outs);
     void ct_binary_batch(int op, const std::vector<const Ct*>& a, const std::vector<const Ct*>& b, const std::vector<Ct*>& outs);
     // MulPtxtNew body (ct_mul_ptxt) for the batch, followed by nb >= 0 divisions by the last modulus (outs have limbs(in) - nb limbs)
     void ct_mul_ptxt_batch(const std::vector<const Ct*>& ins, const u64* dev_pt, int nb, const std::vector<Ct*>& outs);
@@ -209,6 +211,11 @@ class Context {
     // stage_only (alpha = 1, N = 2^14, engine-internal): digit spread + the three cross stages only -- the digits are then consumed by ext_batch through
     // ext_fused_lds_kernel (ExtFuse::staged names them), which finishes the transform in LDS and multiplies in the same kernel (ntt_kernels.h, ExtFusedArgs)
     void decompose_batch(int level, const std::vector<const u64*>& src, const std::vector<u64*>& dst, bool internal = false, bool stage_only = false);
+    // the staged list transform: polynomials [L][N] number 0 .. npolys - 1 of src[i] (src_poly words apart) -> the same of dst[i] (dst_poly words apart),
+    // NTT_MAX_ITEMS items per launch, forward or inverse, under the first L moduli of Q
+    void ntt_items(bool inverse, const std::vector<const u64*>& src, long src_poly, const std::vector<u64*>& dst, long dst_poly, int npolys, int L);
+    // out [nouter][mtot][N] = [MForm] sum_a keys[a] (.) digits[a] over the active moduli of `level`: the x / y sums of MulAndRelin, on the active stream
+    void key_inner_product(const u64* const* keys, const u64* const* digits, int n, u64* out, int level, int nouter, bool mform);
     bool ext_fused_ok(int level, int nvec) const;
     // stage 0: whole external products; 1: front half only (inner products + inverse NTT into the c1 pool);
     // 2: back half only (ModDown of the c1 pool filled by the preceding stage-1 call with the same items)
@@ -303,9 +310,9 @@ class Context {
     // outs[b] [1 + k][nq][N] <- polynomial 0 = up(down(ins[b] polynomial 0 + sum_i shares[i][b])) + polynomial 0 of reenc[i * count + b];
     // polynomial 1 + i = polynomial 1 of reenc[i * count + b]
     void bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, u64* const* outs);
-    // the tables of the BFV encoder, which both calls read, built here if no encoder call has built them (what = the C entry point: T outside the
-    // encoder's preconditions is refused under its name), and the widest flood a share takes: bitlen(Q div 2 T) - 1
-    void bfv_refresh_prepare(const char* what) { bf_init(what); }
+    // the tables of the BFV encoder, which both calls (and mkhe_bfv_ct_ptxt_dot) read, built here if no encoder call has built them (what = the C
+    // entry point: T outside the encoder's preconditions is refused under its name), and the widest flood a share takes: bitlen(Q div 2 T) - 1
+    void bfv_prepare(const char* what) { bf_init(what); }
     int bfv_refresh_max_flood() const { return flood_room(nq, bfv_t); }
     // bitlen((q_0 .. q_(limbs-1)) div 2 t) - 1: the widest flood that alone leaves a message scaled by Q / t standing (t = 1: a CKKS / mkrlwe ring)
     int flood_room(int limbs, u64 t) const;
@@ -363,10 +370,6 @@ class Context {
     // consecutive items, 0 = one plaintext for all.  what = the C entry point, for the messages.
     void bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& ins, const u64* ptmul, long pt_stride, const std::vector<Ct*>& outs);
     void bfv_ct_add_ptxt(const char* what, int op, const std::vector<const Ct*>& ins, const u64* pt, long pt_stride, const std::vector<Ct*>& outs);
-    // the middle of a BFV plaintext linear transform for nbatch items that share masks and plaintexts: ins = [nbatch][nin], outs = [nbatch][masks.size()],
-    // ptmul = the compact block of prepared plaintexts in (giant, input) order (the numbering of ct_ptxt_dot), nQ * N words each
-    void bfv_ct_ptxt_dot(const char* what, int nbatch, const std::vector<const Ct*>& ins, const std::vector<unsigned int>& masks, const u64* ptmul,
-                         const std::vector<Ct*>& outs);
     // log2 of the largest transform one workgroup does in LDS (BF_TILE_LOG_BIG, or BF_TILE_LOG_DEF when the runtime grants no more LDS), and a way
     // to lower it (BF_TILE_LOG_MIN .. the grant; 0: back to the grant) so that the two-launch form can be run at small N
     int bfv_tile();
@@ -463,7 +466,7 @@ class Context {
     void share_product(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, u64* w);
     // w [count][L][N] <- NTT(polynomial slots[b] of ins[b]): one gathering forward transform (per NTT_MAX_ITEMS items)
     void share_gather_ntt(const std::vector<const Ct*>& ins, const int* slots, u64* w);
-    // w [count][L][N] <- NTT(src[b] [L][N]), the same gathering transform on bare polynomials
+    // w [count][L][N] <- NTT(src[b] [L][N]), the same gathering transform on bare polynomials (ntt_items with one polynomial per item)
     void gather_ntt(const std::vector<const u64*>& src, int L, u64* w);
     // collective refresh: MForm(q_i mod q_j) and (q_0 .. q_l) mod q_j, [nq][nq] each in one block, built at the first merge; the digits of R
     u64* d_rf_tab_ = nullptr;
@@ -647,5 +650,13 @@ class Context {
         ~ProfScope();
     };
 };
+
+// slot0[a] / slot1[a] = where out carries id a of op0 / op1; out's ids must be exactly the union (newCiphertextBinary, mkckks/evaluator.go:306-313).
+// out_name opens the refusals ("mkhe: ctOut")
+void union_slots(const Ct& op0, const Ct& op1, const Ct& out, const char* out_name, std::vector<int>& slot0, std::vector<int>& slot1);
+// the term table of tensor_sum_kernel for a pair laid out c0_0, c0_i, c1_0, c1_j (poly_kernels.h, TensorSumArgs::term)
+void tensor_sum_terms(TensorSumArgs& ta, int n0, int n1, const std::vector<int>& slot0, const std::vector<int>& slot1, int nout);
+// conv.Quantize behind its MulScalar and inverse NTT (basis_extension.go:66-80): ModDownQPtoQ of polyr [npolys][2 nQ][N] with QMul as "P"
+void quantize_tail_args(BasisConvArgs& a, const Context& c, u64* polyr, u64* polyq, int npolys);
 
 }  // namespace mkhe

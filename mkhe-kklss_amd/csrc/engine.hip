@@ -936,6 +936,27 @@ bool Context::ext_fused_ok(int level, int nvec) const {
     if (alpha != 1 || logN != 14 || masked_ || is_bfv() || nvec < 1 || nvec > EXTF_MAX_V || mall > 64) return false;
     return nvec * beta(level) * nslots_qp(level) <= lim;
 }
+void Context::ntt_items(bool inverse, const std::vector<const u64*>& src, long src_poly, const std::vector<u64*>& dst, long dst_poly, int npolys, int L) {
+    for (size_t base = 0; base < src.size(); base += NTT_MAX_ITEMS) {
+        const int cnt = (int)std::min<size_t>(NTT_MAX_ITEMS, src.size() - base);
+        NttBatch b{};
+        b.mods = d_mods; b.psi = inverse ? d_psiinv : d_psi; b.aux = d_inv_aux; slots_range(b, 0, L);
+        b.src_inner = b.dst_inner = N; b.src_outer = src_poly; b.dst_outer = dst_poly;
+        b.nitems = cnt; b.outers_per_item = npolys; b.nouter = cnt * npolys;
+        for (int i = 0; i < cnt; ++i) { b.src_items[i] = src[base + i]; b.dst_items[i] = dst[base + i]; }
+        if (inverse) { ProfScope ps(this, PROF_NTT_INV, 16.0 * N * b.nouter * L); ntt_inv_launch(b); }
+        else ntt_fwd_launch(b, false);
+    }
+}
+void Context::key_inner_product(const u64* const* keys, const u64* const* digits, int n, u64* out, int level, int nouter, bool mform) {
+    const int nslots = nslots_qp(level);
+    InnerProductArgs ip{};
+    for (int a = 0; a < n; ++a) { ip.a[a] = keys[a]; ip.b[a] = digits[a]; }
+    ip.out = out; ip.mods = d_mods; ip.map = map_qp(level);
+    ip.term_outer = ip.out_outer = (long)mtot * N; ip.nterms = n; ip.nslots = nslots; ip.nouter = nouter; ip.N = N; ip.mform_out = mform ? 1 : 0;
+    ProfScope ps(this, PROF_INNER, 8.0 * N * nslots * nouter * (2.0 * n + 1));
+    launch_inner_product(ip, s_);
+}
 void Context::decompose_batch(int level, const std::vector<const u64*>& src, const std::vector<u64*>& dst, bool internal, bool stage_only) {
     check_level(level);
     const int nb = beta(level);

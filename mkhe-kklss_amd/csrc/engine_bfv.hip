@@ -63,7 +63,7 @@ void Context::bfv_rescale(const u64* polyq, u64* polyr, int npolys) {
 
 // conv.Quantize (basis_extension.go:66-80) AFTER the MulScalar(t): InvNTT over R (in place), ModDownQPtoQ with QMul as "P".
 // The MulScalar itself is folded into the producer (tensor kernel) or done by the caller (bfv_quantize_full).
-static void quantize_tail_args(BasisConvArgs& a, const Context& c, u64* polyr, u64* polyq, int npolys) {
+void quantize_tail_args(BasisConvArgs& a, const Context& c, u64* polyr, u64* polyq, int npolys) {
     a.src = polyr + (size_t)c.nq * c.N; a.src_poly = 2L * c.nq * c.N;
     a.xsub = polyr; a.xsub_poly = 2L * c.nq * c.N;
     a.dst = polyq; a.dst_poly = (long)c.nq * c.N;
@@ -138,26 +138,21 @@ void Context::bfv_external_product_hoisted(const u64* ah1, const u64* ah2, const
 //   bfv_mr_finish:  steps E and F with the complete x, y.
 // Quantize rounds, so both tensor terms of an output slot (op0_0 * op1_j + op0_j * op1_0) have to be added before it: a rank
 // must own whole parties (both components of every id it holds).
-void Context::bfv_slots(const Ct& op0, const Ct& op1, const Ct& out, std::vector<int>& slot0, std::vector<int>& slot1) const {
-    const int n0 = op0.n, n1 = op1.n;
-    if (op0.limbs != nq || op1.limbs != nq || out.limbs != nq) throw Error("mkhe: BFV ciphertexts live at the maximum level");
-    if (n0 > 32 || n1 > 32 || out.n > 32) throw Error("mkhe: too many parties");
-    slot0.assign(n0, 0); slot1.assign(n1, 0);
-    auto find = [&](int id) { for (int o = 0; o < out.n; ++o) if (out.ids[o] == id) return o; return -1; };
-    std::vector<char> seen(out.n, 0);
-    for (int a = 0; a < n0; ++a) { int o = find(op0.ids[a]); if (o < 0) throw Error("mkhe: ctOut lacks an id of op0"); slot0[a] = o; seen[o] = 1; }
-    for (int a = 0; a < n1; ++a) { int o = find(op1.ids[a]); if (o < 0) throw Error("mkhe: ctOut lacks an id of op1"); slot1[a] = o; seen[o] = 1; }
-    for (int o = 0; o < out.n; ++o) if (!seen[o]) throw Error("mkhe: ctOut has an id that neither operand has");
+// what every BFV product asks of its shapes before the ids of out are mapped (union_slots)
+static void bfv_shapes(const Context& c, const Ct& op0, const Ct& op1, const Ct& out) {
+    if (op0.limbs != c.nq || op1.limbs != c.nq || out.limbs != c.nq) throw Error("mkhe: BFV ciphertexts live at the maximum level");
+    if (op0.n > 32 || op1.n > 32 || out.n > 32) throw Error("mkhe: too many parties");
 }
 
 void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk_b1, const Swk* const* rlk_b2,
                              const Swk* const* rlk_d1, const Swk* const* rlk_d2, bool with_c0, bool mform, Ct& out,
                              u64* x1, u64* x2, u64* y1, u64* y2, bool fuse_x, bool fuse_y) {
     if (!is_bfv()) throw Error("mkhe: not a BFV context");
-    const int level = nq - 1, L = nq, n0 = op0.n, n1 = op1.n;
+    const int level = nq - 1, n0 = op0.n, n1 = op1.n;
     BfvPlan& bp = bfv_plan_ = BfvPlan{};
     std::vector<int> slot0, slot1;
-    bfv_slots(op0, op1, out, slot0, slot1);
+    bfv_shapes(*this, op0, op1, out);
+    union_slots(op0, op1, out, "mkhe: ctOut", slot0, slot1);
     for (int a = 0; a < n0; ++a) if (!rlk_d1[a] || !rlk_d2[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     for (int a = 0; a < n1; ++a) if (!rlk_b1[a] || !rlk_b2[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
 
@@ -204,7 +199,6 @@ void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk
     }
     // y1, y2 on the main stream (they feed step F, the long chain), x1, x2 on the side stream (step E joins the last
     // batch)   (keyswitch_hoisted.go:76-126)
-    const int nslots = L + np;
     // single-device evaluation with 1..4 parties in op0: x1, x2 come out of step F1 as by-products of the digits it holds anyway
     // (Context::mul_and_relin does the same for mkckks) -- two inner-product launches and one pass over h1(c0_i), h2(c0_i) less
     if (fuse_x) {
@@ -220,19 +214,12 @@ void Context::bfv_mr_partial(const Ct& op0, const Ct& op1, const Swk* const* rlk
     for (int which = fuse_y ? 1 : 3; which >= (fuse_x ? 2 : 0); --which) {
         const int side = which >> 1, half = which & 1;
         const int n = side ? n1 : n0;
-        InnerProductArgs ip{};
-        for (int a = 0; a < n; ++a) {
-            const Swk* key = side ? (half ? rlk_b2[a] : rlk_b1[a]) : (half ? rlk_d2[a] : rlk_d1[a]);
-            ip.a[a] = key->d;
-            ip.b[a] = side ? (half ? h1b[a] : h1a[a]) : (half ? h0b[a] : h0a[a]);
-        }
-        ip.out = side ? (half ? y2 : y1) : (half ? x2 : x1);
-        ip.mods = d_mods; ip.map = map_qp(level);
-        ip.term_outer = ip.out_outer = (long)mtot * N; ip.nterms = n; ip.nslots = nslots; ip.nouter = beta_max; ip.N = N; ip.mform_out = mform ? 1 : 0;
+        std::vector<const u64*> keys(n);
+        for (int a = 0; a < n; ++a) keys[a] = (side ? (half ? rlk_b2[a] : rlk_b1[a]) : (half ? rlk_d2[a] : rlk_d1[a]))->d;
         const bool on_side = side == 0 && overlap;
         if (which == 1 && on_side) fork_side(2);
         if (on_side) s_ = stream2;
-        { ProfScope ps(this, PROF_INNER, 8.0 * N * nslots * beta_max * (2.0 * n + 1)); launch_inner_product(ip, s_); }
+        key_inner_product(keys.data(), (side ? (half ? h1b : h1a) : (half ? h0b : h0a)).data(), n, side ? (half ? y2 : y1) : (half ? x2 : x1), level, beta_max, mform);
         if (on_side) s_ = stream;
         if (which == 0 && on_side) side_done(2);
     }
@@ -249,7 +236,8 @@ void Context::bfv_mr_finish(const Ct& op0, const Ct& op1, const u64* x1, const u
     if (!bp.valid) throw Error("mkhe: bfv_mr_finish without bfv_mr_partial");
     const int level = nq - 1, n0 = op0.n, n1 = op1.n;
     std::vector<int> slot0, slot1;
-    bfv_slots(op0, op1, out, slot0, slot1);
+    bfv_shapes(*this, op0, op1, out);
+    union_slots(op0, op1, out, "mkhe: ctOut", slot0, slot1);
     for (int a = 0; a < n0; ++a) if (!rlk_v[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     const size_t PQ = (size_t)nq * N;
     // F1: t_i = <h(c0_i), (y1,y2)>
@@ -332,7 +320,8 @@ void Context::bfv_mul_relin_unhoisted(const Ct& op0, const Ct& op1, const Swk* c
     if (!is_bfv()) throw Error("mkhe: not a BFV context");
     const int level = nq - 1, L = nq, n0 = op0.n, n1 = op1.n;
     std::vector<int> slot0, slot1;
-    bfv_slots(op0, op1, out, slot0, slot1);
+    bfv_shapes(*this, op0, op1, out);
+    union_slots(op0, op1, out, "mkhe: ctOut", slot0, slot1);
     for (int a = 0; a < n0; ++a) if (!rlk_d1[a] || !rlk_d2[a] || !rlk_v[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     for (int a = 0; a < n1; ++a) if (!rlk_b1[a] || !rlk_b2[a]) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
     const size_t PR = 2 * (size_t)nq * N, PQ = (size_t)nq * N;

@@ -32,7 +32,10 @@ void Context::bfv_mul_relin_sum(const std::vector<const Ct*>& op0, const std::ve
         if (op0[k]->d == out.d || op1[k]->d == out.d) throw Error("mkhe_bfv_mul_relin_sum: out must be distinct from every operand");
     }
     std::vector<int> slot0, slot1;
-    bfv_slots(*op0[0], *op1[0], out, slot0, slot1);        // (out at the maximum level, its ids the union; the C entry point names the call)
+    // (out at the maximum level, its ids the union; the C entry point names the call)
+    if (out.limbs != nq) throw Error("mkhe: BFV ciphertexts live at the maximum level");
+    if (n0 > 32 || n1 > 32 || out.n > 32) throw Error("mkhe: too many parties");
+    union_slots(*op0[0], *op1[0], out, "mkhe: ctOut", slot0, slot1);
     if (n0 > MAX_TERMS || n1 > MAX_TERMS) throw Error("mkhe_bfv_mul_relin_sum: too many parties");
     for (int a = 0; a < n0; ++a) if (!rlk_d1[a] || !rlk_d2[a] || !rlk_v[a]) throw Error("mkhe_bfv_mul_relin_sum: cannot GetRelinearizationKey: there is no relinearization key with given id");
     for (int a = 0; a < n1; ++a) if (!rlk_b1[a] || !rlk_b2[a]) throw Error("mkhe_bfv_mul_relin_sum: cannot GetRelinearizationKey: there is no relinearization key with given id");
@@ -70,7 +73,6 @@ void Context::bfv_mul_relin_sum(const std::vector<const Ct*>& op0, const std::ve
     for (int a = 0; a < n0; ++a) { h0a[a] = hoist_slot(0, a).d; h0b[a] = hoist_slot(3, a).d; if (!f2) hoist_slot(2, a); }
     for (int a = 0; a < n1; ++a) { h1a[a] = hoist_slot(1, a).d; h1b[a] = hoist_slot(4, a).d; }
 
-    const int nslots = L + np;
     for (int k = 0; k < K; ++k) {
         // ---- the pair over R (coefficient domain: this pair only) and its transforms (kept: the tensor kernel reads all K)
         if (k) join_side(1);                               // the side stream has read the previous pair out of r0, r1
@@ -93,18 +95,12 @@ void Context::bfv_mul_relin_sum(const std::vector<const Ct*>& op0, const std::ve
         for (int which = fuse_y ? 1 : 3; which >= (fuse_x ? 2 : 0); --which) {
             const int side = which >> 1, half = which & 1;
             const int n = side ? n1 : n0;
-            InnerProductArgs ip{};
-            for (int a = 0; a < n; ++a) {
-                ip.a[a] = (side ? (half ? rlk_b2[a] : rlk_b1[a]) : (half ? rlk_d2[a] : rlk_d1[a]))->d;
-                ip.b[a] = side ? (half ? h1b[a] : h1a[a]) : (half ? h0b[a] : h0a[a]);
-            }
-            ip.out = side ? (half ? y2_ : y_) : (half ? x2_ : x_);
-            ip.mods = d_mods; ip.map = map_qp(level);
-            ip.term_outer = ip.out_outer = (long)mtot * N; ip.nterms = n; ip.nslots = nslots; ip.nouter = beta_max; ip.N = N; ip.mform_out = 1;
+            std::vector<const u64*> keys(n);
+            for (int a = 0; a < n; ++a) keys[a] = (side ? (half ? rlk_b2[a] : rlk_b1[a]) : (half ? rlk_d2[a] : rlk_d1[a]))->d;
             const bool on_side = side == 0 && overlap;
             if (which == 1 && on_side) fork_side(2);
             if (on_side) { s_ = stream2; x_on_side = true; }
-            { ProfScope ps(this, PROF_INNER, 8.0 * N * nslots * beta_max * (2.0 * n + 1)); launch_inner_product(ip, s_); }
+            key_inner_product(keys.data(), (side ? (half ? h1b : h1a) : (half ? h0b : h0a)).data(), n, side ? (half ? y2_ : y_) : (half ? x2_ : x_), level, beta_max, true);
             if (on_side) s_ = stream;
             if (which == 0 && on_side) side_done(2);
         }
@@ -138,27 +134,12 @@ void Context::bfv_mul_relin_sum(const std::vector<const Ct*>& op0, const std::ve
         TensorSumArgs ta{};
         ta.in = fb; ta.out = tz; ta.mods = d_mods; ta.map = d_map_r; ta.scale = d_t_mont; ta.pair_words = (long)npair * (long)PR;
         ta.K = K; ta.nout = out.n; ta.L = 2 * nq; ta.N = N;
-        const unsigned A0 = 0, B0 = 1 + n0, none = 255;
-        std::vector<unsigned> ta_a(npo, none), ta_b(npo, none);
-        for (int a = 0; a < n0; ++a) ta_a[1 + slot0[a]] = 1 + a;
-        for (int a = 0; a < n1; ++a) ta_b[1 + slot1[a]] = 2 + n0 + a;
-        ta.term[0] = A0 | B0 << 8 | none << 16 | none << 24;
-        for (int o = 1; o <= out.n; ++o) {
-            if (ta_a[o] != none && ta_b[o] != none) ta.term[o] = B0 | ta_a[o] << 8 | A0 << 16 | ta_b[o] << 24;
-            else if (ta_a[o] != none) ta.term[o] = B0 | ta_a[o] << 8 | none << 16 | none << 24;
-            else ta.term[o] = A0 | ta_b[o] << 8 | none << 16 | none << 24;
-        }
+        tensor_sum_terms(ta, n0, n1, slot0, slot1, out.n);
         { ProfScope ps(this, PROF_TENSOR, 8.0 * N * 2 * nq * ((double)K * npair + npo)); launch_tensor_sum(ta, s_); }
         ntt_r(tz, tz, npo, true);
         // conv.Quantize behind its MulScalar (basis_extension.go:66-80): ModDownQPtoQ with QMul as "P"
         BasisConvArgs qa{};
-        qa.src = tz + (size_t)nq * N; qa.src_poly = (long)PR;
-        qa.xsub = tz; qa.xsub_poly = (long)PR;
-        qa.dst = out.d; qa.dst_poly = (long)PQ;
-        qa.mods_s = d_mods + mtot; qa.mods_t = d_mods;
-        qa.downparam = d_down_m_in_q;
-        qa.t = BasisConvTables{d_bm_qoverqiinvqi, d_bm_qoverqimodp, d_bm_vtimes};
-        qa.ns = nq; qa.nt = nq; qa.N = N; qa.npolys = npo;
+        quantize_tail_args(qa, *this, tz, out.d, npo);
         { ProfScope ps(this, PROF_BASISCONV, 8.0 * N * npo * 3.0 * nq); launch_basis_conv(qa, s_); }
     }
     side_done(1);

@@ -50,6 +50,16 @@ void Context::mul_relin_rescale(const Ct& op0, const Ct& op1, const Swk* const* 
     pool_free(full.d, words, &none);
 }
 
+void union_slots(const Ct& op0, const Ct& op1, const Ct& out, const char* out_name, std::vector<int>& slot0, std::vector<int>& slot1) {
+    const std::string w(out_name);
+    slot0.assign(op0.n, 0); slot1.assign(op1.n, 0);
+    auto find = [&](int id) { for (int o = 0; o < out.n; ++o) if (out.ids[o] == id) return o; return -1; };
+    std::vector<char> seen(out.n, 0);
+    for (int a = 0; a < op0.n; ++a) { const int o = find(op0.ids[a]); if (o < 0) throw Error(w + " lacks an id of op0"); slot0[a] = o; seen[o] = 1; }
+    for (int a = 0; a < op1.n; ++a) { const int o = find(op1.ids[a]); if (o < 0) throw Error(w + " lacks an id of op1"); slot1[a] = o; seen[o] = 1; }
+    for (int o = 0; o < out.n; ++o) if (!seen[o]) throw Error(w + " has an id that neither operand has");
+}
+
 // -- step 0: validate, map ids, hoist the operands when the caller did not (MulRelinNew, evaluator.go:416-443)
 // and start step D (tensor).  with_c0 = false leaves c0_0*c1_0 out of out_0 (another rank of a party-sharded
 // evaluation adds it).
@@ -61,13 +71,7 @@ void Context::mr_prepare(const Ct& op0, const Ct& op1, const Swk* const* hoist0,
     if (op0.limbs < p.L || op1.limbs < p.L) throw Error("Cannot MulAndRelin: op0 and op1 have different levels");
     p.n0 = op0.n; p.n1 = op1.n; p.nout = out.n;
     if (p.n0 > 32 || p.n1 > 32 || out.n > 32) throw Error("mkhe: too many parties");
-    // out ids must be the union of the operand id sets (newCiphertextBinary, mkckks/evaluator.go:306-313)
-    p.slot0.assign(p.n0, 0); p.slot1.assign(p.n1, 0);
-    auto find = [&](int id) { for (int o = 0; o < out.n; ++o) if (out.ids[o] == id) return o; return -1; };
-    std::vector<char> seen(out.n, 0);
-    for (int a = 0; a < p.n0; ++a) { int o = find(op0.ids[a]); if (o < 0) throw Error("mkhe: ctOut lacks an id of op0"); p.slot0[a] = o; seen[o] = 1; }
-    for (int a = 0; a < p.n1; ++a) { int o = find(op1.ids[a]); if (o < 0) throw Error("mkhe: ctOut lacks an id of op1"); p.slot1[a] = o; seen[o] = 1; }
-    for (int o = 0; o < out.n; ++o) if (!seen[o]) throw Error("mkhe: ctOut has an id that neither operand has");
+    union_slots(op0, op1, out, "mkhe: ctOut", p.slot0, p.slot1);
     const size_t P0 = (size_t)op0.limbs * N, P1 = (size_t)op1.limbs * N;
     p.h0.assign(p.n0, nullptr); p.h1.assign(p.n1, nullptr);
     const bool same = (&op0 == &op1) && hoist0 == hoist1;
@@ -152,7 +156,7 @@ void Context::mr_prepare(const Ct& op0, const Ct& op1, const Swk* const* hoist0,
 void Context::mr_xy(const Swk* const* rlk_b1, const Swk* const* rlk_d0, u64* x, u64* y, bool mform, bool defer_x, bool fuse_x, bool fuse_y) {
     MrPlan& p = plan_;
     if (!p.valid) throw Error("mkhe: mr_xy without mr_prepare");
-    const int nb = beta(p.level), nslots = nslots_qp(p.level);
+    const int nb = beta(p.level);
     p.xkeys.clear(); p.xfused = nullptr;
     if (fuse_x) {
         if (!mform) throw Error("mkhe: internal: the fused x is produced in Montgomery form");
@@ -174,17 +178,15 @@ void Context::mr_xy(const Swk* const* rlk_b1, const Swk* const* rlk_d0, u64* x, 
     for (int side = fuse_y ? 0 : 1; side >= (fuse_x ? 1 : 0); --side) {
         const int n = side ? p.n1 : p.n0;
         if (n > MAX_TERMS) throw Error("mkhe: too many parties");
-        InnerProductArgs ip{};
+        std::vector<const u64*> keys(n);
         for (int a = 0; a < n; ++a) {
             const Swk* key = side ? rlk_b1[a] : rlk_d0[a];
             if (!key) throw Error("cannot GetRelinearizationKey: there is no relinearization key with given id");
-            ip.a[a] = key->d; ip.b[a] = side ? p.h1[a] : p.h0[a];
+            keys[a] = key->d;
         }
-        ip.out = side ? y : x; ip.mods = d_mods; ip.map = map_qp(p.level);
-        ip.term_outer = ip.out_outer = (long)mtot * N; ip.nterms = n; ip.nslots = nslots; ip.nouter = nb; ip.N = N; ip.mform_out = mform ? 1 : 0;
         const bool on_side = side == 0 && defer_x && overlap;
         if (on_side) { fork_side(2); s_ = stream2; }
-        { ProfScope ps(this, PROF_INNER, 8.0 * N * nslots * nb * (2.0 * n + 1)); launch_inner_product(ip, s_); }
+        key_inner_product(keys.data(), (side ? p.h1 : p.h0).data(), n, side ? y : x, p.level, nb, mform);
         if (on_side) { side_done(2); s_ = stream; p.x_pending = true; }
     }
     MKHE_HIP(hipGetLastError());

@@ -13,6 +13,19 @@
 
 namespace mkhe {
 
+void tensor_sum_terms(TensorSumArgs& ta, int n0, int n1, const std::vector<int>& slot0, const std::vector<int>& slot1, int nout) {
+    const unsigned A0 = 0, B0 = 1 + n0, none = 255;
+    std::vector<unsigned> ta_a(1 + nout, none), ta_b(1 + nout, none);
+    for (int a = 0; a < n0; ++a) ta_a[1 + slot0[a]] = 1 + a;
+    for (int a = 0; a < n1; ++a) ta_b[1 + slot1[a]] = 2 + n0 + a;
+    ta.term[0] = A0 | B0 << 8 | none << 16 | none << 24;
+    for (int o = 1; o <= nout; ++o) {
+        if (ta_a[o] != none && ta_b[o] != none) ta.term[o] = B0 | ta_a[o] << 8 | A0 << 16 | ta_b[o] << 24;
+        else if (ta_a[o] != none) ta.term[o] = B0 | ta_a[o] << 8 | none << 16 | none << 24;
+        else ta.term[o] = A0 | ta_b[o] << 8 | none << 16 | none << 24;
+    }
+}
+
 void Context::mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector<const Ct*>& op1, const std::vector<const Swk*>& hoist0,
                             const std::vector<const Swk*>& hoist1, const Swk* const* rlk_b1, const Swk* const* rlk_d0, const Swk* const* rlk_v0,
                             const Swk& crs_u, bool rescale_out, Ct& out) {
@@ -51,14 +64,7 @@ void Context::mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector
     if (!hoist0.empty() && (int)hoist0.size() != K * n0) throw Error("mkhe_mul_relin_sum: hoist0 must hold one form per pair and party");
     if (!hoist1.empty() && (int)hoist1.size() != K * n1) throw Error("mkhe_mul_relin_sum: hoist1 must hold one form per pair and party");
     // out ids = the union of the operand id sets (mr_prepare)
-    p.slot0.assign(n0, 0); p.slot1.assign(n1, 0);
-    {
-        auto find = [&](int id) { for (int o = 0; o < out.n; ++o) if (out.ids[o] == id) return o; return -1; };
-        std::vector<char> seen(out.n, 0);
-        for (int a = 0; a < n0; ++a) { const int o = find(op0[0]->ids[a]); if (o < 0) throw Error("mkhe_mul_relin_sum: out lacks an id of op0"); p.slot0[a] = o; seen[o] = 1; }
-        for (int a = 0; a < n1; ++a) { const int o = find(op1[0]->ids[a]); if (o < 0) throw Error("mkhe_mul_relin_sum: out lacks an id of op1"); p.slot1[a] = o; seen[o] = 1; }
-        for (int o = 0; o < out.n; ++o) if (!seen[o]) throw Error("mkhe_mul_relin_sum: out has an id that neither operand has");
-    }
+    union_slots(*op0[0], *op1[0], out, "mkhe_mul_relin_sum: out", p.slot0, p.slot1);
     for (int a = 0; a < n0; ++a) if (!rlk_d0[a] || !rlk_v0[a]) throw Error("mkhe_mul_relin_sum: cannot GetRelinearizationKey: there is no relinearization key with given id");
     for (int a = 0; a < n1; ++a) if (!rlk_b1[a]) throw Error("mkhe_mul_relin_sum: cannot GetRelinearizationKey: there is no relinearization key with given id");
     if (n0 > MAX_TERMS || n1 > MAX_TERMS) throw Error("mkhe_mul_relin_sum: too many parties");
@@ -91,16 +97,7 @@ void Context::mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector
         TensorSumArgs ta{};
         ta.in = nb_; ta.out = tens; ta.mods = d_mods; ta.scale = fold ? d_pmodq : nullptr; ta.pair_words = (long)npair * (long)PO;
         ta.K = K; ta.nout = out.n; ta.L = L; ta.N = N;
-        const unsigned A0 = 0, B0 = 1 + n0, none = 255;
-        std::vector<unsigned> ta_a(1 + out.n, none), ta_b(1 + out.n, none);
-        for (int a = 0; a < n0; ++a) ta_a[1 + p.slot0[a]] = 1 + a;
-        for (int a = 0; a < n1; ++a) ta_b[1 + p.slot1[a]] = 2 + n0 + a;
-        ta.term[0] = A0 | B0 << 8 | none << 16 | none << 24;
-        for (int o = 1; o <= out.n; ++o) {
-            if (ta_a[o] != none && ta_b[o] != none) ta.term[o] = B0 | ta_a[o] << 8 | A0 << 16 | ta_b[o] << 24;
-            else if (ta_a[o] != none) ta.term[o] = B0 | ta_a[o] << 8 | none << 16 | none << 24;
-            else ta.term[o] = A0 | ta_b[o] << 8 | none << 16 | none << 24;
-        }
+        tensor_sum_terms(ta, n0, n1, p.slot0, p.slot1, out.n);
         { ProfScope ps(this, PROF_TENSOR, 8.0 * N * L * ((double)K * npair + 1 + out.n)); launch_tensor_sum(ta, s_); }
         if (!fold) ntt(out.d, out.d, 1 + out.n, L, 0, true, false);
     }
@@ -109,7 +106,7 @@ void Context::mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector
     bool tensor_joined = false;
 
     // ---- per pair: hoist, x^k / y^k, F1 (t_i += ..) and E (out_j += ..)
-    const int nb = beta(level), nslots = nslots_qp(level);
+    const int nb = beta(level);
     std::vector<char> e_written(n1, 0);
     for (int k = 0; k < K; ++k) {
         const Ct& c0 = *op0[k]; const Ct& c1 = *op1[k];
@@ -148,11 +145,9 @@ void Context::mul_relin_sum(const std::vector<const Ct*>& op0, const std::vector
         } else {
             for (int side = 1; side >= 0; --side) {
                 const int n = side ? n1 : n0;
-                InnerProductArgs ip{};
-                for (int a = 0; a < n; ++a) { ip.a[a] = (side ? rlk_b1[a] : rlk_d0[a])->d; ip.b[a] = side ? p.h1[a] : p.h0[a]; }
-                ip.out = side ? y_ : x_; ip.mods = d_mods; ip.map = map_qp(level);
-                ip.term_outer = ip.out_outer = (long)mtot * N; ip.nterms = n; ip.nslots = nslots; ip.nouter = nb; ip.N = N; ip.mform_out = 1;
-                { ProfScope ps(this, PROF_INNER, 8.0 * N * nslots * nb * (2.0 * n + 1)); launch_inner_product(ip, s_); }
+                std::vector<const u64*> keys(n);
+                for (int a = 0; a < n; ++a) keys[a] = (side ? rlk_b1[a] : rlk_d0[a])->d;
+                key_inner_product(keys.data(), (side ? p.h1 : p.h0).data(), n, side ? y_ : x_, level, nb, true);
             }
             f1.insert(f1.end(), e.begin(), e.end());
             if (carries_tensor) { join_side(1); tensor_joined = true; }

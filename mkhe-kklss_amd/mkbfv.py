@@ -529,11 +529,7 @@ def linear_transform_batch(ev, cts, lt, rkSet, ckSet=None, fused=True):
     for ct in cts:
         if ct.ids != ids:
             raise MkheError("LinearTransformBatch: the ciphertexts of one call must be over the same ids")
-    keys = {}
-    for r in lt.Rotations():
-        if r not in params.CRS:
-            raise MkheError("LinearTransform: no CRS for rotation index %d" % r)
-        keys[r] = [rkSet.GetRotationKey(i, r).Value.h for i in ids]           # (MkheError when a party has none)
+    keys = mkrlwe.rotation_keys(params, rkSet, ids, lt.Rotations(), "LinearTransform")
     if lt.NeedsConjugation():
         if ckSet is None:
             raise MkheError("LinearTransform: the transform swaps the slot rows: pass the conjugation keys (ckSet)")
@@ -547,14 +543,7 @@ def linear_transform_batch(ev, cts, lt, rkSet, ckSet=None, fused=True):
     new = lambda: NewCiphertext(params, ids, zero=False)
     hoisted = [ev.HoistedForm(ct) if any(babies) else None for ct in cts]
 
-    def summed(terms):
-        while len(terms) > 1:
-            groups = [terms[i: i + CT_SUM_MAX] for i in range(0, len(terms), CT_SUM_MAX)]
-            terms = []
-            for grp in groups:
-                terms.append(new())
-                check(L.mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), terms[-1].h))
-        return terms[0]
+    summed = lambda terms: mkrlwe.sum_in_groups(ctx, terms, new, CT_SUM_MAX)
 
     def finish(part_d, part_e, add_all):
         """LT_d + swap(LT_e~) from the rotated inner sums of each part"""
@@ -581,13 +570,8 @@ def linear_transform_batch(ev, cts, lt, rkSet, ckSet=None, fused=True):
         return outs
 
     def rotate_lanes(srcs, rots, hoists):
-        """srcs[i] rotated by rots[i] != 0 as lanes of one mkhe_rotate_multi; hoists: one hoisted form per lane, or None"""
         outs = mkrlwe.batch_ciphertexts(Ciphertext, params, ids, params.MaxLevel(), len(srcs)) if len(srcs) > 1 else [new()]
-        gal = (C.c_uint64 * len(rots))(*[params.GaloisElementForColumnRotationBy(r) for r in rots])
-        hs = handle_array([h.Value[i].h for h in hoists for i in ids]) if hoists is not None else None
-        check(L.mkhe_rotate_multi(ctx, len(rots), gal, handle_array([c.h for c in srcs]), hs, handle_array([h for r in rots for h in keys[r]]),
-                                  handle_array([params.CRS[r].h for r in rots]), None, handle_array([o.h for o in outs])))
-        return outs
+        return mkrlwe.rotate_lanes(params, keys, ids, srcs, rots, hoists, outs)
 
     nzb = [b for b in babies if b]
     rot = [{0: ct} for ct in cts]

@@ -572,11 +572,7 @@ def linear_transform(ev, ct, lt, rkSet, fused=True):
     if not fused and lt.pt_coeff is None:
         raise MkheError("LinearTransformNew: fused=False needs LinearTransform(.., keep_coeff=True)")
     babies, giants = lt.plan.babies, lt.plan.giants
-    keys = {}
-    for r in lt.Rotations():
-        if r not in params.CRS:
-            raise MkheError("LinearTransformNew: no CRS for rotation index %d" % r)
-        keys[r] = [rkSet.GetRotationKey(i, r).Value.h for i in ct.ids]           # (MkheError when a party has none)
+    keys = mkrlwe.rotation_keys(params, rkSet, ct.ids, lt.Rotations(), "LinearTransformNew")
     L, ctx = lib(), params.ctx
     if ct.Level() > level:
         ct = ev.DropLevelNew(ct, ct.Level() - level)
@@ -584,19 +580,13 @@ def linear_transform(ev, ct, lt, rkSet, fused=True):
     new = lambda scale, lv=level: NewCiphertext(params, ct.IDSet(), lv, scale, zero=False)
     hoisted = ev.HoistedForm(ct) if any(babies) else None
 
-    def rotate_lanes(srcs, rots, hoist):
-        """srcs[i] rotated by rots[i] != 0, as lanes of one mkhe_rotate_multi; hoist: the hoisted form every lane shares, or None"""
-        outs = [new(c.Scale) for c in srcs]
-        gal = (C.c_uint64 * len(rots))(*[params.GaloisElementForColumnRotationBy(r) for r in rots])
-        hs = handle_array([hoist.Value[i].h for i in ct.ids] * len(rots)) if hoist is not None else None
-        check(L.mkhe_rotate_multi(ctx, len(rots), gal, handle_array([c.h for c in srcs]), hs, handle_array([h for r in rots for h in keys[r]]),
-                                  handle_array([params.CRS[r].h for r in rots]), None, handle_array([o.h for o in outs])))
-        return outs
+    def rotate_lanes(srcs, rots, hoists):
+        return mkrlwe.rotate_lanes(params, keys, ct.ids, srcs, rots, hoists, [new(c.Scale) for c in srcs])
 
     words = (level + 1) * params.N()
     if fused:
         nzb = [b for b in babies if b]
-        rot = dict(zip(nzb, rotate_lanes([ct] * len(nzb), nzb, hoisted))) if nzb else {}
+        rot = dict(zip(nzb, rotate_lanes([ct] * len(nzb), nzb, [hoisted] * len(nzb)))) if nzb else {}
         rot[0] = ct
         inner = [new(mid_scale) for _ in giants]
         masks = (C.c_uint32 * len(giants))(*lt.masks)
@@ -607,11 +597,7 @@ def linear_transform(ev, ct, lt, rkSet, fused=True):
         if nzg:
             terms += rotate_lanes([c for _, c in nzg], [g for g, _ in nzg], None)
         while len(terms) > LINCOMB_MAX:
-            groups = [terms[i: i + LINCOMB_MAX] for i in range(0, len(terms), LINCOMB_MAX)]
-            terms = []
-            for grp in groups:
-                terms.append(new(mid_scale))
-                check(L.mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), terms[-1].h))
+            terms = [mkrlwe.sum_in_groups(ctx, terms[i: i + LINCOMB_MAX], lambda: new(mid_scale)) for i in range(0, len(terms), LINCOMB_MAX)]
         consts = np.zeros((len(terms) + 1, 2, level + 1), dtype=np.uint64)
         consts[1:, 0, :] = np.array([(1 << 64) % q for q in params.Q[: level + 1]], dtype=np.uint64)              # MForm(1)
         n = params.N()
@@ -622,16 +608,7 @@ def linear_transform(ev, ct, lt, rkSet, fused=True):
     else:
         rot = {b: ev.RotateHoistedNew(ct, b, hoisted, rkSet) if b else ct for b in babies}
 
-        def summed(cts):
-            if len(cts) == 1:
-                return cts[0]
-            acc = None
-            for i in range(0, len(cts), LINCOMB_MAX - 1):
-                grp = ([acc] if acc is not None else []) + cts[i: i + LINCOMB_MAX - 1]
-                acc = new(mid_scale)
-                check(L.mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), acc.h))
-            return acc
-
+        summed = lambda cts: mkrlwe.sum_in_groups(ctx, cts, lambda: new(mid_scale))
         terms, index = [], 0
         for g, mask in zip(giants, lt.masks):
             prods = []

@@ -430,6 +430,38 @@ def batch_switching_keys(params, count):
     return out
 
 
+# ---- what the plaintext linear transforms of mkckks and mkbfv share (no reference counterpart)
+def rotation_keys(params, rkSet, ids, rotations, prefix):
+    """{r: the rotation-key handle of every id} for the rotation indices a transform needs; prefix opens the refusal of an index without a CRS"""
+    keys = {}
+    for r in rotations:
+        if r not in params.CRS:
+            raise MkheError("%s: no CRS for rotation index %d" % (prefix, r))
+        keys[r] = [rkSet.GetRotationKey(i, r).Value.h for i in ids]              # (MkheError when a party has none)
+    return keys
+
+
+def rotate_lanes(params, keys, ids, srcs, rots, hoists, outs):
+    """outs[i] = srcs[i] rotated by rots[i] != 0, as lanes of one mkhe_rotate_multi; keys: rotation_keys(..); hoists: one hoisted form per lane, or None"""
+    gal = (C.c_uint64 * len(rots))(*[params.GaloisElementForColumnRotationBy(r) for r in rots])
+    hs = handle_array([h.Value[i].h for h in hoists for i in ids]) if hoists is not None else None
+    check(lib().mkhe_rotate_multi(params.ctx, len(rots), gal, handle_array([c.h for c in srcs]), hs, handle_array([h for r in rots for h in keys[r]]),
+                                  handle_array([params.CRS[r].h for r in rots]), None, handle_array([o.h for o in outs])))
+    return outs
+
+
+def sum_in_groups(ctx, terms, new, group=16):
+    """the sum of terms (ciphertexts of one shape): mkhe_ct_sum over groups of `group` into new() until one is left.  Sums of canonical residues: the
+    grouping does not change a bit"""
+    while len(terms) > 1:
+        groups = [terms[i: i + group] for i in range(0, len(terms), group)]
+        terms = []
+        for grp in groups:
+            terms.append(new())
+            check(lib().mkhe_ct_sum(ctx, len(grp), handle_array([c.h for c in grp]), terms[-1].h))
+    return terms[0]
+
+
 class KeySwitcher:
     """mkrlwe.KeySwitcher (keyswitch.go:8-47).  The scratch pools of the reference (ks.Pool,
     swkPool1-3, polyQPool) are engine-internal device buffers owned by the context."""

@@ -332,3 +332,43 @@ def test_sum_of_ciphertexts_is_the_add_chain(case, n, ids, level):
     _, other = case.ct(["a", "d"] if ids != ["a", "d"] else ["b"], level)
     mixed = case.ev.SumNew([pairs[0][1], other])
     assert (mixed.download() == case.ev.AddNew(pairs[0][1], other).download()).all()
+
+
+# ---------------------------------------------------------------- more items than one list transform takes; the id map of the product's output
+@pytest.fixture(scope="module")
+def small():
+    return Case(H.small_ckks(12, 4), ["a", "b"], 78)
+
+
+@pytest.mark.parametrize("level", [None, 0])                  # the top level: the Rescale follows the product; level 0: the inverse list transform
+def test_mul_ptxt_on_sixty_five_inputs(small, level):
+    """BatchEvaluator.MulPtxtNew with B = 65 and one party: the forward (and at level 0 the inverse) list transform takes 64 ciphertexts per launch"""
+    B = 65
+    level = small.level if level is None else level
+    bev = small.mkckks.BatchEvaluator(small.params, B)
+    _, b = small.batch(["a"], B, level)
+    pt = H.uniform_poly(small.rng, small.p["Q"][: level + 1], 1 << small.p["logN"])
+    out = bev.MulPtxtNew(b, pt, small.p["scale"])
+    for k in range(B):
+        ref = small.ev.MulPtxtNew(b.cts[k], pt, small.p["scale"])
+        assert out.cts[k].Level() == ref.Level() and out.cts[k].Scale == ref.Scale
+        assert (out.cts[k].download() == ref.download()).all(), k
+
+
+@pytest.mark.parametrize("out_ids,text", [(["a"], "lacks an id"), (["a", "b", "c"], "neither operand has")])
+def test_mul_relin_refuses_an_output_whose_ids_are_not_the_union(small, out_ids, text):
+    """through mkhe_mul_relin_batch and through the single mkhe_mul_and_relin; the context works afterwards"""
+    from mkhe_kklss_amd._abi import MkheError, check, handle_array, lib
+    params, B = small.params, 2
+    bev = small.mkckks.BatchEvaluator(params, B)
+    _, b0 = small.batch(["a"], B)
+    _, b1 = small.batch(["b"], B)
+    outs = bev._new(set(out_ids), small.level, small.p["scale"])
+    key = lambda n, i: handle_array([small.rlk.GetRelinearizationKey(n).Value[i].h])
+    keys = (key("b", 0), key("a", 1), key("a", 2), params.CRS[-1].h)
+    with pytest.raises(MkheError, match=text):
+        check(lib().mkhe_mul_relin_batch(params.ctx, B, bev._h(b0), bev._h(b1), None, None, *keys, 0, bev._h(outs)))
+    with pytest.raises(MkheError, match=text):
+        check(lib().mkhe_mul_and_relin(params.ctx, b0.cts[0].h, b1.cts[0].h, None, None, *keys, outs.cts[0].h))
+    got = bev.MulRelinNew(b0, b1, small.rlk)
+    assert (got.cts[1].download() == small.ev.MulRelinNew(b0.cts[1], b1.cts[1], small.rlk).download()).all()

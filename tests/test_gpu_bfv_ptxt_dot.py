@@ -131,6 +131,20 @@ def test_one_item_of_a_batch_equals_the_call_alone(worlds):
         assert (outs[2 + g].download() == alone[g].download()).all()
 
 
+def test_sixty_five_inputs_cross_the_transform_launch(worlds):
+    """nbatch * nin = 5 * 13 = 65 input ciphertexts: the forward transform takes 64 per launch.  Every item against its call alone"""
+    w, ids, nbatch, nin = worlds[10], NAMES[:1], 5, 13
+    masks = [(1 << nin) - 1]
+    rng = np.random.default_rng(65)
+    ins = [w.ct(H.uniform_ct(rng, w, 1, w.nq), ids) for _ in range(nbatch * nin)]
+    pt = w.limbs(np.stack([H.uniform_poly(rng, w.Q, w.N) for _ in range(nin)]))
+    outs, alone = [w.new(ids) for _ in range(nbatch)], w.new(ids)
+    assert w.dot(nbatch, nin, ins, masks, pt, outs) == 0, w.error()
+    for b in range(nbatch):
+        assert w.dot(1, nin, ins[b * nin: (b + 1) * nin], masks, pt, [alone]) == 0, w.error()
+        assert (outs[b].download() == alone.download()).all(), b
+
+
 def test_refusals(worlds):
     from mkhe_kklss_amd import mkckks, mkrlwe
     from mkhe_kklss_amd._abi import MkheError

@@ -191,6 +191,22 @@ def test_share_counts_and_separate_streams(ck, level, count):
             assert ((got[b] + q - got[b2]) % q == want).all() and want.any()
 
 
+def test_share_of_more_items_than_one_transform_launch(ck):
+    """65 items: the gathering forward transform takes 64 per launch.  Unflooded, so that item b is what the call on its ciphertext alone gives"""
+    level, count = 1, 65
+    items = [ck.ct(USERS, level, which=b % 4) for b in range(count)]
+    alone = []
+    for b in range(4):
+        rc, got = ck.share([items[b][0]], "user1", 0, key=None)
+        assert rc == 0, error()
+        alone.append(got[0])
+        assert (got[0] == ck.product(items[b][1], items[b][0], "user1")).all()
+    rc, got = ck.share([c for c, _ in items], "user1", 0, key=None)
+    assert rc == 0, error()
+    for b in range(count):
+        assert (got[b] == alone[b % 4]).all(), b
+
+
 @pytest.mark.parametrize("who", ["user0", "user2"])
 def test_share_on_a_bfv_context(bf, who):
     level = bf.nq - 1
