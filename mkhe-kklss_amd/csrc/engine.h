@@ -394,7 +394,8 @@ class Context {
     void wait_for(Context& other);
 
     // ---- per-kernel-class timing with HIP events on the context stream (bench.py roofline leg)
-    enum { PROF_NTT_DECOMP = 0, PROF_NTT_DECOMP_BIGQ, PROF_NTT_DECOMP_MIXED, PROF_NTT16_DECOMP, PROF_NTT16_FWD, PROF_NTT32_DECOMP, PROF_NTT32_FWD, PROF_NTT14_SPLIT, PROF_NTT_FWD, PROF_NTT_FWD_BIGQ, PROF_NTT_INV, PROF_INNER, PROF_EXT_INNER,
+    // (the classes of the NTT launches lead the list: PROF_NTT_DECOMP = 0 .. PROF_NTT_INV, ntt_route.h)
+    enum { PROF_INNER = PROF_NTT_CLASSES, PROF_EXT_INNER,
            PROF_MODDOWN, PROF_TENSOR, PROF_BASISCONV, PROF_SPREAD, PROF_NTT_F2, PROF_OTHER, PROF_NCLASS };
     void prof_enable(bool on);
     void prof_collect(double* ms, long* launches, double* alg_bytes);
@@ -543,7 +544,8 @@ class Context {
     void slots_qp(NttBatch& b, int level) const;
     void slots_range(NttBatch& b, int mod_base, int limbs) const;
     void ntt_fwd_launch(const NttBatch& b, bool decompose);
-    void ntt_inv_launch(NttBatch& b);       // fills in the tables of the H16-class inverse kernel, then launch_ntt_inv
+    void ntt_inv_launch(NttBatch& b);       // fills in the tables of the H16-class inverse kernel, then the steps of ntt_inv_route
+    NttShape ntt_shape(const NttBatch& b, bool decompose, bool inverse) const;
     std::vector<unsigned char> small_q_;                     // per modulus: 34q < 2^63
     std::vector<unsigned char> small16_;                     // per modulus: 48q < 2^62 -- the short class of the H16 / H32 kernels (ntt16_kernels.hip)
     void ext_core(int level, const u64* ah, const u64* bg, u64* c, bool accumulate);

@@ -752,51 +752,55 @@ void Context::slots_range(NttBatch& b, int mod_base, int limbs) const {
     for (int j = 0; j < limbs; ++j) { b.mod[j] = mod_base + j; b.pos[j] = j; }
 }
 
-// forward NTT launch: one kernel per modulus class, each with its own timing record
+// what the routes of ntt_route.h read of a launch: its sizes, the modulus class of every slot and the pair tables this context has
+NttShape Context::ntt_shape(const NttBatch& b, bool decompose, bool inverse) const {
+    NttShape s;
+    s.logN = logN; s.nslots = b.nslots; s.nouter = b.nouter; s.jobs = b.vi ? b.vi_jobs : b.nslots * b.nouter;
+    for (int i = 0; i < b.nslots; ++i) {
+        const int m = b.mod[i];
+        if (small_q_[m]) s.small |= 1ull << i;
+        if (small16_[m]) s.small16 |= 1ull << i;
+        if ((u_mods_ >> m) & 1) s.u |= 1ull << i;
+    }
+    s.reduce_in = b.reduce_in; s.split = b.split; s.prestaged = b.prestaged; s.prestaged_oop = b.prestaged_oop; s.vi = b.vi;
+    s.decompose = decompose;
+    s.psi31 = d_psi31 != nullptr; s.psi31b = d_psi31b != nullptr; s.psi31c = d_psi31c != nullptr;
+    s.psiinv31 = d_psiinv31 != nullptr; s.inv31c = d_inv31c != nullptr;
+    s.no_h16 = (inverse ? d_psiinv31 : d_psi31) == nullptr;
+    return s;
+}
+
+// forward NTT launch: the steps of its route, every part (modulus class, or the whole launch) under its own timing record
 void Context::ntt_fwd_launch(const NttBatch& b_in, bool decompose) {
     NttBatch b = b_in;
     b.psi31 = d_psi31; b.psi31n = d_psi31n; b.psi31c = d_psi31c; b.psi31b = d_psi31b; b.u_mods = u_mods_; b.no_h16 = d_psi31 ? 0 : 1;
     b.psif = d_psif; b.f_mods = f_mods_;
     for (int i = 0; i < mall && i < NTT_MAX_SLOTS; ++i) b.sched[i] = h16_sched_.empty() ? 15 : h16_sched_[i];
-    const bool ok32 = ntt32_ok(logN, b), ok16 = ntt16_ok(logN, b);
+    b.trace = ntt_trace;
+    b.lazy_out = 0;             // (inverse only; the H16 kernels read it as a start delay)
+    const NttShape shape = ntt_shape(b, decompose, false);
+    const NttRoute r = ntt_fwd_route(shape, ntt_switches());
+    int first = 0, n = r.nparts;
     NttTune* sampling = nullptr;
-    int use32 = ok32 ? 1 : 0;
-    if (ok32 && ok16 && ntt32_mode() == 2) use32 = ntt_pick((((long)b.nslots * b.nouter) << 2) | (decompose ? 2 : 0) | (b.src_lazy ? 1 : 0), sampling);
+    if (r.pick) { first = ntt_pick((((long)b.nslots * b.nouter) << 2) | (decompose ? 2 : 0) | (b.src_lazy ? 1 : 0), sampling) ? 0 : 1; n = 1; }
     if (sampling) (void)hipEventRecord(sampling->e0[sampling->slot], s_);
-    if (use32) {
-        ProfScope ps(this, decompose ? PROF_NTT32_DECOMP : PROF_NTT32_FWD, 16.0 * N * b.nouter * b.nslots);
-        NttBatch bt = b; bt.trace = ntt_trace;
-        launch_ntt32_fwd(bt, small16_.data(), s_);
-    } else if (ok16) {
-        ProfScope ps(this, decompose ? PROF_NTT16_DECOMP : PROF_NTT16_FWD, 16.0 * N * b.nouter * b.nslots);
-        NttBatch bt = b; bt.trace = ntt_trace;
-        launch_ntt16_fwd(bt, small16_.data(), s_, logN);
-    }
-    if (use32 || ok16) return;
-    if (decompose && ntt_fwd_mixed_ok(logN, b, small_q_.data())) {
-        // large Decompose launches: both modulus classes in one persistent grid (no ragged tail of the big-modulus class)
-        ProfScope ps(this, PROF_NTT_DECOMP_MIXED, 16.0 * N * b.nouter * b.nslots);
-        launch_ntt_fwd_mixed(logN, b, small_q_.data(), s_);
-        return;
-    }
-    NttBatch part[2];
-    const int n = split_ntt_fwd(b, small_q_.data(), part);
-    for (int i = 0; i < n; ++i) part[i].trace = ntt_trace;
-    // two classes = two kernels; the second one runs on the side stream so that their partial last
-    // waves of workgroups (one workgroup per CU) fill each other's idle CUs
-    const bool side = (n == 2) && (s_ == stream);
-    for (int i = n - 1; i >= 0; --i) {
-        const bool small = part[i].lazy_out != 0;
-        const int cls = b.prestaged == 2 ? PROF_NTT14_SPLIT : decompose ? (small ? PROF_NTT_DECOMP : PROF_NTT_DECOMP_BIGQ) : (small ? PROF_NTT_FWD : PROF_NTT_FWD_BIGQ);
-        const bool on_side = side && i == 1;
-        if (on_side) { fork_side(0); s_ = overlap ? stream2 : stream; }
+    bool forked = false;
+    for (int i = first; i < first + n; ++i) {
+        const NttPart& p = r.part[i];
+        unsigned long long cls[3];
+        const int ncls = ntt_part_classes(shape, p.slots, cls);
+        const NttBatch c = order_slots_by_class(b, cls, ncls);
+        // two classes = two kernels; the first one runs on the side stream so that their partial last
+        // waves of workgroups (one workgroup per CU) fill each other's idle CUs
+        const bool on_side = p.side && s_ == stream;
+        if (on_side) { fork_side(0); s_ = overlap ? stream2 : stream; forked = true; }
         {
-            ProfScope ps(this, cls, 16.0 * N * part[i].nouter * part[i].nslots);
-            launch_ntt_fwd_class(logN, part[i], s_);
+            ProfScope ps(this, p.prof, 16.0 * N * c.nouter * c.nslots);
+            for (int k = 0; k < p.nsteps; ++k) launch_ntt_step(p.step[k], c, p.slots == NS_SMALL, s_);
         }
         if (on_side) { side_done(0); s_ = stream; }
     }
-    if (side) join_side(0);
+    if (forked) join_side(0);
 }
 
 void Context::ntt_reset(NttTune& t, int choice) {
@@ -856,9 +860,12 @@ int Context::ntt_pick(long key, NttTune*& sampling) {
     return k;
 }
 
+// (inside the caller's PROF_NTT_INV record: callers count the bytes of merged launches themselves)
 void Context::ntt_inv_launch(NttBatch& b) {
     b.psi31 = d_psiinv31; b.inv31c = d_inv31c; b.u_mods = u_mods_; b.small_mods = small_mods_; b.no_h16 = d_psiinv31 ? 0 : 1;
-    launch_ntt_inv(logN, b, s_);
+    const NttRoute r = ntt_inv_route(ntt_shape(b, false, true), ntt_switches());
+    for (int i = 0; i < r.nparts; ++i)
+        for (int k = 0; k < r.part[i].nsteps; ++k) launch_ntt_step(r.part[i].step[k], b, false, s_);
 }
 
 // ------------------------------------------------------------------ ring level
@@ -978,8 +985,8 @@ void Context::decompose_batch(int level, const std::vector<const u64*>& src, con
             bool h16 = false;
             if (logN == 16 && !masked_ && d_psi31) {
                 NttBatch q{};                                  // the launch as ntt_fwd_launch will see it: does every class part run on H16?
-                q.mods = d_mods; slots_qp(q, level); q.nouter = n * nb; q.prestaged = 1; q.psi31 = d_psi31; q.no_h16 = 0;
-                h16 = ntt_fwd_prestaged_oop_ok(logN, q, small_q_.data());
+                slots_qp(q, level); q.nouter = n * nb; q.prestaged = 1;
+                h16 = ntt_prestaged_on_h16(ntt_shape(q, false, false), ntt_switches());
             }
             bool radix4 = h16 && radix4_env && d_tb30 && d_tw30;
             // (what the H16 sub-transforms then load is below 22.2 p, not 4 p: a U-class modulus -- never reduced -- has to hold that input, 14 stages

@@ -613,7 +613,7 @@ __device__ __forceinline__ void fwd_body(const NttBatch& b, u32* lds) {
         // The first `lpt_long` jobs of the list are the long ones (59/60-bit moduli: +35 % instructions); they go to those lighter CUs, row by
         // row -- 896 limbs with 168 long ones on 256 CUs: no CU carries more than 4.0 limb-units where the list order gives half of them 4.35
         // (141.8 -> 138.3 us for that launch).  A bijection of [0, njobs): every limb is still transformed exactly once.
-        // (every quotient of the mapping is a launch constant computed by launch_ntt16_fwd -- NttBatch::lpt -- or a multiply-high by a
+        // (every quotient of the mapping is a launch constant computed by launch_ntt16_step -- NttBatch::lpt -- or a multiply-high by a
         // precomputed reciprocal on the scalar unit: an integer division here runs on the VALU, in all sixteen waves, for every limb)
         int job = job2, half_pass = 0;
         if constexpr (!SPLIT) {
@@ -1197,145 +1197,49 @@ __global__ void __launch_bounds__(NT, 8) ntt14_inv_kernel(NttBatch b) {
 }  // namespace h16
 
 // ------------------------------------------------------------------ launcher
-namespace {
-struct LaunchState16 { std::mutex mu; int resident[64] = {}; };      // per device, see ntt_kernels.hip
-}
-namespace {
-int resident16(size_t lds) {
+// The steps of a route (ntt_route.h) that run on this file's kernels.  `part`: slots ordered with the big-modulus limbs (the longer jobs) first and
+// small_slots set (whole launches), or the slots of one modulus class (`small`: 31 q < 2^62 for every slot) for the sub-transforms of N = 2^16.
+void launch_ntt16_step(const NttStep& s, const NttBatch& part, bool small, hipStream_t st) {
     using namespace h16;
-    static LaunchState16 ls;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> g(ls.mu);
-    if (!ls.resident[dev & 63]) {
-        (void)hipFuncSetAttribute((const void*)ntt16_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)ntt16_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)ntt16_fwd_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)ntt14_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)ntt14_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)ntt14_fwd_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int cus = 256, per = 1;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)ntt16_fwd_kernel<true>, NT, lds) != hipSuccess || per < 1) per = 1;
-        // (grid size, LPT placement and half-limb jobs all rest on this figure: take the minimum over the kernels that share it)
-        const void* others[] = {(const void*)ntt16_fwd_kernel<false>, (const void*)ntt16_fwd_split_kernel, (const void*)ntt14_fwd_kernel<true>,
-                                (const void*)ntt14_fwd_kernel<false>, (const void*)ntt14_fwd_split_kernel};
-        for (const void* f : others) { int p2 = per; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, f, NT, lds) == hipSuccess && p2 >= 1 && p2 < per) per = p2; }
-        ls.resident[dev & 63] = cus * per;
-    }
-    return ls.resident[dev & 63];
-}
-}
-// launch constants of the job walk (fwd_body): reciprocals for the scalar multiply-high divisions and the placement of the long jobs
-static int ab_ntt16() { static const int v = MKHE_AB_INT("MKHE_NTT16", 1); return v; }
-static int ab_ntt16_min() { static const int v = MKHE_AB_INT("MKHE_NTT16_MIN", 128); return v; }
-static unsigned magic_of(int d) { return d > 1 ? (unsigned)((1ull << 32) / (unsigned)d + 1) : 0u; }      // (0: divisor 1, see udiv_magic)
-static void fill_job_constants(NttBatch& c, int njobs, int blocks, int lpt_long) {
-    if (njobs >= 65536 || c.nouter >= 65536) throw std::runtime_error("mkhe: internal: an H16 launch of 2^16 limbs or more");
-    c.magic_nouter = magic_of(c.nouter);
-    c.magic_opi = magic_of(c.nitems > 0 ? c.outers_per_item : 1);
-    c.lpt = NttBatch::Lpt{};
-    const int C = blocks >> 1;
-    if (lpt_long > 0 && C > 0 && blocks == 2 * C && njobs > blocks && njobs % C != 0) {
-        const int r = njobs % C, w = C - r, q = njobs / C;             // CUs 0 .. r-1 own one position more; w light CUs; q complete rows
-        const int B = lpt_long < q * w ? lpt_long : q * w;             // long jobs that find a light position
-        c.lpt.B = B; c.lpt.C = C; c.lpt.r = r; c.lpt.full = B / w; c.lpt.rem = B - (B / w) * w; c.lpt.magic_C = magic_of(C);
-    }
-}
-// sub-transforms of a split N = 2^16 launch (one modulus class per launch: `small` = 31 q < 2^62 for every slot)
-bool ntt16_split_ok(const NttBatch& c) {
-    const int on = ab_ntt16(), minl = ab_ntt16_min();
-    // (the job walk divides by multiply-high reciprocals that are exact below 2^16: larger launches keep the round-1 kernels)
-    return on && !c.no_h16 && c.psi31 && (c.split == 1 || c.split == 2) && !c.reduce_in && c.nslots <= 64 && 2 * c.nslots * c.nouter >= minl &&
-           (long)c.nslots * c.nouter < 65536 && c.nouter < 65536;
-}
-void launch_ntt16_fwd_split(const NttBatch& b, bool small, hipStream_t st) {
-    using namespace h16;
-    NttBatch c = b;
-    c.small_slots = small ? ~0ull : 0ull;
-    c.lazy_out = 0;
+    NttBatch c = ntt_step_batch(part, s);
     const size_t lds = (size_t)LDS_WORDS * sizeof(u32);
-    const int resident = resident16(lds);
-    const int need = (c.nslots * c.nouter) << c.split;
-    fill_job_constants(c, c.nslots * c.nouter, 0, 0);
-    if (c.split == 2) hipLaunchKernelGGL(ntt14_fwd_split_kernel, dim3(need < resident ? need : resident), dim3(NT), lds, st, c);
-    else hipLaunchKernelGGL(ntt16_fwd_split_kernel, dim3(need < resident ? need : resident), dim3(NT), lds, st, c);
-}
-// inverse: launches of at least MKHE_NTT16_INV_MIN one-pass jobs (2^14 points each); the caller (launch_ntt_inv) runs the cross stages of
-// N = 2^15 / 2^16 behind it.  b.psi31 / b.psi are the INVERSE tables here, b.inv31c the pairs of the last stage.
-bool ntt16_inv_ok(int logN, const NttBatch& b) {
-    static const int on = MKHE_AB_INT("MKHE_NTT16_INV", 1), minj = MKHE_AB_INT("MKHE_NTT16_INV_MIN", 256), minj14 = MKHE_AB_INT("MKHE_NTT14_INV_MIN", 129);
-    if (!on || b.no_h16 || !b.psi31 || !b.inv31c || b.split || b.nslots > 64 || logN < 14 || logN > 16) return false;
-    const int limbs = b.vi ? b.vi_jobs : b.nslots * b.nouter;
-    // N = 2^14 (round 4): up to 128 limbs run as LDS sub-transforms (launch_ntt_inv), everything above comes here -- between 129 and 255 limbs
-    // the launch used to fall to the round-1 register kernel, 69 us per launch whatever its size: the batched evaluation of the small rings
-    // (batch.hip) lives in exactly that range
-    if (logN == 14) return limbs >= minj14 && b.nslots * b.nouter < 65536;
-    return (limbs << (logN - 14)) >= minj && b.nslots * b.nouter < 65536;
-}
-void launch_ntt16_inv(const NttBatch& b, hipStream_t st, int logN) {
-    using namespace h16;
-    NttBatch c = b;
-    c.split = logN - 14;
-    const size_t lds = (size_t)LDS_WORDS * sizeof(u32);
-    static LaunchState16 ls;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int resident = 0;
-    {
-        std::lock_guard<std::mutex> g(ls.mu);
-        if (!ls.resident[dev & 63]) {
-            (void)hipFuncSetAttribute((const void*)ntt14_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            int cus = 256, per = 1;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)ntt14_inv_kernel, NT, lds) != hipSuccess || per < 1) per = 1;
-            ls.resident[dev & 63] = cus * per;
-        }
-        resident = ls.resident[dev & 63];
+    const int limbs = c.nslots * c.nouter;
+    if (s.kernel == NK_H14_INV) {
+        // c.psi31 / c.psi are the INVERSE tables here, c.inv31c the pairs of the last stage; the route runs the cross stages of N = 2^15 / 2^16 behind it
+        static NttLaunchCache cache;
+        const int resident = ntt_resident_workgroups(cache, {(const void*)ntt14_inv_kernel}, NT, lds);
+        fill_job_constants(c, limbs, 0, 0, 2);
+        c.magic_vi_np = magic_of(c.vi ? c.vi_np : 1);
+        hipLaunchKernelGGL(ntt14_inv_kernel, dim3(s.jobs < resident ? s.jobs : resident), dim3(NT), lds, st, c);
+        return;
     }
-    const int need = (c.nslots * c.nouter) << c.split;
-    fill_job_constants(c, c.nslots * c.nouter, 0, 0);
-    c.magic_vi_np = magic_of(c.vi ? c.vi_np : 1);
-    hipLaunchKernelGGL(ntt14_inv_kernel, dim3(need < resident ? need : resident), dim3(NT), lds, st, c);
-}
-bool ntt16_ok(int logN, const NttBatch& b) {
-    static const int minl14 = MKHE_AB_INT("MKHE_NTT14_MIN", 128);
-    const int on = ab_ntt16(), minl = ab_ntt16_min();
-    if (!on || b.no_h16 || !b.psi31 || b.split || b.prestaged || b.nslots > 64) return false;
-    if ((long)b.nslots * b.nouter >= 65536 || b.nouter >= 65536) return false;      // (fill_job_constants: reciprocals exact below 2^16)
-    if (logN == 14) return b.nslots * b.nouter >= minl14;      // (one pass: a workgroup has loaded its whole limb before it stores, in place included)
-    return logN == 15 && b.nslots * b.nouter >= minl;
-}
-void launch_ntt16_fwd(const NttBatch& b, const unsigned char* small_q, hipStream_t st, int logN) {
-    using namespace h16;
-    NttBatch c = b;
-    // big-modulus limbs (the longer jobs) first, as in launch_ntt_fwd_mixed
-    c.small_slots = 0; c.nslots = 0;
-    for (int cls = 0; cls < 2; ++cls)
-        for (int s = 0; s < b.nslots; ++s)
-            if ((small_q[b.mod[s]] != 0) == (cls == 1)) {
-                c.mod[c.nslots] = b.mod[s]; c.pos[c.nslots] = b.pos[s];
-                if (cls) c.small_slots |= 1ull << c.nslots;
-                ++c.nslots;
-            }
-    const size_t lds = (size_t)LDS_WORDS * sizeof(u32);
-    c.lazy_out = 0;                                    // (no start delay of the co-resident workgroups: measured, not kept -- docs/DESIGN_HISTORY.md)
+    static NttLaunchCache cache;
+    const int resident = ntt_resident_workgroups(cache, {(const void*)ntt16_fwd_kernel<true>, (const void*)ntt16_fwd_kernel<false>, (const void*)ntt16_fwd_split_kernel,
+                                                         (const void*)ntt14_fwd_kernel<true>, (const void*)ntt14_fwd_kernel<false>, (const void*)ntt14_fwd_split_kernel}, NT, lds);
+    if (s.kernel == NK_H16_SPLIT || s.kernel == NK_H14_SPLIT) {
+        c.small_slots = small ? ~0ull : 0ull;
+        fill_job_constants(c, limbs, 0, 0, 2);
+        const dim3 grid(s.jobs < resident ? s.jobs : resident);
+        if (s.kernel == NK_H14_SPLIT) hipLaunchKernelGGL(ntt14_fwd_split_kernel, grid, dim3(NT), lds, st, c);
+        else hipLaunchKernelGGL(ntt16_fwd_split_kernel, grid, dim3(NT), lds, st, c);
+        return;
+    }
+    if (s.kernel != NK_H16_FWD && s.kernel != NK_H14_FWD) throw std::runtime_error("mkhe: internal: an NTT step outside the H16 kernels");
     int nbig = 0;                                      // the long jobs lead the slot-major list: every slot of a 59/60-bit modulus, nouter limbs each
     for (int s2 = 0; s2 < c.nslots; ++s2) if (!((c.small_slots >> s2) & 1)) ++nbig;
     const int lpt_long = nbig < c.nslots ? nbig * c.nouter : 0;
-    const int resident = resident16(lds);
-    const int need = c.nslots * c.nouter;
+    const int need = limbs;
     const int blocks = need < resident ? need : resident;
     // half-limb jobs: Decompose launches only (source = ciphertext limbs, destination = hoisted digits: never in place) whose whole limbs would
     // leave the last row of positions ragged (896 limbs on 256 CUs: 134.0 -> 128.7 us); a launch that deals whole limbs evenly keeps them -- as
     // half-limb jobs the 1792-limb launch (7 limbs per CU either way) is 5 % SLOWER (256 -> 270 us, measured twice on one box; MKHE_NTT16_HALVES=2
     // forces them for every launch)
-    static const int halfj = MKHE_AB_INT("MKHE_NTT16_HALVES", 1);
+    const int halfj = ntt_switches().ntt16_halves;
     const int cus = resident >> 1;
-    c.half_jobs = (halfj && logN == 15 && c.reduce_in && need > resident && 2 * need < 65536 && (halfj == 2 || (cus > 0 && need % cus != 0))) ? 1 : 0;
+    c.half_jobs = (halfj && s.kernel == NK_H16_FWD && c.reduce_in && need > resident && 2 * need < 65536 && (halfj == 2 || (cus > 0 && need % cus != 0))) ? 1 : 0;
     if (c.half_jobs && need % 8 == 0 && lpt_long % 8 == 0) c.half_jobs = 2;      // 8 limbs x 2 passes per block of 16 positions (see fwd_body)
-    fill_job_constants(c, c.half_jobs ? 2 * need : need, blocks, c.half_jobs ? 2 * lpt_long : lpt_long);
-    if (logN == 14) {
+    fill_job_constants(c, c.half_jobs ? 2 * need : need, blocks, c.half_jobs ? 2 * lpt_long : lpt_long, 2);
+    if (s.kernel == NK_H14_FWD) {
         if (c.reduce_in) hipLaunchKernelGGL(ntt14_fwd_kernel<true>, dim3(blocks), dim3(NT), lds, st, c);
         else hipLaunchKernelGGL(ntt14_fwd_kernel<false>, dim3(blocks), dim3(NT), lds, st, c);
         return;

@@ -61,15 +61,7 @@ constexpr int RING = MKHE_H32_RING;        // twiddle pairs (4 VGPRs each) live 
 #ifndef MKHE_H32_PREFETCH
 #define MKHE_H32_PREFETCH 0                // (experiment, slower by 3 %: DESIGN.md section 10) the next limb's source loads are issued between the stores of this one (register by register)
 #endif
-#ifndef MKHE_NTT32_DEFAULT
-// MKHE_NTT32: 0 = every launch on the two-pass H16 kernel, 1 = this kernel wherever it applies, 2 (default) = per launch shape the engine times a block
-// of launches of each kernel inside the caller's workload, once its clocks have settled, and keeps the faster one (Context::ntt_pick).  Back to back
-// this kernel is ahead on every part (230 against 244 us for 1792 limbs, same call); inside the MulRelin it is ahead by 2-5 % on most parts (0.526-0.542
-// against 0.506-0.519 of the roofline, eight same-call pairs, MulRelin/s + 0-2 %) and BEHIND by 6 % on some (0.46-0.48 against 0.49-0.515, MulRelin/s
-// - 1.6 %: parts that sit at 1255 W and 2.09 GHz under it where the others reach 1400 W and 2.2-2.3 GHz, with the same configured cap -- the two-pass
-// kernel's in-context time is the same on both kinds): profiles/README.md.
-#define MKHE_NTT32_DEFAULT 2
-#endif
+// (which launches take this kernel: MKHE_NTT32 and Context::ntt_pick, see ntt_route.h)
 template <int... I, class F> __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 template <bool SW, bool UC> __device__ __forceinline__ void bf(u64& U, u64& V, const u64* tw, const MC& c) {
@@ -572,76 +564,22 @@ __global__ void __launch_bounds__(NT, 4) __attribute__((amdgpu_num_vgpr(128))) n
 }  // namespace h32
 
 // ------------------------------------------------------------------ launcher
-namespace {
-struct LaunchState32 { std::mutex mu; int resident[64] = {}; };
-unsigned magic_of32(int d) { return d > 1 ? (unsigned)((1ull << 32) / (unsigned)d + 1) : 0u; }
-// CU count of the CURRENT device, cached per device behind a mutex (a process may hold contexts on several GPUs, driven by several threads)
-int device_cus32() {
-    static std::mutex mu; static int cus_of[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> g(mu);
-    int& c = cus_of[dev & 63];
-    if (!c) { int v = 256; (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); c = v > 0 ? v : 256; }
-    return c;
-}
-}
-int ntt32_mode() { static const int on = MKHE_CFG_INT("MKHE_NTT32", MKHE_NTT32_DEFAULT); return on; }
-bool ntt32_ok(int logN, const NttBatch& b) {
-    static const int on = MKHE_CFG_INT("MKHE_NTT32", MKHE_NTT32_DEFAULT), minl = MKHE_AB_INT("MKHE_NTT32_MIN", 512);
-    if (!on || logN != 15 || b.no_h16 || !b.psi31 || !b.psi31c || !b.psi31b || b.split || b.prestaged || b.nslots > 64) return false;
-    if ((long)b.nslots * b.nouter >= 65536 || b.nouter >= 65536) return false;      // (job-walk reciprocals: exact below 2^16)
-    // (one workgroup per CU, whole limbs: a launch that does not deal the limbs evenly leaves CUs idle in its last round, where the H16 kernel deals
-    // half-limb jobs -- which kernel a shape takes is measured, Context::ntt_pick)
-    return b.nslots * b.nouter >= minl;
-}
-void launch_ntt32_fwd(const NttBatch& b, const unsigned char* small_q, hipStream_t st) {
+// `part`: the big-modulus limbs (the longer jobs) first, then the moduli between the classes, the U class last (the kernel runs the two
+// instantiations of its limb in two loops, in this order); small_slots = everything behind the big-modulus limbs
+void launch_ntt32_step(const NttStep& s, const NttBatch& part, hipStream_t st) {
     using namespace h32;
-    NttBatch c = b;
-    // big-modulus limbs (the longer jobs) first, as in launch_ntt16_fwd
-    // ... then the moduli between the classes, the U class last (the kernel runs the two instantiations of its limb in two loops, in this order)
-    c.small_slots = 0; c.nslots = 0;
-    for (int cls = 0; cls < 3; ++cls)
-        for (int s = 0; s < b.nslots; ++s) {
-            const bool small = small_q[b.mod[s]] != 0, u = small && ((b.u_mods >> b.mod[s]) & 1);
-            if ((cls == 0 && !small) || (cls == 1 && small && !u) || (cls == 2 && u)) {
-                c.mod[c.nslots] = b.mod[s]; c.pos[c.nslots] = b.pos[s];
-                if (cls) c.small_slots |= 1ull << c.nslots;
-                ++c.nslots;
-            }
-        }
-    if (c.nslots != b.nslots) throw std::runtime_error("mkhe: internal: a U-class modulus outside the small class");
+    if (s.kernel != NK_H32_FWD) throw std::runtime_error("mkhe: internal: an NTT step outside the H32 kernel");
+    NttBatch c = ntt_step_batch(part, s);
     const size_t lds = (size_t)LDS_WORDS * sizeof(u32);
-    static LaunchState32 ls;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int resident = 0;
-    {
-        std::lock_guard<std::mutex> g(ls.mu);
-        if (!ls.resident[dev & 63]) {
-            (void)hipFuncSetAttribute((const void*)ntt32_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)ntt32_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            ls.resident[dev & 63] = cus;                      // one workgroup per CU (133 KB of LDS, 1024 threads x 128 VGPRs)
-        }
-        resident = ls.resident[dev & 63];
-    }
+    static NttLaunchCache cache;
+    const int resident = ntt_resident_workgroups(cache, {(const void*)ntt32_fwd_kernel<true>, (const void*)ntt32_fwd_kernel<false>}, NT, lds,
+                                                 1);      // one workgroup per CU (133 KB of LDS, 1024 threads x 128 VGPRs)
     const int need = c.nslots * c.nouter;
     const int blocks = need < resident ? need : resident;
     int nbig = 0;
     for (int s2 = 0; s2 < c.nslots; ++s2) if (!((c.small_slots >> s2) & 1)) ++nbig;
-    const int lpt_long = nbig < c.nslots ? nbig * c.nouter : 0;
-    c.magic_nouter = magic_of32(c.nouter);
-    c.magic_opi = magic_of32(c.nitems > 0 ? c.outers_per_item : 1);
-    c.lpt = NttBatch::Lpt{};
-    c.half_jobs = 0; c.lazy_out = 0;
-    const int C = blocks;
-    if (lpt_long > 0 && C > 0 && need > blocks && need % C != 0) {
-        const int r = need % C, w = C - r, q = need / C;
-        const int B = lpt_long < q * w ? lpt_long : q * w;
-        c.lpt.B = B; c.lpt.C = C; c.lpt.r = r; c.lpt.full = B / w; c.lpt.rem = B - (B / w) * w; c.lpt.magic_C = magic_of32(C);
-    }
+    c.half_jobs = 0;
+    fill_job_constants(c, need, blocks, nbig < c.nslots ? nbig * c.nouter : 0, 1);
     if (c.reduce_in) hipLaunchKernelGGL(ntt32_fwd_kernel<true>, dim3(blocks), dim3(NT), lds, st, c);
     else hipLaunchKernelGGL(ntt32_fwd_kernel<false>, dim3(blocks), dim3(NT), lds, st, c);
 }

@@ -30,6 +30,9 @@
 // mkrlwe/keyswitch.go:29-30,58,88,114-115,206 and keyswitch_hoisted.go:36-37,120-143.
 #pragma once
 #include "modarith.h"
+#include "ntt_route.h"
+#include <initializer_list>
+#include <mutex>
 
 // Timing experiments that produce WRONG RESULTS on purpose -- the MKHE_*_X_* switches of the NTT kernels (butterflies, LDS exchanges, result
 // stores, source or twiddle loads taken out: tools/ntt16_ablation.sh, tools/build_variant.sh) -- exist only in builds that say so with
@@ -69,8 +72,8 @@ struct NttBatch {
                             // for engine-internal outputs whose only consumers are Montgomery products (hoisted digits)
     int split;              // N = 2^16: the register-resident kernels transform the two halves of a limb as 2^15-point
                             // sub-transforms (twiddle rows of 2^16 words, root index 2 + half); the cross-half radix-2 stage
-                            // runs as a separate streaming pass (launch_ntt_* do both)
-    unsigned long long small_slots;   // mixed forward launch (launch_ntt_fwd_mixed): bit s set = slot s is a small-modulus (MODE 1) limb
+                            // runs as a separate streaming pass (the steps of a route: ntt_route.h)
+    unsigned long long small_slots;   // launches of both modulus classes (order_slots_by_class): bit s set = slot s is a small-modulus (MODE 1) limb
     int prestaged;          // forward, split launches only: 1 = the cross-half stage was already applied by the producer of src
                             // (decomp_spread_kernel with first_stage): only the sub-transforms run, in place on dst.  2 (N = 2^16, H16 only) = the
                             // first TWO stages were (first_stage = 2): what remains are four independent 2^14-point sub-transforms per limb,
@@ -127,31 +130,38 @@ struct NttBatch {
 };
 constexpr int VI_SUMS = 3 * VI_MAX + 1;   // summands an inverse job may have at its load: members x parts + the Q-only extra (Context::ext_front keeps to it)
 
-// small_q[m] != 0 marks moduli with 34q < 2^63 (forward NTT without in-loop reductions).  The forward
-// kernels are specialised per modulus class: split_ntt_fwd cuts the slots of `b` into one batch per
-// class (returns how many, small-modulus class first), launch_ntt_fwd_class launches one of them.
-int  split_ntt_fwd(const NttBatch& b, const unsigned char* small_q, NttBatch out[2]);
-void launch_ntt_fwd_class(int logN, const NttBatch& b, hipStream_t st);
-bool ntt_fwd_prestaged_oop_ok(int logN, const NttBatch& b, const unsigned char* small_q);
-// both modulus classes of `b` in ONE persistent launch (N = 2^15 Decompose launches that fill the chip several times over);
-// ntt_fwd_mixed_ok: false when the launch does not qualify (the caller then issues one launch per class)
-bool ntt_fwd_mixed_ok(int logN, const NttBatch& b, const unsigned char* small_q);
-void launch_ntt_fwd_mixed(int logN, const NttBatch& b, const unsigned char* small_q, hipStream_t st);
-void launch_ntt_inv(int logN, const NttBatch& b, hipStream_t st);
-// N = 2^15 launches that fill the chip (ntt16_kernels.hip): 16 coefficients per thread, two workgroups per CU, both modulus
-// classes in one persistent launch.  ntt16_ok: false when the launch does not qualify (MKHE_NTT16=0 switches the path off).
-bool ntt16_inv_ok(int logN, const NttBatch& b);
-void launch_ntt16_inv(const NttBatch& b, hipStream_t st, int logN);
-bool ntt16_ok(int logN, const NttBatch& b);
-void launch_ntt16_fwd(const NttBatch& b, const unsigned char* small_q, hipStream_t st, int logN = 15);
-// N = 2^15 launches of several limbs per CU, one pass per limb (ntt32_kernels.hip: one 1024-thread workgroup per CU, 32 coefficients per thread)
-bool ntt32_ok(int logN, const NttBatch& b);
-int ntt32_mode();      // MKHE_NTT32: 0 off, 1 on, 2 (default) = Context::ntt_pick times both kernels per launch shape inside the workload and keeps the faster
-void launch_ntt32_fwd(const NttBatch& b, const unsigned char* small_q, hipStream_t st);
-// the same kernel on the 2^15-point sub-transforms of a split N = 2^16 launch (one modulus class per launch)
-bool ntt16_split_ok(const NttBatch& c);
-void launch_ntt16_fwd_split(const NttBatch& c, bool small, hipStream_t st);
+// Which kernels a launch runs is decided by ntt_fwd_route / ntt_inv_route (ntt_route.h) from the launch's shape and ntt_switches(); Context::ntt_fwd_launch /
+// ntt_inv_launch walk the steps.  A forward route may have one part per modulus class (the kernels are specialised): order_slots_by_class cuts the part's
+// slots out of the launch, ntt_step_batch makes the kernel argument of one step from the part's batch, launch_ntt_step launches it.
+const NttSwitches& ntt_switches();       // the MKHE_* values of the routes, read once per process
+// the slots of `b` that are in cls[0], then those in cls[1], ... (bit s of a mask = slot s; slots in no class are left out); small_slots = the slots
+// taken from cls[1] on.  The long jobs (big-modulus limbs) lead the list, so that a ragged last round holds the cheap kind.
+NttBatch order_slots_by_class(const NttBatch& b, const unsigned long long* cls, int nclasses);
+inline NttBatch ntt_step_batch(const NttBatch& part, const NttStep& s) {
+    NttBatch c = part;
+    if (s.in_place) {
+        c.src = part.dst; c.src_outer = part.dst_outer; c.src_inner = part.dst_inner; c.src_mapped = part.dst_mapped;
+        for (int i = 0; i < NTT_MAX_ITEMS; ++i) c.src_items[i] = part.dst_items[i];
+    }
+    if (!s.dec) c.reduce_in = 0;
+    c.split = s.split;
+    return c;
+}
+// `small`: the part is the small-modulus class (NS_SMALL).  launch_ntt_step hands the H16 / H32 kernels' steps to their translation units.
+void launch_ntt_step(const NttStep& s, const NttBatch& part, bool small, hipStream_t st);
+void launch_ntt16_step(const NttStep& s, const NttBatch& part, bool small, hipStream_t st);      // ntt16_kernels.hip
+void launch_ntt32_step(const NttStep& s, const NttBatch& part, hipStream_t st);                  // ntt32_kernels.hip
 
+// Launch state is kept PER DEVICE (a process may hold contexts on several GPUs: the function attribute has to be set and the persistent grid sized on
+// each of them) and behind a mutex (contexts may be driven from different host threads).  ntt_resident_workgroups sets the dynamic-LDS attribute of
+// every kernel of the list once per device and returns the workgroups that are co-resident on the whole chip -- the minimum over the list (grid size,
+// placement of the long jobs and half-limb jobs all rest on one figure); per_cu > 0: that many per CU, no occupancy query.
+struct NttLaunchCache { std::mutex mu; int resident[64] = {}; };
+int ntt_resident_workgroups(NttLaunchCache& cache, std::initializer_list<const void*> kernels, int threads, size_t lds, int per_cu = 0);
+// launch constants of the H16 / H32 job walk: reciprocals for the scalar multiply-high divisions, and the placement of the `lpt_long` long jobs
+// that lead the list on the CUs that own fewer positions -- wg_per_cu workgroups share a CU (H16: 2, H32: 1), `blocks` must be a whole number of CUs
+unsigned magic_of(int d);
+void fill_job_constants(NttBatch& c, int njobs, int blocks, int lpt_long, int wg_per_cu);
 
 // Small rings (N = 2^14), small launches: the forward sub-transforms of an engine-internal Decompose and the inner products that consume them in ONE
 // kernel (round 5).  A key switch of one ciphertext there is a chain of launches of a few dozen limbs that last as long as one workgroup each; the
@@ -174,7 +184,7 @@ struct ExtFusedArgs {
     const u64* psiinv;                     // inv != 0: the inverse twiddles [nmod][N] and
     const u64* aux;                        // the inverse constants (NttBatch::aux)
     int inv;                               // the products leave the kernel after their inverse 2^11-point sub-transforms ([0, 2q), N^-1 folded in): the
-                                           // caller follows with launch_ntt_inv_cross8_sum instead of launch_ntt_inv (always two groups of threads)
+                                           // caller follows with launch_ntt_inv_cross8_sum instead of the inverse route (always two groups of threads)
     long digit_stride;
     int nb, nslots, N, logN, nv;
 };

@@ -694,40 +694,6 @@ __global__ void __launch_bounds__(SmGeo<LOGM>::T) ntt_inv_ldsS_kernel(NttBatch b
     sm_phase<0, 3, false, true, 2, 2, LOGM, true>(src, dst, sm_lds, psi, root, t, md, ninvR, 0, 1, nullptr, t0);
 }
 
-// cross-block radix-2 passes below the first one (level L >= 1: blocks of N >> L coefficients, twiddle index 2^L + block),
-// in place on dst; forward: values < 4q in and out; inverse: [0,2q) in and out (N^-1 already folded in)
-__global__ void __launch_bounds__(SPLIT_THREADS) ntt_pass_fwd_kernel(NttBatch b, int logN, int L) {
-    const int N = 1 << logN, G = N >> (L + 1);
-    gcptr src; gptr dst; int m, outer;
-    job_pointers(b, blockIdx.y, src, dst, m, outer);
-    const Mod md = b.mods[m];
-    const u64 q = md.q, q2 = md.q2;
-    const u32 ninv = md.ninv32;
-    for (int j = blockIdx.x * SPLIT_THREADS + threadIdx.x; j < (N >> 1); j += gridDim.x * SPLIT_THREADS) {
-        const int blk = j >> (logN - L - 1), off = j - blk * G, i0 = blk * 2 * G + off;         // G = 2^(logN - L - 1)
-        const u64 w = b.psi[(long)m * N + (1 << L) + blk];
-        const u64 U = csub(dst[i0], q2), V = dst[i0 + G];
-        const u64 Tm = mont_mul_sdu(V, w, md.qs, q, ninv);
-        dst[i0] = U + Tm;
-        dst[i0 + G] = U + (q2 - Tm);
-    }
-}
-__global__ void __launch_bounds__(SPLIT_THREADS) ntt_pass_inv_kernel(NttBatch b, int logN, int L) {
-    const int N = 1 << logN, G = N >> (L + 1);
-    gcptr src; gptr dst; int m, outer;
-    if (!job_pointers<true>(b, blockIdx.y, src, dst, m, outer)) return;
-    const Mod md = b.mods[m];
-    const u64 q = md.q, q2 = md.q2;
-    const u32 ninv = md.ninv32;
-    for (int j = blockIdx.x * SPLIT_THREADS + threadIdx.x; j < (N >> 1); j += gridDim.x * SPLIT_THREADS) {
-        const int blk = j >> (logN - L - 1), off = j - blk * G, i0 = blk * 2 * G + off;         // G = 2^(logN - L - 1)
-        const u64 w = b.psi[(long)m * N + (1 << L) + blk];
-        const u64 U = dst[i0], V = dst[i0 + G];
-        dst[i0] = csub(U + V, q2);
-        dst[i0 + G] = mont_mul_sdu(U + q2 - V, w, md.qs, q, ninv);
-    }
-}
-
 // The two outermost stages in ONE streaming pass (low-latency path at N = 2^15: four 2^13-point sub-transforms per limb):
 // every thread owns the coefficients j, j + N/4, j + N/2, j + 3N/4.  Forward: src -> dst (optionally with the Decompose
 // reduction), values < 4q out; inverse: in place on dst, [0,2q) in (N^-1 folded in by the sub-transforms), canonical or
@@ -1006,277 +972,178 @@ __global__ void __launch_bounds__(NG * 256) ext_fused_lds_kernel(ExtFusedArgs a)
     else extf_body<NG, 0, INV>(a, sm_lds, md, m, part, v);
 }
 
-static NttBatch in_place_of_dst(const NttBatch& b) {
+// ------------------------------------------------------------------ launchers
+const NttSwitches& ntt_switches() {
+    static const NttSwitches w = [] {
+        const NttSwitches d;
+        NttSwitches v;
+        v.ntt32 = MKHE_CFG_INT("MKHE_NTT32", d.ntt32);
+        v.ntt32_min = MKHE_AB_INT("MKHE_NTT32_MIN", d.ntt32_min);
+        v.ntt16 = MKHE_AB_INT("MKHE_NTT16", d.ntt16);
+        v.ntt16_min = MKHE_AB_INT("MKHE_NTT16_MIN", d.ntt16_min);
+        v.ntt14_min = MKHE_AB_INT("MKHE_NTT14_MIN", d.ntt14_min);
+        v.ntt16_inv = MKHE_AB_INT("MKHE_NTT16_INV", d.ntt16_inv);
+        v.ntt16_inv_min = MKHE_AB_INT("MKHE_NTT16_INV_MIN", d.ntt16_inv_min);
+        v.ntt14_inv_min = MKHE_AB_INT("MKHE_NTT14_INV_MIN", d.ntt14_inv_min);
+        v.ntt_lds = MKHE_AB_INT("MKHE_NTT_LDS", d.ntt_lds);
+        v.ntt16_radix4 = MKHE_AB_INT("MKHE_NTT16_RADIX4", d.ntt16_radix4);
+        v.ntt16_halves = MKHE_AB_INT("MKHE_NTT16_HALVES", d.ntt16_halves);
+        return v;
+    }();
+    return w;
+}
+
+int ntt_resident_workgroups(NttLaunchCache& cache, std::initializer_list<const void*> kernels, int threads, size_t lds, int per_cu) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> g(cache.mu);
+    int& resident = cache.resident[dev & 63];
+    if (!resident) {
+        int cus = 256, per = per_cu;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        for (const void* f : kernels) {
+            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (per_cu > 0) continue;
+            int p = 1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, f, threads, lds) != hipSuccess || p < 1) p = 1;      // (a failed query counts as one per CU)
+            if (!per || p < per) per = p;
+        }
+        resident = cus * per;
+    }
+    return resident;
+}
+unsigned magic_of(int d) { return d > 1 ? (unsigned)((1ull << 32) / (unsigned)d + 1) : 0u; }      // (0: divisor 1, see udiv_magic)
+void fill_job_constants(NttBatch& c, int njobs, int blocks, int lpt_long, int wg_per_cu) {
+    if (njobs >= 65536 || c.nouter >= 65536) throw std::runtime_error("mkhe: internal: an H16 / H32 launch of 2^16 limbs or more");
+    c.magic_nouter = magic_of(c.nouter);
+    c.magic_opi = magic_of(c.nitems > 0 ? c.outers_per_item : 1);
+    c.lpt = NttBatch::Lpt{};
+    const int C = blocks / wg_per_cu;
+    if (lpt_long > 0 && C > 0 && blocks == wg_per_cu * C && njobs > blocks && njobs % C != 0) {
+        const int r = njobs % C, w = C - r, q = njobs / C;             // CUs 0 .. r-1 own one position more; w light CUs; q complete rows
+        const int B = lpt_long < q * w ? lpt_long : q * w;             // long jobs that find a light position
+        c.lpt.B = B; c.lpt.C = C; c.lpt.r = r; c.lpt.full = B / w; c.lpt.rem = B - (B / w) * w; c.lpt.magic_C = magic_of(C);
+    }
+}
+NttBatch order_slots_by_class(const NttBatch& b, const unsigned long long* cls, int nclasses) {
     NttBatch c = b;
-    c.src = b.dst; c.src_outer = b.dst_outer; c.src_inner = b.dst_inner; c.src_mapped = b.dst_mapped;
-    for (int i = 0; i < NTT_MAX_ITEMS; ++i) c.src_items[i] = b.dst_items[i];
-    c.reduce_in = 0; c.split = 1;
+    c.nslots = 0; c.small_slots = 0;
+    for (int k = 0; k < nclasses; ++k)
+        for (int s = 0; s < b.nslots; ++s)
+            if ((cls[k] >> s) & 1) {
+                c.mod[c.nslots] = b.mod[s]; c.pos[c.nslots] = b.pos[s];
+                if (k) c.small_slots |= 1ull << c.nslots;
+                ++c.nslots;
+            }
     return c;
 }
 
-// ------------------------------------------------------------------ launchers
-// Launch state is kept PER DEVICE (a process may hold contexts on several GPUs: the function attribute has to be set and the
-// persistent grid sized on each of them) and behind a mutex (contexts may be driven from different host threads).
-namespace {
-struct LaunchState { std::mutex mu; int resident[64] = {}; bool attr[64] = {}; };
-int current_device() { int dev = 0; (void)hipGetDevice(&dev); return dev & 63; }
-}
-// workgroups that are co-resident on the whole chip for this kernel (persistent grid size)
-static int resident_blocks(const void* fn, int threads, size_t lds) {
+// persistent grid of the register-resident kernels (MKHE_NTT_GRID=full in the switches build: one workgroup per limb, for A/B tests)
+static int reg_blocks(NttLaunchCache& cache, const void* fn, int threads, size_t lds, int need) {
+    const int resident = ntt_resident_workgroups(cache, {fn}, threads, lds);
 #ifdef MKHE_SWITCHES
-    if (const char* e = getenv("MKHE_NTT_GRID")) { if (e[0] == 'f') return 1 << 30; }     // "full": one workgroup per limb (A/B testing)
+    if (const char* e = getenv("MKHE_NTT_GRID")) { if (e[0] == 'f') return need; }
 #endif
-    int dev = 0, cus = 256, per = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, threads, lds) != hipSuccess || per < 1) per = 1;
-    return cus * per;
+    return need < resident ? need : resident;
 }
 template <int LOGN, int MODE, bool DEC> static void launch_fwd_t(const NttBatch& b, hipStream_t st) {
     using G = Geo<LOGN>;
-    static LaunchState ls;
+    static NttLaunchCache cache;
     const size_t lds = (size_t)G::LPB * lds_words<LOGN>() * sizeof(u32);
-    int resident;
-    {
-        const int dev = current_device();
-        std::lock_guard<std::mutex> g(ls.mu);
-        if (!ls.attr[dev]) { (void)hipFuncSetAttribute((const void*)ntt_fwd_kernel<LOGN, MODE, DEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); ls.attr[dev] = true; }
-        if (!ls.resident[dev]) ls.resident[dev] = resident_blocks((const void*)ntt_fwd_kernel<LOGN, MODE, DEC>, G::BT, lds);
-        resident = ls.resident[dev];
-    }
     const int need = (((b.nslots * b.nouter) << b.split) + G::LPB - 1) / G::LPB;
-    const int blocks = need < resident ? need : resident;
+    const int blocks = reg_blocks(cache, (const void*)ntt_fwd_kernel<LOGN, MODE, DEC>, G::BT, lds, need);
     hipLaunchKernelGGL((ntt_fwd_kernel<LOGN, MODE, DEC>), dim3(blocks), dim3(G::BT), lds, st, b);
 }
 template <int LOGN, bool VI> static void launch_inv_tv(const NttBatch& b, hipStream_t st) {
     using G = Geo<LOGN>;
-    static LaunchState ls;
+    static NttLaunchCache cache;
     const size_t lds = (size_t)G::LPB * lds_words<LOGN>() * sizeof(u32);
-    int resident;
-    {
-        const int dev = current_device();
-        std::lock_guard<std::mutex> g(ls.mu);
-        if (!ls.attr[dev]) { (void)hipFuncSetAttribute((const void*)ntt_inv_kernel<LOGN, VI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); ls.attr[dev] = true; }
-        if (!ls.resident[dev]) ls.resident[dev] = resident_blocks((const void*)ntt_inv_kernel<LOGN, VI>, G::BT, lds);
-        resident = ls.resident[dev];
-    }
     const int need = (((b.nslots * b.nouter) << b.split) + G::LPB - 1) / G::LPB;
-    const int blocks = need < resident ? need : resident;
+    const int blocks = reg_blocks(cache, (const void*)ntt_inv_kernel<LOGN, VI>, G::BT, lds, need);
     hipLaunchKernelGGL((ntt_inv_kernel<LOGN, VI>), dim3(blocks), dim3(G::BT), lds, st, b);
 }
-template <int LOGN> static void launch_inv_t(const NttBatch& b, hipStream_t st) {
-    if (b.vi) launch_inv_tv<LOGN, true>(b, st); else launch_inv_tv<LOGN, false>(b, st);
+// (the routes ask for 2^10 .. 2^15 points only: ntt_route.h need_reg)
+template <int MODE, bool DEC> static void launch_fwd_mode(int logn, const NttBatch& b, hipStream_t st) {
+    switch (logn) {
+        case 10: return launch_fwd_t<10, MODE, DEC>(b, st);
+        case 11: return launch_fwd_t<11, MODE, DEC>(b, st);
+        case 12: return launch_fwd_t<12, MODE, DEC>(b, st);
+        case 13: return launch_fwd_t<13, MODE, DEC>(b, st);
+        case 14: return launch_fwd_t<14, MODE, DEC>(b, st);
+        case 15: return launch_fwd_t<15, MODE, DEC>(b, st);
+    }
+    throw std::runtime_error("mkhe: internal: register-resident forward NTT of a size no kernel has");
+}
+template <bool VI> static void launch_inv_mode(int logn, const NttBatch& b, hipStream_t st) {
+    switch (logn) {
+        case 10: return launch_inv_tv<10, VI>(b, st);
+        case 11: return launch_inv_tv<11, VI>(b, st);
+        case 12: return launch_inv_tv<12, VI>(b, st);
+        case 13: return launch_inv_tv<13, VI>(b, st);
+        case 14: return launch_inv_tv<14, VI>(b, st);
+        case 15: return launch_inv_tv<15, VI>(b, st);
+    }
+    throw std::runtime_error("mkhe: internal: register-resident inverse NTT of a size no kernel has");
+}
+// the 2^12-point LDS kernels need more dynamic LDS than the default limit (2^11 points: 18 KB, below it)
+static void lds12_attribute() {
+    static NttLaunchCache cache;
+    (void)ntt_resident_workgroups(cache, {(const void*)ntt_fwd_lds_kernel<0, 12>, (const void*)ntt_fwd_lds_kernel<1, 12>, (const void*)ntt_inv_ldsS_kernel<12>},
+                                  SmGeo<12>::T, SmGeo<12>::LDSW * sizeof(u64));
 }
 
-template <int MODE, bool DEC> static void launch_fwd_mode(int logN, const NttBatch& b, hipStream_t st) {
-    switch (logN) {
-        case 10: launch_fwd_t<10, MODE, DEC>(b, st); break;
-        case 11: launch_fwd_t<11, MODE, DEC>(b, st); break;
-        case 12: launch_fwd_t<12, MODE, DEC>(b, st); break;
-        case 13: launch_fwd_t<13, MODE, DEC>(b, st); break;
-        case 14: launch_fwd_t<14, MODE, DEC>(b, st); break;
-        case 15: launch_fwd_t<15, MODE, DEC>(b, st); break;
-        default: break;
+void launch_ntt_step(const NttStep& s, const NttBatch& part, bool small, hipStream_t st) {
+    switch (s.kernel) {
+        case NK_H32_FWD: return launch_ntt32_step(s, part, st);
+        case NK_H16_FWD: case NK_H14_FWD: case NK_H16_SPLIT: case NK_H14_SPLIT: case NK_H14_INV: return launch_ntt16_step(s, part, small, st);
+        default: break;         // (this file's kernels: below)
     }
-}
-
-int split_ntt_fwd(const NttBatch& b, const unsigned char* small_q, NttBatch out[2]) {
-    int n = 0;
-    for (int cls = 1; cls >= 0; --cls) {
-        NttBatch c = b;
-        c.nslots = 0;
-        for (int s = 0; s < b.nslots; ++s)
-            if ((small_q[b.mod[s]] != 0) == (cls == 1)) { c.mod[c.nslots] = b.mod[s]; c.pos[c.nslots] = b.pos[s]; ++c.nslots; }
-        c.lazy_out = cls;          // carries the class to launch_ntt_fwd_class (field unused by the forward kernels)
-        if (c.nslots) out[n++] = c;
-    }
-    return n;
-}
-// A limb is one workgroup's work for 60-70 us whatever the batch size, so a launch with fewer limbs than CUs is latency
-// bound at half the chip idle.  Such launches (and every N = 2^16 launch) run split: cross-half radix-2 pass + two
-// half-size sub-transforms per limb (2 workgroups per CU fit), which nearly halves the latency of the small launches
-// on the critical path (tensor / ExternalProduct inverse NTTs).
-static bool use_split(int logN, const NttBatch& b) {
-    if (logN == 16) return true;
-    if (logN < 13) return false;
-    const int limbs = b.vi ? b.vi_jobs : b.nslots * b.nouter;                // merged launches: the jobs that exist
-    return limbs <= 128;        // at most one sub-transform workgroup per CU (256 CUs)
-}
-// depth of the low-latency path for this launch: 0 = register-resident sub-transforms, d >= 1 = 2^d LDS sub-transforms of
-// 2^13 coefficients per limb after d streaming passes.  MKHE_NTT_LDS=0 switches it off (A/B tests).
-static int lds_depth(int logN, const NttBatch& b) {
-    static const int on = MKHE_AB_INT("MKHE_NTT_LDS", 1);
-    if (!on || b.prestaged) return 0;
-    if (logN != 14 && logN != 15) return 0;
-    // N = 2^14: four 2^12-point sub-transforms per limb; N = 2^15: eight of them behind the radix-8 pass (the 2^13-point forms lost in rounds 3 and 4)
-    {
-        static LaunchState ls12;
-        const int dev = current_device();
-        std::lock_guard<std::mutex> g(ls12.mu);
-        if (!ls12.attr[dev]) {
-            const int lds = SmGeo<12>::LDSW * (int)sizeof(u64);
-            (void)hipFuncSetAttribute((const void*)ntt_fwd_lds_kernel<0, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)ntt_fwd_lds_kernel<1, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)ntt_inv_ldsS_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            ls12.attr[dev] = true;
-        }
-        // N = 2^14 launches that would not even give every CU one 2^12-point workgroup: eight 2^11-point sub-transforms per limb (256 threads)
-        const int limbs = b.vi ? b.vi_jobs : b.nslots * b.nouter;
-        if (logN == 14 && limbs < 64) return 3;
-        return logN - 12;
-    }
-}
-bool ntt_fwd_mixed_ok(int logN, const NttBatch& b, const unsigned char* small_q) {
-    if (logN != 15 || !b.reduce_in || b.split || b.nslots > 64 || b.nslots * b.nouter <= 512) return false;
-    int nsmall = 0;
-    for (int s = 0; s < b.nslots; ++s) if (small_q[b.mod[s]]) ++nsmall;
-    return nsmall != 0 && nsmall != b.nslots;               // a single class: the specialised kernel
-}
-void launch_ntt_fwd_mixed(int logN, const NttBatch& b, const unsigned char* small_q, hipStream_t st) {
-    (void)logN;
-    NttBatch c = b;
-    // slots reordered: the big-modulus limbs (the longer jobs) first, so that a ragged last round holds the cheap kind
-    c.small_slots = 0; c.nslots = 0;
-    for (int cls = 0; cls < 2; ++cls)
-        for (int s = 0; s < b.nslots; ++s)
-            if ((small_q[b.mod[s]] != 0) == (cls == 1)) {
-                c.mod[c.nslots] = b.mod[s]; c.pos[c.nslots] = b.pos[s];
-                if (cls) c.small_slots |= 1ull << c.nslots;
-                ++c.nslots;
-            }
-    launch_fwd_t<15, 2, true>(c, st);
-}
-// would every class part of this prestaged N = 2^16 launch run on the H16 sub-transform kernel?  (only then may the producer stage its
-// output in a separate buffer: NttBatch::prestaged_oop)
-bool ntt_fwd_prestaged_oop_ok(int logN, const NttBatch& b, const unsigned char* small_q) {
-    if (logN != 16 || !b.prestaged) return false;
-    NttBatch part[2];
-    const int n = split_ntt_fwd(b, small_q, part);
-    for (int i = 0; i < n; ++i) {
-        NttBatch o = part[i]; o.reduce_in = 0; o.split = 1;
-        if (!use_split(logN, part[i]) || lds_depth(logN, part[i]) != 0 || !ntt16_split_ok(o)) return false;
-    }
-    return n > 0;
-}
-void launch_ntt_fwd_class(int logN, const NttBatch& b, hipStream_t st) {
-    if (b.nslots <= 0 || b.nouter <= 0) return;
-    const bool small = b.lazy_out != 0;
-    if (b.prestaged == 2) {
-        // N = 2^16, both cross stages applied by the producer (decomp_spread_kernel<2>): four one-pass 2^14-point sub-transforms per limb on
-        // the H16 kernel, in place on dst or from the producer's staging buffer (the caller has asked ntt_fwd_prestaged_oop_ok)
-        NttBatch o = b.prestaged_oop ? b : in_place_of_dst(b);
-        o.reduce_in = 0; o.split = 2;
-        if (logN != 16 || !ntt16_split_ok(o)) throw std::runtime_error("mkhe: internal: radix-4 prestaged launch outside the H16 path");
-        launch_ntt16_fwd_split(o, small, st);
-        return;
-    }
-    if (logN == 16 && !b.prestaged) {
-        // N = 2^16 without a fused producer (the tensor-step inputs, plain NTTs): both cross stages as ONE streaming pass, then the four one-pass
-        // 2^14-point sub-transforms per limb on the H16 kernel -- instead of a radix-2 pass and two-pass 2^15-point halves (MKHE_NTT16_RADIX4=0)
-        static const int r4 = MKHE_AB_INT("MKHE_NTT16_RADIX4", 1);
-        NttBatch o = in_place_of_dst(b);
-        o.reduce_in = 0; o.split = 2;
-        if (r4 && ntt16_split_ok(o)) {
-            const dim3 grid(32, b.nslots * b.nouter);
-            if (b.reduce_in) hipLaunchKernelGGL(ntt_pass4_fwd_kernel<true>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-            else hipLaunchKernelGGL(ntt_pass4_fwd_kernel<false>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-            launch_ntt16_fwd_split(o, small, st);
+    const NttBatch b = ntt_step_batch(part, s);
+    const dim3 cross(32, part.nslots * part.nouter), threads(SPLIT_THREADS);      // the streaming passes: one row of workgroups per limb
+    switch (s.kernel) {
+        case NK_FWD_REG:
+            if (s.dec) { if (small) launch_fwd_mode<1, true>(s.logn, b, st); else launch_fwd_mode<0, true>(s.logn, b, st); }
+            else       { if (small) launch_fwd_mode<1, false>(s.logn, b, st); else launch_fwd_mode<0, false>(s.logn, b, st); }
             return;
-        }
-    }
-    if (use_split(logN, b)) {
-        const dim3 grid(32, b.nslots * b.nouter);
-        const int d = lds_depth(logN, b);
-        if (b.prestaged) { /* first stage done by the producer */ }
-        else if (d == 3) {
-            if (b.reduce_in) hipLaunchKernelGGL(ntt_pass8_fwd_kernel<true>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-            else hipLaunchKernelGGL(ntt_pass8_fwd_kernel<false>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-        }
-        else if (d == 2) {
-            if (b.reduce_in) hipLaunchKernelGGL(ntt_pass4_fwd_kernel<true>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-            else hipLaunchKernelGGL(ntt_pass4_fwd_kernel<false>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-        }
-        else if (b.reduce_in) hipLaunchKernelGGL(ntt_split_fwd_kernel<true>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-        else hipLaunchKernelGGL(ntt_split_fwd_kernel<false>, grid, dim3(SPLIT_THREADS), 0, st, b, logN);
-        NttBatch c = in_place_of_dst(b);
-        if (b.prestaged && b.prestaged_oop && !d && logN == 16) {
-            // the producer staged the data in src: sub-transforms src -> dst (the H16 kernel only; anything else copies nothing and would
-            // need the data in dst, so the caller only asks for this when ntt16_split_ok holds)
-            NttBatch o = b; o.reduce_in = 0; o.split = 1;
-            if (ntt16_split_ok(o)) c = o;
-            else throw std::runtime_error("mkhe: internal: out-of-place prestaged launch outside the H16 path");
-        }
-        if (d) {
-            for (int L = 1; L < d && d != 2 && d != 3; ++L) hipLaunchKernelGGL(ntt_pass_fwd_kernel, grid, dim3(SPLIT_THREADS), 0, st, c, logN, L);
-            const int jobs = (b.nslots * b.nouter) << d;
-            if (logN - d == 12) {
-                const size_t lds = SmGeo<12>::LDSW * sizeof(u64);
-                if (small) hipLaunchKernelGGL((ntt_fwd_lds_kernel<1, 12>), dim3(jobs), dim3(512), lds, st, c, d);
-                else hipLaunchKernelGGL((ntt_fwd_lds_kernel<0, 12>), dim3(jobs), dim3(512), lds, st, c, d);
+        case NK_FWD_MIXED: return launch_fwd_t<15, 2, true>(b, st);
+        case NK_SPLIT_FWD:
+            if (s.dec) hipLaunchKernelGGL(ntt_split_fwd_kernel<true>, cross, threads, 0, st, b, s.logn);
+            else hipLaunchKernelGGL(ntt_split_fwd_kernel<false>, cross, threads, 0, st, b, s.logn);
+            return;
+        case NK_PASS4_FWD:
+            if (s.dec) hipLaunchKernelGGL(ntt_pass4_fwd_kernel<true>, cross, threads, 0, st, b, s.logn);
+            else hipLaunchKernelGGL(ntt_pass4_fwd_kernel<false>, cross, threads, 0, st, b, s.logn);
+            return;
+        case NK_PASS8_FWD:
+            if (s.dec) hipLaunchKernelGGL(ntt_pass8_fwd_kernel<true>, cross, threads, 0, st, b, s.logn);
+            else hipLaunchKernelGGL(ntt_pass8_fwd_kernel<false>, cross, threads, 0, st, b, s.logn);
+            return;
+        case NK_FWD_LDS:
+            if (s.logn == 12) {
+                lds12_attribute();
+                if (small) hipLaunchKernelGGL((ntt_fwd_lds_kernel<1, 12>), dim3(s.jobs), dim3(SmGeo<12>::T), SmGeo<12>::LDSW * sizeof(u64), st, b, s.depth);
+                else hipLaunchKernelGGL((ntt_fwd_lds_kernel<0, 12>), dim3(s.jobs), dim3(SmGeo<12>::T), SmGeo<12>::LDSW * sizeof(u64), st, b, s.depth);
                 return;
             }
-            if (logN - d == 11) {
-                const size_t lds = SmGeo<11>::LDSW * sizeof(u64);            // (18 KB: below the default dynamic-LDS limit, no attribute needed)
-                if (small) hipLaunchKernelGGL((ntt_fwd_lds_kernel<1, 11>), dim3(jobs), dim3(256), lds, st, c, d);
-                else hipLaunchKernelGGL((ntt_fwd_lds_kernel<0, 11>), dim3(jobs), dim3(256), lds, st, c, d);
+            if (s.logn == 11) {
+                if (small) hipLaunchKernelGGL((ntt_fwd_lds_kernel<1, 11>), dim3(s.jobs), dim3(SmGeo<11>::T), SmGeo<11>::LDSW * sizeof(u64), st, b, s.depth);
+                else hipLaunchKernelGGL((ntt_fwd_lds_kernel<0, 11>), dim3(s.jobs), dim3(SmGeo<11>::T), SmGeo<11>::LDSW * sizeof(u64), st, b, s.depth);
                 return;
             }
-            throw std::runtime_error("mkhe: internal: LDS sub-transforms of a size no kernel has");
-        }
-        if (logN == 16 && ntt16_split_ok(c)) launch_ntt16_fwd_split(c, small, st);
-        else if (small) launch_fwd_mode<1, false>(logN - 1, c, st); else launch_fwd_mode<0, false>(logN - 1, c, st);
-        return;
-    }
-    if (b.reduce_in) { if (small) launch_fwd_mode<1, true>(logN, b, st); else launch_fwd_mode<0, true>(logN, b, st); }
-    else             { if (small) launch_fwd_mode<1, false>(logN, b, st); else launch_fwd_mode<0, false>(logN, b, st); }
-}
-void launch_ntt_inv(int logN, const NttBatch& b, hipStream_t st) {
-    if (b.nslots <= 0 || b.nouter <= 0) return;
-    if (ntt16_inv_ok(logN, b)) {
-        // launches that fill the chip: one-pass 2^14-point sub-transforms on the H16-class inverse kernel (src -> dst, canonical, N^-1 folded in),
-        // then the cross stages of the larger rings as one streaming pass in place on dst
-        launch_ntt16_inv(b, st, logN);
-        if (logN > 14) {
-            NttBatch e = in_place_of_dst(b);                  // only the dst addressing is used
-            e.lazy_out = b.lazy_out; e.psi = b.psi; e.split = 0;
-            const dim3 grid(32, b.nslots * b.nouter);
-            if (logN == 15) hipLaunchKernelGGL(ntt_split_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, e, logN);
-            else hipLaunchKernelGGL(ntt_pass4_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, e, logN);
-        }
-        return;
-    }
-    if (!b.split && use_split(logN, b)) {
-        if (const int d = lds_depth(logN, b)) {
-            const int jobs = (b.nslots * b.nouter) << d;
-            if (logN - d == 12) hipLaunchKernelGGL(ntt_inv_ldsS_kernel<12>, dim3(jobs), dim3(512), SmGeo<12>::LDSW * sizeof(u64), st, b, d);
-            else if (logN - d == 11) hipLaunchKernelGGL(ntt_inv_ldsS_kernel<11>, dim3(jobs), dim3(256), SmGeo<11>::LDSW * sizeof(u64), st, b, d);
-            else throw std::runtime_error("mkhe: internal: LDS sub-transforms of a size no kernel has");     // (src -> dst, [0,2q), N^-1 folded in)
-            const NttBatch ip = in_place_of_dst(b);
-            const dim3 grid(32, b.nslots * b.nouter);
-            NttBatch e = ip; e.lazy_out = b.lazy_out; e.psi = b.psi;
-            if (d == 3) { hipLaunchKernelGGL(ntt_pass8_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, e, logN); return; }
-            if (d == 2) { hipLaunchKernelGGL(ntt_pass4_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, e, logN); return; }
-            for (int L = d - 1; L >= 1; --L) hipLaunchKernelGGL(ntt_pass_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, ip, logN, L);
-            hipLaunchKernelGGL(ntt_split_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, e, logN);
+            break;
+        case NK_INV_REG:
+            if (b.vi) launch_inv_mode<true>(s.logn, b, st); else launch_inv_mode<false>(s.logn, b, st);
             return;
-        }
-        NttBatch c = b;
-        c.split = 1;
-        launch_ntt_inv(logN - 1, c, st);                      // src halves -> dst halves, lazy, N^-1 folded in
-        const NttBatch d = in_place_of_dst(b);                // only the dst addressing is used
-        NttBatch e = d; e.lazy_out = b.lazy_out; e.psi = b.psi;
-        hipLaunchKernelGGL(ntt_split_inv_kernel, dim3(32, b.nslots * b.nouter), dim3(SPLIT_THREADS), 0, st, e, logN);
-        return;
-    }
-    switch (logN) {
-        case 10: launch_inv_t<10>(b, st); break;
-        case 11: launch_inv_t<11>(b, st); break;
-        case 12: launch_inv_t<12>(b, st); break;
-        case 13: launch_inv_t<13>(b, st); break;
-        case 14: launch_inv_t<14>(b, st); break;
-        case 15: launch_inv_t<15>(b, st); break;
+        case NK_INV_LDS:
+            if (s.logn == 12) { lds12_attribute(); hipLaunchKernelGGL(ntt_inv_ldsS_kernel<12>, dim3(s.jobs), dim3(SmGeo<12>::T), SmGeo<12>::LDSW * sizeof(u64), st, b, s.depth); return; }
+            if (s.logn == 11) { hipLaunchKernelGGL(ntt_inv_ldsS_kernel<11>, dim3(s.jobs), dim3(SmGeo<11>::T), SmGeo<11>::LDSW * sizeof(u64), st, b, s.depth); return; }
+            break;
+        case NK_SPLIT_INV: hipLaunchKernelGGL(ntt_split_inv_kernel, cross, threads, 0, st, b, s.logn); return;
+        case NK_PASS4_INV: hipLaunchKernelGGL(ntt_pass4_inv_kernel, cross, threads, 0, st, b, s.logn); return;
+        case NK_PASS8_INV: hipLaunchKernelGGL(ntt_pass8_inv_kernel, cross, threads, 0, st, b, s.logn); return;
         default: break;
     }
+    throw std::runtime_error("mkhe: internal: an NTT step no launcher takes");
 }
 
 void launch_ntt_cross8_dec(const NttBatch& b, int logN, hipStream_t st) {
@@ -1299,8 +1166,8 @@ void launch_ext_fused_lds(const ExtFusedArgs& a, hipStream_t st) {
 // destination summed at the load
 void launch_ntt_inv_cross8_sum(const NttBatch& b, int logN, hipStream_t st) {
     if (b.nslots <= 0 || b.nouter <= 0) return;
-    NttBatch e = in_place_of_dst(b);
-    e.lazy_out = b.lazy_out; e.psi = b.psi; e.sum_in_cross = 1;
+    NttBatch e = ntt_step_batch(b, NttStep{NK_PASS8_INV, logN, 1, 0, b.nslots * b.nouter, true, false});
+    e.sum_in_cross = 1;
     const dim3 grid(((1 << logN) / 8 + SPLIT_THREADS - 1) / SPLIT_THREADS, b.nslots * b.nouter);
     hipLaunchKernelGGL(ntt_pass8_inv_kernel, grid, dim3(SPLIT_THREADS), 0, st, e, logN);
 }
