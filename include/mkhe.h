@@ -908,6 +908,30 @@ int  mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* cons
 int  mkhe_bfv_ct_ptxt_dot(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* const* in, int ngiant, const uint32_t* masks,
                           const void* dev_ptmul, mkhe_ct* const* out);
 
+/* ==== BFV weighted sums: integer-weighted sums of ciphertexts and additive constants mod T =============
+ * No reference counterpart (mkbfv.Evaluator of the reference adds, multiplies and rotates); the MK-BFV twin of mkhe_ct_lincomb, for nout sums of the
+ * same nin ciphertexts at once: every inner sum of a baby-step / giant-step polynomial evaluation over Z_T in one launch.  The preconditions and
+ * refusals of "BFV plaintext operands" apply: a BFV context that owns every modulus, T within the encoder's preconditions, not between
+ * mkhe_capture_begin and mkhe_capture_end, every handle at the maximum level (nQ limbs) with the same ids, the outputs distinct and aliasing no
+ * input, dev_consts non-null and 16-byte aligned.  1 <= nin <= 16, 1 <= nout <= 64; the counts are checked before the context is looked at.  Every
+ * error message starts with the name of the function; a refused call enqueues nothing and leaves the context usable.
+ *   out[g] = sum_b W[g][b] * in[b] + C[g],      g < nout
+ * for every component and every limb l < nQ, mod q_l, canonical; C[g] is added to coefficient 0 of component 0 only (the all-c slot vector is the
+ * constant polynomial c).  dev_consts = device uint64[nout][nin + 1][nQ] (mkhe_buf_alloc), read when the call executes:
+ *   [g][0][l]      the additive constant as a plain canonical residue: for a slot constant c in [0, T) the scale_up of the "BFV batch encoder",
+ *                  floor((Q c + floor(T/2)) / T) mod q_l
+ *   [g][1 + b][l]  the weight in the engine's 2^64 Montgomery form, reduced: for an integer weight w mod T the lift of "BFV plaintext operands",
+ *                  MForm(c mod q_l) with c the centred representative of w in (-T/2, T/2]
+ * A weight whose residue is 0 under limb l costs no product for that limb (a wave-uniform branch); the input is loaded once for all outputs anyway.
+ * Launch set: ONE kernel, one thread per coefficient of one component; it reads every input limb once and writes every output limb once,
+ * 8 N nQ (1 + k) (nin + nout) bytes for k parties.  mkhe_ct_lincomb once per output moves nout * (nin_g + 1) passes of 8 N nQ (1 + k) instead.
+ * Bit-exactness: out[g] is the canonical residue of the integer sum.  For nout = 1 it equals, bit for bit, mkhe_ct_lincomb on the same context with
+ * every im_k = 0, the constant (C, 0) and nb_rescale = 0 (that call accepts a BFV context), and the chain mkhe_ct_mul_const, mkhe_ct_sum.
+ * Noise: with pt(a) = round(Q a / T) and w the centred weight, w * pt(a) = (Q/T) [w a]_T + Q k + eps w with |eps| <= 1/2 -- no Q mod T term -- and
+ * the constant adds its own rounding |eps| <= 1/2: a sum of ciphertexts of noise e_b has noise at most sum_b |w_b| (|e_b| + 1/2) + 1/2, and decrypts
+ * to sum_b w_b a_b + c mod T slot by slot while that stays below Q / (2T).  No key is used and no party is added. */
+int  mkhe_bfv_ct_lincomb(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int nout, const void* dev_consts, mkhe_ct* const* out);
+
 /* ---- measurement support (no reference counterpart): HIP-event timing per kernel class on the
  *      context stream, one record per kernel launch.  Classes (mkhe_prof_name gives the kernel symbol
  *      each class corresponds to in a rocprofv3 kernel trace). */

@@ -1257,6 +1257,11 @@ class Evaluator {
         MulRelinSum(ops0, ops1, rlkSet, *out);
         return out;
     }
+    // mkhe_bfv_ct_lincomb as it is (no reference counterpart; include/mkhe.h, "BFV weighted sums"): outs[g] = sum_b W[g][b] cts[b] + C[g] for every g as
+    // one launch.  dev_consts: device uint64[outs.size()][cts.size() + 1][nQ], row 0 of an output its constant (plain), rows 1 .. its weights (Montgomery form)
+    void LinCombs(const std::vector<const mkhe_ct*>& cts, const void* dev_consts, const std::vector<mkhe_ct*>& outs) {
+        check(mkhe_bfv_ct_lincomb(params.ctx, (int)cts.size(), cts.data(), (int)outs.size(), dev_consts, outs.data()));
+    }
     CiphertextPtr RotateNew(const Ciphertext& ct0, int rotidx, mkrlwe::RotationKeySet& rkSet) {                                    // evaluator.go:142-180 (precomputed indices)
         auto out = std::make_unique<Ciphertext>(params, ct0.IDSet_(), false);
         ksw.Rotate(ct0, rotidx, rkSet, *out);

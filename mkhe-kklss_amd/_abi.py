@@ -151,6 +151,7 @@ SIGNATURES = {
     "mkhe_bfv_ct_mul_ptxt": (C.c_int, [vp, C.c_int, vpp, vp, C.c_long, vpp]),
     "mkhe_bfv_ct_ptxt_dot": (C.c_int, [vp, C.c_int, C.c_int, vpp, C.c_int, C.POINTER(C.c_uint32), vp, vpp]),
     "mkhe_bfv_ct_add_ptxt": (C.c_int, [vp, C.c_int, C.c_int, vpp, vp, C.c_long, vpp]),
+    "mkhe_bfv_ct_lincomb": (C.c_int, [vp, C.c_int, vpp, C.c_int, vp, vpp]),
     "mkhe_ctx_bfv_tile": (C.c_int, [vp]),
     "mkhe_ctx_set_bfv_tile": (C.c_int, [vp, C.c_int]),
     "mkhe_ctx_bfv_slot_psi": (C.c_uint64, [vp]),

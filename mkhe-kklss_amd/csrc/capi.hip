@@ -1289,6 +1289,28 @@ int mkhe_bfv_ct_ptxt_dot(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* cons
         c->ct_ptxt_dot(what, nbatch, i, std::vector<unsigned int>(masks, masks + ngiant), (const u64*)dev_ptmul, (long)c->nq * c->N, c->nq, o);
     })
 }
+// BFV weighted sums (engine_ops.hip); the counts first, as above
+int mkhe_bfv_ct_lincomb(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int nout, const void* dev_consts, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_ct_lincomb";
+        const std::string w = std::string(what) + ": ";
+        if (nin < 1 || nin > BLIN_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(BLIN_MAX_IN));
+        if (nout < 1 || nout > BLIN_MAX_OUT) throw Error(w + "nout must be 1 .. " + std::to_string(BLIN_MAX_OUT));
+        Context* c = enter(ctx, what);
+        if (!in || !dev_consts || !out) throw Error(w + "null argument");
+        need_aligned(dev_consts, what);
+        scheme_ok(c, what, true, ": needs a BFV context");
+        unmasked(c, what);
+        not_captured(c, what, "(the call may allocate or stage)");
+        for (int i = 0; i < nin; ++i) ct_at(in, i, what);
+        for (int i = 0; i < nout; ++i) if (!out[i]) throw Error(w + "null output in the batch");
+        commit(c);
+        auto i = ct_list(ctx, in, nin, what);
+        auto o = ct_list_out(ctx, out, nout, what);
+        c->bfv_prepare(what);
+        c->bfv_ct_lincomb(what, i, (const u64*)dev_consts, o);
+    })
+}
 int mkhe_bfv_ct_add_ptxt(mkhe_ctx* ctx, int op, int nbatch, const mkhe_ct* const* in, const void* dev_pt, long pt_stride_words, mkhe_ct* const* out) {
     MKHE_TRY({
         const char* what = "mkhe_bfv_ct_add_ptxt";

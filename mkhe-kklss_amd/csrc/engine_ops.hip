@@ -214,6 +214,39 @@ void Context::ct_lincomb(const std::vector<const Ct*>& ins, const u64* dev_const
     MKHE_HIP(hipGetLastError());
 }
 
+// outs[g] = sum_b W[g][b] ins[b] + C[g] with integer weights, for all outputs in ONE pass (launch_bfv_ct_lincomb): every input limb is read once and
+// every output limb written once, 8 N nQ (1 + k) (nin + nout) bytes -- ct_lincomb once per output moves nout * (nin_g + 1) passes of 8 N nQ (1 + k).
+// Every refusal is under `what` (the C entry point) and comes before the launch.
+void Context::bfv_ct_lincomb(const char* what, const std::vector<const Ct*>& ins, const u64* dev_consts, const std::vector<Ct*>& outs) {
+    const std::string w = std::string(what) + ": ";
+    const int nin = (int)ins.size(), nout = (int)outs.size();
+    if (nin < 1 || nin > BLIN_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(BLIN_MAX_IN));
+    if (nout < 1 || nout > BLIN_MAX_OUT) throw Error(w + "nout must be 1 .. " + std::to_string(BLIN_MAX_OUT));
+    if (!dev_consts) throw Error(w + "null argument");
+    const Ct& c0 = *ins[0];
+    const int L = nq, np_ = 1 + c0.n;
+    const size_t CO = (size_t)np_ * L * N;
+    BfvLincombArgs a{};
+    for (int b = 0; b < nin; ++b) {
+        if (ins[b]->n != c0.n || ins[b]->ids != c0.ids) throw Error(w + "the ciphertexts of a list must share their ids");
+        if (ins[b]->limbs != L) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
+        a.in[b] = ins[b]->d;
+    }
+    for (int g = 0; g < nout; ++g) {
+        if (outs[g]->n != c0.n || outs[g]->ids != c0.ids) throw Error(w + "an output must carry the ids of the inputs");
+        if (outs[g]->limbs != L) throw Error(w + "BFV ciphertexts sit at the maximum level (nQ limbs)");
+        for (int h = 0; h < g; ++h)
+            if (outs[g]->d < outs[h]->d + CO && outs[h]->d < outs[g]->d + CO) throw Error(w + "the outputs must be distinct");
+        // a thread stores its word of every output while other threads still read the inputs: no overlap at all
+        for (const Ct* c : ins)
+            if (c->d < outs[g]->d + CO && outs[g]->d < c->d + CO) throw Error(w + "an output must not alias an input");
+        a.out[g] = outs[g]->d;
+    }
+    a.mods = d_mods; a.consts = dev_consts; a.nin = nin; a.nout = nout; a.L = L; a.N = N; a.npolys = np_;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * L * np_ * (nin + nout)); launch_bfv_ct_lincomb(a, s_); }
+    MKHE_HIP(hipGetLastError());
+}
+
 void Context::ct_mul_ptxt(const Ct& in, const u64* dev_pt, Ct& out) {
     const int L = in.limbs, np_ = 1 + in.n;
     if (out.limbs != L || out.n != in.n || out.ids != in.ids) throw Error("mkhe: ctOut shape does not match ct");

@@ -409,6 +409,20 @@ struct CtPtxtDotArgs {
     int nin, ngiant, L, N, npolys, nbatch;
 };
 void launch_ct_ptxt_dot(const CtPtxtDotArgs& a, hipStream_t st);
+// out[g] = sum_b W[g][b] * in[b] + C[g], g < nout, over whole ciphertexts of ONE shape ([npolys][L][N] each), per limb mod q_l, canonical
+// (mkhe_bfv_ct_lincomb; no reference counterpart): every inner sum of a polynomial evaluation over Z_T from the same baby powers, each input word
+// read once for all outputs.  consts = [nout][nin + 1][L] on the device: entry [g][0][l] = C[g] as a plain canonical residue, added to coefficient 0 of
+// polynomial 0 only; entry [g][1 + b][l] = W[g][b] in Montgomery form, reduced; a weight that is 0 under limb l costs no product there.  No output
+// may overlap an input or another output.
+constexpr int BLIN_MAX_IN = 16, BLIN_MAX_OUT = 64;
+struct BfvLincombArgs {
+    const u64* in[BLIN_MAX_IN];
+    u64* out[BLIN_MAX_OUT];
+    const Mod* mods;
+    const u64* consts;
+    int nin, nout, L, N, npolys;
+};
+void launch_bfv_ct_lincomb(const BfvLincombArgs& a, hipStream_t st);
 // dst = MForm(src) for count polynomials of L limbs each (limb l under mods[l]); dst may be src
 void launch_mform_polys(u64* dst, const u64* src, const Mod* mods, int L, int N, int count, hipStream_t st);
 

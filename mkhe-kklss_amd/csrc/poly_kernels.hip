@@ -1280,6 +1280,56 @@ void launch_ct_ptxt_dot(const CtPtxtDotArgs& a, hipStream_t st) {
     else if (a.nin > 4) hipLaunchKernelGGL(ct_ptxt_dot_kernel<8>, grid, blk, 0, st, a);
     else hipLaunchKernelGGL(ct_ptxt_dot_kernel<4>, grid, blk, 0, st, a);
 }
+// Weighted sums of whole ciphertexts with integer weights (BfvLincombArgs), in the register scheme of ct_ptxt_dot_kernel: one thread per coefficient j
+// of one polynomial (component), lanes on consecutive j (coalesced 8-byte streams), the limb -- with it the modulus and every weight -- wave-uniform,
+// limbs dealt to gridDim.z groups as in ct_lincomb_kernel.  The thread loads its coefficient of the nin inputs ONCE into registers (NI = 4, 8 or 16
+// slots of two VGPRs) and then walks the outputs: the weights of output g under limb l come through scalar loads, a weight of 0 is a skipped scalar
+// branch (no product), one 128-bit accumulator takes the products and is reduced once.  At most BLIN_MAX_IN = 16 products of values below q < 2^60
+// per sum (inputs canonical, weights MForm'ed and reduced): half of what redc128 accepts.  redc128 leaves sum * 2^-64, which the Montgomery form of
+// the weights cancels: the canonical residue of the integer sum, the same words as ct_lincomb_kernel's for real weights.
+static_assert(BLIN_MAX_IN <= 16, "bfv_ct_lincomb_kernel: one sum is at most 16 products, half of the 32 that redc128 accepts for q < 2^60");
+typedef const __attribute__((address_space(4))) BfvLincombArgs* blin_kargs;
+template <int NI>
+__global__ void __launch_bounds__(PW_THREADS) bfv_ct_lincomb_kernel(BfvLincombArgs a) {
+    blin_kargs ka = (blin_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    const int j = blockIdx.x * PW_THREADS + threadIdx.x, p = blockIdx.y;
+    if (j >= a.N) return;
+    const sc_u64 cs = (sc_u64)a.consts;
+    const bool constant_term = p == 0 && j == 0;
+    const long row = (long)(a.nin + 1) * a.L;
+    for (int l = blockIdx.z; l < a.L; l += gridDim.z) {
+        const Mod md = load_mod((sc_mod)a.mods + l);
+        const long off = ((long)p * a.L + l) * a.N + j;
+        u64 x[NI];
+#pragma unroll
+        for (int b = 0; b < NI; ++b) x[b] = b < a.nin ? ka->in[b][off] : 0;
+        for (int g = 0; g < a.nout; ++g) {
+            const sc_u64 w = cs + g * row + l;
+            u64 hi = 0, lo = 0;
+#pragma unroll
+            for (int b = 0; b < NI; ++b)
+                if (b < a.nin) {
+                    const u64 wb = w[(long)(1 + b) * a.L];
+                    if (wb) mac128(wb, x[b], hi, lo);
+                }
+            u64 v = redc128(hi, lo, md);
+            if (constant_term) v = csub(v + w[0], md.q);
+            ka->out[g][off] = v;
+        }
+    }
+}
+void launch_bfv_ct_lincomb(const BfvLincombArgs& a, hipStream_t st) {
+    if (a.nin < 1 || a.nin > BLIN_MAX_IN || a.nout < 1 || a.nout > BLIN_MAX_OUT || a.npolys < 1 || a.npolys > 65535 || a.L < 1)
+        throw std::runtime_error("mkhe: launch_bfv_ct_lincomb: bad shape");
+    const int bx = (a.N + PW_THREADS - 1) / PW_THREADS;
+    // limb groups as in launch_ct_lincomb: until every SIMD of the chip has four waves, at most one group per limb
+    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys;
+    const int groups = (int)std::min<long>(a.L, (fill + threads - 1) / threads);
+    const dim3 grid(bx, a.npolys, groups), blk(PW_THREADS);
+    if (a.nin > 8) hipLaunchKernelGGL(bfv_ct_lincomb_kernel<16>, grid, blk, 0, st, a);
+    else if (a.nin > 4) hipLaunchKernelGGL(bfv_ct_lincomb_kernel<8>, grid, blk, 0, st, a);
+    else hipLaunchKernelGGL(bfv_ct_lincomb_kernel<4>, grid, blk, 0, st, a);
+}
 __global__ void __launch_bounds__(PW_THREADS) mform_polys_kernel(u64* dst, const u64* src, const Mod* mods, int L, int N) {
     const int l = blockIdx.y;
     const Mod md = mods[l];

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi, mkrlwe
 from ._abi import MkheError, check, handle_array, lib
-from .mkckks import PTXT_DOT_MAX_GIANT, linear_transform_plan
+from .mkckks import PTXT_DOT_MAX_GIANT, linear_transform_plan, poly_eval_plan
 
 
 class Parameters(mkrlwe.Parameters):
@@ -384,8 +384,184 @@ class Evaluator:
         """ct - pt, pt as for AddPtxtNew"""
         return self.AddPtxtBatch([ct], pt, sub=True)[0]
 
+    # ---- weighted sums, additive constants and polynomials over Z_T (no reference counterpart: include/mkhe.h, "BFV weighted sums").  No key is
+    # used and no party is added by the sums; the constants are encoded and uploaded per call: not inside a graph capture.
+    def _consts_buffer(self, arr):
+        n = self.params.N()
+        buf = mkrlwe.DeviceLimbs(self.params, 1, -(-arr.size // n))
+        return buf.upload(np.concatenate([arr.ravel(), np.zeros(buf.words - arr.size, dtype=np.uint64)]).reshape(1, buf.limbs, n))
+
+    def LinCombsNew(self, cts, weight_rows, consts):
+        """[sum_b weight_rows[g][b] * cts[b] + consts[g] for every g] slot by slot mod T as ONE engine call (mkhe_bfv_ct_lincomb): 1 to 16 ciphertexts
+        of one id set, 1 to 64 rows of integer weights (any int, taken mod T) with one integer constant each.  The results are views of one pooled
+        block."""
+        cts, rows, consts = list(cts), [list(r) for r in weight_rows], list(consts)
+        if not cts or len(cts) > LINCOMB_MAX_IN:
+            raise MkheError("LinCombsNew: 1 to %d ciphertexts per call" % LINCOMB_MAX_IN)
+        if not rows or len(rows) > LINCOMB_MAX_OUT or len(rows) != len(consts):
+            raise MkheError("LinCombsNew: 1 to %d rows of weights per call, one constant per row" % LINCOMB_MAX_OUT)
+        if any(len(r) != len(cts) for r in rows):
+            raise MkheError("LinCombsNew: one weight per ciphertext in every row")
+        if any(c.ids != cts[0].ids for c in cts):
+            raise MkheError("LinCombsNew: the ciphertexts must carry the same ids")
+        params = self.params
+        buf = self._consts_buffer(bfv_lincomb_consts(params.Q, params.T(), rows, consts))
+        outs = self._outputs([cts[0]] * len(rows))
+        check(lib().mkhe_bfv_ct_lincomb(params.ctx, len(cts), handle_array([c.h for c in cts]), len(rows), buf.devptr(),
+                                        handle_array([c.h for c in outs])))
+        return outs
+
+    def LinCombNew(self, cts, weights, const=0, fused=True):
+        """sum_b weights[b] * cts[b] + const: the one-row form of LinCombsNew.  fused=False: the same sum through mkhe_ct_lincomb (real weights, no
+        division), the same ciphertext bit for bit."""
+        if fused:
+            return self.LinCombsNew(cts, [weights], [const])[0]
+        cts, weights = list(cts), list(weights)
+        if not cts or len(cts) > LINCOMB_MAX_IN or len(cts) != len(weights):
+            raise MkheError("LinCombNew: 1 to %d ciphertexts per call, one weight each" % LINCOMB_MAX_IN)
+        if any(c.ids != cts[0].ids for c in cts):
+            raise MkheError("LinCombNew: the ciphertexts must carry the same ids")
+        params = self.params
+        row = bfv_lincomb_consts(params.Q, params.T(), [weights], [const])[0]            # [nin + 1][nQ]
+        buf = self._consts_buffer(np.stack([row, np.zeros_like(row)], axis=1))               # [nin + 1][2][nQ]: no imaginary part
+        out = NewCiphertext(params, cts[0].IDSet(), zero=False)
+        check(lib().mkhe_ct_lincomb(params.ctx, len(cts), handle_array([c.h for c in cts]), buf.devptr(), 0, out.h))
+        return out
+
+    def AddConstNew(self, ct, c):
+        """ct + c in every slot: the weight 1, so only coefficient 0 of component 0 changes, limb by limb"""
+        return self.LinCombNew([ct], [1], c)
+
+    def MulConstNew(self, ct, w):
+        """w * ct in every slot for an integer w (taken mod T, centred): a scalar per limb, no NTT"""
+        return self.LinCombNew([ct], [w], 0)
+
+    def EvaluatePolysNew(self, ct, polys, rlkSet, fused=True):
+        """[sum_k coeffs[k] * ct^k mod T for every coeffs of polys] slot by slot (monomial basis, integer coefficients taken mod T, degree 1 .. 255)
+        by baby steps and giant steps (mkckks.poly_eval_plan for the largest degree): the polynomials share the powers of ct and ONE LinCombsNew that
+        writes every inner sum of every polynomial, then one MulRelinSumNew and one AddNew each.  MkheError before any engine call for a degree out of
+        range, a zero polynomial, more than 64 inner sums in all or a missing CRS[-1].  fused=False runs the same schedule through one mkhe_ct_lincomb
+        per inner sum and one MulRelinNew per giant product: the same decryption, another ciphertext."""
+        return evaluate_polys(self, ct, polys, rlkSet, fused)
+
+    def EvaluatePolyNew(self, ct, coeffs, rlkSet, fused=True):
+        """EvaluatePolysNew of one polynomial"""
+        return self.EvaluatePolysNew(ct, [coeffs], rlkSet, fused)[0]
+
 
 MULRELIN_SUM_MAX = 16     # pairs per mkhe_bfv_mul_relin_sum call (csrc/poly_kernels.h, TSUM_MAX_K)
+LINCOMB_MAX_IN, LINCOMB_MAX_OUT = 16, 64      # ciphertexts and rows per mkhe_bfv_ct_lincomb call (csrc/poly_kernels.h, BLIN_MAX_IN / BLIN_MAX_OUT)
+POLY_MAX_DEGREE = 255
+
+
+def bfv_lincomb_consts(Q, T, weight_rows, consts):
+    """The constant block of mkhe_bfv_ct_lincomb, uint64 [nout][nin + 1][nQ], a pure function (Python integers).  Entry [g][0][l]: consts[g] taken to
+    [0, T), then scale_up of include/mkhe.h: floor((Q c + floor(T/2)) / T) mod q_l.  Entry [g][1 + b][l]: weight_rows[g][b] taken mod T, then the lift of
+    mkhe_bfv_lift: the centred representative w in (-T/2, T/2] as MForm(w mod q_l) = (w mod q_l) 2^64 mod q_l."""
+    Q, T = [int(q) for q in Q], int(T)
+    rows, consts = [list(r) for r in weight_rows], list(consts)
+    if not rows or len(rows) != len(consts) or any(len(r) != len(rows[0]) for r in rows) or not rows[0]:
+        raise MkheError("bfv_lincomb_consts: rows of one length, at least one weight, one constant per row")
+    prod = 1
+    for q in Q:
+        prod *= q
+    out = np.zeros((len(rows), len(rows[0]) + 1, len(Q)), dtype=np.uint64)
+    for g, (row, c) in enumerate(zip(rows, consts)):
+        up = ((int(c) % T) * prod + T // 2) // T
+        for l, q in enumerate(Q):
+            out[g, 0, l] = up % q
+        for b, w in enumerate(row):
+            w = int(w) % T
+            w = w - T if w > T // 2 else w
+            for l, q in enumerate(Q):
+                out[g, 1 + b, l] = ((w % q) << 64) % q
+    return out
+
+
+def interpolate(xs, ys, T):
+    """The coefficients mod T (monomial basis, constant first) of the polynomial of degree < len(xs) through the points (xs[i], ys[i]) over Z_T, T
+    prime (Lagrange, Python integers).  MkheError when two abscissae agree mod T."""
+    T = int(T)
+    xs, ys = [int(x) % T for x in xs], [int(y) % T for y in ys]
+    n = len(xs)
+    if n < 1 or n != len(ys):
+        raise MkheError("interpolate: as many values as abscissae, at least one")
+    if len(set(xs)) != n:
+        raise MkheError("interpolate: two abscissae agree mod T")
+    master = [1]                                            # prod_i (X - x_i), constant first
+    for x in xs:
+        master = [(a - x * b) % T for a, b in zip([0] + master, master + [0])]
+    out = [0] * n
+    for x, y in zip(xs, ys):
+        quot, carry = [0] * n, 0                            # master / (X - x) by synthetic division
+        for k in range(n, 0, -1):
+            carry = (master[k] + x * carry) % T
+            quot[k - 1] = carry
+        denom = 1
+        for z in xs:
+            if z != x:
+                denom = denom * (x - z) % T
+        s = y * pow(denom, -1, T) % T
+        out = [(o + s * a) % T for o, a in zip(out, quot)]
+    return out
+
+
+def evaluate_polys(ev, ct, polys, rlkSet, fused=True):
+    """Evaluator.EvaluatePolysNew on any evaluator with params, MulRelinNew, LinCombsNew, MulRelinSumNew and AddNew (fused=False: LinCombNew instead of
+    the two fused calls).  With m, g of poly_eval_plan(largest degree): p(X) = sum_i inner_i(X) X^(m i), inner_i = sum_j coeffs[i m + j] X^j.  Stages:
+    the baby powers X^2 .. X^(m-1) and giant powers X^(m i) that some polynomial uses (MulRelinNew); ONE LinCombsNew whose rows are the non-zero inner_i
+    of every polynomial (an inner_i that is only a constant is a row of zero weights); per polynomial ONE MulRelinSumNew of its pairs (inner_i, X^(m i)),
+    i >= 1; ONE AddNew with inner_0.  There is no scale to manage: every sum and product is exact mod T while the noise lasts."""
+    params = ev.params
+    T = int(params.T())
+    polys = [[int(c) % T for c in p] for p in polys]
+    if not polys:
+        raise MkheError("EvaluatePolysNew: at least one polynomial")
+    for p in polys:
+        if len(p) - 1 < 1 or len(p) - 1 > POLY_MAX_DEGREE:
+            raise MkheError("EvaluatePolysNew: the degree must be between 1 and %d" % POLY_MAX_DEGREE)
+        if not any(p):
+            raise MkheError("EvaluatePolysNew: the zero polynomial")
+    plan = poly_eval_plan(max(len(p) - 1 for p in polys))
+    m = plan.m
+    inner = [[p[i: i + m] for i in range(0, len(p), m)] for p in polys]
+    rows = [(k, i) for k, blocks in enumerate(inner) for i, c in enumerate(blocks) if any(c)]
+    if len(rows) > LINCOMB_MAX_OUT:
+        raise MkheError("EvaluatePolysNew: %d inner sums, at most %d per call" % (len(rows), LINCOMB_MAX_OUT))
+    babies = sorted({j for k, i in rows for j, c in enumerate(inner[k][i]) if j and c}) or [1]
+    giants = sorted({m * i for k, i in rows if i})
+    if (giants or babies != [1]) and -1 not in params.CRS:
+        raise MkheError("mkhe: CRS[-1] (u) has not been uploaded")
+    needed = set(babies) | set(giants)
+    for k, a, b in reversed(plan.products):                 # a power nobody uses is not computed
+        if k in needed:
+            needed |= {a, b}
+    power = {1: ct}
+    for k, a, b in plan.products:
+        if k in needed:
+            power[k] = ev.MulRelinNew(power[a], power[b], rlkSet)
+    ins = [power[j] for j in babies]
+    weights = [[(inner[k][i][j] if j < len(inner[k][i]) else 0) for j in babies] for k, i in rows]
+    consts = [inner[k][i][0] for k, i in rows]
+    if fused:
+        sums = ev.LinCombsNew(ins, weights, consts)
+    else:
+        sums = [ev.LinCombNew(ins, w, c, fused=False) for w, c in zip(weights, consts)]
+    sums = dict(zip(rows, sums))
+    out = []
+    for k in range(len(polys)):
+        pairs = [(sums[(k, i)], power[m * i]) for kk, i in rows if kk == k and i]
+        res = None
+        if pairs and fused:
+            res = ev.MulRelinSumNew([a for a, _ in pairs], [b for _, b in pairs], rlkSet)
+        elif pairs:
+            for a, b in pairs:
+                prod = ev.MulRelinNew(a, b, rlkSet)
+                res = prod if res is None else ev.AddNew(res, prod)
+        if (k, 0) in sums:
+            res = sums[(k, 0)] if res is None else ev.AddNew(res, sums[(k, 0)])
+        out.append(res)
+    return out
 
 
 def NewEvaluator(params):

@@ -1,0 +1,25 @@
+"""The refusals of mkhe_bfv_ct_lincomb that need no device (no GPU), in the style of tests/test_bfv_ptxt_dot_refusals_host.py: the counts are checked
+before the context is looked at, then a NULL context is reported under the function's own name.  Nothing reaches a HIP call."""
+import pytest
+
+NAME = "mkhe_bfv_ct_lincomb"
+
+# (nin, nout, message)
+ROWS = [
+    (0, 1, NAME + ": nin must be 1 .. 16"),
+    (17, 1, NAME + ": nin must be 1 .. 16"),
+    (-1, 1, NAME + ": nin must be 1 .. 16"),
+    (16, 0, NAME + ": nout must be 1 .. 64"),
+    (16, 65, NAME + ": nout must be 1 .. 64"),
+    (1, 1, NAME + ": null context"),
+    (16, 64, NAME + ": null context"),
+]
+
+
+@pytest.mark.parametrize("nin,nout,message", ROWS, ids=["%d-%d" % r[:2] for r in ROWS])
+def test_a_call_without_a_context_is_refused_with_exactly_this_message(nin, nout, message):
+    from mkhe_kklss_amd._abi import lib
+    # a message of another call first, so that the one read back is this call's
+    assert lib().mkhe_swk_fold(None, None, 0, 0) == 1 and lib().mkhe_last_error().decode() == "mkhe_swk_fold: null argument"
+    assert lib().mkhe_bfv_ct_lincomb(None, nin, None, nout, None, None) == 1
+    assert lib().mkhe_last_error().decode() == message
