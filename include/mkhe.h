@@ -813,6 +813,19 @@ int  mkhe_ckks_scale_down(mkhe_ctx* ctx, int limbs, int count, const void* dev_p
 int  mkhe_ckks_encode(mkhe_ctx* ctx, int level, int count, const void* dev_slots, double scale, void* dev_pt);
 /* the decoding of Decrypt decryptor.go:34-43 == project(scale_down), bit for bit */
 int  mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, double scale, void* dev_slots);
+/* Sparse packing: n = 2^log_slots slots, 0 <= log_slots <= logN - 1 (params.LogSlots() of mkckks/encryptor.go:18,43,62), slots
+ * double[count][n][2]; coeffs and pt keep their full shapes.  With the gap g = N / 2n the message is a polynomial in X^g:
+ * coeffs[k g] = m'[k], k < 2n, where m' is the embedding above for the ring of degree 2n (slot j = the evaluation at exp(i pi 5^j / 2n);
+ * n = 1: m' = Re z + Y Im z), and exactly 0.0 elsewhere; seen through the full embedding it is the n slots repeated N / 2n times, so
+ * the evaluator acts on it slot-wise and a rotation by k rotates it by k mod n.  embed and encode write every word of their output
+ * (off the grid: 0.0, residue 0 in every limb); project and decode read only the 2n coefficients on the grid, which for arbitrary
+ * coefficients is the mean over the N / 2n replicas of the full projection.  encode_sparse == scale_up(embed_sparse) and
+ * decode_sparse == project_sparse(scale_down), bit for bit; log_slots = logN - 1 is the four calls above, bit for bit.  Refusals
+ * as above, and "<entry>: log_slots must be 0 .. <logN - 1>". */
+int  mkhe_ckks_embed_sparse(mkhe_ctx* ctx, int log_slots, int count, const void* dev_slots, void* dev_coeffs);
+int  mkhe_ckks_project_sparse(mkhe_ctx* ctx, int log_slots, int count, const void* dev_coeffs, void* dev_slots);
+int  mkhe_ckks_encode_sparse(mkhe_ctx* ctx, int level, int log_slots, int count, const void* dev_slots, double scale, void* dev_pt);
+int  mkhe_ckks_decode_sparse(mkhe_ctx* ctx, int limbs, int log_slots, int count, const void* dev_pt, double scale, void* dev_slots);
 /* log2 of the largest transform (N/2 points) that one workgroup does in LDS: 13 where the runtime grants 128 KiB of dynamic LDS, else 11;
  * larger transforms take two launches over a work buffer (same bits).  -1 = error.  mkhe_ctx_set_ckks_tile lowers the limit to 11 (or
  * puts it back: 0, or the granted value), so that the two-launch form of N/2 = 2^12, 2^13 can be run and tested on any machine. */

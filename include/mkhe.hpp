@@ -1005,27 +1005,33 @@ class Evaluator {
     }
 };
 
-// The CKKS encoder on the device (mkhe_ckks_encode / mkhe_ckks_decode): the message layer of mkckks/encryptor.go:42-64 and
+// The CKKS encoder on the device (mkhe_ckks_encode_sparse / mkhe_ckks_decode_sparse): the message layer of mkckks/encryptor.go:42-64 and
 // mkckks/decryptor.go:34-43.  lattigo's ckks.Encoder, which those lines call, is not in the reference tree: this is the canonical
-// embedding with full packing (Slots() = N/2 complex values per message), not lattigo's code path.  Messages cross the bus as slots;
+// embedding, not lattigo's code path.  Slots() = 2^logSlots complex values per message; the default is full packing, logSlots = logN - 1,
+// below it the packing is sparse (include/mkhe.h: the message is a polynomial in X^(N / 2 Slots())).  Messages cross the bus as slots;
 // plaintexts are device buffers uint64[count][level+1][N], coefficient domain: what mkrlwe::Encryptor takes and Decryptor writes.
 class Encoder {
   public:
-    explicit Encoder(Parameters& p) : params(p) {}
-    int Slots() const { return params.N() / 2; }
+    explicit Encoder(Parameters& p, int logSlots = -1) : params(p), logSlots_(logSlots < 0 ? p.LogN() - 1 : logSlots) {
+        if (logSlots_ > p.LogN() - 1) throw Error("mkckks::Encoder: logSlots must lie between 0 and logN - 1");
+    }
+    int LogSlots() const { return logSlots_; }
+    int Slots() const { return 1 << logSlots_; }
     // count messages (host: count * Slots() values) at `level` and `scale` -> dev_pt, as one launch set
     void Encode(int count, const std::complex<double>* values, int level, double scale, void* dev_pt) {
-        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
+        mkrlwe::DeviceWords z(params, 2 * (size_t)count * Slots());
         check(mkhe_buf_upload(params.ctx, z.d, reinterpret_cast<const uint64_t*>(values), z.words));
-        check(mkhe_ckks_encode(params.ctx, level, count, z.d, scale, dev_pt));
+        check(mkhe_ckks_encode_sparse(params.ctx, level, logSlots_, count, z.d, scale, dev_pt));
     }
     // count plaintexts of `limbs` limbs at `scale` -> values (host: count * Slots())
     void Decode(int limbs, int count, const void* dev_pt, double scale, std::complex<double>* values) {
-        mkrlwe::DeviceWords z(params, (size_t)count * params.N());
-        check(mkhe_ckks_decode(params.ctx, limbs, count, dev_pt, scale, z.d));
+        mkrlwe::DeviceWords z(params, 2 * (size_t)count * Slots());
+        check(mkhe_ckks_decode_sparse(params.ctx, limbs, logSlots_, count, dev_pt, scale, z.d));
         z.download(reinterpret_cast<uint64_t*>(values));
     }
     Parameters& params;
+  private:
+    int logSlots_;
 };
 // mkrlwe::Decryptor with the noise of a ciphertext against the message it should hold: the residual of the phase against the device encoder's plaintext
 // of msg (Slots() values) at the level and scale of ct.  NoiseBits is what the floodBits of a ShareNew must exceed.

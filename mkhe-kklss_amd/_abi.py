@@ -138,6 +138,10 @@ SIGNATURES = {
     "mkhe_ckks_scale_down": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
     "mkhe_ckks_encode": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
     "mkhe_ckks_decode": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),
+    "mkhe_ckks_embed_sparse": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "mkhe_ckks_project_sparse": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "mkhe_ckks_encode_sparse": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp]),
+    "mkhe_ckks_decode_sparse": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp]),
     "mkhe_ctx_ckks_tile": (C.c_int, [vp]),
     "mkhe_ctx_set_ckks_tile": (C.c_int, [vp, C.c_int]),
     "mkhe_bfv_slots_to_coeffs": (C.c_int, [vp, C.c_int, vp, vp]),

@@ -1211,6 +1211,34 @@ int mkhe_ckks_decode(mkhe_ctx* ctx, int limbs, int count, const void* dev_pt, do
         c->ckks_decode(limbs, count, (const u64*)dev_pt, scale, (double*)dev_slots);
     })
 }
+int mkhe_ckks_embed_sparse(mkhe_ctx* ctx, int log_slots, int count, const void* dev_slots, void* dev_coeffs) {
+    MKHE_TRY({
+        encoder_enter(ctx, false, "mkhe_ckks_embed_sparse", count, dev_slots, dev_coeffs)->ckks_embed_sparse(log_slots, count, (const double*)dev_slots,
+                                                                                                             (double*)dev_coeffs);
+    })
+}
+int mkhe_ckks_project_sparse(mkhe_ctx* ctx, int log_slots, int count, const void* dev_coeffs, void* dev_slots) {
+    MKHE_TRY({
+        encoder_enter(ctx, false, "mkhe_ckks_project_sparse", count, dev_coeffs, dev_slots)->ckks_project_sparse(log_slots, count, (const double*)dev_coeffs,
+                                                                                                                 (double*)dev_slots);
+    })
+}
+int mkhe_ckks_encode_sparse(mkhe_ctx* ctx, int level, int log_slots, int count, const void* dev_slots, double scale, void* dev_pt) {
+    MKHE_TRY({
+        ck_scale_ok(scale, "mkhe_ckks_encode_sparse");
+        Context* c = encoder_enter(ctx, false, "mkhe_ckks_encode_sparse", count, dev_slots, dev_pt);
+        ck_limbs_ok(c, level + 1, "mkhe_ckks_encode_sparse", "level");
+        c->ckks_encode_sparse(level, log_slots, count, (const double*)dev_slots, scale, (u64*)dev_pt);
+    })
+}
+int mkhe_ckks_decode_sparse(mkhe_ctx* ctx, int limbs, int log_slots, int count, const void* dev_pt, double scale, void* dev_slots) {
+    MKHE_TRY({
+        ck_scale_ok(scale, "mkhe_ckks_decode_sparse");
+        Context* c = encoder_enter(ctx, false, "mkhe_ckks_decode_sparse", count, dev_pt, dev_slots);
+        ck_limbs_ok(c, limbs, "mkhe_ckks_decode_sparse", "limbs");
+        c->ckks_decode_sparse(limbs, log_slots, count, (const u64*)dev_pt, scale, (double*)dev_slots);
+    })
+}
 
 // ---- BFV batch encoder (bfv_encode.hip)
 int mkhe_ctx_bfv_tile(mkhe_ctx* ctx) {

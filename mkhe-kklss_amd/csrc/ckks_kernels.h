@@ -1,5 +1,6 @@
 // ckks_kernels.h -- the CKKS encoder on the device: the canonical embedding between n = N/2 complex slots and N real coefficients
-// (full packing), and the scaling between real coefficients and RNS polynomials.  What mkckks/encryptor.go:42-64 and
+// (full packing; sparse packing, n < N/2, is the same embedding for the ring of degree 2n on a grid of the coefficients: below), and the scaling
+// between real coefficients and RNS polynomials.  What mkckks/encryptor.go:42-64 and
 // mkckks/decryptor.go:34-43 reach through lattigo's ckks.Encoder; that encoder is not part of the reference tree, so what is restated
 // here is the embedding itself, not lattigo's code path.  Every kernel takes a batch count (grid.y).
 //
@@ -65,5 +66,20 @@ void launch_ck_scale_up(int count, const double* coeffs, double scale, u64* pt, 
 // pt must hold canonical residues.
 void launch_ck_scale_down(int count, const u64* pt, double scale, double* coeffs, u64* dig, const u64* garner, int nq, const Mod* mods, int limbs, int N,
                           hipStream_t st);
+
+// ---- sparse packing: n = 2^logSlots < N/2 slots.  The message is a polynomial in X^g, g = N / 2n = 2^gap_log: m[k g] = m'[k], k < 2n, with m'
+// the embedding of the ring of degree 2n (the transform above with logn = logSlots and that ring's tables), and exactly zero elsewhere.  The
+// transforms work on COMPACT arrays [count][2n] that hold m'; these kernels move between them and the grid of the full-length arrays.
+// pt[b][l][i] = the residues of launch_ck_scale_up for compact[b][i / g] on the grid, 0 off it: every word of pt is written.  One thread per (i, b).
+void launch_ck_sparse_scale_up(int count, const double* compact, double scale, u64* pt, const Mod* mods, int limbs, int N, int gap_log, hipStream_t st);
+// compact[b][c] = the value of launch_ck_scale_down for the coefficient c g of pt[b]; off-grid words of pt are not read.  dig [count][limbs][2n].
+void launch_ck_sparse_scale_down(int count, const u64* pt, double scale, double* compact, u64* dig, const u64* garner, int nq, const Mod* mods, int limbs,
+                                 int N, int gap_log, hipStream_t st);
+// coeffs[b][c g] = compact[b][c], 0.0 elsewhere / compact[b][c] = coeffs[b][c g]
+void launch_ck_spread(int count, const double* compact, double* coeffs, int N, int gap_log, hipStream_t st);
+void launch_ck_pick(int count, const double* coeffs, double* compact, int N, int gap_log, hipStream_t st);
+// n = 2^logn < 16 slots (the register tail of the tile transform takes 16 points): the embedding as a direct sum of n products per output, one thread
+// per output.  root [n][n]: zeta_j^k = exp(i pi 5^j k / 2n).  inverse (embed): in slots [count][n][2], out compact [count][2n]; else the reverse.
+void launch_ck_direct(bool inverse, int count, const double* in, double* out, const double2* root, int logn, hipStream_t st);
 
 }  // namespace mkhe

@@ -82,10 +82,9 @@ void launch_ck_fft(bool inverse, const CkFft& a, int count, hipStream_t st) {
 
 constexpr int CK_THREADS = 256;
 
-__global__ void __launch_bounds__(CK_THREADS) ck_scale_up_kernel(const double* coeffs, double scale, u64* pt, const Mod* mods, int limbs, int N) {
-    const int n = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
-    if (n >= N) return;
-    const double r = rint(coeffs[(long)b * N + n] * scale), mag = fabs(r);
+// the residues of r = rint(c * scale) under mods[0 .. limbs) into pt[l * N] (ckks_kernels.h, launch_ck_scale_up)
+__device__ __forceinline__ void ck_residues(double c, double scale, u64* pt, const Mod* mods, int limbs, long N) {
+    const double r = rint(c * scale), mag = fabs(r);
     const bool neg = r < 0.0;
     // |r| = a * 2^e with a < 2^62
     u64 a;
@@ -107,8 +106,31 @@ __global__ void __launch_bounds__(CK_THREADS) ck_scale_up_kernel(const double* c
             }
         }
         const u64 v = mont_mul(a, w, md.q, md.ninv32);
-        pt[((long)b * limbs + l) * N + n] = (neg && v) ? md.q - v : v;
+        pt[l * N] = (neg && v) ? md.q - v : v;
     }
+}
+// (centred lift of the residues x[l * xs]) / scale, through the digits d[l * ds] (ckks_kernels.h, launch_ck_scale_down)
+__device__ __forceinline__ double ck_lift(const u64* x, long xs, u64* d, long ds, double scale, const u64* garner, int nq, const Mod* mods, int limbs) {
+    garner_digits([&](int j, const Mod&) { return x[j * xs]; }, d, garner, nq, mods, limbs, ds);
+    bool neg = false;
+    for (int i = limbs - 1; i >= 0; --i) {
+        const u64 di = d[i * ds], oi = mods[i].q - 1 - di;
+        if (di != oi) { neg = di > oi; break; }
+    }
+    double acc = 0.0;
+    for (int i = limbs - 1; i >= 0; --i) {
+        const u64 q = mods[i].q, di = d[i * ds];
+        acc = acc * (double)q + (double)(neg ? q - 1 - di : di);
+    }
+    if (neg) acc += 1.0;
+    const double v = acc / scale;
+    return neg ? -v : v;
+}
+
+__global__ void __launch_bounds__(CK_THREADS) ck_scale_up_kernel(const double* coeffs, double scale, u64* pt, const Mod* mods, int limbs, int N) {
+    const int n = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
+    if (n >= N) return;
+    ck_residues(coeffs[(long)b * N + n], scale, pt + (long)b * limbs * N + n, mods, limbs, N);
 }
 void launch_ck_scale_up(int count, const double* coeffs, double scale, u64* pt, const Mod* mods, int limbs, int N, hipStream_t st) {
     hipLaunchKernelGGL(ck_scale_up_kernel, dim3((N + CK_THREADS - 1) / CK_THREADS, count), dim3(CK_THREADS), 0, st, coeffs, scale, pt, mods, limbs, N);
@@ -118,27 +140,80 @@ __global__ void __launch_bounds__(CK_THREADS) ck_scale_down_kernel(const u64* pt
                                                                    const Mod* mods, int limbs, int N) {
     const int n = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
     if (n >= N) return;
-    const u64* x = pt + (long)b * limbs * N + n;
-    u64* d = dig + (long)b * limbs * N + n;
-    garner_digits([&](int j, const Mod&) { return x[(long)j * N]; }, d, garner, nq, mods, limbs, N);
-    bool neg = false;
-    for (int i = limbs - 1; i >= 0; --i) {
-        const u64 di = d[(long)i * N], oi = mods[i].q - 1 - di;
-        if (di != oi) { neg = di > oi; break; }
-    }
-    double acc = 0.0;
-    for (int i = limbs - 1; i >= 0; --i) {
-        const u64 q = mods[i].q, di = d[(long)i * N];
-        acc = acc * (double)q + (double)(neg ? q - 1 - di : di);
-    }
-    if (neg) acc += 1.0;
-    const double v = acc / scale;
-    coeffs[(long)b * N + n] = neg ? -v : v;
+    coeffs[(long)b * N + n] = ck_lift(pt + (long)b * limbs * N + n, N, dig + (long)b * limbs * N + n, N, scale, garner, nq, mods, limbs);
 }
 void launch_ck_scale_down(int count, const u64* pt, double scale, double* coeffs, u64* dig, const u64* garner, int nq, const Mod* mods, int limbs, int N,
                           hipStream_t st) {
     hipLaunchKernelGGL(ck_scale_down_kernel, dim3((N + CK_THREADS - 1) / CK_THREADS, count), dim3(CK_THREADS), 0, st, pt, scale, coeffs, dig, garner, nq,
                        mods, limbs, N);
+}
+
+// ---- sparse packing: compact [count][M] (M = 2n = N >> gap_log) <-> the grid i = c << gap_log of [count][N]
+__global__ void __launch_bounds__(CK_THREADS) ck_sparse_scale_up_kernel(const double* compact, double scale, u64* pt, const Mod* mods, int limbs, int N,
+                                                                        int gap_log) {
+    const int i = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
+    if (i >= N) return;
+    u64* col = pt + (long)b * limbs * N + i;
+    if (i & ((1 << gap_log) - 1)) {
+        for (int l = 0; l < limbs; ++l) col[(long)l * N] = 0;
+        return;
+    }
+    ck_residues(compact[(long)b * (N >> gap_log) + (i >> gap_log)], scale, col, mods, limbs, N);
+}
+void launch_ck_sparse_scale_up(int count, const double* compact, double scale, u64* pt, const Mod* mods, int limbs, int N, int gap_log, hipStream_t st) {
+    hipLaunchKernelGGL(ck_sparse_scale_up_kernel, dim3((N + CK_THREADS - 1) / CK_THREADS, count), dim3(CK_THREADS), 0, st, compact, scale, pt, mods, limbs,
+                       N, gap_log);
+}
+__global__ void __launch_bounds__(CK_THREADS) ck_sparse_scale_down_kernel(const u64* pt, double scale, double* compact, u64* dig, const u64* garner, int nq,
+                                                                          const Mod* mods, int limbs, int N, int gap_log) {
+    const int M = N >> gap_log, c = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
+    if (c >= M) return;
+    compact[(long)b * M + c] = ck_lift(pt + (long)b * limbs * N + ((long)c << gap_log), N, dig + (long)b * limbs * M + c, M, scale, garner, nq, mods, limbs);
+}
+void launch_ck_sparse_scale_down(int count, const u64* pt, double scale, double* compact, u64* dig, const u64* garner, int nq, const Mod* mods, int limbs,
+                                 int N, int gap_log, hipStream_t st) {
+    const int M = N >> gap_log;
+    hipLaunchKernelGGL(ck_sparse_scale_down_kernel, dim3((M + CK_THREADS - 1) / CK_THREADS, count), dim3(CK_THREADS), 0, st, pt, scale, compact, dig, garner,
+                       nq, mods, limbs, N, gap_log);
+}
+__global__ void __launch_bounds__(CK_THREADS) ck_spread_kernel(const double* compact, double* coeffs, int N, int gap_log) {
+    const int i = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
+    if (i >= N) return;
+    coeffs[(long)b * N + i] = (i & ((1 << gap_log) - 1)) ? 0.0 : compact[(long)b * (N >> gap_log) + (i >> gap_log)];
+}
+void launch_ck_spread(int count, const double* compact, double* coeffs, int N, int gap_log, hipStream_t st) {
+    hipLaunchKernelGGL(ck_spread_kernel, dim3((N + CK_THREADS - 1) / CK_THREADS, count), dim3(CK_THREADS), 0, st, compact, coeffs, N, gap_log);
+}
+__global__ void __launch_bounds__(CK_THREADS) ck_pick_kernel(const double* coeffs, double* compact, int N, int gap_log) {
+    const int M = N >> gap_log, c = blockIdx.x * CK_THREADS + threadIdx.x, b = blockIdx.y;
+    if (c >= M) return;
+    compact[(long)b * M + c] = coeffs[(long)b * N + ((long)c << gap_log)];
+}
+void launch_ck_pick(int count, const double* coeffs, double* compact, int N, int gap_log, hipStream_t st) {
+    const int M = N >> gap_log;
+    hipLaunchKernelGGL(ck_pick_kernel, dim3((M + CK_THREADS - 1) / CK_THREADS, count), dim3(CK_THREADS), 0, st, coeffs, compact, N, gap_log);
+}
+
+// n < 16 slots: the embedding as a direct sum, one thread per output.  root[j * n + k] = zeta_j^k
+template <bool INV> __global__ void __launch_bounds__(CK_THREADS) ck_direct_kernel(const double* in, double* out, const cplx* root, int logn, int count) {
+    const int n = 1 << logn, t = blockIdx.x * CK_THREADS + threadIdx.x, b = t >> logn, o = t & (n - 1);
+    if (b >= count) return;
+    cplx acc{0.0, 0.0};
+    if (INV) {              // w_k = (1/n) sum_j z_j conj(zeta_j^k), k = o
+        const cplx* z = reinterpret_cast<const cplx*>(in) + (long)b * n;
+        for (int j = 0; j < n; ++j) { const cplx v = cmulc(z[j], root[j * n + o]); acc.x += v.x; acc.y += v.y; }
+        const double invn = 1.0 / (double)n;
+        out[(long)b * 2 * n + o] = acc.x * invn; out[(long)b * 2 * n + n + o] = acc.y * invn;
+    } else {                // z_j = sum_k (m_k + i m_(k+n)) zeta_j^k, j = o
+        const double* m = in + (long)b * 2 * n;
+        for (int k = 0; k < n; ++k) { const cplx v = cmul(cplx{m[k], m[k + n]}, root[o * n + k]); acc.x += v.x; acc.y += v.y; }
+        reinterpret_cast<cplx*>(out)[(long)b * n + o] = acc;
+    }
+}
+void launch_ck_direct(bool inverse, int count, const double* in, double* out, const double2* root, int logn, hipStream_t st) {
+    const dim3 grid((((long)count << logn) + CK_THREADS - 1) / CK_THREADS), block(CK_THREADS);
+    if (inverse) hipLaunchKernelGGL(ck_direct_kernel<true>, grid, block, 0, st, in, out, root, logn, count);
+    else hipLaunchKernelGGL(ck_direct_kernel<false>, grid, block, 0, st, in, out, root, logn, count);
 }
 
 }  // namespace mkhe

@@ -352,6 +352,12 @@ class Context {
     void ckks_scale_down(int limbs, int count, const u64* pt, double scale, double* coeffs);
     void ckks_encode(int level, int count, const double* slots, double scale, u64* pt);
     void ckks_decode(int limbs, int count, const u64* pt, double scale, double* slots);
+    // sparse packing, n = 2^log_slots slots (0 .. logN - 1; logN - 1 is the calls above): slots double[count][n][2]; coeffs and pt as above, with the
+    // message on the grid of stride N / 2n and zero off it (ckks_kernels.h)
+    void ckks_embed_sparse(int log_slots, int count, const double* slots, double* coeffs);
+    void ckks_project_sparse(int log_slots, int count, const double* coeffs, double* slots);
+    void ckks_encode_sparse(int level, int log_slots, int count, const double* slots, double scale, u64* pt);
+    void ckks_decode_sparse(int limbs, int log_slots, int count, const u64* pt, double scale, double* slots);
     // log2 of the largest transform one workgroup does in LDS (CK_TILE_LOG_BIG, or CK_TILE_LOG when the runtime grants no more LDS), and a way
     // to lower it to CK_TILE_LOG so that the two-launch form of n = 2^12, 2^13 can be run where the runtime does grant it (0: back to the grant)
     int ckks_tile();
@@ -433,7 +439,7 @@ class Context {
   private:
     // Every table above and every pool, lazily built table and Scratch buffer below is a block of mem_ (device_memory.h): the members are non-owning
     // pointers into it and release_all names none of them.  (Handles are not in it: pool_free.)  Then the scratch pools:
-    // The tables of a first-use build (kg_*, d_ck_*, d_bf_*) keep stale values after a build that failed and was rolled back: read them only behind
+    // The tables of a first-use build (kg_*, ck_tab_, d_bf_*) keep stale values after a build that failed and was rolled back: read them only behind
     // their *_ready_ flag, never test them for null.
     DeviceMemory mem_;
     u64 *x_ = nullptr, *y_ = nullptr, *swk3_ = nullptr;      // swkPool1..3
@@ -501,14 +507,18 @@ class Context {
             launch();
         }
     }
-    // CKKS encoder: tables built at the first call (twiddles [n/2][2], twist [n][2], permutation [n]), the largest
-    // FFT one workgroup does in LDS, and the scratch for the two-launch FFT, the Garner digits and the coefficients of the fused calls
-    double *d_ck_w = nullptr, *d_ck_twist = nullptr; u32* d_ck_pos = nullptr;
+    // CKKS encoder: tables per slot count n = 2^logn built at its first use (n >= 16: twiddles [n/2][2], twist [n][2], permutation [n]; below:
+    // the roots [n][n][2] of the direct sum), the largest FFT one workgroup does in LDS, and the scratch for the two-launch FFT, the Garner digits
+    // and the coefficients of the fused calls (sparse packing: compact [count][2n])
+    struct CkTables { double *w = nullptr, *twist = nullptr, *root = nullptr; u32* pos = nullptr; bool ready = false; };
+    std::vector<CkTables> ck_tab_;                           // by logn < logN
     bool ck_ready_ = false;
     TileLimit ck_tile_{CK_TILE_LOG, CK_TILE_LOG};
     Scratch ck_work_, ck_dig_, ck_coeff_;
     void ck_init(const char* what);
-    void ck_fft(bool inverse, int count, const double* in, double* out);
+    const CkTables& ck_tables(int logn);
+    int ck_sparse_init(const char* what, int log_slots);     // ck_init + the range of log_slots; -> gap_log
+    void ck_fft(bool inverse, int logn, int count, const double* in, double* out);
     void ck_scale_up(int level, int count, const double* coeffs, double scale, u64* pt);
     void ck_scale_down(int limbs, int count, const u64* pt, double scale, double* coeffs);
     // BFV batch encoder: tables built at the first call (bf_init), scratch that holds message-derived values (zeroed behind its last use)

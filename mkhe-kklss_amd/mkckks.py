@@ -21,13 +21,21 @@ def scaleUpExact(value, n, q):
     return q - res if value < 0 else res
 
 
+def _check_log_slots(who, logSlots, logN):
+    if isinstance(logSlots, bool) or int(logSlots) != logSlots or not 0 <= logSlots <= logN - 1:
+        raise MkheError("%s: logSlots must lie between 0 and logN - 1 = %d, got %r" % (who, logN - 1, logSlots))
+
+
 class Parameters(mkrlwe.Parameters):
-    """mkckks.Parameters (mkckks/params.go:11-24): mkrlwe parameters with gamma = 2 + default scale."""
+    """mkckks.Parameters (mkckks/params.go:11-24): mkrlwe parameters with gamma = 2 + default scale.  logSlots (default logN - 1, full packing):
+    messages have 2^logSlots slots (sparse packing below logN - 1: Encoder)."""
 
     def __init__(self, logN, Q, P, scale, logSlots=None, psiQ=None, psiP=None, device=0):
+        logSlots = logN - 1 if logSlots is None else logSlots
+        _check_log_slots("mkckks.Parameters", logSlots, logN)          # (before the context is opened)
         super().__init__(logN, Q, P, gamma=2, psiQ=psiQ, psiP=psiP, device=device)
         self._scale = float(scale)
-        self.logSlots = logN - 1 if logSlots is None else logSlots
+        self.logSlots = int(logSlots)
 
     def Scale(self): return self._scale
     def LogSlots(self): return self.logSlots
@@ -476,7 +484,7 @@ LinTransPlan = collections.namedtuple("LinTransPlan", "n1 babies giants")
 
 
 def linear_transform_plan(indices, n, n1=None):
-    """Baby steps and giant steps for the diagonal indices `indices` (taken mod n = N/2), a pure function: k = b + g with b = k mod n1 and g = k - b.
+    """Baby steps and giant steps for the diagonal indices `indices` (taken mod n, the number of slots), a pure function: k = b + g with b = k mod n1 and g = k - b.
     -> (n1, sorted babies, sorted giants).  n1 is a power of two <= 16; the default minimises the number of rotations (non-zero babies + non-zero
     giants), ties to the smaller n1.  MkheError when the diagonals need more than 64 giants."""
     n = int(n)
@@ -497,7 +505,7 @@ def linear_transform_plan(indices, n, n1=None):
 
 
 class LinearTransform:
-    """The diagonals {k: d_k} of (M z)[j] = sum_k d_k[j] z[(j + k) mod n], n = N/2 slots -- the convention of RotateNew(ct, k), which moves slot j + k to
+    """The diagonals {k: d_k} of (M z)[j] = sum_k d_k[j] z[(j + k) mod n], n = 2^params.LogSlots() slots -- the convention of RotateNew(ct, k), which moves slot j + k to
     slot j -- encoded once for Evaluator.LinearTransformNew.  Diagonal k = g + b (linear_transform_plan) is stored pre-rotated, np.roll(d_k, g), so that
     M z = sum_g rot_g(sum_b d'_(g,b) (.) rot_b z).  All of them are encoded on the device in ONE EncodeBatch at `level` and at the scale
     pt_scale = out_scale * Q[level] / in_scale (both default to params.Scale()), then prepared in ONE mkhe_ptxt_prepare into a compact block in (g, b)
@@ -505,7 +513,7 @@ class LinearTransform:
     fused=False))."""
 
     def __init__(self, params, diagonals, level, in_scale=None, out_scale=None, n1=None, keep_coeff=False):
-        n = params.N() // 2
+        n = 1 << params.LogSlots()
         level = int(level)
         if level < 0 or level > params.MaxLevel():
             raise MkheError("LinearTransform: the level must lie between 0 and %d" % params.MaxLevel())
@@ -534,9 +542,10 @@ class LinearTransform:
     @classmethod
     def FromMatrix(cls, params, M, level, **kw):
         """the d x d matrix M, d a power of two <= n, as the d diagonals of the d-periodic operator d_k[j] = M[j mod d][(j + k) mod d]: on a vector whose
-        d entries are replicated n / d times it gives M @ v, replicated.  Diagonals that are zero throughout are left out."""
+        d entries are replicated n / d times it gives M @ v, replicated (d = n = 2^params.LogSlots(): M @ v itself).  Diagonals that are zero
+        throughout are left out."""
         M = np.asarray(M, dtype=np.complex128)
-        n, d = params.N() // 2, M.shape[0]
+        n, d = 1 << params.LogSlots(), M.shape[0]
         if M.ndim != 2 or M.shape != (d, d) or d < 1 or d & (d - 1) or d > n:
             raise MkheError("LinearTransform.FromMatrix: the matrix must be d x d with d a power of two, at most %d" % n)
         diags = matrix_diagonals(M, n)
@@ -886,28 +895,38 @@ class Plaintext:
 
 
 class Encoder:
-    """The canonical embedding of lattigo's ckks.Encoder on the HOST (numpy): slot j <-> evaluation at zeta^(5^j), zeta = exp(i*pi/N),
-    computed with one FFT of length 2N.  Full packing only (logSlots = logN - 1)."""
+    """The canonical embedding of lattigo's ckks.Encoder on the HOST (numpy): n = 2^logSlots slots (default params.LogSlots()).  With M = 2n and
+    the gap g = N / M a message is a polynomial in X^g: coefficient k g is coefficient k of the embedding for the ring of degree M -- slot j <->
+    evaluation at zeta^(5^j), zeta = exp(i*pi/M), computed with one FFT of length 2M -- and every other coefficient is exactly 0.0.  Seen through
+    the full embedding it is the n slots repeated g times.  Project and Decode read the coefficients on the grid only: for arbitrary coefficients
+    that is the mean over the g replicas of the full projection.  logSlots = logN - 1 is full packing (g = 1)."""
 
-    def __init__(self, params):
+    def __init__(self, params, logSlots=None):
         self.params = params
         self.N = params.N()
-        if params.LogSlots() != params.LogN() - 1:
-            raise MkheError("mkckks.Encoder: only logSlots = logN - 1 is supported")
-        self.n = self.N // 2
+        self.logSlots = params.LogSlots() if logSlots is None else logSlots
+        _check_log_slots("mkckks.Encoder", self.logSlots, params.LogN())
+        self.n = 1 << self.logSlots
+        self.M = 2 * self.n
+        self.gap = self.N // self.M
         rot, r = np.empty(self.n, dtype=np.int64), 1
         for j in range(self.n):
-            rot[j], r = r, r * mkrlwe.GALOIS_GEN % (2 * self.N)
+            rot[j], r = r, r * mkrlwe.GALOIS_GEN % (2 * self.M)
         self.rot = rot
 
     def Embed(self, values):
-        """slots -> real coefficients m with sum_k m_k zeta_j^k = z_j:  m_k = (2/N) Re sum_j z_j conj(zeta_j)^k"""
+        """slots -> real coefficients m with sum_k m_(k g) zeta_j^k = z_j:  m_(k g) = (2/M) Re sum_j z_j conj(zeta_j)^k, 0.0 off the grid"""
         z = np.asarray(values, dtype=np.complex128)
         if z.shape != (self.n,):
             raise MkheError("mkckks.Encoder: expected %d slots, got %r" % (self.n, z.shape))
-        a = np.zeros(2 * self.N, dtype=np.complex128)
+        a = np.zeros(2 * self.M, dtype=np.complex128)
         a[self.rot] = z
-        return (2.0 / self.N) * np.real(np.fft.fft(a)[: self.N])
+        m = (2.0 / self.M) * np.real(np.fft.fft(a)[: self.M])
+        if self.gap == 1:
+            return m
+        out = np.zeros(self.N, dtype=np.float64)
+        out[:: self.gap] = m
+        return out
 
     def Encode(self, values, level, scale):
         """-> RNS plaintext uint64 [level+1][N]: round(m * scale) per coefficient (half to even), reduced exactly whatever its size"""
@@ -920,24 +939,27 @@ class Encoder:
         return np.stack([np.array([int(v) for v in r % q], dtype=np.uint64) for q in Q])
 
     def Decode(self, poly, scale):
-        """RNS polynomial [limbs][N] (canonical residues) at `scale` -> slots: CRT, centring, then the embedding"""
-        poly = np.asarray(poly, dtype=np.uint64)
+        """RNS polynomial [limbs][N] (canonical residues) at `scale` -> slots: CRT and centring of the coefficients on the grid, then the embedding"""
+        poly = np.asarray(poly, dtype=np.uint64)[:, :: self.gap]
         Q = self.params.Q[: poly.shape[0]]
         Qp = 1
         for q in Q:
             Qp *= q
-        x = np.zeros(self.N, dtype=object)
+        x = np.zeros(self.M, dtype=object)
         for l, q in enumerate(Q):
             Mi = Qp // q
             x = x + poly[l].astype(object) * (Mi * pow(Mi, -1, q))
         x = x % Qp
-        return self.Project(np.array([float(v - Qp if v > Qp // 2 else v) for v in x]) / float(scale))
+        return self._project(np.array([float(v - Qp if v > Qp // 2 else v) for v in x]) / float(scale))
 
     def Project(self, m):
-        """real coefficients -> slots: z_j = sum_k m_k zeta_j^k"""
-        a = np.zeros(2 * self.N, dtype=np.complex128)
-        a[: self.N] = m
-        return (2 * self.N) * np.fft.ifft(a)[self.rot]
+        """real coefficients [N] -> slots: z_j = sum_k m_(k g) zeta_j^k"""
+        return self._project(np.asarray(m)[:: self.gap])
+
+    def _project(self, m):
+        a = np.zeros(2 * self.M, dtype=np.complex128)
+        a[: self.M] = m
+        return (2 * self.M) * np.fft.ifft(a)[self.rot]
 
 
 def slot_permutation(logN):
@@ -952,20 +974,35 @@ def slot_permutation(logN):
 
 class DeviceEncoder:
     """The interface of Encoder on the DEVICE (mkhe_ckks_*: csrc/ckks_kernels.hip), plus batch forms.  Messages go up and come down as
-    N/2 complex slots (16 bytes each); plaintexts stay resident as mkrlwe.DeviceLimbs.  Same embedding convention as Encoder; float64
-    arithmetic with another factorisation, so the bits of an encoding differ from the host encoder's in the last places."""
+    n = 2^logSlots complex slots (16 bytes each; default params.LogSlots()); plaintexts stay resident as mkrlwe.DeviceLimbs.  Same embedding
+    convention as Encoder, sparse packing included (mkhe_ckks_*_sparse); float64 arithmetic with another factorisation, so the bits of an encoding
+    differ from the host encoder's in the last places."""
 
-    def __init__(self, params):
+    def __init__(self, params, logSlots=None):
         self.params = params
         self.N = params.N()
-        if params.LogSlots() != params.LogN() - 1:
-            raise MkheError("mkckks.DeviceEncoder: only logSlots = logN - 1 is supported")
-        self.n = self.N // 2
+        self.logSlots = params.LogSlots() if logSlots is None else logSlots
+        _check_log_slots("mkckks.DeviceEncoder", self.logSlots, params.LogN())
+        self.n = 1 << self.logSlots
+        self.full = self.logSlots == params.LogN() - 1
 
-    # a float64 array of count * N values <-> a raw device buffer (one 8-byte word per double)
-    def _up(self, a, count):
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(count, 1, self.N)
-        return mkrlwe.DeviceLimbs(self.params, count, 1).upload(a.view(np.uint64))
+    def _call(self, stage, *args):
+        """mkhe_ckks_<stage>(ctx, [level or limbs,] count, ..) or, below full packing, mkhe_ckks_<stage>_sparse with log_slots in front of count"""
+        if self.full:
+            check(getattr(lib(), "mkhe_ckks_" + stage)(self.params.ctx, *args))
+        else:
+            at = 0 if stage in ("embed", "project") else 1
+            check(getattr(lib(), "mkhe_ckks_%s_sparse" % stage)(self.params.ctx, *args[:at], self.logSlots, *args[at:]))
+
+    # a float64 array <-> a raw device buffer (one 8-byte word per double) of whole rows of N words
+    def _up(self, a):
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        rows = -(-a.size // self.N)
+        a = np.concatenate([a, np.zeros(rows * self.N - a.size)])
+        return mkrlwe.DeviceLimbs(self.params, 1, rows).upload(a.view(np.uint64).reshape(1, rows, self.N))
+
+    def _slot_buffer(self, count):
+        return mkrlwe.DeviceLimbs(self.params, 1, -(-2 * self.n * count // self.N))
 
     def _slots(self, values):
         """-> (complex128 [count][n], whether the caller passed one message)"""
@@ -976,16 +1013,16 @@ class DeviceEncoder:
             raise MkheError("mkckks.DeviceEncoder: expected %d slots per message, got %r" % (self.n, np.shape(values)))
         return np.ascontiguousarray(z), one
 
-    def _down_slots(self, d, one):
-        z = d.download().view(np.float64).reshape(d.count, self.n, 2)
+    def _down_slots(self, d, count, one):
+        z = d.download().view(np.float64).ravel()[: count * self.n * 2].reshape(count, self.n, 2)
         z = z[..., 0] + 1j * z[..., 1]
         return z[0] if one else z
 
     def Embed(self, values):
         """slots [n] (or [count][n]) -> real coefficients [N] (or [count][N])"""
         z, one = self._slots(values)
-        src, dst = self._up(z.view(np.float64), len(z)), mkrlwe.DeviceLimbs(self.params, len(z), 1)
-        check(lib().mkhe_ckks_embed(self.params.ctx, len(z), src.devptr(), dst.devptr()))
+        src, dst = self._up(z.view(np.float64)), mkrlwe.DeviceLimbs(self.params, len(z), 1)
+        self._call("embed", len(z), src.devptr(), dst.devptr())
         m = dst.download().view(np.float64).reshape(len(z), self.N)
         return m[0] if one else m
 
@@ -996,15 +1033,15 @@ class DeviceEncoder:
         m = m[None] if one else m
         if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] != self.N:
             raise MkheError("mkckks.DeviceEncoder: expected %d coefficients per message, got %r" % (self.N, np.shape(coeffs)))
-        src, dst = self._up(m, len(m)), mkrlwe.DeviceLimbs(self.params, len(m), 1)
-        check(lib().mkhe_ckks_project(self.params.ctx, len(m), src.devptr(), dst.devptr()))
-        return self._down_slots(dst, one)
+        src, dst = self._up(m), self._slot_buffer(len(m))
+        self._call("project", len(m), src.devptr(), dst.devptr())
+        return self._down_slots(dst, len(m), one)
 
     def EncodeBatch(self, values, level, scale):
         """count messages -> device plaintexts [count][level+1][N] (coefficient domain, canonical) as one launch set"""
         z, _ = self._slots(values)
-        src, pt = self._up(z.view(np.float64), len(z)), mkrlwe.DeviceLimbs(self.params, len(z), level + 1)
-        check(lib().mkhe_ckks_encode(self.params.ctx, level, len(z), src.devptr(), float(scale), pt.devptr()))
+        src, pt = self._up(z.view(np.float64)), mkrlwe.DeviceLimbs(self.params, len(z), level + 1)
+        self._call("encode", level, len(z), src.devptr(), float(scale), pt.devptr())
         return pt
 
     def Encode(self, values, level, scale):
@@ -1019,9 +1056,9 @@ class DeviceEncoder:
         if not isinstance(poly, mkrlwe.DeviceLimbs):
             poly = np.ascontiguousarray(poly, dtype=np.uint64)
             poly = mkrlwe.DeviceLimbs(self.params, 1, poly.shape[0]).upload(poly[None])
-        dst = mkrlwe.DeviceLimbs(self.params, poly.count, 1)
-        check(lib().mkhe_ckks_decode(self.params.ctx, poly.limbs, poly.count, poly.devptr(), float(scale), dst.devptr()))
-        return self._down_slots(dst, poly.count == 1)
+        dst = self._slot_buffer(poly.count)
+        self._call("decode", poly.limbs, poly.count, poly.devptr(), float(scale), dst.devptr())
+        return self._down_slots(dst, poly.count, poly.count == 1)
 
 
 def _encoder(params, which):
@@ -1152,7 +1189,8 @@ class Decryptor(mkrlwe.Decryptor):
 
     def FloodSlotBound(self, parties, flood_bits, scale):
         """how far a merge of `parties` shares with flood_bits bits moves a slot, at most: N * parties * 2^(flood_bits - 1) / scale (the sum of
-        the flooding noises is below parties * 2^(flood_bits - 1) per coefficient, and a slot is a sum of N coefficients times unit-modulus roots)"""
+        the flooding noises is below parties * 2^(flood_bits - 1) per coefficient, and a slot is a sum of N coefficients times unit-modulus roots).
+        It remains an upper bound for sparse messages: a sparse slot is the mean of replicas that each meet it."""
         return self.params.N() * self.FloodBound(parties, flood_bits) / float(scale)
 
     def NoiseNorm(self, ct, skSet, msg):
@@ -1189,7 +1227,7 @@ class Refresher(mkrlwe.Refresher):
     def MaxMaskBits(self, parties, level, scale, max_abs_slot=1.0):
         """mkrlwe.Refresher.MaxMaskBits for ciphertexts at `level` whose slots are at most max_abs_slot in modulus: msg_bits =
         ceil(log2(scale * max_abs_slot)) + 1 -- a coefficient of the embedding is at most max|z| * scale in magnitude, and one more bit is
-        for the noise."""
+        for the noise.  This holds for sparse messages too: a coefficient of the embedding of the ring of degree 2n is at most max|z| as well."""
         q = 1
         for m in self.params.Q[: level + 1]:
             q *= int(m)
@@ -1199,7 +1237,8 @@ class Refresher(mkrlwe.Refresher):
     def RefreshSlotBound(self, parties, scale, sigma=3.2):
         """how far a refresh moves a slot, at most: N * parties * (2N + 1) * floor(6 sigma) / scale.  Each party's fresh encryption adds
         |u e_pk + e0 + e1 s| <= (2N + 1) floor(6 sigma) per coefficient (u and s ternary, the table truncated at floor(6 sigma)); a slot moves
-        by at most N times the coefficient error over the scale."""
+        by at most N times the coefficient error over the scale.  It remains an upper bound for sparse messages: a sparse slot is the mean of
+        replicas that each meet it."""
         N = self.params.N()
         return N * int(parties) * (2 * N + 1) * int(6 * float(sigma)) / float(scale)
 
@@ -1217,7 +1256,7 @@ class PublicKeySwitcher(mkrlwe.PublicKeySwitcher):
 
     def SwitchSlotBound(self, parties, flood_bits, scale, bound=19):
         """how far a switch moves a slot, at most: N * NoiseBound(parties, flood_bits, N, bound) / scale (a slot is a sum of N coefficients times
-        unit-modulus roots)"""
+        unit-modulus roots).  It remains an upper bound for sparse messages: a sparse slot is the mean of replicas that each meet it."""
         N = self.params.N()
         return N * self.NoiseBound(parties, flood_bits, N, bound) / float(scale)
 

@@ -1,5 +1,6 @@
 """Wall time of the message layer with the CKKS encoder on the host and on the device: Decrypt to slots of one PN15QP880
-top-level ciphertext over 4 parties, and encode + encrypt of the 16 plaintexts of the cnn scenario (PN14QP433).  3 warm-ups, median of 7
+top-level ciphertext over 4 parties, the decode of one PN15QP880 plaintext with sparse packing (logSlots 14 = full, 10, 6), and encode + encrypt
+of the 16 plaintexts of the cnn scenario (PN14QP433).  3 warm-ups, median of 7
 (min .. max), every leg ends in a device synchronise.  Needs a GPU:  python tools/ckks_encoder_timing.py"""
 import os, sys, time, types
 import numpy as np
@@ -44,6 +45,15 @@ print("decrypt PN15QP880 4 parties: |host - sum| %.3g |dev - sum| %.3g" % (np.ab
 print("  host decoder  ms median %.3f (min %.3f max %.3f)" % med(lambda: dh.Decrypt(ct, skSet), params))
 print("  device decoder ms median %.3f (min %.3f max %.3f)" % med(lambda: dd.Decrypt(ct, skSet), params))
 print("  mkhe_decrypt alone ms median %.3f (min %.3f max %.3f)" % med(lambda: mkrlwe.Decryptor.Decrypt(dd, ct, skSet), params))
+# leg 3: mkhe_ckks_decode_sparse of one top-level plaintext (uniform residues) on device buffers, by slot count; logSlots 14 is full packing
+from mkhe_kklss_amd._abi import check, lib
+L, N = len(p["Q"]), 1 << p["logN"]
+pt = mkrlwe.DeviceLimbs(params, 1, L).upload(H.uniform_poly(rng, p["Q"], N)[None])
+out = mkrlwe.DeviceLimbs(params, 1, 1)
+print("decode of one PN15QP880 plaintext, %d limbs (the call alone, buffers on the device):" % L)
+for ls in (14, 10, 6):
+    f = lambda ls=ls: check(lib().mkhe_ckks_decode_sparse(params.ctx, L, ls, 1, pt.devptr(), p["scale"], out.devptr()))
+    print("  logSlots %2d ms median %.3f (min %.3f max %.3f)" % ((ls,) + med(f, params)))
 params.close()
 # leg 2
 p = __import__("harness_cnn").PN14QP433
