@@ -748,6 +748,63 @@ int  mkhe_pcks_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const i
  * cannot check which -- with the limbs of the input.  Every limb of both polynomials of out is written.  One streaming launch; count > 16 or
  * nshares > 16 stages pointer tables, which synchronises.  nshares = 0 on ciphertexts without parties gives (c_0 reduced, 0). */
 int  mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, mkhe_ct* const* out);
+/* ---- threshold secret keys: t-of-n Shamir shares, additive keys, share fold (eprint 2022/780) -----------------------------------------------
+ * Every share call above needs the party's secret key, so one party that is offline or has lost its key blocks the decryption, refresh or hand-over
+ * of every ciphertext it contributed to.  The answer of multiparty RLWE is t-out-of-n thresholdisation (lattigo's drlwe.Thresholdizer / Combiner):
+ * a party Shamir-shares its key among n holders; any t of them turn their Shamir share into an ADDITIVE share for that active set; and because every
+ * share call here is linear in the key, those t holders run the existing share calls on their additive keys and their outputs add up to the absent
+ * party's share.  No reference counterpart; the definitions are this project's own.
+ *
+ * Notation.  R = nQ + nP is the number of rows of a SecretKey buffer uint64[R][N] (NTT domain, Montgomery form, as mkhe_keygen_secret writes it);
+ * m_j is the modulus of row j: the Q primes, then the P primes.  S[j][i] is the stored word of the secret, with no conversion: Shamir sharing is
+ * linear over Z_{m_j}, so it is applied to the stored words directly.  A share is therefore itself a buffer of SecretKey shape in the same
+ * representation, and ANY call that takes dev_sk accepts a share or an additive key.
+ *
+ * Kind 7 of the keystream: uniform mod m_j over all R rows, under a SECRET (key, nonce).  Coefficient polynomial k (1 <= k <= t - 1), row j < R, owns
+ * the streams 2 ((k-1) R + j) (lo) and 2 ((k-1) R + j) + 1 (hi).  The block and word rule is that of kinds 0-6 (coefficient i takes block i / 8, words
+ * 2 (i % 8) and 2 (i % 8) + 1); with r = hi 2^64 + lo,
+ *     c_k[j][i] = (r m_j) >> 128:
+ * the formula of kind 6, indexed over R rows instead of nQ.
+ *
+ * Shares.  The holders have public points x_0 .. x_(n-1), each a uint32, pairwise distinct, at least 1 and smaller than every m_j of the context
+ * (refused otherwise): every x_a - x_p is then invertible mod every m_j.
+ *     share_p[j][i] = (S[j][i] + sum_{k=1}^{t-1} c_k[j][i] x_p^k) mod m_j                          canonical
+ * Fewer than t shares say nothing about S; the t shares of an active set together ARE the key.
+ *
+ * Additive key, for an active set A of at least t holders with p in A, given as its points (A may be larger than t: the interpolation still holds):
+ *     lambda_p[j]  = prod_{a in A, a != p} x_a (x_a - x_p)^-1  mod m_j
+ *     add_p[j][i]  = share_p[j][i] lambda_p[j]  mod m_j                                            canonical
+ * so that sum_{p in A} add_p = S mod m_j, word for word.  An additive key is used exactly like a key -- in particular a share made from it must be
+ * FLOODED exactly like one made from a key, and a party covered by t holders contributes t floods: where a bound counts k parties, count k - 1 + t.
+ *
+ * Fold.  dst[b][j][i] = sum_{s < nsrc} src_s[b][j][i] mod m_j, canonical, for buffers uint64[count][limbs][N]: the outputs that the t holders'
+ * share calls wrote add up to the share of the absent party.  mkhe_decrypt_share: fold the buffers (limbs = level + 1).  mkhe_pcks_share: fold with
+ * count * 2 items.  mkhe_refresh_share / mkhe_bfv_refresh_share: fold the share buffers and add the holders' re-encryptions with mkhe_ct_add; the
+ * merge then runs unchanged.  With limbs = R the fold adds SecretKey buffers: the additive keys of an active set give S back (tests, key recovery).
+ *
+ * Rules: those of the seeded encryption and of distributed decryption.  Messages start with the function's name; a refused call has enqueued
+ * nothing and leaves the context usable; all three are refused on a context with mkhe_ctx_set_owned; CKKS, mkrlwe and BFV contexts alike (on a BFV
+ * context the rows are those of the Q / P primes, as for the secret key); raw buffers are 16-byte aligned. */
+/* dev_out[p] = uint64[R][N] <- share_p, p < nshares, of the secret at dev_sk.  1 <= threshold <= nshares <= 32.  threshold = 1 reads no stream and
+ * writes S to every output (TESTS ONLY: every holder then has the key).  ONE launch: points and output pointers travel in the kernel arguments,
+ * nothing is staged and the call does not synchronise with the host; the c_k are formed in registers and never exist in memory.  The key travels in
+ * the kernel arguments only and its host copy there is overwritten behind the launch; it never appears in a message.  A (key, nonce) pair serves
+ * ONE call.  Refused: between mkhe_capture_begin and mkhe_capture_end (a replay would repeat the keystream); a NULL key, even at threshold 1; NULL,
+ * misaligned or duplicate outputs, an output equal to dev_sk; bad points (see above); threshold or nshares out of range.  The shares are key
+ * material: the caller guards (and wipes) its buffers. */
+int  mkhe_threshold_gen_shares(mkhe_ctx* ctx, const void* dev_sk, int threshold, int nshares, const uint32_t* points, const uint32_t key[8],
+                               uint64_t nonce, void* const* dev_out /* nshares buffers uint64[R][N] */);
+/* dev_out = uint64[R][N] <- add_p for the holder at `point` and the active set active_points[0 .. nactive); dev_out may equal dev_share.  The
+ * threshold is not an argument: the caller's protocol knows it, and fewer than t active holders simply do not add up to S.  1 <= nactive <= 32; the
+ * points valid and distinct as above; `point` occurs in active_points exactly once.  The lambda_p[j] are computed on the host and
+ * travel in Montgomery form in the kernel arguments: one streaming launch, nothing staged, so the call may be captured. */
+int  mkhe_threshold_additive_key(mkhe_ctx* ctx, const void* dev_share, uint32_t point, int nactive, const uint32_t* active_points,
+                                 void* dev_out /* uint64[R][N]; may equal dev_share */);
+/* dev_dst = uint64[count][limbs][N] <- the fold of the nsrc buffers dev_src[s] of that shape.  limbs in 1 .. nQ (row j mod q_j: what the shares of
+ * every protocol here look like) or limbs == R (SecretKey rows).  1 <= nsrc <= 32, 1 <= count <= 65535.  All inputs are canonical.  dev_dst may
+ * equal one dev_src[s] exactly (partial overlap is refused).  One streaming launch; nsrc > 16 stages a pointer table, which synchronises (and is
+ * refused inside a capture). */
+int  mkhe_limbs_sum(mkhe_ctx* ctx, int count, int limbs, int nsrc, const void* const* dev_src, void* dev_dst /* may equal one dev_src[s] exactly */);
 /* ---- noise measurement: the exact centred max norm of a phase (no reference counterpart) --------------------------------------------
  * Every share call above takes a width that the caller must put above the noise of the ciphertext.  This call measures that noise on the device,
  * from a phase: what mkhe_decrypt writes for whoever holds every key, or what mkhe_decrypt_merge writes for parties that hold only their own

@@ -618,6 +618,8 @@ class Decryptor {
         Decrypt(ct, skSet, pt.d);
         return NoiseNormBatch(ct.Level() + 1, 1, pt.d, dev_ref, 0, kind)[0];
     }
+    // what a merge of `parties` shares with floodBits bits adds to a coefficient, at most: parties * 2^(floodBits - 1) (0 bits: 0)
+    static long double FloodBound(int parties, int floodBits) { return floodBits == 0 ? 0.0L : (long double)parties * std::ldexp(1.0L, floodBits - 1); }
     // The shares of the party of sk for the ciphertexts cts (one level; their id sets may differ) as one engine call.  floodBits = 1 .. 62: the width of
     // the flooding noise, drawn on the device under one nonce of `sampler`; no default -- it must exceed the noise of the ciphertext by the statistical
     // security parameter, which the engine cannot know.  floodBits = 0 (sampler may be null) is for tests only: such a share reveals sk.
@@ -654,6 +656,21 @@ class Decryptor {
         check(mkhe_decrypt_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), dev_pt_out));
     }
     void MergeShares(const Ciphertext& ct, const std::vector<const DecryptionShare*>& shares, void* dev_pt_out) { MergeSharesBatch({&ct}, shares, dev_pt_out); }
+    // The shares that the t holders of ONE absent party's key made with their additive keys (Combiner::AdditiveKey; same id, level and count) -> one
+    // DecryptionShare of that id, their sum (mkhe_limbs_sum); MergeShares* then works unchanged.  A party covered by t holders contributes t floods:
+    // FloodBound / FloodSlotBound are called with k - 1 + t in the place of k.
+    std::shared_ptr<DecryptionShare> FoldShares(const std::vector<const DecryptionShare*>& shares) {
+        if (shares.empty()) throw Error("Cannot FoldShares: no share");
+        std::vector<const void*> src;
+        for (auto* sh : shares) {
+            if (sh->ID != shares[0]->ID) throw Error("Cannot FoldShares: shares of different parties (a fold is over the holders of ONE party's key)");
+            if (sh->Level != shares[0]->Level || sh->Count != shares[0]->Count) throw Error("Cannot FoldShares: shares at different levels or for different batch sizes");
+            src.push_back(sh->Value.d);
+        }
+        auto out = std::make_shared<DecryptionShare>(params, shares[0]->ID, shares[0]->Level, shares[0]->Count);
+        check(mkhe_limbs_sum(params.ctx, shares[0]->Count, shares[0]->Level + 1, (int)src.size(), src.data(), out->Value.d));
+        return out;
+    }
     // decryptor.go:26-43; the Go version works in place and deletes ct.Value[sk.ID]: here the result is a new ciphertext over the remaining ids.
     // WARNING: the result REVEALS sk to anyone who sees it (c_0 and c_id are public, c_id is invertible with overwhelming probability): it is for a
     // process that holds every key, as in the reference's tests.  Between parties use ShareNew / MergeShares.
@@ -817,6 +834,69 @@ class PublicKeySwitcher {
         for (auto& o : outs) oh.push_back(o->h);
         check(mkhe_pcks_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), oh.data()));
     }
+};
+
+// ---- threshold secret keys (include/mkhe.h, "threshold secret keys")
+// The Shamir share of the secret key of party ID that Holder keeps, at the public point Point, under a t-of-n sharing with t = Threshold:
+// uint64[nQ+nP][N] on the device, in the representation of SecretKey::Value.  Fewer than t shares say nothing about the key, but the t shares of an
+// active set together ARE the key: a share is key material and travels only to its holder, over a private channel (Value.download / upload).
+struct SecretKeyShare {
+    SecretKeyShare(Parameters& p, std::string id, std::string holder, uint32_t point, int threshold)
+        : ID(std::move(id)), Holder(std::move(holder)), Point(point), Threshold(threshold), Value(p, (size_t)(p.QCount() + p.PCount()) * p.N()) {}
+    std::string ID, Holder;
+    uint32_t Point;
+    int Threshold;
+    DeviceWords Value;
+};
+// The party side of t-out-of-n thresholdisation (lattigo's drlwe.Thresholdizer): Shamir-shares a secret key among n holders as ONE engine call
+// (mkhe_threshold_gen_shares).  The coefficient polynomials are drawn on the device under one nonce of `sampler` and exist in registers only.
+// threshold = 1 hands every holder the key itself (tests only).
+class Thresholdizer {
+  public:
+    explicit Thresholdizer(Parameters& p) : params(p) {}
+    std::map<std::string, std::shared_ptr<SecretKeyShare>> GenShares(const SecretKey& sk, int threshold, const std::map<std::string, uint32_t>& points,
+                                                                      DeviceSampler& sampler) {
+        std::map<std::string, std::shared_ptr<SecretKeyShare>> out;
+        std::vector<uint32_t> xs;
+        std::vector<void*> bufs;
+        for (auto& hp : points) {
+            auto sh = std::make_shared<SecretKeyShare>(params, sk.ID, hp.first, hp.second, threshold);
+            xs.push_back(hp.second);
+            bufs.push_back(sh->Value.d);
+            out[hp.first] = sh;
+        }
+        check(mkhe_threshold_gen_shares(params.ctx, sk.Value.d, threshold, (int)xs.size(), xs.data(), sampler.Key(), sampler.NextNonce(), bufs.data()));
+        return out;
+    }
+    Parameters& params;
+};
+// The holder side (lattigo's drlwe.Combiner): from a Shamir share to the additive key for one active set.
+class Combiner {
+  public:
+    explicit Combiner(Parameters& p) : params(p) {}
+    // share times its Lagrange coefficient for the active set activePoints (the points of at least t holders, share.Point among them) -> a SecretKey
+    // with ID = share.ID (mkhe_threshold_additive_key).  The additive keys of the active set sum to the key of party share.ID, so Decryptor, Refresher
+    // and PublicKeySwitcher ShareBatch take it unchanged and the holders' outputs add up to that party's share (Decryptor::FoldShares).  It is key
+    // material of the same rank as a key, and a share made from it must be FLOODED exactly like one made from a key.
+    std::shared_ptr<SecretKey> AdditiveKey(const SecretKeyShare& share, const std::vector<uint32_t>& activePoints) {
+        auto out = std::make_shared<SecretKey>(params, share.ID);
+        check(mkhe_threshold_additive_key(params.ctx, share.Value.d, share.Point, (int)activePoints.size(), activePoints.data(), out->Value.d));
+        return out;
+    }
+    // the sum of the additive keys of ONE active set (mkhe_limbs_sum over the nQ+nP rows) -> the SecretKey of their party.  For tests and key
+    // recovery: in the protocols the additive keys never meet.
+    std::shared_ptr<SecretKey> Reconstruct(const std::vector<const SecretKey*>& keys) {
+        if (keys.empty()) throw Error("Cannot Reconstruct: no key");
+        std::vector<const void*> src;
+        for (auto* k : keys) {
+            if (k->ID != keys[0]->ID) throw Error("Cannot Reconstruct: additive keys of different parties");
+            src.push_back(k->Value.d);
+        }
+        auto out = std::make_shared<SecretKey>(params, keys[0]->ID);
+        check(mkhe_limbs_sum(params.ctx, 1, params.QCount() + params.PCount(), (int)src.size(), src.data(), out->Value.d));
+        return out;
+    }
+    Parameters& params;
 };
 }  // namespace mkrlwe
 

@@ -131,6 +131,9 @@ SIGNATURES = {
     "mkhe_bfv_refresh_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp, vpp]),
     "mkhe_pcks_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, vp, u32p, C.c_uint64, C.c_int, u64p, C.c_int, vp]),
     "mkhe_pcks_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp]),
+    "mkhe_threshold_gen_shares": (C.c_int, [vp, vp, C.c_int, C.c_int, u32p, u32p, C.c_uint64, vpp]),
+    "mkhe_threshold_additive_key": (C.c_int, [vp, vp, C.c_uint32, C.c_int, u32p, vp]),
+    "mkhe_limbs_sum": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vpp, vp]),
     "mkhe_noise_norm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_long, vp]),
     "mkhe_ckks_embed": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_project": (C.c_int, [vp, C.c_int, vp, vp]),

@@ -1142,6 +1142,88 @@ int mkhe_pcks_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nsha
         c->pcks_merge(i, sh, d.data());
     })
 }
+// threshold secret keys, under the rules of the protocol family.  The sharing draws from a SECRET keystream and is refused inside a capture; the
+// additive key and the fold allocate nothing and may be captured as long as they stage no table (the fold: at most 16 sources).  points_ok: the
+// points of a sharing or of an active set are 1 .. 32, pairwise distinct, at least 1 and below every modulus of the rows.
+static void points_ok(const Context* c, const char* what, const char* name, int n, const uint32_t* x) {
+    const std::string w(what);
+    if (n < 1 || n > THR_MAX) throw Error(w + ": " + name + " must be 1 .. 32");
+    if (!x) throw Error(w + ": null points");
+    for (int p = 0; p < n; ++p) {
+        if (x[p] < 1) throw Error(w + ": every point must be at least 1 (0 is where the secret sits)");
+        for (int j = 0; j < c->mtot; ++j)
+            if ((u64)x[p] >= c->moduli[j]) throw Error(w + ": every point must be smaller than every modulus of the context");
+        for (int k = 0; k < p; ++k) if (x[k] == x[p]) throw Error(w + ": the points must be pairwise distinct");
+    }
+}
+int mkhe_threshold_gen_shares(mkhe_ctx* ctx, const void* dev_sk, int threshold, int nshares, const uint32_t* points, const uint32_t key[8],
+                              uint64_t nonce, void* const* dev_out) {
+    MKHE_TRY({
+        const char* what = "mkhe_threshold_gen_shares";
+        const std::string w(what);
+        Context* c = enter(ctx, what);
+        if (!key) throw Error(w + ": null key");                                // (threshold = 1 reads no stream: the rule is that of mkhe_pcks_share)
+        if (!dev_sk || !dev_out) throw Error(w + ": null argument");
+        points_ok(c, what, "nshares", nshares, points);
+        if (threshold < 1 || threshold > nshares) throw Error(w + ": threshold must be 1 .. nshares");
+        need_aligned(dev_sk, what);
+        std::vector<u64*> o(nshares);
+        for (int p = 0; p < nshares; ++p) {
+            if (!dev_out[p]) throw Error(w + ": null output in the per-holder list");
+            need_aligned(dev_out[p], what);
+            if (dev_out[p] == dev_sk) throw Error(w + ": an output must not be the secret key's buffer");
+            for (int k = 0; k < p; ++k) if (dev_out[k] == dev_out[p]) throw Error(w + ": the outputs must be distinct");
+            o[p] = (u64*)dev_out[p];
+        }
+        unmasked(c, what);
+        not_captured(c, what, REPLAYS);
+        commit(c);
+        c->threshold_gen_shares((const u64*)dev_sk, threshold, nshares, points, key, nonce, o.data());
+    })
+}
+int mkhe_threshold_additive_key(mkhe_ctx* ctx, const void* dev_share, uint32_t point, int nactive, const uint32_t* active_points, void* dev_out) {
+    MKHE_TRY({
+        const char* what = "mkhe_threshold_additive_key";
+        const std::string w(what);
+        Context* c = enter(ctx, what);
+        if (!dev_share || !dev_out) throw Error(w + ": null argument");
+        points_ok(c, what, "nactive", nactive, active_points);
+        int found = 0;
+        for (int i = 0; i < nactive; ++i) found += active_points[i] == point ? 1 : 0;
+        if (found != 1) throw Error(w + ": point must occur in active_points exactly once");
+        need_aligned(dev_share, what); need_aligned(dev_out, what);
+        static_assert(THR_MAX_ROWS >= NTT_MAX_SLOTS, "the Lagrange coefficients of every row of a context travel in the kernel arguments");
+        unmasked(c, what);
+        commit(c);
+        c->threshold_additive_key((const u64*)dev_share, point, nactive, active_points, (u64*)dev_out);
+    })
+}
+int mkhe_limbs_sum(mkhe_ctx* ctx, int count, int limbs, int nsrc, const void* const* dev_src, void* dev_dst) {
+    MKHE_TRY({
+        const char* what = "mkhe_limbs_sum";
+        const std::string w(what);
+        Context* c = enter(ctx, what);
+        count_ok(what, count);
+        if (!(limbs >= 1 && limbs <= c->nq) && limbs != c->mtot) throw Error(w + ": limbs must be 1 .. nQ, or nQ + nP (the rows of a secret key)");
+        if (nsrc < 1 || nsrc > THR_MAX) throw Error(w + ": nsrc must be 1 .. 32");
+        if (!dev_src || !dev_dst) throw Error(w + ": null argument");
+        need_aligned(dev_dst, what);
+        std::vector<const u64*> src(nsrc);
+        const size_t bytes = (size_t)count * limbs * c->N * sizeof(u64);
+        for (int s = 0; s < nsrc; ++s) {
+            if (!dev_src[s]) throw Error(w + ": null source in the list");
+            need_aligned(dev_src[s], what);
+            const uintptr_t a = (uintptr_t)dev_src[s];
+            const uintptr_t d = (uintptr_t)dev_dst;
+            if (a != d && a < d + bytes && d < a + bytes) throw Error(w + ": dst may equal a source exactly, not overlap it");
+            src[s] = (const u64*)dev_src[s];
+        }
+        unmasked(c, what);
+        if (nsrc > ED_INLINE) not_captured(c, what, "with more than 16 sources (the pointer table is staged)");
+        commit(c);
+        c->limbs_sum(count, limbs, src, (u64*)dev_dst);
+    })
+}
 
 // ---- CKKS encoder (ckks_encode.hip)
 // the argument checks every call of the two encoders shares (the BFV batch encoder is bfv_encode.hip); their null context is need()'s

@@ -513,6 +513,55 @@ void Context::encrypt_sk(int level, int count, const u64* sk, const u64* pt, boo
     MKHE_HIP(hipGetLastError());
 }
 
+// ---- threshold secret keys (include/mkhe.h; threshold_kernels.h).  Three single launches.  Shares and additive keys are key material of the
+// caller's, written to the caller's buffers only: the engine has no scratch to wipe here, and the key of kind 7 is overwritten behind its launch.
+void Context::threshold_gen_shares(const u64* sk, int t, int n, const u32* points, const u32* key, u64 nonce, u64* const* outs) {
+    need_unmasked("mkhe_threshold_gen_shares");
+    ThresholdShareArgs a{};
+    stream_fill(a, key, nonce, t > 1);
+    a.t = t; a.n = n;
+    for (int p = 0; p < n; ++p) { a.x[p] = points[p]; a.out[p] = outs[p]; }
+    {
+        // S once per group of points, every share once; 2 (t - 1) ChaCha20 blocks per thread and group
+        const double groups = (double)((n + THR_G - 1) / THR_G);
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * mtot * (groups + n));
+        launch_threshold_share(a, sk, d_mods, mtot, N, s_);
+    }
+    wipe(a);
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::threshold_additive_key(const u64* share, u32 point, int nactive, const u32* active, u64* out) {
+    need_unmasked("mkhe_threshold_additive_key");
+    ThresholdScaleArgs a{};
+    for (int j = 0; j < mtot; ++j) {
+        const u64 m = moduli[j];
+        u64 num = 1, den = 1;
+        for (int i = 0; i < nactive; ++i) {
+            if (active[i] == point) continue;
+            num = mulmod(num, active[i], m);
+            den = mulmod(den, (active[i] + m - point) % m, m);
+        }
+        a.lam[j] = to_mont(mulmod(num, powmod(den, m - 2, m), m), m);        // m is prime and den a unit: the points are distinct and below m
+    }
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * N * mtot);
+        launch_threshold_scale(a, out, share, d_mods, mtot, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
+void Context::limbs_sum(int count, int limbs, const std::vector<const u64*>& src, u64* dst) {
+    need_unmasked("mkhe_limbs_sum");
+    if (src.size() > (size_t)ED_INLINE) scratch(ed_tab_, src.size());
+    const EdTable st = ed_table(src, 0);                                    // more than ED_INLINE sources: staged, which synchronises
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * limbs * count * (1.0 + (double)src.size()));
+        launch_limbs_sum(count, limbs, (int)src.size(), st, dst, d_mods, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
 // ---- noise measurement (include/mkhe.h; noise_kernels.h).  rf_dig_ holds the digit scratch [count][limbs][N] and behind it the candidates of the
 // workgroups [count][blocks][limbs + 1].  Both are the noise of the ciphertext, which depends on the keys: wiped behind the second launch, as
 // decrypt_share wipes its unflooded product.  The result itself is the caller's.

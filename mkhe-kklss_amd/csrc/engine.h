@@ -24,6 +24,7 @@
 #include "bfv_refresh_kernels.h"
 #include "pcks_kernels.h"
 #include "skenc_kernels.h"
+#include "threshold_kernels.h"
 #include "noise_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
@@ -343,6 +344,14 @@ class Context {
     void sample_uniform(int limbs, int count, const u32* key, u64 nonce, u64* dev_out);
     // polynomial 1 of outs[b] [2][limbs][N] <- the rows (b, j), j < limbs; polynomial 0 is not touched
     void ct_expand_seeded(int count, int limbs, const u32* key, u64 nonce, u64* const* outs);
+    // threshold secret keys (include/mkhe.h; threshold_kernels.h).  outs[p] [mtot][N] <- the Shamir share of sk [mtot][N] at points[p], p < n, the
+    // coefficient polynomials c_1 .. c_(t-1) = kind 7 under the SECRET (key, nonce): one launch, nothing staged, the c_k in registers only.
+    void threshold_gen_shares(const u64* sk, int t, int n, const u32* points, const u32* key, u64 nonce, u64* const* outs);
+    // out [mtot][N] <- share * lambda_j, lambda_j = prod_{a != point} x_a (x_a - point)^-1 mod m_j over the active points (host_modarith.h), which
+    // travel as MForm values in the kernel arguments: one streaming launch, nothing staged.  out may be share.
+    void threshold_additive_key(const u64* share, u32 point, int nactive, const u32* active, u64* out);
+    // dst [count][limbs][N] <- the sum of the sources mod mods[j], canonical; more than ED_INLINE sources stage their table, which synchronises
+    void limbs_sum(int count, int limbs, const std::vector<const u64*>& src, u64* dst);
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).

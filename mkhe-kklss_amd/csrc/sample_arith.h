@@ -25,6 +25,23 @@ __device__ __forceinline__ u64 small_q(i32 e, u64 q) { return e < 0 ? q - (u64)(
 // a sample given as |e| mod q (canonical) and its sign: e mod q, by a select
 __device__ __forceinline__ u64 signed_mod_q(u64 mag_mod_q, bool neg, u64 q) { return neg ? csub(q - mag_mod_q, q) : mag_mod_q; }
 
+// kinds 6 and 7 of the keystream: v[i] = ((hi 2^64 + lo) q) >> 128 = (hi q + ((lo q) >> 64)) >> 64 with lo / hi the 64-bit values of coefficient
+// 8 blk + i of the streams s0 and s0 + 1 of k: one full 64 x 64 product, the high word of a second and a carry.  Below q, since r < 2^128.
+__device__ __forceinline__ void uniform_mod_q8(const StreamKey& k, u32 blk, u32 s0, u64 q, u64 (&v)[8]) {
+    u64 lo[8], hi[8];
+    chacha_block8(k, blk, s0, lo);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) lo[i] = mulhi64(lo[i], q);                  // only (lo q) >> 64 is needed
+    chacha_block8(k, blk, s0 + 1, hi);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        u64 ph, pl;
+        mul64x64(hi[i], q, ph, pl);
+        const u64 s = pl + lo[i];
+        v[i] = ph + (s < pl ? 1 : 0);
+    }
+}
+
 // (c0 + sum_{i < nshares} sh[i][at]) mod q, canonical, for any c0 below 3 q and canonical shares: one conditional subtraction per addend.
 // One coefficient at word `at`, or the pair of coefficients at pair `at` (16-byte loads).
 __device__ __forceinline__ u64 sum_shares(u64 c0, const EdTable& sh, int nshares, long at, u64 q) {

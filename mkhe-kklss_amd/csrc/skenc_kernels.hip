@@ -13,18 +13,8 @@ __global__ void __launch_bounds__(BLK_THREADS) uniform_sample_kernel(UniformArgs
     const int j = blockIdx.y, b = blockIdx.z;
     const u64 q = mods[j].q;
     const u32 s0 = 2u * ((u32)b * (u32)nq + (u32)j);
-    u64 lo[8], hi[8], v[8];
-    chacha_block8(a, blk, s0, lo);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) lo[i] = mulhi64(lo[i], q);                  // only (lo q) >> 64 is needed
-    chacha_block8(a, blk, s0 + 1, hi);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        u64 ph, pl;
-        mul64x64(hi[i], q, ph, pl);
-        const u64 s = pl + lo[i];
-        v[i] = ph + (s < pl ? 1 : 0);                                       // below q: (r q) >> 128 with r < 2^128
-    }
+    u64 v[8];
+    uniform_mod_q8(a, blk, s0, q, v);                                       // below q: (r q) >> 128 with r < 2^128
     st8(const_cast<u64*>(ed_entry(out, b)) + poly_off + (long)j * N, 4 * (long)blk, v);
 }
 void launch_uniform_sample(const UniformArgs& a, int count, const EdTable& out, long poly_off, const Mod* mods, int limbs, int nq, int N, hipStream_t st) {

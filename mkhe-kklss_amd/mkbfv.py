@@ -1349,3 +1349,11 @@ class PublicKeySwitcher(mkrlwe.PublicKeySwitcher):
 
 def NewPublicKeySwitcher(params):
     return PublicKeySwitcher(params)
+
+
+# ---- threshold secret keys (include/mkhe.h, "threshold secret keys"): keys are the ring's, so the classes are mkrlwe's
+SecretKeyShare = mkrlwe.SecretKeyShare
+Thresholdizer = mkrlwe.Thresholdizer
+Combiner = mkrlwe.Combiner
+NewThresholdizer = mkrlwe.NewThresholdizer
+NewCombiner = mkrlwe.NewCombiner

@@ -724,6 +724,10 @@ class DeviceSampler:
         """(e_key, e_nonce, cdt, ncdt) for ONE mkhe_encrypt_sk_seeded call: the same counter as the other calls"""
         return self._key, self._next_nonce(), self._cdt, len(self.cdt)
 
+    def threshold_args(self):
+        """(key, nonce) for ONE mkhe_threshold_gen_shares call: the same counter as the other calls"""
+        return self._key, self._next_nonce()
+
     def refresh_args(self):
         """(key, nonce_mask, nonce_enc) for ONE mkhe_refresh_share call: two values of the same counter, taken under the lock"""
         with self._lock:
@@ -1290,6 +1294,27 @@ class Decryptor:
         """MergeSharesBatch of one ciphertext -> DeviceLimbs [1][level+1][N]"""
         return self.MergeSharesBatch([ct], shares)
 
+    def FoldShares(self, shares):
+        """The DecryptionShares that the t holders of ONE absent party's key made with their additive keys (Combiner.AdditiveKey; same id, level
+        and count) -> one DecryptionShare of that id, their sum (mkhe_limbs_sum): what the party itself would have published, with t floods in
+        the place of one.  MergeShares* then works unchanged.  A party covered by t holders contributes t floods: call FloodBound /
+        FloodSlotBound with k - 1 + t in the place of k."""
+        shares = list(shares)
+        if not shares:
+            raise MkheError("Cannot FoldShares: no share")
+        first = shares[0]
+        for sh in shares:
+            if sh.ID != first.ID:
+                raise MkheError("Cannot FoldShares: shares of the parties %r and %r (a fold is over the holders of ONE party's key)" % (first.ID, sh.ID))
+            if sh.Level() != first.Level():
+                raise MkheError("Cannot FoldShares: shares at the levels %d and %d" % (first.Level(), sh.Level()))
+            if sh.count != first.count:
+                raise MkheError("Cannot FoldShares: shares for %d and %d ciphertexts" % (first.count, sh.count))
+        out = DecryptionShare(self.params, first.ID, first.Level(), first.count)
+        check(lib().mkhe_limbs_sum(self.params.ctx, first.count, first.Level() + 1, len(shares),
+                                   handle_array([sh.Value.devptr() for sh in shares]), out.Value.devptr()))
+        return out
+
     def PartialDecrypt(self, ct, sk):
         """decryptor.go:26-43.  The Go version works in place and deletes ct.Value[sk.ID]; a device ciphertext keeps its shape, so the
         result is a NEW ciphertext over the remaining ids and `ct` is left as it was (the deviation Rescale already makes).
@@ -1587,3 +1612,95 @@ class PublicKeySwitcher:
 
 def NewPublicKeySwitcher(params):
     return PublicKeySwitcher(params)
+
+
+# ---- threshold secret keys (include/mkhe.h, "threshold secret keys")
+def _points(points, who):
+    """holder points -> (uint32 * n); the engine checks them against the moduli"""
+    xs = [int(x) for x in points]
+    if not 1 <= len(xs) <= 32 or any(not 1 <= x < (1 << 32) for x in xs) or len(set(xs)) != len(xs):
+        raise MkheError("%s: 1 .. 32 pairwise distinct points, each 1 .. 2^32 - 1" % who)
+    return (C.c_uint32 * len(xs))(*xs)
+
+
+class SecretKeyShare:
+    """The Shamir share of the secret key of party `id` that `holder` keeps, at the public point `point`, under a t-of-n sharing with t =
+    `threshold`: Value = uint64 [1][nQ+nP][N] on the device, in the representation of SecretKey.Value.  Fewer than t shares say nothing about the
+    key, but the t shares of an active set together ARE the key: a share is key material and travels only to its holder, over a private channel
+    (download() gives the host array, SecretKeyShare(params, id, holder, point, threshold).upload(host) takes it on the receiving side)."""
+
+    def __init__(self, params, id, holder, point, threshold):
+        self.ID, self.Holder, self.Point, self.Threshold = id, holder, int(point), int(threshold)
+        self.Value = DeviceLimbs(params, 1, params.QCount() + params.PCount())
+
+    def download(self):
+        return self.Value.download()
+
+    def upload(self, host):
+        self.Value.upload(host)
+        return self
+
+
+class Thresholdizer:
+    """The party side of t-out-of-n thresholdisation (lattigo's drlwe.Thresholdizer): Shamir-shares a secret key among n holders."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def GenShares(self, sk, threshold, points, sampler):
+        """{holder: SecretKeyShare} for points = {holder: x}, 1 <= threshold <= len(points) <= 32, as ONE engine call
+        (mkhe_threshold_gen_shares).  The coefficient polynomials are drawn on the device under one nonce of `sampler` (a DeviceSampler) and
+        exist in registers only.  threshold = 1 hands every holder the key itself (TESTS ONLY)."""
+        if not isinstance(sampler, DeviceSampler):
+            raise MkheError("Cannot GenShares: the coefficient polynomials are drawn on the device -- pass a DeviceSampler")
+        holders = list(points)
+        xs = _points([points[h] for h in holders], "Cannot GenShares")
+        if not isinstance(threshold, int) or not 1 <= threshold <= len(holders):
+            raise MkheError("Cannot GenShares: threshold must be an integer 1 .. %d" % len(holders))
+        out = {h: SecretKeyShare(self.params, sk.ID, h, points[h], threshold) for h in holders}
+        key, nonce = sampler.threshold_args()
+        check(lib().mkhe_threshold_gen_shares(self.params.ctx, sk.Value.devptr(), threshold, len(holders), xs, key, nonce,
+                                              handle_array([out[h].Value.devptr() for h in holders])))
+        return out
+
+
+class Combiner:
+    """The holder side (lattigo's drlwe.Combiner): from a Shamir share to the additive key for one active set."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def AdditiveKey(self, share, active_points):
+        """share (a SecretKeyShare) times its Lagrange coefficient for the active set `active_points` (the points of at least t holders, share.Point
+        among them; a dict {holder: x} or a list) -> a SecretKey with ID = share.ID, as ONE engine call (mkhe_threshold_additive_key).  The additive
+        keys of the active set sum to the key of party share.ID, so Decryptor.ShareBatch, Refresher.ShareBatch and PublicKeySwitcher.ShareBatch take
+        it unchanged and the holders' outputs add up to that party's share (Decryptor.FoldShares).  It is key material of the same rank as a key,
+        and a share made from it must be FLOODED exactly like one made from a key."""
+        xs = list(active_points.values()) if isinstance(active_points, dict) else list(active_points)
+        arr = _points(xs, "Cannot AdditiveKey")
+        if [int(x) for x in xs].count(share.Point) != 1:
+            raise MkheError("Cannot AdditiveKey: the point of the share must be one of the active points")
+        out = SecretKey(self.params, share.ID)
+        check(lib().mkhe_threshold_additive_key(self.params.ctx, share.Value.devptr(), share.Point, len(xs), arr, out.Value.devptr()))
+        return out
+
+    def Reconstruct(self, keys):
+        """the sum of the additive keys of ONE active set (mkhe_limbs_sum over the nQ+nP rows) -> the SecretKey of their party.  For tests and key
+        recovery: in the protocols the additive keys never meet."""
+        keys = list(keys)
+        if not keys:
+            raise MkheError("Cannot Reconstruct: no key")
+        if any(k.ID != keys[0].ID for k in keys):
+            raise MkheError("Cannot Reconstruct: additive keys of different parties")
+        out = SecretKey(self.params, keys[0].ID)
+        check(lib().mkhe_limbs_sum(self.params.ctx, 1, self.params.QCount() + self.params.PCount(), len(keys),
+                                   handle_array([k.Value.devptr() for k in keys]), out.Value.devptr()))
+        return out
+
+
+def NewThresholdizer(params):
+    return Thresholdizer(params)
+
+
+def NewCombiner(params):
+    return Combiner(params)
