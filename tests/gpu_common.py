@@ -6,6 +6,41 @@ import harness as H
 from oracle import oracle as O
 
 
+def pset_swk(pset, rng, beta=None):
+    """uniform residues, switching-key shaped uint64[beta][nQ+nP][N]"""
+    Q, P, N = pset["Q"], pset["P"], 1 << pset["logN"]
+    beta = len(Q) if beta is None else beta
+    out = np.empty((beta, len(Q) + len(P), N), dtype=np.uint64)
+    for j, q in enumerate(Q + P):
+        out[:, j] = rng.integers(0, q, (beta, N), dtype=np.uint64)
+    return out
+
+
+def pset_ct(pset, rng, n, limbs):
+    """uniform residues, ciphertext shaped uint64[1+n][limbs][N]"""
+    N = 1 << pset["logN"]
+    out = np.empty((1 + n, limbs, N), dtype=np.uint64)
+    for l in range(limbs):
+        out[:, l] = rng.integers(0, pset["Q"][l], (1 + n, N), dtype=np.uint64)
+    return out
+
+
+def launch_counts(ctx, fn):
+    """{kernel class name: launches} of what fn() runs on the context (mkhe_prof_enable / mkhe_prof_collect)"""
+    import ctypes as C
+    from mkhe_kklss_amd._abi import check, lib
+    L = lib()
+    ncls = L.mkhe_prof_nclass()
+    ms, cnt, byt = (C.c_double * ncls)(), (C.c_long * ncls)(), (C.c_double * ncls)()
+    check(L.mkhe_prof_enable(ctx, 1))
+    try:
+        fn()
+        check(L.mkhe_prof_collect(ctx, ms, cnt, byt))
+    finally:
+        check(L.mkhe_prof_enable(ctx, 0))
+    return {L.mkhe_prof_name(i).decode(): cnt[i] for i in range(ncls)}
+
+
 class Pair:
     """One parameter set instantiated on the oracle (ks) and on the device (params)."""
 

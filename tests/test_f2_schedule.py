@@ -83,6 +83,76 @@ def test_every_pass_exactly_once(parties, level):
         _check(parties, nb, nslots, w, grid)
 
 
+@pytest.mark.parametrize("parties", range(9, 17))
+def test_every_pass_exactly_once_nine_to_sixteen_parties(parties):
+    # the band in which out_0 has more members than one inverse job takes (VI_MAX = 4: parts <= 3), at EVERY level of PN15QP880 (14 Q + 2 P primes):
+    # the cut on the whole chip (256 and 304 workgroups, a quarter of one) and the engine's plan for those chips
+    for level in range(14):
+        nb, nslots = level + 1, level + 1 + 2
+        assert _max_parts(parties) == 3
+        for grid in (256, 304, 64, -256, -304):
+            _check(parties, nb, nslots, [100] * nslots, grid)
+        w = [100] * nslots
+        w[0] = 115
+        w[-1] = w[-2] = 105
+        _check(parties, nb, nslots, w, 256)
+        _check(parties, nb, nslots, w, -256)
+
+
+EXT_MAX_ITEMS, NTT_MAX_SLOTS = 64, 48      # csrc/poly_kernels.h, csrc/ntt_kernels.h
+
+
+def _tail_jobs(ids0, ids1, parts, members):
+    """The tail batch of a MulAndRelin whose F2 products arrive in `parts` parts, restated from csrc/engine_mulrelin.hip (mr_finish_tail: per party of
+    op0 the products with v_i -> out_0 and with u -> its own slot, then step E per party of op1 -> its slot; the tensor term rides on the first product
+    of every destination) and csrc/engine.hip (ext_plan_merge: the products of a destination in virtual items of `members`; ext_front: the summands of
+    a virtual item's inverse job = its members' parts + the tensor term).  Returns (summands per inverse job, highest c1 slot an item's parts name)."""
+    items = []                                          # (destination, parts)
+    for i in ids0:
+        items.append((0, parts))
+        items.append((1 + i, parts))
+    for j in ids1:
+        items.append((1 + j, 1))
+    jobs = []
+    for dst in dict.fromkeys(d for d, _ in items):      # destinations in the order of their first product
+        mem = [p for d, p in items if d == dst]
+        for k in range(0, len(mem), members):
+            jobs.append(sum(mem[k:k + members]) + (1 if k == 0 else 0))
+    n, nf2 = len(items), 2 * len(ids0)
+    return jobs, n + nf2 * (parts - 1)
+
+
+def test_inverse_job_summands_and_part_slots_for_every_party_count():
+    """For every (n0, n1 <= 32, level) of PN15QP880 whose tail the engine would run through ntt16_f2_kernel (n0 <= F2_MAX_P, the folded tensor term: 2 n0 + n1 <=
+    EXT_MAX_ITEMS, a plan on a 256- or 304-CU device): no inverse job adds more than VI_SUMS summands at its load (csrc/engine.hip ext_front throws
+    otherwise: a legal call would fail) and the c1 slot index packed into 8 bits of f2_parts[i] stays at or below 255 -- with equal id sets (every
+    party's slot holds its u product, its step-E product and the tensor term) and with disjoint ones."""
+    shapes = 0
+    for n0 in range(1, 17):
+        for level in range(14):
+            members = min(VI_MAX, 16 // 2, (NTT_MAX_SLOTS - (level + 1)) // 2)          # Context::ext_merge_members, two special primes
+            for grid in (-256, -304):
+                nwg, parts, _ = _probe(n0, level + 1, level + 3, [100] * (level + 3), grid)
+                if nwg == 0:
+                    continue
+                assert parts <= _max_parts(n0)
+                # Rotate / Conjugate of n0 >= 2 components (csrc/engine_ops.hip): n0 key products onto out_0 (c_0 is the ModDown's addend, no summand of
+                # the inverse job), one CRS product per party slot, 2 n0 items and their parts behind them
+                assert min(members, n0) * parts <= VI_SUMS and 2 * n0 + 2 * n0 * (parts - 1) <= 255
+                for n1 in range(0, 33):
+                    if 2 * n0 + n1 > EXT_MAX_ITEMS:
+                        continue
+                    layouts = [(list(range(n0)), list(range(n1)))]
+                    if n0 + n1 <= 32:
+                        layouts.append((list(range(n0)), list(range(n0, n0 + n1))))
+                    for ids0, ids1 in layouts:
+                        jobs, top = _tail_jobs(ids0, ids1, parts, members)
+                        assert max(jobs) <= VI_SUMS, (n0, n1, level, parts, jobs)
+                        assert top <= 255, (n0, n1, level, parts, top)
+                        shapes += 1
+    assert shapes > 1000
+
+
 F2_RUN_COST, F2_PART_COST, F2_SLACK = 80, 8, 190       # csrc/ntt_kernels.h, in units of a pass = 100
 
 

@@ -14,27 +14,9 @@ import numpy as np
 import pytest
 
 import harness as H
-from gpu_common import Pair
+from gpu_common import Pair, pset_ct as _ct, pset_swk as _swk
 
 pytestmark = pytest.mark.gpu
-
-
-def _swk(pset, rng, beta=None):
-    """uniform residues, switching-key shaped uint64[beta][nQ+nP][N]"""
-    Q, P, N = pset["Q"], pset["P"], 1 << pset["logN"]
-    beta = len(Q) if beta is None else beta
-    out = np.empty((beta, len(Q) + len(P), N), dtype=np.uint64)
-    for j, q in enumerate(Q + P):
-        out[:, j] = rng.integers(0, q, (beta, N), dtype=np.uint64)
-    return out
-
-
-def _ct(pset, rng, n, limbs):
-    N = 1 << pset["logN"]
-    out = np.empty((1 + n, limbs, N), dtype=np.uint64)
-    for l in range(limbs):
-        out[:, l] = rng.integers(0, pset["Q"][l], (1 + n, N), dtype=np.uint64)
-    return out
 
 
 @pytest.fixture(scope="module")
