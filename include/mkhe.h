@@ -696,6 +696,43 @@ int  mkhe_bfv_refresh_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, 
  * Everything is canonical, and every limb of every component of out is written.  One streaming launch; w never reaches memory. */
 int  mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares,
                             const mkhe_ct* const* reenc /* [i * count + b] */, mkhe_ct* const* out);
+/* ---- encryption to shares (E2S) and back (S2E): the seam of the two refreshes, opened --------------------------------------------------------
+ * A collective refresh is E2S followed by S2E, welded shut: the party forms its mask, publishes the masked share, encrypts the negated mask and
+ * forgets it.  The calls below stop in the middle.  E2S takes the parties from a ciphertext to ADDITIVE SHARES of its plaintext -- each party keeps
+ * the negated mask it would have encrypted, anyone computes the public share from c_0 and the published shares -- and nobody sees the plaintext.
+ * Between E2S and S2E the parties can do in ordinary secret sharing what no evaluator here can (comparisons, divisions, table look-ups, an arbitrary
+ * shuffle).  S2E needs no entry point: every party encrypts its additive share as a plaintext (mkhe_encrypt / mkhe_encrypt_seeded) and anyone adds
+ * the ciphertexts (mkhe_ct_add); the holder of the public share first adds it into its own (mkhe_limbs_sum; for BFV mod T by any means).
+ *
+ * mkrlwe / MK-CKKS: notation, keystream kind 3 and rules of "collective refresh" above.  The shares are exact over R_Q in the coefficient domain.
+ *   mkhe_e2s_share  dev_shares = uint64[count][Lin][N]: bit for bit what mkhe_refresh_share writes to its dev_shares for the same (key, nonce_mask,
+ *                   mask_bits) -- M_b from the streams 2 b and 2 b + 1.  dev_secret = uint64[count][secret_limbs][N], 1 <= secret_limbs <= nQ:
+ *                   secret[b][j][n] = (-M_b[n]) mod q_j, canonical, coefficient domain: the plaintext mkhe_refresh_share encrypts when Lout =
+ *                   secret_limbs.  It is the party's additive share, in a buffer the caller owns: the engine does not wipe it.  It still wipes
+ *                   the unmasked product from its own scratch.  key may be NULL when mask_bits = 0 (no stream is read; tests only).
+ *   mkhe_e2s_merge  steps 1-3 of mkhe_refresh_merge with no re-encryption: dev_pt_out = uint64[count][limbs_out][N], R~ mod q_j for j < limbs_out,
+ *                   1 <= limbs_out <= nQ: polynomial 0 of mkhe_refresh_merge called with all-zero reenc, bit for bit.  The same kernel.
+ * Identity: for j < Lin, (R~ + sum_i secret_i) mod q_j is mkhe_decrypt's plaintext, bit for bit, for any mask_bits: the masks cancel modulo every
+ * prime.  Above Lin the sum is the exact centred lift of the message only under the caller's condition of "collective refresh".
+ * Refused, with messages that start with the function's name: BFV contexts; contexts with mkhe_ctx_set_owned; both calls between mkhe_capture_begin
+ * and mkhe_capture_end; mask_bits outside 0 .. 120; a NULL key with mask_bits > 0; a slot out of range; inputs at different levels (merge: over
+ * different ids, nshares other than the number of parties); secret_limbs or limbs_out outside 1 .. nQ; a NULL or misaligned buffer; count outside
+ * 1 .. 65535.  A refused call has enqueued nothing and leaves the context usable.  nonce_mask obeys the one-call rule of the seeded calls. */
+int  mkhe_e2s_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8],
+                    uint64_t nonce_mask, int mask_bits, void* dev_shares /* uint64[count][Lin][N] */, int secret_limbs,
+                    void* dev_secret /* uint64[count][secret_limbs][N] */);
+int  mkhe_e2s_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, int limbs_out,
+                    void* dev_pt_out /* uint64[count][limbs_out][N] */);
+/* MK-BFV: notation, keystream kinds 4 and 5 and rules of "collective refresh for MK-BFV" above.  The shares are exact over Z_T, slot by slot.
+ *   dev_shares = uint64[count][nQ][N]: bit for bit mkhe_bfv_refresh_share's dev_shares with mask = 1 and the same (key, nonce_mask, flood_bits); item
+ *   b owns the streams b S .. b S + S - 1.  dev_secret = uint64[count][N]: secret[b][n] = (T - A_b[n]) mod T, coefficients over Z_T in the format
+ *   mkhe_bfv_scale_down writes: mkhe_bfv_scale_up of it is exactly the plaintext mkhe_bfv_refresh_share encrypts, mkhe_bfv_coeffs_to_slots of it the
+ *   party's additive share of the slots.  The caller owns it; the engine wipes the unmasked product from its scratch.
+ * The public side needs no entry point: mkhe_decrypt_merge followed by mkhe_bfv_scale_down gives w = (m + sum_i A_i) mod T coefficient-wise (under
+ * the condition on the noise stated there), so w + sum_i secret_i = m (mod T) coefficient-wise, and slot by slot after mkhe_bfv_coeffs_to_slots.
+ * Refused: what mkhe_bfv_refresh_share refuses (there is no mask argument and no nonce_enc). */
+int  mkhe_bfv_e2s_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8],
+                        uint64_t nonce_mask, int flood_bits, void* dev_shares /* uint64[count][nQ][N] */, void* dev_secret /* uint64[count][N], each < T */);
 /* ---- collective public-key switch: shares under a recipient's public key and their merge (PCKS of multiparty RLWE) ------------------------
  * mkhe_decrypt_merge gives the plaintext in the clear to whoever merges and to everyone who sees the shares.  With this protocol a result goes to
  * ONE recipient -- a client who is not among the computing parties, or one of them alone: every party publishes one share made from its secret key
@@ -924,6 +961,24 @@ int  mkhe_ctx_bfv_tile(mkhe_ctx* ctx);
 int  mkhe_ctx_set_bfv_tile(mkhe_ctx* ctx, int log_points);
 /* psi of the definitions above; 0 = error (the same conditions as the encoder calls) */
 uint64_t mkhe_ctx_bfv_slot_psi(mkhe_ctx* ctx);
+/* BFV slot map (no reference counterpart).  A slot map is out_slot[i] = mult[i] * in_slot[index[i]] mod T for 0 <= i < N, slots numbered as above (two
+ * rows of N/2); index is ANY function into 0 .. N-1 (a permutation, a replication, ..), and every such map is Z_T-linear, so it commutes with
+ * additive masks mod T: applied to the public and to the secret shares of "encryption to shares" it maps the message (mkbfv.Refresher.ShareMapBatch:
+ * a refresh that permutes, with no rotation key and no key switch).
+ *   mkhe_bfv_slot_map_prepare   dev_index uint32[N], dev_mult uint64[N] (taken mod T; NULL = all ones) -> dev_map uint64[N], opaque: the map composed
+ *       with the encoder's position table, one word per position.  Downloads, validates on the host (an index[i] >= N is refused) and uploads:
+ *       synchronous, once per map.
+ *   mkhe_bfv_slot_map   coeffs_out = slots_to_coeffs(map(coeffs_to_slots(coeffs_in))), bit for bit; coeffs as in the encoder calls (inputs taken mod
+ *       T, outputs < T); dev_coeffs_out may equal dev_coeffs_in.  N up to the tile of mkhe_ctx_bfv_tile: ONE launch, one workgroup per message --
+ *       forward transform, gather, product, inverse transform on one tile in LDS.  Larger N, or a tile lowered with mkhe_ctx_set_bfv_tile: five launches
+ *       around a work buffer (wiped behind the call).  The same bits.  Whatever dev_map holds, the kernels read inside the message and write values
+ *       below T: a map that mkhe_bfv_slot_map_prepare did not write gives a wrong result, never a fault.
+ * Refused: what the encoder calls refuse (non-BFV contexts, T outside the preconditions, captures, NULL or misaligned buffers, count outside
+ * 1 .. 65535). */
+int  mkhe_bfv_slot_map_prepare(mkhe_ctx* ctx, const void* dev_index /* uint32[N] */, const void* dev_mult /* uint64[N] or NULL */,
+                               void* dev_map /* uint64[N] */);
+int  mkhe_bfv_slot_map(mkhe_ctx* ctx, int count, const void* dev_coeffs_in /* uint64[count][N] */, const void* dev_map,
+                       void* dev_coeffs_out /* uint64[count][N] */);
 
 /* ==== BFV plaintext operands: AddPtxt, SubPtxt, MulPtxt ===============================================
  * No reference counterpart: mkbfv.Evaluator of the reference has no operation with a plaintext operand; the definitions are this project's own, in

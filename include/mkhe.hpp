@@ -10,6 +10,7 @@
 #include <cmath>
 #include <complex>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -763,6 +764,108 @@ class Refresher {
     std::shared_ptr<Ciphertext> MergeNew(const Ciphertext& ct, const std::vector<const RefreshShare*>& shares) { return MergeBatch({&ct}, shares)[0]; }
     Parameters& params;
 };
+// An ADDITIVE share of the plaintexts of `count` ciphertexts (include/mkhe.h, "encryption to shares"): uint64[count][limbs][N] on the device, the id of the
+// party that holds it (empty: the public share, which anyone can compute) and the level (-1 where the share is over Z_T: mkbfv, limbs = 1).  A
+// party's share is as secret as its mask and travels to nobody.  Wipe() overwrites the device buffer with zeros and then frees it.
+struct SecretShare {
+    SecretShare(Parameters& p, std::string id, int level, int count = 1, int limbs = -1)
+        : ID(std::move(id)), Level(level), Count(count), Limbs(limbs < 0 ? level + 1 : limbs), Value(p, (size_t)count * (limbs < 0 ? level + 1 : limbs) * p.N()) {}
+    void Wipe() {
+        if (!Value.d) return;
+        const std::vector<uint64_t> zero(Value.words, 0);
+        Value.upload(zero.data());
+        mkhe_buf_free(Value.params.ctx, Value.d);
+        Value.d = nullptr;
+    }
+    std::string ID;
+    int Level, Count, Limbs;
+    DeviceWords Value;
+};
+
+// HE <-> additive secret sharing between parties, exact over R_Q in the coefficient domain (the Python mirror's mkrlwe.ShareConverter).  E2S: every party
+// runs E2SShareBatch on its own key and DeviceSampler, publishes the DecryptionShare (Refresher::ShareBatch's, bit for bit) and KEEPS the SecretShare;
+// anyone runs E2SMergeBatch, which gives the public share.  public + the sum of the secret shares is the plaintext of Decrypt modulo every prime of
+// the input level, whatever maskBits is.  S2E: the holder of the public share folds it into its own (FoldPublic: mkhe_limbs_sum) BEFORE it encrypts;
+// every party encrypts its share under its own public key (S2EShareBatch); S2EMergeNew is the AddNew chain over the parties' ciphertexts.
+class ShareConverter {
+  public:
+    explicit ShareConverter(Parameters& p) : params(p) {}
+    virtual ~ShareConverter() = default;
+    // one nonce of `sampler`; levelOut: the level of the secret share (default: the maximum level)
+    std::pair<std::shared_ptr<DecryptionShare>, std::shared_ptr<SecretShare>> E2SShareBatch(const std::vector<const Ciphertext*>& cts, const SecretKey& sk, int maskBits,
+                                                                                            DeviceSampler& sampler, int levelOut = -1) {
+        if (cts.empty()) throw Error("Cannot E2SShare: no ciphertext");
+        if (maskBits < 0 || maskBits > 120) throw Error("Cannot E2SShare: maskBits must be 0 .. 120");
+        if (levelOut < 0) levelOut = params.MaxLevel();
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        auto pub = std::make_shared<DecryptionShare>(params, sk.ID, cts[0]->Level(), (int)cts.size());
+        auto sec = std::make_shared<SecretShare>(params, sk.ID, levelOut, (int)cts.size());
+        check(mkhe_e2s_share(params.ctx, (int)cts.size(), in.data(), slots.data(), sk.Value.d, sampler.Key(), sampler.NextNonce(), maskBits, pub->Value.d,
+                             levelOut + 1, sec->Value.d));
+        return {pub, sec};
+    }
+    // one DecryptionShare of count cts.size() per party, in any order, for ciphertexts over the same ids at one level -> the public share (ID empty)
+    std::shared_ptr<SecretShare> E2SMergeBatch(const std::vector<const Ciphertext*>& cts, const std::vector<const DecryptionShare*>& shares, int levelOut = -1) {
+        if (cts.empty()) throw Error("Cannot E2SMerge: no ciphertext");
+        if (levelOut < 0) levelOut = params.MaxLevel();
+        std::vector<const mkhe_ct*> in;
+        for (auto* ct : cts) in.push_back(ct->h);
+        const std::vector<const void*> ordered = orderShares(*cts[0], (int)cts.size(), shares);
+        auto out = std::make_shared<SecretShare>(params, std::string(), levelOut, (int)cts.size());
+        check(mkhe_e2s_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), levelOut + 1, out->Value.d));
+        return out;
+    }
+    std::shared_ptr<SecretShare> FoldPublic(const SecretShare& secret, const SecretShare& pub) {
+        if (secret.Count != pub.Count || secret.Limbs != pub.Limbs) throw Error("Cannot FoldPublic: the shares differ in count or level");
+        auto out = std::make_shared<SecretShare>(params, secret.ID, secret.Level, secret.Count, secret.Limbs);
+        const void* src[2] = {secret.Value.d, pub.Value.d};
+        check(mkhe_limbs_sum(params.ctx, secret.Count, secret.Limbs, 2, src, out->Value.d));
+        return out;
+    }
+    // the party of pk encrypts its share as a plaintext under its own public key (mkhe_encrypt_seeded, one nonce): Count ciphertexts over its id
+    std::vector<std::shared_ptr<Ciphertext>> S2EShareBatch(const SecretShare& secret, const PublicKey& pk, DeviceSampler& sampler) {
+        if (!secret.ID.empty() && secret.ID != pk.ID) throw Error("Cannot S2EShare: the share and pk belong to different parties");
+        std::vector<std::shared_ptr<Ciphertext>> cts;
+        std::vector<mkhe_ct*> out;
+        for (int b = 0; b < secret.Count; ++b) { cts.push_back(newCt(IDSet{pk.ID}, secret.Limbs - 1)); out.push_back(cts.back()->h); }
+        check(mkhe_encrypt_seeded(params.ctx, secret.Limbs - 1, secret.Count, pk.Value.d, secret.Value.d, 0, sampler.Key(), sampler.NextNonce(),
+                                  sampler.cdt.data(), (int)sampler.cdt.size(), out.data()));
+        return cts;
+    }
+    // the AddNew chain over the parties' ciphertexts (one each) -> one ciphertext over all their ids
+    std::shared_ptr<Ciphertext> S2EMergeNew(const std::vector<const Ciphertext*>& ctsByParty) {
+        if (ctsByParty.empty()) throw Error("Cannot S2EMerge: no ciphertext");
+        std::shared_ptr<Ciphertext> acc;
+        const Ciphertext* cur = ctsByParty[0];
+        for (size_t i = 1; i < ctsByParty.size(); ++i) {
+            auto out = newCt(Union(cur->IDSet_(), ctsByParty[i]->IDSet_()), cur->Level());
+            check(mkhe_ct_add(params.ctx, cur->h, ctsByParty[i]->h, out->h));
+            acc = out;
+            cur = acc.get();
+        }
+        if (!acc) { acc = newCt(cur->IDSet_(), cur->Level()); check(mkhe_ct_copy(params.ctx, cur->h, acc->h)); }
+        return acc;
+    }
+    // the shares of a merge in the slot order of a ciphertext; throws on a missing, duplicate or foreign share, another level or batch size
+    static std::vector<const void*> orderShares(const Ciphertext& like, int count, const std::vector<const DecryptionShare*>& shares) {
+        std::vector<const void*> ordered;
+        for (auto& id : like.ids) {
+            const DecryptionShare* found = nullptr;
+            for (auto* sh : shares)
+                if (sh->ID == id) { if (found) throw Error("Cannot MergeShares: two shares of one party"); found = sh; }
+            if (!found) throw Error("Cannot MergeShares: the share of a party is missing");
+            if (found->Level != like.Level() || found->Count != count) throw Error("Cannot MergeShares: a share is at another level or for another batch size");
+            ordered.push_back(found->Value.d);
+        }
+        if (shares.size() != ordered.size()) throw Error("Cannot MergeShares: a share of a party the ciphertext does not have");
+        return ordered;
+    }
+    Parameters& params;
+  protected:
+    virtual std::shared_ptr<Ciphertext> newCt(const IDSet& ids, int level) { return std::make_shared<Ciphertext>(params, ids, level, false); }
+};
 // What one party publishes in a collective key switch to a recipient's public key (include/mkhe.h, "collective public-key switch") of `count`
 // ciphertexts at `level`: the pairs (h0, h1), uint64[count][2][level+1][N] on the device.  Shares travel between parties: Value.download on one
 // side, Value.upload on the other.
@@ -1125,6 +1228,17 @@ class Decryptor : public mkrlwe::Decryptor {
         return mkrlwe::Decryptor::NoiseNorm(ct, skSet, ref.d);
     }
     int NoiseBits(const Ciphertext& ct, const mkrlwe::SecretKeySet& skSet, const std::complex<double>* msg) { return NoiseNorm(ct, skSet, msg).Bits(); }
+  private:
+    Parameters& ckks;
+};
+// mkrlwe::ShareConverter on mkckks ciphertexts.  The shares are over R_Q in the coefficient domain and carry no scale (a 120-bit mask does not survive a
+// float64 decode, so there is no slot form): the caller sets Scale to that of the ciphertexts E2S started from, and S2E gives mkckks::Ciphertexts with it.
+class ShareConverter : public mkrlwe::ShareConverter {
+  public:
+    explicit ShareConverter(Parameters& p, double scale = 0.0) : mkrlwe::ShareConverter(p), Scale(scale), ckks(p) {}
+    double Scale;
+  protected:
+    std::shared_ptr<mkrlwe::Ciphertext> newCt(const mkrlwe::IDSet& ids, int level) override { return std::make_shared<Ciphertext>(ckks, ids, level, Scale, false); }
   private:
     Parameters& ckks;
 };
@@ -1536,6 +1650,150 @@ class Decryptor : public mkrlwe::Decryptor {
     Parameters& bfv;
 };
 
+// mkrlwe::SecretShare over Z_T (include/mkhe.h, "encryption to shares"): coefficients uint64[count][N], each below T, in the format mkhe_bfv_scale_down
+// writes; no level.  Slots() is the share of the SLOTS: additive mod T slot by slot, as the transform is Z_T-linear.
+struct SecretShare : mkrlwe::SecretShare {
+    SecretShare(Parameters& p, std::string id, int count = 1) : mkrlwe::SecretShare(p, std::move(id), -1, count, 1), bfv(p) {}
+    // -> values (host: Count * N), centred
+    void Slots(int64_t* values) const {
+        mkrlwe::DeviceWords z(bfv, Value.words);
+        check(mkhe_bfv_coeffs_to_slots(bfv.ctx, Count, Value.d, z.d));
+        z.download(reinterpret_cast<uint64_t*>(values));
+    }
+    // the inverse: count * N slots (any int64) -> the share whose Slots() they are mod T
+    static std::shared_ptr<SecretShare> FromSlots(Parameters& p, int count, const int64_t* values, std::string id = std::string()) {
+        auto out = std::make_shared<SecretShare>(p, std::move(id), count);
+        mkrlwe::DeviceWords z(p, out->Value.words);
+        z.upload(reinterpret_cast<const uint64_t*>(values));
+        check(mkhe_bfv_slots_to_coeffs(p.ctx, count, z.d, out->Value.d));
+        return out;
+    }
+    Parameters& bfv;
+};
+
+// out_slot[i] = mult[i] * in_slot[index[i]] mod T for 0 <= i < N (include/mkhe.h, "BFV slot map"), slots numbered as the batch encoder numbers them (two
+// rows of N/2): any permutation, replication or slot-wise scaling.  index: N values in 0 .. N-1, any function; mult: N values taken mod T, empty = all
+// ones.  Prepared once, in the constructor (mkhe_bfv_slot_map_prepare, which refuses an index >= N).
+class SlotMap {
+  public:
+    SlotMap(Parameters& p, std::vector<uint32_t> index_, std::vector<uint64_t> mult_ = {}) : params(p), index(std::move(index_)), mult(std::move(mult_)), map_(p, (size_t)p.N()) {
+        const size_t N = (size_t)p.N();
+        if (index.size() != N || (!mult.empty() && mult.size() != N)) throw Error("mkbfv::SlotMap: index and mult have N entries");
+        if (mult.empty()) mult.assign(N, 1);
+        for (auto& m : mult) m %= p.T();
+        mkrlwe::DeviceWords in(p, N + N / 2);                              // mult, then the index as uint32[N]
+        std::vector<uint64_t> host(N + N / 2, 0);
+        std::copy(mult.begin(), mult.end(), host.begin());
+        std::memcpy(host.data() + N, index.data(), N * sizeof(uint32_t));
+        in.upload(host.data());
+        check(mkhe_bfv_slot_map_prepare(p.ctx, static_cast<const uint64_t*>(in.d) + N, in.d, map_.d));
+    }
+    static std::shared_ptr<SlotMap> Permutation(Parameters& p, const std::vector<uint32_t>& perm) {
+        std::vector<char> seen(perm.size(), 0);
+        for (uint32_t v : perm) { if (v >= perm.size() || seen[v]) throw Error("mkbfv::SlotMap: Permutation takes a permutation of 0 .. N-1"); seen[v] = 1; }
+        return std::make_shared<SlotMap>(p, perm);
+    }
+    // what RotateNew(ct, k) does to the slots: slot i + k moves to slot i within each row of N/2; swapRows: and the rows change places
+    static std::shared_ptr<SlotMap> Rotation(Parameters& p, int k, bool swapRows = false) {
+        const int N = p.N(), half = N / 2;
+        std::vector<uint32_t> idx(N);
+        for (int i = 0; i < N; ++i) idx[i] = (uint32_t)((((i / half) ^ (swapRows ? 1 : 0)) * half) + (((i % half + k) % half + half) % half));
+        return std::make_shared<SlotMap>(p, std::move(idx));
+    }
+    // the host definition: (mult * values[index]) mod T, centred (one message of N slots)
+    std::vector<int64_t> Apply(const int64_t* values) const {
+        const int64_t T = (int64_t)params.T();
+        std::vector<int64_t> out(index.size());
+        for (size_t i = 0; i < out.size(); ++i) {
+            const uint64_t v = (uint64_t)(((values[index[i]] % T) + T) % T);
+            const int64_t r = (int64_t)(v * mult[i] % (uint64_t)T);         // both below 2^32: the product fits
+            out[i] = r > T / 2 ? r - T : r;
+        }
+        return out;
+    }
+    // the map applied to a SecretShare -> a new SecretShare of the same party: one engine call
+    std::shared_ptr<SecretShare> MapCoeffs(const SecretShare& s) const {
+        auto out = std::make_shared<SecretShare>(params, s.ID, s.Count);
+        check(mkhe_bfv_slot_map(params.ctx, s.Count, s.Value.d, map_.d, out->Value.d));
+        return out;
+    }
+    const void* dev() const { return map_.d; }
+    Parameters& params;
+    std::vector<uint32_t> index;
+    std::vector<uint64_t> mult;
+  private:
+    mkrlwe::DeviceWords map_;
+};
+
+// HE <-> additive secret sharing over Z_T for MK-BFV, exact slot by slot (the Python mirror's mkbfv.ShareConverter).  E2S: every party runs
+// E2SShareBatch, publishes the DecryptionShare (Refresher::ShareBatch's, bit for bit) and KEEPS the SecretShare (T - A); anyone runs E2SMergeBatch
+// (mkhe_decrypt_merge, then mkhe_bfv_scale_down), which gives the public share w = (m + sum A_i) mod T.  S2E: every party encrypts its share
+// (mkhe_bfv_scale_up, mkhe_encrypt_seeded), S2EMergeNew is the AddNew chain, and the public share, scaled up, is added to the result as a plaintext.
+class ShareConverter {
+  public:
+    explicit ShareConverter(Parameters& p) : params(p) {}
+    std::pair<std::shared_ptr<mkrlwe::DecryptionShare>, std::shared_ptr<SecretShare>> E2SShareBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const mkrlwe::SecretKey& sk,
+                                                                                                    int floodBits, mkrlwe::DeviceSampler& sampler) {
+        if (cts.empty()) throw Error("Cannot E2SShare: no ciphertext");
+        if (floodBits < 0 || floodBits > 1024) throw Error("Cannot E2SShare: floodBits must be 0 .. 1024");
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        auto pub = std::make_shared<mkrlwe::DecryptionShare>(params, sk.ID, params.MaxLevel(), (int)cts.size());
+        auto sec = std::make_shared<SecretShare>(params, sk.ID, (int)cts.size());
+        check(mkhe_bfv_e2s_share(params.ctx, (int)cts.size(), in.data(), slots.data(), sk.Value.d, sampler.Key(), sampler.NextNonce(), floodBits, pub->Value.d,
+                                 sec->Value.d));
+        return {pub, sec};
+    }
+    std::shared_ptr<SecretShare> E2SMergeBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const std::vector<const mkrlwe::DecryptionShare*>& shares) {
+        if (cts.empty()) throw Error("Cannot E2SMerge: no ciphertext");
+        std::vector<const mkhe_ct*> in;
+        for (auto* ct : cts) in.push_back(ct->h);
+        const std::vector<const void*> ordered = mkrlwe::ShareConverter::orderShares(*cts[0], (int)cts.size(), shares);
+        mkrlwe::DeviceWords pt(params, (size_t)cts.size() * params.QCount() * params.N());
+        check(mkhe_decrypt_merge(params.ctx, (int)cts.size(), in.data(), (int)ordered.size(), ordered.data(), pt.d));
+        auto out = std::make_shared<SecretShare>(params, std::string(), (int)cts.size());
+        check(mkhe_bfv_scale_down(params.ctx, (int)cts.size(), pt.d, out->Value.d));
+        return out;
+    }
+    std::vector<std::shared_ptr<Ciphertext>> S2EShareBatch(const SecretShare& secret, const mkrlwe::PublicKey& pk, mkrlwe::DeviceSampler& sampler) {
+        if (!secret.ID.empty() && secret.ID != pk.ID) throw Error("Cannot S2EShare: the share and pk belong to different parties");
+        mkrlwe::SecretShare pt(params, secret.ID, params.MaxLevel(), secret.Count);
+        std::vector<std::shared_ptr<Ciphertext>> cts;
+        std::vector<mkhe_ct*> out;
+        for (int b = 0; b < secret.Count; ++b) { cts.push_back(std::make_shared<Ciphertext>(params, mkrlwe::IDSet{pk.ID}, false)); out.push_back(cts.back()->h); }
+        check(mkhe_bfv_scale_up(params.ctx, secret.Count, secret.Value.d, pt.Value.d));
+        const int rc = mkhe_encrypt_seeded(params.ctx, params.MaxLevel(), secret.Count, pk.Value.d, pt.Value.d, 0, sampler.Key(), sampler.NextNonce(), sampler.cdt.data(),
+                                           (int)sampler.cdt.size(), out.data());
+        pt.Wipe();
+        check(rc);
+        return cts;
+    }
+    std::shared_ptr<Ciphertext> S2EMergeNew(const std::vector<const Ciphertext*>& ctsByParty, const SecretShare* pub = nullptr) {
+        if (ctsByParty.empty()) throw Error("Cannot S2EMerge: no ciphertext");
+        if (pub && pub->Count != 1) throw Error("Cannot S2EMerge: the public share of one ciphertext expected");
+        mkrlwe::IDSet ids = ctsByParty[0]->IDSet_();
+        auto acc = std::make_shared<Ciphertext>(params, ids, false);
+        check(mkhe_ct_copy(params.ctx, ctsByParty[0]->h, acc->h));
+        for (size_t i = 1; i < ctsByParty.size(); ++i) {
+            ids = mkrlwe::Union(ids, ctsByParty[i]->IDSet_());
+            auto out = std::make_shared<Ciphertext>(params, ids, false);
+            check(mkhe_ct_add(params.ctx, acc->h, ctsByParty[i]->h, out->h));
+            acc = out;
+        }
+        if (pub) {
+            mkrlwe::DeviceWords pt(params, (size_t)params.QCount() * params.N());
+            check(mkhe_bfv_scale_up(params.ctx, 1, pub->Value.d, pt.d));
+            auto out = std::make_shared<Ciphertext>(params, ids, false);
+            const mkhe_ct* in = acc->h; mkhe_ct* o = out->h;
+            check(mkhe_bfv_ct_add_ptxt(params.ctx, 0, 1, &in, pt.d, 0, &o));
+            acc = out;
+        }
+        return acc;
+    }
+    Parameters& params;
+};
+
 // The collective refresh of MK-BFV between parties (include/mkhe.h, "collective refresh for MK-BFV"): ShareNew (each party, on its own keys and its
 // own DeviceSampler) and MergeNew (anyone) give a ciphertext of the same message over the same parties with the noise of a fresh encryption.  What
 // travels is mkrlwe::RefreshShare, with both levels the maximum level.  The caller chooses floodBits: floodBits minus the bit size of the
@@ -1590,6 +1848,79 @@ class Refresher {
         return outs;
     }
     std::shared_ptr<Ciphertext> MergeNew(const mkrlwe::Ciphertext& ct, const std::vector<const mkrlwe::RefreshShare*>& shares) { return MergeBatch({&ct}, shares)[0]; }
+    // The refresh that applies a slot map: the result encrypts map.Apply(message), with no rotation key and no key switch.  The map is Z_T-linear, so it
+    // commutes with the masks.  ShareMapBatch = mkhe_bfv_e2s_share -> mkhe_bfv_slot_map -> mkhe_bfv_scale_up -> mkhe_encrypt_seeded on the two nonces
+    // ShareBatch takes; with the identity map it is ShareBatch's, bit for bit.  The intermediate secret buffers are zeroed behind their last use.
+    std::shared_ptr<mkrlwe::RefreshShare> ShareMapBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const mkrlwe::SecretKey& sk, const mkrlwe::PublicKey& pk,
+                                                        int floodBits, mkrlwe::DeviceSampler& sampler, const SlotMap& map) {
+        if (cts.empty()) throw Error("Cannot RefreshShare: no ciphertext");
+        if (sk.ID != pk.ID) throw Error("Cannot RefreshShare: sk and pk belong to different parties");
+        if (floodBits < 0 || floodBits > 1024) throw Error("Cannot RefreshShare: floodBits must be 0 .. 1024");
+        std::vector<const mkhe_ct*> in;
+        std::vector<int> slots;
+        for (auto* ct : cts) { in.push_back(ct->h); slots.push_back(ct->slot(sk.ID)); }
+        const int level = params.MaxLevel(), B = (int)cts.size();
+        auto out = std::make_shared<mkrlwe::RefreshShare>(params, sk.ID, level, level, B);
+        std::vector<mkhe_ct*> re;
+        for (auto& c : out->Reenc) re.push_back(c->h);
+        const uint64_t nonce = sampler.NextNoncePair();
+        SecretShare sec(params, sk.ID, B);
+        mkrlwe::SecretShare pt(params, sk.ID, level, B);
+        int rc = mkhe_bfv_e2s_share(params.ctx, B, in.data(), slots.data(), sk.Value.d, sampler.Key(), nonce, floodBits, out->Share.Value.d, sec.Value.d);
+        if (!rc) rc = mkhe_bfv_slot_map(params.ctx, B, sec.Value.d, map.dev(), sec.Value.d);
+        if (!rc) rc = mkhe_bfv_scale_up(params.ctx, B, sec.Value.d, pt.Value.d);
+        if (!rc) rc = mkhe_encrypt_seeded(params.ctx, level, B, pk.Value.d, pt.Value.d, 0, sampler.Key(), nonce + 1, sampler.cdt.data(), (int)sampler.cdt.size(), re.data());
+        const std::string err = rc ? mkhe_last_error() : "";
+        sec.Wipe();
+        pt.Wipe();
+        if (rc) throw Error(err);
+        return out;
+    }
+    std::shared_ptr<mkrlwe::RefreshShare> ShareMapNew(const mkrlwe::Ciphertext& ct, const mkrlwe::SecretKey& sk, const mkrlwe::PublicKey& pk, int floodBits,
+                                                      mkrlwe::DeviceSampler& sampler, const SlotMap& map) {
+        return ShareMapBatch({&ct}, sk, pk, floodBits, sampler, map);
+    }
+    // MergeBatch for shares made by ShareMapBatch with the same map: E2SMergeBatch -> mkhe_bfv_slot_map -> mkhe_bfv_scale_up, added (mkhe_bfv_ct_add_ptxt)
+    // into c_0 of the sum of the re-encryptions (mkhe_ct_add over the unions).  With the identity map it is MergeBatch's, bit for bit.
+    std::vector<std::shared_ptr<Ciphertext>> MergeMapBatch(const std::vector<const mkrlwe::Ciphertext*>& cts, const std::vector<const mkrlwe::RefreshShare*>& shares,
+                                                           const SlotMap& map) {
+        if (cts.empty()) throw Error("Cannot RefreshMerge: no ciphertext");
+        if (cts[0]->ids.empty()) throw Error("Cannot RefreshMerge: ciphertexts without parties have nothing to refresh");
+        const int B = (int)cts.size();
+        std::vector<const mkrlwe::RefreshShare*> ordered;
+        std::vector<const mkrlwe::DecryptionShare*> pubs;
+        for (auto& id : cts[0]->ids) {
+            const mkrlwe::RefreshShare* found = nullptr;
+            for (auto* sh : shares)
+                if (sh->ID == id) { if (found) throw Error("Cannot MergeShares: two shares of one party"); found = sh; }
+            if (!found) throw Error("Cannot MergeShares: the share of a party is missing");
+            ordered.push_back(found);
+            pubs.push_back(&found->Share);
+        }
+        if (shares.size() != ordered.size()) throw Error("Cannot MergeShares: a share of a party the ciphertext does not have");
+        auto w = ShareConverter(params).E2SMergeBatch(cts, pubs);
+        mkrlwe::DeviceWords pt(params, (size_t)B * params.QCount() * params.N());
+        check(mkhe_bfv_slot_map(params.ctx, B, w->Value.d, map.dev(), w->Value.d));
+        check(mkhe_bfv_scale_up(params.ctx, B, w->Value.d, pt.d));
+        std::vector<std::shared_ptr<Ciphertext>> outs;
+        for (int b = 0; b < B; ++b) {
+            mkrlwe::IDSet ids{ordered[0]->ID};
+            std::shared_ptr<mkrlwe::Ciphertext> acc = ordered[0]->Reenc[b];
+            for (size_t i = 1; i < ordered.size(); ++i) {
+                ids.insert(ordered[i]->ID);
+                auto next = std::make_shared<Ciphertext>(params, ids, false);
+                check(mkhe_ct_add(params.ctx, acc->h, ordered[i]->Reenc[b]->h, next->h));
+                acc = next;
+            }
+            outs.push_back(std::make_shared<Ciphertext>(params, cts[0]->IDSet_(), false));
+            const mkhe_ct* in = acc->h; mkhe_ct* o = outs.back()->h;
+            check(mkhe_bfv_ct_add_ptxt(params.ctx, 0, 1, &in, static_cast<const uint64_t*>(pt.d) + (size_t)b * params.QCount() * params.N(), 0, &o));
+        }
+        return outs;
+    }
+    std::shared_ptr<Ciphertext> MergeMapNew(const mkrlwe::Ciphertext& ct, const std::vector<const mkrlwe::RefreshShare*>& shares, const SlotMap& map) {
+        return MergeMapBatch({&ct}, shares, map)[0];
+    }
     Parameters& params;
 };
 // The collective key switch of mkrlwe::PublicKeySwitcher on mkbfv ciphertexts: the message stays exact as long as NoiseBound plus the noise of

@@ -129,6 +129,9 @@ SIGNATURES = {
     "mkhe_refresh_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp, vpp]),
     "mkhe_bfv_refresh_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, vp, u32p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, u64p, C.c_int, vp, vpp]),
     "mkhe_bfv_refresh_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp, vpp]),
+    "mkhe_e2s_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, u32p, C.c_uint64, C.c_int, vp, C.c_int, vp]),
+    "mkhe_e2s_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, C.c_int, vp]),
+    "mkhe_bfv_e2s_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, u32p, C.c_uint64, C.c_int, vp, vp]),
     "mkhe_pcks_share": (C.c_int, [vp, C.c_int, vpp, i32p, vp, vp, u32p, C.c_uint64, C.c_int, u64p, C.c_int, vp]),
     "mkhe_pcks_merge": (C.c_int, [vp, C.c_int, vpp, C.c_int, vpp, vpp]),
     "mkhe_threshold_gen_shares": (C.c_int, [vp, vp, C.c_int, C.c_int, u32p, u32p, C.c_uint64, vpp]),
@@ -153,6 +156,8 @@ SIGNATURES = {
     "mkhe_bfv_scale_down": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_bfv_encode": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_bfv_decode": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mkhe_bfv_slot_map_prepare": (C.c_int, [vp, vp, vp, vp]),
+    "mkhe_bfv_slot_map": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "mkhe_bfv_lift": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_bfv_encode_mul": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_bfv_ct_mul_ptxt": (C.c_int, [vp, C.c_int, vpp, vp, C.c_long, vpp]),

@@ -176,6 +176,69 @@ void Context::bfv_decode(int count, const u64* pt, u64* slots) {
     bf_ntt(false, BF_FUSE_SCALE, count, pt, slots);
     MKHE_HIP(hipGetLastError());
 }
+// ---- slot map (bfv_kernels.h).  prepare validates on the host from a synchronous download and uploads one word per position.
+void Context::bfv_slot_map_prepare(const u32* dev_index, const u64* dev_mult, u64* dev_map) {
+    bf_init("mkhe_bfv_slot_map_prepare");
+    const size_t n = (size_t)N;
+    const u64 T = bfv_t;
+    std::vector<u32> index(n);
+    std::vector<u64> mult(n, 1), map(n);
+    MKHE_HIP(hipMemcpyAsync(index.data(), dev_index, n * sizeof(u32), hipMemcpyDeviceToHost, stream));
+    if (dev_mult) MKHE_HIP(hipMemcpyAsync(mult.data(), dev_mult, n * sizeof(u64), hipMemcpyDeviceToHost, stream));
+    sync();
+    for (size_t i = 0; i < n; ++i)
+        if (index[i] >= n) throw Error("mkhe_bfv_slot_map_prepare: index[" + std::to_string(i) + "] = " + std::to_string(index[i]) + " is not a slot (0 .. N - 1)");
+    const std::vector<u32> pos = slot_positions(logN, 1, true);
+    std::vector<u32> inv(n);
+    for (size_t p = 0; p < n; ++p) inv[pos[p]] = (u32)p;
+    for (size_t p = 0; p < n; ++p) map[p] = ((u64)shoup(mult[pos[p]] % T, T).y << 32) | inv[index[pos[p]]];
+    MKHE_HIP(hipMemcpyAsync(dev_map, map.data(), n * sizeof(u64), hipMemcpyHostToDevice, stream));
+    sync();                                                                     // map is pageable and about to go out of scope
+}
+void Context::bfv_slot_map(int count, const u64* coeffs_in, const u64* dev_map, u64* coeffs_out) {
+    bf_init("mkhe_bfv_slot_map");
+    const size_t n = (size_t)N;
+    const double tables = 2.0 * (8.0 * n + 4.0 * n) + 8.0 * n;                  // both twists, both twiddle tables, the map
+    if (logN <= bf_tile_.log) {
+        BfvSlotMap m{};
+        m.in = coeffs_in; m.out = coeffs_out; m.map = dev_map;
+        m.w = d_bf_w; m.winv = d_bf_winv; m.twist = d_bf_twist; m.itwist = d_bf_itwist;
+        m.logn = logN; m.t = bf_t_;
+        {
+            ProfScope ps(this, PROF_OTHER, 16.0 * n * count + tables);
+            launch_bf_slot_map(m, count, s_);
+        }
+        MKHE_HIP(hipGetLastError());
+        return;
+    }
+    // two-launch form: forward into the first work buffer (position order: neither launch is the `last` one, whose store would scatter the
+    // slots), the gather into the second, the inverse from there (neither launch the `first` one, whose load would gather slots)
+    const size_t cwords = (size_t)count * n;                                    // two buffers of 32-bit words
+    u32* work = reinterpret_cast<u32*>(scratch(bf_work_, cwords));
+    u32* work2 = work + cwords;
+    BfvNtt a{};
+    a.pos = d_bf_pos; a.p.logn = logN; a.sc = bf_scale();
+    a.p.logt = std::min(bf_tile_.log, BF_TILE_LOG_MULTI);
+    a.w = d_bf_w; a.twist = d_bf_twist; a.in = coeffs_in; a.work = work;
+    tile_two_pass(a.p, false, logN - a.p.logt, [&] {
+        a.p.last = 0;
+        ProfScope ps(this, PROF_OTHER, (a.p.first ? 8.0 : 4.0) * n * count + 4.0 * n * count + tables / 4);
+        launch_bf_ntt(false, a, count, s_);
+    });
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * n * count + 8.0 * n);
+        launch_bf_slot_gather(work, work2, dev_map, N, bf_t_.T, count, s_);
+    }
+    a.w = d_bf_winv; a.twist = d_bf_itwist; a.in = nullptr; a.out = coeffs_out; a.work = work2;
+    tile_two_pass(a.p, true, logN - a.p.logt, [&] {
+        a.p.first = 0;
+        ProfScope ps(this, PROF_OTHER, 4.0 * n * count + (a.p.last ? 8.0 : 4.0) * n * count + tables / 4);
+        launch_bf_ntt(true, a, count, s_);
+    });
+    MKHE_HIP(hipMemsetAsync(work, 0, cwords * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
+}
+
 void Context::bfv_lift(int count, const u64* coeffs, u64* ptmul_coeff) {
     bf_init("mkhe_bfv_lift");
     bf_lift(count, coeffs, ptmul_coeff);

@@ -77,7 +77,27 @@ bool bf_ntt_big_lds();
 // inverse = slots_to_coeffs direction.  Launches N / 2^logt tiles per message.
 void launch_bf_ntt(bool inverse, const BfvNtt& a, int count, hipStream_t st);
 
-// pt[b][l][n] = floor((Q m + floor(T/2)) / T) mod q_l = (floor(T/2) - r) T^-1 mod q_l, r = (Q m + floor(T/2)) mod T (Q = 0 mod q_l), m = coeffs[b][n] mod T.
+// ---- slot map (include/mkhe.h, "BFV slot map"; no reference counterpart): coeffs_out = slots_to_coeffs(map(coeffs_to_slots(coeffs_in))) for
+// out_slot[i] = mult[i] * in_slot[index[i]] mod T.  After the forward stages position p holds slot pos[p], so in positions the map is
+//     y[p] = mult[pos[p]] * x[src[p]],   src[p] = pos^-1[index[pos[p]]],
+// and the prepared map (Context::bfv_slot_map_prepare) is one word per position: src[p] in the low 32 bits and, above it, the Shoup companion
+// floor(m 2^32 / T) of m = mult[pos[p]] mod T.  The multiplier itself is not stored: m = ceil(companion * T / 2^32), one multiplication.  The kernels read
+// position (word & (N - 1)) whatever the word holds, and write values below T whatever it holds.
+struct BfvSlotMap {
+    const u64* in;          // coeffs uint64 [count][N], any 64-bit value (taken mod T)
+    u64* out;               // coeffs uint64 [count][N], < T; may be in
+    const u64* map;         // [N], as above
+    const uint2 *w, *winv;  // [N/2]: omega^k, omega^-k with companions
+    const uint2 *twist, *itwist;    // [N]: psi^k, psi^-k N^-1 with companions
+    int logn;
+    BfvT t;
+};
+// single-workgroup form, N = 2^logn at most the tile: one launch, one workgroup per message, the transform pair and the gather on one tile in LDS
+void launch_bf_slot_map(const BfvSlotMap& a, int count, hipStream_t st);
+// two-launch form: dst[b][p] = src[b][map[p] & (n - 1)] * m_p mod T between the forward and the inverse launches, over the 32-bit work buffers
+void launch_bf_slot_gather(const u32* src, u32* dst, const u64* map, int n, u32 T, int count, hipStream_t st);
+
+// pt[b][l][n] = floor((Q m + floor(T/2)) / T) mod q_l =(floor(T/2) - r) T^-1 mod q_l, r = (Q m + floor(T/2)) mod T (Q = 0 mod q_l), m = coeffs[b][n] mod T.
 // One thread per coefficient, looping over the limbs.
 void launch_bf_scale_up(int count, const u64* coeffs, u64* pt, const BfvScale& sc, hipStream_t st);
 

@@ -92,7 +92,63 @@ template <bool INV> __global__ void __launch_bounds__(1024) bf_ntt_kernel(BfvNtt
     }
 }
 
-bool bf_ntt_big_lds() { return tile_request_lds(&bf_ntt_kernel<false>, &bf_ntt_kernel<true>, (int)sizeof(u32) << BF_TILE_LOG_BIG); }
+// ---- slot map (bfv_kernels.h).  The pair of entry e: the companion travels, the multiplier is recovered from it (w = ceil(w' T / 2^32), exact for
+// every w < T; any other 32-bit w' gives some w <= T, and the Shoup product of a canonical value then stays below 2T before its one subtraction).
+__device__ __forceinline__ uint2 bf_map_pair(u64 e, u32 T) { return uint2{hi32((e >> 32) * T + 0xffffffffull), hi32(e)}; }
+
+// One workgroup = one message: twist-load, forward stages, gather, multiply, inverse stages, twist-store; nothing intermediate leaves LDS.  The tile
+// may fill LDS, so the gather has no second buffer: every thread reads its sources into registers, the workgroup takes a barrier, every thread
+// writes the products to its own elements.  The gathered position is masked to the tile whatever the map holds.
+constexpr int BF_MAP_EPT = 32;          // elements per thread at the largest tile (2^15 points, 1024 threads); smaller tiles have 16 or fewer
+
+__global__ void __launch_bounds__(1024) bf_slot_map_kernel(BfvSlotMap a) {
+    extern __shared__ uint4 bf_lds[];
+    u32* s = reinterpret_cast<u32*>(bf_lds);
+    const int n = 1 << a.logn, b = blockIdx.y;
+    const u32 T = a.t.T;
+    const TilePass p{a.logn, a.logn, 0, 1, 1};
+    const TileGeom ge = TileGeom::of(p);
+    for (int l = threadIdx.x; l < n; l += blockDim.x) s[BfTr::swz(l)] = bf_mul(bf_reduce64(a.in[(long)b * n + l], a.t), a.twist[l], T);
+    __syncthreads();
+    tile_stages<false, BfTr>(s, a.w, p, ge, T);
+    u32 v[BF_MAP_EPT];
+#pragma unroll
+    for (int k = 0; k < BF_MAP_EPT; ++k) {
+        const int l = threadIdx.x + k * blockDim.x;
+        if (l < n) v[k] = s[BfTr::swz((int)((u32)a.map[l] & (u32)(n - 1)))];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < BF_MAP_EPT; ++k) {
+        const int l = threadIdx.x + k * blockDim.x;
+        if (l < n) s[BfTr::swz(l)] = bf_mul(v[k], bf_map_pair(a.map[l], T), T);
+    }
+    __syncthreads();
+    tile_stages<true, BfTr>(s, a.winv, p, ge, T);
+    for (int l = threadIdx.x; l < n; l += blockDim.x) a.out[(long)b * n + l] = bf_mul(s[BfTr::swz(l)], a.itwist[l], T);
+}
+void launch_bf_slot_map(const BfvSlotMap& a, int count, hipStream_t st) {
+    const TilePass p{a.logn, a.logn, 0, 1, 1};
+    const TileLaunch l = tile_launch_shape(p, count, BfTr::EPT, sizeof(u32));
+    hipLaunchKernelGGL(bf_slot_map_kernel, l.grid, l.block, l.lds, st, a);
+}
+
+// the gather and the product of the two-launch form, over the work buffers in global memory: one thread per position
+__global__ void __launch_bounds__(256) bf_slot_gather_kernel(const u32* __restrict__ src, u32* __restrict__ dst, const u64* __restrict__ map, int n, u32 T) {
+    const int l = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (l >= n) return;
+    const u64 e = map[l];
+    dst[(long)b * n + l] = bf_mul(src[(long)b * n + (int)((u32)e & (u32)(n - 1))], bf_map_pair(e, T), T);
+}
+void launch_bf_slot_gather(const u32* src, u32* dst, const u64* map, int n, u32 T, int count, hipStream_t st) {
+    hipLaunchKernelGGL(bf_slot_gather_kernel, dim3((n + 255) / 256, count), dim3(256), 0, st, src, dst, map, n, T);
+}
+
+bool bf_ntt_big_lds() {
+    const int bytes = (int)sizeof(u32) << BF_TILE_LOG_BIG;
+    const bool ntt = tile_request_lds(&bf_ntt_kernel<false>, &bf_ntt_kernel<true>, bytes);
+    return tile_request_lds(&bf_slot_map_kernel, &bf_slot_map_kernel, bytes) && ntt;
+}
 
 void launch_bf_ntt(bool inverse, const BfvNtt& a, int count, hipStream_t st) {
     const TileLaunch l = tile_launch_shape(a.p, count, BfTr::EPT, sizeof(u32));

@@ -28,6 +28,10 @@ struct BfvRefreshArgs : StreamKey {
 // limb: the limb is in the grid, so that a thread holds 8 Horner accumulators and the 8 words of one stream, not 8 x W words; the blocks are
 // recomputed per limb.  Neither A nor e ever exists in memory.  N is a multiple of 8, count <= 65535.
 void launch_bfv_refresh_finish(const BfvRefreshArgs& a, int count, u64* share, const u64* acc, u64* pt, const BfvScale& sc, hipStream_t st);
+// The compile-time variant of the same kernel body for mkhe_bfv_e2s_share (bfv_e2s_finish_kernel): the same streams, blocks and share;
+//   secret[b][n] = (T - A_b[n]) mod T                                               [count][N] over Z_T, the caller's; written by the limb-0 row only
+// and no plaintext.  up(secret) is the pt of the call above.
+void launch_bfv_e2s_finish(const BfvRefreshArgs& a, int count, u64* share, const u64* acc, u64* secret, const BfvScale& sc, hipStream_t st);
 
 // R = (c0[b] + sum_i sh[i][b]) mod Q by its residues (as share_merge_kernel), w = down(R) (its Garner digits into dig [count][limbs][N], Horner mod
 // T: bf_scale_down of bfv_kernels.h), then out[b] polynomial 0 = up(w) + sum_i polynomial 0 of re[i * count + b] under every modulus, polynomial

@@ -12,8 +12,10 @@ namespace mkhe {
 // MForm(T^-1 mod q_j).  The flood is reduced by Horner over its words, high to low: f <- f 2^64 + v_w mod q_j, the first as a Montgomery product
 // with r2 = 2^128 mod q_j, one block of one stream at a time (8 accumulators and 8 words live, whatever W is); 2^(flood_bits-1) mod q_j, which
 // centres it, is wave-uniform.  The blocks are recomputed for every limb: W <= 16 blocks against the 8 W words a thread would otherwise hold.
-__global__ void __launch_bounds__(BLK_THREADS) bfv_refresh_finish_kernel(BfvRefreshArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
-                                                                         BfvScale sc) {
+// SECRET (bfv_e2s_finish_kernel, mkhe_bfv_e2s_share): pt is the caller's secret [count][N] and takes (T - A) mod T itself, over Z_T, from the limb-0 row
+// of the grid only; no plaintext is written.  The blocks drawn, their order and the share are the same.  One body, two kernels.
+template <bool SECRET> __device__ __forceinline__ void bfv_refresh_finish(const BfvRefreshArgs& a, u64* __restrict__ share, const u64* __restrict__ acc,
+                                                                          u64* __restrict__ pt, const BfvScale& sc) {
     const u32 blk = blockIdx.x * BLK_THREADS + threadIdx.x;                 // block index c: coefficients 8 c .. 8 c + 7
     if (blk >= (u32)(sc.N / 8)) return;
     const int j = blockIdx.y, b = blockIdx.z;
@@ -31,7 +33,7 @@ __global__ void __launch_bounds__(BLK_THREADS) bfv_refresh_finish_kernel(BfvRefr
     }
     const u64 tinv = sc.tinv_mont[j];
     const u32 T = sc.t.T;
-    u64 up[8], dn[8];                                                       // up(A) and up((T - A) mod T) under q_j
+    u64 up[8], dn[8];                                                       // up(A) and up((T - A) mod T) under q_j (SECRET: (T - A) mod T)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const unsigned __int128 ph = (unsigned __int128)hi[i] * T;          // below 2^96
@@ -41,8 +43,11 @@ __global__ void __launch_bounds__(BLK_THREADS) bfv_refresh_finish_kernel(BfvRefr
         bool neg;
         u64 mag = bf_scale_up_mag(sc.t, A, neg);
         up[i] = bf_scale_up_limb(mag, neg, tinv, md);
-        mag = bf_scale_up_mag(sc.t, An, neg);
-        dn[i] = bf_scale_up_limb(mag, neg, tinv, md);
+        if (SECRET) dn[i] = An;
+        else {
+            mag = bf_scale_up_mag(sc.t, An, neg);
+            dn[i] = bf_scale_up_limb(mag, neg, tinv, md);
+        }
     }
     // kind 5 mod q_j
     u64 f[8];
@@ -53,10 +58,22 @@ __global__ void __launch_bounds__(BLK_THREADS) bfv_refresh_finish_kernel(BfvRefr
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = csub(csub(v[i] + up[i], q) + f[i], q);
     st8(share, row, v);
-    st8(pt, row, dn);
+    if (!SECRET) st8(pt, row, dn);
+    else if (j == 0) st8(pt, ((long)b * sc.N) / 2 + 4 * (long)blk, dn);
+}
+__global__ void __launch_bounds__(BLK_THREADS) bfv_refresh_finish_kernel(BfvRefreshArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ pt,
+                                                                         BfvScale sc) {
+    bfv_refresh_finish<false>(a, share, acc, pt, sc);
+}
+__global__ void __launch_bounds__(BLK_THREADS) bfv_e2s_finish_kernel(BfvRefreshArgs a, u64* __restrict__ share, const u64* __restrict__ acc, u64* __restrict__ secret,
+                                                                     BfvScale sc) {
+    bfv_refresh_finish<true>(a, share, acc, secret, sc);
 }
 void launch_bfv_refresh_finish(const BfvRefreshArgs& a, int count, u64* share, const u64* acc, u64* pt, const BfvScale& sc, hipStream_t st) {
     hipLaunchKernelGGL(bfv_refresh_finish_kernel, dim3(blk_bx(sc.N), sc.limbs, count), dim3(BLK_THREADS), 0, st, a, share, acc, pt, sc);
+}
+void launch_bfv_e2s_finish(const BfvRefreshArgs& a, int count, u64* share, const u64* acc, u64* secret, const BfvScale& sc, hipStream_t st) {
+    hipLaunchKernelGGL(bfv_e2s_finish_kernel, dim3(blk_bx(sc.N), sc.limbs, count), dim3(BLK_THREADS), 0, st, a, share, acc, secret, sc);
 }
 
 // ---- bfv_refresh_merge_kernel: grid.x over the coefficients, grid.y = the item.  One thread owns coefficient n of item b through every modulus:

@@ -965,13 +965,14 @@ int mkhe_noise_norm(mkhe_ctx* ctx, int kind, int limbs, int count, const void* d
 }
 // collective refresh, for the CKKS side and for MK-BFV (every ciphertext of a BFV context that the calls take has nq limbs): under the rules of
 // distributed decryption; why_capture closes the capture message
-static Context* refresh_enter(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, const char* why_capture) {
+static Context* refresh_enter(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, const char* why_capture,
+                              const char* why_scheme = nullptr) {
     Context* c = enter(ctx, what);
     count_ok(what, count);
     if (!in) throw Error(std::string(what) + ": null argument");
     if (!bfv) batch_ok(what, count, in);
-    scheme_ok(c, what, bfv, bfv ? ": needs a BFV context (mkhe_refresh_share / mkhe_refresh_merge serve the others)"
-                                : ": not available on a BFV context (a mask mod T is another protocol)");
+    scheme_ok(c, what, bfv, why_scheme ? why_scheme : bfv ? ": needs a BFV context (mkhe_refresh_share / mkhe_refresh_merge serve the others)"
+                                                          : ": not available on a BFV context (a mask mod T is another protocol)");
     unmasked(c, what);
     if (bfv) batch_ok(what, count, in, c->nq, ": every ciphertext must have the nQ limbs of the context");
     not_captured(c, what, why_capture);
@@ -1087,6 +1088,61 @@ int mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int n
 int mkhe_bfv_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, const mkhe_ct* const* reenc,
                            mkhe_ct* const* out) {
     MKHE_TRY(refresh_merge_entry(ctx, "mkhe_bfv_refresh_merge", true, count, in, nshares, dev_shares, reenc, out))
+}
+// encryption to shares: the guard, the order of the refusals and their words are those of the refresh calls, under the new names
+int mkhe_e2s_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8], uint64_t nonce_mask,
+                   int mask_bits, void* dev_shares, int secret_limbs, void* dev_secret) {
+    MKHE_TRY({
+        const char* what = "mkhe_e2s_share";
+        const std::string w(what);
+        if (mask_bits < 0 || mask_bits > RF_MAX_BITS) throw Error(w + ": mask_bits must be 0 .. 120");
+        if (mask_bits > 0 && !key) throw Error(w + ": null key");
+        Context* c = refresh_enter(ctx, what, false, count, in, REPLAYS);
+        if (!slots || !dev_sk || !dev_shares || !dev_secret) throw Error(w + ": null argument");
+        if (secret_limbs < 1 || secret_limbs > c->nq) throw Error(w + ": secret_limbs must be 1 .. nQ");
+        need_aligned(dev_sk, what); need_aligned(dev_shares, what); need_aligned(dev_secret, what);
+        slots_ok(what, count, in, slots);
+        commit(c);
+        auto i = ct_list(ctx, in, count, what);
+        c->e2s_share(i, slots, (const u64*)dev_sk, key, nonce_mask, mask_bits, (u64*)dev_shares, secret_limbs, (u64*)dev_secret);
+    })
+}
+int mkhe_e2s_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, int limbs_out, void* dev_pt_out) {
+    MKHE_TRY({
+        const char* what = "mkhe_e2s_merge";
+        const std::string w(what);
+        Context* c = refresh_enter(ctx, what, false, count, in, UPLOADS);
+        if (!dev_pt_out) throw Error(w + ": null argument");
+        merge_shape(what, count, in, nshares);
+        if (nshares > 0 && !dev_shares) throw Error(w + ": null argument");
+        if (limbs_out < 1 || limbs_out > c->nq) throw Error(w + ": limbs_out must be 1 .. nQ");
+        need_aligned(dev_pt_out, what);
+        auto sh = share_list(dev_shares, nshares, what);
+        commit(c);
+        auto i = ct_list(ctx, in, count, what);
+        c->e2s_merge(i, sh, limbs_out, (u64*)dev_pt_out);
+    })
+}
+int mkhe_bfv_e2s_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8], uint64_t nonce_mask,
+                       int flood_bits, void* dev_shares, void* dev_secret) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_e2s_share";
+        const std::string w(what);
+        if (flood_bits < 0 || flood_bits > BRF_MAX_FLOOD) throw Error(w + ": flood_bits must be 0 .. 1024");
+        if (!key) throw Error(w + ": null key");                                // (the mask is always drawn)
+        Context* c = refresh_enter(ctx, what, true, count, in, REPLAYS, ": needs a BFV context (mkhe_e2s_share / mkhe_e2s_merge serve the others)");
+        if (!slots || !dev_sk || !dev_shares || !dev_secret) throw Error(w + ": null argument");
+        need_aligned(dev_sk, what); need_aligned(dev_shares, what); need_aligned(dev_secret, what);
+        slots_ok(what, count, in, slots);
+        commit(c, [&] {
+            c->bfv_prepare(what);                                               // T outside the encoder's preconditions: refused here
+            const int most = c->bfv_refresh_max_flood();
+            if (flood_bits > most)
+                throw Error(w + ": flood_bits must be at most bitlen(Q div 2T) - 1 = " + std::to_string(most) + " (a wider flood alone destroys the message)");
+        });
+        auto i = ct_list(ctx, in, count, what);
+        c->bfv_e2s_share(i, slots, (const u64*)dev_sk, key, nonce_mask, flood_bits, (u64*)dev_shares, (u64*)dev_secret);
+    })
 }
 // collective key switch to a recipient's public key, under the rules of distributed decryption.  The share draws from the keystream and is refused
 // inside a capture; the merge allocates nothing, uploads nothing that outlives the call and may be captured as long as it stages no table (count
@@ -1353,6 +1409,24 @@ int mkhe_bfv_encode(mkhe_ctx* ctx, int count, const void* dev_slots, void* dev_p
 }
 int mkhe_bfv_decode(mkhe_ctx* ctx, int count, const void* dev_pt, void* dev_slots) {
     MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_decode", count, dev_pt, dev_slots)->bfv_decode(count, (const u64*)dev_pt, (u64*)dev_slots); })
+}
+// slot map: the encoder's guard; prepare downloads and validates on the host (the index check is the call's own refusal, behind the guard)
+int mkhe_bfv_slot_map_prepare(mkhe_ctx* ctx, const void* dev_index, const void* dev_mult, void* dev_map) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_slot_map_prepare";
+        enter(ctx, nullptr);
+        need_aligned(dev_mult, what);
+        encoder_enter(ctx, true, what, 1, dev_index, dev_map)->bfv_slot_map_prepare((const u32*)dev_index, (const u64*)dev_mult, (u64*)dev_map);
+    })
+}
+int mkhe_bfv_slot_map(mkhe_ctx* ctx, int count, const void* dev_coeffs_in, const void* dev_map, void* dev_coeffs_out) {
+    MKHE_TRY({
+        const char* what = "mkhe_bfv_slot_map";
+        enter(ctx, nullptr);
+        if (!dev_map) throw Error(std::string(what) + ": null argument");
+        need_aligned(dev_map, what);
+        encoder_enter(ctx, true, what, count, dev_coeffs_in, dev_coeffs_out)->bfv_slot_map(count, (const u64*)dev_coeffs_in, (const u64*)dev_map, (u64*)dev_coeffs_out);
+    })
 }
 int mkhe_bfv_lift(mkhe_ctx* ctx, int count, const void* dev_coeffs, void* dev_ptmul_coeff) {
     MKHE_TRY({ encoder_enter(ctx, true, "mkhe_bfv_lift", count, dev_coeffs, dev_ptmul_coeff)->bfv_lift(count, (const u64*)dev_coeffs, (u64*)dev_ptmul_coeff); })

@@ -287,6 +287,29 @@ void Context::refresh_share(const std::vector<const Ct*>& ins, const int* slots,
     });
 }
 
+// ---- encryption to shares (include/mkhe.h, "encryption to shares"): the share chain of the refresh with its seam open.  The same product, the same
+// finish kernel -- which writes the plaintext -M into the CALLER's buffer, the party's additive share, instead of the scratch -- and no encryption.
+// Only the unmasked product is the engine's to wipe.
+void Context::e2s_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce_mask, int bits, u64* shares,
+                        int secret_limbs, u64* secret) {
+    need_unmasked("mkhe_e2s_share");
+    check_level(secret_limbs - 1);
+    const int count = (int)ins.size(), lin = ins[0]->limbs;
+    const size_t pin = (size_t)count * lin * N;
+    u64* prod = scratch(ed_w_, pin);
+    share_product(ins, slots, sk, prod);
+    RefreshMaskArgs m;
+    stream_fill(m, key, nonce_mask, bits > 0);
+    m.bits = bits;
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (2.0 * lin + secret_limbs));
+        launch_refresh_finish(m, count, shares, prod, secret, d_mods, lin, secret_limbs, N, s_);
+    }
+    wipe(m);
+    MKHE_HIP(hipMemsetAsync(prod, 0, pin * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
+}
+
 // the pointer tables of a merge in ed_tab_: [outs][polynomial 0 of ins][shares][reenc]
 Context::MergeTables Context::merge_tables(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,
                                            u64* const* outs) {
@@ -303,6 +326,20 @@ Context::MergeTables Context::merge_tables(const std::vector<const Ct*>& ins, co
 void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
                             u64* const* outs) {
     need_unmasked("mkhe_refresh_merge");
+    refresh_merge_launch(ins, shares, reenc, lout, outs);
+}
+
+// E2S, anyone's side: the merge of the refresh without its re-encryptions -- R~ alone into pt [count][lout][N]
+void Context::e2s_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, int lout, u64* pt) {
+    need_unmasked("mkhe_e2s_merge");
+    std::vector<u64*> o(ins.size());
+    for (size_t b = 0; b < o.size(); ++b) o[b] = pt + b * (size_t)lout * N;
+    refresh_merge_launch(ins, shares, {}, lout, o.data());
+}
+
+// reenc empty: no re-encryption is added and outs[b] is the one polynomial [lout][N]
+void Context::refresh_merge_launch(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
+                                   u64* const* outs) {
     check_level(lout - 1);
     const int count = (int)ins.size(), lin = ins[0]->limbs, k = (int)shares.size();
     if (!d_rf_tab_) {
@@ -322,9 +359,10 @@ void Context::refresh_merge(const std::vector<const Ct*>& ins, const std::vector
     a.garner = garner_table(); a.qmont = d_rf_tab_; a.qprod = d_rf_tab_ + (size_t)nq * nq;
     a.dig = scratch(rf_dig_, (size_t)count * lin * N);
     a.mods = d_mods; a.nq = nq; a.lin = lin; a.lout = lout; a.nshares = k; a.count = count; a.N = N;
+    a.nre = reenc.empty() ? 0 : k;
     const MergeTables t = merge_tables(ins, shares, reenc, outs);
     {
-        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (lin * (1.0 + k) + (lout > lin ? 2.0 * lin : 0.0) + lout * (1.0 + 3.0 * k)));
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * count * (lin * (1.0 + k) + (lout > lin ? 2.0 * lin : 0.0) + lout * (1.0 + 3.0 * a.nre)));
         launch_refresh_merge(a, t.ot, t.ct, t.st, t.rt, s_);
     }
     MKHE_HIP(hipGetLastError());
@@ -373,6 +411,26 @@ void Context::bfv_refresh_share(const std::vector<const Ct*>& ins, const int* sl
         launch_bfv_refresh_finish(m, count, shares, prod, pt, bf_scale(), s_);
         wipe(m);
     });
+}
+
+// E2S for MK-BFV: the same chain with bfv_e2s_finish_kernel, the SECRET variant of bfv_refresh_finish_kernel's body, which writes (T - A) mod T over Z_T into the caller's buffer
+void Context::bfv_e2s_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce_mask, int flood_bits, u64* shares,
+                            u64* secret) {
+    bf_init("mkhe_bfv_e2s_share");
+    const int count = (int)ins.size(), W = (flood_bits + 63) / 64;
+    const size_t pin = (size_t)count * nq * N;
+    u64* prod = scratch(ed_w_, pin);
+    share_product(ins, slots, sk, prod);
+    BfvRefreshArgs m;
+    stream_fill(m, key, nonce_mask);
+    m.mask = 1; m.flood_bits = flood_bits;
+    {
+        ProfScope ps(this, PROF_OTHER, 16.0 * N * count * nq + 8.0 * N * count + 64.0 * (N / 8) * count * nq * (2.0 + W));
+        launch_bfv_e2s_finish(m, count, shares, prod, secret, bf_scale(), s_);
+    }
+    wipe(m);
+    MKHE_HIP(hipMemsetAsync(prod, 0, pin * sizeof(u64), s_));
+    MKHE_HIP(hipGetLastError());
 }
 
 void Context::bfv_refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,

@@ -305,6 +305,15 @@ class Context {
     // polynomial 0 of reenc[i * count + b]; polynomial 1 + i = polynomial 1 of reenc[i * count + b].  Builds its tables at the first use.
     void refresh_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
                        u64* const* outs);
+    // encryption to shares (include/mkhe.h): the share of refresh_share, bit for bit, and its plaintext -M_b under the first secret_limbs moduli into
+    // the caller's secret [count][secret_limbs][N] instead of an encryption; the merge of refresh_merge without re-encryptions, R~ into pt
+    // [count][lout][N].  The caller (capi.hip) has checked slots, levels, limbs and the capture.
+    void e2s_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce_mask, int bits, u64* shares,
+                   int secret_limbs, u64* secret);
+    void e2s_merge(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, int lout, u64* pt);
+    // the same for MK-BFV: the share of bfv_refresh_share with mask = 1, bit for bit, and secret [count][N] <- (T - A_b) mod T over Z_T
+    void bfv_e2s_share(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u32* key, u64 nonce_mask, int flood_bits, u64* shares,
+                       u64* secret);
     // collective refresh for MK-BFV (include/mkhe.h; bfv_refresh_kernels.h), every ciphertext with nq limbs: shares [count][nq][N] <- the product of
     // decrypt_share + up(A_b) + e_b, A_b = kind 4 (mask = 0: none) and e_b = kind 5 (flood_bits wide; 0: none) of the keystream on the streams
     // b S .. b S + S - 1 of (key, nonce_mask), S = 2 + ceil(flood_bits / 64); outs[b] [2][nq][N] <- encrypt_seeded of the plaintext up(-A_b) at the
@@ -388,6 +397,11 @@ class Context {
     // consecutive items, 0 = one plaintext for all.  what = the C entry point, for the messages.
     void bfv_ct_mul_ptxt(const char* what, const std::vector<const Ct*>& ins, const u64* ptmul, long pt_stride, const std::vector<Ct*>& outs);
     void bfv_ct_add_ptxt(const char* what, int op, const std::vector<const Ct*>& ins, const u64* pt, long pt_stride, const std::vector<Ct*>& outs);
+    // slot map (bfv_kernels.h): dev_map uint64[N] <- the map out_slot[i] = mult[i] * in_slot[index[i]] by position (index uint32[N], mult uint64[N] or
+    // null = ones; downloads, validates on the host, uploads: synchronous); coeffs_out = slots_to_coeffs(map(coeffs_to_slots(coeffs_in))), one launch
+    // when one workgroup holds the polynomial, else five around bf_work_ (two buffers of 32-bit words, wiped behind the call).  out may be in.
+    void bfv_slot_map_prepare(const u32* dev_index, const u64* dev_mult, u64* dev_map);
+    void bfv_slot_map(int count, const u64* coeffs_in, const u64* dev_map, u64* coeffs_out);
     // log2 of the largest transform one workgroup does in LDS (BF_TILE_LOG_BIG, or BF_TILE_LOG_DEF when the runtime grants no more LDS), and a way
     // to lower it (BF_TILE_LOG_MIN .. the grant; 0: back to the grant) so that the two-launch form can be run at small N
     int bfv_tile();
@@ -500,6 +514,9 @@ class Context {
     // the wipe of the product, encrypt_sampled of the plaintext at lout limbs, the wipe of the plaintext
     template <class F> void refresh_share_chain(const std::vector<const Ct*>& ins, const int* slots, const u64* sk, const u64* pk, const u32* key,
                                                 u64 nonce_enc, const u64* cdt, int ncdt, int lout, u64* const* outs, double finish_bytes, F finish);
+    // the body of refresh_merge and e2s_merge (reenc empty: none is read, outs[b] is one polynomial)
+    void refresh_merge_launch(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc, int lout,
+                              u64* const* outs);
     struct MergeTables { EdTable ot, ct, st, rt; };
     MergeTables merge_tables(const std::vector<const Ct*>& ins, const std::vector<const u64*>& shares, const std::vector<const u64*>& reenc,
                              u64* const* outs);

@@ -31,6 +31,7 @@ struct RefreshMergeArgs {
     u64* dig;                      // [count][lin][N] mixed-radix digits of R
     const Mod* mods;
     int nq, lin, lout, nshares, count, N;
+    int nre;                       // re-encryptions per item: nshares, or 0 = none (mkhe_e2s_merge: re is not read, out[b] is polynomial 0 alone)
 };
 // R = (c0[b] + sum_i sh[i][b]) mod Q_l by its residues (as share_merge_kernel), its mixed-radix digits (garner_digits), R > (Q_l - 1) / 2 decided
 // on the digits (as ck_scale_down_kernel decides its sign), the digits evaluated by Horner under q_j for lin <= j < lout, Q_l mod q_j

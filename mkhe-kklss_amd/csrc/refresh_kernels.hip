@@ -70,7 +70,8 @@ void launch_refresh_finish(const RefreshMaskArgs& a, int count, u64* share, cons
 
 // ---- refresh_merge_kernel: grid.x over the coefficients, grid.y = the item.  One thread owns coefficient n of item b through every modulus: the
 // sums of the lin input limbs feed garner_digits (which stores the digits in this thread's column of the digit scratch) and, with the
-// re-encryptions added, are polynomial 0 of the output there; the lift to the moduli above is Horner over the digits.
+// re-encryptions added, are polynomial 0 of the output there; the lift to the moduli above is Horner over the digits.  nre = 0 (mkhe_e2s_merge):
+// no re-encryption is read and out[b] is the one polynomial R~ [lout][N].
 constexpr int RFM_THREADS = 256;
 
 __global__ void __launch_bounds__(RFM_THREADS) refresh_merge_kernel(RefreshMergeArgs a, EdTable out, EdTable c0, EdTable sh, EdTable re) {
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(RFM_THREADS) refresh_merge_kernel(RefreshMerge
         const u64 v = sum_shares(c[j * N + n], sh, a.nshares, ((long)b * lin + j) * N + n, q);
         if (j < lout) {
             u64 w = v;
-            for (int i = 0; i < a.nshares; ++i) w = csub(w + ed_entry(re, i * a.count + b)[j * N + n], q);
+            for (int i = 0; i < a.nre; ++i) w = csub(w + ed_entry(re, i * a.count + b)[j * N + n], q);
             o[j * N + n] = w;
         }
         return v;
@@ -107,13 +108,13 @@ __global__ void __launch_bounds__(RFM_THREADS) refresh_merge_kernel(RefreshMerge
                 v = csub(mont_mul(v, a.qmont[i * nq + j], q, md.ninv32) + mont_mul(d[i * N], md.r1, q, md.ninv32), q);
             const u64 qp = a.qprod[(lin - 1) * nq + j];                     // Q_l mod q_j
             if (neg) v = v >= qp ? v - qp : v + q - qp;
-            for (int i = 0; i < a.nshares; ++i) v = csub(v + ed_entry(re, i * a.count + b)[j * N + n], q);
+            for (int i = 0; i < a.nre; ++i) v = csub(v + ed_entry(re, i * a.count + b)[j * N + n], q);
             o[j * N + n] = v;
         }
     } else {
         for (int j = 0; j < lout; ++j) residue(j, a.mods[j]);
     }
-    for (int i = 0; i < a.nshares; ++i) {
+    for (int i = 0; i < a.nre; ++i) {
         const u64* r1 = ed_entry(re, i * a.count + b) + (long)lout * N;
         u64* o1 = o + (long)(1 + i) * lout * N;
         for (int j = 0; j < lout; ++j) o1[j * N + n] = r1[j * N + n];

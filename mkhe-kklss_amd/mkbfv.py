@@ -1325,9 +1325,271 @@ class Refresher:
         """MergeBatch of one ciphertext -> the refreshed ciphertext"""
         return self.MergeBatch([ct], shares)[0]
 
+    # -- the refresh that applies a slot map: the message comes out as slot_map.apply(message), with no rotation key and no key switch.  The map is
+    # Z_T-linear, so it commutes with the masks: every party maps its own -A before it encrypts, anyone maps the masked plaintext in the clear.
+    def ShareMapBatch(self, cts, sk, pk, flood_bits, sampler, slot_map):
+        """ShareBatch with slot_map (a SlotMap) applied to the mask that is re-encrypted: mkhe_bfv_e2s_share -> mkhe_bfv_slot_map ->
+        mkhe_bfv_scale_up -> mkhe_encrypt_seeded, on the two nonces ShareBatch takes (nonce_mask = n, nonce_enc = n + 1) -> one
+        mkrlwe.RefreshShare of count B.  With the identity map it is ShareBatch's, bit for bit.  The intermediate secret buffers are zeroed
+        behind their last use."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot RefreshShare: no ciphertext")
+        if sk.ID != pk.ID:
+            raise MkheError("Cannot RefreshShare: sk and pk belong to different parties")
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot RefreshShare: the ciphertext has no component for the id of sk")
+        if not isinstance(flood_bits, int) or not 0 <= flood_bits <= self.MaxFloodBits(1):
+            raise MkheError("Cannot RefreshShare: flood_bits must be an integer 0 .. %d" % self.MaxFloodBits(1))
+        if not isinstance(sampler, mkrlwe.DeviceSampler):
+            raise MkheError("Cannot RefreshShare: mask, flood and encryption samples are drawn on the device -- pass a DeviceSampler")
+        if not isinstance(slot_map, SlotMap):
+            raise MkheError("Cannot RefreshShare: slot_map must be a mkbfv.SlotMap")
+        B, level, ctx = len(cts), self.params.MaxLevel(), self.params.ctx
+        key, nonce_mask, nonce_enc = sampler.refresh_args()
+        out = mkrlwe.RefreshShare(self.params, sk.ID, level, level, B)
+        sec, pt = SecretShare(self.params, sk.ID, B), mkrlwe.SecretShare(self.params, sk.ID, level, B)
+        slots = (C.c_int * B)(*[ct.slot(sk.ID) for ct in cts])
+        try:
+            check(lib().mkhe_bfv_e2s_share(ctx, B, handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), key, nonce_mask, flood_bits,
+                                           out.Share.Value.devptr(), sec.Value.devptr()))
+            check(lib().mkhe_bfv_slot_map(ctx, B, sec.Value.devptr(), slot_map.devptr(), sec.Value.devptr()))
+            check(lib().mkhe_bfv_scale_up(ctx, B, sec.Value.devptr(), pt.Value.devptr()))
+            check(lib().mkhe_encrypt_seeded(ctx, level, B, pk.Value.devptr(), pt.Value.devptr(), 0, key, nonce_enc, sampler._cdt, len(sampler.cdt),
+                                            handle_array([c.h for c in out.Reenc])))
+        finally:
+            sec.wipe()
+            pt.wipe()
+        return out
+
+    def ShareMapNew(self, ct, sk, pk, flood_bits, sampler, slot_map):
+        """ShareMapBatch of one ciphertext"""
+        return self.ShareMapBatch([ct], sk, pk, flood_bits, sampler, slot_map)
+
+    def MergeMapBatch(self, cts, shares, slot_map):
+        """MergeBatch for shares made by ShareMapBatch with the same slot_map: ShareConverter.E2SMergeBatch (w = (m + sum A_i) mod T) ->
+        mkhe_bfv_slot_map -> mkhe_bfv_scale_up, added (mkhe_bfv_ct_add_ptxt) into c_0 of the sum of the re-encryptions (mkhe_ct_add over the
+        unions) -> B ciphertexts over the same ids that encrypt slot_map.apply(message).  With the identity map it is MergeBatch's, bit for bit."""
+        if not isinstance(slot_map, SlotMap):
+            raise MkheError("Cannot RefreshMerge: slot_map must be a mkbfv.SlotMap")
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot RefreshMerge: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids:
+                raise MkheError("Cannot RefreshMerge: the ciphertexts of one call must be over the same ids")
+        B, level, nq, ctx = len(cts), self.params.MaxLevel(), self.params.QCount(), self.params.ctx
+        ordered = mkrlwe.order_shares(cts[0].ids, level, B, shares)
+        if not ordered:
+            raise MkheError("Cannot RefreshMerge: ciphertexts without parties have nothing to refresh")
+        w = ShareConverter(self.params).E2SMergeBatch(cts, [sh.Share for sh in ordered])
+        pt = mkrlwe.DeviceLimbs(self.params, B, nq)
+        check(lib().mkhe_bfv_slot_map(ctx, B, w.Value.devptr(), slot_map.devptr(), w.Value.devptr()))
+        check(lib().mkhe_bfv_scale_up(ctx, B, w.Value.devptr(), pt.devptr()))
+        acc, ids = list(ordered[0].Reenc), [ordered[0].ID]
+        for sh in ordered[1:]:
+            ids = sorted(set(ids) | {sh.ID})
+            nxt = mkrlwe.batch_ciphertexts(Ciphertext, self.params, ids, level, B)
+            check(lib().mkhe_ct_binary_batch(ctx, 0, B, handle_array([c.h for c in acc]), handle_array([c.h for c in sh.Reenc]),
+                                             handle_array([c.h for c in nxt])))
+            acc = nxt
+        outs = mkrlwe.batch_ciphertexts(Ciphertext, self.params, cts[0].ids, level, B)
+        check(lib().mkhe_bfv_ct_add_ptxt(ctx, 0, B, handle_array([c.h for c in acc]), pt.devptr(), nq * self.params.N(), handle_array([c.h for c in outs])))
+        return outs
+
+    def MergeMapNew(self, ct, shares, slot_map):
+        """MergeMapBatch of one ciphertext -> the refreshed, mapped ciphertext"""
+        return self.MergeMapBatch([ct], shares, slot_map)[0]
+
 
 def NewRefresher(params):
     return Refresher(params)
+
+
+# ---- encryption to shares and back; slot maps (include/mkhe.h, "encryption to shares", "BFV slot map")
+class SecretShare(mkrlwe.SecretShare):
+    """mkrlwe.SecretShare over Z_T: coefficients uint64 [count][1][N], each below T, in the format mkhe_bfv_scale_down writes; no level.
+    Slots() is the share of the SLOTS (additive mod T slot by slot, as the transform is Z_T-linear)."""
+
+    def __init__(self, params, id, count=1):
+        super().__init__(params, id, None, count, limbs=1)
+
+    def Slots(self):
+        """-> int64 [count][N], centred, through mkhe_bfv_coeffs_to_slots"""
+        dst = mkrlwe.DeviceLimbs(self.params, self.count, 1)
+        check(lib().mkhe_bfv_coeffs_to_slots(self.params.ctx, self.count, self.Value.devptr(), dst.devptr()))
+        return dst.download().view(np.int64).reshape(self.count, self.params.N())
+
+    @classmethod
+    def FromSlots(cls, params, values, id=None):
+        """the inverse of Slots: int64 [count][N] (or [N]) -> SecretShare, through mkhe_bfv_slots_to_coeffs"""
+        z = np.asarray(values, dtype=np.int64)
+        z = z[None] if z.ndim == 1 else z
+        if z.ndim != 2 or z.shape[0] < 1 or z.shape[1] != params.N():
+            raise MkheError("mkbfv.SecretShare: expected %d slots per item, got %r" % (params.N(), z.shape))
+        src = mkrlwe.DeviceLimbs(params, len(z), 1).upload(np.ascontiguousarray(z).view(np.uint64).reshape(len(z), 1, params.N()))
+        out = cls(params, id, len(z))
+        check(lib().mkhe_bfv_slots_to_coeffs(params.ctx, len(z), src.devptr(), out.Value.devptr()))
+        return out
+
+
+class ShareConverter:
+    """HE <-> additive secret sharing over Z_T for MK-BFV, exact slot by slot.  E2S: every party runs E2SShareBatch on its own key and
+    DeviceSampler, publishes the DecryptionShare and KEEPS the SecretShare (T - A); anyone runs E2SMergeBatch, which gives the public share
+    w = (m + sum A_i) mod T.  (public + the sum of the secret shares) mod T is the message, coefficient by coefficient and -- after Slots() --
+    slot by slot, as long as the noise of the ciphertext and the floods stay below Q / (2 T) (Refresher.MaxFloodBits).  S2E: every party
+    encrypts its share (S2EShareBatch: mkhe_bfv_scale_up, then mkhe_encrypt / mkhe_encrypt_seeded), S2EMergeNew is the AddNew chain over the
+    parties' ciphertexts, and the public share, scaled up, is added to the result as a plaintext (mkhe_bfv_ct_add_ptxt)."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def MaxFloodBits(self, parties):
+        return Refresher(self.params).MaxFloodBits(parties)
+
+    def E2SShareBatch(self, cts, sk, flood_bits, sampler):
+        """The party of sk, for B ciphertexts (their id sets may differ), as ONE engine call (mkhe_bfv_e2s_share) -> (DecryptionShare to
+        publish: Refresher.ShareBatch's, bit for bit; SecretShare to keep).  One nonce of `sampler` (a DeviceSampler)."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot E2SShare: no ciphertext")
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot E2SShare: the ciphertext has no component for the id of sk")
+        if not isinstance(flood_bits, int) or not 0 <= flood_bits <= self.MaxFloodBits(1):
+            raise MkheError("Cannot E2SShare: flood_bits must be an integer 0 .. %d" % self.MaxFloodBits(1))
+        if not isinstance(sampler, mkrlwe.DeviceSampler):
+            raise MkheError("Cannot E2SShare: mask and flood are drawn on the device -- pass a DeviceSampler")
+        key, nonce = sampler.e2s_args()
+        pub = mkrlwe.DecryptionShare(self.params, sk.ID, self.params.MaxLevel(), len(cts))
+        sec = SecretShare(self.params, sk.ID, len(cts))
+        slots = (C.c_int * len(cts))(*[ct.slot(sk.ID) for ct in cts])
+        check(lib().mkhe_bfv_e2s_share(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), key, nonce,
+                                       flood_bits, pub.Value.devptr(), sec.Value.devptr()))
+        return pub, sec
+
+    def E2SMergeBatch(self, cts, shares):
+        """Anyone, for B ciphertexts over the same ids and one DecryptionShare of count B per party, in any order -> the public share, a
+        SecretShare with id None: mkhe_decrypt_merge followed by mkhe_bfv_scale_down."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot E2SMerge: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids:
+                raise MkheError("Cannot E2SMerge: the ciphertexts of one call must be over the same ids")
+        ordered = mkrlwe.order_shares(cts[0].ids, self.params.MaxLevel(), len(cts), shares)
+        pt = mkrlwe.DeviceLimbs(self.params, len(cts), self.params.QCount())
+        check(lib().mkhe_decrypt_merge(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), len(ordered),
+                                       handle_array([sh.Value.devptr() for sh in ordered]), pt.devptr()))
+        out = SecretShare(self.params, None, len(cts))
+        check(lib().mkhe_bfv_scale_down(self.params.ctx, len(cts), pt.devptr(), out.Value.devptr()))
+        return out
+
+    def _scale_up(self, share):
+        pt = mkrlwe.DeviceLimbs(self.params, share.count, self.params.QCount())
+        check(lib().mkhe_bfv_scale_up(self.params.ctx, share.count, share.Value.devptr(), pt.devptr()))
+        return pt
+
+    def S2EShareBatch(self, secret, pk, sampler):
+        """The party of pk encrypts its SecretShare under its own public key -> `count` ciphertexts over the party's id"""
+        if secret.ID is not None and secret.ID != pk.ID:
+            raise MkheError("Cannot S2EShare: the share and pk belong to different parties")
+        enc = mkrlwe.Encryptor(self.params, sampler)
+        level = self.params.MaxLevel()
+        outs = mkrlwe.batch_ciphertexts(Ciphertext, self.params, [pk.ID], level, secret.count)
+        enc._engine_encrypt(level, pk, self._scale_up(secret), False, enc._draw(None, secret.count), outs)
+        return outs
+
+    def S2EMergeNew(self, cts_by_party, public=None):
+        """The AddNew chain over the parties' ciphertexts (one each) -> one ciphertext over all their ids; public (a SecretShare of count 1):
+        scaled up and added to the result as a plaintext"""
+        cts = list(cts_by_party)
+        if not cts:
+            raise MkheError("Cannot S2EMerge: no ciphertext")
+        ev = Evaluator(self.params)
+        acc = cts[0]
+        for ct in cts[1:]:
+            acc = ev.AddNew(acc, ct)
+        if public is not None:
+            if public.count != 1:
+                raise MkheError("Cannot S2EMerge: the public share of one ciphertext expected")
+            acc = ev.AddPtxtNew(acc, self._scale_up(public))
+        return acc
+
+
+def NewShareConverter(params):
+    return ShareConverter(params)
+
+
+class SlotMap:
+    """out_slot[i] = mult[i] * in_slot[index[i]] mod T for 0 <= i < N, slots numbered as the batch encoder numbers them (two rows of N/2): any
+    permutation, replication or slot-wise scaling.  index: N integers in 0 .. N-1, any function; mult: N integers taken mod T, default all
+    ones.  The constructor checks on the host and touches no device; the device form (mkhe_bfv_slot_map_prepare) is prepared once, at the
+    first use."""
+
+    def __init__(self, params, index, mult=None):
+        N, T = params.N(), int(params.T())
+        idx = np.asarray(index)
+        if idx.shape != (N,) or idx.dtype.kind not in "iu":
+            raise MkheError("mkbfv.SlotMap: index must be %d integers, got %r of %s" % (N, idx.shape, idx.dtype))
+        if len(idx) and (int(idx.min()) < 0 or int(idx.max()) >= N):
+            raise MkheError("mkbfv.SlotMap: every index must be a slot 0 .. %d" % (N - 1))
+        if mult is None:
+            m = np.ones(N, dtype=np.uint64)
+        else:
+            m = mult if isinstance(mult, np.ndarray) else np.asarray(mult, dtype=object)      # (Python integers of any size)
+            if m.shape != (N,) or m.dtype.kind not in "iuO" or not all(isinstance(x, (int, np.integer)) for x in m.tolist()):
+                raise MkheError("mkbfv.SlotMap: mult must be %d integers, got %r of %s" % (N, m.shape, m.dtype))
+            m = np.asarray([int(x) % T for x in m.tolist()], dtype=np.uint64)
+        self.params, self.N, self.T = params, N, T
+        self.index, self.mult = idx.astype(np.int64), m
+        self._map = None
+
+    @classmethod
+    def Permutation(cls, params, perm, mult=None):
+        """out_slot[i] = in_slot[perm[i]] for a permutation perm of 0 .. N-1"""
+        p = np.asarray(perm)
+        if p.shape != (params.N(),) or p.dtype.kind not in "iu" or not np.array_equal(np.sort(p), np.arange(params.N())):
+            raise MkheError("mkbfv.SlotMap: Permutation takes a permutation of 0 .. %d" % (params.N() - 1))
+        return cls(params, p, mult)
+
+    @classmethod
+    def Rotation(cls, params, k, swap_rows=False):
+        """what RotateNew(ct, k) does to the slots: slot i + k moves to slot i within each row of N/2; swap_rows: and the rows change places
+        (ConjugateNew)"""
+        half = params.N() // 2
+        i = np.arange(params.N())
+        row = (i // half) ^ (1 if swap_rows else 0)
+        return cls(params, row * half + (i % half + int(k)) % half)
+
+    def apply(self, values):
+        """the host definition: (mult * values[index]) mod T, centred, int64 [N] (or [count][N])"""
+        v = np.asarray(values, dtype=np.int64)
+        if v.shape[-1] != self.N:
+            raise MkheError("mkbfv.SlotMap: expected %d slots, got %r" % (self.N, v.shape))
+        r = (np.mod(v, self.T).astype(np.uint64)[..., self.index] * self.mult) % np.uint64(self.T)        # both below 2^32: the product fits
+        r = r.astype(np.int64)
+        return np.where(r > self.T // 2, r - self.T, r)
+
+    def devptr(self):
+        if self._map is None:
+            N = self.N
+            words = mkrlwe.DeviceLimbs(self.params, 2, 1)                     # row 0: the index as uint32 [N] (half a row), row 1: mult
+            host = np.zeros((2, 1, N), dtype=np.uint64)
+            host[0, 0, : N // 2] = self.index.astype(np.uint32).view(np.uint64)
+            host[1, 0] = self.mult
+            words.upload(host)
+            m = mkrlwe.DeviceLimbs(self.params, 1, 1)
+            check(lib().mkhe_bfv_slot_map_prepare(self.params.ctx, words.devptr(), C.c_void_p(words.devptr().value + 8 * N), m.devptr()))
+            self._map = m
+        return self._map.devptr()
+
+    def MapCoeffs(self, secret_share):
+        """the map applied to a SecretShare (coefficients over Z_T) -> a new SecretShare of the same party: ONE engine call (mkhe_bfv_slot_map)"""
+        out = SecretShare(self.params, secret_share.ID, secret_share.count)
+        check(lib().mkhe_bfv_slot_map(self.params.ctx, secret_share.count, secret_share.Value.devptr(), self.devptr(), out.Value.devptr()))
+        return out
 
 
 class PublicKeySwitcher(mkrlwe.PublicKeySwitcher):

@@ -1247,6 +1247,36 @@ def NewRefresher(params):
     return Refresher(params)
 
 
+class ShareConverter(mkrlwe.ShareConverter):
+    """mkrlwe.ShareConverter on mkckks ciphertexts: the shares are over R_Q in the coefficient domain (a 120-bit mask does not survive a float64
+    decode, so there is no slot form), and S2E gives mkckks.Ciphertexts at `scale` -- the Scale of the ciphertexts E2S started from, which
+    the caller carries across (SecretShare.Scale is set by E2SShareBatch / E2SMergeBatch and kept by FoldPublic)."""
+
+    def _new(self, ids, level, count, like=None):
+        return mkrlwe.batch_ciphertexts(Ciphertext, self.params, ids, level, count, Scale=float(getattr(like, "Scale", 0.0) or 0.0))
+
+    def E2SShareBatch(self, cts, sk, mask_bits, sampler, level_out=None):
+        pub, sec = super().E2SShareBatch(cts, sk, mask_bits, sampler, level_out)
+        sec.Scale = list(cts)[0].ScalingFactor()
+        return pub, sec
+
+    def E2SMergeBatch(self, cts, shares, level_out=None):
+        out = super().E2SMergeBatch(cts, shares, level_out)
+        out.Scale = list(cts)[0].ScalingFactor()
+        return out
+
+    def FoldPublic(self, secret, public):
+        out = super().FoldPublic(secret, public)
+        out.Scale = secret.Scale
+        return out
+
+    MaxMaskBits = Refresher.MaxMaskBits
+
+
+def NewShareConverter(params):
+    return ShareConverter(params)
+
+
 class PublicKeySwitcher(mkrlwe.PublicKeySwitcher):
     """The collective key switch of mkrlwe.PublicKeySwitcher on mkckks ciphertexts: the result is a mkckks.Ciphertext over the recipient's id with
     the input's Scale (the message and its scale are untouched; only the noise of the shares is added: SwitchSlotBound)."""

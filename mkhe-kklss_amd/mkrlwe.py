@@ -728,6 +728,10 @@ class DeviceSampler:
         """(key, nonce) for ONE mkhe_threshold_gen_shares call: the same counter as the other calls"""
         return self._key, self._next_nonce()
 
+    def e2s_args(self):
+        """(key, nonce_mask) for ONE mkhe_e2s_share / mkhe_bfv_e2s_share call: one value of the same counter, taken under the lock"""
+        return self._key, self._next_nonce()
+
     def refresh_args(self):
         """(key, nonce_mask, nonce_enc) for ONE mkhe_refresh_share call: two values of the same counter, taken under the lock"""
         with self._lock:
@@ -1497,6 +1501,145 @@ class Refresher:
 
 def NewRefresher(params):
     return Refresher(params)
+
+
+# ---- encryption to shares and back (include/mkhe.h, "encryption to shares")
+class SecretShare:
+    """An ADDITIVE share of the plaintexts of `count` ciphertexts: a device buffer uint64 [count][limbs][N] plus the id of the party that holds
+    it (None: the public share, which anyone can compute), the level (None where the share is over Z_T: mkbfv) and the count.  A party's share
+    is as secret as its mask: it travels to nobody.  download() / upload() move it between the device and its owner's host; wipe() overwrites
+    the device buffer with zeros and then frees it."""
+
+    def __init__(self, params, id, level, count=1, limbs=None):
+        self.params, self.ID, self.count = params, id, int(count)
+        self._level = None if level is None else int(level)
+        self.Value = DeviceLimbs(params, self.count, int(limbs) if limbs is not None else self._level + 1)
+
+    def Level(self):
+        return self._level
+
+    def download(self):
+        return self.Value.download()
+
+    def upload(self, host):
+        self.Value.upload(host)
+        return self
+
+    def wipe(self):
+        v = self.Value
+        if v is not None and v.d:
+            v.upload(np.zeros((v.count, v.limbs, self.params.N()), dtype=np.uint64))
+            lib().mkhe_buf_free(self.params.ctx, v.d)
+            v.d = None
+        self.Value = None
+
+
+class ShareConverter:
+    """HE <-> additive secret sharing between parties, exact over R_Q in the coefficient domain.  E2S: every party runs E2SShareBatch on its own
+    key and DeviceSampler, publishes the DecryptionShare and KEEPS the SecretShare; anyone runs E2SMergeBatch on the published shares, which
+    gives the public share.  public + the sum of the secret shares is the plaintext of Decrypt modulo every prime of the input level, whatever
+    mask_bits is; nobody has seen it.  S2E: the party that holds the public share folds it into its own (FoldPublic: mkhe_limbs_sum) BEFORE it
+    encrypts -- a plaintext cannot be added behind the merge without an operation the ring has none of here; every party encrypts its share
+    under its own public key (S2EShareBatch), and S2EMergeNew is the AddNew chain over the parties' ciphertexts.  With the nonces of a
+    Refresher.ShareNew (e2s_args then encrypt_args take the two counter values refresh_args takes) the result is Refresher.MergeNew's, bit for bit."""
+
+    def __init__(self, params):
+        self.params = params
+
+    MaxMaskBits = staticmethod(Refresher.MaxMaskBits)
+
+    def _new(self, ids, level, count, like=None):
+        """`count` output ciphertexts over ids at level"""
+        return batch_ciphertexts(Ciphertext, self.params, ids, level, count)
+
+    def _level_out(self, level_out, who):
+        level_out = self.params.MaxLevel() if level_out is None else int(level_out)
+        if not 0 <= level_out <= self.params.MaxLevel():
+            raise MkheError("Cannot %s: level_out %d out of range" % (who, level_out))
+        return level_out
+
+    def E2SShareBatch(self, cts, sk, mask_bits, sampler, level_out=None):
+        """The party of sk, for B ciphertexts at one level (their id sets may differ), as ONE engine call (mkhe_e2s_share) -> (DecryptionShare
+        to publish: Refresher.ShareBatch's, bit for bit; SecretShare to keep: -M under the level_out + 1 first moduli, default the maximum
+        level).  mask_bits = 1 .. 120 (MaxMaskBits); 0 (no mask) is for TESTS ONLY: such a share reveals sk.  One nonce of `sampler`."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot E2SShare: no ciphertext")
+        level = cts[0].Level()
+        level_out = self._level_out(level_out, "E2SShare")
+        for ct in cts:
+            if sk.ID not in ct.ids:
+                raise MkheError("Cannot E2SShare: the ciphertext has no component for the id of sk")
+            if ct.Level() != level:
+                raise MkheError("Cannot E2SShare: the ciphertexts of one call must be at the same level")
+        if not isinstance(mask_bits, int) or not 0 <= mask_bits <= 120:
+            raise MkheError("Cannot E2SShare: mask_bits must be an integer 0 .. 120")
+        if not isinstance(sampler, DeviceSampler):
+            raise MkheError("Cannot E2SShare: the mask is drawn on the device -- pass a DeviceSampler")
+        key, nonce = sampler.e2s_args()
+        pub = DecryptionShare(self.params, sk.ID, level, len(cts))
+        sec = SecretShare(self.params, sk.ID, level_out, len(cts))
+        slots = (C.c_int * len(cts))(*[ct.slot(sk.ID) for ct in cts])
+        check(lib().mkhe_e2s_share(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), slots, sk.Value.devptr(), key, nonce, mask_bits,
+                                   pub.Value.devptr(), level_out + 1, sec.Value.devptr()))
+        return pub, sec
+
+    def E2SMergeBatch(self, cts, shares, level_out=None):
+        """Anyone, for B ciphertexts over the same ids at one level and one DecryptionShare of count B per party, in any order -> the public
+        additive share, a SecretShare with id None at level_out: the exact centred lift of c_0 + the shares.  ONE engine call (mkhe_e2s_merge)."""
+        cts = list(cts)
+        if not cts:
+            raise MkheError("Cannot E2SMerge: no ciphertext")
+        for ct in cts:
+            if ct.ids != cts[0].ids or ct.Level() != cts[0].Level():
+                raise MkheError("Cannot E2SMerge: the ciphertexts of one call must be over the same ids and at the same level")
+        level_out = self._level_out(level_out, "E2SMerge")
+        ordered = order_shares(cts[0].ids, cts[0].Level(), len(cts), shares)
+        out = SecretShare(self.params, None, level_out, len(cts))
+        check(lib().mkhe_e2s_merge(self.params.ctx, len(cts), handle_array([ct.h for ct in cts]), len(ordered),
+                                   handle_array([sh.Value.devptr() for sh in ordered]), level_out + 1, out.Value.devptr()))
+        return out
+
+    def FoldPublic(self, secret, public):
+        """the share of the party that holds the public share, with the public share added in (mkhe_limbs_sum) -> a new SecretShare of that party"""
+        if secret.count != public.count or secret.Value.limbs != public.Value.limbs:
+            raise MkheError("Cannot FoldPublic: the shares differ in count or level")
+        out = SecretShare(self.params, secret.ID, secret.Level(), secret.count, secret.Value.limbs)
+        check(lib().mkhe_limbs_sum(self.params.ctx, secret.count, secret.Value.limbs, 2,
+                                   handle_array([secret.Value.devptr(), public.Value.devptr()]), out.Value.devptr()))
+        return out
+
+    def S2EShareBatch(self, secret, pk, sampler):
+        """The party of pk encrypts its SecretShare as a plaintext under its own public key -> `count` ciphertexts over the party's id at the
+        share's level.  mkhe_encrypt_seeded with a DeviceSampler (one nonce), mkhe_encrypt with a host sampler: nothing new in the engine."""
+        if secret.ID is not None and secret.ID != pk.ID:
+            raise MkheError("Cannot S2EShare: the share and pk belong to different parties")
+        enc = Encryptor(self.params, sampler)
+        level = secret.Value.limbs - 1
+        outs = self._new([pk.ID], level, secret.count, like=secret)
+        enc._engine_encrypt(level, pk, secret.Value, False, enc._draw(None, secret.count), outs)
+        return outs
+
+    def S2EMergeNew(self, cts_by_party, public=None):
+        """The AddNew chain over the parties' ciphertexts (one each, from S2EShareBatch) -> one ciphertext over all their ids.  public must be
+        None: the public share is not an argument of the merge -- its holder folds it into its own share (FoldPublic) before S2EShareBatch."""
+        if public is not None:
+            raise MkheError("Cannot S2EMerge: the public share is folded into its holder's share (FoldPublic) before that party encrypts")
+        cts = list(cts_by_party)
+        if not cts:
+            raise MkheError("Cannot S2EMerge: no ciphertext")
+        acc = cts[0]
+        for ct in cts[1:]:
+            if ct.Level() != acc.Level():
+                raise MkheError("Cannot S2EMerge: the ciphertexts must be at the same level")
+            out = self._new(sorted(set(acc.ids) | set(ct.ids)), acc.Level(), 1, like=acc)[0]
+            check(lib().mkhe_ct_add(self.params.ctx, acc.h, ct.h, out.h))
+            acc = out
+        return acc
+
+
+def NewShareConverter(params):
+    return ShareConverter(params)
 
 
 # ---- collective public-key switch (include/mkhe.h, "collective public-key switch")
