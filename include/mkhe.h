@@ -554,7 +554,8 @@ int  mkhe_ct_expand_seeded(mkhe_ctx* ctx, int count, const uint32_t a_key[8], ui
  * key (its tests).  Between parties use mkhe_decrypt_share / mkhe_decrypt_merge below. */
 int  mkhe_partial_decrypt(mkhe_ctx* ctx, const mkhe_ct* in, int slot, const void* dev_sk, mkhe_ct* out);
 /* Decrypt decryptor.go:48-66: dev_sk[i] = the secret of the party at slot 1+i; dev_pt_out = uint64[limbs][N], canonical residues,
- * coefficient domain */
+ * coefficient domain.  More than 16 parties stage the pointer tables of the keys and the polynomials, which synchronises (and is refused inside a
+ * capture, with nothing enqueued). */
 int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, void* dev_pt_out);
 /* ---- distributed decryption: flooded decryption shares and their merge (eprint 2022/347) ----------------------------
  * mkhe_decrypt needs every secret key in one place, and the output of mkhe_partial_decrypt gives the key away.  In the protocol of the
@@ -574,7 +575,14 @@ int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, v
  * k 2^(bits-1) plus the noise of the ciphertext is below Q / (2 T).
  *
  * Rules: those of the seeded encryption.  A (key, nonce) pair serves ONE call; mkhe_decrypt_share with flood_bits > 0 is refused between
- * mkhe_capture_begin and mkhe_capture_end; both calls are refused on a context that owns a subset of the moduli; the key travels only in
+ * mkhe_capture_begin and mkhe_capture_end (a replay would repeat the keystream).  A call that draws no keystream MAY be captured as long as it
+ * stages no pointer table: refused inside a capture are mkhe_decrypt_share with flood_bits = 0 and count > 16, mkhe_decrypt_merge with count > 16
+ * or nshares > 16, and mkhe_decrypt of a ciphertext over more than 16 parties (a staged table is copied from the host and waited for, which a
+ * capturing stream cannot do).  The scratch of these calls (the products, the pointer tables) is grow-only and allocated at the first call of
+ * a shape: a call to be captured must have run once with that shape, or a larger one, BEFORE mkhe_capture_begin -- replacing a scratch block
+ * waits for the stream, which invalidates the capture, and this the engine does not check.  The same holds for the other calls of the protocol
+ * family that may be captured (mkhe_pcks_merge, mkhe_limbs_sum, mkhe_threshold_additive_key, mkhe_sample_uniform, mkhe_ct_expand_seeded).
+ * Both calls are refused on a context that owns a subset of the moduli; the key travels only in
  * the kernel arguments of one launch and its host copy there is overwritten behind the launch; messages start with the function's name;
  * a refused call has enqueued nothing and leaves the context usable.  Also refused: flood_bits outside 0 .. 62, a slot out of range,
  * ciphertexts at different levels, ciphertexts over different ids in the merge, a misaligned buffer, a NULL key with flood_bits > 0. */
@@ -582,13 +590,14 @@ int  mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, v
  * polynomial slots[b] (1 .. n_b) of in[b] and e_b is stream b of (key, nonce), kind 2 with flood_bits bits.  All in[b] are at one level; their id
  * sets may differ.  One launch set whatever count is (one forward NTT of count polynomials, one product kernel, one inverse NTT, one finish
  * kernel); the unflooded product is wiped from the engine's scratch behind the finish kernel.  1 <= count <= 65535; count > 16 stages a
- * pointer table, which synchronises. */
+ * pointer table, which synchronises (and is refused inside a capture). */
 int  mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8],
                         uint64_t nonce, int flood_bits, void* dev_shares);
 /* dev_pt_out = uint64[count][limbs][N]: pt[b] = (c_0[b] + sum_i share_i[b]) mod q_j, canonical.  All in[b] are over the same ids and at the same
  * level; nshares = the number of parties, dev_shares[i] = the buffer uint64[count][limbs][N] of the party at slot 1 + i (what that party's
  * mkhe_decrypt_share wrote for the same batch).  One streaming launch.  With flood_bits = 0 shares the result is mkhe_decrypt's, bit for bit.
- * nshares = 0 on ciphertexts without parties reduces c_0. */
+ * nshares = 0 on ciphertexts without parties reduces c_0.  count > 16 or nshares > 16 stages a pointer table, which synchronises (and is refused
+ * inside a capture). */
 int  mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int nshares, const void* const* dev_shares, void* dev_pt_out);
 /* ---- collective refresh: masked shares, re-encryption, exact lift (the interactive bootstrapping of multiparty RLWE) -----------------
  * Every MulRelin drops a level and at level 0 the evaluator stops; there is no bootstrapping here.  Parties that publish decryption shares
@@ -671,7 +680,9 @@ int  mkhe_refresh_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int 
  *
  * Rules: those of mkhe_refresh_share / mkhe_refresh_merge.  Refused: a context that is not a BFV context, or one with mkhe_ctx_set_owned; T
  * outside the encoder's preconditions; both calls between mkhe_capture_begin and mkhe_capture_end; mask other than 0 or 1; flood_bits < 0,
- * > 1024 or > bitlen(Q div 2T) - 1 (such a flood alone destroys the message); a slot out of range; an input, reenc or out that does not have nQ
+ * > 1024 or > bitlen(Q div 2T) - 1 (such a flood alone destroys the message; a BFV context holds at most 16 primes of Q, each below 2^60, so
+ * this bound is at most 960 - bitlen(2T) on every context that can be created and it, not 1024, is the one that binds: the sixteen words of a
+ * 1024-bit flood are reached by mkhe_pcks_share on a CKKS / mkrlwe chain only); a slot out of range; an input, reenc or out that does not have nQ
  * limbs; in the merge inputs over different ids, or a reenc that is not over exactly the id of its slot; an output that aliases an input; a
  * NULL key (the encryption draws its samples from it whatever mask and flood_bits are); a misaligned buffer; count outside 1 .. 65535;
  * nonce_mask == nonce_enc when mask = 1 or flood_bits > 0.  Each of the two nonces obeys the one-call rule of the seeded calls.  Messages

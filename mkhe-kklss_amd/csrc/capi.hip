@@ -899,10 +899,12 @@ int mkhe_decrypt(mkhe_ctx* ctx, const mkhe_ct* ct, const void* const* dev_sk, vo
             need_aligned(dev_sk[i], "mkhe_decrypt");
             sk[i] = (const u64*)dev_sk[i];
         }
+        if (ct->c.n > ED_INLINE) not_captured(enter(ctx, nullptr), "mkhe_decrypt", "on a ciphertext over more than 16 parties (the pointer tables are staged)");
         need(ctx)->decrypt(ct->c, sk.data(), (u64*)dev_pt_out);
     })
 }
-// distributed decryption: a share with a flood draws from the keystream and is refused inside a capture
+// distributed decryption: a share with a flood draws from the keystream and is refused inside a capture; without one the share, and the merge, may be
+// captured as long as they stage no table (count and nshares at most 16)
 static Context* ds_enter(mkhe_ctx* ctx, const char* what, int count, const mkhe_ct* const* in, const void* out, bool keystream) {
     Context* c = enter(ctx, what);
     count_ok(what, count);
@@ -911,6 +913,7 @@ static Context* ds_enter(mkhe_ctx* ctx, const char* what, int count, const mkhe_
     batch_ok(what, count, in);
     unmasked(c, what);
     if (keystream) not_captured(c, what, REPLAYS);
+    else if (count > ED_INLINE) not_captured(c, what, STAGES);
     return c;
 }
 int mkhe_decrypt_share(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, const int* slots, const void* dev_sk, const uint32_t key[8], uint64_t nonce,
@@ -933,6 +936,7 @@ int mkhe_decrypt_merge(mkhe_ctx* ctx, int count, const mkhe_ct* const* in, int n
         merge_shape("mkhe_decrypt_merge", count, in, nshares);
         if (nshares > 0 && !dev_shares) throw Error("mkhe_decrypt_merge: null argument");
         auto sh = share_list(dev_shares, nshares, "mkhe_decrypt_merge");
+        if (nshares > ED_INLINE) not_captured(c, "mkhe_decrypt_merge", STAGES);
         commit(c);
         auto i = ct_list(ctx, in, count, "mkhe_decrypt_merge");
         c->decrypt_merge(i, sh, (u64*)dev_pt_out);

@@ -25,6 +25,64 @@ def pset_ct(pset, rng, n, limbs):
     return out
 
 
+def error():
+    """the message of the last refused call of this thread"""
+    from mkhe_kklss_amd._abi import lib
+    return lib().mkhe_last_error().decode()
+
+
+def is_prime(n):
+    """Miller-Rabin with the bases that decide every n < 2^64"""
+    if n < 2:
+        return False
+    for p in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
+        if n % p == 0:
+            return n == p
+    d, s = n - 1, 0
+    while d % 2 == 0:
+        d, s = d // 2, s + 1
+    for a in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
+        x = pow(a, d, n)
+        if x in (1, n - 1):
+            continue
+        for _ in range(s - 1):
+            x = x * x % n
+            if x == n - 1:
+                break
+        else:
+            return False
+    return True
+
+
+def prime_below(limit, step=1 << 11):
+    """the largest prime = 1 mod step below limit (step = 2^11: the primes of a ring of degree 2^10)"""
+    q = (limit - 2) // step * step + 1
+    while not is_prime(q):
+        q -= step
+    return q
+
+
+# the chain of the protocol tests at N = 2^10 (tests/test_gpu_refresh.py and the files that share its world): just under 2^60 first (the class
+# of the reference's q_0), then near 2^45, then below 2^31
+CHAIN = [prime_below(1 << 60), prime_below(1 << 45), prime_below(1 << 31)]
+
+
+def digits_neighbours(lin):
+    """the x of the crafted lifts over CHAIN[:lin]: 0, 1, (Q-1)/2, (Q+1)/2, Q-1 and, for every lower mixed-radix digit, (Q-1)/2 with that digit
+    one up and one down (the top digit is that of (Q-1)/2: the comparison has to go on to the lower digits)"""
+    Q = 1
+    for q in CHAIN[:lin]:
+        Q *= q
+    h, xs, weight = (Q - 1) // 2, [], 1
+    xs = [0, 1, h, h + 1, Q - 1]
+    for q in CHAIN[: lin - 1]:
+        xs += [h + weight, h - weight]
+        weight *= q
+    top_weight = weight
+    assert all(x // top_weight == h // top_weight for x in xs[5:]) and all(0 <= x < Q for x in xs)
+    return xs, Q
+
+
 def launch_counts(ctx, fn):
     """{kernel class name: launches} of what fn() runs on the context (mkhe_prof_enable / mkhe_prof_collect)"""
     import ctypes as C

@@ -13,7 +13,7 @@ import bfv_refresh_model as B
 import device_sampler_model as M
 import harness as H
 import harness_bfv as HB
-from test_gpu_refresh import is_prime
+from gpu_common import is_prime
 
 pytestmark = pytest.mark.gpu
 

@@ -12,6 +12,7 @@ import device_sampler_model as M
 import harness as H
 import harness_bfv as HB
 import refresh_model as R
+from gpu_common import CHAIN, digits_neighbours, error, is_prime, prime_below  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,51 +22,11 @@ SENTINEL = 0x7B7B7B7B7B7B7B7B
 BITS = [0, 1, 62, 63, 64, 65, 120]
 USERS = ["user0", "user1", "user2"]
 LOGN = 10
-
-
-def is_prime(n):
-    """Miller-Rabin with the bases that decide every n < 2^64"""
-    if n < 2:
-        return False
-    for p in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
-        if n % p == 0:
-            return n == p
-    d, s = n - 1, 0
-    while d % 2 == 0:
-        d, s = d // 2, s + 1
-    for a in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
-        x = pow(a, d, n)
-        if x in (1, n - 1):
-            continue
-        for _ in range(s - 1):
-            x = x * x % n
-            if x == n - 1:
-                break
-        else:
-            return False
-    return True
-
-
-def prime_below(limit, step=1 << (LOGN + 1)):
-    """the largest prime = 1 mod 2^11 below limit"""
-    q = (limit - 2) // step * step + 1
-    while not is_prime(q):
-        q -= step
-    return q
-
-
-# just under 2^60 first (the class of the reference's q_0), then near 2^45, then below 2^31
-CHAIN = [prime_below(1 << 60), prime_below(1 << 45), prime_below(1 << 31)]
 NQ = len(CHAIN)
 
 
 def key_arg(key=KEY):
     return None if key is None else (C.c_uint32 * 8)(*key)
-
-
-def error():
-    from mkhe_kklss_amd._abi import lib
-    return lib().mkhe_last_error().decode()
 
 
 _streams = {}
@@ -238,22 +199,6 @@ def test_share_depends_on_both_nonces_and_the_key(w):
 
 
 # ------------------------------------------------------------------ the merge as a pure function
-def digits_neighbours(lin):
-    """the x of the crafted test: 0, 1, (Q-1)/2, (Q+1)/2, Q-1 and, for every lower mixed-radix digit, (Q-1)/2 with that digit one up and one down
-    (the top digit is that of (Q-1)/2: the comparison has to go on to the lower digits)"""
-    Q = 1
-    for q in CHAIN[:lin]:
-        Q *= q
-    h, xs, weight = (Q - 1) // 2, [], 1
-    xs = [0, 1, h, h + 1, Q - 1]
-    for q in CHAIN[: lin - 1]:
-        xs += [h + weight, h - weight]
-        weight *= q
-    top_weight = weight
-    assert all(x // top_weight == h // top_weight for x in xs[5:]) and all(0 <= x < Q for x in xs)
-    return xs, Q
-
-
 @pytest.mark.parametrize("k", [0, 1, 3])
 @pytest.mark.parametrize("lin,lout,count", [(1, NQ, 1), (2, NQ, 3), (3, NQ, 1), (1, 1, 1), (2, 2, 17), (2, 1, 1)])
 def test_merge_is_the_integer_model(w, lin, lout, count, k):
