@@ -264,6 +264,29 @@ int  mkhe_ct_sum(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, mkhe_ct* out);
  *   acc[j + h] = sum_k re_k[l] x_k[j + h] + im_k[l] x_k[j]
  * and on polynomial 0 only acc[0] += add_re[l], acc[h] += add_im[l].  With nb_rescale = 1 out receives what mkhe_rescale(acc, 1) would, bit for bit. */
 int  mkhe_ct_lincomb(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, const void* dev_consts, int nb_rescale, mkhe_ct* out);
+/* ==== Weighted sums, many at once: nout sums of mkhe_ct_lincomb from the same nin ciphertexts ===========
+ * No reference counterpart; the MK-CKKS twin of mkhe_bfv_ct_lincomb: every inner sum of a baby-step / giant-step polynomial evaluation from the same
+ * baby powers in one launch.
+ *   out[g] = sum_b (re[g][b] + i im[g][b]) in[b] + (add_re[g] + i add_im[g]),      g < nout,
+ * then nb_rescale (0 or 1) DivRoundByLastModulus steps.  i = X^(N/2) exactly as mkhe_ct_lincomb defines it: with h = N/2 and j < h, per limb l < Lc and
+ * for every polynomial of the ciphertexts, mod q_l and canonical,
+ *   acc_g[j]     = sum_b re[g][b][l] x_b[j]     - im[g][b][l] x_b[j + h]
+ *   acc_g[j + h] = sum_b re[g][b][l] x_b[j + h] + im[g][b][l] x_b[j]
+ * and on polynomial 0 only acc_g[0] += add_re[g][l], acc_g[h] += add_im[g][l].
+ * Shapes: 1 <= nin <= 16, 1 <= nout <= 16; all handles carry the same ids; every output has the same number of limbs L; every input has at least
+ * Lc = L + nb_rescale limbs, of which the first Lc are read (an implicit DropLevel); the outputs are distinct and alias no input.
+ * dev_consts = device uint64[nout][nin + 1][2][Lc] (mkhe_buf_alloc): row [g][0] = (add_re, add_im) as plain canonical residues, row [g][1 + b] = (re, im)
+ * in the engine's 2^64 Montgomery form, reduced.  The block is read when the call executes, and the call takes no pool allocation: it is legal between
+ * mkhe_capture_begin and mkhe_capture_end, like mkhe_ct_lincomb.
+ * Refusals: the counts (nin, nout, nb_rescale) are checked before the context is looked at; every error message starts with the name of the function;
+ * a refused call enqueues nothing and leaves the context usable.  Accepted on mkckks / mkrlwe contexts that own every modulus (not on a BFV context,
+ * whose call is mkhe_bfv_ct_lincomb, and not on a limb-sharded one).
+ * Launch set: ONE kernel, one thread per coefficient pair (j, j + h) of one component; it reads every input limb once and writes every output limb
+ * once, 8 N (1 + k) (nin Lc + nout L) bytes for k parties.  mkhe_ct_lincomb once per output reads the inputs nout times.  A pair (re, im) that is zero
+ * under limb l costs no product for that limb, an im that is zero half of them (wave-uniform branches).
+ * Bit-exactness: out[g] equals, bit for bit, mkhe_ct_lincomb(nin, in, row g of dev_consts, nb_rescale): both are the canonical residue of the same
+ * integer, zero weights included. */
+int  mkhe_ct_lincomb_multi(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int nout, const void* dev_consts, int nb_rescale, mkhe_ct* const* out);
 /* mkckks.Evaluator.MulPtxtNew body (evaluator.go:465-478) without its Rescale: every component times the plaintext
  * polynomial dev_pt = uint64[limbs][N] (coefficient domain, device), via NTT / MForm / InvNTT. */
 int  mkhe_ct_mul_ptxt(mkhe_ctx* ctx, const mkhe_ct* in, const void* dev_pt, mkhe_ct* out);

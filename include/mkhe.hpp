@@ -1048,6 +1048,11 @@ class Evaluator {
     }
     // mkhe_ct_lincomb as it is (no reference counterpart): the caller encodes dev_consts [cts.size() + 1][2][ctOut.Level() + 1 + nb_rescale] and sets ctOut.Scale
     void LinComb(const std::vector<const mkhe_ct*>& cts, const void* dev_consts, int nb_rescale, Ciphertext& ctOut) { check(mkhe_ct_lincomb(params.ctx, (int)cts.size(), cts.data(), dev_consts, nb_rescale, ctOut.h)); }
+    // mkhe_ct_lincomb_multi as it is (no reference counterpart): outs[g] = row g of mkhe_ct_lincomb for every g as one launch.  dev_consts: device
+    // uint64[outs.size()][cts.size() + 1][2][Level(outs) + 1 + nb_rescale]; the caller sets the Scale of every output
+    void LinCombs(const std::vector<const mkhe_ct*>& cts, const void* dev_consts, int nb_rescale, const std::vector<mkhe_ct*>& outs) {
+        check(mkhe_ct_lincomb_multi(params.ctx, (int)cts.size(), cts.data(), (int)outs.size(), dev_consts, nb_rescale, outs.data()));
+    }
     // mkhe_mul_relin_sum as it is (no reference counterpart): ctOut = [Rescale] sum_k ops0[k] * ops1[k] under one relinearisation tail.  Every ops0[k]
     // carries the ids of ops0[0], every ops1[k] those of ops1[0]; hoisted0 / hoisted1: one form per pair, or empty (the engine hoists that side); the
     // caller sets ctOut.Scale

@@ -586,6 +586,27 @@ static std::vector<const Swk*> swk_flat(const mkhe_ctx* ctx, const mkhe_swk* con
     for (size_t i = 0; i < n; ++i) { if (!v[i]) throw Error("mkhe: null hoisted form in a batch"); mark(ctx, v[i]); r[i] = &v[i]->s; }
     return r;
 }
+// nout sums of mkhe_ct_lincomb from the same inputs (engine_ops.hip); the counts first, then the context.  Nothing is allocated or uploaded: legal
+// inside a capture, like mkhe_ct_lincomb
+int mkhe_ct_lincomb_multi(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int nout, const void* dev_consts, int nb_rescale, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_ct_lincomb_multi";
+        const std::string w = std::string(what) + ": ";
+        if (nin < 1 || nin > CTLM_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(CTLM_MAX_IN));
+        if (nout < 1 || nout > CTLM_MAX_OUT) throw Error(w + "nout must be 1 .. " + std::to_string(CTLM_MAX_OUT));
+        if (nb_rescale != 0 && nb_rescale != 1) throw Error(w + "nb_rescale must be 0 or 1");
+        Context* c = enter(ctx, what);
+        if (!in || !dev_consts || !out) throw Error(w + "null argument");
+        scheme_ok(c, what, false, ": needs a CKKS or mkrlwe context (mkhe_bfv_ct_lincomb is the BFV call)");
+        unmasked(c, what);
+        for (int i = 0; i < nin; ++i) ct_at(in, i, what);
+        for (int i = 0; i < nout; ++i) if (!out[i]) throw Error(w + "null output in the batch");
+        commit(c);
+        auto i = ct_list(ctx, in, nin, what);
+        auto o = ct_list_out(ctx, out, nout, what);
+        c->ct_lincomb_multi(what, i, (const u64*)dev_consts, nb_rescale, o);
+    })
+}
 int mkhe_hoisted_form_batch(mkhe_ctx* ctx, int level, int nbatch, const mkhe_ct* const* cts, mkhe_swk* const* out) {
     MKHE_TRY({
         if (nbatch < 1) throw Error("mkhe_hoisted_form_batch: empty batch");

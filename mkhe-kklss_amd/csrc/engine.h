@@ -197,6 +197,10 @@ class Context {
     // outs[g] = sum_b W[g][b] ins[b] + C[g] for 1 .. 64 outputs from 1 .. 16 inputs as one launch, every handle with the same ids and nQ limbs (no
     // reference counterpart).  dev_consts: device uint64[nout][nin + 1][nQ] (poly_kernels.h, BfvLincombArgs); refusals under `what`, before the launch
     void bfv_ct_lincomb(const char* what, const std::vector<const Ct*>& ins, const u64* dev_consts, const std::vector<Ct*>& outs);
+    // outs[g] = sum_b (re[g][b] + i im[g][b]) ins[b] + (add_re[g] + i add_im[g]), then nb_rescale (0 or 1) divisions by the last modulus, for 1 .. 16
+    // outputs of one shape from 1 .. 16 inputs as one launch: row g is ct_lincomb's sum, bit for bit (no reference counterpart).  dev_consts: device
+    // uint64[nout][nin + 1][2][Lc], Lc = limbs(outs) + nb_rescale (poly_kernels.h, CtLincombMultiArgs); refusals under `what`, before the launch
+    void ct_lincomb_multi(const char* what, const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, const std::vector<Ct*>& outs);
     // plaintext linear transform (no reference counterpart; batch.hip): ptntt = MForm(NTT(pt)) for count plaintexts [limbs][N] (ptntt may be pt), and
     // the dot of both schemes for nbatch items that share masks and plaintexts: outs[b][g] = sum over the set bits i of masks[g] of ins[b][i] * P(g, i),
     // ins = [nbatch][nin] with at least L limbs, outs = [nbatch][masks.size()] with L limbs, pt = the compact block of prepared plaintexts in (g, i)

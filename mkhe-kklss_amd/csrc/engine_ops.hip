@@ -247,6 +247,46 @@ void Context::bfv_ct_lincomb(const char* what, const std::vector<const Ct*>& ins
     MKHE_HIP(hipGetLastError());
 }
 
+// outs[g] = sum_b (re[g][b] + i im[g][b]) ins[b] + (add_re[g] + i add_im[g]), then nb_rescale divisions by the last modulus, for all outputs in ONE pass
+// (launch_ct_lincomb_multi): every input limb is read once and every output limb written once, 8 N (1 + k) (nin Lc + nout L) bytes -- ct_lincomb once
+// per output reads the nin inputs nout times.  Every refusal is under `what` (the C entry point) and comes before the launch.
+void Context::ct_lincomb_multi(const char* what, const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, const std::vector<Ct*>& outs) {
+    const std::string w = std::string(what) + ": ";
+    const int nin = (int)ins.size(), nout = (int)outs.size();
+    if (nin < 1 || nin > CTLM_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(CTLM_MAX_IN));
+    if (nout < 1 || nout > CTLM_MAX_OUT) throw Error(w + "nout must be 1 .. " + std::to_string(CTLM_MAX_OUT));
+    if (nb_rescale != 0 && nb_rescale != 1) throw Error(w + "nb_rescale must be 0 or 1");
+    if (!dev_consts) throw Error(w + "null argument");
+    const Ct& o0 = *outs[0];
+    const int L = o0.limbs, Lc = L + nb_rescale, np_ = 1 + o0.n;
+    if (L < 1) throw Error(w + "cannot Rescale: input Ciphertext already at level 0");          // (Lc = 1 with a division: nothing would be left)
+    if (Lc > nq) throw Error(w + "level out of range");
+    const size_t PO = (size_t)L * N, out_words = (size_t)np_ * PO;
+    CtLincombMultiArgs a{};
+    for (int g = 0; g < nout; ++g) {
+        const Ct& o = *outs[g];
+        if (o.n != o0.n || o.ids != o0.ids) throw Error(w + "every input and output must carry the same ids");
+        if (o.limbs != L) throw Error(w + "the outputs must have the same number of limbs");
+        for (int h = 0; h < g; ++h)
+            if (o.d < outs[h]->d + out_words && outs[h]->d < o.d + out_words) throw Error(w + "the outputs must be distinct");
+        a.out[g] = o.d;
+    }
+    for (int b = 0; b < nin; ++b) {
+        const Ct& c = *ins[b];
+        if (c.n != o0.n || c.ids != o0.ids) throw Error(w + "every input and output must carry the same ids");
+        if (c.limbs < Lc) throw Error(w + "an input has fewer limbs than the sums (limbs(out) + nb_rescale)");
+        // a thread stores its words of every output while other threads still read the inputs: no overlap at all
+        for (int g = 0; g < nout; ++g)
+            if (c.d < outs[g]->d + out_words && outs[g]->d < c.d + (size_t)np_ * c.limbs * N) throw Error(w + "an output must not alias an input");
+        a.in[b] = c.d; a.in_poly[b] = (long)c.limbs * N;
+    }
+    a.out_poly = (long)PO; a.mods = d_mods; a.consts = dev_consts;
+    if (nb_rescale) { a.rescale_row = d_rescale + (size_t)(Lc - 2) * nq; a.rescale_h = a.rescale_row + (size_t)nq * nq; }
+    a.nin = nin; a.nout = nout; a.Lc = Lc; a.N = N; a.npolys = np_;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * np_ * ((double)nin * Lc + (double)nout * L)); launch_ct_lincomb_multi(a, s_); }
+    MKHE_HIP(hipGetLastError());
+}
+
 void Context::ct_mul_ptxt(const Ct& in, const u64* dev_pt, Ct& out) {
     const int L = in.limbs, np_ = 1 + in.n;
     if (out.limbs != L || out.n != in.n || out.ids != in.ids) throw Error("mkhe: ctOut shape does not match ct");

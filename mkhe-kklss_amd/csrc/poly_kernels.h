@@ -423,6 +423,26 @@ struct BfvLincombArgs {
     int nin, nout, L, N, npolys;
 };
 void launch_bfv_ct_lincomb(const BfvLincombArgs& a, hipStream_t st);
+// out[g] = sum_b (re[g][b] + i im[g][b]) in[b] + (add_re[g] + i add_im[g]), g < nout, optionally followed by ONE DivRoundByLastModulus step: nout sums of
+// CtLincombArgs from the same nin inputs in one launch (mkhe_ct_lincomb_multi; no reference counterpart) -- every inner sum of a baby-step / giant-step
+// evaluation from the same baby powers, each input word read once for all outputs.  i, the two formulas per coefficient pair and the rescale are those of
+// CtLincombArgs, and so are the words: out[g] is what launch_ct_lincomb gives for row g.  consts = [nout][nin + 1][2][Lc] on the device: row [g][0] =
+// (add_re, add_im) as plain residues, row [g][1 + b] = (re, im) in Montgomery form, all below q_l; a pair (re, im) that is zero under limb l costs no
+// product there.  rescale_row / rescale_h as in CtLincombArgs: NULL, or out[g] has Lc - 1 limbs.  Inputs may have more than Lc limbs; the outputs have
+// one shape (out_poly words per polynomial).  No output may overlap an input or another output.
+constexpr int CTLM_MAX_IN = CTLIN_MAX, CTLM_MAX_OUT = 16;
+struct CtLincombMultiArgs {
+    const u64* in[CTLM_MAX_IN];
+    long in_poly[CTLM_MAX_IN];
+    u64* out[CTLM_MAX_OUT];
+    long out_poly;
+    const Mod* mods;
+    const u64* consts;
+    const u64* rescale_row;
+    const u64* rescale_h;
+    int nin, nout, Lc, N, npolys;
+};
+void launch_ct_lincomb_multi(const CtLincombMultiArgs& a, hipStream_t st);
 // dst = MForm(src) for count polynomials of L limbs each (limb l under mods[l]); dst may be src
 void launch_mform_polys(u64* dst, const u64* src, const Mod* mods, int L, int N, int count, hipStream_t st);
 

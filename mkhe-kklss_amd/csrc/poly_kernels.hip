@@ -1330,6 +1330,130 @@ void launch_bfv_ct_lincomb(const BfvLincombArgs& a, hipStream_t st) {
     else if (a.nin > 4) hipLaunchKernelGGL(bfv_ct_lincomb_kernel<8>, grid, blk, 0, st, a);
     else hipLaunchKernelGGL(bfv_ct_lincomb_kernel<4>, grid, blk, 0, st, a);
 }
+// Weighted sums of whole ciphertexts with complex weights (CtLincombMultiArgs): ct_lincomb_kernel's sums in the register scheme of bfv_ct_lincomb_kernel.
+// One thread per coefficient pair (j, j + N/2) of one polynomial, lanes on consecutive j, the limb -- with it the modulus and every weight -- wave-uniform
+// (scalar loads), limbs dealt to gridDim.z groups as in ct_lincomb_kernel.  The thread loads its pair of the nin inputs ONCE per limb into registers (NI =
+// 4, 8 or 16 slots of four VGPRs) and then walks the outputs: per output two 128-bit accumulators take the lincomb_term products (a zero im costs half
+// of them, a pair (re, im) that is zero under the limb is a skipped scalar branch) and are reduced once.  At most 2 * CTLM_MAX_IN = 32 products per
+// accumulator: what redc128 accepts for q < 2^60, as in ct_lincomb_kernel; a skipped term would have added zero, so the words are that kernel's.
+// With a rescale (NO > 0) the rounded top-limb residues t0[g], t1[g] of ALL outputs are formed first and stay in registers while the thread walks its
+// limb group: 2 NO values of two VGPRs beside the 2 NI inputs.  NO = 4, 8 or 16 by nout is a template argument, so that a launch with few outputs does
+// not pay the registers of sixteen.  The output loop is rolled in both paths, like bfv_ct_lincomb_kernel's; with a rescale t is a ring that turns once
+// per output (see below), so that it is indexed statically all the same.
+static_assert(CTLM_MAX_IN <= 16, "ct_lincomb_multi_kernel: 2 * CTLM_MAX_IN products must stay within the 32 that redc128 accepts for q < 2^60");
+static_assert(CTLM_MAX_OUT <= 16, "ct_lincomb_multi_kernel: NO is 4, 8 or 16");
+typedef const __attribute__((address_space(4))) CtLincombMultiArgs* ctlm_kargs;
+template <int NI, int NO>
+__global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombMultiArgs a) {
+    ctlm_kargs ka = (ctlm_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    const int half = a.N >> 1, j = blockIdx.x * PW_THREADS + threadIdx.x, p = blockIdx.y, top = a.Lc - 1;
+    if (j >= half) return;
+    const sc_u64 cs = (sc_u64)a.consts;
+    const bool constant_term = p == 0 && j == 0;
+    const long row = 2L * (a.nin + 1) * a.Lc;
+    u64 xa[NI], xb[NI];
+    // this pair of every input under limb l
+    // (a wave-uniform base per input and the two lane offsets shared by all of them: 2 address VGPRs, not 4 NI)
+    const unsigned ja = (unsigned)j, jb = (unsigned)(j + half);
+    auto load = [&](int l) {
+#pragma unroll
+        for (int b = 0; b < NI; ++b) {
+            xa[b] = 0; xb[b] = 0;
+            if (b < a.nin) { const u64* x = ka->in[b] + ((long)p * ka->in_poly[b] + (long)l * a.N); xa[b] = x[ja]; xb[b] = x[jb]; }
+        }
+    };
+    // the canonical sums of output g under limb l from the loaded pairs
+    auto sums = [&](int g, int l, const Mod& md, u64& v0, u64& v1) {
+        const sc_u64 w = cs + g * row + l;
+        u64 h0 = 0, l0 = 0, h1 = 0, l1 = 0;
+        // NI = 16 (two or three resident waves per SIMD): the weights of eight inputs are fetched together, ahead of the branches that skip zero terms
+        // (the last chunk repeats the last input, whose copies are skipped) -- one wait per chunk instead of one scalar round trip per term, which so
+        // few waves cannot hide: 530 -> 386 us at 15 x 15 sums of six limbs.  NI = 4 and 8 have the waves and fetch term by term
+        // (chunks of eight there cost SGPR spills and 6 % at 7 x 7)
+        constexpr int CH = NI > 8 ? 8 : 1;
+#pragma unroll
+        for (int b0 = 0; b0 < NI; b0 += CH) {
+            u64 re[CH], im[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int bb = b0 + u < a.nin ? b0 + u : a.nin - 1;
+                re[u] = w[(long)(2 * bb + 2) * a.Lc]; im[u] = w[(long)(2 * bb + 3) * a.Lc];
+            }
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+                if (b0 + u < a.nin && (re[u] | im[u])) lincomb_term(xa[b0 + u], xb[b0 + u], re[u], im[u], md.q, h0, l0, h1, l1);
+        }
+        v0 = redc128(h0, l0, md); v1 = redc128(h1, l1, md);
+        if (constant_term) { v0 = csub(v0 + w[0], md.q); v1 = csub(v1 + w[a.Lc], md.q); }
+    };
+    u64 v0, v1;
+    if constexpr (NO == 0) {
+        for (int l = blockIdx.z; l <= top; l += gridDim.z) {
+            const Mod md = load_mod((sc_mod)a.mods + l);
+            load(l);
+            for (int g = 0; g < a.nout; ++g) {
+                sums(g, l, md, v0, v1);
+                u64* d = ka->out[g] + ((long)p * a.out_poly + (long)l * a.N);
+                d[ja] = v0; d[jb] = v1;
+            }
+        }
+    } else {
+        // DivRoundByLastModulus as ct_lincomb_kernel restates it
+        const Mod mt = load_mod((sc_mod)a.mods + top);
+        const u64 h = (mt.q - 1) >> 1;
+        // t is a ring of registers: iteration g of a rolled loop uses slot 0, then every slot moves down by one and slot 0 goes to the end, so that
+        // after NO iterations (those at and above nout only turn the ring) t[g] is back in slot g.  The loop body exists once -- unrolled NO times it
+        // was NO * NI terms of code per limb, beyond the instruction cache at sixteen by sixteen -- and no slot is indexed by a run-time value
+        u64 t0[NO] = {}, t1[NO] = {};
+        auto turn =[&](u64 n0, u64 n1) {
+#pragma unroll
+            for (int u = 0; u + 1 < NO; ++u) { t0[u] = t0[u + 1]; t1[u] = t1[u + 1]; }
+            t0[NO - 1] = n0; t1[NO - 1] = n1;
+        };
+        load(top);
+#pragma unroll 1
+        for (int g = 0; g < NO; ++g) {
+            u64 n0 = 0, n1 = 0;
+            if (g < a.nout) { sums(g, top, mt, v0, v1); n0 = csub(v0 + h, mt.q); n1 = csub(v1 + h, mt.q); }
+            turn(n0, n1);                         // (slot NO - 1 now, slot g after the NO - 1 - g turns that follow)
+        }
+        for (int l = blockIdx.z; l < top; l += gridDim.z) {
+            const Mod md = load_mod((sc_mod)a.mods + l);
+            const u64 hneg = md.q - ((sc_u64)a.rescale_h)[l], rp = md.q - ((sc_u64)a.rescale_row)[l];
+            load(l);
+#pragma unroll 1
+            for (int g = 0; g < NO; ++g) {
+                const u64 c0 = t0[0], c1 = t1[0];
+                if (g < a.nout) {
+                    sums(g, l, md, v0, v1);
+                    u64* d = ka->out[g] + ((long)p * a.out_poly + (long)l * a.N);
+                    d[ja] = mont_mul(c0 + hneg + md.q2 - v0, rp, md.q, md.ninv32);
+                    d[jb] = mont_mul(c1 + hneg + md.q2 - v1, rp, md.q, md.ninv32);
+                }
+                turn(c0, c1);
+            }
+        }
+    }
+}
+template <int NI> static void launch_ctlm_no(const CtLincombMultiArgs& a, dim3 grid, dim3 blk, hipStream_t st) {
+    if (!a.rescale_row) hipLaunchKernelGGL((ct_lincomb_multi_kernel<NI, 0>), grid, blk, 0, st, a);
+    else if (a.nout > 8) hipLaunchKernelGGL((ct_lincomb_multi_kernel<NI, 16>), grid, blk, 0, st, a);
+    else if (a.nout > 4) hipLaunchKernelGGL((ct_lincomb_multi_kernel<NI, 8>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((ct_lincomb_multi_kernel<NI, 4>), grid, blk, 0, st, a);
+}
+void launch_ct_lincomb_multi(const CtLincombMultiArgs& a, hipStream_t st) {
+    const int lout = a.rescale_row ? a.Lc - 1 : a.Lc;
+    if (a.nin < 1 || a.nin > CTLM_MAX_IN || a.nout < 1 || a.nout > CTLM_MAX_OUT || a.npolys < 1 || a.npolys > 65535 || lout < 1 || (a.N & 1))
+        throw std::runtime_error("mkhe: launch_ct_lincomb_multi: bad shape");
+    const int bx = ((a.N >> 1) + PW_THREADS - 1) / PW_THREADS;
+    // limb groups as in launch_ct_lincomb: until every SIMD of the chip has four waves, at most one group per output limb
+    const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys;
+    const int groups = (int)std::min<long>(lout, (fill + threads - 1) / threads);
+    const dim3 grid(bx, a.npolys, groups), blk(PW_THREADS);
+    if (a.nin > 8) launch_ctlm_no<16>(a, grid, blk, st);
+    else if (a.nin > 4) launch_ctlm_no<8>(a, grid, blk, st);
+    else launch_ctlm_no<4>(a, grid, blk, st);
+}
 __global__ void __launch_bounds__(PW_THREADS) mform_polys_kernel(u64* dst, const u64* src, const Mod* mods, int L, int N) {
     const int l = blockIdx.y;
     const Mod md = mods[l];

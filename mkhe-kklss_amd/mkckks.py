@@ -369,19 +369,50 @@ class Evaluator:
         if len(terms) > LINCOMB_MAX:
             raise MkheError("LinCombNew: at most %d non-zero weights per call" % LINCOMB_MAX)
         s_mid = scale * float(params.Q[l]) if rescale else scale
-        consts = np.zeros((len(terms) + 1, 2, l + 1), dtype=np.uint64)
-        for i, q in enumerate(params.Q[: l + 1]):
-            consts[0, 0, i], consts[0, 1, i] = scaleUpExact(const.real, s_mid, q) % q, scaleUpExact(const.imag, s_mid, q) % q
-            for k, (c, w) in enumerate(terms):
-                ratio = s_mid / c.Scale
-                consts[k + 1, 0, i] = ((scaleUpExact(w.real, ratio, q) % q) << 64) % q              # MForm
-                consts[k + 1, 1, i] = ((scaleUpExact(w.imag, ratio, q) % q) << 64) % q
-        n = params.N()
-        buf = mkrlwe.DeviceLimbs(params, 1, -(-consts.size // n))
-        buf.upload(np.concatenate([consts.ravel(), np.zeros(buf.words - consts.size, dtype=np.uint64)]).reshape(1, buf.limbs, n))
+        buf = _upload_consts(params, lincomb_consts(params.Q[: l + 1], s_mid, const, [c.Scale for c, _ in terms], [w for _, w in terms]))
         out = NewCiphertext(params, cts[0].IDSet(), l - (1 if rescale else 0), scale, zero=False)
         check(lib().mkhe_ct_lincomb(params.ctx, len(terms), handle_array([c.h for c, _ in terms]), buf.devptr(), 1 if rescale else 0, out.h))
         return out
+
+    def LinCombsNew(self, cts, weight_rows, consts, scales=None, rescale=True, level=None):
+        """[sum_b weight_rows[g][b] * cts[b] + consts[g] for every g] as ONE engine call (mkhe_ct_lincomb_multi) with ONE constants upload: 1 to 16 rows
+        of complex weights over the same ciphertexts, one complex constant each.  Row g follows the rules of LinCombNew -- weight b encoded at S_mid_g /
+        cts[b].Scale, the result at Scale == scales[g] exactly (one float for all rows, or one per row; default params.Scale()) -- and equals
+        LinCombNew(cts, weight_rows[g], consts[g], scale=scales[g], rescale=rescale, level=level) bit for bit.  All rows share the work level and
+        `rescale`.  A ciphertext whose weight is zero in every row is dropped (at most 16 may remain); zeros inside the table stay, the kernel skips
+        them.  MkheError before any engine call on a shape error.  Not inside a graph capture (the constants are uploaded here)."""
+        params = self.params
+        cts, rows, consts = list(cts), [[complex(w) for w in r] for r in weight_rows], [complex(c) for c in consts]
+        if not cts:
+            raise MkheError("LinCombsNew: at least one ciphertext")
+        if not rows or len(rows) > LINCOMBS_MAX_OUT or len(rows) != len(consts):
+            raise MkheError("LinCombsNew: 1 to %d rows of weights per call, one constant per row" % LINCOMBS_MAX_OUT)
+        if any(len(r) != len(cts) for r in rows):
+            raise MkheError("LinCombsNew: one weight per ciphertext in every row")
+        if any(c.ids != cts[0].ids for c in cts):
+            raise MkheError("LinCombsNew: the ciphertexts must carry the same ids")
+        lmin = min(c.Level() for c in cts)
+        l = lmin if level is None else int(level)
+        if l > lmin or l < 0:
+            raise MkheError("LinCombsNew: the work level must lie between 0 and the lowest level of the ciphertexts")
+        if rescale and l < 1:
+            raise MkheError("cannot Rescale: input Ciphertext already at level 0")
+        if scales is None or np.ndim(scales) == 0:
+            scales = [params.Scale() if scales is None else float(scales)] * len(rows)
+        scales = [float(s) for s in scales]
+        if len(scales) != len(rows):
+            raise MkheError("LinCombsNew: one scale for all rows, or one per row")
+        keep = [b for b in range(len(cts)) if any(r[b] != 0 for r in rows)] or [0]
+        if len(keep) > LINCOMB_MAX:
+            raise MkheError("LinCombsNew: at most %d ciphertexts with a non-zero weight per call" % LINCOMB_MAX)
+        Q = params.Q[: l + 1]
+        block = np.stack([lincomb_consts(Q, s * float(params.Q[l]) if rescale else s, c, [cts[b].Scale for b in keep], [r[b] for b in keep])
+                          for r, c, s in zip(rows, consts, scales)])
+        buf = _upload_consts(params, block)
+        outs = [NewCiphertext(params, cts[0].IDSet(), l - (1 if rescale else 0), s, zero=False) for s in scales]
+        check(lib().mkhe_ct_lincomb_multi(params.ctx, len(keep), handle_array([cts[b].h for b in keep]), len(rows), buf.devptr(), 1 if rescale else 0,
+                                          handle_array([o.h for o in outs])))
+        return outs
 
     def AddConstNew(self, ct, c):
         """ct + c for a complex constant c: the weight 1 at ratio 1 is the integer 1, so the ciphertext part is unchanged bit for bit"""
@@ -402,11 +433,29 @@ class Evaluator:
             res.Scale = float(scale)
         return res
 
-    def EvaluatePolyNew(self, ct, coeffs, rlkSet, scale=None):
+    def MulRelinRawNew(self, op0, op1, rlkSet):
+        """the relinearised product at level min(levels) with Scale = the product of the scales and NO Rescale (a node of a Chebyshev recurrence folds
+        the division into the LinCombNew that follows it)"""
+        level = min(op0.Level(), op1.Level())
+        res = NewCiphertext(self.params, op0.IDSet() | op1.IDSet(), level, op0.ScalingFactor() * op1.ScalingFactor(), zero=False)
+        self.ksw.MulAndRelinHoisted(op0, op1, None, None, rlkSet, res, rescaled=False)
+        return res
+
+    def EvaluatePolyNew(self, ct, coeffs, rlkSet, scale=None, fused=False):
         """sum_k coeffs[k] * ct^k (monomial basis, real or complex coefficients, degree 1 .. 63) by baby steps and giant steps (poly_eval_plan): the result
         has Scale == scale (default params.Scale()) exactly and level ct.Level() - (ceil(log2(degree + 1)) + 1); MkheError before any engine call when
-        that is below 0."""
-        return evaluate_poly(self, ct, coeffs, rlkSet, scale)
+        that is below 0.  fused=True: the inner sums of the giant products come from ONE LinCombsNew instead of one LinCombNew each -- the same
+        ciphertext bit for bit."""
+        return evaluate_poly(self, ct, coeffs, rlkSet, scale, fused)
+
+    def EvaluateChebyshevNew(self, ct, coeffs, interval, rlkSet, scale=None, fused=True):
+        """sum_k coeffs[k] * T_k((2 x - a - b) / (b - a)) for the slots x of ct in the real interval (a, b) = interval (Chebyshev basis, degree 1 .. 255;
+        chebyshev_approx gives the coefficients of a function): the change of variable (one LinCombNew and one level, skipped for (-1, 1)), the powers
+        T_k by T_(a'+b') = 2 T_a' T_b' - T_|a'-b'| on the schedule of poly_eval_plan, the inner sums of chebyshev_blocks, the giant products.  The
+        result has Scale == scale (default params.Scale()) exactly and level ct.Level() - (change of variable: 0 or 1) - (ceil(log2(degree + 1)) + 1);
+        MkheError before any engine call when that is below 0, on the zero polynomial or when a >= b.  fused=True: the inner sums of the giant products
+        are ONE LinCombsNew; fused=False: one LinCombNew each, the same ciphertext bit for bit."""
+        return evaluate_chebyshev(self, ct, coeffs, interval, rlkSet, scale, fused)
 
     def LinearTransformNew(self, ct, lt, rkSet, fused=True):
         """M z for the cleartext diagonals of `lt` (LinearTransform): sum_g rot_g(sum_b d'_(g,b) (.) rot_b ct) with one Rescale, the result at level
@@ -418,7 +467,29 @@ class Evaluator:
 
 MULRELIN_SUM_MAX = 16     # pairs per mkhe_mul_relin_sum call (csrc/poly_kernels.h, TSUM_MAX_K)
 LINCOMB_MAX = 16          # ciphertexts per mkhe_ct_lincomb call (csrc/poly_kernels.h, CTLIN_MAX)
+LINCOMBS_MAX_OUT = 16     # rows per mkhe_ct_lincomb_multi call (csrc/poly_kernels.h, CTLM_MAX_OUT)
+CHEBYSHEV_MAX_DEGREE = 255
 PolyEvalPlan = collections.namedtuple("PolyEvalPlan", "degree m g products depth")
+
+
+def lincomb_consts(Q, s_mid, const, scales, weights):
+    """One constant block of mkhe_ct_lincomb, uint64 [n + 1][2][len(Q)], a pure function: row 0 = the complex constant at s_mid as plain residues, row
+    1 + k = weights[k] at s_mid / scales[k] in Montgomery form (scaleUpExact, the rounding of the reference's constants)."""
+    const = complex(const)
+    out = np.zeros((len(weights) + 1, 2, len(Q)), dtype=np.uint64)
+    for i, q in enumerate(Q):
+        out[0, 0, i], out[0, 1, i] = scaleUpExact(const.real, s_mid, q) % q, scaleUpExact(const.imag, s_mid, q) % q
+        for k, (s, w) in enumerate(zip(scales, weights)):
+            w, ratio = complex(w), s_mid / s
+            out[k + 1, 0, i] = ((scaleUpExact(w.real, ratio, q) % q) << 64) % q              # MForm
+            out[k + 1, 1, i] = ((scaleUpExact(w.imag, ratio, q) % q) << 64) % q
+    return out
+
+
+def _upload_consts(params, block):
+    n = params.N()
+    buf = mkrlwe.DeviceLimbs(params, 1, -(-block.size // n))
+    return buf.upload(np.concatenate([block.ravel(), np.zeros(buf.words - block.size, dtype=np.uint64)]).reshape(1, buf.limbs, n))
 
 
 def poly_eval_plan(degree):
@@ -438,8 +509,24 @@ def poly_eval_plan(degree):
     return PolyEvalPlan(degree, m, g, products, depth)
 
 
-def evaluate_poly(ev, ct, coeffs, rlkSet, scale=None):
-    """Evaluator.EvaluatePolyNew on any evaluator with params, MulRelinOnceNew, LinCombNew and SumNew.  p(X) = sum_i inner_i(X) * X^(m i), inner_i = sum_j
+def _giant_parts(ev, babies, rows, consts, taus, level, fused):
+    """the inner sums that meet a giant power: row i = sum_j rows[i][j] * babies[j] + consts[i], rescaled from `level` onto (level - 1, taus[i]).  fused: ONE
+    LinCombsNew over the babies that some row uses; otherwise one LinCombNew per row over the babies that row uses -- the same ciphertexts bit for bit"""
+    if not rows:
+        return []
+    if fused:
+        cols = [j for j in range(len(babies)) if any(r[j] != 0 for r in rows)] or [0]
+        return ev.LinCombsNew([babies[j] for j in cols], [[r[j] for j in cols] for r in rows], consts, scales=taus, rescale=True, level=level)
+    parts = []
+    for r, c, tau in zip(rows, consts, taus):
+        cols = [j for j in range(len(babies)) if r[j] != 0]
+        parts.append(ev.LinCombNew([babies[j] for j in cols] or babies[:1], [r[j] for j in cols] or [0], c, scale=tau, rescale=True, level=level))
+    return parts
+
+
+def evaluate_poly(ev, ct, coeffs, rlkSet, scale=None, fused=False):
+    """Evaluator.EvaluatePolyNew on any evaluator with params, MulRelinOnceNew, LinCombNew and SumNew (fused=True: LinCombsNew as well, for the inner sums
+    i >= 1 in one call).  p(X) = sum_i inner_i(X) * X^(m i), inner_i = sum_j
     coeffs[i m + j] X^j one LinCombNew each.  Scale bookkeeping, with S the target and l_out the level of the result: inner_0 is summed at S * Q[l_out + 1]
     and rescaled onto (l_out, S); inner_i, i >= 1, is summed at tau_i * Q[l_out + 2] and rescaled to (l_out + 1, tau_i) with tau_i = S * Q[l_out + 1] /
     scale(X^(m i)), so that its product with the giant power lands on S after that product's single Rescale.  Equal scales, one mkhe_ct_sum."""
@@ -469,12 +556,100 @@ def evaluate_poly(ev, ct, coeffs, rlkSet, scale=None):
     terms = []
     if any(inner[0]):
         terms.append(ev.LinCombNew(babies(inner[0]), weights(inner[0]), inner[0][0], scale=S, rescale=True, level=l_out + 1))
+    if fused:
+        used = [i for i in range(1, plan.g) if any(inner[i])]
+        taus = [S * float(params.Q[l_out + 1]) / power[m * i].Scale for i in used]
+        rows = [(inner[i][1:] + [0j] * m)[: m - 1] for i in used]
+        parts = _giant_parts(ev, [power.get(j) for j in range(1, m)], rows, [inner[i][0] for i in used], taus, l_out + 2, True)
+        return ev.SumNew(terms + [ev.MulRelinOnceNew(part, power[m * i], rlkSet, scale=S) for part, i in zip(parts, used)])
     for i in range(1, plan.g):
         if any(inner[i]):
             giant = power[m * i]
             tau = S * float(params.Q[l_out + 1]) / giant.Scale
             part = ev.LinCombNew(babies(inner[i]), weights(inner[i]), inner[i][0], scale=tau, rescale=True, level=l_out + 2)
             terms.append(ev.MulRelinOnceNew(part, giant, rlkSet, scale=S))
+    return ev.SumNew(terms)
+
+
+def chebyshev_approx(f, a, b, degree):
+    """float64 Chebyshev coefficients c_0 .. c_degree of the interpolant of f at the degree + 1 Chebyshev nodes of [a, b]: f(x) ~ sum_k c_k T_k((2 x - a -
+    b) / (b - a)).  f takes a numpy array.  Pure numpy, host only."""
+    a, b, degree = float(a), float(b), int(degree)
+    if not a < b or degree < 0:
+        raise MkheError("chebyshev_approx: needs a < b and a degree of at least 0")
+    return np.polynomial.chebyshev.chebinterpolate(lambda y: np.asarray(f(0.5 * (b - a) * y + 0.5 * (b + a)), dtype=np.float64), degree)
+
+
+def chebyshev_blocks(coeffs, m):
+    """sum_k c_k T_k = sum_i inner_i * T_(m i) with inner_i = sum_(j < m) B[i][j] T_j: the blocks B [ceil(len / m)][m] of a baby-step / giant-step evaluation
+    in the Chebyshev basis, a pure function.  From T_(m i + j) = 2 T_j T_(m i) - T_(m i - j), top block down on running coefficients c': B[i][0] = c'[m i];
+    B[i][j] = 2 c'[m i + j] and c'[m i - j] -= c'[m i + j] for 1 <= j < m; B[0] = c'[0 : m].  |B| stays below 14 for |c_k| <= 1 up to degree 255."""
+    m = int(m)
+    c = np.asarray(coeffs)
+    c = c.astype(np.complex128 if np.iscomplexobj(c) else np.float64)
+    if m < 1 or c.ndim != 1 or c.size < 1:
+        raise MkheError("chebyshev_blocks: a list of coefficients and a block length of at least 1")
+    g = -(-c.size // m)
+    c = np.concatenate([c, np.zeros(g * m - c.size, dtype=c.dtype)])
+    B = np.zeros((g, m), dtype=c.dtype)
+    for i in range(g - 1, 0, -1):
+        B[i, 0] = c[m * i]
+        for j in range(1, m):
+            B[i, j] = 2 * c[m * i + j]
+            c[m * i - j] -= c[m * i + j]
+    B[0] = c[:m]
+    return B
+
+
+def evaluate_chebyshev(ev, ct, coeffs, interval, rlkSet, scale=None, fused=True):
+    """Evaluator.EvaluateChebyshevNew on any evaluator with params, LinCombNew, LinCombsNew, MulRelinRawNew, MulRelinOnceNew and SumNew.
+    Change of variable: y = (2 x - a - b) / (b - a), one LinCombNew at the scale of ct, one level; none for (a, b) = (-1, 1).
+    Powers, on poly_eval_plan(degree) as it is: for (k, a', b'), T_k = 2 T_a' T_b' - T_c with c = a' - b' (an earlier power, or 0: T_0 = 1).  With prod =
+    MulRelinRawNew(T_a', T_b') at level l, T_k = LinCombNew([prod, T_c], [2, -1], 0, scale=prod.Scale / Q[l], level=l) -- the division of the product
+    rides on the sum, the weight of prod is the integer 2 and T_c is re-weighted onto prod.Scale by an integer, so no scale mismatch is tolerated
+    anywhere.  T_c lies no deeper than T_a' (c <= a'), so it has level l at least; depth[k] = ceil(log2 k) as in the monomial basis.
+    Inner sums and giant products: the bookkeeping of evaluate_poly (S, tau_i, l_out) on the blocks of chebyshev_blocks: inner_0 is summed at S * Q[l_out
+    + 1] onto (l_out, S); inner_i, i >= 1, at tau_i * Q[l_out + 2] onto (l_out + 1, tau_i), tau_i = S * Q[l_out + 1] / scale(T_(m i)), all in ONE
+    LinCombsNew (fused) or one LinCombNew each; MulRelinOnceNew(inner_i, T_(m i)) lands on (l_out, S); one SumNew."""
+    params = ev.params
+    coeffs = [complex(c) for c in coeffs]
+    d = len(coeffs) - 1
+    if d < 1 or d > CHEBYSHEV_MAX_DEGREE:
+        raise MkheError("EvaluateChebyshevNew: the degree must be between 1 and %d" % CHEBYSHEV_MAX_DEGREE)
+    a, b = (float(v) for v in interval)
+    if not a < b:
+        raise MkheError("EvaluateChebyshevNew: the interval (a, b) needs a < b")
+    change = (a, b) != (-1.0, 1.0)
+    need = (1 if change else 0) + d.bit_length() + 1
+    l_out = ct.Level() - need
+    if l_out < 0:
+        raise MkheError("EvaluateChebyshevNew: degree %d on this interval needs level %d, the ciphertext is at level %d" % (d, need, ct.Level()))
+    if not any(coeffs):
+        raise MkheError("EvaluateChebyshevNew: the zero polynomial")
+    S = params.Scale() if scale is None else float(scale)
+    plan = poly_eval_plan(d)
+    m, B = plan.m, [list(r) for r in chebyshev_blocks(coeffs, plan.m)]
+    needed = {j for r in B for j in range(1, m) if r[j] != 0} | {m * i for i in range(1, plan.g) if any(B[i])}
+    for k, p, q in reversed(plan.products):                 # a power nobody uses is not computed; T_(p - q) is used by T_k
+        if k in needed:
+            needed |= {p, q, p - q} - {0}
+    y = ev.LinCombNew([ct], [2 / (b - a)], -(a + b) / (b - a), scale=ct.Scale, rescale=True) if change else ct
+    power = {1: y}
+    for k, p, q in plan.products:
+        if k in needed:
+            prod = ev.MulRelinRawNew(power[p], power[q], rlkSet)
+            l = prod.Level()
+            rest, w, const = ([power[p - q]], [-1], 0) if p != q else ([], [], -1)
+            power[k] = ev.LinCombNew([prod] + rest, [2] + w, const, scale=prod.Scale / float(params.Q[l]), rescale=True, level=l)
+    babies = [power.get(j) for j in range(1, m)]
+    terms = []
+    if any(B[0]):
+        cols = [j for j in range(1, m) if B[0][j] != 0]
+        terms.append(ev.LinCombNew([power[j] for j in cols] or [y], [B[0][j] for j in cols] or [0], B[0][0], scale=S, rescale=True, level=l_out + 1))
+    used = [i for i in range(1, plan.g) if any(B[i])]
+    taus = [S * float(params.Q[l_out + 1]) / power[m * i].Scale for i in used]
+    parts = _giant_parts(ev, babies, [B[i][1:] for i in used], [B[i][0] for i in used], taus, l_out + 2, fused)
+    terms += [ev.MulRelinOnceNew(part, power[m * i], rlkSet, scale=S) for part, i in zip(parts, used)]
     return ev.SumNew(terms)
 
 
