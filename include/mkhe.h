@@ -914,6 +914,26 @@ int  mkhe_limbs_sum(mkhe_ctx* ctx, int count, int limbs, int nsrc, const void* c
 int  mkhe_noise_norm(mkhe_ctx* ctx, int kind, int limbs, int count, const void* dev_phase, const void* dev_ref, long ref_stride_words,
                      void* dev_out /* uint64[count][limbs + 1] */);
 
+/* ==== raising the modulus ============================================================================
+ * No reference counterpart (the reference has no bootstrapping).  The first step of one: a ciphertext at level 0, whose phase is m + e mod q_0, read
+ * as integer polynomials and written under the moduli q_0 .. q_(L-1) of a higher level, where its phase is m + e + q_0 I for a small integer
+ * polynomial I (|I| is about sqrt((1 + total Hamming weight of the keys) / 12): sparse keys keep it small).  The rest of a bootstrapping removes
+ * q_0 I homomorphically (mkckks.Bootstrapper of the Python mirror).
+ *
+ * Definition (integers only).  in is at level 0: one limb, coefficient domain, canonical.  out has L = limbs(out) >= 2 limbs.  For every polynomial
+ * p of the ciphertext (1 + k of them) and every coefficient x = in[p][0][n] < q_0: the centred lift is v = x for x <= (q_0 - 1) / 2 and v = x - q_0
+ * above it; out[p][l][n] is the canonical residue of v mod q_l for l < L (limb 0: x itself).  q_l may be shorter than q_0 (45 against 55 bits in
+ * the PN16 chain): |v| is reduced for real, with the Montgomery constants of the context, and the sign is folded in by a select, so the result is
+ * exact for negative v.
+ * Bytes: one streaming launch that reads 8 N (1 + k) bytes once and writes 8 N (1 + k) L: a thread holds a row of 8 coefficients in registers and
+ * stores it under every modulus with 16-byte accesses.  No LDS, no scratch, no table, no upload: legal between mkhe_capture_begin and
+ * mkhe_capture_end.
+ *
+ * Refused, with a message that starts with `mkhe_ct_mod_raise: `, nothing enqueued and the context left usable: a NULL context, in or out; a BFV
+ * context; a context with mkhe_ctx_set_owned; out aliasing in; in not at level 0; out at level 0 (or with more limbs than nQ); in and out over
+ * different ids. */
+int  mkhe_ct_mod_raise(mkhe_ctx* ctx, const mkhe_ct* in, mkhe_ct* out);
+
 /* ==== CKKS encoder: slots <-> RNS plaintext =========================================================
  * The message layer of mkckks/encryptor.go:42-64 (EncryptMsg, EncodeMsgNew) and mkckks/decryptor.go:34-43 (Decrypt).  Those lines call
  * lattigo's ckks.Encoder, which is not in the reference tree: what these calls restate is the canonical embedding itself, not

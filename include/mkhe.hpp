@@ -1158,6 +1158,12 @@ class Evaluator {
         ksw.Conjugate(ct0, ckSet, *out);
         return out;
     }
+    // mkhe_ct_mod_raise (no reference counterpart): the level-0 ciphertext ct0, read as its centred representatives mod Q[0], at `level` >= 1; Scale unchanged
+    CiphertextPtr ModRaiseNew(const Ciphertext& ct0, int level) {
+        auto out = std::make_unique<Ciphertext>(params, ct0.IDSet_(), level, ct0.Scale, false);
+        check(mkhe_ct_mod_raise(params.ctx, ct0.h, out->h));
+        return out;
+    }
     Parameters& params;
     mkrlwe::KeySwitcher ksw;
 

@@ -139,6 +139,7 @@ SIGNATURES = {
     "mkhe_threshold_additive_key": (C.c_int, [vp, vp, C.c_uint32, C.c_int, u32p, vp]),
     "mkhe_limbs_sum": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vpp, vp]),
     "mkhe_noise_norm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_long, vp]),
+    "mkhe_ct_mod_raise": (C.c_int, [vp, vp, vp]),
     "mkhe_ckks_embed": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_project": (C.c_int, [vp, C.c_int, vp, vp]),
     "mkhe_ckks_scale_up": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, vp]),

@@ -988,6 +988,25 @@ int mkhe_noise_norm(mkhe_ctx* ctx, int kind, int limbs, int count, const void* d
         c->noise_norm(kind, limbs, count, (const u64*)dev_phase, (const u64*)dev_ref, ref_stride_words, (u64*)dev_out);
     })
 }
+// raising the modulus: every refusal before the launch, under the guard of the protocol family; one launch without table or scratch, so a capture holds it
+int mkhe_ct_mod_raise(mkhe_ctx* ctx, const mkhe_ct* in, mkhe_ct* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_ct_mod_raise";
+        const std::string w(what);
+        Context* c = enter(ctx, what);
+        if (!in || !out) throw Error(w + ": null argument");
+        scheme_ok(c, what, false, ": not available on a BFV context (its ciphertexts live at one level)");
+        unmasked(c, what);
+        if (in == out || in->c.d == out->c.d) throw Error(w + ": out must not alias in");
+        if (in->c.limbs != 1) throw Error(w + ": in must be at level 0");
+        if (out->c.limbs < 2) throw Error(w + ": out must be above level 0");
+        if (out->c.limbs > c->nq) throw Error(w + ": out has more limbs than the context has moduli");
+        if (in->c.n != out->c.n || in->c.ids != out->c.ids) throw Error(w + ": in and out must carry the same ids");
+        commit(c);
+        mark(ctx, in, out);
+        c->mod_raise(in->c, out->c);
+    })
+}
 // collective refresh, for the CKKS side and for MK-BFV (every ciphertext of a BFV context that the calls take has nq limbs): under the rules of
 // distributed decryption; why_capture closes the capture message
 static Context* refresh_enter(mkhe_ctx* ctx, const char* what, bool bfv, int count, const mkhe_ct* const* in, const char* why_capture,

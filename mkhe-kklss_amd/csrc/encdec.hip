@@ -620,6 +620,15 @@ void Context::limbs_sum(int count, int limbs, const std::vector<const u64*>& src
     MKHE_HIP(hipGetLastError());
 }
 
+void Context::mod_raise(const Ct& in, Ct& out) {
+    need_unmasked("mkhe_ct_mod_raise");
+    {
+        ProfScope ps(this, PROF_OTHER, 8.0 * N * (1 + in.n) * (1.0 + out.limbs));
+        launch_mod_raise(1 + in.n, out.d, in.d, d_mods, out.limbs, N, s_);
+    }
+    MKHE_HIP(hipGetLastError());
+}
+
 // ---- noise measurement (include/mkhe.h; noise_kernels.h).  rf_dig_ holds the digit scratch [count][limbs][N] and behind it the candidates of the
 // workgroups [count][blocks][limbs + 1].  Both are the noise of the ciphertext, which depends on the keys: wiped behind the second launch, as
 // decrypt_share wipes its unflooded product.  The result itself is the caller's.

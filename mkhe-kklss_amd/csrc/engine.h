@@ -26,6 +26,7 @@
 #include "skenc_kernels.h"
 #include "threshold_kernels.h"
 #include "noise_kernels.h"
+#include "modraise_kernels.h"
 #include "ckks_kernels.h"
 #include "bfv_kernels.h"
 
@@ -365,6 +366,9 @@ class Context {
     void threshold_additive_key(const u64* share, u32 point, int nactive, const u32* active, u64* out);
     // dst [count][limbs][N] <- the sum of the sources mod mods[j], canonical; more than ED_INLINE sources stage their table, which synchronises
     void limbs_sum(int count, int limbs, const std::vector<const u64*>& src, u64* dst);
+    // raising the modulus (include/mkhe.h; modraise_kernels.h): out [1 + k][out.limbs][N] <- the centred representatives of the level-0 ciphertext
+    // in [1 + k][1][N] under the first out.limbs moduli.  One launch, no table, no scratch.  The caller (capi.hip) has checked levels, ids and aliasing.
+    void mod_raise(const Ct& in, Ct& out);
 
     // ---- CKKS encoder (ckks_encode.hip, ckks_kernels.h): full packing, n = N/2 slots.  Device buffers: slots double[count][n][2] (re, im),
     // coeffs double[count][N], pt uint64[count][limbs][N] (coefficient domain, canonical).  encode = scale_up(embed), decode = project(scale_down).

@@ -464,6 +464,33 @@ class Evaluator:
         through the single-operation entry points (it needs LinearTransform(.., keep_coeff=True)) and gives the same ciphertext bit for bit."""
         return linear_transform(self, ct, lt, rkSet, fused)
 
+    # ---- the two ciphertext steps that open a bootstrapping (no reference counterpart; Bootstrapper below composes the rest)
+    def ModRaiseNew(self, ct, level=None):
+        """the level-0 ciphertext ct, read as its centred representatives mod Q[0], at `level` (default: the top) as ONE engine call (mkhe_ct_mod_raise).
+        Its phase there is m + e + Q[0] I for a small integer polynomial I; the Scale is unchanged."""
+        level = self.params.MaxLevel() if level is None else int(level)
+        if ct.Level() != 0:
+            raise MkheError("ModRaiseNew: the ciphertext must be at level 0, it is at level %d" % ct.Level())
+        if not 1 <= level <= self.params.MaxLevel():
+            raise MkheError("ModRaiseNew: the target level must lie between 1 and %d" % self.params.MaxLevel())
+        out = NewCiphertext(self.params, ct.IDSet(), level, ct.Scale, zero=False)
+        check(lib().mkhe_ct_mod_raise(self.params.ctx, ct.h, out.h))
+        return out
+
+    def SubSumNew(self, ct, rkSet):
+        """the trace onto the sub-ring of X^gap, gap = N / 2n, n = 2^params.LogSlots(): log2(gap) calls of RotateAndAddNew, by n, 2n, 4n, .. (X -> X^(5^n)
+        generates the automorphisms that fix X^gap).  A coefficient on the grid is multiplied by gap, every other one cancels; the declared Scale is
+        ct.Scale * gap (exact: gap is a power of two), so the slots read the same.  Full packing: ct itself."""
+        n, half = 1 << self.params.LogSlots(), self.params.N() // 2
+        if n == half:
+            return ct
+        out, r = ct, n
+        while r < half:
+            out = self.RotateAndAddNew(out, r, rkSet)
+            r *= 2
+        out.Scale = ct.Scale * (half // n)
+        return out
+
 
 MULRELIN_SUM_MAX = 16     # pairs per mkhe_mul_relin_sum call (csrc/poly_kernels.h, TSUM_MAX_K)
 LINCOMB_MAX = 16          # ciphertexts per mkhe_ct_lincomb call (csrc/poly_kernels.h, CTLIN_MAX)
@@ -808,6 +835,159 @@ def linear_transform(ev, ct, lt, rkSet, fused=True):
         check(L.mkhe_rescale(ctx, total.h, 1, out.h))
     out.Scale = lt.out_scale if ct.Scale == lt.in_scale else mid_scale / float(params.Q[level])
     return out
+
+
+# ---- bootstrapping for 2^logSlots <= 1024 slots (no reference counterpart; DESIGN.md, "Bootstrapping"): ModRaise, SubSum, CoeffsToSlots, EvalMod, SlotsToCoeffs
+BOOTSTRAP_MAX_LOG_SLOTS = 10      # one LinearTransform holds 16 x 64 diagonals (PTXT_DOT_MAX_IN x PTXT_DOT_MAX_GIANT)
+BOOTSTRAP_MIN_RATIO = 2.0 ** 8    # Q[0] / scale: below it the sine's cubic term, (2 pi / ratio)^2 / 6, costs more than 2^-11.6
+
+
+def bootstrap_matrices(params):
+    """(M1, M2, C0, C1), n x n complex, n = 2^params.LogSlots(), in the convention of Encoder: for the 2n real grid coefficients a of the plaintext
+    whose slots are z, w = M1 z + M2 conj(z) has w[t] = a[t] + i a[t + n], and z = C0 a[:n] + C1 a[n:].  With zeta_j = exp(i pi 5^j / 2n), z_j = sum_k
+    a_k zeta_j^k: C0[j][k] = zeta_j^k, C1[j][k] = zeta_j^(k + n).  zeta_j^n = i^(5^j) = i for every j, so C1 = i C0 and z = C0 w: the map is complex-linear,
+    M2 is identically zero, and M1 = C0^-1 = C0^H / n (the zeta_j conj(zeta_j') are distinct n-th roots of unity).  Pure numpy, no device."""
+    enc = Encoder(params)
+    n, k = enc.n, np.arange(enc.n, dtype=np.int64)
+    root = lambda e: np.exp(1j * np.pi * ((enc.rot[:, None] * e[None, :]) % (2 * enc.M)) / enc.M)          # zeta_j^e
+    C0, C1 = root(k), root(k + n)
+    return np.conj(C0).T / n, np.zeros((n, n), dtype=np.complex128), C0, C1
+
+
+def eval_mod_coeffs(K=16, double_angle=3, degree=31):
+    """Chebyshev coefficients c_0 .. c_degree of cos(2 pi (K y - 1/4) / 2^double_angle) on (-1, 1): after double_angle steps of 2 v^2 - 1 it is
+    cos(2 pi (K y - 1/4)) = sin(2 pi K y)"""
+    return chebyshev_approx(lambda y: np.cos(2 * np.pi * (K * y - 0.25) / 2.0 ** double_angle), -1, 1, degree)
+
+
+def eval_mod_model(t, K, double_angle, coeffs, ratio):
+    """the cleartext pipeline of EvalModNew on t = m / ratio + I: the series at t / K, double_angle steps of 2 v^2 - 1, times ratio / (2 pi) -- m, up to the
+    series' error and the sine's cubic term m (2 pi m / ratio)^2 / 6.  t may be complex (the pipeline is a polynomial: a slot with a small imaginary
+    part comes out with it times the derivative)."""
+    t = np.asarray(t)
+    v = np.polynomial.chebyshev.chebval(t.astype(np.complex128 if np.iscomplexobj(t) else np.float64) / K, coeffs)
+    for _ in range(int(double_angle)):
+        v = 2 * v * v - 1
+    return v * (float(ratio) / (2 * np.pi))
+
+
+class Bootstrapper:
+    """A refresh of a level-0 MK-CKKS ciphertext that uses PUBLIC evaluation keys only (Refresher needs every party online with its secret key).
+
+    Contract.  The slots of the ciphertext are bounded by 1 in modulus.  Every party's secret key is SPARSE (KeyGenerator.GenSecretKeySparse): the
+    raised phase is m + e + Q[0] I, and the integer part I has a standard deviation of about sqrt((1 + total Hamming weight) / 12) per coefficient;
+    EvalMod removes it only while |I| <= K - 1, so K is chosen against the TOTAL weight over the parties (K = 16 against a total weight of 64 fails with
+    probability below 1e-9 per bootstrapping).  ratio = Q[0] / ct.Scale >= 2^8; the result differs from the message by the series' error plus the
+    sine's cubic term, at most (2 pi / ratio)^2 / 6 per coefficient over the scale, plus the evaluation noise ("Bootstrapping").
+
+    Steps of BootstrapNew and their levels, from `level` (default: the top) down: ModRaise; SubSum; CoeffsToSlots (1: one transform, M2 being zero) and
+    the split into real and imaginary part onto params.Scale() (1); EvaluateChebyshevNew on (-1, 1) (ceil(log2(degree + 1)) + 1); double_angle
+    steps of 2 v^2 - 1 (1 each); SlotsToCoeffs (1).  The constants cost no level: 1 / gap and 1 / (K ratio) are the declared scale Q[0] K gap of the
+    ciphertext that enters CoeffsToSlots, ratio / (2 pi) is the declared scale of the one that leaves EvalMod.  The transforms are encoded on the device
+    at their first use, for the input scale they meet; another input scale re-encodes them."""
+
+    def __init__(self, params, K=16, double_angle=3, degree=31, level=None):
+        self.params, self.K, self.double_angle, self.degree = params, int(K), int(double_angle), int(degree)
+        self.level = params.MaxLevel() if level is None else int(level)
+        self.n = 1 << params.LogSlots()
+        self.gap = params.N() // (2 * self.n)
+        if params.LogSlots() > BOOTSTRAP_MAX_LOG_SLOTS:
+            raise MkheError("Bootstrapper: logSlots = %d, at most %d (one transform holds %d x %d diagonals)"
+                            % (params.LogSlots(), BOOTSTRAP_MAX_LOG_SLOTS, PTXT_DOT_MAX_IN, PTXT_DOT_MAX_GIANT))
+        if self.K < 1 or self.double_angle < 0 or not 1 <= self.degree <= CHEBYSHEV_MAX_DEGREE:
+            raise MkheError("Bootstrapper: needs K >= 1, double_angle >= 0 and a degree between 1 and %d" % CHEBYSHEV_MAX_DEGREE)
+        if self.level > params.MaxLevel() or self.level < self.Depth():
+            raise MkheError("Bootstrapper: the chain must hold Depth() + 1 = %d moduli up to `level`, level = %d of %d"
+                            % (self.Depth() + 1, self.level, params.MaxLevel()))
+        self.coeffs = eval_mod_coeffs(self.K, self.double_angle, self.degree)
+        self.plan = linear_transform_plan(range(self.n), self.n)
+        self._lts = {}
+
+    def Depth(self):
+        """levels between the raised ciphertext and the result: 1 + 1 + (ceil(log2(degree + 1)) + 1) + double_angle + 1"""
+        return 2 + self.degree.bit_length() + 1 + self.double_angle + 1
+
+    def Rotations(self):
+        """every index a party must hold a CRS slot and a rotation key for: n, 2n, .. N / 4 (SubSum: powers of two, so GenDefaultCRS and
+        GenDefaultRotationKeys cover them) and the baby and giant steps of the two transforms"""
+        sub = [self.n << i for i in range(self.gap.bit_length() - 1)]
+        return sorted(set(sub) | {r for r in self.plan.babies + self.plan.giants if r})
+
+    def _transform(self, which, in_scale, out_scale):
+        """the transform `which` (0: M1 at `level`; 1: C0 at level - Depth() + 1) for ciphertexts at in_scale, encoded once per (in_scale, out_scale)"""
+        hit = self._lts.get(which)
+        if hit is None or hit.in_scale != in_scale or hit.out_scale != out_scale:
+            M1, _, C0, _ = bootstrap_matrices(self.params)
+            level = self.level if which == 0 else self.level - self.Depth() + 1
+            hit = self._lts[which] = LinearTransform.FromMatrix(self.params, M1 if which == 0 else C0, level, in_scale=in_scale, out_scale=out_scale)
+        return hit
+
+    def CoeffsToSlotsNew(self, ct, rkSet, ckSet, ev=None):
+        """(lo, hi): for the plaintext polynomial of ct with the 2n grid coefficients a (over ct.Scale), the slots of lo are a[:n] and those of hi are
+        a[n:], real.  One transform w = M1 z, then lo = (w + conj w) / 2 and hi = (w - conj w) / 2i by one ConjugateNew and one LinCombsNew.  ct at
+        `level` or above (LinearTransformNew drops a higher one to the transform's level first, and refuses a lower one); the halves are at level - 2 with Scale == params.Scale() exactly: the transform leaves at S Q[level - 1] / 2^B, B >= 1 chosen
+        so that its plaintexts are encoded at about Q[level], and the weights 1/2 of the split are then the integers 2^(B - 1)."""
+        ev = Evaluator(self.params) if ev is None else ev
+        params, S = self.params, self.params.Scale()
+        top = S * float(params.Q[self.level - 1])
+        B = max(1, int(round(math.log2(top / ct.Scale))))
+        w = ev.LinearTransformNew(ct, self._transform(0, ct.Scale, top / 2.0 ** B), rkSet)
+        return ev.LinCombsNew([w, ev.ConjugateNew(w, ckSet)], [[0.5, 0.5], [-0.5j, 0.5j]], [0, 0], scales=S, rescale=True)
+
+    def EvalModNew(self, ct, rlkSet, ratio=None, ev=None):
+        """on a ciphertext whose slots are real and lie in (-1, 1), y = (m / ratio + I) / K with integers |I| <= K - 1: m in its slots (eval_mod_model).
+        The series of eval_mod_coeffs on (-1, 1), then double_angle times LinCombNew([MulRelinRawNew(v, v)], [2], -1, ..), whose weight is the integer
+        2; the factor ratio / (2 pi) is the declared Scale of the result.  ratio defaults to Q[0] / params.Scale().  ceil(log2(degree + 1)) + 1 +
+        double_angle levels."""
+        ev = Evaluator(self.params) if ev is None else ev
+        params = self.params
+        ratio = float(params.Q[0]) / params.Scale() if ratio is None else float(ratio)
+        v = ev.EvaluateChebyshevNew(ct, self.coeffs, (-1, 1), rlkSet)
+        for _ in range(self.double_angle):
+            prod = ev.MulRelinRawNew(v, v, rlkSet)
+            l = prod.Level()
+            v = ev.LinCombNew([prod], [2], -1, scale=prod.Scale / float(params.Q[l]), rescale=True, level=l)
+        v.Scale = v.Scale * (2 * math.pi / ratio)
+        return v
+
+    def SlotsToCoeffsNew(self, ct_lo, ct_hi, rkSet, ev=None):
+        """the ciphertext whose plaintext has the grid coefficients (slots of ct_lo, slots of ct_hi), both real: z = C0 (lo + i hi), C1 being i C0 -- one
+        LinCombNew without rescale (the weights 1 and i are exact) and one transform.  Both halves carry one Scale; the result is at level - Depth()
+        with Scale == params.Scale() exactly."""
+        ev = Evaluator(self.params) if ev is None else ev
+        if ct_lo.Scale != ct_hi.Scale:
+            raise MkheError("SlotsToCoeffsNew: the two halves must carry one scale")
+        w = ev.LinCombNew([ct_lo, ct_hi], [1, 1j], 0, scale=ct_lo.Scale, rescale=False)
+        return ev.LinearTransformNew(w, self._transform(1, w.Scale, self.params.Scale()), rkSet)
+
+    def _refuse(self, ct, rlkSet, rkSet, ckSet):
+        """every refusal of BootstrapNew that depends on the call: no engine call is made here"""
+        params = self.params
+        if ct.Level() != 0:
+            raise MkheError("BootstrapNew: the ciphertext must be at level 0, it is at level %d" % ct.Level())
+        ratio = float(params.Q[0]) / ct.Scale
+        if ratio < BOOTSTRAP_MIN_RATIO:
+            raise MkheError("BootstrapNew: Q[0] / scale = %g is below 2^8" % ratio)
+        for idx in (-1, -2):
+            if idx not in params.CRS:
+                raise MkheError("BootstrapNew: no CRS slot %d" % idx)
+        mkrlwe.rotation_keys(params, rkSet, ct.ids, self.Rotations(), "BootstrapNew")
+        for i in ct.ids:
+            rlkSet.GetRelinearizationKey(i)
+            ckSet.GetConjugationKey(i)
+        return ratio
+
+    def BootstrapNew(self, ct, rlkSet, rkSet, ckSet, ev=None):
+        """ct at level 0 -> the same message under the same ids at level `level` - Depth() with Scale == params.Scale() exactly.  MkheError before any
+        engine call when ct is not at level 0, Q[0] / ct.Scale < 2^8, or a key or CRS slot of Rotations(), a relinearisation or conjugation key or
+        CRS slot -1 / -2 is missing (logSlots > 10 and a chain shorter than Depth() + 1 are refused by the constructor)."""
+        ratio = self._refuse(ct, rlkSet, rkSet, ckSet)
+        ev = Evaluator(self.params) if ev is None else ev
+        raised = ev.ModRaiseNew(ct, self.level)
+        sub = ev.SubSumNew(raised, rkSet)
+        sub.Scale = sub.Scale * (self.K * ratio)                    # = Q[0] K gap: the slots of lo / hi are (m / ratio + I) / K
+        lo, hi = self.CoeffsToSlotsNew(sub, rkSet, ckSet, ev)
+        return self.SlotsToCoeffsNew(self.EvalModNew(lo, rlkSet, ratio, ev), self.EvalModNew(hi, rlkSet, ratio, ev), rkSet, ev)
 
 
 def NewEvaluator(params):

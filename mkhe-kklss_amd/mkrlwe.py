@@ -628,6 +628,17 @@ class HostSampler:
         u = self._uniform(N)
         return np.where(u < p, 0, np.where(u < p + (1 - p) / 2, 1, -1)).astype(np.int32)
 
+    def ternary_hw(self, N, h):
+        """exactly h non-zero coefficients, their positions a uniform h-subset of the N (the h smallest of N uniforms) and their signs uniform: the
+        sparse secret of a bootstrapping, whose raised phase carries an integer part of standard deviation about sqrt((1 + h) / 12) per key"""
+        N, h = int(N), int(h)
+        if not 0 <= h <= N:
+            raise MkheError("HostSampler.ternary_hw: the Hamming weight must lie between 0 and N = %d, got %d" % (N, h))
+        s = np.zeros(N, dtype=np.int32)
+        pos = np.argsort(self._uniform(N), kind="stable")[:h]
+        s[pos] = np.where(self._uniform(h) < 0.5, 1, -1)
+        return s
+
     def gaussian(self, count, N):
         """round(N(0, sigma)), resampled while |.| > bound"""
         e = np.rint(self._normal(count * N)).reshape(count, N)
@@ -781,6 +792,11 @@ class KeyGenerator:
         sk = SecretKey(self.params, id)
         check(lib().mkhe_keygen_secret(self.params.ctx, ptr, sk.Value.devptr()))
         return sk
+
+    def GenSecretKeySparse(self, id, h):
+        """a ternary key of Hamming weight exactly h, signs uniform (HostSampler.ternary_hw; no reference counterpart): what mkckks.Bootstrapper asks of
+        every party"""
+        return self.GenSecretKeyWithDistrib(0.0, id, self.sampler.ternary_hw(self.params.N(), h))
 
     def GenSecretKeyGaussian(self, id, s=None):
         """keygen.go:63-65"""
