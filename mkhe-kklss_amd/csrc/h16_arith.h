@@ -64,7 +64,7 @@ __device__ __forceinline__ void ld2(u64* out, gcptr2 base, unsigned idx) {
 struct MC { i32 q0, q1; u32 ninv; u64 q; float finv; i32 p0, p1; /* radix-2^31 digits of q, balanced (mm31) */ };
 
 // ------------------------------------------------------------------ signed-digit Montgomery product (modarith.h mont_mul_sd)
-// a * w * 2^-64 mod q as a signed representative, |r| <= q/2 + |a| w / 2^64 + 1: 12 multiplier-class + 2 plain instructions.
+// a * w * 2^-64 mod q as a signed representative, |r| <= q/2 + q/2^33 + |a| w / 2^64 + 1: 12 multiplier-class + 2 plain instructions.
 // The two reduction rounds are spelled out as two asm blocks of v_mad_i64_i32 chains: written in C the compiler starts the
 // products that do not depend on the carry word early and adds it with separate 64-bit additions (2 extra instructions per
 // product), and written as one asm statement per instruction it pads every statement with an s_nop (it has to assume a
@@ -206,9 +206,15 @@ template <bool SW> __device__ __forceinline__ i64 mm30u(i64 a, u64 us, u64 vs, c
     return acc;
 }
 
-// Cheap partial reduction: x -> x - round(x / q) * q, |result| <= q/2 + q * 2^-19, for any |x| < 2^62.9.  The quotient is estimated
-// from the high word in float32 (3 plain VALU instructions: convert, fma with the 1.5 * 2^23 rounding constant, subtract) and is at
-// most a few dozen, so the product is one v_mad_i64_i32 for the low digit of q plus a 32-bit multiply-add for the high digit:
+// Cheap partial reduction: x -> x - n * q with n an estimate of round(x / q), for any |x| < 2^62.9 with |x| < 2^22 q:
+//   |result| <= q/2 + |x| * 2^-22 + 2^33.
+// The quotient is estimated from the high word in float32 (3 plain VALU instructions: convert, fma with the 1.5 * 2^23 rounding constant,
+// subtract): the conversion of the high word and the constant 2^32 / q are each rounded to 24 bits, so the estimate is off by up to
+// |x / q| * 2^-23, and the low word that it ignores is worth 2^32 / q more.  Where the kernels apply it the quotient is a few dozen at most
+// (values of a few dozen q before a phase): |result| <= q/2 + q * 2^-19 for |x| + 2^55 <= 8 q, and the 0.51 q of the reduction schedules
+// (engine.hip h16_sched_) holds for |x| <= 2^15 q, q >= 2^45 -- canonical digits below 2^60 of any modulus.  It is NOT q/2 + q * 2^-19 over
+// the whole range: at |x| near 2^62.9 a 45-bit q gives up to 0.56 q (0.512 q measured, tests/test_gpu_arith_probe.py).
+// The product is one v_mad_i64_i32 for the low digit of q plus a 32-bit multiply-add for the high digit:
 // 7 instructions, 3 of them multiplier-class, against 14 / 12 for a Montgomery product by R mod q.
 __device__ __forceinline__ i64 pred(i64 x, const MC& c) {
     const float f = __builtin_fmaf((float)(i32)hi32((u64)x), c.finv, 12582912.0f);
@@ -217,6 +223,29 @@ __device__ __forceinline__ i64 pred(i64 x, const MC& c) {
     return (i64)((u64)y + ((u64)(u32)(nt * c.q1) << 32));                         // high word += nt * q1 (v_mul_lo_u32 + v_add_u32)
 }
 
+// ------------------------------------------------------------------ the F class: exact integers held in doubles (derivation: ntt16_kernels.hip, "the F class")
+// u64 <-> double by the 2^52 trick; FC: q and 1/q (rounded) as doubles, wave-uniform.
+__device__ __forceinline__ double u2d(u64 v) { return __builtin_bit_cast(double, v | 0x4330000000000000ull) - 4503599627370496.0; }      // v < 2^52
+__device__ __forceinline__ u64 d2u(double y) { return __builtin_bit_cast(u64, y + 4503599627370496.0) & 0x000fffffffffffffull; }         // 0 <= y < 2^52
+struct FC { double q, qinv; };
+// butterfly on the bit patterns of two integer-valued doubles u = U, a = V and a plain twiddle w in [0, q): T = a w - k q exactly with |T| <= 1.25 q,
+// U' = u + T, V' = u - T.  Needs |a| < 2^51 and every sum below 2^53.
+__device__ __forceinline__ void bflyF(u64& U, u64& V, double w, const FC& c) {
+    const double a = __builtin_bit_cast(double, V), u = __builtin_bit_cast(double, U);
+    const double h = a * w;
+    const double l = __builtin_fma(a, w, -h);
+    const double k = __builtin_rint(h * c.qinv);
+    const double r = __builtin_fma(-k, c.q, h);
+    const double T = r + l;
+    U = __builtin_bit_cast(u64, u + T);
+    V = __builtin_bit_cast(u64, u - T);
+}
+// output representative of the F class: the canonical residue in [0, q) of an integer-valued v, |v| < 2^52, as a u64
+__device__ __forceinline__ u64 canonF(double v, const FC& c) {
+    double y = __builtin_fma(-__builtin_rint(v * c.qinv), c.q, v);          // |y| <= (q + 1) / 2
+    y = y < 0.0 ? y + c.q : y;
+    return d2u(y);
+}
 
 template <bool CROSS> __device__ __forceinline__ void xsync() {
     if constexpr (CROSS) __syncthreads();

@@ -83,7 +83,9 @@ __device__ __forceinline__ i64 mad_i64(i32 a, i32 b, i64 c) {
 }
 
 // Signed word-serial Montgomery product for the NTT kernels: a*w*R^-1 mod q as a SIGNED representative r with
-// |r| <= q/2 + |a|*w/2^64 + 1.  a: any signed 64-bit value with |a| < 2^62; ws, qs: signed-split forms of w < q < 2^61.
+// |r| <= q/2 + q/2^33 + |a|*w/2^64 + 1.  a: any signed 64-bit value with |a| < 2^62; ws, qs: signed-split forms of w < q < 2^61.
+// (r 2^64 = a w + m q + m2 q 2^32 with both m in [-2^31, 2^31): the second round's m2 gives the q/2, the first round's m the q/2^33, reached at
+// m = m2 = -2^31 -- tests/test_gpu_arith_probe.py.)
 // With balanced 32-bit digits every partial sum fits a signed 64-bit accumulator, so each round is
 //   P = a_i*w0 [+ carry-in]; m = lo(P)*(-q^-1); S = m*q0 + P (low word 0); next = m*q1 + a_i*w1 + (S >> 32)
 // = 4 v_mad_i64_i32 + 1 v_mul_lo_u32 + 1 v_ashrrev_i64 and nothing else (no widening moves, no carry chains): 12

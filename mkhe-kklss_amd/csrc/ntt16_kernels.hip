@@ -439,19 +439,7 @@ __device__ __forceinline__ void limb(const Job& jb, const bool big_, u32* lds, c
 // stages of growth by at most 1.25 q: x in (-17.5 q, 39.7 q), and the 40 q bias of internal digits: (22.5 q, 79.7 q) -- 80 q < 2^52 is the class,
 // the 45-bit primes of PN16QP1761 (33 of its 38 moduli).  Twiddles are PLAIN residues as doubles (NttBatch::psif), values travel
 // through the LDS re-distributions as their bit patterns, u64 <-> double by the 2^52 trick (one OR / AND on the high word, one add).
-__device__ __forceinline__ double u2d(u64 v) { return __builtin_bit_cast(double, v | 0x4330000000000000ull) - 4503599627370496.0; }      // v < 2^52
-__device__ __forceinline__ u64 d2u(double y) { return __builtin_bit_cast(u64, y + 4503599627370496.0) & 0x000fffffffffffffull; }         // 0 <= y < 2^52
-struct FC { double q, qinv; };
-__device__ __forceinline__ void bflyF(u64& U, u64& V, double w, const FC& c) {
-    const double a = __builtin_bit_cast(double, V), u = __builtin_bit_cast(double, U);
-    const double h = a * w;
-    const double l = __builtin_fma(a, w, -h);
-    const double k = __builtin_rint(h * c.qinv);
-    const double r = __builtin_fma(-k, c.q, h);
-    const double T = r + l;
-    U = __builtin_bit_cast(u64, u + T);
-    V = __builtin_bit_cast(u64, u - T);
-}
+// The pieces themselves -- FC, u2d, d2u, bflyF, canonF -- are in h16_arith.h.
 template <int B, int G0 = 0, int NG = 8> __device__ __forceinline__ void stageF(u64 (&x)[16], const u64* tw, const FC& c) {
 #pragma unroll
     for (int g = G0; g < G0 + NG; ++g) {
@@ -578,11 +566,8 @@ __device__ __forceinline__ void limb_f(const Job& jb, u32* lds, const int wv) {
     // reduction is four instructions more than adding a bias, and one code path instead of two keeps the pass within its 64 registers)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const double v = __builtin_bit_cast(double, x[r]);
-        double y = __builtin_fma(-__builtin_rint(v * c.qinv), c.q, v);          // |y| <= (q + 1) / 2
-        y = y < 0.0 ? y + c.q : y;
-        x[r] = d2u(y);
-        __builtin_amdgcn_sched_barrier(0);                                        // (one value at a time: interleaved, their temporaries spill)
+        x[r] = canonF(__builtin_bit_cast(double, x[r]), c);
+        __builtin_amdgcn_sched_barrier(0);                                      // (one value at a time: interleaved, their temporaries spill)
     }
     exchange<X_DE>(x, lds, wv);
     {

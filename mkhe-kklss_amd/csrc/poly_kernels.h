@@ -456,6 +456,16 @@ void launch_automorphism(u64* dst, const u64* src, const Mod* mods, int L, int l
 // dst[i] (i < level) from src limbs 0..level;  src is not modified.
 void launch_div_round_last(u64* dst, const u64* src, const Mod* mods, const u64* rescale_row /*[level]*/,
                            int level, int N, int npolys, long src_poly, long dst_poly, hipStream_t st);
+// h mod q (the BRedAdd(h, q_i) of that step), canonical, for h < 2^60 and q > 2^20.  The 64-bit `%` is a long software loop that every thread
+// would run for one coefficient's worth of work: the quotient (< 2^40) is estimated in float64 (off by at most one) and the remainder fixed up --
+// same value.
+__device__ __forceinline__ u64 mod_by_estimate(u64 h, u64 q) {
+    const u64 k = (u64)((double)h / (double)q);
+    u64 hr = h - k * q;
+    if ((i64)hr < 0) hr += q;
+    if (hr >= q) hr -= q;
+    return hr;
+}
 
 // the same step on a contiguous source [ngroups * per_group polys] whose results go to ngroups separate destinations (the ciphertexts of a batch,
 // batch.hip): polynomial p of group g -> dst[g] + p * dst_poly
