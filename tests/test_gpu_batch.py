@@ -267,8 +267,9 @@ def test_rotate_multi_each_lane_its_own_rotation(case, ids, level, hoisted):
 @pytest.mark.parametrize("ids,level", [(["a", "b"], None), (["a", "b", "c", "d"], 1), (["d"], 0)])
 def test_rotate_and_add_is_the_two_calls(case, ids, level):
     """AddNew(ct, RotateNew(ct, r)) in one engine call (the add on the rotation's store; cnn/cnn.go:33-37): against the oracle's Rotate followed by
-    ring.Add, for one ciphertext, for a batch, and with an addend that is NOT the rotated ciphertext; a rotated zero coefficient with a sign flip is
-    stored as q by the permutation (keyswitch.go:290) and must still add up canonically"""
+    ring.Add, for one ciphertext, for a batch, and with an addend that is NOT the rotated ciphertext.  (A rotated zero coefficient with a sign flip is
+    stored as q by the permutation, keyswitch.go:290, and must still add up canonically: uniform data never produces one -- that case is planted by
+    tests/test_gpu_moddown_edges.py::test_rotate_and_add_reads_a_stored_q_under_a_foreign_addend.)"""
     from mkhe_kklss_amd._abi import check, lib, handle_array, MkheError
     import ctypes as C
     level = case.level if level is None else level
