@@ -287,6 +287,25 @@ int  mkhe_ct_lincomb(mkhe_ctx* ctx, int n, const mkhe_ct* const* in, const void*
  * Bit-exactness: out[g] equals, bit for bit, mkhe_ct_lincomb(nin, in, row g of dev_consts, nb_rescale): both are the canonical residue of the same
  * integer, zero weights included. */
 int  mkhe_ct_lincomb_multi(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int nout, const void* dev_consts, int nb_rescale, mkhe_ct* const* out);
+/* ==== Weighted sums in lock step: mkhe_ct_lincomb_multi on nbatch independent items with ONE constant block ===========
+ * No reference counterpart; what mkckks.BatchEvaluator.LinCombsNew issues: item b is the nout sums of its own nin ciphertexts in[b * nin + k] into
+ * out[b * nout + g], with the weights and constants all items share (the items of a batch carry one scale, so their encoded weights are the same).
+ * Contract: for every item b, out[b * nout ..] equals, bit for bit, mkhe_ct_lincomb_multi(ctx, nin, in + b * nin, nout, dev_consts, nb_rescale,
+ * out + b * nout); the formulas, dev_consts = device uint64[nout][nin + 1][2][Lc] and the rescale are that call's.
+ * Shapes: nbatch >= 1 with no upper bound other than memory; 1 <= nin <= 16, 1 <= nout <= 16, nb_rescale 0 or 1; all handles carry the same ids; every
+ * output has the same number of limbs L; input k has the same number of limbs in every item, at least Lc = L + nb_rescale (different k may differ;
+ * the first Lc limbs are read).  The same handle may be input k of several items (a broadcast operand).  The outputs are pairwise distinct, and no
+ * output is an input of ANY item, its own included.
+ * Refusals: the counts (nbatch, nin, nout, nb_rescale) are checked before the context is looked at; every error message starts with
+ * "mkhe_ct_lincomb_batch: "; a refused call enqueues nothing and leaves the context usable.  Accepted where mkhe_ct_lincomb_multi is: not on a BFV
+ * context and not on a limb-sharded one.
+ * Launch set: the item is a grid dimension next to the component, a thread is mkhe_ct_lincomb_multi's; 8 N (1 + k) nbatch (nin Lc + nout L) bytes.  The
+ * base addresses of all handles travel in the kernel arguments: nothing is uploaded and no pool allocation is taken, so the call is legal between
+ * mkhe_capture_begin and mkhe_capture_end.  One launch holds 384 / (nin + nout) items (12 at 16 x 16, 192 at 1 x 1); further items go into further
+ * launches of the same kernel on the same stream. */
+int  mkhe_ct_lincomb_batch(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* const* in /* [nbatch * nin], in[b * nin + k] */,
+                           int nout, const void* dev_consts /* uint64[nout][nin + 1][2][Lc], the block of mkhe_ct_lincomb_multi */,
+                           int nb_rescale, mkhe_ct* const* out /* [nbatch * nout], out[b * nout + g] */);
 /* mkckks.Evaluator.MulPtxtNew body (evaluator.go:465-478) without its Rescale: every component times the plaintext
  * polynomial dev_pt = uint64[limbs][N] (coefficient domain, device), via NTT / MForm / InvNTT. */
 int  mkhe_ct_mul_ptxt(mkhe_ctx* ctx, const mkhe_ct* in, const void* dev_pt, mkhe_ct* out);

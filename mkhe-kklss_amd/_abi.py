@@ -86,6 +86,7 @@ SIGNATURES = {
     "mkhe_ct_sum": (C.c_int, [vp, C.c_int, vpp, vp]),
     "mkhe_ct_lincomb": (C.c_int, [vp, C.c_int, vpp, vp, C.c_int, vp]),
     "mkhe_ct_lincomb_multi": (C.c_int, [vp, C.c_int, vpp, C.c_int, vp, C.c_int, vpp]),
+    "mkhe_ct_lincomb_batch": (C.c_int, [vp, C.c_int, C.c_int, vpp, C.c_int, vp, C.c_int, vpp]),
     "mkhe_rotate_multi":(C.c_int, [vp, C.c_int, u64p, vpp, vpp, vpp, vpp, vpp, vpp]),
     "mkhe_mul_relin_batch": (C.c_int, [vp, C.c_int, vpp, vpp, vpp, vpp, vpp, vpp, vpp, vp, C.c_int, vpp]),
     "mkhe_mul_relin_sum": (C.c_int, [vp, C.c_int, vpp, vpp, vpp, vpp, vpp, vpp, vpp, vp, C.c_int, vp]),

@@ -607,6 +607,32 @@ int mkhe_ct_lincomb_multi(mkhe_ctx* ctx, int nin, const mkhe_ct* const* in, int 
         c->ct_lincomb_multi(what, i, (const u64*)dev_consts, nb_rescale, o);
     })
 }
+// mkhe_ct_lincomb_multi on nbatch items that share the constants (engine_ops.hip); the counts first, then the context.  Nothing is allocated or uploaded
+// on the device: legal inside a capture.  (Distinct outputs are the engine's check, by address: the handle lists may be long.)
+int mkhe_ct_lincomb_batch(mkhe_ctx* ctx, int nbatch, int nin, const mkhe_ct* const* in, int nout, const void* dev_consts, int nb_rescale, mkhe_ct* const* out) {
+    MKHE_TRY({
+        const char* what = "mkhe_ct_lincomb_batch";
+        const std::string w = std::string(what) + ": ";
+        if (nbatch < 1) throw Error(w + "nbatch must be at least 1");
+        if (nin < 1 || nin > CTLM_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(CTLM_MAX_IN));
+        if (nout < 1 || nout > CTLM_MAX_OUT) throw Error(w + "nout must be 1 .. " + std::to_string(CTLM_MAX_OUT));
+        if (nb_rescale != 0 && nb_rescale != 1) throw Error(w + "nb_rescale must be 0 or 1");
+        Context* c = enter(ctx, what);
+        if (!in || !dev_consts || !out) throw Error(w + "null argument");
+        scheme_ok(c, what, false, ": needs a CKKS or mkrlwe context (mkhe_bfv_ct_lincomb is the BFV call)");
+        unmasked(c, what);
+        const size_t ni = (size_t)nbatch * nin;
+        const size_t no = (size_t)nbatch * nout;
+        for (size_t i = 0; i < ni; ++i) if (!in[i]) throw Error(w + "null ciphertext in the batch");
+        for (size_t i = 0; i < no; ++i) if (!out[i]) throw Error(w + "null output in the batch");
+        commit(c);
+        std::vector<const Ct*> vi(ni);
+        std::vector<Ct*> vo(no);
+        for (size_t i = 0; i < ni; ++i) { mark(ctx, in[i]); vi[i] = &in[i]->c; }
+        for (size_t i = 0; i < no; ++i) { mark(ctx, out[i]); vo[i] = &out[i]->c; }
+        c->ct_lincomb_batch(what, vi, nin, (const u64*)dev_consts, nb_rescale, vo, nout);
+    })
+}
 int mkhe_hoisted_form_batch(mkhe_ctx* ctx, int level, int nbatch, const mkhe_ct* const* cts, mkhe_swk* const* out) {
     MKHE_TRY({
         if (nbatch < 1) throw Error("mkhe_hoisted_form_batch: empty batch");

@@ -202,6 +202,11 @@ class Context {
     // outputs of one shape from 1 .. 16 inputs as one launch: row g is ct_lincomb's sum, bit for bit (no reference counterpart).  dev_consts: device
     // uint64[nout][nin + 1][2][Lc], Lc = limbs(outs) + nb_rescale (poly_kernels.h, CtLincombMultiArgs); refusals under `what`, before the launch
     void ct_lincomb_multi(const char* what, const std::vector<const Ct*>& ins, const u64* dev_consts, int nb_rescale, const std::vector<Ct*>& outs);
+    // ct_lincomb_multi on nbatch = ins.size() / nin items in lock step that share dev_consts: item i sums ins[i * nin ..] into outs[i * nout ..], bit for bit
+    // what ct_lincomb_multi gives on them.  Input k has one limb count in all items; the same Ct may be an input of several items; no output overlaps
+    // an input of any item or another output.  Base addresses in the kernel arguments (no upload, no allocation), as many launches as they need
+    void ct_lincomb_batch(const char* what, const std::vector<const Ct*>& ins, int nin, const u64* dev_consts, int nb_rescale, const std::vector<Ct*>& outs,
+                          int nout);
     // plaintext linear transform (no reference counterpart; batch.hip): ptntt = MForm(NTT(pt)) for count plaintexts [limbs][N] (ptntt may be pt), and
     // the dot of both schemes for nbatch items that share masks and plaintexts: outs[b][g] = sum over the set bits i of masks[g] of ins[b][i] * P(g, i),
     // ins = [nbatch][nin] with at least L limbs, outs = [nbatch][masks.size()] with L limbs, pt = the compact block of prepared plaintexts in (g, i)

@@ -287,6 +287,58 @@ void Context::ct_lincomb_multi(const char* what, const std::vector<const Ct*>& i
     MKHE_HIP(hipGetLastError());
 }
 
+// ct_lincomb_multi for nbatch = ins.size() / nin items in lock step (launch_ct_lincomb_batch): item i sums ins[i * nin ..] into outs[i * nout ..] with the
+// constants all items share, 8 N (1 + k) nbatch (nin Lc + nout L) bytes.  The base addresses travel in the kernel arguments -- no table, no pool
+// allocation -- and the launcher deals the items to as many launches as that takes.  An output of one launch could be an input of a later one, so no
+// output may overlap an input of ANY item.  Every refusal is under `what` (the C entry point) and comes before the first launch.
+void Context::ct_lincomb_batch(const char* what, const std::vector<const Ct*>& ins, int nin, const u64* dev_consts, int nb_rescale, const std::vector<Ct*>& outs,
+                               int nout) {
+    const std::string w = std::string(what) + ": ";
+    if (nin < 1 || nin > CTLM_MAX_IN) throw Error(w + "nin must be 1 .. " + std::to_string(CTLM_MAX_IN));
+    if (nout < 1 || nout > CTLM_MAX_OUT) throw Error(w + "nout must be 1 .. " + std::to_string(CTLM_MAX_OUT));
+    if (nb_rescale != 0 && nb_rescale != 1) throw Error(w + "nb_rescale must be 0 or 1");
+    if (ins.empty() || ins.size() % nin || outs.size() != ins.size() / nin * nout) throw Error(w + "nbatch must be at least 1, with nin inputs and nout outputs per item");
+    if (!dev_consts) throw Error(w + "null argument");
+    const size_t nbatch = ins.size() / nin;
+    const Ct& o0 = *outs[0];
+    const int L = o0.limbs, Lc = L + nb_rescale, np_ = 1 + o0.n;
+    if (L < 1) throw Error(w + "cannot Rescale: input Ciphertext already at level 0");          // (Lc = 1 with a division: nothing would be left)
+    if (Lc > nq) throw Error(w + "level out of range");
+    const size_t out_words = (size_t)np_ * L * N;
+    CtLincombBatchArgs a{};
+    const int per = nin + nout;
+    std::vector<u64*> sets(nbatch * per);
+    std::vector<const u64*> ostart(outs.size());
+    for (size_t i = 0; i < outs.size(); ++i) {
+        const Ct& o = *outs[i];
+        if (o.n != o0.n || o.ids != o0.ids) throw Error(w + "every input and output must carry the same ids");
+        if (o.limbs != L) throw Error(w + "the outputs must have the same number of limbs");
+        sets[i / nout * per + nin + i % nout] = o.d; ostart[i] = o.d;
+    }
+    // the outputs are blocks of one size: sorted by their start, two of them overlap only if two neighbours do
+    std::sort(ostart.begin(), ostart.end(), std::less<const u64*>());
+    for (size_t i = 1; i < ostart.size(); ++i)
+        if (ostart[i] < ostart[i - 1] + out_words) throw Error(w + "the outputs must be distinct");
+    for (size_t i = 0; i < ins.size(); ++i) {
+        const Ct& c = *ins[i];
+        const int b = (int)(i % nin);
+        if (c.n != o0.n || c.ids != o0.ids) throw Error(w + "every input and output must carry the same ids");
+        if (c.limbs < Lc) throw Error(w + "an input has fewer limbs than the sums (limbs(out) + nb_rescale)");
+        if (c.limbs != ins[b]->limbs) throw Error(w + "input k must have the same number of limbs in every item");
+        // the last output that starts below the end of this input is the only one that can reach into it
+        const u64* end = c.d + (size_t)np_ * c.limbs * N;
+        const auto it = std::lower_bound(ostart.begin(), ostart.end(), end, std::less<const u64*>());
+        if (it != ostart.begin() && c.d < *(it - 1) + out_words) throw Error(w + "an output must not alias an input");
+        sets[i / nin * per + b] = c.d;
+        if (i < (size_t)nin) a.in_poly[b] = (long)c.limbs * N;
+    }
+    a.out_poly = (long)L * N; a.mods = d_mods; a.consts = dev_consts;
+    if (nb_rescale) { a.rescale_row = d_rescale + (size_t)(Lc - 2) * nq; a.rescale_h = a.rescale_row + (size_t)nq * nq; }
+    a.nin = nin; a.nout = nout; a.Lc = Lc; a.N = N; a.npolys = np_;
+    { ProfScope ps(this, PROF_OTHER, 8.0 * N * np_ * nbatch * ((double)nin * Lc + (double)nout * L)); launch_ct_lincomb_batch(a, sets.data(), (int)nbatch, s_); }
+    MKHE_HIP(hipGetLastError());
+}
+
 void Context::ct_mul_ptxt(const Ct& in, const u64* dev_pt, Ct& out) {
     const int L = in.limbs, np_ = 1 + in.n;
     if (out.limbs != L || out.n != in.n || out.ids != in.ids) throw Error("mkhe: ctOut shape does not match ct");

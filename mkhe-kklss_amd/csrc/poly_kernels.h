@@ -443,6 +443,26 @@ struct CtLincombMultiArgs {
     int nin, nout, Lc, N, npolys;
 };
 void launch_ct_lincomb_multi(const CtLincombMultiArgs& a, hipStream_t st);
+// The same sums for nbatch independent items in lock step (mkhe_ct_lincomb_batch; no reference counterpart): item i has its own nin inputs and nout
+// outputs and is what launch_ct_lincomb_multi gives on them, word for word; all items share consts, Lc, the limb counts in_poly[b] of input b and the
+// shape of the outputs.  The base addresses travel in the kernel arguments (nothing is uploaded or allocated: the call may be captured): ptr holds,
+// item after item, the nin input bases and then the nout output bases of the items of ONE launch.  The caller passes the whole list (sets =
+// [nbatch][nin + nout], host memory) and fills every field but ptr and nbatch; launch_ct_lincomb_batch deals the items to as many launches as the
+// list needs -- CTLB_MAX_PTRS / (nin + nout) items each, so that the argument block stays below the 4 KiB a kernel may take.  The same base may
+// be an input of several items.  No output may overlap an input of ANY item or another output.
+constexpr int CTLB_MAX_PTRS = 384;
+struct CtLincombBatchArgs {
+    u64* ptr[CTLB_MAX_PTRS];
+    long in_poly[CTLM_MAX_IN];
+    long out_poly;
+    const Mod* mods;
+    const u64* consts;
+    const u64* rescale_row;
+    const u64* rescale_h;
+    int nin, nout, Lc, N, npolys, nbatch;
+};
+static_assert(sizeof(CtLincombBatchArgs) <= 4096 && CTLB_MAX_PTRS >= CTLM_MAX_IN + CTLM_MAX_OUT, "one launch holds at least one item within the kernel-argument limit");
+void launch_ct_lincomb_batch(CtLincombBatchArgs& a, u64* const* sets, int nbatch, hipStream_t st);
 // dst = MForm(src) for count polynomials of L limbs each (limb l under mods[l]); dst may be src
 void launch_mform_polys(u64* dst, const u64* src, const Mod* mods, int L, int N, int count, hipStream_t st);
 

@@ -1343,10 +1343,13 @@ void launch_bfv_ct_lincomb(const BfvLincombArgs& a, hipStream_t st) {
 static_assert(CTLM_MAX_IN <= 16, "ct_lincomb_multi_kernel: 2 * CTLM_MAX_IN products must stay within the 32 that redc128 accepts for q < 2^60");
 static_assert(CTLM_MAX_OUT <= 16, "ct_lincomb_multi_kernel: NO is 4, 8 or 16");
 typedef const __attribute__((address_space(4))) CtLincombMultiArgs* ctlm_kargs;
-template <int NI, int NO>
-__global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombMultiArgs a) {
-    ctlm_kargs ka = (ctlm_kargs)__builtin_amdgcn_kernarg_segment_ptr();
-    const int half = a.N >> 1, j = blockIdx.x * PW_THREADS + threadIdx.x, p = blockIdx.y, top = a.Lc - 1;
+typedef const __attribute__((address_space(4))) long* sc_long;
+// The sums of ONE set of inputs and outputs for the calling thread's pair j of polynomial p: the body of ct_lincomb_multi_kernel and of
+// ct_lincomb_batch_kernel.  a = the kernel's argument block (both kinds name the shared fields alike); ins[b] / in_poly[b] / outs[g] = the base
+// addresses of this set, lists in the kernel arguments (scalar loads).
+template <int NI, int NO, class Args, class InList, class OutList>
+__device__ __forceinline__ void ctlm_body(const Args& a, const int p, const InList ins, const sc_long in_poly, const OutList outs) {
+    const int half = a.N >> 1, j = blockIdx.x * PW_THREADS + threadIdx.x, top = a.Lc - 1;
     if (j >= half) return;
     const sc_u64 cs = (sc_u64)a.consts;
     const bool constant_term = p == 0 && j == 0;
@@ -1359,7 +1362,7 @@ __global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombM
 #pragma unroll
         for (int b = 0; b < NI; ++b) {
             xa[b] = 0; xb[b] = 0;
-            if (b < a.nin) { const u64* x = ka->in[b] + ((long)p * ka->in_poly[b] + (long)l * a.N); xa[b] = x[ja]; xb[b] = x[jb]; }
+            if (b < a.nin) { const u64* x = ins[b] + ((long)p * in_poly[b] + (long)l * a.N); xa[b] = x[ja]; xb[b] = x[jb]; }
         }
     };
     // the canonical sums of output g under limb l from the loaded pairs
@@ -1393,7 +1396,7 @@ __global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombM
             load(l);
             for (int g = 0; g < a.nout; ++g) {
                 sums(g, l, md, v0, v1);
-                u64* d = ka->out[g] + ((long)p * a.out_poly + (long)l * a.N);
+                u64* d = outs[g] + ((long)p * a.out_poly + (long)l * a.N);
                 d[ja] = v0; d[jb] = v1;
             }
         }
@@ -1426,7 +1429,7 @@ __global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombM
                 const u64 c0 = t0[0], c1 = t1[0];
                 if (g < a.nout) {
                     sums(g, l, md, v0, v1);
-                    u64* d = ka->out[g] + ((long)p * a.out_poly + (long)l * a.N);
+                    u64* d = outs[g] + ((long)p * a.out_poly + (long)l * a.N);
                     d[ja] = mont_mul(c0 + hneg + md.q2 - v0, rp, md.q, md.ninv32);
                     d[jb] = mont_mul(c1 + hneg + md.q2 - v1, rp, md.q, md.ninv32);
                 }
@@ -1434,6 +1437,22 @@ __global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombM
             }
         }
     }
+}
+template <int NI, int NO>
+__global__ void __launch_bounds__(PW_THREADS) ct_lincomb_multi_kernel(CtLincombMultiArgs a) {
+    ctlm_kargs ka = (ctlm_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    ctlm_body<NI, NO>(a, blockIdx.y, ka->in, ka->in_poly, ka->out);
+}
+// nbatch items in lock step (CtLincombBatchArgs): the item is a grid dimension next to the polynomial -- blockIdx.y = item * npolys + polynomial, like
+// ct_ptxt_dot_kernel -- and selects its nin + nout base addresses in the kernel arguments; everything else of a thread is ct_lincomb_multi_kernel's,
+// and so are the words.  The constants are shared: a weight is fetched (1 + parties) * nbatch times, from the scalar cache.
+typedef const __attribute__((address_space(4))) CtLincombBatchArgs* ctlb_kargs;
+template <int NI, int NO>
+__global__ void __launch_bounds__(PW_THREADS) ct_lincomb_batch_kernel(CtLincombBatchArgs a) {
+    ctlb_kargs ka = (ctlb_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    const int item = blockIdx.y / a.npolys, p = blockIdx.y - item * a.npolys;      // (wave-uniform)
+    const auto set = ka->ptr + item * (a.nin + a.nout);
+    ctlm_body<NI, NO>(a, p, set, ka->in_poly, set + a.nin);
 }
 template <int NI> static void launch_ctlm_no(const CtLincombMultiArgs& a, dim3 grid, dim3 blk, hipStream_t st) {
     if (!a.rescale_row) hipLaunchKernelGGL((ct_lincomb_multi_kernel<NI, 0>), grid, blk, 0, st, a);
@@ -1453,6 +1472,31 @@ void launch_ct_lincomb_multi(const CtLincombMultiArgs& a, hipStream_t st) {
     if (a.nin > 8) launch_ctlm_no<16>(a, grid, blk, st);
     else if (a.nin > 4) launch_ctlm_no<8>(a, grid, blk, st);
     else launch_ctlm_no<4>(a, grid, blk, st);
+}
+template <int NI> static void launch_ctlb_no(const CtLincombBatchArgs& a, dim3 grid, dim3 blk, hipStream_t st) {
+    if (!a.rescale_row) hipLaunchKernelGGL((ct_lincomb_batch_kernel<NI, 0>), grid, blk, 0, st, a);
+    else if (a.nout > 8) hipLaunchKernelGGL((ct_lincomb_batch_kernel<NI, 16>), grid, blk, 0, st, a);
+    else if (a.nout > 4) hipLaunchKernelGGL((ct_lincomb_batch_kernel<NI, 8>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((ct_lincomb_batch_kernel<NI, 4>), grid, blk, 0, st, a);
+}
+void launch_ct_lincomb_batch(CtLincombBatchArgs& a, u64* const* sets, int nbatch, hipStream_t st) {
+    const int lout = a.rescale_row ? a.Lc - 1 : a.Lc;
+    if (a.nin < 1 || a.nin > CTLM_MAX_IN || a.nout < 1 || a.nout > CTLM_MAX_OUT || a.npolys < 1 || a.npolys > 65535 || lout < 1 || (a.N & 1) || nbatch < 1)
+        throw std::runtime_error("mkhe: launch_ct_lincomb_batch: bad shape");
+    const int per = a.nin + a.nout, bx = ((a.N >> 1) + PW_THREADS - 1) / PW_THREADS;
+    // what one launch holds: the pointer list of its arguments, and the rows of a grid
+    const int cap = std::min(CTLB_MAX_PTRS / per, 65535 / a.npolys);
+    for (int first = 0; first < nbatch; first += cap) {
+        a.nbatch = std::min(cap, nbatch - first);
+        std::copy(sets + (size_t)first * per, sets + (size_t)(first + a.nbatch) * per, a.ptr);
+        // limb groups as in launch_ct_lincomb, over the threads of all items of the launch: until every SIMD of the chip has four waves
+        const long fill = 256L * 4 * 4 * 64, threads = (long)bx * PW_THREADS * a.npolys * a.nbatch;
+        const int groups = (int)std::min<long>(lout, (fill + threads - 1) / threads);
+        const dim3 grid(bx, a.npolys * a.nbatch, groups), blk(PW_THREADS);
+        if (a.nin > 8) launch_ctlb_no<16>(a, grid, blk, st);
+        else if (a.nin > 4) launch_ctlb_no<8>(a, grid, blk, st);
+        else launch_ctlb_no<4>(a, grid, blk, st);
+    }
 }
 __global__ void __launch_bounds__(PW_THREADS) mform_polys_kernel(u64* dst, const u64* src, const Mod* mods, int L, int N) {
     const int l = blockIdx.y;

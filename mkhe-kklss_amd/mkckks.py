@@ -353,25 +353,10 @@ class Evaluator:
         lower `level`: the summands' higher limbs are not read); scale defaults to params.Scale().  A weight that is exactly zero drops its ciphertext.
         The constants are encoded and uploaded here, once per call: not inside a graph capture."""
         params = self.params
-        cts, weights, const = list(cts), [complex(w) for w in weights], complex(const)
-        if not cts or len(cts) != len(weights):
-            raise MkheError("LinCombNew: one weight per ciphertext, at least one ciphertext")
-        if any(c.ids != cts[0].ids for c in cts):
-            raise MkheError("LinCombNew: the ciphertexts must carry the same ids")
-        lmin = min(c.Level() for c in cts)
-        l = lmin if level is None else int(level)
-        if l > lmin or l < 0:
-            raise MkheError("LinCombNew: the work level must lie between 0 and the lowest level of the ciphertexts")
-        if rescale and l < 1:
-            raise MkheError("cannot Rescale: input Ciphertext already at level 0")
-        scale = params.Scale() if scale is None else float(scale)
-        terms = [(c, w) for c, w in zip(cts, weights) if w != 0] or [(cts[0], 0j)]
-        if len(terms) > LINCOMB_MAX:
-            raise MkheError("LinCombNew: at most %d non-zero weights per call" % LINCOMB_MAX)
-        s_mid = scale * float(params.Q[l]) if rescale else scale
-        buf = _upload_consts(params, lincomb_consts(params.Q[: l + 1], s_mid, const, [c.Scale for c, _ in terms], [w for _, w in terms]))
-        out = NewCiphertext(params, cts[0].IDSet(), l - (1 if rescale else 0), scale, zero=False)
-        check(lib().mkhe_ct_lincomb(params.ctx, len(terms), handle_array([c.h for c, _ in terms]), buf.devptr(), 1 if rescale else 0, out.h))
+        terms, l, scale, block = _lincomb_plan(params, cts, weights, const, scale, rescale, level)
+        buf = _upload_consts(params, block)
+        out = NewCiphertext(params, terms[0].IDSet(), l - (1 if rescale else 0), scale, zero=False)
+        check(lib().mkhe_ct_lincomb(params.ctx, len(terms), handle_array([c.h for c in terms]), buf.devptr(), 1 if rescale else 0, out.h))
         return out
 
     def LinCombsNew(self, cts, weight_rows, consts, scales=None, rescale=True, level=None):
@@ -382,35 +367,10 @@ class Evaluator:
         `rescale`.  A ciphertext whose weight is zero in every row is dropped (at most 16 may remain); zeros inside the table stay, the kernel skips
         them.  MkheError before any engine call on a shape error.  Not inside a graph capture (the constants are uploaded here)."""
         params = self.params
-        cts, rows, consts = list(cts), [[complex(w) for w in r] for r in weight_rows], [complex(c) for c in consts]
-        if not cts:
-            raise MkheError("LinCombsNew: at least one ciphertext")
-        if not rows or len(rows) > LINCOMBS_MAX_OUT or len(rows) != len(consts):
-            raise MkheError("LinCombsNew: 1 to %d rows of weights per call, one constant per row" % LINCOMBS_MAX_OUT)
-        if any(len(r) != len(cts) for r in rows):
-            raise MkheError("LinCombsNew: one weight per ciphertext in every row")
-        if any(c.ids != cts[0].ids for c in cts):
-            raise MkheError("LinCombsNew: the ciphertexts must carry the same ids")
-        lmin = min(c.Level() for c in cts)
-        l = lmin if level is None else int(level)
-        if l > lmin or l < 0:
-            raise MkheError("LinCombsNew: the work level must lie between 0 and the lowest level of the ciphertexts")
-        if rescale and l < 1:
-            raise MkheError("cannot Rescale: input Ciphertext already at level 0")
-        if scales is None or np.ndim(scales) == 0:
-            scales = [params.Scale() if scales is None else float(scales)] * len(rows)
-        scales = [float(s) for s in scales]
-        if len(scales) != len(rows):
-            raise MkheError("LinCombsNew: one scale for all rows, or one per row")
-        keep = [b for b in range(len(cts)) if any(r[b] != 0 for r in rows)] or [0]
-        if len(keep) > LINCOMB_MAX:
-            raise MkheError("LinCombsNew: at most %d ciphertexts with a non-zero weight per call" % LINCOMB_MAX)
-        Q = params.Q[: l + 1]
-        block = np.stack([lincomb_consts(Q, s * float(params.Q[l]) if rescale else s, c, [cts[b].Scale for b in keep], [r[b] for b in keep])
-                          for r, c, s in zip(rows, consts, scales)])
+        terms, l, scales, block = _lincombs_plan(params, cts, weight_rows, consts, scales, rescale, level)
         buf = _upload_consts(params, block)
-        outs = [NewCiphertext(params, cts[0].IDSet(), l - (1 if rescale else 0), s, zero=False) for s in scales]
-        check(lib().mkhe_ct_lincomb_multi(params.ctx, len(keep), handle_array([cts[b].h for b in keep]), len(rows), buf.devptr(), 1 if rescale else 0,
+        outs = [NewCiphertext(params, terms[0].IDSet(), l - (1 if rescale else 0), s, zero=False) for s in scales]
+        check(lib().mkhe_ct_lincomb_multi(params.ctx, len(terms), handle_array([c.h for c in terms]), len(scales), buf.devptr(), 1 if rescale else 0,
                                           handle_array([o.h for o in outs])))
         return outs
 
@@ -511,6 +471,59 @@ def lincomb_consts(Q, s_mid, const, scales, weights):
             out[k + 1, 0, i] = ((scaleUpExact(w.real, ratio, q) % q) << 64) % q              # MForm
             out[k + 1, 1, i] = ((scaleUpExact(w.imag, ratio, q) % q) << 64) % q
     return out
+
+
+def _lincomb_plan(params, cts, weights, const, scale, rescale, level):
+    """the checks of LinCombNew and its constant block, before any engine call, on ciphertexts or batches of them (anything with ids, Level() and Scale)
+    -> (the summands whose weight is not zero, the work level, the declared scale, the block)"""
+    cts, weights, const = list(cts), [complex(w) for w in weights], complex(const)
+    if not cts or len(cts) != len(weights):
+        raise MkheError("LinCombNew: one weight per ciphertext, at least one ciphertext")
+    if any(c.ids != cts[0].ids for c in cts):
+        raise MkheError("LinCombNew: the ciphertexts must carry the same ids")
+    lmin = min(c.Level() for c in cts)
+    l = lmin if level is None else int(level)
+    if l > lmin or l < 0:
+        raise MkheError("LinCombNew: the work level must lie between 0 and the lowest level of the ciphertexts")
+    if rescale and l < 1:
+        raise MkheError("cannot Rescale: input Ciphertext already at level 0")
+    scale = params.Scale() if scale is None else float(scale)
+    terms = [(c, w) for c, w in zip(cts, weights) if w != 0] or [(cts[0], 0j)]
+    if len(terms) > LINCOMB_MAX:
+        raise MkheError("LinCombNew: at most %d non-zero weights per call" % LINCOMB_MAX)
+    s_mid = scale * float(params.Q[l]) if rescale else scale
+    return [c for c, _ in terms], l, scale, lincomb_consts(params.Q[: l + 1], s_mid, const, [c.Scale for c, _ in terms], [w for _, w in terms])
+
+
+def _lincombs_plan(params, cts, weight_rows, consts, scales, rescale, level):
+    """the same for LinCombsNew -> (the summands with a non-zero weight in some row, the work level, one declared scale per row, the block of all rows)"""
+    cts, rows, consts = list(cts), [[complex(w) for w in r] for r in weight_rows], [complex(c) for c in consts]
+    if not cts:
+        raise MkheError("LinCombsNew: at least one ciphertext")
+    if not rows or len(rows) > LINCOMBS_MAX_OUT or len(rows) != len(consts):
+        raise MkheError("LinCombsNew: 1 to %d rows of weights per call, one constant per row" % LINCOMBS_MAX_OUT)
+    if any(len(r) != len(cts) for r in rows):
+        raise MkheError("LinCombsNew: one weight per ciphertext in every row")
+    if any(c.ids != cts[0].ids for c in cts):
+        raise MkheError("LinCombsNew: the ciphertexts must carry the same ids")
+    lmin = min(c.Level() for c in cts)
+    l = lmin if level is None else int(level)
+    if l > lmin or l < 0:
+        raise MkheError("LinCombsNew: the work level must lie between 0 and the lowest level of the ciphertexts")
+    if rescale and l < 1:
+        raise MkheError("cannot Rescale: input Ciphertext already at level 0")
+    if scales is None or np.ndim(scales) == 0:
+        scales = [params.Scale() if scales is None else float(scales)] * len(rows)
+    scales = [float(s) for s in scales]
+    if len(scales) != len(rows):
+        raise MkheError("LinCombsNew: one scale for all rows, or one per row")
+    keep = [b for b in range(len(cts)) if any(r[b] != 0 for r in rows)] or [0]
+    if len(keep) > LINCOMB_MAX:
+        raise MkheError("LinCombsNew: at most %d ciphertexts with a non-zero weight per call" % LINCOMB_MAX)
+    Q = params.Q[: l + 1]
+    block = np.stack([lincomb_consts(Q, s * float(params.Q[l]) if rescale else s, c, [cts[b].Scale for b in keep], [r[b] for b in keep])
+                      for r, c, s in zip(rows, consts, scales)])
+    return [cts[b] for b in keep], l, scales, block
 
 
 def _upload_consts(params, block):
@@ -938,7 +951,11 @@ class Bootstrapper:
         """on a ciphertext whose slots are real and lie in (-1, 1), y = (m / ratio + I) / K with integers |I| <= K - 1: m in its slots (eval_mod_model).
         The series of eval_mod_coeffs on (-1, 1), then double_angle times LinCombNew([MulRelinRawNew(v, v)], [2], -1, ..), whose weight is the integer
         2; the factor ratio / (2 pi) is the declared Scale of the result.  ratio defaults to Q[0] / params.Scale().  ceil(log2(degree + 1)) + 1 +
-        double_angle levels."""
+        double_angle levels.  A BatchCiphertext goes through a BatchEvaluator of its length (ev, or a new one): every node is then one batched call."""
+        if isinstance(ct, BatchCiphertext):
+            ev = BatchEvaluator(self.params, len(ct)) if ev is None else ev
+            if not isinstance(ev, BatchEvaluator) or ev.B != len(ct):
+                raise MkheError("EvalModNew: a batch of %d ciphertexts needs a BatchEvaluator of that many inputs" % len(ct))
         ev = Evaluator(self.params) if ev is None else ev
         params = self.params
         ratio = float(params.Q[0]) / params.Scale() if ratio is None else float(ratio)
@@ -977,17 +994,22 @@ class Bootstrapper:
             ckSet.GetConjugationKey(i)
         return ratio
 
-    def BootstrapNew(self, ct, rlkSet, rkSet, ckSet, ev=None):
+    def BootstrapNew(self, ct, rlkSet, rkSet, ckSet, ev=None, pair=False):
         """ct at level 0 -> the same message under the same ids at level `level` - Depth() with Scale == params.Scale() exactly.  MkheError before any
         engine call when ct is not at level 0, Q[0] / ct.Scale < 2^8, or a key or CRS slot of Rotations(), a relinearisation or conjugation key or
-        CRS slot -1 / -2 is missing (logSlots > 10 and a chain shorter than Depth() + 1 are refused by the constructor)."""
+        CRS slot -1 / -2 is missing (logSlots > 10 and a chain shorter than Depth() + 1 are refused by the constructor).  pair=True: the two halves
+        go through EvalModNew once, as a batch of two on ev.Lanes(2), instead of one after the other -- the same ciphertext bit for bit."""
         ratio = self._refuse(ct, rlkSet, rkSet, ckSet)
         ev = Evaluator(self.params) if ev is None else ev
         raised = ev.ModRaiseNew(ct, self.level)
         sub = ev.SubSumNew(raised, rkSet)
         sub.Scale = sub.Scale * (self.K * ratio)                    # = Q[0] K gap: the slots of lo / hi are (m / ratio + I) / K
         lo, hi = self.CoeffsToSlotsNew(sub, rkSet, ckSet, ev)
-        return self.SlotsToCoeffsNew(self.EvalModNew(lo, rlkSet, ratio, ev), self.EvalModNew(hi, rlkSet, ratio, ev), rkSet, ev)
+        if pair:
+            lo, hi = self.EvalModNew(BatchCiphertext([lo, hi]), rlkSet, ratio, ev.Lanes(2)).cts
+        else:
+            lo, hi = self.EvalModNew(lo, rlkSet, ratio, ev), self.EvalModNew(hi, rlkSet, ratio, ev)
+        return self.SlotsToCoeffsNew(lo, hi, rkSet, ev)
 
 
 def NewEvaluator(params):
@@ -1004,8 +1026,18 @@ class BatchCiphertext:
         for c in self.cts:
             if c.ids != c0.ids or c.Level() != c0.Level() or c.Scale != c0.Scale:
                 raise MkheError("BatchCiphertext: the ciphertexts of a batch must have one shape and scale")
-        self.ids, self.Scale, self.params = c0.ids, c0.Scale, c0.params
+        self.ids, self._scale, self.params = c0.ids, c0.Scale, c0.params
         self._harr = handle_array([c.h for c in self.cts])          # (built once: every batched call passes it)
+
+    @property
+    def Scale(self): return self._scale
+
+    @Scale.setter
+    def Scale(self, scale):
+        """a declared scale is one number for the batch: every member takes it (evaluate_poly and Bootstrapper.EvalModNew assign it)"""
+        self._scale = scale
+        for c in self.cts:
+            c.Scale = scale
 
     def __len__(self): return len(self.cts)
     def IDSet(self): return set(self.ids)
@@ -1119,23 +1151,32 @@ class BatchEvaluator:
     def MulRelinNew(self, op0, op1, rlkSet):
         return self.MulRelinHoistedNew(op0, op1, None, None, rlkSet)
 
-    def MulRelinHoistedNew(self, op0, op1, op0Hoisted, op1Hoisted, rlkSet):
+    def _product(self, op0, op1, op0Hoisted, op1Hoisted, rlkSet, rescale):
+        """ONE mkhe_mul_relin_batch: the relinearised products at the level of the operands and the product of their scales, or (rescale) one level
+        below at that scale over the dropped modulus"""
         a, b = self._cts(op0), self._cts(op1)
         params = self.params
         level, prod_scale = min(a[0].Level(), b[0].Level()), a[0].ScalingFactor() * b[0].ScalingFactor()
         if -1 not in params.CRS:
             raise MkheError("mkhe: CRS[-1] (u) has not been uploaded")
-        nb1, scale1 = self.ev._nb_rescales(level, prod_scale, params.Scale())
-        # the single evaluator's branch (Evaluator.MulRelinHoistedNew): the Rescale is folded into the engine call only when it is the usual single
-        # one and fuse_rescale is set; otherwise the product is formed at its level and ONE mkhe_rescale(nb) per input follows, as there
-        rescale = nb1 == 1 and level >= 1 and self.ev.fuse_rescale
-        ids = a[0].IDSet() | b[0].IDSet()
-        out = self._new(ids, level - 1 if rescale else level, prod_scale / float(params.Q[level]) if rescale else prod_scale)
+        out = self._new(a[0].IDSet() | b[0].IDSet(), level - 1 if rescale else level, prod_scale / float(params.Q[level]) if rescale else prod_scale)
         d0 = [rlkSet.GetRelinearizationKey(i).Value[1].h for i in a[0].ids]
         v0 = [rlkSet.GetRelinearizationKey(i).Value[2].h for i in a[0].ids]
         b1 = [rlkSet.GetRelinearizationKey(i).Value[0].h for i in b[0].ids]
         check(lib().mkhe_mul_relin_batch(params.ctx, self.B, self._h(op0), self._h(op1), self._hoists(op0Hoisted, a), self._hoists(op1Hoisted, b),
                                          handle_array(b1), handle_array(d0), handle_array(v0), params.CRS[-1].h, 1 if rescale else 0, self._h(out)))
+        return out
+
+    def MulRelinHoistedNew(self, op0, op1, op0Hoisted, op1Hoisted, rlkSet):
+        a, b = self._cts(op0), self._cts(op1)
+        params = self.params
+        level, prod_scale = min(a[0].Level(), b[0].Level()), a[0].ScalingFactor() * b[0].ScalingFactor()
+        nb1, scale1 = self.ev._nb_rescales(level, prod_scale, params.Scale())
+        # the single evaluator's branch (Evaluator.MulRelinHoistedNew): the Rescale is folded into the engine call only when it is the usual single
+        # one and fuse_rescale is set; otherwise the product is formed at its level and ONE mkhe_rescale(nb) per input follows, as there
+        rescale = nb1 == 1 and level >= 1 and self.ev.fuse_rescale
+        ids = a[0].IDSet() | b[0].IDSet()
+        out = self._product(op0, op1, op0Hoisted, op1Hoisted, rlkSet, rescale)
         if rescale:
             return out
         nb, scale = self.ev.nbRescales(out.cts[0], params.Scale())
@@ -1145,6 +1186,62 @@ class BatchEvaluator:
         for c, r in zip(out.cts, res.cts):              # (nb != 1 or fuse_rescale off: not in the circuits of the reference -- per input)
             check(lib().mkhe_rescale(params.ctx, c.h, nb, r.h))
         return res
+
+    def MulRelinRawNew(self, op0, op1, rlkSet):
+        """Evaluator.MulRelinRawNew on the batch: the products at level min(levels) with Scale = the product of the scales, no Rescale"""
+        return self._product(op0, op1, None, None, rlkSet, False)
+
+    def MulRelinOnceNew(self, op0, op1, rlkSet, scale=None):
+        """Evaluator.MulRelinOnceNew on the batch: the batch MulRelinNew where that takes the usual MulRelinNew, otherwise the product with exactly ONE
+        Rescale folded into the engine call; the declared scales are those of Evaluator"""
+        a, b = self._cts(op0), self._cts(op1)
+        level, prod = min(a[0].Level(), b[0].Level()), a[0].ScalingFactor() * b[0].ScalingFactor()
+        if level < 1:
+            raise MkheError("cannot Rescale: input Ciphertext already at level 0")
+        if self.ev._nb_rescales(level, prod, self.params.Scale())[0] == 1:
+            res = self.MulRelinNew(op0, op1, rlkSet)
+        else:
+            res = self._product(op0, op1, None, None, rlkSet, True)
+        if scale is not None:
+            res.Scale = float(scale)
+        return res
+
+    # -- weighted sums and polynomials (Evaluator.LinCombNew .. EvaluateChebyshevNew; no reference counterpart)
+    def _lincomb_call(self, terms, block, l, scales, rescale):
+        """ONE constants upload and ONE mkhe_ct_lincomb_batch: row g of `block` over `terms` (batches, or plain ciphertexts that every item shares) -> one batch per row"""
+        params, B = self.params, self.B
+        for c in terms:
+            if isinstance(c, BatchCiphertext) and len(c) != B:
+                raise MkheError("BatchEvaluator: a batch of %d ciphertexts on an evaluator of %d inputs" % (len(c), B))
+        buf = _upload_consts(params, block)
+        outs = [self._new(terms[0].IDSet(), l - (1 if rescale else 0), s) for s in scales]
+        members = [self._cts(c) for c in terms]
+        check(lib().mkhe_ct_lincomb_batch(params.ctx, B, len(terms), handle_array([m[b].h for b in range(B) for m in members]), len(outs), buf.devptr(),
+                                          1 if rescale else 0, handle_array([o.cts[b].h for b in range(B) for o in outs])))
+        return outs
+
+    def LinCombNew(self, cts, weights, const=0, scale=None, rescale=True, level=None):
+        """Evaluator.LinCombNew on every input of the batch (same arguments, defaults, rules and refusals): the one-row case of LinCombsNew"""
+        terms, l, scale, block = _lincomb_plan(self.params, cts, weights, const, scale, rescale, level)
+        return self._lincomb_call(terms, block[None], l, [scale], rescale)[0]
+
+    def LinCombsNew(self, cts, weight_rows, consts, scales=None, rescale=True, level=None):
+        """Evaluator.LinCombsNew on every input of the batch (same arguments, defaults, rules and refusals); cts are BatchCiphertexts, or plain Ciphertexts
+        that every input shares.  The inputs of a batch carry one scale, so ONE constant block serves them all: one upload and ONE engine call
+        (mkhe_ct_lincomb_batch) whatever B.  MkheError before any engine call on a shape error, a batch whose length is not B included."""
+        terms, l, scales, block = _lincombs_plan(self.params, cts, weight_rows, consts, scales, rescale, level)
+        return self._lincomb_call(terms, block, l, scales, rescale)
+
+    def AddConstNew(self, ct, c):
+        return self.LinCombNew([ct], [1], c, scale=ct.Scale, rescale=False)
+
+    def EvaluatePolyNew(self, ct, coeffs, rlkSet, scale=None, fused=False):
+        """Evaluator.EvaluatePolyNew on every input of the batch: the same schedule, every node one batched engine call"""
+        return evaluate_poly(self, ct, coeffs, rlkSet, scale, fused)
+
+    def EvaluateChebyshevNew(self, ct, coeffs, interval, rlkSet, scale=None, fused=True):
+        """Evaluator.EvaluateChebyshevNew on every input of the batch: the same schedule, every node one batched engine call"""
+        return evaluate_chebyshev(self, ct, coeffs, interval, rlkSet, scale, fused)
 
     # -- RotateNew / RotateHoistedNew (evaluator.go:485-525,585-617)
     def _rotate(self, ct, rotidx, hoisted, rkSet):

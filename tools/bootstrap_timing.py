@@ -3,6 +3,7 @@ ratio = 2^10), uniform material -- the times do not depend on the values:
   modraise       mkhe_ct_mod_raise of a level-0 ciphertext to the top, 2 and 4 parties, against its byte count 8 N (1 + k) (1 + L)
   boot-S-k       one BootstrapNew at logSlots = S with k parties, from level 0 to level 33 - 12; stages timed apart in the same run: ModRaise + SubSum,
                  CoeffsToSlots, the two EvalMod, SlotsToCoeffs
+  pair-S-k       BootstrapNew(pair=True), the two halves through EvalMod as a batch of two, against BootstrapNew(pair=False), alternating in one process
 Every party's rotation keys are ONE uniform switching key shared by all its rotation indices (83 indices at logSlots = 10 would otherwise be 28 GB
 per party); the CRS slots are expanded on the device.  The transforms are encoded in the warm-ups and are not part of the times.
 HIP events on mkhe_ctx_stream around each call, REPS repetitions after WARM warm-ups; a call's time includes the host's constant uploads between
@@ -24,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 WARM = 2
-LEGS = {"modraise": 120, "boot-4-2": 240, "boot-4-4": 300, "boot-10-2": 400, "boot-10-4": 400}      # leg -> its time limit in seconds
+LEGS = {"modraise": 120, "boot-4-2": 240, "boot-4-4": 300, "boot-10-2": 400, "boot-10-4": 400, "pair-4-2": 300}      # leg -> its time limit in seconds
 
 
 def hip_runtime(lib):
@@ -108,15 +109,27 @@ def run_leg(leg, reps):
             assert out.Level() == params.MaxLevel() - boot.Depth()
             return t0, t1, t2, t3
 
-        whole = lambda: boot.BootstrapNew(ct, rlk, rks, cks, ev)
-        for _ in range(WARM):
-            timed(stream, whole)
-            staged()
-        total = stat([timed(stream, whole)[0] for _ in range(reps)])
-        parts = np.array([staged() for _ in range(reps)])
-        rows.append(dict(leg=leg, ring="PN16QP1761", logSlots=logSlots, parties=k, level_in=params.MaxLevel(), level_out=params.MaxLevel() - boot.Depth(),
-                         rotations=len(boot.Rotations()), reps=reps, bootstrap=total,
-                         stages={name: stat(parts[:, i]) for i, name in enumerate(["modraise_subsum", "coeffs_to_slots", "eval_mod_x2", "slots_to_coeffs"])}))
+        common = dict(leg=leg, ring="PN16QP1761", logSlots=logSlots, parties=k, level_in=params.MaxLevel(), level_out=params.MaxLevel() - boot.Depth(), reps=reps)
+        if leg.startswith("pair"):
+            legs = {name: (lambda p=p: boot.BootstrapNew(ct, rlk, rks, cks, ev, pair=p)) for name, p in (("pair", True), ("default", False))}
+            for _ in range(WARM):
+                for f in legs.values():
+                    timed(stream, f)
+            t = {name: [] for name in legs}
+            for _ in range(reps):
+                for name, f in legs.items():
+                    t[name].append(timed(stream, f)[0])
+            t = {name: stat(v) for name, v in t.items()}
+            rows.append(dict(common, pair=t["pair"], default=t["default"], ratio=round(t["pair"]["median_us"] / t["default"]["median_us"], 3)))
+        else:
+            whole = lambda: boot.BootstrapNew(ct, rlk, rks, cks, ev)
+            for _ in range(WARM):
+                timed(stream, whole)
+                staged()
+            total = stat([timed(stream, whole)[0] for _ in range(reps)])
+            parts = np.array([staged() for _ in range(reps)])
+            rows.append(dict(common, rotations=len(boot.Rotations()), bootstrap=total,
+                             stages={name: stat(parts[:, i]) for i, name in enumerate(["modraise_subsum", "coeffs_to_slots", "eval_mod_x2", "slots_to_coeffs"])}))
         print(json.dumps(rows[-1]), flush=True)
         params.close()
     for e in (e0, e1):

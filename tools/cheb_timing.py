@@ -6,11 +6,15 @@ uniform material:
                             upload of the constants
   kernel                    mkhe_ct_lincomb_multi(nin, nout) against nout x mkhe_ct_lincomb(nin), constants resident, real weights (a Chebyshev
                             series) and complex ones, with the fused rescale, at (nin, nout) = (7, 7) and (15, 15) and at 6 and 14 limbs
-The two legs of a row give the same bits; nothing is compared here: tests/test_gpu_lincomb_multi.py and tests/test_gpu_chebyshev_e2e.py pin that.
+  batch_kernel              mkhe_ct_lincomb_batch on nbatch = 2 and 8 items against nbatch calls of mkhe_ct_lincomb_multi, constants resident, real
+                            weights, with the fused rescale, at (nin, nout) = (7, 7) and (15, 15) and 6 limbs
+  batch_cheb31              BatchEvaluator.EvaluateChebyshevNew of degree 31 on B = 2 and 8 inputs against B evaluations on the single Evaluator
+The two legs of a row give the same bits; nothing is compared here: tests/test_gpu_lincomb_multi.py, tests/test_gpu_chebyshev_e2e.py,
+tests/test_gpu_lincomb_batch.py and tests/test_gpu_batch_polyeval.py pin that.
 HIP events on mkhe_ctx_stream around each leg, the legs alternating, REPS repetitions each after WARM warm-ups.  Every leg runs in a process of its
 own under its own `timeout`; the first failure stops the script.  Writes one JSON object (times in microseconds: median, min, quartiles; launch and
 byte counts as derived in DESIGN.md) to --out and prints it.
-Needs a GPU:  python tools/cheb_timing.py [--out FILE] [--reps N]"""
+Needs a GPU:  python tools/cheb_timing.py [--out FILE] [--reps N] [--legs a,b]"""
 import argparse
 import ctypes as C
 import json
@@ -25,7 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 WARM = 3
-LEGS = {"cheb15": 300, "cheb63": 300, "cheb255": 400, "kernel": 300}             # leg -> its time limit in seconds
+LEGS = {"cheb15": 300, "cheb63": 300, "cheb255": 400, "kernel": 300, "batch_kernel": 300, "batch_cheb31": 400}             # leg -> its time limit in seconds
 IDS = ["p0", "p1", "p2", "p3"]
 INTERVAL = (-8.0, 8.0)
 
@@ -81,13 +85,25 @@ def run_leg(leg, reps):
 
     poly = 8.0 * N * (1 + len(IDS))                               # bytes of one limb of a ciphertext
     rows = []
-    if leg.startswith("cheb"):
-        degree = int(leg[4:])
+    if leg.startswith("cheb") or leg == "batch_cheb31":
         swk = lambda: np.stack([H.uniform_poly(rng, Q + P, N) for _ in range(len(Q))])        # (alpha = 1: one digit per limb of Q)
         rlk = mkrlwe.RelinearizationKeySet(params)
         for n in IDS:
             rlk.AddRelinearizationKey(mkrlwe.RelinearizationKey(params, n, swk(), swk(), swk()))
         params.AddCRS(-1, swk())
+    if leg == "batch_cheb31":
+        degree = 31
+        coeffs = rng.uniform(-1, 1, degree + 1)
+        for B in (2, 8):
+            x = mkckks.BatchCiphertext([ct(len(Q)) for _ in range(B)])
+            bev = mkckks.BatchEvaluator(params, B, ev=ev)
+            batch, single = alternate(lambda: bev.EvaluateChebyshevNew(x, coeffs, INTERVAL, rlk),
+                                      lambda: [ev.EvaluateChebyshevNew(c, coeffs, INTERVAL, rlk) for c in x.cts])
+            rows.append(dict(leg=leg, ring="PN15QP880", parties=len(IDS), degree=degree, interval=INTERVAL, B=B, reps=reps, batch=batch, per_item=single,
+                             ratio=round(batch["median_us"] / single["median_us"], 3)))
+            print(json.dumps(rows[-1]), flush=True)
+    elif leg.startswith("cheb"):
+        degree = int(leg[4:])
         x = ct(len(Q))
         coeffs = rng.uniform(-1, 1, degree + 1)
         plan = mkckks.poly_eval_plan(degree)
@@ -102,6 +118,34 @@ def run_leg(leg, reps):
                          sum_bytes_fused=poly * (nin * Lc + (g - 1) * (Lc - 1)), sum_bytes_plain=poly * (g - 1) * (nin * Lc + Lc - 1),
                          saved_us=round(plain["median_us"] - fused["median_us"], 1), ratio=round(fused["median_us"] / plain["median_us"], 3)))
         print(json.dumps(rows[-1]), flush=True)
+    elif leg == "batch_kernel":
+        L, Lc = lib(), 6
+        ins = [[ct(Lc) for _ in range(15)] for _ in range(8)]
+        outs = [[mkckks.NewCiphertext(params, IDS, Lc - 2, pset["scale"]) for _ in range(15)] for _ in range(8)]
+        for nin, nout in ((7, 7), (15, 15)):
+            res = lambda: [int(rng.integers(1, q)) for q in Q[:Lc]]
+            block = np.array([[[res(), res()]] + [[res(), [0] * Lc] for _ in range(nin)] for _ in range(nout)], dtype=np.uint64)
+            buf = mkckks._upload_consts(params, block)
+            for nbatch in (2, 8):
+                hin = [handle_array([c.h for c in ins[b][:nin]]) for b in range(nbatch)]
+                hout = [handle_array([c.h for c in outs[b][:nout]]) for b in range(nbatch)]
+                hin_all = handle_array([c.h for b in range(nbatch) for c in ins[b][:nin]])
+                hout_all = handle_array([c.h for b in range(nbatch) for c in outs[b][:nout]])
+
+                def lock_step():
+                    check(L.mkhe_ct_lincomb_batch(params.ctx, nbatch, nin, hin_all, nout, buf.devptr(), 1, hout_all))
+
+                def per_item():
+                    for b in range(nbatch):
+                        check(L.mkhe_ct_lincomb_multi(params.ctx, nin, hin[b], nout, buf.devptr(), 1, hout[b]))
+
+                one, many = alternate(lock_step, per_item)
+                nbytes = poly * nbatch * (nin * Lc + nout * (Lc - 1))
+                rows.append(dict(leg=leg, ring="PN15QP880", parties=len(IDS), nbatch=nbatch, nin=nin, nout=nout, limbs=Lc, nb_rescale=1, weights="real",
+                                 reps=reps, batch=one, per_item=many, launches=dict(batch=1, per_item=nbatch), bytes=nbytes,
+                                 gbps=dict(batch=round(nbytes / one["median_us"] / 1e3, 1), per_item=round(nbytes / many["median_us"] / 1e3, 1)),
+                                 ratio=round(one["median_us"] / many["median_us"], 3)))
+                print(json.dumps(rows[-1]), flush=True)
     else:
         L = lib()
         for Lc in (6, 14):
@@ -142,6 +186,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cheb_timing.json"))
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated subset of " + ", ".join(LEGS))
     ap.add_argument("--leg", choices=sorted(LEGS), help="run this leg in this process and print its rows (what the script starts for every leg)")
     args = ap.parse_args()
     if args.reps < 10:
@@ -150,7 +195,7 @@ def main():
         print("ROWS " + json.dumps(run_leg(args.leg, args.reps)), flush=True)
         return
     rows = []
-    for leg, limit in LEGS.items():               # a fresh process per leg, each under its own time limit; the first failure ends the script
+    for leg, limit in ((leg, LEGS[leg]) for leg in args.legs.split(",")):               # a fresh process per leg, each under its own time limit; the first failure ends the script
         out = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--reps", str(args.reps)],
                              capture_output=True, text=True)
         sys.stdout.write(out.stdout)
@@ -165,7 +210,9 @@ def main():
     names = sorted({line.split(":", 1)[1].strip() for line in device.splitlines() if "Marketing Name" in line and "Instinct" in line})
     res = dict(device=names, host=os.uname().nodename,
                legs=dict(fused="EvaluateChebyshevNew(fused=True)", plain="EvaluateChebyshevNew(fused=False)",
-                         one_launch="mkhe_ct_lincomb_multi(nin, nout)", per_output="nout x mkhe_ct_lincomb(nin)"), rows=rows)
+                         one_launch="mkhe_ct_lincomb_multi(nin, nout)", per_output="nout x mkhe_ct_lincomb(nin)",
+                         batch="mkhe_ct_lincomb_batch(nbatch, nin, nout) / BatchEvaluator.EvaluateChebyshevNew on B inputs",
+                         per_item="nbatch x mkhe_ct_lincomb_multi(nin, nout) / B x Evaluator.EvaluateChebyshevNew"), rows=rows)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
