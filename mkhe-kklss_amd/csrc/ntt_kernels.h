@@ -66,7 +66,9 @@ struct NttBatch {
     int src_mapped, dst_mapped;
     int reduce_in;          // forward only: input is a digit spread under a foreign modulus (Decompose)
     int reduce_src_mod_is_outer;   // the digit's own modulus index: 1 = outer (alpha = 1), 2 = outer_mod[outer] (BFV digits of R)
-    int src_lazy;           // digit values are lazy base-conversion outputs (< 4 * own modulus) rather than canonical
+    int src_lazy;           // digit values are lazy base-conversion outputs rather than canonical: accepted below 4 * own modulus (the bound of
+                            // the alpha >= 2 digit spread); the BFV conversions stay below 3 (multSum of <= 16 terms below 2^60: DESIGN.md 3.1b,
+                            // 2.52 the largest planted), and 3 q - 1 everywhere is pinned by tests/test_gpu_bfv_conv_edges.py
     int lazy_out;           // inverse only: leave [0,2q) (InvNTTLazy)
     int skip_norm;          // forward, moduli with 34q < 2^63 only: leave the un-normalised values (< 34q, same residues) --
                             // for engine-internal outputs whose only consumers are Montgomery products (hoisted digits)

@@ -10,7 +10,6 @@ moddown_literal() is the reference's ModDownQPtoQ for one coefficient on oracle/
 moddown_with_index() restates the same arithmetic around a pluggable index (the mutants of tests/test_steer_model.py)."""
 import functools
 import random
-from fractions import Fraction
 
 import numpy as np
 
@@ -54,8 +53,16 @@ def index_literal(y, P):
     return int(vi)
 
 
+@functools.lru_cache(maxsize=None)
+def _cofactors(P):
+    Pp = prod(P)
+    return Pp, tuple(Pp // p for p in P)
+
+
 def index_exact(y, P):
-    return int(sum(Fraction(v, p) for v, p in zip(y, P)))
+    """floor(sum_i y_i / p_i), over the common denominator prod(P)"""
+    Pp, co = _cofactors(tuple(int(p) for p in P))
+    return sum(int(v) * c for v, c in zip(y, co)) // Pp
 
 
 def index_reciprocal(y, P):
@@ -134,30 +141,50 @@ def quotient_edge(p):
     return y + 1, y
 
 
-def boundary_tuples(mods, seed=0, count=16):
+def boundary_tuples(mods, seed=0, count=16, wide=False, under=0, max_tries=None):
     """{"below": [...], "above": [...], "above_hi": [...]} of tuples y over mods (the special primes, or the moduli of a gadget digit):
     below   : exact sum just below an integer k in 1..n-1, float index k      (the float index is one above the true floor)
     above   : exact sum just above k - 1 for the same k, float index k - 1
     above_hi: exact sum just above k, float index k                            (half as many: where a rounded-down quotient would lose the step)
     rounding: see below
+    under   : (only when under > 0) exact sum just above k, float index k - 1  (the float index is one BELOW the true floor: a sum of many terms
+              whose roundings went down; two or four special primes do not have it)
     The y of an integer X under M = prod(mods) sum to exactly k +- e/M for X = M - e and X = e (CRT), so small e are the values next to an
     integer; every other draw takes e between M * 2^-55 and M * 2^-52, the scale of one float64 rounding of the sum, where the order and the form of
     the operations start to decide.
+    wide: those draws reach further, up to M * n * ulp(n) -- n roundings of a sum near n, each as large as half an ulp of that sum -- with the
+    exponent drawn uniformly, so that a sum of sixteen terms near 8 (ulp 2^-49) is still met inside its own rounding error.
+    max_tries: None -- a family the search cannot fill is an error (today's callers: two and four special primes); a number -- each of the two
+    searches stops there and every family holds what was found, possibly nothing: the caller decides what it requires.
     Searched, never tabulated: a candidate is kept only if its float index and its exact floor are the intended ones."""
     n = len(mods)
     rnd = random.Random(1000003 * seed + n)
     out = {"below": [], "above": [], "above_hi": []}
+    if under:
+        out["under"] = []
     if n < 2:
         return out
     Mp = prod(mods)
     per_k = -(-count // (n - 1))
     want = {"below": count, "above": count, "above_hi": count // 2}
+    if under:
+        want["under"] = under
     seen = {kind: {} for kind in out}
+    top = (8 * n << (n.bit_length() - 1)).bit_length() if wide else 0       # e / (M 2^-55) below 2^top: 8 n ulp(n) / 2^-52
+
+    def rounding_scale():
+        if not wide:
+            return max(1, (Mp >> 55) * rnd.randrange(1, 9) + rnd.randrange(0, 1 << 16))
+        b = rnd.randrange(0, top)
+        return max(1, (Mp >> 55) * rnd.randrange(1 << b, 2 << b) + rnd.randrange(0, 1 << 16))
+
     tries = 0
     while any(len(out[kind]) < want[kind] for kind in out):
         tries += 1
+        if max_tries is not None and tries > max_tries:
+            break
         assert tries < 200000, "the search for boundary tuples found too few under these moduli"
-        e = rnd.randrange(1, 1 << 16) if tries & 1 else max(1, (Mp >> 55) * rnd.randrange(1, 9) + rnd.randrange(0, 1 << 16))
+        e = rnd.randrange(1, 1 << 16) if tries & 1 else rounding_scale()
         for kind, X in (("below", Mp - e), ("above", e)):
             y = y_of([X % m for m in mods], mods)
             fl, lit = index_exact(y, mods), index_literal(y, mods)
@@ -165,6 +192,10 @@ def boundary_tuples(mods, seed=0, count=16):
                 k, ok = fl + 1, lit == fl + 1
             else:
                 k, ok = fl + 1, lit == fl
+                if under and lit == fl - 1 and len(out["under"]) < want["under"] and seen["under"].get(fl, 0) < per_k:
+                    seen["under"][fl] = seen["under"].get(fl, 0) + 1
+                    out["under"].append(y)
+                    continue
                 if ok and fl >= 1 and len(out["above_hi"]) < want["above_hi"] and seen["above_hi"].get(fl, 0) < per_k:
                     seen["above_hi"][fl] = seen["above_hi"].get(fl, 0) + 1
                     out["above_hi"].append(y)
@@ -186,8 +217,10 @@ def boundary_tuples(mods, seed=0, count=16):
     tries = 0
     while min(got.values()) < count // 4:
         tries += 1
+        if max_tries is not None and tries > max_tries:
+            break
         assert tries < 400000, "the search for rounding-scale tuples found too few under these moduli"
-        e = max(1, (Mp >> 55) * rnd.randrange(1, 9) + rnd.randrange(0, 1 << 16))
+        e = rounding_scale()
         for X in (Mp - e, e):
             y = y_of([X % m for m in mods], mods)
             lit = index_literal(y, mods)
@@ -198,12 +231,13 @@ def boundary_tuples(mods, seed=0, count=16):
     return out
 
 
-def patterns(P, seed=0):
-    return list(_patterns(tuple(int(p) for p in P), seed))
+def patterns(P, seed=0, **search):
+    """search: keywords of boundary_tuples (none: today's families and today's requirement that each be filled)"""
+    return list(_patterns(tuple(int(p) for p in P), seed, tuple(sorted(search.items()))))
 
 
 @functools.lru_cache(maxsize=None)
-def _patterns(P, seed):
+def _patterns(P, seed, search=()):
     """[(name, y tuple)]: the planted [T]_P of one parameter set, as reconstruction terms y"""
     n = len(P)
     pats = [("y=0", [0] * n), ("x_P=1", y_of([1] * n, P)), ("y=p-1 all", [p - 1 for p in P])]
@@ -213,7 +247,7 @@ def _patterns(P, seed):
         one, below = quotient_edge(p)
         pats.append(("y_%d last quotient 1.0" % i, [one if k == i else 0 for k in range(n)]))
         pats.append(("y_%d first quotient <1" % i, [below if k == i else 0 for k in range(n)]))
-    for kind, ts in boundary_tuples(list(P), seed).items():
+    for kind, ts in boundary_tuples(list(P), seed, **dict(search)).items():
         for t in ts:
             pats.append((kind, t))
     return pats

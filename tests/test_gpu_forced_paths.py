@@ -193,6 +193,11 @@ for conv, ora in ((ev.conv.ModUpQtoR, bfv.modup_q_to_r), (ev.conv.Rescale, bfv.r
     got = dst.download()
     for c in range(6):
         assert (got[c] == bfv.ntt_r(ref[c])).all(), c
+# the same transform at the bound of its lazy inputs: every coefficient 3 m_j - 1 under every modulus m_j of R
+edge = np.stack([np.full(N, 3 * m - 1, dtype=np.uint64) for m in pset["Q"] + pset["QMul"]])
+dst = mkbfv.PolyR(params, 1).upload(edge[None])
+check(lib().mkhe_bfv_ntt_r(params.ctx, dst.devptr(), dst.devptr(), 1, 0))
+assert (dst.download()[0] == bfv.ntt_r(edge)).all()
 names = ["a", "b"]
 h0, h1 = H.uniform_ct(rng, bfv.ks, 2, nq), H.uniform_ct(rng, bfv.ks, 2, nq)
 c0, c1 = mkbfv.NewCiphertext(params, names).upload(h0), mkbfv.NewCiphertext(params, names).upload(h1)
