@@ -424,6 +424,12 @@ class Evaluator:
         through the single-operation entry points (it needs LinearTransform(.., keep_coeff=True)) and gives the same ciphertext bit for bit."""
         return linear_transform(self, ct, lt, rkSet, fused)
 
+    def FactoredTransformNew(self, ct, ft, rkSet, fused=True):
+        """F_f .. F_1 z for the factors of `ft` (FactoredTransform): LinearTransformNew on each factor in turn, ft.Depth() levels; the result is at level
+        ft.level - ft.Depth() and at Scale ft.out_scale exactly when ct.Scale == ft.in_scale.  MkheError before any engine call when a CRS / rotation key
+        of ft.Rotations() is missing; fused as in LinearTransformNew."""
+        return factored_transform(self, ct, ft, rkSet, fused)
+
     # ---- the two ciphertext steps that open a bootstrapping (no reference counterpart; Bootstrapper below composes the rest)
     def ModRaiseNew(self, ct, level=None):
         """the level-0 ciphertext ct, read as its centred representatives mod Q[0], at `level` (default: the top) as ONE engine call (mkhe_ct_mod_raise).
@@ -698,19 +704,27 @@ PTXT_DOT_MAX_IN, PTXT_DOT_MAX_GIANT = 16, 64          # csrc/poly_kernels.h, CTD
 LinTransPlan = collections.namedtuple("LinTransPlan", "n1 babies giants")
 
 
-def linear_transform_plan(indices, n, n1=None):
+def linear_transform_plan(indices, n, n1=None, stride=1):
     """Baby steps and giant steps for the diagonal indices `indices` (taken mod n, the number of slots), a pure function: k = b + g with b = k mod n1 and g = k - b.
     -> (n1, sorted babies, sorted giants).  n1 is a power of two <= 16; the default minimises the number of rotations (non-zero babies + non-zero
-    giants), ties to the smaller n1.  MkheError when the diagonals need more than 64 giants."""
-    n = int(n)
+    giants), ties to the smaller n1.  MkheError when the diagonals need more than 64 giants.
+    stride = s > 1 is for diagonals that all lie at multiples of s (a factor of a factored transform): with k = s u, b = s (u mod n1) and g = k - b, so
+    the babies are s, 2 s, .. instead of all collapsing onto baby 0.  The stride is declared, never guessed from the indices; an index that is no
+    multiple of it is refused."""
+    n, s = int(n), int(stride)
     idx = sorted({int(k) % n for k in indices})
     if not idx:
         raise MkheError("linear_transform_plan: no diagonal")
     if n1 is not None and (int(n1) != n1 or n1 < 1 or n1 > PTXT_DOT_MAX_IN or n1 & (n1 - 1)):
         raise MkheError("linear_transform_plan: n1 must be a power of two, at most %d" % PTXT_DOT_MAX_IN)
+    if s != stride or s < 1:
+        raise MkheError("linear_transform_plan: the stride must be a positive integer")
+    off = [k for k in idx if k % s]
+    if off:
+        raise MkheError("linear_transform_plan: diagonal %d is no multiple of the stride %d" % (off[0], s))
     best = None
     for m in ([int(n1)] if n1 is not None else [1, 2, 4, 8, 16]):
-        babies, giants = sorted({k % m for k in idx}), sorted({k - k % m for k in idx})
+        babies, giants = sorted({k % (s * m) for k in idx}), sorted({k - k % (s * m) for k in idx})
         cost = sum(1 for b in babies if b) + sum(1 for g in giants if g)
         if len(giants) <= PTXT_DOT_MAX_GIANT and (best is None or cost < best[0]):
             best = (cost, LinTransPlan(m, babies, giants))
@@ -725,9 +739,9 @@ class LinearTransform:
     M z = sum_g rot_g(sum_b d'_(g,b) (.) rot_b z).  All of them are encoded on the device in ONE EncodeBatch at `level` and at the scale
     pt_scale = out_scale * Q[level] / in_scale (both default to params.Scale()), then prepared in ONE mkhe_ptxt_prepare into a compact block in (g, b)
     order: no plaintext transform is left for the evaluation.  keep_coeff=True also keeps the coefficient-domain plaintexts (LinearTransformNew(..,
-    fused=False))."""
+    fused=False)).  stride: the declared common divisor of the indices (linear_transform_plan)."""
 
-    def __init__(self, params, diagonals, level, in_scale=None, out_scale=None, n1=None, keep_coeff=False):
+    def __init__(self, params, diagonals, level, in_scale=None, out_scale=None, n1=None, keep_coeff=False, stride=1):
         n = 1 << params.LogSlots()
         level = int(level)
         if level < 0 or level > params.MaxLevel():
@@ -741,7 +755,7 @@ class LinearTransform:
                 raise MkheError("LinearTransform: diagonal %d is given twice (indices are taken mod %d)" % (k, n))
             diag[int(k) % n] = d
         self.params, self.level, self.n = params, level, n
-        self.plan = linear_transform_plan(diag, n, n1)
+        self.plan = linear_transform_plan(diag, n, n1, stride)
         self.in_scale = params.Scale() if in_scale is None else float(in_scale)
         self.out_scale = params.Scale() if out_scale is None else float(out_scale)
         self.pt_scale = self.out_scale * float(params.Q[level]) / self.in_scale
@@ -850,8 +864,119 @@ def linear_transform(ev, ct, lt, rkSet, fused=True):
     return out
 
 
-# ---- bootstrapping for 2^logSlots <= 1024 slots (no reference counterpart; DESIGN.md, "Bootstrapping"): ModRaise, SubSum, CoeffsToSlots, EvalMod, SlotsToCoeffs
-BOOTSTRAP_MAX_LOG_SLOTS = 10      # one LinearTransform holds 16 x 64 diagonals (PTXT_DOT_MAX_IN x PTXT_DOT_MAX_GIANT)
+class FactoredTransform:
+    """A product of sparse factors, M = F_f .. F_2 F_1 with `factors` = [F_1, .. F_f] in the order they are applied, each a dict of diagonals in the
+    convention of LinearTransform: one LinearTransform per factor at the levels level, level - 1, .., each with its own stride (`strides`, default 1
+    throughout).  The class knows nothing about what the factors are; dft_factors gives those of the slot matrix C0.
+    Scales.  Factor t (t = 0 .. f - 1) takes its input at s_t and leaves it at s_(t+1), with s_0 = in_scale, s_f = out_scale (both default to
+    params.Scale()) and s_t = in_scale (out_scale / in_scale)^(t / f) in between: every factor's plaintexts are then encoded at Q[level - t] times the
+    same ratio (out_scale / in_scale)^(1 / f), and a ciphertext that enters at in_scale leaves at out_scale exactly.  A pure power of two common to a
+    factor's entries (the 2^-g of an inverse butterfly) is better put into a declared scale by the caller than into these plaintexts."""
+
+    def __init__(self, params, factors, level, in_scale=None, out_scale=None, strides=None, keep_coeff=False):
+        factors = [dict(F) for F in factors]
+        f, level = len(factors), int(level)
+        if not f:
+            raise MkheError("FactoredTransform: no factor")
+        strides = [1] * f if strides is None else [int(s) for s in strides]
+        if len(strides) != f:
+            raise MkheError("FactoredTransform: %d strides for %d factors" % (len(strides), f))
+        if level - (f - 1) < 0 or level > params.MaxLevel():
+            raise MkheError("FactoredTransform: %d factors from level %d need the levels %d .. %d of 0 .. %d" % (f, level, level, level - f + 1, params.MaxLevel()))
+        self.params, self.level = params, level
+        self.in_scale = params.Scale() if in_scale is None else float(in_scale)
+        self.out_scale = params.Scale() if out_scale is None else float(out_scale)
+        self.scales = [self.in_scale] + [self.in_scale * (self.out_scale / self.in_scale) ** (t / f) for t in range(1, f)] + [self.out_scale]
+        self.transforms = [LinearTransform(params, F, level - t, in_scale=self.scales[t], out_scale=self.scales[t + 1], stride=s, keep_coeff=keep_coeff)
+                           for t, (F, s) in enumerate(zip(factors, strides))]
+
+    def Rotations(self):
+        """the union of the factors' Rotations()"""
+        return sorted({r for lt in self.transforms for r in lt.Rotations()})
+
+    def Depth(self):
+        """one level per factor"""
+        return len(self.transforms)
+
+
+def factored_transform(ev, ct, ft, rkSet, fused=True):
+    """Evaluator.FactoredTransformNew: linear_transform on each factor in turn; every key of ft.Rotations() is looked up before the first engine call"""
+    if ft.params is not ev.params:
+        raise MkheError("FactoredTransformNew: the transform was encoded for other parameters")
+    mkrlwe.rotation_keys(ev.params, rkSet, ct.ids, ft.Rotations(), "FactoredTransformNew")
+    for lt in ft.transforms:
+        ct = linear_transform(ev, ct, lt, rkSet, fused)
+    return ct
+
+
+def _dft_stage(n, l, inverse):
+    """the diagonals {k mod n: d_k} of the radix-2 stage S_l over n slots (dft_factors), or of its inverse"""
+    h, p = l // 2, np.arange(n) % l
+    low = p < h
+    e, acc = [], 1
+    for _ in range(h):
+        e.append(acc)
+        acc = acc * 5 % (4 * l)
+    om = np.exp(2j * np.pi * np.array(e)[p % h] / (4 * l))
+    if inverse:
+        parts = [(0, np.where(low, 0.5, -0.5 / om)), (h, np.where(low, 0.5, 0)), (-h, np.where(low, 0, 0.5 / om))]
+    else:
+        parts = [(0, np.where(low, 1, -om)), (h, np.where(low, om, 0)), (-h, np.where(low, 0, 1))]
+    out = {}
+    for k, d in parts:
+        out[k % n] = out.get(k % n, 0) + d.astype(np.complex128)
+    return out
+
+
+def _diag_product(A, B, n):
+    """the diagonals of A B: (A B z)[j] = sum_a A_a[j] sum_b B_b[j + a] z[j + a + b]"""
+    out = {}
+    for a, da in A.items():
+        for b, db in B.items():
+            k = (a + b) % n
+            out[k] = out.get(k, 0) + da * np.roll(db, -a)
+    return out
+
+
+def dft_groups(logSlots, groups, who="dft_factors"):
+    """(strides, index sets) of the factors of dft_factors(logSlots, groups), without their entries: stride_t = 2^(g_1 + .. + g_(t-1)), the indices of F_t are
+    the multiples u stride_t with |u| < 2^g_t, taken mod n.  MkheError for a group below 1 or a sum other than logSlots."""
+    groups = [int(g) for g in groups]
+    if int(logSlots) < 1 or not groups or min(groups) < 1 or sum(groups) != int(logSlots):
+        raise MkheError("%s: the groups %r must be positive and sum to logSlots = %d >= 1" % (who, tuple(groups), logSlots))
+    n, strides = 1 << int(logSlots), [1 << sum(groups[:t]) for t in range(len(groups))]
+    return strides, [sorted({u * s % n for u in range(-(1 << g) + 1, 1 << g)}) for g, s in zip(groups, strides)]
+
+
+def dft_factors(logSlots, groups, inverse=False):
+    """The slot matrix C0 of bootstrap_matrices as a product of sparse factors, pure numpy.  n = 2^logSlots.  The radix-2 stage S_l, l = 2, 4, .. n, acts on
+    every block of l entries: out[i + j] = in[i + j] + w in[i + j + l/2], out[i + j + l/2] = in[i + j] - w in[i + j + l/2] for j < l / 2 with
+    w = exp(2 pi i (5^j mod 4l) / 4l); C0 = S_n .. S_4 S_2 R with (R a)[i] = a[bitrev(i)].  groups = (g_1, .. g_f), positive, summing to logSlots: F_t is
+    the product of the next g_t stages in ascending l (F_1 holds S_2), so C0 = F_f .. F_1 R.
+    -> (factors, strides): factors[t] = {k: d_k} of F_(t+1) in the convention of LinearTransform, indices in [0, n), all-zero diagonals left out;
+    strides[t] = 2^(g_1 + .. + g_t) divides every index of it.  A factor has 2^(g+1) - 1 diagonals (the last 2^g: +k and -k meet mod n) with entries of
+    modulus 1 or 0.  inverse=True: the F_t^-1 in the same list order, on the negated indices, entries of modulus 2^-g_t or 0."""
+    strides, _ = dft_groups(logSlots, groups)
+    n, factors, l = 1 << int(logSlots), [], 2
+    for g in groups:
+        acc = None
+        for _ in range(int(g)):
+            S = _dft_stage(n, l, inverse)
+            acc = S if acc is None else (_diag_product(acc, S, n) if inverse else _diag_product(S, acc, n))
+            l *= 2
+        factors.append({k: d for k, d in sorted(acc.items()) if d.any()})
+    return factors, strides
+
+
+def bit_reverse(n):
+    """the permutation i -> bitrev(i) over log2(n) bits, as an index array: a[bit_reverse(n)] is R a"""
+    bits = int(n).bit_length() - 1
+    return np.array([int(format(i, "0%db" % bits)[::-1], 2) if bits else 0 for i in range(n)], dtype=np.int64)
+
+
+# ---- bootstrapping (no reference counterpart; DESIGN.md, "Bootstrapping"): ModRaise, SubSum, CoeffsToSlots, EvalMod, SlotsToCoeffs; dense transforms for
+# 2^logSlots <= 1024 slots, factored ones (dft_factors above) for any number
+BOOTSTRAP_MAX_LOG_SLOTS = 10      # without `factors`: one LinearTransform holds 16 x 64 diagonals (PTXT_DOT_MAX_IN x PTXT_DOT_MAX_GIANT)
 BOOTSTRAP_MIN_RATIO = 2.0 ** 8    # Q[0] / scale: below it the sine's cubic term, (2 pi / ratio)^2 / 6, costs more than 2^-11.6
 
 
@@ -897,14 +1022,31 @@ class Bootstrapper:
     the split into real and imaginary part onto params.Scale() (1); EvaluateChebyshevNew on (-1, 1) (ceil(log2(degree + 1)) + 1); double_angle
     steps of 2 v^2 - 1 (1 each); SlotsToCoeffs (1).  The constants cost no level: 1 / gap and 1 / (K ratio) are the declared scale Q[0] K gap of the
     ciphertext that enters CoeffsToSlots, ratio / (2 pi) is the declared scale of the one that leaves EvalMod.  The transforms are encoded on the device
-    at their first use, for the input scale they meet; another input scale re-encodes them."""
+    at their first use, for the input scale they meet; another input scale re-encodes them.
 
-    def __init__(self, params, K=16, double_angle=3, degree=31, level=None):
+    factors=(c2s_groups, s2c_groups), two tuples of positive integers that each sum to logSlots, replaces each dense transform by the sparse factors of
+    dft_factors (any logSlots >= 1, past 1024 slots too) at one level per factor: Depth() = 10 + len(c2s_groups) + len(s2c_groups) at the defaults.
+    CoeffsToSlots applies F_f^-1 first and F_1^-1 last, which leaves the grid coefficients in BIT-REVERSED slot order (C0^-1 = R F_1^-1 .. F_f^-1 and R is
+    never applied); EvalMod is slot-wise; SlotsToCoeffs applies F_1 .. F_f to lo + i hi, and C0 = F_f .. F_1 R undoes the order.  The inverse factors
+    are encoded with their entries times 2^g_t (modulus 1), and the 1 / n that is left goes into the declared scale.  factors=None is the dense
+    object in every respect."""
+
+    def __init__(self, params, K=16, double_angle=3, degree=31, level=None, factors=None):
         self.params, self.K, self.double_angle, self.degree = params, int(K), int(double_angle), int(degree)
         self.level = params.MaxLevel() if level is None else int(level)
         self.n = 1 << params.LogSlots()
         self.gap = params.N() // (2 * self.n)
-        if params.LogSlots() > BOOTSTRAP_MAX_LOG_SLOTS:
+        self.groups = None
+        if factors is not None:
+            if len(factors) != 2:
+                raise MkheError("Bootstrapper: factors is (c2s_groups, s2c_groups), two tuples of group sizes")
+            c2s, s2c = factors
+            self.groups = (tuple(int(g) for g in c2s), tuple(int(g) for g in s2c))
+            # [which] -> (strides, index sets) in the order the factors are APPLIED: F_f^-1 .. F_1^-1 (on the negated = the same index sets), then F_1 .. F_f
+            shape = [dft_groups(params.LogSlots(), g, "Bootstrapper") for g in self.groups]
+            self._shape = [(shape[0][0][::-1], shape[0][1][::-1]), shape[1]]
+            self.plans = [[linear_transform_plan(idx, self.n, stride=s) for s, idx in zip(*sh)] for sh in self._shape]
+        elif params.LogSlots() > BOOTSTRAP_MAX_LOG_SLOTS:
             raise MkheError("Bootstrapper: logSlots = %d, at most %d (one transform holds %d x %d diagonals)"
                             % (params.LogSlots(), BOOTSTRAP_MAX_LOG_SLOTS, PTXT_DOT_MAX_IN, PTXT_DOT_MAX_GIANT))
         if self.K < 1 or self.double_angle < 0 or not 1 <= self.degree <= CHEBYSHEV_MAX_DEGREE:
@@ -913,38 +1055,62 @@ class Bootstrapper:
             raise MkheError("Bootstrapper: the chain must hold Depth() + 1 = %d moduli up to `level`, level = %d of %d"
                             % (self.Depth() + 1, self.level, params.MaxLevel()))
         self.coeffs = eval_mod_coeffs(self.K, self.double_angle, self.degree)
-        self.plan = linear_transform_plan(range(self.n), self.n)
+        if self.groups is None:
+            self.plan = linear_transform_plan(range(self.n), self.n)
         self._lts = {}
 
+    def _depths(self):
+        """(levels of CoeffsToSlots without the split, levels of SlotsToCoeffs): one per factor, 1 for a dense transform"""
+        return (1, 1) if self.groups is None else (len(self.groups[0]), len(self.groups[1]))
+
     def Depth(self):
-        """levels between the raised ciphertext and the result: 1 + 1 + (ceil(log2(degree + 1)) + 1) + double_angle + 1"""
-        return 2 + self.degree.bit_length() + 1 + self.double_angle + 1
+        """levels between the raised ciphertext and the result: 1 + 1 + (ceil(log2(degree + 1)) + 1) + double_angle + 1; with `factors`, one per factor in
+        place of the 1 of each transform"""
+        return self._depths()[0] + 1 + self.degree.bit_length() + 1 + self.double_angle + self._depths()[1]
 
     def Rotations(self):
         """every index a party must hold a CRS slot and a rotation key for: n, 2n, .. N / 4 (SubSum: powers of two, so GenDefaultCRS and
         GenDefaultRotationKeys cover them) and the baby and giant steps of the two transforms"""
         sub = [self.n << i for i in range(self.gap.bit_length() - 1)]
-        return sorted(set(sub) | {r for r in self.plan.babies + self.plan.giants if r})
+        plans = [self.plan] if self.groups is None else self.plans[0] + self.plans[1]
+        return sorted(set(sub) | {r for p in plans for r in p.babies + p.giants if r})
 
     def _transform(self, which, in_scale, out_scale):
         """the transform `which` (0: M1 at `level`; 1: C0 at level - Depth() + 1) for ciphertexts at in_scale, encoded once per (in_scale, out_scale)"""
         hit = self._lts.get(which)
         if hit is None or hit.in_scale != in_scale or hit.out_scale != out_scale:
-            M1, _, C0, _ = bootstrap_matrices(self.params)
-            level = self.level if which == 0 else self.level - self.Depth() + 1
-            hit = self._lts[which] = LinearTransform.FromMatrix(self.params, M1 if which == 0 else C0, level, in_scale=in_scale, out_scale=out_scale)
+            level = self.level if which == 0 else self.level - self.Depth() + self._depths()[1]
+            if self.groups is None:
+                M1, _, C0, _ = bootstrap_matrices(self.params)
+                hit = LinearTransform.FromMatrix(self.params, M1 if which == 0 else C0, level, in_scale=in_scale, out_scale=out_scale)
+            else:
+                groups = self.groups[which]
+                factors, _ = dft_factors(self.params.LogSlots(), groups, inverse=which == 0)
+                if which == 0:              # 2^g_t F_t^-1, entries of modulus 1, last factor first; the caller declares the 1 / n
+                    factors = [{k: d * 2.0 ** g for k, d in F.items()} for F, g in zip(factors, groups)][::-1]
+                hit = FactoredTransform(self.params, factors, level, in_scale=in_scale, out_scale=out_scale, strides=self._shape[which][0])
+            self._lts[which] = hit
         return hit
+
+    def _apply(self, ev, ct, tr, rkSet):
+        return ev.LinearTransformNew(ct, tr, rkSet) if self.groups is None else ev.FactoredTransformNew(ct, tr, rkSet)
 
     def CoeffsToSlotsNew(self, ct, rkSet, ckSet, ev=None):
         """(lo, hi): for the plaintext polynomial of ct with the 2n grid coefficients a (over ct.Scale), the slots of lo are a[:n] and those of hi are
         a[n:], real.  One transform w = M1 z, then lo = (w + conj w) / 2 and hi = (w - conj w) / 2i by one ConjugateNew and one LinCombsNew.  ct at
         `level` or above (LinearTransformNew drops a higher one to the transform's level first, and refuses a lower one); the halves are at level - 2 with Scale == params.Scale() exactly: the transform leaves at S Q[level - 1] / 2^B, B >= 1 chosen
-        so that its plaintexts are encoded at about Q[level], and the weights 1/2 of the split are then the integers 2^(B - 1)."""
+        so that its plaintexts are encoded at about Q[level], and the weights 1/2 of the split are then the integers 2^(B - 1).
+        With `factors` the slots come in BIT-REVERSED order: slot i of lo is a[bitrev(i)], slot i of hi is a[n + bitrev(i)] (bitrev over logSlots
+        bits); the f factors take the levels level .. level - f + 1 and the halves are at level - f - 1.  The factors are encoded with entries of
+        modulus 1, n C0^-1 in all, at about Q[their level]: their product leaves at S Q[level - f] / (2^B n), which is then declared as
+        S Q[level - f] / 2^B, an exact division by n."""
         ev = Evaluator(self.params) if ev is None else ev
         params, S = self.params, self.params.Scale()
-        top = S * float(params.Q[self.level - 1])
-        B = max(1, int(round(math.log2(top / ct.Scale))))
-        w = ev.LinearTransformNew(ct, self._transform(0, ct.Scale, top / 2.0 ** B), rkSet)
+        top = S * float(params.Q[self.level - self._depths()[0]])
+        norm = 1 if self.groups is None else self.n
+        B = max(1, int(round(math.log2(top / (ct.Scale * norm)))))
+        w = self._apply(ev, ct, self._transform(0, ct.Scale, top / 2.0 ** B / norm), rkSet)
+        w.Scale = w.Scale * norm
         return ev.LinCombsNew([w, ev.ConjugateNew(w, ckSet)], [[0.5, 0.5], [-0.5j, 0.5j]], [0, 0], scales=S, rescale=True)
 
     def EvalModNew(self, ct, rlkSet, ratio=None, ev=None):
@@ -970,12 +1136,13 @@ class Bootstrapper:
     def SlotsToCoeffsNew(self, ct_lo, ct_hi, rkSet, ev=None):
         """the ciphertext whose plaintext has the grid coefficients (slots of ct_lo, slots of ct_hi), both real: z = C0 (lo + i hi), C1 being i C0 -- one
         LinCombNew without rescale (the weights 1 and i are exact) and one transform.  Both halves carry one Scale; the result is at level - Depth()
-        with Scale == params.Scale() exactly."""
+        with Scale == params.Scale() exactly.  With `factors` the halves are taken in the BIT-REVERSED slot order in which CoeffsToSlotsNew leaves them
+        (slot i of ct_lo is a[bitrev(i)], slot i of ct_hi is a[n + bitrev(i)]), and F_1 .. F_f are applied at one level each: z = F_f .. F_1 R w = C0 w."""
         ev = Evaluator(self.params) if ev is None else ev
         if ct_lo.Scale != ct_hi.Scale:
             raise MkheError("SlotsToCoeffsNew: the two halves must carry one scale")
         w = ev.LinCombNew([ct_lo, ct_hi], [1, 1j], 0, scale=ct_lo.Scale, rescale=False)
-        return ev.LinearTransformNew(w, self._transform(1, w.Scale, self.params.Scale()), rkSet)
+        return self._apply(ev, w, self._transform(1, w.Scale, self.params.Scale()), rkSet)
 
     def _refuse(self, ct, rlkSet, rkSet, ckSet):
         """every refusal of BootstrapNew that depends on the call: no engine call is made here"""
@@ -997,7 +1164,7 @@ class Bootstrapper:
     def BootstrapNew(self, ct, rlkSet, rkSet, ckSet, ev=None, pair=False):
         """ct at level 0 -> the same message under the same ids at level `level` - Depth() with Scale == params.Scale() exactly.  MkheError before any
         engine call when ct is not at level 0, Q[0] / ct.Scale < 2^8, or a key or CRS slot of Rotations(), a relinearisation or conjugation key or
-        CRS slot -1 / -2 is missing (logSlots > 10 and a chain shorter than Depth() + 1 are refused by the constructor).  pair=True: the two halves
+        CRS slot -1 / -2 is missing (logSlots > 10 without `factors`, bad groups and a chain shorter than Depth() + 1 are refused by the constructor).  pair=True: the two halves
         go through EvalModNew once, as a batch of two on ev.Lanes(2), instead of one after the other -- the same ciphertext bit for bit."""
         ratio = self._refuse(ct, rlkSet, rkSet, ckSet)
         ev = Evaluator(self.params) if ev is None else ev

@@ -1,8 +1,9 @@
 """Device time of mkckks.Bootstrapper.BootstrapNew and of mkhe_ct_mod_raise alone ("Bootstrapping"), on PN16QP1761 (N = 2^16, 34 moduli of Q,
 ratio = 2^10), uniform material -- the times do not depend on the values:
   modraise       mkhe_ct_mod_raise of a level-0 ciphertext to the top, 2 and 4 parties, against its byte count 8 N (1 + k) (1 + L)
-  boot-S-k       one BootstrapNew at logSlots = S with k parties, from level 0 to level 33 - 12; stages timed apart in the same run: ModRaise + SubSum,
-                 CoeffsToSlots, the two EvalMod, SlotsToCoeffs
+  boot-S-k       one BootstrapNew at logSlots = S with k parties, from level 0 to level 33 - Depth(); stages timed apart in the same run: ModRaise +
+                 SubSum, CoeffsToSlots, the two EvalMod, SlotsToCoeffs
+  boot-S-k@A/B   the same with Bootstrapper(.., factors=(A, B)), the groups of each transform joined by dots: boot-10-2@5.5/5.5, boot-15-2@5.5.5/5.5.5
   pair-S-k       BootstrapNew(pair=True), the two halves through EvalMod as a batch of two, against BootstrapNew(pair=False), alternating in one process
 Every party's rotation keys are ONE uniform switching key shared by all its rotation indices (83 indices at logSlots = 10 would otherwise be 28 GB
 per party); the CRS slots are expanded on the device.  The transforms are encoded in the warm-ups and are not part of the times.
@@ -26,6 +27,26 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 WARM = 2
 LEGS = {"modraise": 120, "boot-4-2": 240, "boot-4-4": 300, "boot-10-2": 400, "boot-10-4": 400, "pair-4-2": 300}      # leg -> its time limit in seconds
+FACTORED = {"boot-10-2": 300, "boot-15-2": 400}          # legs that only exist with @A/B (more than 1024 slots), and the limit of a factored leg
+
+
+def split_leg(leg):
+    """'boot-10-2@5.5/5.5' -> ('boot-10-2', ((5, 5), (5, 5))); a leg without '@' -> (leg, None)"""
+    base, _, spec = leg.partition("@")
+    if not spec:
+        return base, None
+    groups = tuple(tuple(int(g) for g in part.split(".")) for part in spec.split("/"))
+    if len(groups) != 2 or not base.startswith("boot-"):
+        raise SystemExit("factors go on a boot-S-k leg as @A/B, as in boot-10-2@5.5/5.5: %r" % leg)
+    return base, groups
+
+
+def time_limit(leg):
+    base, groups = split_leg(leg)
+    table = LEGS if groups is None else dict(LEGS, **FACTORED)
+    if base not in table:
+        raise SystemExit("unknown leg %r" % leg)
+    return table[base]
 
 
 def hip_runtime(lib):
@@ -82,11 +103,12 @@ def run_leg(leg, reps):
             print(json.dumps(rows[-1]), flush=True)
         params.close()
     else:
-        logSlots, k = (int(v) for v in leg.split("-")[1:])
+        base, factors = split_leg(leg)
+        logSlots, k = (int(v) for v in base.split("-")[1:])
         ids = ["p%d" % i for i in range(k)]
         params = mkckks.Parameters(pset["logN"], Q, P, pset["scale"], logSlots=logSlots)
         stream = C.c_void_p(params.stream())
-        boot = mkckks.Bootstrapper(params)
+        boot = mkckks.Bootstrapper(params, factors=factors)
         for idx in [-1, -2] + boot.Rotations():
             params.AddCRS(idx, seed=16)
         swk = lambda: np.stack([H.uniform_poly(rng, Q + P, N) for _ in range(params.Beta(params.MaxLevel()))])
@@ -128,7 +150,13 @@ def run_leg(leg, reps):
                 staged()
             total = stat([timed(stream, whole)[0] for _ in range(reps)])
             parts = np.array([staged() for _ in range(reps)])
-            rows.append(dict(common, rotations=len(boot.Rotations()), bootstrap=total,
+            lts = [t.transforms if factors else [t] for t in (boot._lts[0], boot._lts[1])]          # encoded in the warm-ups
+            plans = [[lt.plan for lt in group] for group in lts]
+            shape = dict(factors=factors, depth=boot.Depth(),
+                         diagonals=[[len(lt.order) for lt in group] for group in lts],
+                         key_switches=[sum(1 for p in group for r in p.babies + p.giants if r) for group in plans],
+                         plaintext_bytes=[sum(8 * N * (lt.level + 1) * len(lt.order) for lt in group) for group in lts])
+            rows.append(dict(common, **shape, rotations=len(boot.Rotations()), bootstrap=total,
                              stages={name: stat(parts[:, i]) for i, name in enumerate(["modraise_subsum", "coeffs_to_slots", "eval_mod_x2", "slots_to_coeffs"])}))
         print(json.dumps(rows[-1]), flush=True)
         params.close()
@@ -142,16 +170,18 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bootstrap_timing.json"))
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated subset of " + ", ".join(LEGS))
-    ap.add_argument("--leg", choices=sorted(LEGS), help="run this leg in this process and print its rows (what the script starts for every leg)")
+    ap.add_argument("--leg", help="run this leg in this process and print its rows (what the script starts for every leg)")
     args = ap.parse_args()
     if args.reps < 5:
         raise SystemExit("at least 5 repetitions")
+    for leg in [args.leg] if args.leg else args.legs.split(","):
+        time_limit(leg)
     if args.leg:
         print("ROWS " + json.dumps(run_leg(args.leg, args.reps)), flush=True)
         return
     rows, failed = [], None
     for leg in args.legs.split(","):              # a fresh process per leg, each under its own time limit; the first failure ends the measurements
-        out = subprocess.run(["timeout", "-k", "10", str(LEGS[leg]), sys.executable, os.path.abspath(__file__), "--leg", leg, "--reps", str(args.reps)],
+        out = subprocess.run(["timeout", "-k", "10", str(time_limit(leg)), sys.executable, os.path.abspath(__file__), "--leg", leg, "--reps", str(args.reps)],
                              capture_output=True, text=True)
         sys.stdout.write(out.stdout)
         if out.returncode != 0:
